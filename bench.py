@@ -11,6 +11,13 @@ back on the host.  Binned inputs and the restart tables are uploaded / drawn bef
 With N > 1 every rank processes its own batch of the stream (weak scaling, no data-path collective);
 value = UTRs all ranks processed / max-over-ranks time.
 
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the
+per-kernel HIP-event times of the timed steps).  `--full` adds everything else the bench measures: the
+re_run_mode leg, the roofline step, the CPU port baseline with its parity sample, the other BASELINE
+shapes, the single-chunk / CLI / end-to-end legs and, with N > 1, the multi-GPU end-to-end leg.
+`--dump-outputs DIR` writes what the last timed step returned (per-UTR fits, per-read labels) as
+DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
+
 Launch: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` every rank reads
 RANK / LOCAL_RANK / WORLD_SIZE from the environment.  Started plainly with `--gpus N` (N > 1, no WORLD_SIZE)
 this process starts the N ranks itself as fresh child processes BEFORE touching the GPU, runs the multi-GPU
@@ -65,7 +72,57 @@ def parse():
                          "names: more work per worker without writing more synthetic input)")
     ap.add_argument("--e2e-workers", type=int, default=0, help="prep processes of the end-to-end leg (0 = auto)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU work for the baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (re_run_mode, roofline, CPU baseline, other configs, "
+                         "single-chunk / CLI / end-to-end legs); the --no-* and --e2e-* options apply to them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64 / float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 << 20        # --dump-outputs: cap on all ranks' files together
+
+
+def dump_outputs(root, preps, res, rank, world):
+    """What Engine.process returned for the batch, one array per field: per-UTR K, alpha / beta (the grid values of
+    the chosen components), ws, bic, lb_arr, lb_len and n_jobs (rows padded with 0.0 beyond K / K + 1 / lb_len, so
+    every value is finite), and the label of every read (labels_bin mapped through the UTR's read -> bin index).  Reads beyond this rank's share of DUMP_BYTES are
+    represented by a fixed, seeded sample (labels_read_index.npy holds the global read index of each kept label)."""
+    out_dir = root if rank == 0 else os.path.join(root, f"rank{rank}")
+    os.makedirs(out_dir, exist_ok=True)
+    U = len(res)
+    kmax = max(1, max(f.K for f, _, _ in res))
+    nlb = max(1, max(len(f.lb) for f, _, _ in res))
+    K = np.zeros(U)
+    alpha = np.zeros((U, kmax))
+    beta = np.zeros((U, kmax))
+    ws = np.zeros((U, kmax + 1))
+    bic = np.zeros(U)
+    lb = np.zeros((U, nlb))
+    lb_len = np.zeros(U)
+    n_jobs = np.zeros(U)
+    labels = []
+    for u, (f, lab_bin, nj) in enumerate(res):
+        q = preps[u]
+        K[u], bic[u], n_jobs[u] = f.K, f.bic, nj
+        alpha[u, :f.K] = q.theta[f.a_idx]
+        beta[u, :f.K] = q.betas[f.b_idx]
+        ws[u, :f.K + 1] = f.ws
+        lb[u, :len(f.lb)], lb_len[u] = f.lb, len(f.lb)
+        labels.append(np.asarray(lab_bin)[q.idx])
+    labels = np.concatenate(labels).astype(np.float32)
+    arrays = dict(K=K, alpha=alpha, beta=beta, ws=ws, bic=bic, lb=lb, lb_len=lb_len, n_jobs=n_jobs, labels=labels)
+    budget = DUMP_BYTES // world - sum(a.nbytes for k, a in arrays.items() if k != "labels") - (1 << 20)
+    if labels.nbytes > budget:
+        keep = max(1, budget // 12)          # float32 label + float64 index per kept read
+        sel = np.sort(np.random.default_rng(20250225).choice(len(labels), size=keep, replace=False))
+        arrays["labels"] = labels[sel]
+        arrays["labels_read_index"] = sel.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(preps, plan, target_s, cores, max_utrs=None):
@@ -432,7 +489,7 @@ def launch_ranks(args):
     import socket
     import subprocess
     pool = None
-    if args.e2e_multi_utrs > 0:
+    if args.full and args.e2e_multi_utrs > 0:
         from scape_amd.pipeline import shared_pool
         pool = shared_pool(args.e2e_workers or None)
     with socket.socket() as sk:
@@ -476,7 +533,8 @@ def main():
     child = os.environ.get("SCAPE_BENCH_CHILD") == "1"       # ranks started by launch_ranks: the parent runs the e2e legs
     dist = None
     pool = None
-    want_e2e = (world == 1 and args.e2e_utrs > 0) or (world > 1 and rank == 0 and not child and args.e2e_multi_utrs > 0)
+    want_e2e = args.full and ((world == 1 and args.e2e_utrs > 0) or
+                              (world > 1 and rank == 0 and not child and args.e2e_multi_utrs > 0))
     if want_e2e:
         # the end-to-end legs' prep workers (and the fork server the multi-GPU workers come from): started before
         # this process touches the GPU, idle until then
@@ -531,9 +589,9 @@ def main():
     eng = Engine(device=dev)
     lib, h = eng.ctx.lib, eng.ctx.h
 
-    def measure(U, reads, kcap, steps, warmup, index0, base_seed, rerun_leg=True):
+    def measure(U, reads, kcap, steps, warmup, index0, base_seed, rerun_leg=True, roofline_leg=True):
         """One workload shape: U synthetic UTRs x `reads` reads resident in HBM, K = 1..kcap x 10 restarts; `steps` timed
-        passes of the hot path, then one extra sweep with an event pair around every per-round kernel (roofline)."""
+        passes of the hot path, then (roofline_leg) one extra sweep with an event pair around every per-round kernel."""
         kw = dict(n_max_apa=kcap, n_min_apa=1)
         t_prep = time.perf_counter()
         preps = []
@@ -567,17 +625,23 @@ def main():
         rounds, slab, zel = eng.last_main_counters
         em_avg_ms = em_ms[0] / steps
         host_ms = dict(eng.last_host_ms)
+        N = np.array([q.N for q in preps])
+        T = np.array([q.T for q in preps])
+        m = dict(preps=preps, plan=plan, res=res, batch=batch, elapsed=elapsed, kern=kern, host_ms=host_ms, rr=None,
+                 roofline=None, t_prep=t_prep, t_h2d=t_h2d, n_frag_mean=float(N.mean()), n_frag_max=int(N.max()),
+                 n_theta_mean=float(T.mean()), value=world * U * steps / elapsed, ms_per_step=1e3 * elapsed / steps)
 
         # the same timed region with re_run_mode on (the reference's default): UTRs whose K hits the cap
         # get a second, larger sweep through the generic state machine
-        rr = None
         if rerun_leg:
             rr_steps = max(1, min(steps, 2))
             rr_elapsed, _ = timed(lambda: eng.process(batch, preps, plan, re_run_mode=True), rr_steps)
-            rr = {"value": world * U * rr_steps / rr_elapsed, "unit": "UTRs/s", "steps": rr_steps,
-                  "ms_per_step": 1e3 * rr_elapsed / rr_steps,
-                  "note": "same resident batch and timed region with the re-run rule of subsample_run "
-                          "(apa_core.py:1023-1030) on"}
+            m["rr"] = {"value": world * U * rr_steps / rr_elapsed, "unit": "UTRs/s", "steps": rr_steps,
+                       "ms_per_step": 1e3 * rr_elapsed / rr_steps,
+                       "note": "same resident batch and timed region with the re-run rule of subsample_run "
+                               "(apa_core.py:1023-1030) on"}
+        if not roofline_leg:
+            return m
 
         # one extra, untimed step with an event pair around every per-round kernel: average duration of the
         # dominant kernel (the M-step, one launch per EM round) measured live on the launch stream, and the
@@ -601,8 +665,6 @@ def main():
         hbm_bytes = (traffic["tensor_bytes"] + traffic["v_bytes_unique"]) / max(m_n, 1)
         achieved = hbm_bytes / (m_avg_ms * 1e-3) / 1e9
         tensor_bytes = 8.0 * sum(q.T * len(q.betas) * ((q.N + 15) // 16 * 16) for q in preps)
-        N = np.array([q.N for q in preps])
-        T = np.array([q.T for q in preps])
         roofline = {"bound": "hbm", "kernel": "k3_mstep (tile-stationary f64-MFMA M-step on LDS-DMA rings, one launch per EM round)",
                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                     "traffic": hbm_bytes,
@@ -621,13 +683,15 @@ def main():
                             "per round for all jobs that need it: reuse_factor = algorithmic / traffic",
                     "em_sweep_ms": em_avg_ms, "em_rounds_per_sweep": int(rounds),
                     "mfma_f64_tflops": 2.0 * slab / (m_ms * 1e-3) / 1e12}
-        return dict(preps=preps, plan=plan, res=res, batch=batch, elapsed=elapsed, kern=kern, host_ms=host_ms, rr=rr,
-                    roofline=roofline, t_prep=t_prep, t_h2d=t_h2d, n_frag_mean=float(N.mean()), n_frag_max=int(N.max()),
-                    n_theta_mean=float(T.mean()), value=world * U * steps / elapsed, ms_per_step=1e3 * elapsed / steps)
+        m["roofline"] = roofline
+        return m
 
     U = args.utrs
-    m = measure(U, args.reads, args.kcap, args.steps, args.warmup, rank * U, args.base_seed)
+    m = measure(U, args.reads, args.kcap, args.steps, args.warmup, rank * U, args.base_seed,
+                rerun_leg=args.full, roofline_leg=args.full)
     preps, plan, res, batch = m["preps"], m["plan"], m["res"], m["batch"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, preps, res, rank, world)
 
     if rank == 0:
         out = {
@@ -642,12 +706,13 @@ def main():
                        "em_jobs_per_step": int(len(plan["main"])), "n_frag_mean": m["n_frag_mean"],
                        "n_frag_max": m["n_frag_max"], "n_theta_mean": m["n_theta_mean"], "re_run_mode": False,
                        "rng_mode": "per_utr", "parallelism": f"utr-shard x{world}"},
-            "roofline": m["roofline"],
             "kernels_ms": m["kern"],
-            "re_run_mode_true": m["rr"],
             "host": {"prep_s": m["t_prep"], "h2d_s": m["t_h2d"], "process_ms": m["host_ms"], **host_info()},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"] = m["roofline"]
+            out["re_run_mode_true"] = m["rr"]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             hi = host_info()
             cores = hi["physical_cores"]
             if hi["cgroup_cpu_limit"]:
@@ -660,7 +725,7 @@ def main():
             out["cpu_baseline"]["gpu_over_cpu_single_thread"] = out["value"] / cb["single_thread_value"]
             out["cpu_baseline"].update(hi)
     batch.free()
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         # The other single-GPU BASELINE shapes, two steps each through the same timed region: config #2 (1k x 500 reads,
         # K <= 5), and - one GPU's share of - config #4 (10k reads, K <= 10) and config #5 (5k reads, K = 1..12)
         oc = []
