@@ -166,6 +166,40 @@ int scape_hip_em_counters(scape_hip_ctx *ctx, int64_t *rounds, int64_t *slab_ele
 int scape_hip_em_traffic(scape_hip_ctx *ctx, int64_t *mstep_tensor_bytes, int64_t *mstep_v_bytes_requested,
                          int64_t *mstep_v_bytes_unique, int64_t *mstep_launches);
 
+/* ---- reporting stages after merge_pa (report.inc) ---------------------------------------------------------------
+ * ex_pa_cnt_mat (reference utils.py:438-553) and cal_exp_pa_len (utils.py:319-427, apa_core.py:1038-1063).  A batch is
+ * n_rec records; record r owns reads [read_off[r], read_off[r+1]) of label / cb_id and has K[r] pA sites.  Barcode ids
+ * map to columns (or cluster codes) through id2x[cb_id - id_min] for 0 <= cb_id - id_min < id_span, -1 = unknown.
+ * bad_read_out[0] is the first read whose id has no column / code (for the matrix: among reads with label < K),
+ * bad_read_out[1] the first read with a negative label; -1 if none.  Counts are 32-bit: a record may hold at most
+ * INT32_MAX reads.
+ */
+/* (record, label < K, column) counts, kept on the device for rendering; row_tot_out[sum K] = reads per (record, label)
+   (rows of record r start at the sum of K over the records before it); complete_out[r] = 1 when every column with a read
+   in record r has reads in every row of r that has reads (the reference's pivot then prints integers) */
+int scape_hip_report_counts(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *read_off, const int32_t *K,
+                            const int64_t *label, const int64_t *cb_id, int64_t id_min, int64_t id_span,
+                            const int32_t *id2col, int32_t n_cols, int64_t *row_tot_out, int8_t *complete_out,
+                            int64_t *bad_read_out);
+/* Render n_rows CSV rows of the last counts call into slot 0 or 1: row i is the quoted prefix pre[pre_off[i],
+   pre_off[i+1]), then for every column ',"0.0"' for a zero and ',"<n>"' (is_int[i] != 0) or ',"<n>.0"' otherwise,
+   then a newline.  Returns once the block's size is known (*bytes_out); the text itself is rendered and copied to a
+   pinned host buffer behind it.  The host buffer of the slot must no longer be in use (scape_hip_report_fetch). */
+int scape_hip_report_render(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, const int64_t *rows, const int8_t *is_int,
+                            const int64_t *pre_off, const char *pre, int64_t *bytes_out);
+/* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
+int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
+/* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then
+   scape_hip_report_hist_fetch returns the codes (ascending per record, records in order) and the counts
+   [group][K[r] + 1] per record (slot K = reads with label >= K).  Nothing is queued when bad_read_out reports a read. */
+int scape_hip_report_hist(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *read_off, const int32_t *K,
+                          const int64_t *label, const int64_t *cb_id, int64_t id_min, int64_t id_span,
+                          const int32_t *id2code, int32_t n_codes, int64_t *n_groups_out, int64_t *bad_read_out);
+int scape_hip_report_hist_fetch(scape_hip_ctx *ctx, int64_t n_groups, int32_t *codes_out, int64_t n_hist,
+                                int32_t *hist_out);
+/* release every buffer of the reporting stages (also done by scape_hip_destroy) */
+int scape_hip_report_free(scape_hip_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

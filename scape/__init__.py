@@ -1,6 +1,6 @@
-"""``scape`` command surface for the MI355X build: only ``infer_pa`` is provided here
-(reference console script ``scape = scape:main``, pyproject.toml:34-35; the other five
-sub-commands of the reference are outside this build's scope)."""
+"""``scape`` command surface for the MI355X build: ``infer_pa`` and the stages after it, ``merge_pa``,
+``cal_exp_pa_len`` and ``ex_pa_cnt_mat`` (reference console script ``scape = scape:main``, pyproject.toml:34-35;
+``gen_utr_annotation`` and ``prepare_input`` are outside this build's scope)."""
 import time as _time
 
 _t0 = _time.perf_counter()

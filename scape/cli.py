@@ -1,9 +1,11 @@
-"""click group exposing ``infer_pa`` and its consumer ``merge_pa`` (reference cli.py:7-31 registers six
-commands; the other four are outside this build's scope)."""
+"""click group exposing ``infer_pa``, its consumer ``merge_pa`` and the two stages after it, ``cal_exp_pa_len`` and
+``ex_pa_cnt_mat`` (reference cli.py:7-31 registers six commands; ``gen_utr_annotation`` and ``prepare_input`` are
+outside this build's scope)."""
 import click
 
 from scape_amd.apa_core import infer_pa, infer_pa_all, prebin
 from scape_amd.junction_handler import merge_pa
+from scape_amd.report import cal_exp_pa_len, ex_pa_cnt_mat
 
 
 @click.group()
@@ -22,3 +24,5 @@ cli.add_command(infer_pa)
 cli.add_command(infer_pa_all)
 cli.add_command(merge_pa)
 cli.add_command(prebin)
+cli.add_command(cal_exp_pa_len)
+cli.add_command(ex_pa_cnt_mat)

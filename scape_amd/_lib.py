@@ -62,6 +62,14 @@ SIGNATURES = {
     "scape_hip_timing_get": (c_i, [P_void, c_i32, P_d, P_i32]),
     "scape_hip_em_counters": (c_i, [P_void, P_i64, P_i64, P_i64]),
     "scape_hip_em_traffic": (c_i, [P_void, P_i64, P_i64, P_i64, P_i64]),
+    "scape_hip_report_counts": (c_i, [P_void, c_i32, P_i64, P_i32, P_i64, P_i64, c_i64, c_i64, P_i32, c_i32,
+                                      P_i64, P_i8, P_i64]),
+    "scape_hip_report_render": (c_i, [P_void, c_i32, c_i32, P_i64, P_i8, P_i64, ctypes.c_char_p, P_i64]),
+    "scape_hip_report_fetch": (c_i, [P_void, c_i32, ctypes.POINTER(P_void), P_i64]),
+    "scape_hip_report_hist": (c_i, [P_void, c_i32, P_i64, P_i32, P_i64, P_i64, c_i64, c_i64, P_i32, c_i32,
+                                    P_i64, P_i64]),
+    "scape_hip_report_hist_fetch": (c_i, [P_void, c_i64, P_i32, c_i64, P_i32]),
+    "scape_hip_report_free": (c_i, [P_void]),
 }
 
 _lib = None

@@ -1024,6 +1024,8 @@ struct EventPair {
     hipEvent_t a, b;
 };
 
+struct ReportState;   // report.inc
+
 #define N_COUNTERS (4 + 5 * 64 + 16 + 48)   // (+16: ESTEP_STAMPS, +48: M4_STAMPS tools builds) rounds, slab elements (v1), z elements, unused, then five 64-way sharded counters (em_lockstep.inc)
 struct scape_hip_ctx {
     int device = 0;
@@ -1055,6 +1057,7 @@ struct scape_hip_ctx {
     int n_acc[6] = {0, 0, 0, 0, 0, 0};
     unsigned long long h_counters[3] = {0, 0, 0};
     unsigned long long h_traffic[4] = {0, 0, 0, 0};   // last EM call: M-step tensor bytes, v bytes requested / unique, launches
+    ReportState *rep = nullptr;       // count-matrix / expected-length buffers (report.inc), made on first use
 };
 
 static int ev_begin(scape_hip_ctx *c, int which) {
@@ -1460,6 +1463,8 @@ static int em_lockstep(scape_hip_ctx *c, int n_jobs, int kmax, const int32_t *jo
     return 0;
 }
 
+static void report_release(scape_hip_ctx *c);   // report.inc
+
 extern "C" {
 
 int scape_hip_abi_version(void) { return SCAPE_HIP_ABI_VERSION; }
@@ -1517,6 +1522,7 @@ int scape_hip_destroy(scape_hip_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     scape_hip_batch_free(c);
+    report_release(c);
     c->d_err.release();
     c->d_counters.release();
     for (int w = 0; w < 6; ++w)
@@ -2144,3 +2150,5 @@ int scape_hip_em_traffic(scape_hip_ctx *c, int64_t *mstep_tensor_bytes, int64_t 
 }
 
 }  // extern "C"
+
+#include "report.inc"

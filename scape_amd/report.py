@@ -1,0 +1,448 @@
+"""``scape cal_exp_pa_len`` and ``scape ex_pa_cnt_mat``: the two stages after ``merge_pa`` (reference
+``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of
+``apa_core.py:1038-1063``).
+
+Both stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
+``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc``:
+
+* ``ex_pa_cnt_mat``: the device counts (record, label < K, barcode column), flags the records whose pandas pivot would
+  be complete, and renders every CSV row; the host builds the quoted ``pa_info`` prefixes and gzips finished blocks on
+  ``host_threads()`` threads (zlib releases the GIL) while the device renders the next block.  The file is a
+  multi-member gzip whose decompressed text equals the reference's.
+* ``cal_exp_pa_len``: the device builds, per record, the cluster codes present and the (cluster, label) histogram; the
+  host names and orders the clusters with the reference's own ``np.unique(np.array(...))`` and finishes
+  ``exp_pa_len`` with the reference's numpy expressions, so every printed digit matches by construction.
+
+Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
+the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
+record decide the dtype of its partition (strings mixed with NaN make NaN the string 'nan'; all-float partitions keep
+NaN, whose group never matches itself and gets NaN); unknown barcode or cluster ids raise ``KeyError``.
+"""
+from __future__ import annotations
+
+import csv
+import ctypes
+import io
+import os
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+from timeit import default_timer as timer
+
+import click
+import numpy as np
+
+from . import _hostlib, _lib, safe_pickle
+from ._lib import P_i8, P_i32, P_i64, check, ptr
+
+# device bytes one batch may take (None: a quarter of what the device has free) and text bytes per render block;
+# the tests set both small to run several batches and blocks
+MAX_BATCH_BYTES = None
+MAX_BLOCK_BYTES = 256 << 20
+GZIP_LEVEL = 9            # gzip.open's default, what the reference writes with
+GZIP_PART = 8 << 20       # text bytes per gzip member (one host thread each)
+MAX_ID_SPAN = 1 << 30     # barcode ids are looked up in a dense table over [min id, max id]
+
+_TIMES_KEYS = ("decode", "h2d_counts", "render", "gzip_wait", "finish")
+
+
+class ReportTimes(dict):
+    """Wall seconds per stage of the last command (tools/report_rate.py)."""
+
+
+LAST_TIMES = ReportTimes()
+
+
+# ---------------------------------------------------------------- inputs
+class _IdMap:
+    """dense int32 table id -> slot over [id_min, id_min + span), -1 = no such id"""
+
+    def __init__(self, ids, slots, what):
+        ids = np.asarray(ids)
+        if ids.dtype.kind not in "iu":
+            raise ValueError(f"{what}: the index column must hold integer ids")
+        ids = ids.astype(np.int64)
+        self.id_min = int(ids.min()) if len(ids) else 0
+        span = (int(ids.max()) - self.id_min + 1) if len(ids) else 0
+        if span > MAX_ID_SPAN:
+            raise ValueError(f"{what}: barcode ids span {span} values, more than {MAX_ID_SPAN}")
+        self.span = span
+        self.table = np.full(max(span, 1), -1, dtype=np.int32)
+        self.table[ids - self.id_min] = slots        # a repeated id keeps its last row, as DataFrame.to_dict does
+
+
+def _record_arrays(recs):
+    """read offsets, K, labels and cell ids of a batch of records (int64, concatenated)"""
+    n = np.array([len(p.label_arr) for p in recs], dtype=np.int64)
+    off = np.zeros(len(recs) + 1, dtype=np.int64)
+    np.cumsum(n, out=off[1:])
+    K = np.array([int(p.K) for p in recs], dtype=np.int32)
+    lab = np.concatenate([np.asarray(p.label_arr) for p in recs]).astype(np.int64, copy=False) if off[-1] else \
+        np.zeros(1, np.int64)
+    cb = np.concatenate([np.asarray(p.cb_id_arr) for p in recs]).astype(np.int64, copy=False) if off[-1] else \
+        np.zeros(1, np.int64)
+    if len(lab) != max(off[-1], 1) or len(cb) != max(off[-1], 1):
+        raise ValueError("a record's cb_id_arr and label_arr differ in length")
+    return off, K, np.ascontiguousarray(lab), np.ascontiguousarray(cb)
+
+
+def _batches(path, cost, budget, times):
+    """records of the result stream in file order, grouped so that the sum of cost(record) stays within budget
+    (a record above the budget goes alone)"""
+    t0 = timer()
+    batch, used = [], 0
+    for para in safe_pickle.iter_pickles(path):
+        c = cost(para)
+        if batch and used + c > budget:
+            times["decode"] += timer() - t0
+            yield batch
+            t0 = timer()
+            batch, used = [], 0
+        batch.append(para)
+        used += c
+    times["decode"] += timer() - t0
+    if batch:
+        yield batch
+
+
+def _budget(ctx):
+    if MAX_BATCH_BYTES is not None:
+        return int(MAX_BATCH_BYTES)
+    free = ctypes.c_int64(0)
+    check(ctx.lib.scape_hip_batch_bytes(ctx.h, None, ctypes.byref(free), None), "batch_bytes")
+    return max(64 << 20, free.value // 4)
+
+
+def _raise_bad_read(bad, recs, off, cb, what):
+    if bad[1] >= 0:
+        r = int(np.searchsorted(off, bad[1], side="right") - 1)
+        raise ValueError(f"{recs[r].gene_info_str}: negative label in label_arr")
+    r = int(np.searchsorted(off, bad[0], side="right") - 1)
+    raise KeyError(f"{recs[r].gene_info_str}: cell barcode id {int(cb[bad[0]])} is not in {what}")
+
+
+def _atomic_target(path):
+    return path + ".part"
+
+
+# ---------------------------------------------------------------- ex_pa_cnt_mat
+def _csv_field(s):
+    return '"' + s.replace('"', '""') + '"'
+
+
+def _pa_info(para, labels):
+    """pa_info of the rows `labels` of one record (utils.py:494-512: the same fields, str() of the same numpy values)"""
+    gene_info = para.gene_info_str.split(sep=":")
+    st, en = gene_info[3].split(sep="-")
+    alpha = np.asarray(para.alpha_arr)[labels]
+    loc = alpha + int(st) if gene_info[4] == "+" else int(en) - alpha + 1
+    beta = np.asarray(para.beta_arr)[labels]
+    head, tail = str(gene_info[0]) + ":", ":" + str(gene_info[4]) + ":"
+    end = ":" + str(gene_info[1]) + ":" + str(gene_info[2])
+    return [head + str(a) + ":" + str(b) + tail + str(lb + 1) + end
+            for a, b, lb in zip(loc.tolist(), beta.tolist(), labels.tolist())]
+
+
+def _gzip_part(view):
+    co = zlib.compressobj(GZIP_LEVEL, zlib.DEFLATED, 31)
+    return co.compress(view) + co.flush()
+
+
+class _GzipWriter:
+    """multi-member gzip: each part of the text is compressed on a pool thread, members are written in order"""
+
+    def __init__(self, fh, pool, times):
+        self.fh, self.pool, self.times = fh, pool, times
+        self.pending = []        # futures in file order
+
+    def submit(self, view):
+        n = len(view)
+        for a in range(0, n, GZIP_PART):
+            self.pending.append(self.pool.submit(_gzip_part, view[a:min(n, a + GZIP_PART)]))
+
+    def drain(self):
+        t0 = timer()
+        for f in self.pending:
+            self.fh.write(f.result())
+        self.pending = []
+        self.times["gzip_wait"] += timer() - t0
+
+
+def _render_batch(ctx, recs, K, row_tot, complete, n_cols, writer, times):
+    """every row of one counted batch: prefixes on the host, text on the device; block b is gzipped on the pool while
+    the device renders block b + 1 into the other slot"""
+    rows, is_int, pres = [], [], []
+    base = 0
+    for r, para in enumerate(recs):
+        k = int(K[r])
+        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
+        if len(labs):
+            rows.append(base + labs)
+            is_int.append(np.full(len(labs), complete[r], dtype=np.int8))
+            pres.extend(_csv_field(s) for s in _pa_info(para, labs))
+        base += k
+    if not rows:
+        return
+    rows = np.concatenate(rows).astype(np.int64)
+    is_int = np.concatenate(is_int)
+    pre_b = [s.encode() for s in pres]
+    plen = np.array([len(b) for b in pre_b], dtype=np.int64)
+    # rows per block from an upper bound of the row length (every field ',"<10 digits>.0"')
+    per_row = int(plen.max()) + 15 * n_cols + 2
+    step = max(1, min(1 << 20, MAX_BLOCK_BYTES // per_row))
+    queued = []                  # slots rendered, not yet handed to the pool
+    gzipping = False             # some slot's pinned buffer is still read by pool threads
+    for blk, a in enumerate(range(0, len(rows), step)):
+        b, slot = min(len(rows), a + step), blk % 2
+        if gzipping and blk >= 2:
+            writer.drain()       # the slot's host buffer is about to be overwritten
+            gzipping = False
+        poff = np.zeros(b - a + 1, dtype=np.int64)
+        np.cumsum(plen[a:b], out=poff[1:])
+        blob = b"".join(pre_b[a:b])
+        nbytes = ctypes.c_int64(0)
+        t0 = timer()
+        check(ctx.lib.scape_hip_report_render(ctx.h, slot, b - a, ptr(rows[a:b], P_i64), ptr(is_int[a:b], P_i8),
+                                              ptr(poff, P_i64), blob, ctypes.byref(nbytes)), "report_render")
+        times["render"] += timer() - t0
+        if queued:               # the previous block is complete behind this one's scan: compress it now
+            _hand_over(ctx, queued.pop(0), writer, times)
+            gzipping = True
+        queued.append(slot)
+    for s in queued:
+        _hand_over(ctx, s, writer, times)
+    writer.drain()
+
+
+def _hand_over(ctx, slot, writer, times):
+    hp, nb = ctypes.c_void_p(), ctypes.c_int64(0)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_fetch(ctx.h, slot, ctypes.byref(hp), ctypes.byref(nb)), "report_fetch")
+    times["render"] += timer() - t0
+    writer.submit(memoryview((ctypes.c_char * nb.value).from_address(hp.value)).cast("B"))
+
+
+def _ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, device=None):
+    import pandas as pd
+    res_pkl = os.path.join(output_dir, res_pkl_file)
+    if not (os.path.exists(output_dir)):
+        raise Exception("Given output_dir folder does not exists.")
+    if not (os.path.exists(res_pkl)):
+        raise Exception(f"Invalid file {res_pkl}. Given res_pkl_file is not in output_dir.")
+    outpath = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt.tsv.gz"))
+    cb_df = pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")
+    cb_lst = cb_df["CB"].tolist()
+    n_cols = len(cb_lst)
+    if n_cols == 0:
+        raise ValueError("barcode_index.csv lists no barcode")
+    idmap = _IdMap(cb_df.index.to_numpy(), np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
+    hdr = io.StringIO()
+    csv.writer(hdr, delimiter=',', quoting=csv.QUOTE_ALL, lineterminator='\n').writerow(["pa_info"] + cb_lst)
+
+    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
+    start_t = timer()
+    tmp = _atomic_target(outpath)
+    ctx = None
+    try:
+        with open(tmp, "wb") as fh, ThreadPoolExecutor(_hostlib.host_threads()) as pool:
+            writer = _GzipWriter(fh, pool, times)
+            writer.submit(memoryview(hdr.getvalue().encode()))
+            writer.drain()
+            ctx = _lib.default_context(device)
+            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 4 + len(p.label_arr) * 16 + 64,
+                                 _budget(ctx), times):
+                _count_and_render(ctx, recs, idmap, n_cols, writer, times)
+        os.replace(tmp, outpath)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        if ctx is not None:
+            ctx.lib.scape_hip_report_free(ctx.h)
+    end_t = timer()
+    LAST_TIMES.clear()
+    LAST_TIMES.update(times)
+    LAST_TIMES["total"] = end_t - start_t
+    print("Finish counting for each gene")
+    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
+    return outpath
+
+
+def _count_and_render(ctx, recs, idmap, n_cols, writer, times):
+    t0 = timer()
+    off, K, lab, cb = _record_arrays(recs)
+    row_tot = np.zeros(int(K.sum()), dtype=np.int64)
+    complete = np.zeros(len(recs), dtype=np.int8)
+    bad = np.zeros(2, dtype=np.int64)
+    check(ctx.lib.scape_hip_report_counts(ctx.h, len(recs), ptr(off, P_i64), ptr(K, P_i32), ptr(lab, P_i64),
+                                          ptr(cb, P_i64), idmap.id_min, idmap.span, ptr(idmap.table, P_i32), n_cols,
+                                          ptr(row_tot, P_i64), ptr(complete, P_i8), ptr(bad, P_i64)), "report_counts")
+    times["h2d_counts"] += timer() - t0
+    if bad[0] >= 0 or bad[1] >= 0:
+        _raise_bad_read(bad, recs, off, cb, "barcode_index.csv")
+    _render_batch(ctx, recs, K, row_tot, complete, n_cols, writer, times)
+
+
+# ---------------------------------------------------------------- cal_exp_pa_len
+def _exp_len_rows(K, alpha_arr, counts):
+    """exp_pa_len (apa_core.py:1038-1052) for every row of counts [groups, K + 1] (slot K: reads with label >= K);
+    row-wise numpy reductions run the same pairwise sums as the reference's 1-D np.sum"""
+    out = np.zeros(counts.shape[0])
+    if K == 1:
+        out[:] = 1.0
+        return out
+    below = counts[:, :K]
+    n_all = counts.sum(axis=1)
+    n_below = below.sum(axis=1)
+    live = (n_all > 0) & (n_below > 0)
+    out[~live] = np.nan
+    if np.any(live):
+        ws = below[live].astype(np.float64)
+        ws = ws / np.sum(ws, axis=1, keepdims=True)
+        a_arr = alpha_arr
+        with np.errstate(all="ignore"):
+            n_arr = 1.0 + 9.0 * (a_arr - a_arr[0]) / (a_arr[-1] - a_arr[0])
+            out[live] = np.sum(ws * n_arr, axis=1)
+    return out
+
+
+def _cal_exp_pa_len(output_dir: str, cell_cluster_file: str, res_pkl_file: str, device=None):
+    import pandas as pd
+    if not os.path.exists(os.path.join(output_dir, "pkl_output")):
+        raise Exception("Please use the same directory that stores res pickle files by infer_pa")
+    if not os.path.exists(os.path.join(output_dir, "pkl_input")):
+        raise Exception("Please use the same directory that stores res pickle files by prepare_input")
+    final_res = os.path.join(output_dir, res_pkl_file)
+    if not (os.path.exists(final_res)):
+        raise Exception("Must run apajunction before apaexppalen")
+    if not (os.path.exists(os.path.join(output_dir, "barcode_index.csv"))):
+        raise Exception("Please use the same output directory as in prepare_input and infer_pa")
+    pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")   # read (and checked) as the reference does
+    if cell_cluster_file == "None":
+        idmap, values = None, None
+        output_path = os.path.join(output_dir, "all_cell." + res_pkl_file.replace(".pkl", ".pa.len.csv").replace("res.", ""))
+    else:
+        if not (os.path.exists(cell_cluster_file)):
+            raise Exception("Given cell_cluster_file file does not exists")
+        cluster_df = pd.read_csv(cell_cluster_file, index_col="index")
+        prefix = os.path.splitext(os.path.basename(cell_cluster_file))[0]
+        output_path = os.path.join(output_dir, prefix + "." + res_pkl_file.replace(".pkl", ".pa.len.csv").replace("res.", ""))
+        col = cluster_df.iloc[:, 0]
+        vals = col.tolist()                             # the Python objects cluster_dict holds (utils.py:387)
+        codes, _uniq = pd.factorize(pd.Series(vals, dtype=object), use_na_sentinel=False)
+        codes = np.asarray(codes, dtype=np.int32)
+        first = np.unique(codes, return_index=True)[1]  # factorize numbers values by first appearance
+        values = [vals[i] for i in first]               # one representative object per code
+        idmap = _IdMap(col.index.to_numpy(), codes, cell_cluster_file)
+
+    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
+    start_t = timer()
+    exp_len_lst = []
+    ctx = None
+    try:
+        n_codes = len(values) if values is not None else 1
+        n_words = (max(n_codes, 1) + 31) // 32
+
+        def cost(p):
+            n = len(p.label_arr)
+            return n * 16 + n_words * 8 + min(n, n_codes) * (int(p.K) + 1) * 4 + 64
+
+        ctx = _lib.default_context(device)
+        for recs in _batches(final_res, cost, _budget(ctx), times):
+            _hist_batch(ctx, recs, idmap, values, n_codes, exp_len_lst, times, cell_cluster_file)
+    finally:
+        if ctx is not None:
+            ctx.lib.scape_hip_report_free(ctx.h)
+    end_t = timer()
+    print(f"Done calculating expected pa length each gene in {(end_t - start_t) / 60} min.")
+    t0 = timer()
+    if cell_cluster_file == "None":
+        final_df = pd.DataFrame(exp_len_lst, columns=["gene_id", "exp_length", "num_pa"])
+    else:
+        final_df = pd.DataFrame(exp_len_lst, columns=["gene_id", "cell_cluster", "exp_length", "num_pa"])
+    tmp = _atomic_target(output_path)
+    try:
+        final_df.to_csv(tmp, header=True, index=False)
+        os.replace(tmp, output_path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    times["finish"] += timer() - t0
+    end_t = timer()
+    LAST_TIMES.clear()
+    LAST_TIMES.update(times)
+    LAST_TIMES["total"] = end_t - start_t
+    print(f"Done in {(end_t - start_t) / 60} min. ")
+    return output_path
+
+
+def _hist_batch(ctx, recs, idmap, values, n_codes, exp_len_lst, times, cell_cluster_file):
+    t0 = timer()
+    off, K, lab, cb = _record_arrays(recs)
+    n_groups = np.zeros(len(recs), dtype=np.int64)
+    bad = np.zeros(2, dtype=np.int64)
+    lib = ctx.lib
+    table = ptr(idmap.table, P_i32) if idmap is not None else None
+    check(lib.scape_hip_report_hist(ctx.h, len(recs), ptr(off, P_i64), ptr(K, P_i32), ptr(lab, P_i64), ptr(cb, P_i64),
+                                    idmap.id_min if idmap else 0, idmap.span if idmap else 0, table, n_codes,
+                                    ptr(n_groups, P_i64), ptr(bad, P_i64)), "report_hist")
+    if bad[0] >= 0 or bad[1] >= 0:
+        _raise_bad_read(bad, recs, off, cb, cell_cluster_file)
+    n_hist = int(np.sum(n_groups * (K.astype(np.int64) + 1)))
+    codes = np.zeros(max(int(n_groups.sum()), 1), dtype=np.int32)
+    hist = np.zeros(max(n_hist, 1), dtype=np.int32)
+    check(lib.scape_hip_report_hist_fetch(ctx.h, int(n_groups.sum()), ptr(codes, P_i32), n_hist, ptr(hist, P_i32)),
+          "report_hist_fetch")
+    times["h2d_counts"] += timer() - t0
+    t0 = timer()
+    g0 = h0 = 0
+    for r, para in enumerate(recs):
+        chrom, gene_id, utr_id, st_en, strand = para.gene_info_str.split(":")
+        k, g = int(K[r]), int(n_groups[r])
+        cnt = hist[h0:h0 + g * (k + 1)].reshape(g, k + 1).astype(np.int64)
+        alpha = para.alpha_arr
+        if values is None:
+            exp_len = _exp_len_rows(k, alpha, cnt.sum(axis=0, keepdims=True))[0] if g else \
+                (1.0 if para.K == 1 else np.nan)
+            exp_len_lst.append([gene_id + ":" + utr_id, exp_len, para.K])
+        elif g:
+            # the partition of the record holds exactly these values: np.array of them has the dtype the reference's
+            # per-read np.array gets, and np.unique orders / merges them the same way (apa_core.py:1056-1057)
+            part = np.array([values[c] for c in codes[g0:g0 + g].tolist()])
+            uni_clusters = np.unique(part)
+            grp = np.zeros((len(uni_clusters), k + 1), dtype=np.int64)
+            for i, c in enumerate(uni_clusters):
+                m = part == c
+                if np.any(m):
+                    grp[i] = cnt[m].sum(axis=0)
+            avg_len_arr = np.zeros(len(uni_clusters))
+            avg_len_arr[:] = _exp_len_rows(k, alpha, grp)
+            for idx in range(len(uni_clusters)):
+                exp_len_lst.append([gene_id + ":" + utr_id, uni_clusters[idx], avg_len_arr[idx], para.K])
+        g0 += g
+        h0 += g * (k + 1)
+    times["finish"] += timer() - t0
+
+
+# ---------------------------------------------------------------- commands (reference utils.py:323-342, :442-454)
+@click.command(name="cal_exp_pa_len")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa')
+@click.option('--cell_cluster_file', type=str, default="None",
+              help='An csv file containing two columns in order: cell barcode (CB) and respective group '
+                   '(cell_cluster_file). Its name will be included in the file name of final result.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs for calculating expected PA length. Its name will be '
+                   'included in the file name of final result.')
+def cal_exp_pa_len(output_dir: str, cell_cluster_file: str, res_pkl_file: str):
+    """Expected pA length per gene (and per cell cluster) from res.gene.pkl / res.utr.pkl (reference utils.py:319-427)."""
+    _cal_exp_pa_len(output_dir, cell_cluster_file, res_pkl_file)
+
+
+@click.command(name="ex_pa_cnt_mat")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs for calculating expected PA length. Its name will be '
+                   'included in the file name of final result.')
+def ex_pa_cnt_mat(output_dir: str, res_pkl_file: str):
+    """pA x cell read-count matrix <res name>.cnt.tsv.gz from res.gene.pkl / res.utr.pkl (reference utils.py:438-553)."""
+    _ex_pa_cnt_mat(output_dir, res_pkl_file)
