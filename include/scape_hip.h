@@ -187,6 +187,11 @@ int scape_hip_report_counts(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *re
    pinned host buffer behind it.  The host buffer of the slot must no longer be in use (scape_hip_report_fetch). */
 int scape_hip_report_render(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, const int64_t *rows, const int8_t *is_int,
                             const int64_t *pre_off, const char *pre, int64_t *bytes_out);
+/* Render the same rows as Matrix Market coordinate entries into slot 0 or 1: row i is number row_no0 + i of the file
+   (row_no0 >= 1), and each of its nonzero columns c, ascending, gives the line "<row_no0 + i> <c + 1> <count>\n".
+   *bytes_out = the block's text bytes, *nnz_out = its entries; the rest as scape_hip_report_render. */
+int scape_hip_report_render_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, const int64_t *rows, int64_t row_no0,
+                                int64_t *bytes_out, int64_t *nnz_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

@@ -13,6 +13,9 @@
 //                   byte length of every CSV row, their scan, and the row text itself (the host supplies each row's quoted
 //                   pa_info prefix); rows are rendered in blocks into one of two buffers so the host compresses block b
 //                   while the device renders block b + 1
+//   k_rep_mtx_rowlen / k_rep_scan / k_rep_mtx_render
+//                   the same rows as Matrix Market coordinate entries ("<row> <col> <count>\n", nonzero counts only,
+//                   1-based): per row its entries and bytes, their scans, and the entries, through the same two slots
 //   k_rep_present / k_rep_groups / k_rep_hist
 //                   per record, the bitmap of cluster codes present, its compaction to the record's groups and the
 //                   (group, label) histogram; labels >= K share the last slot (they decide whether a group exists and
@@ -35,6 +38,7 @@ struct ReportState {
     int64_t h_groups = 0, h_hist_n = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
+    DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
     void *host_out[2] = {nullptr, nullptr};
     size_t host_cap[2] = {0, 0};
     int64_t slot_bytes[2] = {0, 0};
@@ -54,7 +58,8 @@ static void report_release(scape_hip_ctx *c) {
                      &s->r_cflag, &s->r_err, &s->h_bits, &s->h_wpre, &s->h_nloc, &s->h_goff, &s->h_hoff, &s->h_codes,
                      &s->h_hist, &s->s_rows[0], &s->s_rows[1], &s->s_int[0], &s->s_int[1], &s->s_poff[0],
                      &s->s_poff[1], &s->s_pre[0], &s->s_pre[1], &s->s_len[0], &s->s_len[1], &s->s_roff[0],
-                     &s->s_roff[1], &s->s_out[0], &s->s_out[1]};
+                     &s->s_roff[1], &s->s_out[0], &s->s_out[1], &s->s_nnz[0], &s->s_nnz[1], &s->s_noff[0],
+                     &s->s_noff[1]};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;
@@ -101,6 +106,15 @@ __device__ __forceinline__ T rep_block_excl(T v, T *lds, T *total) {
 }
 
 __device__ __forceinline__ int rep_digits(uint32_t v) {
+    int n = 1;
+    while (v >= 10) {
+        v /= 10;
+        ++n;
+    }
+    return n;
+}
+
+__device__ __forceinline__ int rep_digits64(uint64_t v) {
     int n = 1;
     while (v >= 10) {
         v /= 10;
@@ -259,6 +273,85 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_render(const int64_t *__res
     if (threadIdx.x == 0) dst[pos] = '\n';
 }
 
+// ---- Matrix Market rendering ----------------------------------------------------------------------------------------
+// row i of a block: count row rows[i] of the last counts call, number row_no0 + i of the file; its entries are
+// "<row number> <column + 1> <count>\n" for the nonzero columns, ascending.  rnnz[i] = entries, rlen[i] = bytes
+__global__ __launch_bounds__(REP_THREADS) void k_rep_mtx_rowlen(const int64_t *__restrict__ rows, int64_t row_no0,
+                                                                int32_t n_cols, const int32_t *__restrict__ cnt,
+                                                                int64_t *__restrict__ rlen,
+                                                                int64_t *__restrict__ rnnz) {
+    __shared__ long long lds[REP_WAVES];
+    const int i = blockIdx.x;
+    const int32_t *row = cnt + rows[i] * n_cols;
+    long long n = 0, e = 0;
+    for (int c = threadIdx.x; c < n_cols; c += REP_THREADS) {
+        const int v = row[c];
+        if (v) {
+            ++n;
+            e += rep_digits((uint32_t)c + 1) + rep_digits((uint32_t)v);
+        }
+    }
+    n = rep_block_sum<long long, REP_WAVES>(n, lds);
+    e = rep_block_sum<long long, REP_WAVES>(e, lds);
+    if (threadIdx.x == 0) {
+        rnnz[i] = n;
+        rlen[i] = e + n * (rep_digits64((uint64_t)(row_no0 + i)) + 3);   // two spaces and the newline
+    }
+}
+
+// one workgroup per row, 256 columns per step: each lane's entry position is the tile's running offset plus the
+// exclusive scan of the entry lengths (0 for a zero count); the row number is formatted once, into LDS
+__global__ __launch_bounds__(REP_THREADS) void k_rep_mtx_render(const int64_t *__restrict__ rows, int64_t row_no0,
+                                                                int32_t n_cols, const int32_t *__restrict__ cnt,
+                                                                const int64_t *__restrict__ roff,
+                                                                char *__restrict__ out) {
+    __shared__ int lds[REP_WAVES];
+    __shared__ char row_txt[20];
+    const int i = blockIdx.x;
+    const int32_t *row = cnt + rows[i] * n_cols;
+    const uint64_t row_no = (uint64_t)(row_no0 + i);
+    const int rd = rep_digits64(row_no);
+    if (threadIdx.x == 0) {
+        uint64_t x = row_no;
+        for (int d = rd - 1; d >= 0; --d) {
+            row_txt[d] = (char)('0' + x % 10);
+            x /= 10;
+        }
+    }
+    __syncthreads();
+    char *dst = out + roff[i];
+    int64_t pos = 0;
+    for (int base = 0; base < n_cols; base += REP_THREADS) {
+        const int c = base + threadIdx.x;
+        const int v = c < n_cols ? row[c] : 0;
+        const int cd = v ? rep_digits((uint32_t)c + 1) : 0;
+        const int vd = v ? rep_digits((uint32_t)v) : 0;
+        const int elen = v ? rd + cd + vd + 3 : 0;
+        int tile;
+        const int ex = rep_block_excl<int, REP_WAVES>(elen, lds, &tile);
+        if (v) {
+            char *f = dst + pos + ex;
+            for (int d = 0; d < rd; ++d) f[d] = row_txt[d];
+            f[rd] = ' ';
+            f += rd + 1;
+            uint32_t x = (uint32_t)c + 1;
+            for (int d = cd - 1; d >= 0; --d) {
+                f[d] = (char)('0' + x % 10);
+                x /= 10;
+            }
+            f[cd] = ' ';
+            f += cd + 1;
+            x = (uint32_t)v;
+            for (int d = vd - 1; d >= 0; --d) {
+                f[d] = (char)('0' + x % 10);
+                x /= 10;
+            }
+            f[vd] = '\n';
+        }
+        pos += tile;
+    }
+}
+
 // ---- cluster histograms ---------------------------------------------------------------------------------------------
 // one workgroup per record: bit `code` of the record's bitmap for every read; id2code == nullptr: one group (code 0).
 // err[0] = first read whose barcode id has no code, err[1] = first read with a negative label
@@ -374,6 +467,30 @@ static int rep_upload_map(scape_hip_ctx *c, ReportState *s, int64_t id_span, con
     return 0;
 }
 
+// a render slot's device text buffer, pinned host buffer and event, for a block of `total` bytes
+static int rep_slot_out(ReportState *s, int32_t slot, int64_t total) {
+    if (s->s_out[slot].ensure(total)) return 1;
+    if (s->host_cap[slot] < (size_t)total) {
+        if (s->host_out[slot]) HIPCHK(hipHostFree(s->host_out[slot]));
+        s->host_out[slot] = nullptr;
+        s->host_cap[slot] = 0;
+        const size_t want = (size_t)total + (size_t)total / 8;
+        HIPCHK(hipHostMalloc(&s->host_out[slot], want, hipHostMallocDefault));
+        s->host_cap[slot] = want;
+    }
+    if (!s->done[slot]) HIPCHK(hipEventCreateWithFlags(&s->done[slot], hipEventDisableTiming));
+    return 0;
+}
+
+// queue the copy of a rendered block into the slot's pinned host buffer (scape_hip_report_fetch waits for it)
+static int rep_slot_queue(scape_hip_ctx *c, ReportState *s, int32_t slot, int64_t total) {
+    HIPCHK(hipMemcpyAsync(s->host_out[slot], s->s_out[slot].p, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(s->done[slot], c->stream));
+    s->pending[slot] = true;
+    s->slot_bytes[slot] = total;
+    return 0;
+}
+
 static int rep_fetch_err(scape_hip_ctx *c, ReportState *s, int64_t *bad) {
     unsigned long long e[2];
     HIPCHK(hipMemcpyAsync(e, s->r_err.p, 16, hipMemcpyDeviceToHost, c->stream));
@@ -458,25 +575,57 @@ int scape_hip_report_render(scape_hip_ctx *c, int32_t slot, int32_t n_rows, cons
     HIPCHK(hipMemcpyAsync(&total, s->s_roff[slot].as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (total <= 0) return fail("empty render block");
-    if (s->s_out[slot].ensure(total)) return 1;
-    if (s->host_cap[slot] < (size_t)total) {
-        if (s->host_out[slot]) HIPCHK(hipHostFree(s->host_out[slot]));
-        s->host_out[slot] = nullptr;
-        s->host_cap[slot] = 0;
-        const size_t want = (size_t)total + (size_t)total / 8;
-        HIPCHK(hipHostMalloc(&s->host_out[slot], want, hipHostMallocDefault));
-        s->host_cap[slot] = want;
-    }
-    if (!s->done[slot]) HIPCHK(hipEventCreateWithFlags(&s->done[slot], hipEventDisableTiming));
+    if (rep_slot_out(s, slot, total)) return 1;
     hipLaunchKernelGGL(k_rep_render, dim3(n_rows), dim3(REP_THREADS), 0, c->stream, s->s_rows[slot].as<int64_t>(),
                        s->s_int[slot].as<int8_t>(), s->s_poff[slot].as<int64_t>(), s->s_pre[slot].as<char>(), s->n_cols,
                        s->r_cnt.as<int32_t>(), s->s_roff[slot].as<int64_t>(), s->s_out[slot].as<char>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->host_out[slot], s->s_out[slot].p, total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipEventRecord(s->done[slot], c->stream));
-    s->pending[slot] = true;
-    s->slot_bytes[slot] = total;
+    if (rep_slot_queue(c, s, slot, total)) return 1;
     *bytes_out = total;
+    return 0;
+}
+
+int scape_hip_report_render_mtx(scape_hip_ctx *c, int32_t slot, int32_t n_rows, const int64_t *rows, int64_t row_no0,
+                                int64_t *bytes_out, int64_t *nnz_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
+    if (slot < 0 || slot > 1 || n_rows <= 0 || !rows || !bytes_out || !nnz_out) return fail("bad argument");
+    if (row_no0 < 1 || row_no0 > INT64_MAX - n_rows) return fail("row_no0 out of range");
+    for (int i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
+    if (s->pending[slot]) {              // the host buffer of this slot is handed over again
+        HIPCHK(hipEventSynchronize(s->done[slot]));
+        s->pending[slot] = false;
+    }
+    const int64_t n = n_rows;
+    if (s->s_rows[slot].ensure(n * 8) || s->s_len[slot].ensure(n * 8) || s->s_roff[slot].ensure((n + 1) * 8) ||
+        s->s_nnz[slot].ensure(n * 8) || s->s_noff[slot].ensure((n + 1) * 8))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->s_rows[slot].p, rows, n * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_mtx_rowlen, dim3(n_rows), dim3(REP_THREADS), 0, c->stream, s->s_rows[slot].as<int64_t>(),
+                       row_no0, s->n_cols, s->r_cnt.as<int32_t>(), s->s_len[slot].as<int64_t>(),
+                       s->s_nnz[slot].as<int64_t>());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->s_len[slot].as<int64_t>(), n_rows,
+                       s->s_roff[slot].as<int64_t>());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->s_nnz[slot].as<int64_t>(), n_rows,
+                       s->s_noff[slot].as<int64_t>());
+    HIPCHK(hipGetLastError());
+    int64_t total = 0, nnz = 0;
+    HIPCHK(hipMemcpyAsync(&total, s->s_roff[slot].as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&nnz, s->s_noff[slot].as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (total <= 0) return fail("empty render block");
+    if (rep_slot_out(s, slot, total)) return 1;
+    hipLaunchKernelGGL(k_rep_mtx_render, dim3(n_rows), dim3(REP_THREADS), 0, c->stream, s->s_rows[slot].as<int64_t>(),
+                       row_no0, s->n_cols, s->r_cnt.as<int32_t>(), s->s_roff[slot].as<int64_t>(),
+                       s->s_out[slot].as<char>());
+    HIPCHK(hipGetLastError());
+    if (rep_slot_queue(c, s, slot, total)) return 1;
+    *bytes_out = total;
+    *nnz_out = nnz;
     return 0;
 }
 

@@ -8,7 +8,8 @@ Both stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``
 * ``ex_pa_cnt_mat``: the device counts (record, label < K, barcode column), flags the records whose pandas pivot would
   be complete, and renders every CSV row; the host builds the quoted ``pa_info`` prefixes and gzips finished blocks on
   ``host_threads()`` threads (zlib releases the GIL) while the device renders the next block.  The file is a
-  multi-member gzip whose decompressed text equals the reference's.
+  multi-member gzip whose decompressed text equals the reference's.  ``--format mtx`` writes the same rows and columns
+  as a 10x-style Matrix Market directory instead; the device renders its nonzero entries from the same counts.
 * ``cal_exp_pa_len``: the device builds, per record, the cluster codes present and the (cluster, label) histogram; the
   host names and orders the clusters with the reference's own ``np.unique(np.array(...))`` and finishes
   ``exp_pa_len`` with the reference's numpy expressions, so every printed digit matches by construction.
@@ -24,6 +25,8 @@ import csv
 import ctypes
 import io
 import os
+import shutil
+import tempfile
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 from timeit import default_timer as timer
@@ -221,8 +224,12 @@ def _hand_over(ctx, slot, writer, times):
     writer.submit(memoryview((ctypes.c_char * nb.value).from_address(hp.value)).cast("B"))
 
 
-def _ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, device=None):
+def _ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, device=None, fmt="tsv"):
+    """fmt "tsv": the reference's dense <res>.cnt.tsv.gz; "mtx": the directory <res>.cnt/ with matrix.mtx.gz,
+    features.tsv.gz and barcodes.tsv.gz (_ex_pa_cnt_mtx)"""
     import pandas as pd
+    if fmt not in ("tsv", "mtx"):
+        raise ValueError(f"unknown count matrix format {fmt!r} (tsv or mtx)")
     res_pkl = os.path.join(output_dir, res_pkl_file)
     if not (os.path.exists(output_dir)):
         raise Exception("Given output_dir folder does not exists.")
@@ -235,6 +242,8 @@ def _ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, device=None):
     if n_cols == 0:
         raise ValueError("barcode_index.csv lists no barcode")
     idmap = _IdMap(cb_df.index.to_numpy(), np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
+    if fmt == "mtx":
+        return _ex_pa_cnt_mtx(output_dir, res_pkl_file, res_pkl, cb_lst, idmap, device)
     hdr = io.StringIO()
     csv.writer(hdr, delimiter=',', quoting=csv.QUOTE_ALL, lineterminator='\n').writerow(["pa_info"] + cb_lst)
 
@@ -266,7 +275,8 @@ def _ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, device=None):
     return outpath
 
 
-def _count_and_render(ctx, recs, idmap, n_cols, writer, times):
+def _count(ctx, recs, idmap, n_cols, times):
+    """counts of one batch, kept on the device; K, the row totals and the pivot-complete flags on the host"""
     t0 = timer()
     off, K, lab, cb = _record_arrays(recs)
     row_tot = np.zeros(int(K.sum()), dtype=np.int64)
@@ -278,7 +288,153 @@ def _count_and_render(ctx, recs, idmap, n_cols, writer, times):
     times["h2d_counts"] += timer() - t0
     if bad[0] >= 0 or bad[1] >= 0:
         _raise_bad_read(bad, recs, off, cb, "barcode_index.csv")
+    return K, row_tot, complete
+
+
+def _count_and_render(ctx, recs, idmap, n_cols, writer, times):
+    K, row_tot, complete = _count(ctx, recs, idmap, n_cols, times)
     _render_batch(ctx, recs, K, row_tot, complete, n_cols, writer, times)
+
+
+# ---------------------------------------------------------------- ex_pa_cnt_mat --format mtx
+MTX_FILES = ("matrix.mtx.gz", "features.tsv.gz", "barcodes.tsv.gz")
+MTX_BANNER = "%%MatrixMarket matrix coordinate integer general\n"
+_POW10 = np.array([10 ** k for k in range(1, 19)], dtype=np.int64)
+
+
+def _digits(a):
+    """decimal digits of non-negative int64 values"""
+    return 1 + np.searchsorted(_POW10, a, side="right")
+
+
+def _tsv_lines(fields, per_line, what):
+    """the lines of a .tsv text; a field with a tab, a newline or a carriage return is a ValueError naming it"""
+    text = "".join(per_line(s) for s in fields)
+    n_tabs = per_line("").count("\t")
+    if "\r" in text or text.count("\n") != len(fields) or text.count("\t") != n_tabs * len(fields):
+        for s in fields:
+            if "\t" in s or "\n" in s or "\r" in s:
+                raise ValueError(f"{what} {s!r} holds a tab or a line break: it cannot be a field of a .tsv file")
+    return text
+
+
+class _MtxSink:
+    """gzip writers of the matrix body and of features.tsv, and the rows / entries written so far"""
+
+    def __init__(self, matrix, features):
+        self.matrix, self.features = matrix, features
+        self.n_rows = self.nnz = 0
+
+
+def _ex_pa_cnt_mtx(output_dir, res_pkl_file, res_pkl, cb_lst, idmap, device):
+    """the count matrix as a 10x-style directory <res>.cnt/: matrix.mtx.gz (the dense file's rows and columns, nonzero
+    counts only, row-major), features.tsv.gz (per row: pa_info, pa_info, "Gene Expression"; Seurat's Read10X names rows
+    from column 2, scanpy's read_10x_mtx from column 2 and keeps only "Gene Expression" rows) and barcodes.tsv.gz (the
+    CB column).  The matrix header holds nnz, known only at the end: the body's gzip members go to an anonymous
+    temporary file and are copied behind the header's member.  The three are renamed from .part once all are complete."""
+    n_cols = len(cb_lst)
+    bc_text = _tsv_lines([str(b) for b in cb_lst], lambda s: s + "\n", "barcode")
+    out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt"))
+    if os.path.exists(out_dir) and not os.path.isdir(out_dir):
+        raise FileExistsError(f"{out_dir} exists and is not a directory")
+
+    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
+    start_t = timer()
+    made_dir = not os.path.isdir(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    final = [os.path.join(out_dir, name) for name in MTX_FILES]
+    tmps = [_atomic_target(p) for p in final]
+    ctx, done = None, False
+    try:
+        with tempfile.TemporaryFile(dir=out_dir) as body, open(tmps[1], "wb") as ffh, \
+                ThreadPoolExecutor(_hostlib.host_threads()) as pool:
+            with open(tmps[2], "wb") as bfh:
+                bw = _GzipWriter(bfh, pool, times)
+                bw.submit(memoryview(bc_text.encode()))
+                bw.drain()
+            sink = _MtxSink(_GzipWriter(body, pool, times), _GzipWriter(ffh, pool, times))
+            ctx = _lib.default_context(device)
+            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 4 + len(p.label_arr) * 16 + 64,
+                                 _budget(ctx), times):
+                K, row_tot, _complete = _count(ctx, recs, idmap, n_cols, times)
+                _render_mtx_batch(ctx, recs, K, row_tot, n_cols, sink, times)
+            t0 = timer()
+            with open(tmps[0], "wb") as mfh:
+                mfh.write(_gzip_part(f"{MTX_BANNER}{sink.n_rows} {n_cols} {sink.nnz}\n".encode()))
+                body.seek(0)
+                shutil.copyfileobj(body, mfh, 16 << 20)
+            times["finish"] += timer() - t0
+        for tmp, path in zip(tmps, final):
+            os.replace(tmp, path)
+        done = True
+    finally:
+        for tmp in tmps:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        if made_dir and not done:
+            try:
+                os.rmdir(out_dir)
+            except OSError:
+                pass
+        if ctx is not None:
+            ctx.lib.scape_hip_report_free(ctx.h)
+    end_t = timer()
+    LAST_TIMES.clear()
+    LAST_TIMES.update(times)
+    LAST_TIMES["total"] = end_t - start_t
+    print("Finish counting for each gene")
+    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
+    return out_dir
+
+
+def _render_mtx_batch(ctx, recs, K, row_tot, n_cols, sink, times):
+    """the rows of one counted batch, numbered on from sink.n_rows: features lines on the host, Matrix Market entries
+    on the device; block b is gzipped on the pool while the device renders block b + 1 (as in _render_batch)"""
+    rows, pa = [], []
+    base = 0
+    for r, para in enumerate(recs):
+        k = int(K[r])
+        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
+        if len(labs):
+            rows.append(base + labs)
+            pa.extend(_pa_info(para, labs))
+        base += k
+    if not rows:
+        return
+    rows = np.concatenate(rows).astype(np.int64)
+    sink.features.submit(memoryview(_tsv_lines(pa, lambda s: f"{s}\t{s}\tGene Expression\n", "pa_info").encode()))
+    # blocks cut against an upper bound of each row's text: at most min(reads, barcodes) entries
+    # "<row number> <column> <count>\n", the count at most the row's reads
+    row_no0 = sink.n_rows + 1
+    tot = row_tot[rows]
+    width = len(str(row_no0 + len(rows) - 1)) + len(str(n_cols)) + 3 + _digits(tot)
+    cum = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(np.minimum(tot, n_cols) * width, out=cum[1:])
+    queued = []                  # slots rendered, not yet handed to the pool
+    gzipping = False             # some slot's pinned buffer is still read by pool threads
+    a = blk = 0
+    while a < len(rows):
+        b = int(np.searchsorted(cum, cum[a] + MAX_BLOCK_BYTES, side="right")) - 1
+        b, slot = min(len(rows), a + (1 << 20), max(a + 1, b)), blk % 2
+        if gzipping and blk >= 2:
+            sink.matrix.drain()  # the slot's host buffer is about to be overwritten
+            gzipping = False
+        nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
+        t0 = timer()
+        check(ctx.lib.scape_hip_report_render_mtx(ctx.h, slot, b - a, ptr(rows[a:b], P_i64), row_no0 + a,
+                                                  ctypes.byref(nbytes), ctypes.byref(nnz)), "report_render_mtx")
+        times["render"] += timer() - t0
+        sink.nnz += nnz.value
+        if queued:               # the previous block is complete behind this one's scan: compress it now
+            _hand_over(ctx, queued.pop(0), sink.matrix, times)
+            gzipping = True
+        queued.append(slot)
+        a, blk = b, blk + 1
+    for s in queued:
+        _hand_over(ctx, s, sink.matrix, times)
+    sink.matrix.drain()
+    sink.features.drain()
+    sink.n_rows += len(rows)
 
 
 # ---------------------------------------------------------------- cal_exp_pa_len
@@ -443,6 +599,10 @@ def cal_exp_pa_len(output_dir: str, cell_cluster_file: str, res_pkl_file: str):
 @click.option('--res_pkl_file', type=str, default="None",
               help='Name of res pickle file that contains PASs for calculating expected PA length. Its name will be '
                    'included in the file name of final result.')
-def ex_pa_cnt_mat(output_dir: str, res_pkl_file: str):
+@click.option('--format', 'fmt', type=click.Choice(["tsv", "mtx"]), default="tsv", show_default=True,
+              help='tsv: the dense matrix <res name>.cnt.tsv.gz. mtx: the directory <res name>.cnt/ with '
+                   'matrix.mtx.gz, features.tsv.gz and barcodes.tsv.gz (sparse Matrix Market, as read by Seurat '
+                   'Read10X and scanpy read_10x_mtx).')
+def ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, fmt: str):
     """pA x cell read-count matrix <res name>.cnt.tsv.gz from res.gene.pkl / res.utr.pkl (reference utils.py:438-553)."""
-    _ex_pa_cnt_mat(output_dir, res_pkl_file)
+    _ex_pa_cnt_mat(output_dir, res_pkl_file, fmt=fmt)

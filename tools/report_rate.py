@@ -6,8 +6,11 @@ and a cluster file with 12 groups.  Prints one JSON line with the wall time of e
 read-backs; render = row-length / scan / render kernels and the copy of the text to the host, as far as the host
 waits for them; gzip_wait = time the host waits for the compressing threads; finish = host post-processing and the
 csv write.  Kernel times: run it under `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/report_rate.py ...`.
+`--format mtx` runs the count matrix as the Matrix Market directory instead of the dense file (`both`: one after the
+other on the same stream) and adds its text bytes per file, rows and nnz (entries); its `finish` is the header write
+and the copy of the body behind it.
 
-    python tools/report_rate.py [--records N] [--reads N] [--cells N]
+    python tools/report_rate.py [--records N] [--reads N] [--cells N] [--format tsv|mtx|both]
 """
 import argparse
 import contextlib
@@ -53,11 +56,32 @@ def make_dir(root, n_rec, reads, n_cells, seed=7):
     return n_reads
 
 
+def gz_text(path):
+    """decompressed bytes of a gzip file and its first 256 decompressed bytes"""
+    text, head = 0, b""
+    with gzip.open(path, "rb") as fh:
+        while True:
+            b = fh.read(1 << 26)
+            if not b:
+                break
+            head = head or b[:256]
+            text += len(b)
+    return text, head
+
+
+def size(path):
+    if os.path.isdir(path):
+        return sum(os.path.getsize(os.path.join(path, n)) for n in os.listdir(path))
+    return os.path.getsize(path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=20000)
     ap.add_argument("--reads", type=int, default=3000)
     ap.add_argument("--cells", type=int, default=33088)
+    ap.add_argument("--format", choices=("tsv", "mtx", "both"), default="tsv",
+                    help="count matrix: the dense file (default), the Matrix Market directory, or both")
     a = ap.parse_args()
     from scape_amd import _lib, report
     root = tempfile.mkdtemp(prefix="report_rate_")
@@ -68,26 +92,33 @@ def main():
         out["make_s"] = time.perf_counter() - t0
         out["res_pkl_bytes"] = os.path.getsize(os.path.join(root, "res.gene.pkl"))
         out["device"] = _lib.default_context().name()
-        runs = (("ex_pa_cnt_mat", lambda: report._ex_pa_cnt_mat(root, "res.gene.pkl")),
-                ("cal_exp_pa_len", lambda: report._cal_exp_pa_len(root, "None", "res.gene.pkl")),
-                ("cal_exp_pa_len_groups",
-                 lambda: report._cal_exp_pa_len(root, os.path.join(root, "groups.csv"), "res.gene.pkl")))
+        runs = []
+        if a.format in ("tsv", "both"):
+            runs.append(("ex_pa_cnt_mat", lambda: report._ex_pa_cnt_mat(root, "res.gene.pkl")))
+        if a.format in ("mtx", "both"):
+            runs.append(("ex_pa_cnt_mat_mtx", lambda: report._ex_pa_cnt_mat(root, "res.gene.pkl", fmt="mtx")))
+        runs += [("cal_exp_pa_len", lambda: report._cal_exp_pa_len(root, "None", "res.gene.pkl")),
+                 ("cal_exp_pa_len_groups",
+                  lambda: report._cal_exp_pa_len(root, os.path.join(root, "groups.csv"), "res.gene.pkl"))]
         for name, fn in runs:
             t0 = time.perf_counter()
             with contextlib.redirect_stdout(io.StringIO()):
                 path = fn()
             out[name] = {"wall_s": time.perf_counter() - t0, "stages_s": dict(report.LAST_TIMES),
-                         "out_bytes": os.path.getsize(path)}
-        text = 0
-        with gzip.open(os.path.join(root, "res.gene.cnt.tsv.gz"), "rb") as fh:
-            while True:
-                b = fh.read(1 << 26)
-                if not b:
-                    break
-                text += len(b)
-        m = out["ex_pa_cnt_mat"]
-        m["text_bytes"] = text
-        m["text_GB_per_s"] = text / m["wall_s"] / 1e9
+                         "out_bytes": size(path)}
+        if "ex_pa_cnt_mat" in out:
+            m = out["ex_pa_cnt_mat"]
+            m["text_bytes"] = gz_text(os.path.join(root, "res.gene.cnt.tsv.gz"))[0]
+            m["text_GB_per_s"] = m["text_bytes"] / m["wall_s"] / 1e9
+        if "ex_pa_cnt_mat_mtx" in out:
+            m = out["ex_pa_cnt_mat_mtx"]
+            d = os.path.join(root, "res.gene.cnt")
+            m["text_bytes_per_file"] = {n: gz_text(os.path.join(d, n))[0] for n in report.MTX_FILES}
+            m["out_bytes_per_file"] = {n: os.path.getsize(os.path.join(d, n)) for n in report.MTX_FILES}
+            m["text_bytes"] = sum(m["text_bytes_per_file"].values())
+            m["text_GB_per_s"] = m["text_bytes"] / m["wall_s"] / 1e9
+            rows, cols, nnz = gz_text(os.path.join(d, "matrix.mtx.gz"))[1].split(b"\n")[1].split()
+            m.update(rows=int(rows), cols=int(cols), nnz=int(nnz))
     finally:
         shutil.rmtree(root, ignore_errors=True)
     print(json.dumps(out))
