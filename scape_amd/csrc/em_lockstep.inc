@@ -196,7 +196,7 @@ __device__ __forceinline__ void estep_body(
         // cal_bic (:702-706), sort by alpha (:768-772), outputs
         if (lead && lane == 0) {
             const int n_lb = S.nlb[job];
-            bic_out[job] = -2 * S.ell[job] + (3 * K + 1) * log((double)N);
+            bic_out[job] = d_bic(S.ell[job], K, N);
             nlb_out[job] = n_lb;
             int idx[CMAX];
             for (int i = 0; i < K; ++i) idx[i] = i;

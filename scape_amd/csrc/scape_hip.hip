@@ -145,6 +145,16 @@ __device__ __forceinline__ double d_rcp_mid(double x) {
 }
 
 __device__ __forceinline__ double d_logw(double w) { return (w <= 0.0) ? SENT : log(w); }
+
+// cal_bic (apa_core.py:702-706).  The product and the sum are rounded one after the other, as numpy rounds them: left to
+// the compiler, some instantiations of the E-step (a compile-time K in one, a run-time K in the other) fused them into
+// one FMA and others did not, and the same job came back with a BIC one ulp apart depending on the column class of the
+// call it was part of (tests/test_em_column_classes.py)
+__device__ __forceinline__ double d_bic(double ell, int K, int N) {
+#pragma clang fp contract(off)
+    const double penalty = (double)(3 * K + 1) * log((double)N);
+    return -2.0 * ell + penalty;
+}
 __device__ __forceinline__ double d_logpdf_normal(double x, double mu, double sigma) {
     double z = (x - mu) / sigma;
     return -0.5 * (z * z) - log(sigma) - 0.5 * log(2 * PI_REF);
@@ -885,7 +895,7 @@ __global__ __launch_bounds__(EM_THREADS) void k_em(
 
     // ---- cal_bic (:702-706), sort by alpha (:768-772), outputs -------------------------------
     if (tid == 0) {
-        bic_out[job] = -2 * ell_last + (3 * K + 1) * log((double)N);
+        bic_out[job] = d_bic(ell_last, K, N);
         nlb_out[job] = n_lb;
         int idx[CMAX];
         for (int i = 0; i < K; ++i) idx[i] = i;

@@ -61,3 +61,20 @@ def synth_utr(index, n_reads, k_cap=5, base_seed=0, pa_rate=0.015, noise=0.05, r
 
 def synth_chunk(n_utr, n_reads, k_cap=5, base_seed=0, start=0, **kw):
     return [synth_utr(start + i, n_reads, k_cap=k_cap, base_seed=base_seed, **kw)[:2] for i in range(n_utr)]
+
+
+def many_sites_utr(n_sites=34, reads=3000, seed=5, gap=140, beta=8.0):
+    """A UTR with more true pA sites than the old K <= 31 limit of the kernels (inputs only)."""
+    rng = np.random.default_rng(seed)
+    alphas = 400 + gap * np.arange(n_sites)
+    comp = rng.integers(0, n_sites, reads)
+    theta = rng.normal(alphas[comp], beta)
+    s = rng.choice(np.arange(20, 150, 10), size=reads)
+    x = np.clip(np.rint(rng.normal(theta + s - 300, 50)), 0, np.maximum(theta - 31, 0))
+    room = np.maximum(theta - x, 31)
+    l = np.clip(np.floor(31 + rng.random(reads) * (np.minimum(132, room) - 31 + 1)), 31, 132)
+    pa = np.full(reads, np.nan)
+    has = rng.random(reads) < 0.3
+    pa[has] = np.rint(theta[has])
+    return pd.DataFrame({"x": x.astype(np.int64), "l": l.astype(np.int64), "r": np.full(reads, np.nan), "pa": pa,
+                         "cb_id": np.arange(reads), "read_id": np.arange(reads)})

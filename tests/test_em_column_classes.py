@@ -1,0 +1,539 @@
+"""Every column class of the EM and label kernels against the CPU oracle, K = 0..63.
+
+The E-step kernels are compiled once per column class and the host picks the class from `kmax`, the largest K of a
+scape_hip_batch_em / scape_hip_batch_labels call (scape_hip.hip: LAUNCH_E, LAUNCH_ALL, LAUNCH_LAB; em_lockstep.inc:
+ESTEP_DISPATCH).  Up to 16 columns a job runs the code variant of its exact K + 1; the 24 / 32 / 64-column kernels
+run one generic body with runtime predication for every job of the call.  `kmax` belongs to the CALL, so which
+instantiation a job runs depends on what shares its launch - and its result must not.
+
+LADDER has a K on both sides of every dispatch threshold (tests/test_host.py checks that against the source).  Every
+ladder job is one em_algo call from `Model.init_para(K)` under a seed of its own, run by the oracle non-fixed and
+fixed; the oracle's recorded call is the expectation: alpha, beta and the number of rounds exact, ws / bic / lb_arr to
+the tolerances of the project's other per-call oracle comparisons (ws rtol 1e-6 atol 1e-10, bic rel 1e-9, lb rtol
+1e-9).  Across calls of different classes the same job must return the same BITS.
+
+Measured on an MI355X (printed by every run, not a target): largest deviation from the oracle over all classes ws 7.8e-16
+absolute / 9.6e-15 relative, bic 7.2e-16, lb 9.4e-16 relative; the module takes about 35 s, 12 s of it the oracle.
+"""
+import copy
+import os
+import time
+
+import numpy as np
+import pandas as pd
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+LADDER = (1, 2, 3, 4, 5, 7, 8, 9, 11, 12, 13, 14, 15, 16, 17, 23, 24, 25, 30, 31, 32, 33, 47, 62, 63)
+MIXED_CAPS = (16, 23, 31, 33, 63)            # kmax of the mixed calls: classes 24, 24, 32, 64, 64
+FIXED_CAPS = (3, 7, 11, 15, 23, 31, 63)      # kmax of the calls with only fixed jobs: one per k2_estep_all_rounds class
+N_INIT = (2, 1, 1)                           # inits per K on the many-site, the ordinary and the one-bin UTR
+SEED = 20261016
+# (u, K, init) -> how many seeds further its init is drawn.  An init may only be replaced when the oracle's own
+# arg-max or stopping rule is decided inside the rounding the project allows between the two marginal tensors
+# (at most 1 ladder job in 20; K = 15, 16, 23, 24, 31, 32, 63 keep a non-fixed and a fixed job each).  None was needed.
+RESEED = {}
+
+
+def _e_class(kmax):
+    return next(c for c in (4, 8, 12, 16, 24, 32, 64) if kmax + 1 <= c)
+
+
+class _Dev:
+    """Largest deviations from the oracle seen per (kernel family, column class) - a measurement, printed."""
+
+    def __init__(self):
+        self.tab = {}
+
+    def add(self, key, got_ws, want_ws, got_bic, want_bic, got_lb, want_lb):
+        d = self.tab.setdefault(key, [0.0, 0.0, 0.0, 0.0, 0])
+        d[0] = max(d[0], float(np.max(np.abs(got_ws - want_ws))))
+        big = want_ws >= 1e-4
+        if big.any():
+            d[1] = max(d[1], float(np.max(np.abs(got_ws[big] - want_ws[big]) / want_ws[big])))
+        d[2] = max(d[2], abs(got_bic - want_bic) / abs(want_bic))
+        if len(got_lb) == len(want_lb) and len(want_lb):
+            d[3] = max(d[3], float(np.max(np.abs(got_lb - want_lb) / np.abs(want_lb))))
+        d[4] += 1
+
+    def show(self, title):
+        print(f"\n[{title}] largest deviation from the oracle per (kernel, column class): "
+              "ws abs | ws rel (ws >= 1e-4) | bic rel | lb rel | jobs")
+        for key in sorted(self.tab, key=str):
+            d = self.tab[key]
+            print(f"  {key[0]:<22s} <{key[1]:>2d}>  {d[0]:.2e} | {d[1]:.2e} | {d[2]:.2e} | {d[3]:.2e} | {d[4]}")
+
+
+class _LJob:
+    """One ladder job: an init, and the oracle's non-fixed and fixed em_algo calls from it."""
+
+    def __init__(self, u, K, init, prep, rec_nf, rec_fx):
+        self.u, self.K, self.init, self.prep = u, K, init, prep
+        self.rec = {False: rec_nf, True: rec_fx}
+        a0, b0 = rec_fx["a0"], rec_fx["b0"]
+        self.a_idx = np.searchsorted(prep.theta, a0).astype(np.int32)
+        self.b_idx = np.searchsorted(prep.betas, b0).astype(np.int32)
+        assert np.array_equal(prep.theta[self.a_idx], a0) and np.array_equal(prep.betas[self.b_idx], b0)
+
+    @property
+    def tag(self):
+        return (self.u, self.K, self.init)
+
+    def job(self, fixed):
+        from scape_amd.engine import _Job
+        rec = self.rec[fixed]
+        assert rec is not None, (self.tag, fixed)
+        return _Job(self.u, self.K, fixed, self.a_idx, self.b_idx, rec["w0"], rec["k_arr"].astype(np.int8))
+
+
+def _one_bin_df():
+    n = 120
+    return pd.DataFrame({"x": np.full(n, 400, np.int64), "l": np.full(n, 98, np.int64), "r": np.full(n, np.nan),
+                         "pa": np.full(n, np.nan), "cb_id": np.arange(n), "read_id": np.arange(n)})
+
+
+def _oracle_model(oracle, df, **kw):
+    """The Model subsample_run builds (apa_core.py:994-997), tensors included."""
+    x, l = df["x"].values, df["l"].values
+    m = oracle.Model(x, l, df["r"].values, df["pa"].values, utr_length=max(np.max(x) + np.max(l) + 50, -1), **kw)
+    m.build()
+    return m
+
+
+def _bits(pj, out, i):
+    ao, bo, wo, bic, nlb, lb = out
+    K, n = int(pj.jk[i]), int(nlb[i])
+    return (ao[i, :K].tobytes(), bo[i, :K].tobytes(), wo[i, :K + 1].tobytes(), bic[i].tobytes(), n, lb[i, :n].tobytes())
+
+
+def _bits_differ(a, b):
+    d = [name for name, x, y in zip(("alpha", "beta", "ws", "bic", "n_lb", "lb"), a, b) if x != y]
+    if "bic" in d:
+        d.append(tuple(float(np.frombuffer(x[3])[0]).hex() for x in (a, b)))
+    return d
+
+
+def _vs_oracle(q, pj, out, i, rec, dev, key, tag, problems):
+    """Row i of an EM call against the oracle's record of the same call; mismatches are collected, not raised,
+    so that one run shows every job that disagrees."""
+    ao, bo, wo, bic, nlb, lb = out
+    K, n = int(pj.jk[i]), int(nlb[i])
+    assert K == rec["K"]
+    if not (np.all(ao[i, K:] == -1) and np.all(bo[i, K:] == -1) and np.all(wo[i, K + 1:] == 0.0)):
+        problems.append((tag, "padding", ao[i, K:].tolist(), wo[i, K + 1:].tolist()))
+    a, b = ao[i, :K], bo[i, :K]
+    if not (np.all((a >= 0) & (a < q.T)) and np.all((b >= 0) & (b < len(q.betas)))):
+        problems.append((tag, "index out of the grid", a.tolist(), b.tolist()))
+        return
+    w, lbv = wo[i, :K + 1], lb[i, :max(n, 0)]
+    dev.add(key, w, rec["w1"], float(bic[i]), rec["bic"], lbv, rec["lb"])
+    if not np.array_equal(q.theta[a], rec["a1"]):
+        problems.append((tag, "alpha", q.theta[a].tolist(), rec["a1"].tolist()))
+    if not np.array_equal(q.betas[b], rec["b1"]):
+        problems.append((tag, "beta", q.betas[b].tolist(), rec["b1"].tolist()))
+    if n != len(rec["lb"]):
+        problems.append((tag, "rounds", n, len(rec["lb"])))
+    elif not np.allclose(lbv, rec["lb"], rtol=1e-9):
+        problems.append((tag, "lb", float(np.max(np.abs(lbv - rec["lb"]) / np.abs(rec["lb"])))))
+    if not np.allclose(w, rec["w1"], rtol=1e-6, atol=1e-10):
+        problems.append((tag, "ws", float(np.max(np.abs(w - rec["w1"])))))
+    if not float(bic[i]) == pytest.approx(rec["bic"], rel=1e-9):
+        problems.append((tag, "bic", float(bic[i]), rec["bic"]))
+
+
+def _report(problems, what):
+    assert not problems, f"{what}: {len(problems)} mismatches\n" + "\n".join(repr(p) for p in problems[:40])
+
+
+class _Ladder:
+    def __init__(self, oracle):
+        from scape_amd import _lib
+        from scape_amd.engine import HipBatch
+        from scape_amd.host import prepare_utr
+        from scape_amd.synth import many_sites_utr, synth_utr
+        self.t0 = time.time()
+        self.oracle = oracle
+        g, ordinary, _ = synth_utr(0, 400, k_cap=5, base_seed=8100, pa_rate=0.05, r_rate=0.05)
+        self.dfs = [many_sites_utr(n_sites=66, reads=2000, seed=11), ordinary, _one_bin_df()]
+        names = ["syn:SITES66:1:1-9800:+", g, "syn:ONEBIN:1:1-2000:+"]
+        self.preps = [prepare_utr(df, gene_info_str=n) for df, n in zip(self.dfs, names)]
+        self.models = [_oracle_model(oracle, df) for df in self.dfs]
+        for q, m in zip(self.preps, self.models):         # same grids, same bins: a mismatch later is the kernels'
+            assert np.array_equal(q.theta, m.all_theta) and np.array_equal(q.betas, m.betas)
+            assert q.N == m.N and np.array_equal(q.cnt, m.cnt) and q.L == m.L and q.unif_ll == m.unif_ll
+        assert ((~np.isnan(self.preps[1].pa)).any() and (~np.isnan(self.preps[1].r)).any()
+                and self.preps[2].N == 1 and len(self.preps[0].peaks) < 63)
+        self.jobs = []
+        for u, (q, m) in enumerate(zip(self.preps, self.models)):
+            for K in LADDER:
+                for i in range(N_INIT[u]):
+                    np.random.seed((SEED + 100000 * u + 100 * K + i + 10 * RESEED.get((u, K, i), 0)) % 2 ** 32)
+                    p0 = m.init_para(K)
+                    m.em_algo(copy.deepcopy(p0))
+                    m.em_algo(copy.deepcopy(p0), fixed=True)
+                    self.jobs.append(_LJob(u, K, i, q, m.calls[-2], m.calls[-1]))
+        # K = 0: what rm_component leaves when it drops every component (apa_core.py:832-844), fixed inference only
+        m = self.models[0]
+        m.em_algo(oracle.Para(alpha_arr=np.zeros(0), beta_arr=np.zeros(0), ws=np.array([0.15]), K=0), fixed=True)
+        self.k0 = _LJob(0, 0, 0, self.preps[0], None, m.calls[-1])
+        for j in self.jobs + [self.k0]:
+            for rec in j.rec.values():
+                if rec is not None:
+                    assert np.all(np.isfinite(rec["w1"])) and np.isfinite(rec["bic"]) and np.all(np.isfinite(rec["lb"]))
+        self.t_oracle = time.time() - self.t0
+        self.ctx = _lib.Context(0)              # a handle of its own: engines of other tests load theirs into the default one
+        self.batch = HipBatch(self.ctx, self.preps)
+        self.batch.build()
+        self.dev = _Dev()
+        self.cache = {}
+
+    def run(self, pairs):
+        """pairs: [(ladder job, fixed)] in one EM call -> (job tables, outputs)."""
+        from scape_amd.engine import pack_jobs
+        pj = pack_jobs([j.job(fixed) for j, fixed in pairs])
+        return pj, [np.array(x).copy() for x in self.batch.em_packed(pj)]
+
+    def own(self, wide):
+        """Every non-fixed ladder job in the call of its own K (kmax = K), SCAPE_HIP_WIDE_MAXJOBS = wide:
+        {job tag: (job tables, outputs, row)}."""
+        if ("own", wide) not in self.cache:
+            os.environ["SCAPE_HIP_WIDE_MAXJOBS"] = wide
+            try:
+                res = {}
+                for K in LADDER:
+                    js = [j for j in self.jobs if j.K == K]
+                    pj, out = self.run([(j, False) for j in js])
+                    assert pj.kmax == K
+                    for i, j in enumerate(js):
+                        res[j.tag] = (pj, out, i)
+            finally:
+                del os.environ["SCAPE_HIP_WIDE_MAXJOBS"]
+            self.cache[("own", wide)] = res
+        return self.cache[("own", wide)]
+
+    def mixed_pairs(self, cap):
+        pairs = [(j, False) for j in self.jobs if j.K <= cap] + [(j, True) for j in self.jobs if j.K <= cap]
+        return pairs + ([(self.k0, True)] if cap == 63 else [])
+
+    def mixed(self, cap):
+        """Every ladder job with K <= cap, non-fixed and fixed, in ONE call (kmax = cap; the per-round kernels)."""
+        if ("mixed", cap) not in self.cache:
+            pairs = self.mixed_pairs(cap)
+            pj, out = self.run(pairs)
+            assert pj.kmax == cap
+            self.cache[("mixed", cap)] = (pairs, pj, out)
+        return self.cache[("mixed", cap)]
+
+    def close(self):
+        self.batch.free()
+        self.ctx.close()
+
+
+@pytest.fixture(scope="module")
+def ladder(oracle):
+    lad = _Ladder(oracle)
+    yield lad
+    lad.dev.show("module")
+    print(f"[module] oracle share {lad.t_oracle:.1f} s, wall time since the ladder was set up {time.time() - lad.t0:.1f} s")
+    lad.close()
+
+
+# ---------------------------------------------------------------- 1. per call, class chosen by the job's own K
+def test_own_k_calls_vs_oracle(ladder):
+    """One call per ladder K (kmax = K), non-fixed jobs: every k2_estep class with every exact variant (up to 16
+    columns), the generic body at K = 16..63, K = 63 with all 64 lanes holding a column; for kmax <= 15 both with one
+    wavefront per job (k2_estep) and with four (k2_estep_cs) - bit for bit the same."""
+    problems, dev = [], _Dev()
+    narrow, wide = ladder.own("0"), ladder.own("1000000")
+    for j in ladder.jobs:
+        for name, res in (("k2_estep", narrow), ("k2_estep_cs", wide)):
+            if name == "k2_estep_cs" and j.K > 15:
+                continue
+            pj, out, i = res[j.tag]
+            for d in (dev, ladder.dev):
+                _vs_oracle(j.prep, pj, out, i, j.rec[False], d, (name, _e_class(j.K)), (name,) + j.tag, problems if d is dev else [])
+        d = _bits_differ(_bits(*narrow[j.tag]), _bits(*wide[j.tag]))
+        if d:
+            problems.append((j.tag, "k2_estep and k2_estep_cs bits differ", d))
+    dev.show("own-K calls")
+    _report(problems, "own-K calls")
+    assert set(dev.tab) == {("k2_estep", c) for c in (4, 8, 12, 16, 24, 32, 64)} | {("k2_estep_cs", c) for c in (4, 8, 12, 16)}
+
+
+# ---------------------------------------------------------------- 2. generic body with small K
+@pytest.mark.parametrize("cap", MIXED_CAPS)
+def test_mixed_calls_vs_oracle_and_own_k_bits(ladder, cap):
+    """Every ladder job with K <= cap, non-fixed and fixed, in one call of kmax = cap: jobs of K = 1.. run the generic
+    body of the 24 / 32 / 64-column kernels.  Each job meets the oracle and returns the bits of its own-K call."""
+    problems, dev = [], _Dev()
+    pairs, pj, out = ladder.mixed(cap)
+    own = ladder.own("0")
+    seen = ladder.cache.setdefault("fixed_bits", {})
+    for i, (j, fixed) in enumerate(pairs):
+        tag = (f"kmax={cap}", "fixed" if fixed else "non-fixed") + j.tag
+        key = ("mixed call, fixed" if fixed else "mixed call, non-fixed", _e_class(cap))
+        for d in (dev, ladder.dev):
+            _vs_oracle(j.prep, pj, out, i, j.rec[fixed], d, key, tag, problems if d is dev else [])
+        mine = _bits(pj, out, i)
+        if fixed:
+            first = seen.setdefault(j.tag, (cap, mine))
+            if _bits_differ(first[1], mine):
+                problems.append((tag, f"fixed job: bits differ from the kmax={first[0]} call", _bits_differ(first[1], mine)))
+        else:
+            d = _bits_differ(_bits(*own[j.tag]), mine)
+            if d:
+                problems.append((tag, "bits differ from the own-K call", d))
+    dev.show(f"mixed call kmax={cap}")
+    _report(problems, f"mixed call kmax={cap}")
+    assert sum(1 for j, f in pairs if not f and j.K <= 15) >= 50      # small K inside a wide call
+
+
+# ---------------------------------------------------------------- 3. only fixed jobs
+@pytest.mark.parametrize("cap", FIXED_CAPS)
+def test_fixed_only_calls_vs_oracle_and_mixed_bits(ladder, cap):
+    """Calls with only fixed jobs run all rounds in one launch (k2_estep_all_rounds), one call per column class with
+    the fixed ladder jobs that fit - K = 0 too in the 64-column call; against the oracle's fixed calls, and bit-equal
+    to the same jobs in the mixed kmax = 63 call, where they go through the per-round kernels."""
+    problems, dev = [], _Dev()
+    js = [j for j in ladder.jobs if j.K <= cap] + ([ladder.k0] if cap == 63 else [])
+    pj, out = ladder.run([(j, True) for j in js])
+    assert pj.kmax == cap and np.all(pj.jf == 1)
+    mpairs, mpj, mout = ladder.mixed(63)
+    row = {j.tag: i for i, (j, fixed) in enumerate(mpairs) if fixed}
+    for i, j in enumerate(js):
+        tag = (f"fixed only, kmax={cap}",) + j.tag
+        for d in (dev, ladder.dev):
+            _vs_oracle(j.prep, pj, out, i, j.rec[True], d, ("k2_estep_all_rounds", _e_class(cap)), tag, problems if d is dev else [])
+        d = _bits_differ(_bits(mpj, mout, row[j.tag]), _bits(pj, out, i))
+        if d:
+            problems.append((tag, "bits differ from the mixed kmax=63 call", d))
+    dev.show(f"fixed-only call kmax={cap}")
+    _report(problems, f"fixed-only call kmax={cap}")
+    if cap == 63:
+        i = len(js) - 1
+        assert pj.jk[i] == 0 and out[4][i] == len(ladder.k0.rec[True]["lb"]) >= 2
+
+
+# ---------------------------------------------------------------- 4. M-step kernels
+def test_mstep_kernels_identical_bits_up_to_k63(ladder, monkeypatch):
+    """The mixed kmax = 63 call under every M-step kernel (k2_mstep, k3_mstep, the default) with a tile's jobs kept
+    together and cut into passes for several workgroups: the same bits (test_mstep_kernels_give_identical_bits stops
+    at K = 10, test_small_call_shapes_give_identical_bits at K = 14)."""
+    from scape_amd.engine import pack_jobs
+    pairs = ladder.mixed_pairs(63)
+    pj = pack_jobs([j.job(fixed) for j, fixed in pairs])
+    got = {}
+    for mode in ("v2", "v3", None):
+        for split in ("0", "1000000"):
+            if mode is None:
+                monkeypatch.delenv("SCAPE_HIP_MSTEP", raising=False)
+            else:
+                monkeypatch.setenv("SCAPE_HIP_MSTEP", mode)
+            monkeypatch.setenv("SCAPE_HIP_SPLIT_MAXTILES", split)
+            out = [np.array(x).copy() for x in ladder.batch.em_packed(pj)]
+            got[(mode, split)] = [_bits(pj, out, i) for i in range(len(pairs))]
+    monkeypatch.delenv("SCAPE_HIP_MSTEP", raising=False)
+    monkeypatch.delenv("SCAPE_HIP_SPLIT_MAXTILES", raising=False)
+    ref = got[("v2", "0")]
+    _p, mpj, mout = ladder.mixed(63)
+    got[("default knobs", "")] = [_bits(mpj, mout, i) for i in range(len(pairs))]
+    problems = []
+    for key, rows in got.items():
+        for (j, fixed), a, b in zip(pairs, ref, rows):
+            if _bits_differ(a, b):
+                problems.append((key, fixed) + j.tag + (_bits_differ(a, b),))
+    _report(problems, "M-step kernels")
+
+
+# ---------------------------------------------------------------- 5. labels
+def _want_labels(model, q, K, a_idx, b_idx, ws):
+    from oracle.scape_oracle import Para
+    return model.labels(Para(alpha_arr=q.theta[a_idx], beta_arr=q.betas[b_idx], ws=np.asarray(ws, dtype=np.float64), K=K))
+
+
+def test_labels_every_class_vs_oracle(ladder):
+    """get_label for every fitted model of the own-K calls against the oracle, exact: alone (kmax = K: k_labels<8>,
+    <16>, <32>, <64> by the model's own K) and as one of three models of different K in a table padded to kmax = 63
+    (k_labels<64> with padding columns).  One call labels at most one model per UTR (the output is one label per bin of
+    the batch), so "together" means the three UTRs' models, paired so that small and large K share a call."""
+    from scape_amd.engine import HipBatch
+    own = ladder.own("0")
+    fits = {j.tag: HipBatch.fit_at(*own[j.tag]) for j in ladder.jobs}
+    want = {j.tag: _want_labels(ladder.models[j.u], j.prep, j.K, fits[j.tag].a_idx, fits[j.tag].b_idx, fits[j.tag].ws)
+            for j in ladder.jobs}
+    problems, classes = [], set()
+    for j in ladder.jobs:                                           # alone, kmax = K
+        got = ladder.batch.labels([(j.u, fits[j.tag])])[j.u]
+        classes.add(next(c for c in (8, 16, 32, 64) if j.K + 1 <= c))
+        if not np.array_equal(got, want[j.tag]):
+            problems.append(("alone",) + j.tag + (int((got != want[j.tag]).sum()),))
+    by = {(j.u, j.init): [x for x in ladder.jobs if x.u == j.u and x.init == j.init] for j in ladder.jobs}
+    n, off = len(LADDER), ladder.batch.bin_off
+    for s in range(n):                                              # three models per call, table pitch 63
+        for trio in ([by[(0, 0)][s], by[(1, 0)][n - 1 - s], by[(2, 0)][(s + 7) % n]], [by[(0, 1)][s]]):
+            a, b, w = np.zeros((len(trio), 63), np.int32), np.zeros((len(trio), 63), np.int32), np.zeros((len(trio), 64))
+            for i, j in enumerate(trio):
+                f = fits[j.tag]
+                a[i, :j.K], b[i, :j.K], w[i, :j.K + 1] = f.a_idx, f.b_idx, f.ws
+            flat = ladder.batch.labels_packed([j.u for j in trio], [j.K for j in trio], a, b, w)
+            for j in trio:
+                got = flat[off[j.u]:off[j.u + 1]]
+                if not np.array_equal(got, want[j.tag]):
+                    problems.append(("padded to kmax=63",) + j.tag + (int((got != want[j.tag]).sum()),))
+            rest = np.ones(len(flat), bool)
+            for j in trio:
+                rest[off[j.u]:off[j.u + 1]] = False
+            assert np.all(flat[rest] == -1)                         # bins of UTRs without a model are not written
+    _report(problems, "labels")
+    assert classes == {8, 16, 32, 64}
+    assert max(int(want[j.tag].max()) for j in ladder.jobs if j.K == 63) > 31      # high columns do win bins
+
+
+def test_labels_k0_and_ties_vs_oracle(ladder):
+    """K = 0 (every bin goes to the uniform column) in a one-column and in a 63-column table; two components on the
+    same (alpha, beta) with equal weights, and a component of weight exactly 0: the first maximum wins, as in
+    np.argmax (apa_core.py:880)."""
+    from scape_amd.engine import Fit
+    b, off = ladder.batch, ladder.batch.bin_off
+    k0 = Fit(K=0, a_idx=np.zeros(0, np.int32), b_idx=np.zeros(0, np.int32), ws=np.array([0.15]), bic=0.0, lb=np.zeros(0))
+    for u in range(3):
+        assert np.all(b.labels([(u, k0)])[u] == 0)
+        flat = b.labels_packed([u], [0], np.zeros((1, 63), np.int32), np.zeros((1, 63), np.int32), np.eye(1, 64) * 0.15)
+        assert np.all(flat[off[u]:off[u + 1]] == 0)
+        assert np.array_equal(ladder.models[u].labels(ladder.oracle.Para(np.zeros(0), np.zeros(0), np.array([0.15]), 0)),
+                              np.zeros(ladder.preps[u].N, np.int64))
+    for u in (0, 1):
+        q, m = ladder.preps[u], ladder.models[u]
+        mid = int(np.searchsorted(q.theta, np.median(q.x) + 250))
+        cases = [
+            (np.array([mid, mid], np.int32), np.array([3, 3], np.int32), np.array([0.4, 0.4, 0.2])),            # tie: column 0 wins
+            (np.array([mid - 9, mid, mid], np.int32), np.array([2, 4, 4], np.int32), np.array([0.2, 0.35, 0.35, 0.1])),
+            (np.array([mid, mid + 6], np.int32), np.array([3, 3], np.int32), np.array([0.0, 0.8, 0.2])),          # weight exactly 0
+            (np.array([mid, mid + 6], np.int32), np.array([3, 3], np.int32), np.array([0.85, 0.0, 0.15])),
+        ]
+        for a, bb, w in cases:
+            K = len(a)
+            want = _want_labels(m, q, K, a, bb, w)
+            got = b.labels([(u, Fit(K=K, a_idx=a, b_idx=bb, ws=w, bic=0.0, lb=np.zeros(0)))])[u]
+            assert np.array_equal(got, want), (u, a, w, int((got != want).sum()))
+            pa, pb, pw = np.zeros((1, 63), np.int32), np.zeros((1, 63), np.int32), np.zeros((1, 64))
+            pa[0, :K], pb[0, :K], pw[0, :K + 1] = a, bb, w
+            assert np.array_equal(b.labels_packed([u], [K], pa, pb, pw)[off[u]:off[u + 1]], want), (u, a, w, "kmax=63")
+        tie = _want_labels(m, q, 2, *cases[0])
+        assert not np.any(tie == 1) and np.any(tie == 0)            # the tie is there, and its first column took it
+        zero = _want_labels(m, q, 2, *cases[2])
+        assert not np.any(zero == 0) and np.any(zero == 1)
+
+
+# ---------------------------------------------------------------- 6. limits
+def test_kmax_limits(ladder):
+    """kmax = 63 is accepted, kmax = 64 refused by both entry points, a job with K > kmax refused; the handle works
+    afterwards."""
+    from scape_amd import _lib
+    from scape_amd.engine import PackedJobs
+    assert _lib.MAX_K == 63
+    b = ladder.batch
+
+    def table(kmax, K):
+        a = (np.arange(kmax, dtype=np.int32) % ladder.preps[0].T).reshape(1, kmax)
+        a.sort(axis=1)
+        w = np.full((1, kmax + 1), 1.0 / (kmax + 1))
+        return PackedJobs(np.zeros(1, np.int32), np.array([K], np.int32), np.zeros(1, np.int32), a,
+                          np.zeros((1, kmax), np.int32), w, np.zeros((1, 50), np.int8))
+    top = next(j for j in ladder.jobs if j.K == 63)
+    pj, out = ladder.run([(top, False)])
+    assert pj.kmax == 63 and not _bits_differ(_bits(pj, out, 0), _bits(*ladder.own("0")[top.tag]))
+    with pytest.raises(_lib.ScapeHipError, match="kmax out of range"):
+        b.em_packed(table(64, 63))
+    with pytest.raises(_lib.ScapeHipError, match="kmax out of range"):
+        b.em_packed(table(64, 64))
+    with pytest.raises(_lib.ScapeHipError, match="K out of range"):
+        b.em_packed(table(2, 3))
+    t63, t64 = table(63, 63), table(64, 64)
+    flat = b.labels_packed([0], [63], t63.a, t63.b, t63.w)
+    assert flat[:b.bin_off[1]].min() >= 0 and flat[:b.bin_off[1]].max() <= 63
+    with pytest.raises(_lib.ScapeHipError, match="kmax out of range"):
+        b.labels_packed([0], [64], t64.a, t64.b, t64.w)
+    with pytest.raises(_lib.ScapeHipError, match="kmax out of range"):
+        b.labels_packed([0], [3], t64.a, t64.b, t64.w)
+    t2 = table(2, 2)
+    with pytest.raises(_lib.ScapeHipError, match="K out of range"):
+        b.labels_packed([0], [3], t2.a, t2.b, t2.w)
+    j = ladder.jobs[0]
+    pj, again = ladder.run([(j, False)])                            # the handle is usable afterwards
+    assert not _bits_differ(_bits(pj, again, 0), _bits(*ladder.own("0")[j.tag]))
+
+
+# ---------------------------------------------------------------- 7. product path
+def _oracle_fit(oracle, df, gene, seed, **kw):
+    np.random.seed(seed)
+    res, model = oracle.subsample_run(df["x"].values, df["l"].values, df["r"].values, df["pa"].values, re_run_mode=True, **kw)
+    out = dict(gene=gene, K=int(res.K), alpha=np.asarray(res.alpha_arr), beta=np.asarray(res.beta_arr), ws=np.asarray(res.ws),
+               bic=float(res.bic), lb=np.asarray(res.lb_arr, dtype=np.float64), labels=np.asarray(res.label_arr))
+    return out, model
+
+
+def test_product_sweep_20_to_1_vs_oracle(oracle):
+    """n_max_apa = 20, n_min_apa = 1 with the default min_ws on a UTR with 12 well separated sites: the K = 20..1 sweep
+    is ONE call in the 24-column class (K = 1 next to K = 20), the BIC winner is pruned and re-fitted with a kept K of 10
+    or more (k2_estep_all_rounds<12> or <16>); all final fields against the oracle."""
+    from test_gpu_parity import _assert_parameters_equal_oracle
+    from scape_amd.apa_core import to_parameters
+    from scape_amd.engine import Engine
+    from scape_amd.host import prepare_utr
+    from scape_amd.synth import many_sites_utr
+    df, gene, kw = many_sites_utr(n_sites=12, reads=2000, seed=21, gap=300), "syn:SWEEP20:1:1-4200:+", dict(n_max_apa=20, n_min_apa=1)
+    want, model = _oracle_fit(oracle, df, gene, 3, **kw)
+    assert [c["K"] for c in model.calls[:200:10]] == list(range(20, 0, -1))
+    assert any(c["fixed"] and c["K"] >= 10 for c in model.calls[200:])
+    res = Engine(device=0).run([prepare_utr(df, gene_info_str=gene, **kw)], rng_mode="per_utr", seed=3, re_run_mode=True)
+    assert res[0].n_jobs == len(model.calls)
+    _assert_parameters_equal_oracle([to_parameters(res[0])], [want])
+
+
+def test_product_rerun_loop_crosses_16_to_24_columns_vs_oracle(oracle):
+    """n_max_apa = n_min_apa = 15 and min_ws = 0 on a UTR with 19 sites (the device of
+    test_rerun_loop_beyond_31_components_vs_oracle): the first sweep is K = 15 alone (16-column class, variant
+    estep_body<16, 16>), the re-run loop goes on with K = 17, 16, 15 in the 24-column class.  Every em_algo call and the
+    final Parameters against the oracle."""
+    from test_gpu_parity import _assert_parameters_equal_oracle
+    from scape_amd.apa_core import to_parameters
+    from scape_amd.engine import Engine
+    from scape_amd.host import prepare_utr
+    from scape_amd.synth import many_sites_utr
+    df, gene = many_sites_utr(n_sites=19, reads=1200, seed=23), "syn:RERUN15:1:1-3300:+"
+    kw = dict(n_max_apa=15, n_min_apa=15, min_ws=0.0)
+    want, model = _oracle_fit(oracle, df, gene, 3, **kw)
+    assert [c["K"] for c in model.calls[:40:10]] == [15, 17, 16, 15]
+    eng = Engine(device=0)
+    res = eng.run([prepare_utr(df, gene_info_str=gene, **kw)], rng_mode="per_utr", seed=3, re_run_mode=True, keep_trace=True)[0]
+    assert len(eng.traces[0]) == len(model.calls)
+    q = res.prep
+    for n, (ft, rc) in enumerate(zip(eng.traces[0], model.calls)):
+        assert ft.K == rc["K"]
+        assert np.array_equal(q.theta[ft.a_idx], rc["a1"]) and np.array_equal(q.betas[ft.b_idx], rc["b1"]), (n, rc["K"])
+        assert len(ft.lb) == len(rc["lb"]) and np.allclose(ft.ws, rc["w1"], rtol=1e-6, atol=1e-10), (n, rc["K"])
+    _assert_parameters_equal_oracle([to_parameters(res)], [want])
+
+
+def test_product_results_do_not_depend_on_the_waves_kmax():
+    """Three UTRs with n_max_apa = 3, 12 and 20 in one run share one main call of kmax = 20 (24-column class, generic
+    body); alone their calls run the 4-, 16- and 24-column classes.  Each result is bit-equal to the run alone."""
+    from scape_amd.engine import Engine
+    from scape_amd.host import prepare_utr
+    from scape_amd.synth import synth_utr
+    preps = []
+    for i, n_max in enumerate((3, 12, 20)):
+        g, df, _ = synth_utr(i, 500, k_cap=5, base_seed=8200)
+        preps.append(prepare_utr(df, gene_info_str=g, n_max_apa=n_max, n_min_apa=1))
+    eng = Engine(device=0)
+    seeds = [41, 42, 43]
+    together = eng.run(preps, rng_mode="per_utr", seeds=seeds, re_run_mode=True)
+    for i, q in enumerate(preps):
+        alone = eng.run([q], rng_mode="per_utr", seeds=seeds[i:i + 1], re_run_mode=True)[0]
+        a, b = together[i], alone
+        assert a.n_jobs == b.n_jobs and a.fit.K == b.fit.K and a.fit.bic == b.fit.bic, (i, a.fit.K, b.fit.K)
+        for x, y in ((a.fit.a_idx, b.fit.a_idx), (a.fit.b_idx, b.fit.b_idx), (a.fit.ws, b.fit.ws), (a.fit.lb, b.fit.lb),
+                     (a.labels_bin, b.labels_bin)):
+            assert np.array_equal(x, y), i

@@ -954,23 +954,6 @@ def test_infer_pa_all_then_merge_pa_vs_reference(tmp_path):
     _chain_check(tmp_path, f)
 
 
-def _many_sites_utr(n_sites=34, reads=3000, seed=5, gap=140, beta=8.0):
-    """A UTR with more true pA sites than the old K <= 31 limit of the kernels (inputs only)."""
-    rng = np.random.default_rng(seed)
-    alphas = 400 + gap * np.arange(n_sites)
-    comp = rng.integers(0, n_sites, reads)
-    theta = rng.normal(alphas[comp], beta)
-    s = rng.choice(np.arange(20, 150, 10), size=reads)
-    x = np.clip(np.rint(rng.normal(theta + s - 300, 50)), 0, np.maximum(theta - 31, 0))
-    room = np.maximum(theta - x, 31)
-    l = np.clip(np.floor(31 + rng.random(reads) * (np.minimum(132, room) - 31 + 1)), 31, 132)
-    pa = np.full(reads, np.nan)
-    has = rng.random(reads) < 0.3
-    pa[has] = np.rint(theta[has])
-    return pd.DataFrame({"x": x.astype(np.int64), "l": l.astype(np.int64), "r": np.full(reads, np.nan), "pa": pa,
-                         "cb_id": np.arange(reads), "read_id": np.arange(reads)})
-
-
 def test_rerun_loop_beyond_31_components_vs_oracle(oracle):
     """The reference's re-run loop has no K cap (apa_core.py:1023-1030: n_max_apa += 2 while K == n_max_apa).  A UTR
     with 34 true sites, n_max_apa = n_min_apa = 31 and min_ws = 0 (nothing pruned) ends its first sweep at K = 31 = n_max
@@ -979,7 +962,8 @@ def test_rerun_loop_beyond_31_components_vs_oracle(oracle):
     from scape_amd.apa_core import to_parameters
     from scape_amd.engine import Engine
     from scape_amd.host import prepare_utr
-    df = _many_sites_utr()
+    from scape_amd.synth import many_sites_utr
+    df = many_sites_utr()
     kw = dict(n_max_apa=31, n_min_apa=31, min_ws=0.0)
     prep = prepare_utr(df, gene_info_str="syn:K33:1:1-5500:+", **kw)
     eng = Engine(device=0)

@@ -523,3 +523,36 @@ def test_find_peaks_equals_scipy():
             got = find_peaks(x, d)[0]
             assert np.array_equal(got, want), (x.tolist(), d, got, want)
     assert len(find_peaks(np.array([1.0, 2.0]), 5)[0]) == 0
+
+
+def test_column_class_ladder_covers_every_dispatch_threshold():
+    """tests/test_em_column_classes.py runs the EM and label kernels at the K values of its LADDER.  The column classes
+    are read here from the launch lines of scape_hip.hip: every class boundary (kmax + 1 <= C) must have its last K
+    (C - 1) and the first K of the next class (C) on the ladder, and so must SCAPE_MAX_K - whoever adds a class has
+    to extend the ladder."""
+    from test_em_column_classes import FIXED_CAPS, LADDER, MIXED_CAPS
+    src = open(os.path.join(ROOT, "scape_amd", "csrc", "scape_hip.hip")).read()
+    hdr = open(os.path.join(ROOT, "include", "scape_hip.h")).read()
+    max_k = int(re.search(r"#define\s+SCAPE_MAX_K\s+(\d+)", hdr).group(1))
+    fam = {
+        "k2_estep": [int(c) for c in re.findall(r"LAUNCH_E\(k2_estep,\s*(\d+),", src)],
+        "k2_estep_cs": [int(c) for c in re.findall(r"LAUNCH_E\(k2_estep_cs,\s*(\d+),", src)],
+        "k2_estep_all_rounds": [int(c) for c in re.findall(r"LAUNCH_ALL\((\d+)\)", src)],
+        "k_labels": [int(c) for c in re.findall(r"LAUNCH_LAB\((\d+)\)", src)],
+    }
+    assert len(re.findall(r"LAUNCH_(?:E|ALL|LAB)\([^)]*\d+[^)]*\)", src)) == sum(len(v) for v in fam.values())
+    wide_cap = int(re.search(r"const bool wide = .*kmax \+ 1 <= (\d+);", src).group(1))
+    assert max_k in LADDER and max(LADDER) == max_k and min(LADDER) == 1
+    for name, classes in fam.items():
+        assert len(classes) >= 4 and classes == sorted(set(classes)), (name, classes)
+        top = wide_cap if name == "k2_estep_cs" else max_k + 1
+        assert classes[-1] == top, (name, classes)          # the largest class holds the family's largest kmax
+        for c in classes[:-1] + ([top] if top <= max_k else []):
+            assert c - 1 in LADDER and c in LADDER, (name, c, "no K on both sides of kmax + 1 <= %d" % c)
+    # calls with only fixed jobs: one kmax per class of k2_estep_all_rounds; mixed calls: the generic-body classes
+    e = fam["k2_estep_all_rounds"]
+    cls = lambda kmax: next(c for c in e if kmax + 1 <= c)      # noqa: E731
+    assert sorted(cls(k) for k in FIXED_CAPS) == e and all(k in LADDER for k in FIXED_CAPS + MIXED_CAPS)
+    generic = [c for c in fam["k2_estep"] if c > 16]            # ESTEP_DISPATCH: exact variants up to 16 columns
+    assert "if constexpr (CM <= 16)" in open(os.path.join(ROOT, "scape_amd", "csrc", "em_lockstep.inc")).read()
+    assert {cls(k) for k in MIXED_CAPS} == set(generic) and max_k in MIXED_CAPS
