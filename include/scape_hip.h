@@ -192,6 +192,13 @@ int scape_hip_report_render(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, co
    *bytes_out = the block's text bytes, *nnz_out = its entries; the rest as scape_hip_report_render. */
 int scape_hip_report_render_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, const int64_t *rows, int64_t row_no0,
                                 int64_t *bytes_out, int64_t *nnz_out);
+/* Pseudo-bulk sums of the last counts call (ex_pa_pseudobulk): segment s is the columns [seg_off[s], seg_off[s+1]) of
+   the count matrix, 0 <= seg_off[0] <= ... <= seg_off[n_seg] <= n_cols (the caller passes scape_hip_report_counts an
+   id2col that puts every sample's columns side by side).  For row i (count row rows[i]) and segment s,
+   sum_out[i * n_seg + s] is the sum of the counts and nz_out[i * n_seg + s] the number of counts above 0.  Returns
+   once both arrays are on the host. */
+int scape_hip_report_group_sums(scape_hip_ctx *ctx, int32_t n_seg, const int32_t *seg_off, int32_t n_rows,
+                                const int64_t *rows, int32_t *sum_out, int32_t *nz_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

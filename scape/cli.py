@@ -1,11 +1,12 @@
-"""click group exposing ``infer_pa``, its consumer ``merge_pa`` and the two stages after it, ``cal_exp_pa_len`` and
-``ex_pa_cnt_mat`` (reference cli.py:7-31 registers six commands; ``gen_utr_annotation`` and ``prepare_input`` are
-outside this build's scope)."""
+"""click group exposing ``infer_pa``, its consumer ``merge_pa`` and the stages after it, ``cal_exp_pa_len``,
+``ex_pa_cnt_mat`` and ``ex_pa_pseudobulk`` (the sums the reference's DEXSeq script starts from; reference cli.py:7-31
+registers six commands; ``gen_utr_annotation`` and ``prepare_input`` are outside this build's scope, SURVEY.md
+section 8)."""
 import click
 
 from scape_amd.apa_core import infer_pa, infer_pa_all, prebin
 from scape_amd.junction_handler import merge_pa
-from scape_amd.report import cal_exp_pa_len, ex_pa_cnt_mat
+from scape_amd.report import cal_exp_pa_len, ex_pa_cnt_mat, ex_pa_pseudobulk
 
 
 @click.group()
@@ -26,3 +27,4 @@ cli.add_command(merge_pa)
 cli.add_command(prebin)
 cli.add_command(cal_exp_pa_len)
 cli.add_command(ex_pa_cnt_mat)
+cli.add_command(ex_pa_pseudobulk)

@@ -66,6 +66,7 @@ SIGNATURES = {
                                       P_i64, P_i8, P_i64]),
     "scape_hip_report_render": (c_i, [P_void, c_i32, c_i32, P_i64, P_i8, P_i64, ctypes.c_char_p, P_i64]),
     "scape_hip_report_render_mtx": (c_i, [P_void, c_i32, c_i32, P_i64, c_i64, P_i64, P_i64]),
+    "scape_hip_report_group_sums": (c_i, [P_void, c_i32, P_i32, c_i32, P_i64, P_i32, P_i32]),
     "scape_hip_report_fetch": (c_i, [P_void, c_i32, ctypes.POINTER(P_void), P_i64]),
     "scape_hip_report_hist": (c_i, [P_void, c_i32, P_i64, P_i32, P_i64, P_i64, c_i64, c_i64, P_i32, c_i32,
                                     P_i64, P_i64]),

@@ -20,6 +20,9 @@
 //                   per record, the bitmap of cluster codes present, its compaction to the record's groups and the
 //                   (group, label) histogram; labels >= K share the last slot (they decide whether a group exists and
 //                   whether it has reads, never the weights)
+//   k_rep_segsum    ex_pa_pseudobulk: per count row, the sum and the number of nonzero counts of every column segment
+//                   (the host permutes the columns so that each pseudo-bulk sample is one contiguous segment); one wave
+//                   per segment, no atomics
 // Cluster names, their order and the floating-point finish of exp_pa_len stay on the host (scape_amd/report.py).
 
 #define REP_THREADS 256
@@ -36,6 +39,8 @@ struct ReportState {
     DevBuf h_bits, h_wpre, h_nloc, h_goff, h_hoff, h_codes, h_hist;
     std::vector<int64_t> goff, hoff;   // host side of h_goff / h_hoff: alive until the queued copies have run
     int64_t h_groups = 0, h_hist_n = 0;
+    // segment sums of the last scape_hip_report_group_sums call
+    DevBuf g_rows, g_off, g_sum, g_nz;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
@@ -59,7 +64,7 @@ static void report_release(scape_hip_ctx *c) {
                      &s->h_hist, &s->s_rows[0], &s->s_rows[1], &s->s_int[0], &s->s_int[1], &s->s_poff[0],
                      &s->s_poff[1], &s->s_pre[0], &s->s_pre[1], &s->s_len[0], &s->s_len[1], &s->s_roff[0],
                      &s->s_roff[1], &s->s_out[0], &s->s_out[1], &s->s_nnz[0], &s->s_nnz[1], &s->s_noff[0],
-                     &s->s_noff[1]};
+                     &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;
@@ -352,6 +357,37 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_mtx_render(const int64_t *_
     }
 }
 
+// ---- segment sums (pseudo-bulk) ---------------------------------------------------------------------------------------
+// one workgroup per row i (count row rows[i] of the last counts call); segment s is the columns [seg_off[s], seg_off[s+1]).
+// Wave w takes segments w, w + REP_WAVES, ...: its lanes stride the segment, then the wave adds up.  sum / nz are
+// [row][segment]; a row's sum fits 32 bits because a record holds at most INT32_MAX reads
+__global__ __launch_bounds__(REP_THREADS) void k_rep_segsum(const int64_t *__restrict__ rows, int32_t n_cols,
+                                                            const int32_t *__restrict__ cnt, int32_t n_seg,
+                                                            const int32_t *__restrict__ seg_off,
+                                                            int32_t *__restrict__ sum, int32_t *__restrict__ nz) {
+    const int i = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int32_t *row = cnt + rows[i] * n_cols;
+    int32_t *so = sum + (int64_t)i * n_seg, *zo = nz + (int64_t)i * n_seg;
+    for (int s = w; s < n_seg; s += REP_WAVES) {
+        const int a = seg_off[s], b = seg_off[s + 1];
+        int t = 0, z = 0;
+#pragma unroll 4
+        for (int c = a + lane; c < b; c += 64) {
+            const int v = row[c];
+            t += v;
+            z += v > 0;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            t += __shfl_xor(t, o, 64);
+            z += __shfl_xor(z, o, 64);
+        }
+        if (lane == 0) {
+            so[s] = t;
+            zo[s] = z;
+        }
+    }
+}
+
 // ---- cluster histograms ---------------------------------------------------------------------------------------------
 // one workgroup per record: bit `code` of the record's bitmap for every read; id2code == nullptr: one group (code 0).
 // err[0] = first read whose barcode id has no code, err[1] = first read with a negative label
@@ -626,6 +662,33 @@ int scape_hip_report_render_mtx(scape_hip_ctx *c, int32_t slot, int32_t n_rows, 
     if (rep_slot_queue(c, s, slot, total)) return 1;
     *bytes_out = total;
     *nnz_out = nnz;
+    return 0;
+}
+
+int scape_hip_report_group_sums(scape_hip_ctx *c, int32_t n_seg, const int32_t *seg_off, int32_t n_rows,
+                                const int64_t *rows, int32_t *sum_out, int32_t *nz_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
+    if (n_seg <= 0 || n_rows <= 0 || !seg_off || !rows || !sum_out || !nz_out) return fail("bad argument");
+    if (seg_off[0] < 0 || seg_off[n_seg] > s->n_cols) return fail("seg_off must lie within the columns");
+    for (int k = 0; k < n_seg; ++k)
+        if (seg_off[k + 1] < seg_off[k]) return fail("seg_off must be non-decreasing");
+    for (int i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
+    const int64_t n_out = (int64_t)n_rows * n_seg;
+    if (s->g_rows.ensure((int64_t)n_rows * 8) || s->g_off.ensure(((int64_t)n_seg + 1) * 4) || s->g_sum.ensure(n_out * 4) ||
+        s->g_nz.ensure(n_out * 4))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->g_rows.p, rows, (int64_t)n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->g_off.p, seg_off, ((int64_t)n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_segsum, dim3(n_rows), dim3(REP_THREADS), 0, c->stream, s->g_rows.as<int64_t>(), s->n_cols,
+                       s->r_cnt.as<int32_t>(), n_seg, s->g_off.as<int32_t>(), s->g_sum.as<int32_t>(),
+                       s->g_nz.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sum_out, s->g_sum.p, n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(nz_out, s->g_nz.p, n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 

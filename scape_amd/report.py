@@ -1,4 +1,4 @@
-"""``scape cal_exp_pa_len`` and ``scape ex_pa_cnt_mat``: the two stages after ``merge_pa`` (reference
+"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat`` and ``scape ex_pa_pseudobulk``: the stages after ``merge_pa`` (reference
 ``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of
 ``apa_core.py:1038-1063``).
 
@@ -13,6 +13,10 @@ Both stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``
 * ``cal_exp_pa_len``: the device builds, per record, the cluster codes present and the (cluster, label) histogram; the
   host names and orders the clusters with the reference's own ``np.unique(np.array(...))`` and finishes
   ``exp_pa_len`` with the reference's numpy expressions, so every printed digit matches by construction.
+* ``ex_pa_pseudobulk``: the count matrix summed over cell groups, the input of the reference's DEXSeq script
+  (``examples/Rscript-DEXseq/DifferentialTest.R:63-104``, ``:159-184``).  The host permutes the barcode columns so
+  that every pseudo-replicate is one contiguous segment of a count row; the device counts as for ``ex_pa_cnt_mat``
+  and returns, per row and segment, the sum and the number of nonzero counts.  Nothing cell-level leaves the device.
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -437,6 +441,183 @@ def _render_mtx_batch(ctx, recs, K, row_tot, n_cols, sink, times):
     sink.n_rows += len(rows)
 
 
+# ---------------------------------------------------------------- ex_pa_pseudobulk
+def _split_sizes(n, k):
+    """sizes of the chunks R's ``split(cells, sort(1:n %% k))`` cuts n cells into (DifferentialTest.R:63-104), empty
+    chunks dropped.  ``1:n %% k`` holds remainder 0 for n // k cells and remainder v = 1..k-1 for (n - v) // k + 1
+    cells when v <= n; ``sort`` puts equal remainders side by side, ascending, and ``split`` cuts where the value
+    changes.  The rule is derived from R's documented ``%%``, ``sort`` and ``split``; it has not been run in R."""
+    sizes = [n // k] + [(n - v) // k + 1 if v <= n else 0 for v in range(1, k)]
+    return [c for c in sizes if c]
+
+
+def _read_clusters(cell_cluster_file):
+    """(ids, cluster names) of the rows of a cluster file: the file as cal_exp_pa_len reads it (index_col="index",
+    first other column), the cluster read as text exactly as written; "" = no cluster"""
+    import pandas as pd
+    others = [c for c in pd.read_csv(cell_cluster_file, nrows=0).columns if c != "index"]
+    if not others:
+        raise ValueError(f"{cell_cluster_file}: no cluster column beside index")
+    df = pd.read_csv(cell_cluster_file, index_col="index", dtype={others[0]: str}, keep_default_na=False)
+    ids = df.index.to_numpy()
+    if ids.dtype.kind not in "iu":
+        raise ValueError(f"{cell_cluster_file}: the index column must hold integer ids")
+    return ids.astype(np.int64), df.iloc[:, 0].tolist()
+
+
+def _column_clusters(col_ids, clu_ids, clu_names):
+    """cluster name of every matrix column (None: no group) and the cluster names in order of first appearance among
+    the rows of the cluster file.  A repeated id keeps its last row; ids without a column are ignored."""
+    last = dict(zip(clu_ids.tolist(), clu_names))
+    order = list(dict.fromkeys(c for c in clu_names if c != ""))
+    return [last.get(i) or None for i in col_ids.tolist()], order
+
+
+def _populations(col_clu, order, idents_1, idents_2):
+    """[(population name, its columns ascending)], populations without a cell dropped"""
+    col_clu = np.array([c if c is not None else "" for c in col_clu], dtype=object)
+    if idents_1 is None:
+        pops = [(c, np.nonzero(col_clu == c)[0]) for c in order]
+    else:
+        for ident in (idents_1, idents_2):
+            if ident is not None and ident not in order:
+                raise ValueError(f"ident {ident!r} names no cluster of the cell_cluster_file")
+        rest = (col_clu == idents_2) if idents_2 is not None else ((col_clu != "") & (col_clu != idents_1))
+        pops = [("Population1", np.nonzero(col_clu == idents_1)[0]), ("Population2", np.nonzero(rest)[0])]
+    return [(name, cols) for name, cols in pops if len(cols)]
+
+
+def _samples(pops, num_splits, n_cols):
+    """pseudo-replicates of the populations: (rows of samples.csv, slot of every column, segment offsets, population of
+    every segment).  The slots put sample 0's columns first, then sample 1's, ...; columns of no group come last."""
+    table, order, seg_pop = [], [], []
+    seg_off = [0]
+    for p, (name, cols) in enumerate(pops):
+        a = 0
+        for i, c in enumerate(_split_sizes(len(cols), num_splits)):
+            table.append([f"{name}_{i + 1}", name, i + 1, c])
+            order.append(cols[a:a + c])
+            seg_off.append(seg_off[-1] + c)
+            seg_pop.append(p)
+            a += c
+    order = np.concatenate(order) if order else np.zeros(0, dtype=np.int64)
+    grouped = np.zeros(n_cols, dtype=bool)
+    grouped[order] = True
+    order = np.concatenate([order, np.nonzero(~grouped)[0]])
+    slot = np.empty(n_cols, dtype=np.int32)
+    slot[order] = np.arange(n_cols, dtype=np.int32)
+    return table, slot, np.array(seg_off, dtype=np.int32), np.array(seg_pop, dtype=np.int64)
+
+
+def _group_sums_batch(ctx, recs, K, row_tot, seg_off, seg_pop, n_cells, cnt_w, pct_w, times):
+    """the table lines of one counted batch: segment sums on the device, pa_info and the pct division on the host"""
+    rows, pa = [], []
+    base = 0
+    for r, para in enumerate(recs):
+        k = int(K[r])
+        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
+        if len(labs):
+            rows.append(base + labs)
+            pa.extend(_pa_info(para, labs))
+        base += k
+    if not rows:
+        return 0
+    rows = np.concatenate(rows).astype(np.int64)
+    n_seg = len(seg_off) - 1
+    sums = np.zeros((len(rows), n_seg), dtype=np.int32)
+    nz = np.zeros((len(rows), n_seg), dtype=np.int32)
+    if n_seg:
+        t0 = timer()
+        check(ctx.lib.scape_hip_report_group_sums(ctx.h, n_seg, ptr(seg_off, P_i32), len(rows), ptr(rows, P_i64),
+                                                  ptr(sums, P_i32), ptr(nz, P_i32)), "report_group_sums")
+        times["render"] += timer() - t0
+    t0 = timer()
+    nz_pop = np.zeros((len(rows), len(n_cells)), dtype=np.int64)
+    if n_seg:
+        # a population's columns are the union of its samples' columns (consecutive segments)
+        first = np.nonzero(np.diff(seg_pop, prepend=-1))[0]
+        nz_pop = np.add.reduceat(nz.astype(np.int64), first, axis=1)
+    pct = nz_pop / n_cells.astype(np.float64)
+    cnt_w.writerows([p] + c for p, c in zip(pa, sums.tolist()))
+    pct_w.writerows([p] + [repr(v) for v in c] for p, c in zip(pa, pct.tolist()))
+    times["finish"] += timer() - t0
+    return len(rows)
+
+
+def _ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str, num_splits: int = 6,
+                      idents_1=None, idents_2=None, device=None):
+    """pA x pseudo-replicate counts and the per-population share of cells with a count above 0, as three csv files
+    in output_dir (<prefix>.<kind>[.<A>_vs_<B>].pseudobulk.{cnt,pct,samples}.csv); returns their paths"""
+    import pandas as pd
+    if num_splits < 1:
+        raise ValueError(f"num_splits must be at least 1, not {num_splits}")
+    if idents_2 is not None and idents_1 is None:
+        raise ValueError("idents_2 needs idents_1")
+    if idents_1 is not None and idents_1 == idents_2:
+        raise ValueError(f"idents_1 and idents_2 are the same cluster {idents_1!r}")
+    res_pkl = os.path.join(output_dir, res_pkl_file)
+    if not (os.path.exists(output_dir)):
+        raise Exception("Given output_dir folder does not exists.")
+    if not (os.path.exists(res_pkl)):
+        raise Exception(f"Invalid file {res_pkl}. Given res_pkl_file is not in output_dir.")
+    if not (os.path.exists(cell_cluster_file)):
+        raise Exception("Given cell_cluster_file file does not exists")
+    cb_df = pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")
+    n_cols = len(cb_df)
+    if n_cols == 0:
+        raise ValueError("barcode_index.csv lists no barcode")
+    col_ids = cb_df.index.to_numpy()
+    if col_ids.dtype.kind not in "iu":
+        raise ValueError("barcode_index.csv: the index column must hold integer ids")
+    col_clu, order = _column_clusters(col_ids.astype(np.int64), *_read_clusters(cell_cluster_file))
+    pops = _populations(col_clu, order, idents_1, idents_2)
+    table, slot, seg_off, seg_pop = _samples(pops, num_splits, n_cols)
+    n_cells = np.array([len(cols) for _name, cols in pops], dtype=np.int64)
+    idmap = _IdMap(col_ids, slot, "barcode_index.csv")
+
+    tag = "" if idents_1 is None else f".{idents_1}_vs_{idents_2 if idents_2 is not None else 'rest'}"
+    if os.sep in tag:
+        raise ValueError(f"an ident with {os.sep!r} cannot be part of a file name")
+    stem = os.path.splitext(os.path.basename(cell_cluster_file))[0] + "." + \
+        res_pkl_file.replace(".pkl", "").replace("res.", "") + tag + ".pseudobulk."
+    final = [os.path.join(output_dir, stem + what + ".csv") for what in ("cnt", "pct", "samples")]
+    tmps = [_atomic_target(p) for p in final]
+
+    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
+    start_t = timer()
+    ctx = None
+    n_rows = 0
+    try:
+        with open(tmps[0], "w", newline="") as cfh, open(tmps[1], "w", newline="") as pfh, \
+                open(tmps[2], "w", newline="") as sfh:
+            cnt_w, pct_w, smp_w = (csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n')
+                                   for fh in (cfh, pfh, sfh))
+            cnt_w.writerow(["pa_info"] + [row[0] for row in table])
+            pct_w.writerow(["pa_info"] + [name for name, _cols in pops])
+            smp_w.writerow(["sample", "population", "split", "n_cells"])
+            smp_w.writerows(table)
+            ctx = _lib.default_context(device)
+            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 4 + len(p.label_arr) * 16 + 64,
+                                 _budget(ctx), times):
+                K, row_tot, _complete = _count(ctx, recs, idmap, n_cols, times)
+                n_rows += _group_sums_batch(ctx, recs, K, row_tot, seg_off, seg_pop, n_cells, cnt_w, pct_w, times)
+        for tmp, path in zip(tmps, final):
+            os.replace(tmp, path)
+    finally:
+        for tmp in tmps:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        if ctx is not None:
+            ctx.lib.scape_hip_report_free(ctx.h)
+    end_t = timer()
+    LAST_TIMES.clear()
+    LAST_TIMES.update(times)
+    LAST_TIMES["total"] = end_t - start_t
+    print(f"Finish pseudo-bulk counts of {n_rows} pA sites in {len(table)} samples of {len(pops)} populations")
+    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
+    return final
+
+
 # ---------------------------------------------------------------- cal_exp_pa_len
 def _exp_len_rows(K, alpha_arr, counts):
     """exp_pa_len (apa_core.py:1038-1052) for every row of counts [groups, K + 1] (slot K: reads with label >= K);
@@ -606,3 +787,26 @@ def cal_exp_pa_len(output_dir: str, cell_cluster_file: str, res_pkl_file: str):
 def ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, fmt: str):
     """pA x cell read-count matrix <res name>.cnt.tsv.gz from res.gene.pkl / res.utr.pkl (reference utils.py:438-553)."""
     _ex_pa_cnt_mat(output_dir, res_pkl_file, fmt=fmt)
+
+
+@click.command(name="ex_pa_pseudobulk")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the file names of the '
+                   'final result.')
+@click.option('--cell_cluster_file', type=str, required=True,
+              help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
+                   'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
+                   'names of the final result.')
+@click.option('--num_splits', type=int, default=6, show_default=True,
+              help='Pseudo-replicates per population: its cells, in barcode_index.csv order, are cut into this many '
+                   'consecutive chunks (num.splits of FindDE in DifferentialTest.R).')
+@click.option('--idents_1', type=str, default=None,
+              help='Compare this cluster (Population1) with --idents_2, or with every other cluster. Default: one '
+                   'population per cluster.')
+@click.option('--idents_2', type=str, default=None, help='The cluster of Population2 (needs --idents_1).')
+def ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str, num_splits: int, idents_1, idents_2):
+    """pA x pseudo-replicate read counts (the input of DEXSeq) and the share of each population's cells with a read
+    per pA site, from res.gene.pkl / res.utr.pkl and a cell cluster file (reference DifferentialTest.R:63-104, :159-184)."""
+    _ex_pa_pseudobulk(output_dir, res_pkl_file, cell_cluster_file, num_splits, idents_1, idents_2)

@@ -9,8 +9,12 @@ csv write.  Kernel times: run it under `rocprofv3 --kernel-trace --stats -d <dir
 `--format mtx` runs the count matrix as the Matrix Market directory instead of the dense file (`both`: one after the
 other on the same stream) and adds its text bytes per file, rows and nnz (entries); its `finish` is the header write
 and the copy of the body behind it.
+`--pseudobulk` adds `ex_pa_pseudobulk` on the same stream with groups.csv (12 clusters x 6 splits = 72 samples): its
+`render` is the segment-sum kernel and the read-back of its sums, `finish` the pct division and the csv lines.
+`--repeat N` runs every command N times and reports the median wall time (and that run's stage times).
 
-    python tools/report_rate.py [--records N] [--reads N] [--cells N] [--format tsv|mtx|both]
+    python tools/report_rate.py [--records N] [--reads N] [--cells N] [--format tsv|mtx|both] [--pseudobulk]
+                                [--repeat N]
 """
 import argparse
 import contextlib
@@ -82,6 +86,8 @@ def main():
     ap.add_argument("--cells", type=int, default=33088)
     ap.add_argument("--format", choices=("tsv", "mtx", "both"), default="tsv",
                     help="count matrix: the dense file (default), the Matrix Market directory, or both")
+    ap.add_argument("--pseudobulk", action="store_true", help="also run ex_pa_pseudobulk with the 12-group file")
+    ap.add_argument("--repeat", type=int, default=1, help="runs per command; the median wall time is reported")
     a = ap.parse_args()
     from scape_amd import _lib, report
     root = tempfile.mkdtemp(prefix="report_rate_")
@@ -97,15 +103,22 @@ def main():
             runs.append(("ex_pa_cnt_mat", lambda: report._ex_pa_cnt_mat(root, "res.gene.pkl")))
         if a.format in ("mtx", "both"):
             runs.append(("ex_pa_cnt_mat_mtx", lambda: report._ex_pa_cnt_mat(root, "res.gene.pkl", fmt="mtx")))
+        if a.pseudobulk:
+            runs.append(("ex_pa_pseudobulk",
+                         lambda: report._ex_pa_pseudobulk(root, "res.gene.pkl", os.path.join(root, "groups.csv"))))
         runs += [("cal_exp_pa_len", lambda: report._cal_exp_pa_len(root, "None", "res.gene.pkl")),
                  ("cal_exp_pa_len_groups",
                   lambda: report._cal_exp_pa_len(root, os.path.join(root, "groups.csv"), "res.gene.pkl"))]
         for name, fn in runs:
-            t0 = time.perf_counter()
-            with contextlib.redirect_stdout(io.StringIO()):
-                path = fn()
-            out[name] = {"wall_s": time.perf_counter() - t0, "stages_s": dict(report.LAST_TIMES),
-                         "out_bytes": size(path)}
+            tries = []
+            for _ in range(max(a.repeat, 1)):
+                t0 = time.perf_counter()
+                with contextlib.redirect_stdout(io.StringIO()):
+                    path = fn()
+                tries.append((time.perf_counter() - t0, dict(report.LAST_TIMES)))
+            wall, stages = sorted(tries, key=lambda t: t[0])[len(tries) // 2]
+            out[name] = {"wall_s": wall, "stages_s": stages, "walls_s": [t[0] for t in tries],
+                         "out_bytes": sum(size(p) for p in path) if isinstance(path, list) else size(path)}
         if "ex_pa_cnt_mat" in out:
             m = out["ex_pa_cnt_mat"]
             m["text_bytes"] = gz_text(os.path.join(root, "res.gene.cnt.tsv.gz"))[0]
@@ -119,6 +132,12 @@ def main():
             m["text_GB_per_s"] = m["text_bytes"] / m["wall_s"] / 1e9
             rows, cols, nnz = gz_text(os.path.join(d, "matrix.mtx.gz"))[1].split(b"\n")[1].split()
             m.update(rows=int(rows), cols=int(cols), nnz=int(nnz))
+        if "ex_pa_pseudobulk" in out:
+            m = out["ex_pa_pseudobulk"]
+            with open(os.path.join(root, "groups.gene.pseudobulk.cnt.csv")) as fh:
+                lines = fh.read().splitlines()
+            m.update(rows=len(lines) - 1, samples=lines[0].count(","),
+                     count_bytes_summed=(len(lines) - 1) * a.cells * 4)
     finally:
         shutil.rmtree(root, ignore_errors=True)
     print(json.dumps(out))
