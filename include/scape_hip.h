@@ -199,6 +199,30 @@ int scape_hip_report_render_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows
    once both arrays are on the host. */
 int scape_hip_report_group_sums(scape_hip_ctx *ctx, int32_t n_seg, const int32_t *seg_off, int32_t n_rows,
                                 const int64_t *rows, int32_t *sum_out, int32_t *nz_out);
+/* diff_pa: permutation test of pA usage between two cell populations.  The tested columns are the first n = n1 + n2
+   columns of the count matrix (the caller passes scape_hip_report_counts an id2col that puts population 1's columns
+   first, then population 2's); position j = column j.  Permutation 0 is the observed labelling (positions < n1).
+   Permutation p >= 1 gives population 1 the n1 positions with the smallest key(p, j), all arithmetic mod 2^64:
+     G = 0x9E3779B97F4A7C15
+     mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+     h(p, j) = mix(mix(seed + G * p) + G * (j + 1)),  key(p, j) = (h(p, j) & ~0xFFFFFF) | j
+   scape_hip_report_perm_masks builds the membership bits of permutations p_first .. p_first + p_count - 1 (p_first >= 1)
+   on the device, p_count * ceil(n / 64) * 8 bytes laid out [column word][permutation]; they replace the bits of an
+   earlier call and stay until scape_hip_report_free, across scape_hip_report_counts calls.  n1, n2 >= 1, n < 2^24. */
+int scape_hip_report_perm_masks(scape_hip_ctx *ctx, int32_t n1, int32_t n2, int64_t p_first, int32_t p_count,
+                                uint64_t seed);
+/* The test of n_rec records of the last counts call against the permutations of the last perm_masks call.  Record r owns
+   the kept count rows rows[rec_row_off[r] .. rec_row_off[r+1]) (rec_row_off[0] = 0, non-decreasing).  Per row i:
+   t_out[i] = its sum over the tested columns, a0_out[i] = its sum over population 1 as observed.  With T, A, B the
+   record's sums of t, a and t - a under a labelling, N_i = a_i T - t_i A (64-bit integers),
+     S = sum_i N_i^2 / (t_i A B)   and   d_i = N_i / (A B)      (both 0 when A = 0 or B = 0), in f64, rows in order.
+   stat0_out[r] = S of the observed labelling.  The call ADDS to site_n_ge_out[i] the number of its permutations with
+   |d_i(p)| >= |d_i(0)| (1 - 2^-40) and to gene_n_ge_out[r] those with S(p) >= S(0) (1 - 2^-40): the caller zeroes both
+   arrays before the first chunk of permutations and passes them again for every further chunk (the device counters
+   themselves start at zero in every call, and S(0), d_i(0) are formed anew, so chunks do not depend on each other). */
+int scape_hip_report_perm_test(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                               int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
+                               int64_t *gene_n_ge_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

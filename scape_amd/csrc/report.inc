@@ -23,6 +23,11 @@
 //   k_rep_segsum    ex_pa_pseudobulk: per count row, the sum and the number of nonzero counts of every column segment
 //                   (the host permutes the columns so that each pseudo-bulk sample is one contiguous segment); one wave
 //                   per segment, no atomics
+//   k_rep_perm_mask / k_rep_perm_rowstat / k_rep_perm_fill / k_rep_perm_test
+//                   diff_pa: the membership bits of hashed label permutations (radix select of the n1-th smallest
+//                   64-bit key, one workgroup per permutation), the nonzeros (position, count) of the kept count rows,
+//                   and the permutation test itself (one lane per permutation, exceedance counts per site and record);
+//                   section "permutation test" at the end of this file
 // Cluster names, their order and the floating-point finish of exp_pa_len stay on the host (scape_amd/report.py).
 
 #define REP_THREADS 256
@@ -41,6 +46,10 @@ struct ReportState {
     int64_t h_groups = 0, h_hist_n = 0;
     // segment sums of the last scape_hip_report_group_sums call
     DevBuf g_rows, g_off, g_sum, g_nz;
+    // diff_pa: membership bits of the last scape_hip_report_perm_masks call ([column word][permutation]) and the
+    // buffers of scape_hip_report_perm_test
+    DevBuf m_bits, p_rows, p_roff, p_nnz, p_noff, p_nz, p_t, p_a0, p_recs, p_site, p_gene, p_stat0;
+    int32_t m_n1 = 0, m_n2 = 0, m_count = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
@@ -64,7 +73,9 @@ static void report_release(scape_hip_ctx *c) {
                      &s->h_hist, &s->s_rows[0], &s->s_rows[1], &s->s_int[0], &s->s_int[1], &s->s_poff[0],
                      &s->s_poff[1], &s->s_pre[0], &s->s_pre[1], &s->s_len[0], &s->s_len[1], &s->s_roff[0],
                      &s->s_roff[1], &s->s_out[0], &s->s_out[1], &s->s_nnz[0], &s->s_nnz[1], &s->s_noff[0],
-                     &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz};
+                     &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz, &s->m_bits, &s->p_rows,
+                     &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
+                     &s->p_stat0};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;
@@ -767,6 +778,309 @@ int scape_hip_report_hist_fetch(scape_hip_ctx *c, int64_t n_groups, int32_t *cod
 int scape_hip_report_free(scape_hip_ctx *c) {
     CTX_ENTER(c);
     report_release(c);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- permutation test (diff_pa) -------------------------------------------------------------------------------------
+// The tested columns are the first n = n1 + n2 columns of the count matrix (population 1, then population 2: the caller's
+// id2col puts them there), position j = column j.  Permutation p >= 1 gives population 1 the n1 positions with the
+// smallest key(p, j); all arithmetic mod 2^64 (scape_hip.h states the scheme):
+//   mix = the splitmix64 finaliser,  h(p, j) = mix(mix(seed + G p) + G (j + 1)),  key = (h & ~0xFFFFFF) | j
+#define REP_PERM_G 0x9E3779B97F4A7C15ull
+#define REP_PERM_MAX_N (1 << 24)
+#define REP_PERM_SLACK 0x1.ffffffffffp-1   // 1 - 2^-40: equal rationals count as ties whatever their rounding
+
+__device__ __forceinline__ unsigned long long rep_mix(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ unsigned long long rep_perm_key(unsigned long long base, int j) {
+    return (rep_mix(base + REP_PERM_G * (unsigned long long)(j + 1)) & ~0xFFFFFFull) | (unsigned long long)j;
+}
+
+// one workgroup per permutation p_first + blockIdx.x: radix select (most significant byte first, 256-bin LDS histogram,
+// keys recomputed in every pass) of the n1-th smallest key, then one pass that writes bit j = (key(j) <= that key) of
+// bits[(j / 64) * p_count + blockIdx.x].  Keys are distinct (their low 24 bits are j), so exactly n1 bits are set.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_mask(int32_t n1, int32_t n, unsigned long long p_first,
+                                                               int32_t p_count, unsigned long long seed,
+                                                               unsigned long long *__restrict__ bits) {
+    __shared__ int hist[256];
+    __shared__ unsigned long long sel[2];   // prefix of the key looked for, and its rank among the keys with that prefix
+    const unsigned long long base = rep_mix(seed + REP_PERM_G * (p_first + blockIdx.x));
+    if (threadIdx.x == 0) {
+        sel[0] = 0;
+        sel[1] = (unsigned long long)(n1 - 1);
+    }
+    for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        const unsigned long long prefix = sel[0];
+        for (int j = threadIdx.x; j < n; j += REP_THREADS) {
+            const unsigned long long k = rep_perm_key(base, j);
+            if (pass == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            long long rank = (long long)sel[1];
+            int b = 0;
+            while (b < 255 && rank >= hist[b]) rank -= hist[b++];
+            sel[0] = prefix | ((unsigned long long)b << shift);
+            sel[1] = (unsigned long long)rank;
+        }
+        __syncthreads();
+    }
+    const unsigned long long thr = sel[0];
+    const int lane = threadIdx.x & 63, n_words = (n + 63) >> 6;
+    for (int w = threadIdx.x >> 6; w < n_words; w += REP_WAVES) {
+        const int j = w * 64 + lane;
+        const unsigned long long m = __ballot(j < n && rep_perm_key(base, j) <= thr);
+        if (lane == 0) bits[(int64_t)w * p_count + blockIdx.x] = m;
+    }
+}
+
+// one workgroup per kept row i (count row rows[i]): nonzeros among the tested positions, their sum t and the sum over
+// positions < n1 (population 1 as observed)
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_rowstat(const int64_t *__restrict__ rows, int32_t n_cols,
+                                                                  const int32_t *__restrict__ cnt, int32_t n1, int32_t n,
+                                                                  int64_t *__restrict__ nnz, int64_t *__restrict__ t,
+                                                                  int64_t *__restrict__ a0) {
+    __shared__ long long lds[REP_WAVES];
+    const int i = blockIdx.x;
+    const int32_t *row = cnt + rows[i] * n_cols;
+    long long z = 0, s = 0, a = 0;
+    for (int c = threadIdx.x; c < n; c += REP_THREADS) {
+        const int v = row[c];
+        z += v != 0;
+        s += v;
+        a += c < n1 ? v : 0;
+    }
+    z = rep_block_sum<long long, REP_WAVES>(z, lds);
+    s = rep_block_sum<long long, REP_WAVES>(s, lds);
+    a = rep_block_sum<long long, REP_WAVES>(a, lds);
+    if (threadIdx.x == 0) {
+        nnz[i] = z;
+        t[i] = s;
+        a0[i] = a;
+    }
+}
+
+// one workgroup per kept row: its (position, count) nonzeros, positions ascending, at nz[noff[i] ..]
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_fill(const int64_t *__restrict__ rows, int32_t n_cols,
+                                                               const int32_t *__restrict__ cnt, int32_t n,
+                                                               const int64_t *__restrict__ noff, uint2 *__restrict__ nz) {
+    __shared__ int lds[REP_WAVES];
+    const int i = blockIdx.x;
+    const int32_t *row = cnt + rows[i] * n_cols;
+    uint2 *dst = nz + noff[i];
+    int64_t pos = 0;
+    for (int base = 0; base < n; base += REP_THREADS) {
+        const int c = base + threadIdx.x;
+        const int v = c < n ? row[c] : 0;
+        int tile;
+        const int ex = rep_block_excl<int, REP_WAVES>(v != 0, lds, &tile);
+        if (v) dst[pos + ex] = make_uint2((uint32_t)c, (uint32_t)v);
+        pos += tile;
+    }
+}
+
+// the term of S and the usage difference d of one row, from integers: N = a T - t A exactly in 64 bits (both products are
+// below 2^62), converted once.  The observed labelling and every permutation go through this one function, with
+// contraction off, so equal integers give equal doubles
+__device__ __forceinline__ double rep_perm_row(long long a, long long t, long long A, long long T, double *d) {
+#pragma clang fp contract(off)
+    const long long B = T - A;
+    if (A == 0 || B == 0 || t == 0) {
+        *d = 0.0;
+        return 0.0;
+    }
+    const double N = (double)(a * T - t * A), Ad = (double)A, Bd = (double)B;
+    *d = N / (Ad * Bd);
+    return (N * N) / ((double)t * Ad * Bd);
+}
+
+// a row's sum over this lane's population 1: the nonzeros are wave-uniform, the lane tests its own permutation's bit.
+// Positions ascend within a row, so a mask word is loaded once for all the nonzeros that fall into it
+__device__ __forceinline__ int rep_perm_rowsum(const uint2 *__restrict__ nz, int64_t k0, int64_t k1,
+                                               const unsigned long long *__restrict__ mb, int64_t pstride) {
+    int a = 0, cur = -1;
+    unsigned long long w = 0;
+    for (int64_t k = k0; k < k1; ++k) {
+        const uint2 e = nz[k];
+        const int pos = __builtin_amdgcn_readfirstlane((int)e.x), c = __builtin_amdgcn_readfirstlane((int)e.y);
+        if ((pos >> 6) != cur) {
+            cur = pos >> 6;
+            w = mb[(int64_t)cur * pstride];
+        }
+        a += ((w >> (pos & 63)) & 1) ? c : 0;
+    }
+    return a;
+}
+
+// workgroup = (record recs[blockIdx.x / n_tiles], tile of 256 permutations), one lane per permutation.  a_i(p) of the
+// record's rows are kept in LDS as acc[row][lane] (each lane reads and writes its own column: conflict-free, no barrier)
+// until A(p) = sum a_i(p) is known; a record with more than `cap` rows is taken in groups of cap rows behind one extra
+// walk that forms A(p).  Exceedances are counted per wave (ballot) and added with one atomic per wave and counter.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_test(
+    const unsigned long long *__restrict__ bits, int32_t p_count, int32_t n_tiles, const int32_t *__restrict__ recs,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ noff, const uint2 *__restrict__ nz,
+    const int64_t *__restrict__ t, const int64_t *__restrict__ a0, int32_t cap, int32_t *__restrict__ site_ge,
+    int32_t *__restrict__ gene_ge, double *__restrict__ stat0) {
+#pragma clang fp contract(off)
+    extern __shared__ int32_t rep_acc[];
+    const int r = recs[blockIdx.x / n_tiles], tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const unsigned long long *mb = bits + (valid ? p : p_count - 1);
+    int32_t *acc = rep_acc + threadIdx.x;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    long long T = 0, A0 = 0, A = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        T += t[i];
+        A0 += a0[i];
+    }
+    const bool one = row1 - row0 <= cap;
+    if (!one)
+        for (int64_t i = row0; i < row1; ++i) A += rep_perm_rowsum(nz, noff[i], noff[i + 1], mb, p_count);
+    double S = 0.0, S0 = 0.0;
+    for (int64_t g0 = row0; g0 < row1; g0 += cap) {
+        const int64_t g1 = g0 + cap < row1 ? g0 + cap : row1;
+        long long Ag = 0;
+        for (int64_t i = g0; i < g1; ++i) {
+            const int a = rep_perm_rowsum(nz, noff[i], noff[i + 1], mb, p_count);
+            acc[(i - g0) * REP_THREADS] = a;
+            Ag += a;
+        }
+        if (one) A = Ag;
+        for (int64_t i = g0; i < g1; ++i) {
+            double d, d0;
+            S = S + rep_perm_row(acc[(i - g0) * REP_THREADS], t[i], A, T, &d);
+            S0 = S0 + rep_perm_row(a0[i], t[i], A0, T, &d0);
+            const unsigned long long b = __ballot(valid && fabs(d) >= fabs(d0) * REP_PERM_SLACK);
+            if ((threadIdx.x & 63) == 0 && b) atomicAdd(&site_ge[i], __popcll(b));
+        }
+    }
+    const unsigned long long b = __ballot(valid && S >= S0 * REP_PERM_SLACK);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[r], __popcll(b));
+    if (tile == 0 && threadIdx.x == 0) stat0[r] = S0;
+}
+
+static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
+
+extern "C" {
+
+int scape_hip_report_perm_masks(scape_hip_ctx *c, int32_t n1, int32_t n2, int64_t p_first, int32_t p_count,
+                                uint64_t seed) {
+    CTX_ENTER(c);
+    if (n1 < 1 || n2 < 1) return fail("both populations need at least one cell");
+    if ((int64_t)n1 + n2 >= REP_PERM_MAX_N) return fail("n1 + n2 must be below 2^24 (a key keeps the position in 24 bits)");
+    if (p_first < 1 || p_count < 1) return fail("p_first and p_count must be at least 1 (permutation 0 is the observed labelling)");
+    ReportState *s = report_state(c);
+    s->m_count = 0;
+    const int32_t n = n1 + n2;
+    if (s->m_bits.ensure((int64_t)p_count * ((n + 63) / 64) * 8)) return 1;
+    hipLaunchKernelGGL(k_rep_perm_mask, dim3(p_count), dim3(REP_THREADS), 0, c->stream, n1, n,
+                       (unsigned long long)p_first, p_count, (unsigned long long)seed,
+                       s->m_bits.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    s->m_n1 = n1;
+    s->m_n2 = n2;
+    s->m_count = p_count;
+    return 0;
+}
+
+int scape_hip_report_perm_test(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                               int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
+                               int64_t *gene_n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
+    if (!s->m_count) return fail("scape_hip_report_perm_masks has not been called");
+    if (n_rec <= 0 || !rec_row_off || !rows || !t_out || !a0_out || !site_n_ge_out || !stat0_out || !gene_n_ge_out)
+        return fail("bad argument");
+    const int32_t n1 = s->m_n1, n = s->m_n1 + s->m_n2;
+    if (n > s->n_cols) return fail("the count matrix has fewer columns than the masks have positions");
+    if (rec_row_off[0] != 0) return fail("rec_row_off must start at 0");
+    for (int r = 0; r < n_rec; ++r)
+        if (rec_row_off[r + 1] < rec_row_off[r]) return fail("rec_row_off must be non-decreasing");
+    const int64_t n_rows = rec_row_off[n_rec];
+    if (n_rows <= 0 || n_rows > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
+    for (int64_t i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
+    const int32_t n_tiles = (s->m_count + REP_THREADS - 1) / REP_THREADS;
+    if ((int64_t)n_rec * n_tiles > INT32_MAX) return fail("too many records x permutation tiles for one call");
+
+    if (s->p_rows.ensure(n_rows * 8) || s->p_roff.ensure(((int64_t)n_rec + 1) * 8) || s->p_nnz.ensure(n_rows * 8) ||
+        s->p_noff.ensure((n_rows + 1) * 8) || s->p_t.ensure(n_rows * 8) || s->p_a0.ensure(n_rows * 8) ||
+        s->p_recs.ensure((int64_t)n_rec * 4) || s->p_site.ensure(n_rows * 4) || s->p_gene.ensure((int64_t)n_rec * 4) ||
+        s->p_stat0.ensure((int64_t)n_rec * 8))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->p_rows.p, rows, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->p_roff.p, rec_row_off, ((int64_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_perm_rowstat, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
+                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n1, n, s->p_nnz.as<int64_t>(),
+                       s->p_t.as<int64_t>(), s->p_a0.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->p_nnz.as<int64_t>(),
+                       (int32_t)n_rows, s->p_noff.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, s->p_noff.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(t_out, s->p_t.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(a0_out, s->p_a0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < n_rec; ++r) {
+        int64_t T = 0;
+        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) T += t_out[i];
+        if (T > INT32_MAX) return fail("record " + std::to_string(r) + ": 2^31 or more reads in the tested cells");
+    }
+    if (s->p_nz.ensure(std::max<int64_t>(total, 1) * 8)) return 1;
+    hipLaunchKernelGGL(k_rep_perm_fill, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
+                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n, s->p_noff.as<int64_t>(),
+                       s->p_nz.as<uint2>());
+    HIPCHK(hipGetLastError());
+
+    // records by LDS class: the smallest cap that holds all their rows (the largest cap takes the rest, in groups)
+    const int n_caps = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
+    std::vector<std::vector<int32_t>> by_cap(n_caps);
+    for (int r = 0; r < n_rec; ++r) {
+        const int64_t k = rec_row_off[r + 1] - rec_row_off[r];
+        int q = 0;
+        while (q < n_caps - 1 && k > REP_PERM_CAPS[q]) ++q;
+        by_cap[q].push_back(r);
+    }
+    std::vector<int32_t> recs;
+    for (auto &v : by_cap) recs.insert(recs.end(), v.begin(), v.end());
+    HIPCHK(hipMemcpyAsync(s->p_recs.p, recs.data(), (int64_t)n_rec * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(s->p_site.p, 0, n_rows * 4, c->stream));
+    HIPCHK(hipMemsetAsync(s->p_gene.p, 0, (int64_t)n_rec * 4, c->stream));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_test),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, REP_PERM_CAPS[n_caps - 1] * REP_THREADS * 4));
+    int64_t first = 0;
+    for (int q = 0; q < n_caps; ++q) {
+        const int64_t m = (int64_t)by_cap[q].size();
+        if (!m) continue;
+        const int32_t cap = REP_PERM_CAPS[q];
+        hipLaunchKernelGGL(k_rep_perm_test, dim3((uint32_t)(m * n_tiles)), dim3(REP_THREADS),
+                           (size_t)cap * REP_THREADS * 4, c->stream, s->m_bits.as<unsigned long long>(), s->m_count,
+                           n_tiles, s->p_recs.as<int32_t>() + first, s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(),
+                           s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->p_a0.as<int64_t>(), cap,
+                           s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
+        HIPCHK(hipGetLastError());
+        first += m;
+    }
+    std::vector<int32_t> site(n_rows), gene(n_rec);
+    HIPCHK(hipMemcpyAsync(site.data(), s->p_site.p, n_rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(gene.data(), s->p_gene.p, (int64_t)n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(stat0_out, s->p_stat0.p, (int64_t)n_rec * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n_rows; ++i) site_n_ge_out[i] += site[i];
+    for (int r = 0; r < n_rec; ++r) gene_n_ge_out[r] += gene[r];
     return 0;
 }
 

@@ -1,4 +1,4 @@
-"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat`` and ``scape ex_pa_pseudobulk``: the stages after ``merge_pa`` (reference
+"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk`` and ``scape diff_pa``: the stages after ``merge_pa`` (reference
 ``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of
 ``apa_core.py:1038-1063``).
 
@@ -17,6 +17,10 @@ Both stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``
   (``examples/Rscript-DEXseq/DifferentialTest.R:63-104``, ``:159-184``).  The host permutes the barcode columns so
   that every pseudo-replicate is one contiguous segment of a count row; the device counts as for ``ex_pa_cnt_mat``
   and returns, per row and segment, the sum and the number of nonzero counts.  Nothing cell-level leaves the device.
+* ``diff_pa``: which pA sites two cell populations use differently, by permuting the cell labels (section diff_pa
+  below states the test).  The device builds the permutations' membership bits, compacts the count rows to their
+  nonzeros and counts, per site and record, the permutations whose statistic reaches the observed one; the host
+  turns the integers into p-values, Benjamini-Hochberg adjusted, and writes one csv.
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -48,6 +52,7 @@ MAX_BLOCK_BYTES = 256 << 20
 GZIP_LEVEL = 9            # gzip.open's default, what the reference writes with
 GZIP_PART = 8 << 20       # text bytes per gzip member (one host thread each)
 MAX_ID_SPAN = 1 << 30     # barcode ids are looked up in a dense table over [min id, max id]
+MAX_PERM_BYTES = None     # diff_pa: device bytes of one chunk of permutation bits (None: half of the batch budget)
 
 _TIMES_KEYS = ("decode", "h2d_counts", "render", "gzip_wait", "finish")
 
@@ -618,6 +623,219 @@ def _ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str
     return final
 
 
+# ---------------------------------------------------------------- diff_pa
+# Tested columns: population 1's matrix columns ascending, then population 2's: positions j = 0 .. n-1.  Permutation p of
+# 1 .. n_perm gives population 1 the n1 positions with the smallest key(p, j) (include/scape_hip.h states the hash; it
+# is counter-based, so nothing sequential runs anywhere); p = 0 is the observed labelling.  Per record, with t_i / a_i
+# the sums of row i over the tested columns / over population 1, T = sum t_i, A = sum a_i, B = T - A and the integer
+# N_i = a_i T - t_i A:  S = sum_i N_i^2 / (t_i A B) (Pearson's chi-square of the rows x 2 table) tests the record,
+# d_i = N_i / (A B) = a_i / A - b_i / B (two-sided) the site.  Rows with t_i = 0 are dropped; a record is tested when two
+# rows or more remain and both populations have reads.  p = (1 + #{p: stat(p) >= stat(0)}) / (1 + n_perm).
+DIFF_PA_HEADER = ["gene", "pa_info", "pct.1", "pct.2", "versus", "usage.1", "usage.2", "delta_usage", "n_ge", "p_val",
+                  "p_val_adj", "gene_stat", "gene_n_ge", "gene_p_val", "gene_p_val_adj", "n_perm"]
+MAX_PERM_CELLS = 1 << 24  # a key keeps the position in its low 24 bits
+
+
+def _bh(p):
+    """Benjamini-Hochberg adjusted p-values (R's p.adjust(method = "BH"))"""
+    p = np.asarray(p, dtype=np.float64)
+    m = len(p)
+    if m == 0:
+        return p
+    order = np.argsort(-p, kind="stable")
+    adj = np.minimum.accumulate(p[order] * (m / np.arange(m, 0, -1)))
+    out = np.empty(m)
+    out[order] = np.minimum(adj, 1.0)
+    return out
+
+
+def _perm_masks(ctx, n1, n2, p_first, p_count, seed, times):
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_perm_masks(ctx.h, n1, n2, p_first, p_count, seed), "report_perm_masks")
+    times["render"] += timer() - t0
+
+
+def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, genes, times):
+    """one counted batch: the kept rows of its tested records go through the permutation test; appends the per-line
+    integers to `lines` and the per-record ones to `genes`"""
+    n1, n2 = int(seg_off[1]), int(seg_off[2] - seg_off[1])
+    cand, owner = [], []
+    base = 0
+    for r in range(len(recs)):
+        k = int(K[r])
+        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
+        cand.append(base + labs)
+        owner.append(np.full(len(labs), r, dtype=np.int64))
+        base += k
+    cand, owner = np.concatenate(cand).astype(np.int64), np.concatenate(owner)
+    if not len(cand):
+        return
+    sums = np.zeros((len(cand), 2), dtype=np.int32)
+    nz = np.zeros((len(cand), 2), dtype=np.int32)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_group_sums(ctx.h, 2, ptr(seg_off, P_i32), len(cand), ptr(cand, P_i64),
+                                              ptr(sums, P_i32), ptr(nz, P_i32)), "report_group_sums")
+    times["render"] += timer() - t0
+    t0 = timer()
+    sums = sums.astype(np.int64)
+    keep = sums.sum(axis=1) > 0
+    n_kept = np.bincount(owner[keep], minlength=len(recs))
+    A = np.bincount(owner, weights=sums[:, 0], minlength=len(recs))
+    B = np.bincount(owner, weights=sums[:, 1], minlength=len(recs))
+    tested = (n_kept >= 2) & (A > 0) & (B > 0)
+    keep &= tested[owner]
+    rows, owner, nz = cand[keep], owner[keep], nz[keep]
+    which = np.nonzero(tested)[0]
+    times["finish"] += timer() - t0
+    if not len(which):
+        return
+    off = np.zeros(len(which) + 1, dtype=np.int64)
+    np.cumsum(n_kept[which], out=off[1:])
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
+    site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
+    stat0 = np.zeros(len(which), np.float64)
+    for p_first in range(1, n_perm + 1, chunk):
+        if chunk < n_perm:       # otherwise the one set of masks was built before the first batch
+            _perm_masks(ctx, n1, n2, p_first, min(chunk, n_perm + 1 - p_first), seed, times)
+        t0 = timer()
+        check(ctx.lib.scape_hip_report_perm_test(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(t, P_i64),
+                                                 ptr(a0, P_i64), ptr(site_ge, P_i64), ptr(stat0), ptr(gene_ge, P_i64)),
+              "report_perm_test")
+        times["render"] += timer() - t0
+    t0 = timer()
+    if not (np.array_equal(t, sums[keep].sum(axis=1)) and np.array_equal(a0, sums[keep][:, 0])):
+        raise _lib.ScapeHipError("report_perm_test: row sums differ from report_group_sums")
+    rowbase = np.cumsum(K, dtype=np.int64) - K
+    for g, r in enumerate(which.tolist()):
+        a, b = int(off[g]), int(off[g + 1])
+        T = int(t[a:b].sum())
+        if T >= 1 << 31:
+            raise ValueError(f"{recs[r].gene_info_str}: 2^31 or more reads in the tested cells")
+        labs = rows[a:b] - int(rowbase[r])
+        genes.append((recs[r].gene_info_str, b - a, float(stat0[g]), int(gene_ge[g])))
+        lines["pa"].extend(_pa_info(recs[r], labs))
+    for key, arr in (("t", t), ("a", a0), ("nz1", nz[:, 0]), ("nz2", nz[:, 1]), ("n_ge", site_ge)):
+        lines[key].append(np.asarray(arr, dtype=np.int64).copy())
+    times["finish"] += timer() - t0
+
+
+def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
+             n_perm: int = 9999, seed: int = 1, device=None):
+    """permutation test of pA usage between the cells of cluster idents_1 and those of idents_2 (None: every other cell
+    that has a cluster); writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.diff_pa.csv in output_dir, returns its path"""
+    import pandas as pd
+    if idents_1 is None:
+        raise ValueError("idents_1 is required")
+    if idents_1 == idents_2:
+        raise ValueError(f"idents_1 and idents_2 are the same cluster {idents_1!r}")
+    if n_perm < 1:
+        raise ValueError(f"n_perm must be at least 1, not {n_perm}")
+    if n_perm >= 1 << 31:
+        raise ValueError(f"n_perm must be below 2^31, not {n_perm}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
+    res_pkl = os.path.join(output_dir, res_pkl_file)
+    if not (os.path.exists(output_dir)):
+        raise Exception("Given output_dir folder does not exists.")
+    if not (os.path.exists(res_pkl)):
+        raise Exception(f"Invalid file {res_pkl}. Given res_pkl_file is not in output_dir.")
+    if not (os.path.exists(cell_cluster_file)):
+        raise Exception("Given cell_cluster_file file does not exists")
+    cb_df = pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")
+    n_cols = len(cb_df)
+    if n_cols == 0:
+        raise ValueError("barcode_index.csv lists no barcode")
+    col_ids = cb_df.index.to_numpy()
+    if col_ids.dtype.kind not in "iu":
+        raise ValueError("barcode_index.csv: the index column must hold integer ids")
+    col_clu, order = _column_clusters(col_ids.astype(np.int64), *_read_clusters(cell_cluster_file))
+    pops = _populations(col_clu, order, idents_1, idents_2)
+    if len(pops) < 2:
+        empty = "Population2" if pops and pops[0][0] == "Population1" else "Population1"
+        raise ValueError(f"{empty} ({idents_1 if empty == 'Population1' else idents_2 or 'the rest'}) has no cell in "
+                         "barcode_index.csv")
+    _table, slot, seg_off, _seg_pop = _samples(pops, 1, n_cols)      # population 1's columns first, then population 2's
+    n1, n2 = len(pops[0][1]), len(pops[1][1])
+    if n1 + n2 >= MAX_PERM_CELLS:
+        raise ValueError(f"{n1 + n2} tested cells: diff_pa takes fewer than {MAX_PERM_CELLS}")
+    idmap = _IdMap(col_ids, slot, "barcode_index.csv")
+    versus = f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1)
+
+    tag = f".{idents_1}_vs_{idents_2 if idents_2 is not None else 'rest'}"
+    if os.sep in tag:
+        raise ValueError(f"an ident with {os.sep!r} cannot be part of a file name")
+    outpath = os.path.join(output_dir, os.path.splitext(os.path.basename(cell_cluster_file))[0] + "." +
+                           res_pkl_file.replace(".pkl", "").replace("res.", "") + tag + ".diff_pa.csv")
+    tmp = _atomic_target(outpath)
+
+    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
+    start_t = timer()
+    ctx = None
+    lines = {k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}
+    genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
+    try:
+        with open(tmp, "w", newline="") as fh:
+            ctx = _lib.default_context(device)
+            budget = _budget(ctx)
+            word_bytes = (n1 + n2 + 63) // 64 * 8
+            perm_bytes = int(MAX_PERM_BYTES) if MAX_PERM_BYTES is not None else budget // 2
+            chunk = max(1, min(n_perm, perm_bytes // word_bytes))
+            if chunk == n_perm:
+                _perm_masks(ctx, n1, n2, 1, n_perm, seed, times)
+            if MAX_BATCH_BYTES is None:
+                budget //= 2
+            # the counts of a record and, at worst, as many 8-byte nonzeros as it has tested counts
+            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 12 + len(p.label_arr) * 16 + 64, budget, times):
+                K, row_tot, _complete = _count(ctx, recs, idmap, n_cols, times)
+                _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, genes, times)
+            t0 = timer()
+            w = csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n')
+            w.writerow(DIFF_PA_HEADER)
+            if genes:
+                t, a, nz1, nz2, n_ge = (np.concatenate(lines[k]) for k in ("t", "a", "nz1", "nz2", "n_ge"))
+                n_lines = np.array([g[1] for g in genes], dtype=np.int64)
+                rec_of = np.repeat(np.arange(len(genes)), n_lines)
+                first = np.concatenate([[0], np.cumsum(n_lines)[:-1]])
+                A, T = np.add.reduceat(a, first), np.add.reduceat(t, first)
+                Al, Tl = A[rec_of], T[rec_of]
+                Bl = Tl - Al
+                N = (a * Tl - t * Al).astype(np.float64)
+                ab = Al.astype(np.float64) * Bl.astype(np.float64)
+                p_val = (1 + n_ge) / (1 + n_perm)
+                gene_ge = np.array([g[3] for g in genes], dtype=np.int64)
+                gene_p = (1 + gene_ge) / (1 + n_perm)
+                gene_adj = _bh(gene_p)
+                cols = [[genes[g][0] for g in rec_of.tolist()], lines["pa"],
+                        [repr(v) for v in (nz1 / n1).tolist()], [repr(v) for v in (nz2 / n2).tolist()],
+                        [versus] * len(t)]
+                stat0 = np.array([g[2] for g in genes])
+                for v in (a / Al, (t - a) / Bl, N / ab):
+                    cols.append([repr(x) for x in v.tolist()])
+                cols.append(n_ge.tolist())
+                for v in (p_val, _bh(p_val), stat0[rec_of]):
+                    cols.append([repr(x) for x in v.tolist()])
+                cols.append(gene_ge[rec_of].tolist())
+                for v in (gene_p[rec_of], gene_adj[rec_of]):
+                    cols.append([repr(x) for x in v.tolist()])
+                cols.append([n_perm] * len(t))
+                w.writerows(zip(*cols))
+            times["finish"] += timer() - t0
+        os.replace(tmp, outpath)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        if ctx is not None:
+            ctx.lib.scape_hip_report_free(ctx.h)
+    end_t = timer()
+    LAST_TIMES.clear()
+    LAST_TIMES.update(times)
+    LAST_TIMES["total"] = end_t - start_t
+    print(f"Finish {n_perm} permutations of {n1} + {n2} cells for {sum(g[1] for g in genes)} pA sites of "
+          f"{len(genes)} tested records")
+    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
+    return outpath
+
+
 # ---------------------------------------------------------------- cal_exp_pa_len
 def _exp_len_rows(K, alpha_arr, counts):
     """exp_pa_len (apa_core.py:1038-1052) for every row of counts [groups, K + 1] (slot K: reads with label >= K);
@@ -810,3 +1028,25 @@ def ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str,
     """pA x pseudo-replicate read counts (the input of DEXSeq) and the share of each population's cells with a read
     per pA site, from res.gene.pkl / res.utr.pkl and a cell cluster file (reference DifferentialTest.R:63-104, :159-184)."""
     _ex_pa_pseudobulk(output_dir, res_pkl_file, cell_cluster_file, num_splits, idents_1, idents_2)
+
+
+@click.command(name="diff_pa")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the '
+                   'final result.')
+@click.option('--cell_cluster_file', type=str, required=True,
+              help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
+                   'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
+                   'name of the final result.')
+@click.option('--idents_1', type=str, required=True, help='The cluster of population 1.')
+@click.option('--idents_2', type=str, default=None,
+              help='The cluster of population 2. Default: every other cell that has a cluster.')
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True, help='Seed of the permutations, 0 .. 2^64 - 1.')
+def diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_perm: int, seed: int):
+    """pA sites used differently by two cell populations: a permutation test of the cell labels on the pA x cell counts
+    of res.gene.pkl / res.utr.pkl (the question of the reference's FindDE, DifferentialTest.R:159-196, without DEXSeq)."""
+    _diff_pa(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed)
