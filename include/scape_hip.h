@@ -223,6 +223,26 @@ int scape_hip_report_perm_masks(scape_hip_ctx *ctx, int32_t n1, int32_t n2, int6
 int scape_hip_report_perm_test(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                                int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                int64_t *gene_n_ge_out);
+/* diff_pa_len: permutation test of a record's mean pA position between the two populations, on the counts call, the
+   masks call, the kept rows and the labellings of scape_hip_report_perm_test (same seed = same labellings).  Kept row i
+   carries the weight w[i] = x_i - min x over its record's rows, x_i the row's position (alpha_arr[label], f64: larger =
+   more distal = longer 3'UTR), so 0 <= w[i] <= span = max x - min x; tol[r] = 2^-40 * span of record r.  Under a
+   labelling with row sums a_i over population 1 and b_i = t_i - a_i (formed as an integer), A = sum a_i, B = sum b_i,
+   the device forms in f64, contraction off, rows in order,
+     W1 = sum_i (double)a_i * w_i,  W2 = sum_i (double)b_i * w_i,  delta = W1 / A - W2 / B   (0 when A = 0 or B = 0)
+   through one device function for the observed labelling and every permutation; delta = mean_pos.1 - mean_pos.2 (the
+   shift by min x cancels), > 0 when population 1's reads end further out.  delta0_out[r] = delta of the observed
+   labelling, t_out / a0_out as for perm_test.  The call ADDS to n_ge_out[r] the number of its permutations with
+   |delta(p)| >= |delta(0)| - tol[r] (two-sided; the caller zeroes the array before the first chunk of permutations).
+   Each mean is within (R + 1) 2^-53 span of its exact value for R rows, delta within (2 R + 3) 2^-53 span, and a
+   record may own at most 1,024 rows (checked), so the observed and a permuted |delta| and the threshold's subtraction
+   are together off by at most 4,103 * 2^-53 span, about half of tol: a labelling whose exact |delta| reaches the observed
+   one is always counted, one more than 2 tol below it never (derivation: csrc/report.inc above k_rep_perm_len).  The
+   band is absolute, not relative as in perm_test, because delta is a difference of two means and can cancel.
+   w and tol must be finite and not negative. */
+int scape_hip_report_perm_len(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                              const double *w, const double *tol, int64_t *t_out, int64_t *a0_out, double *delta0_out,
+                              int64_t *n_ge_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

@@ -28,6 +28,8 @@
 //                   64-bit key, one workgroup per permutation), the nonzeros (position, count) of the kept count rows,
 //                   and the permutation test itself (one lane per permutation, exceedance counts per site and record);
 //                   section "permutation test" at the end of this file
+//   k_rep_perm_len  diff_pa_len: the same walk for the record's mean pA position in the two populations (one lane per
+//                   permutation, two f64 sums and two integer sums per lane, exceedance counts per record)
 // Cluster names, their order and the floating-point finish of exp_pa_len stay on the host (scape_amd/report.py).
 
 #define REP_THREADS 256
@@ -49,6 +51,7 @@ struct ReportState {
     // diff_pa: membership bits of the last scape_hip_report_perm_masks call ([column word][permutation]) and the
     // buffers of scape_hip_report_perm_test
     DevBuf m_bits, p_rows, p_roff, p_nnz, p_noff, p_nz, p_t, p_a0, p_recs, p_site, p_gene, p_stat0;
+    DevBuf l_w, l_tol;                 // diff_pa_len: row weights and record tolerances of scape_hip_report_perm_len
     int32_t m_n1 = 0, m_n2 = 0, m_count = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
@@ -75,7 +78,7 @@ static void report_release(scape_hip_ctx *c) {
                      &s->s_roff[1], &s->s_out[0], &s->s_out[1], &s->s_nnz[0], &s->s_nnz[1], &s->s_noff[0],
                      &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz, &s->m_bits, &s->p_rows,
                      &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
-                     &s->p_stat0};
+                     &s->p_stat0, &s->l_w, &s->l_tol};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;
@@ -969,7 +972,139 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_test(
     if (tile == 0 && threadIdx.x == 0) stat0[r] = S0;
 }
 
+// ---- diff_pa_len: mean pA position ------------------------------------------------------------------------------------
+// Row i of a record carries the weight w_i = x_i - min x of its pA position (f64, 0 <= w_i <= span = max x - min x).
+// Under a labelling with row sums a_i (population 1) and b_i = t_i - a_i (population 2), A = sum a_i, B = sum b_i:
+//   W1 = sum_i (double)a_i * w_i,  W2 = sum_i (double)b_i * w_i   (rows in order; b_i is formed as an integer, NOT
+//   W - W1, which cancels when B is small against T),   delta = W1 / A - W2 / B,   0 when A = 0 or B = 0.
+// Rounding of the code below (contraction off, unit roundoff u = 2^-53, R rows):
+//   * (double)a_i is exact (a_i < 2^31) and a_i * w_i rounds by at most u a_i w_i: all products together by at most
+//     u sum a_i w_i <= u A span;
+//   * the first addition (0 + product) is exact, each of the other R - 1 rounds by at most u times a partial sum that
+//     is at most A span (1 + R u);
+//   so |W1 - exact| <= R u A span up to second order.  (double)A is exact and the division rounds by u times a quotient
+//   of at most span: each mean is within (R + 1) u span of the mean of the w_i as passed.  The subtraction rounds by at
+//   most u span more: |delta - exact| <= (2 R + 3) u span =: e, for the observed labelling and for every permutation.
+// The test counts a permutation when |delta(p)| >= |delta(0)| - tol, tol = 2^-40 span, and the threshold's own
+// subtraction rounds by at most u span.  A labelling whose exact |delta| reaches the observed one is counted whatever
+// the rounding, and one more than 2 tol below it never is, as long as 2 e + u span <= tol.  With R <= 1,024
+// (REP_LEN_MAX_ROWS, checked by the entry point) 2 e + u span = (4 R + 7) u span = 4,103 * 2^-53 span, 1.002 * 2^-41
+// span: half of tol.  (The host's own rounding of w_i = x_i - min x, at most u span per row and therefore per mean,
+// and of tol fit into the other half many times over.)
+#define REP_LEN_MAX_ROWS 1024
+
+// one row's share of the four sums of a labelling; the observed labelling and every permutation go through this function
+// and rep_len_delta, with contraction off, so equal integers give equal doubles
+__device__ __forceinline__ void rep_len_row(int a, int t, double w, double *W1, double *W2, long long *A,
+                                            long long *B) {
+#pragma clang fp contract(off)
+    const int b = t - a;          // a <= t < 2^31 (the entry point refuses a record with 2^31 reads or more)
+    *W1 = *W1 + (double)a * w;
+    *W2 = *W2 + (double)b * w;
+    *A += a;
+    *B += b;
+}
+
+__device__ __forceinline__ double rep_len_delta(double W1, double W2, long long A, long long B) {
+#pragma clang fp contract(off)
+    if (A == 0 || B == 0) return 0.0;
+    return W1 / (double)A - W2 / (double)B;
+}
+
+// workgroup = (record blockIdx.x / n_tiles, tile of 256 permutations), one lane per permutation.  W1, W2, A and B
+// accumulate in the one walk over the record's rows (registers only: no LDS, any number of rows in one launch);
+// t, a0 and w of a row are wave-uniform loads.  Exceedances are counted per wave (ballot) and added with one atomic
+// per wave.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len(
+    const unsigned long long *__restrict__ bits, int32_t p_count, int32_t n_tiles, const int64_t *__restrict__ roff,
+    const int64_t *__restrict__ noff, const uint2 *__restrict__ nz, const int64_t *__restrict__ t,
+    const int64_t *__restrict__ a0, const double *__restrict__ w, const double *__restrict__ tol,
+    int32_t *__restrict__ n_ge, double *__restrict__ delta0) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const unsigned long long *mb = bits + (valid ? p : p_count - 1);
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    double W1 = 0.0, W2 = 0.0, V1 = 0.0, V2 = 0.0;
+    long long A = 0, B = 0, A0 = 0, B0 = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        const int ti = (int)t[i];
+        const double wi = w[i];
+        rep_len_row(rep_perm_rowsum(nz, noff[i], noff[i + 1], mb, p_count), ti, wi, &W1, &W2, &A, &B);
+        rep_len_row((int)a0[i], ti, wi, &V1, &V2, &A0, &B0);
+    }
+    const double d = rep_len_delta(W1, W2, A, B), d0 = rep_len_delta(V1, V2, A0, B0);
+    const unsigned long long b = __ballot(valid && fabs(d) >= fabs(d0) - tol[r]);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&n_ge[r], __popcll(b));
+    if (tile == 0 && threadIdx.x == 0) delta0[r] = d0;
+}
+
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
+
+// the part scape_hip_report_perm_test and scape_hip_report_perm_len share: the checks (outs_ok = the caller's own
+// other pointers are there; max_rec_rows > 0: a record may own at most that many rows; w / tol, when given, must be
+// finite and not negative), all of them before anything is queued on the device, then the upload of rows and offsets
+// and the compaction of the kept rows to their nonzeros (p_noff / p_nz), with t and a0 of every row on the host
+static int rep_perm_prepare(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                            int64_t *t_out, int64_t *a0_out, bool outs_ok, int64_t max_rec_rows, const double *w,
+                            const double *tol, int64_t *n_rows_out, int32_t *n_tiles_out) {
+    ReportState *s = c->rep;
+    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
+    if (!s->m_count) return fail("scape_hip_report_perm_masks has not been called");
+    if (n_rec <= 0 || !rec_row_off || !rows || !t_out || !a0_out || !outs_ok) return fail("bad argument");
+    const int32_t n1 = s->m_n1, n = s->m_n1 + s->m_n2;
+    if (n > s->n_cols) return fail("the count matrix has fewer columns than the masks have positions");
+    if (rec_row_off[0] != 0) return fail("rec_row_off must start at 0");
+    for (int r = 0; r < n_rec; ++r)
+        if (rec_row_off[r + 1] < rec_row_off[r]) return fail("rec_row_off must be non-decreasing");
+    const int64_t n_rows = rec_row_off[n_rec];
+    if (n_rows <= 0 || n_rows > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
+    if (max_rec_rows > 0)
+        for (int r = 0; r < n_rec; ++r)
+            if (rec_row_off[r + 1] - rec_row_off[r] > max_rec_rows)
+                return fail("record " + std::to_string(r) + ": more than " + std::to_string(max_rec_rows) + " rows");
+    for (int64_t i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
+    const int32_t n_tiles = (s->m_count + REP_THREADS - 1) / REP_THREADS;
+    if ((int64_t)n_rec * n_tiles > INT32_MAX) return fail("too many records x permutation tiles for one call");
+    for (int64_t i = 0; w && i < n_rows; ++i)
+        if (!(w[i] >= 0.0) || std::isinf(w[i])) return fail("row weights must be finite and not negative");
+    for (int r = 0; tol && r < n_rec; ++r)
+        if (!(tol[r] >= 0.0) || std::isinf(tol[r])) return fail("tolerances must be finite and not negative");
+
+    if (s->p_rows.ensure(n_rows * 8) || s->p_roff.ensure(((int64_t)n_rec + 1) * 8) || s->p_nnz.ensure(n_rows * 8) ||
+        s->p_noff.ensure((n_rows + 1) * 8) || s->p_t.ensure(n_rows * 8) || s->p_a0.ensure(n_rows * 8) ||
+        s->p_gene.ensure((int64_t)n_rec * 4) || s->p_stat0.ensure((int64_t)n_rec * 8))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->p_rows.p, rows, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->p_roff.p, rec_row_off, ((int64_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_perm_rowstat, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
+                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n1, n, s->p_nnz.as<int64_t>(),
+                       s->p_t.as<int64_t>(), s->p_a0.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->p_nnz.as<int64_t>(),
+                       (int32_t)n_rows, s->p_noff.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, s->p_noff.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(t_out, s->p_t.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(a0_out, s->p_a0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < n_rec; ++r) {
+        int64_t T = 0;
+        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) T += t_out[i];
+        if (T > INT32_MAX) return fail("record " + std::to_string(r) + ": 2^31 or more reads in the tested cells");
+    }
+    if (s->p_nz.ensure(std::max<int64_t>(total, 1) * 8)) return 1;
+    hipLaunchKernelGGL(k_rep_perm_fill, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
+                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n, s->p_noff.as<int64_t>(),
+                       s->p_nz.as<uint2>());
+    HIPCHK(hipGetLastError());
+    *n_rows_out = n_rows;
+    *n_tiles_out = n_tiles;
+    return 0;
+}
 
 extern "C" {
 
@@ -998,52 +1133,13 @@ int scape_hip_report_perm_test(scape_hip_ctx *c, int32_t n_rec, const int64_t *r
                                int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                int64_t *gene_n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
-    if (!s->m_count) return fail("scape_hip_report_perm_masks has not been called");
-    if (n_rec <= 0 || !rec_row_off || !rows || !t_out || !a0_out || !site_n_ge_out || !stat0_out || !gene_n_ge_out)
-        return fail("bad argument");
-    const int32_t n1 = s->m_n1, n = s->m_n1 + s->m_n2;
-    if (n > s->n_cols) return fail("the count matrix has fewer columns than the masks have positions");
-    if (rec_row_off[0] != 0) return fail("rec_row_off must start at 0");
-    for (int r = 0; r < n_rec; ++r)
-        if (rec_row_off[r + 1] < rec_row_off[r]) return fail("rec_row_off must be non-decreasing");
-    const int64_t n_rows = rec_row_off[n_rec];
-    if (n_rows <= 0 || n_rows > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
-    for (int64_t i = 0; i < n_rows; ++i)
-        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
-    const int32_t n_tiles = (s->m_count + REP_THREADS - 1) / REP_THREADS;
-    if ((int64_t)n_rec * n_tiles > INT32_MAX) return fail("too many records x permutation tiles for one call");
-
-    if (s->p_rows.ensure(n_rows * 8) || s->p_roff.ensure(((int64_t)n_rec + 1) * 8) || s->p_nnz.ensure(n_rows * 8) ||
-        s->p_noff.ensure((n_rows + 1) * 8) || s->p_t.ensure(n_rows * 8) || s->p_a0.ensure(n_rows * 8) ||
-        s->p_recs.ensure((int64_t)n_rec * 4) || s->p_site.ensure(n_rows * 4) || s->p_gene.ensure((int64_t)n_rec * 4) ||
-        s->p_stat0.ensure((int64_t)n_rec * 8))
+    int64_t n_rows = 0;
+    int32_t n_tiles = 0;
+    if (rep_perm_prepare(c, n_rec, rec_row_off, rows, t_out, a0_out, site_n_ge_out && stat0_out && gene_n_ge_out, 0,
+                         nullptr, nullptr, &n_rows, &n_tiles))
         return 1;
-    HIPCHK(hipMemcpyAsync(s->p_rows.p, rows, n_rows * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(s->p_roff.p, rec_row_off, ((int64_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_rep_perm_rowstat, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
-                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n1, n, s->p_nnz.as<int64_t>(),
-                       s->p_t.as<int64_t>(), s->p_a0.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->p_nnz.as<int64_t>(),
-                       (int32_t)n_rows, s->p_noff.as<int64_t>());
-    HIPCHK(hipGetLastError());
-    int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, s->p_noff.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(t_out, s->p_t.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(a0_out, s->p_a0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < n_rec; ++r) {
-        int64_t T = 0;
-        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) T += t_out[i];
-        if (T > INT32_MAX) return fail("record " + std::to_string(r) + ": 2^31 or more reads in the tested cells");
-    }
-    if (s->p_nz.ensure(std::max<int64_t>(total, 1) * 8)) return 1;
-    hipLaunchKernelGGL(k_rep_perm_fill, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
-                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n, s->p_noff.as<int64_t>(),
-                       s->p_nz.as<uint2>());
-    HIPCHK(hipGetLastError());
+    ReportState *s = c->rep;
+    if (s->p_recs.ensure((int64_t)n_rec * 4) || s->p_site.ensure(n_rows * 4)) return 1;
 
     // records by LDS class: the smallest cap that holds all their rows (the largest cap takes the rest, in groups)
     const int n_caps = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
@@ -1081,6 +1177,33 @@ int scape_hip_report_perm_test(scape_hip_ctx *c, int32_t n_rec, const int64_t *r
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n_rows; ++i) site_n_ge_out[i] += site[i];
     for (int r = 0; r < n_rec; ++r) gene_n_ge_out[r] += gene[r];
+    return 0;
+}
+
+int scape_hip_report_perm_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                              const double *w, const double *tol, int64_t *t_out, int64_t *a0_out, double *delta0_out,
+                              int64_t *n_ge_out) {
+    CTX_ENTER(c);
+    int64_t n_rows = 0;
+    int32_t n_tiles = 0;
+    if (rep_perm_prepare(c, n_rec, rec_row_off, rows, t_out, a0_out, w && tol && delta0_out && n_ge_out,
+                         REP_LEN_MAX_ROWS, w, tol, &n_rows, &n_tiles))
+        return 1;
+    ReportState *s = c->rep;
+    if (s->l_w.ensure(n_rows * 8) || s->l_tol.ensure((int64_t)n_rec * 8)) return 1;
+    HIPCHK(hipMemcpyAsync(s->l_w.p, w, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->l_tol.p, tol, (int64_t)n_rec * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(s->p_gene.p, 0, (int64_t)n_rec * 4, c->stream));
+    hipLaunchKernelGGL(k_rep_perm_len, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), 0, c->stream,
+                       s->m_bits.as<unsigned long long>(), s->m_count, n_tiles, s->p_roff.as<int64_t>(),
+                       s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->p_a0.as<int64_t>(),
+                       s->l_w.as<double>(), s->l_tol.as<double>(), s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> ge(n_rec);
+    HIPCHK(hipMemcpyAsync(ge.data(), s->p_gene.p, (int64_t)n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(delta0_out, s->p_stat0.p, (int64_t)n_rec * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < n_rec; ++r) n_ge_out[r] += ge[r];
     return 0;
 }
 

@@ -1,4 +1,4 @@
-"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk`` and ``scape diff_pa``: the stages after ``merge_pa`` (reference
+"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa`` and ``scape diff_pa_len``: the stages after ``merge_pa`` (reference
 ``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of
 ``apa_core.py:1038-1063``).
 
@@ -21,6 +21,10 @@ Both stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``
   below states the test).  The device builds the permutations' membership bits, compacts the count rows to their
   nonzeros and counts, per site and record, the permutations whose statistic reaches the observed one; the host
   turns the integers into p-values, Benjamini-Hochberg adjusted, and writes one csv.
+* ``diff_pa_len``: whether one of the two populations uses longer 3'UTRs, per gene: the same populations, kept rows and
+  label permutations as ``diff_pa`` (they share the code), tested on the difference of the mean pA position (section
+  diff_pa_len below).  The device walks the same membership bits with one weighted sum per population; the host adds
+  the exact means and the reference's ``exp_pa_len`` of both populations.
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -37,7 +41,9 @@ import shutil
 import tempfile
 import zlib
 from concurrent.futures import ThreadPoolExecutor
+from fractions import Fraction
 from timeit import default_timer as timer
+from types import SimpleNamespace
 
 import click
 import numpy as np
@@ -655,10 +661,11 @@ def _perm_masks(ctx, n1, n2, p_first, p_count, seed, times):
     times["render"] += timer() - t0
 
 
-def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, genes, times):
-    """one counted batch: the kept rows of its tested records go through the permutation test; appends the per-line
-    integers to `lines` and the per-record ones to `genes`"""
-    n1, n2 = int(seg_off[1]), int(seg_off[2] - seg_off[1])
+def _perm_rows(ctx, recs, K, row_tot, seg_off, times, each_kept=None):
+    """the tested records of one counted batch and their kept rows: (batch indices of the tested records, row offsets
+    per tested record, count rows, cells with a count above 0 per row and population, sums per row and population),
+    or None when no record of the batch is tested.  each_kept(r, labels), when given, is called for every record of
+    K >= 2 that has a kept row, tested or not, with the labels of its kept rows"""
     cand, owner = [], []
     base = 0
     for r in range(len(recs)):
@@ -669,7 +676,7 @@ def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, g
         base += k
     cand, owner = np.concatenate(cand).astype(np.int64), np.concatenate(owner)
     if not len(cand):
-        return
+        return None
     sums = np.zeros((len(cand), 2), dtype=np.int32)
     nz = np.zeros((len(cand), 2), dtype=np.int32)
     t0 = timer()
@@ -680,30 +687,52 @@ def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, g
     sums = sums.astype(np.int64)
     keep = sums.sum(axis=1) > 0
     n_kept = np.bincount(owner[keep], minlength=len(recs))
+    if each_kept is not None:
+        rowbase = np.cumsum(K, dtype=np.int64) - K
+        cut = np.cumsum(n_kept)
+        labs = cand[keep] - rowbase[owner[keep]]
+        for r in np.nonzero((n_kept > 0) & (K >= 2))[0].tolist():
+            each_kept(r, labs[cut[r] - n_kept[r]:cut[r]])
     A = np.bincount(owner, weights=sums[:, 0], minlength=len(recs))
     B = np.bincount(owner, weights=sums[:, 1], minlength=len(recs))
     tested = (n_kept >= 2) & (A > 0) & (B > 0)
     keep &= tested[owner]
-    rows, owner, nz = cand[keep], owner[keep], nz[keep]
     which = np.nonzero(tested)[0]
     times["finish"] += timer() - t0
     if not len(which):
-        return
+        return None
     off = np.zeros(len(which) + 1, dtype=np.int64)
     np.cumsum(n_kept[which], out=off[1:])
-    t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
-    site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
-    stat0 = np.zeros(len(which), np.float64)
+    return which, off, cand[keep], nz[keep], sums[keep]
+
+
+def _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, test):
+    """test() once per chunk of permutations, behind that chunk's masks"""
+    n1, n2 = int(seg_off[1]), int(seg_off[2] - seg_off[1])
     for p_first in range(1, n_perm + 1, chunk):
         if chunk < n_perm:       # otherwise the one set of masks was built before the first batch
             _perm_masks(ctx, n1, n2, p_first, min(chunk, n_perm + 1 - p_first), seed, times)
         t0 = timer()
-        check(ctx.lib.scape_hip_report_perm_test(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(t, P_i64),
-                                                 ptr(a0, P_i64), ptr(site_ge, P_i64), ptr(stat0), ptr(gene_ge, P_i64)),
-              "report_perm_test")
+        test()
         times["render"] += timer() - t0
+
+
+def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, genes, times):
+    """one counted batch: the kept rows of its tested records go through the permutation test; appends the per-line
+    integers to `lines` and the per-record ones to `genes`"""
+    sel = _perm_rows(ctx, recs, K, row_tot, seg_off, times)
+    if sel is None:
+        return
+    which, off, rows, nz, sums = sel
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
+    site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
+    stat0 = np.zeros(len(which), np.float64)
+    _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, lambda: check(
+        ctx.lib.scape_hip_report_perm_test(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(t, P_i64),
+                                           ptr(a0, P_i64), ptr(site_ge, P_i64), ptr(stat0), ptr(gene_ge, P_i64)),
+        "report_perm_test"))
     t0 = timer()
-    if not (np.array_equal(t, sums[keep].sum(axis=1)) and np.array_equal(a0, sums[keep][:, 0])):
+    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums[:, 0])):
         raise _lib.ScapeHipError("report_perm_test: row sums differ from report_group_sums")
     rowbase = np.cumsum(K, dtype=np.int64) - K
     for g, r in enumerate(which.tolist()):
@@ -719,10 +748,10 @@ def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, g
     times["finish"] += timer() - t0
 
 
-def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
-             n_perm: int = 9999, seed: int = 1, device=None):
-    """permutation test of pA usage between the cells of cluster idents_1 and those of idents_2 (None: every other cell
-    that has a cluster); writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.diff_pa.csv in output_dir, returns its path"""
+def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, command):
+    """what diff_pa and diff_pa_len do before the device is opened: the argument and prerequisite checks, the two
+    populations, the id -> column table that puts population 1's columns first and population 2's behind them, and the
+    output path <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.<command>.csv"""
     import pandas as pd
     if idents_1 is None:
         raise ValueError("idents_1 is required")
@@ -757,70 +786,45 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
     _table, slot, seg_off, _seg_pop = _samples(pops, 1, n_cols)      # population 1's columns first, then population 2's
     n1, n2 = len(pops[0][1]), len(pops[1][1])
     if n1 + n2 >= MAX_PERM_CELLS:
-        raise ValueError(f"{n1 + n2} tested cells: diff_pa takes fewer than {MAX_PERM_CELLS}")
-    idmap = _IdMap(col_ids, slot, "barcode_index.csv")
-    versus = f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1)
-
+        raise ValueError(f"{n1 + n2} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     tag = f".{idents_1}_vs_{idents_2 if idents_2 is not None else 'rest'}"
     if os.sep in tag:
         raise ValueError(f"an ident with {os.sep!r} cannot be part of a file name")
     outpath = os.path.join(output_dir, os.path.splitext(os.path.basename(cell_cluster_file))[0] + "." +
-                           res_pkl_file.replace(".pkl", "").replace("res.", "") + tag + ".diff_pa.csv")
-    tmp = _atomic_target(outpath)
+                           res_pkl_file.replace(".pkl", "").replace("res.", "") + tag + f".{command}.csv")
+    return SimpleNamespace(res_pkl=res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
+                           idmap=_IdMap(col_ids, slot, "barcode_index.csv"),
+                           versus=f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1))
 
+
+def _perm_run(su, n_perm, seed, device, batch, write):
+    """the run both commands share: the masks (once, when all permutations fit MAX_PERM_BYTES; otherwise per chunk inside
+    every batch), batch(ctx, recs, K, row_tot, chunk, times) per counted batch, then write(csv writer) into the .part
+    file that is renamed when complete.  Returns the wall seconds; LAST_TIMES holds the stages"""
+    tmp = _atomic_target(su.outpath)
     times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
     start_t = timer()
     ctx = None
-    lines = {k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}
-    genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
     try:
         with open(tmp, "w", newline="") as fh:
             ctx = _lib.default_context(device)
             budget = _budget(ctx)
-            word_bytes = (n1 + n2 + 63) // 64 * 8
+            word_bytes = (su.n1 + su.n2 + 63) // 64 * 8
             perm_bytes = int(MAX_PERM_BYTES) if MAX_PERM_BYTES is not None else budget // 2
             chunk = max(1, min(n_perm, perm_bytes // word_bytes))
             if chunk == n_perm:
-                _perm_masks(ctx, n1, n2, 1, n_perm, seed, times)
+                _perm_masks(ctx, su.n1, su.n2, 1, n_perm, seed, times)
             if MAX_BATCH_BYTES is None:
                 budget //= 2
             # the counts of a record and, at worst, as many 8-byte nonzeros as it has tested counts
-            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 12 + len(p.label_arr) * 16 + 64, budget, times):
-                K, row_tot, _complete = _count(ctx, recs, idmap, n_cols, times)
-                _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, genes, times)
+            for recs in _batches(su.res_pkl, lambda p: int(p.K) * su.n_cols * 12 + len(p.label_arr) * 16 + 64, budget,
+                                 times):
+                K, row_tot, _complete = _count(ctx, recs, su.idmap, su.n_cols, times)
+                batch(ctx, recs, K, row_tot, chunk, times)
             t0 = timer()
-            w = csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n')
-            w.writerow(DIFF_PA_HEADER)
-            if genes:
-                t, a, nz1, nz2, n_ge = (np.concatenate(lines[k]) for k in ("t", "a", "nz1", "nz2", "n_ge"))
-                n_lines = np.array([g[1] for g in genes], dtype=np.int64)
-                rec_of = np.repeat(np.arange(len(genes)), n_lines)
-                first = np.concatenate([[0], np.cumsum(n_lines)[:-1]])
-                A, T = np.add.reduceat(a, first), np.add.reduceat(t, first)
-                Al, Tl = A[rec_of], T[rec_of]
-                Bl = Tl - Al
-                N = (a * Tl - t * Al).astype(np.float64)
-                ab = Al.astype(np.float64) * Bl.astype(np.float64)
-                p_val = (1 + n_ge) / (1 + n_perm)
-                gene_ge = np.array([g[3] for g in genes], dtype=np.int64)
-                gene_p = (1 + gene_ge) / (1 + n_perm)
-                gene_adj = _bh(gene_p)
-                cols = [[genes[g][0] for g in rec_of.tolist()], lines["pa"],
-                        [repr(v) for v in (nz1 / n1).tolist()], [repr(v) for v in (nz2 / n2).tolist()],
-                        [versus] * len(t)]
-                stat0 = np.array([g[2] for g in genes])
-                for v in (a / Al, (t - a) / Bl, N / ab):
-                    cols.append([repr(x) for x in v.tolist()])
-                cols.append(n_ge.tolist())
-                for v in (p_val, _bh(p_val), stat0[rec_of]):
-                    cols.append([repr(x) for x in v.tolist()])
-                cols.append(gene_ge[rec_of].tolist())
-                for v in (gene_p[rec_of], gene_adj[rec_of]):
-                    cols.append([repr(x) for x in v.tolist()])
-                cols.append([n_perm] * len(t))
-                w.writerows(zip(*cols))
+            write(csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n'))
             times["finish"] += timer() - t0
-        os.replace(tmp, outpath)
+        os.replace(tmp, su.outpath)
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
@@ -830,10 +834,185 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
     LAST_TIMES.clear()
     LAST_TIMES.update(times)
     LAST_TIMES["total"] = end_t - start_t
+    return end_t - start_t
+
+
+def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
+             n_perm: int = 9999, seed: int = 1, device=None):
+    """permutation test of pA usage between the cells of cluster idents_1 and those of idents_2 (None: every other cell
+    that has a cluster); writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.diff_pa.csv in output_dir, returns its path"""
+    su = _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, "diff_pa")
+    n1, n2, versus = su.n1, su.n2, su.versus
+    lines = {k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}
+    genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
+
+    def batch(ctx, recs, K, row_tot, chunk, times):
+        _diff_pa_batch(ctx, recs, K, row_tot, su.seg_off, n_perm, chunk, seed, lines, genes, times)
+
+    def write(w):
+        w.writerow(DIFF_PA_HEADER)
+        if not genes:
+            return
+        t, a, nz1, nz2, n_ge = (np.concatenate(lines[k]) for k in ("t", "a", "nz1", "nz2", "n_ge"))
+        n_lines = np.array([g[1] for g in genes], dtype=np.int64)
+        rec_of = np.repeat(np.arange(len(genes)), n_lines)
+        first = np.concatenate([[0], np.cumsum(n_lines)[:-1]])
+        A, T = np.add.reduceat(a, first), np.add.reduceat(t, first)
+        Al, Tl = A[rec_of], T[rec_of]
+        Bl = Tl - Al
+        N = (a * Tl - t * Al).astype(np.float64)
+        ab = Al.astype(np.float64) * Bl.astype(np.float64)
+        p_val = (1 + n_ge) / (1 + n_perm)
+        gene_ge = np.array([g[3] for g in genes], dtype=np.int64)
+        gene_p = (1 + gene_ge) / (1 + n_perm)
+        gene_adj = _bh(gene_p)
+        cols = [[genes[g][0] for g in rec_of.tolist()], lines["pa"],
+                [repr(v) for v in (nz1 / n1).tolist()], [repr(v) for v in (nz2 / n2).tolist()],
+                [versus] * len(t)]
+        stat0 = np.array([g[2] for g in genes])
+        for v in (a / Al, (t - a) / Bl, N / ab):
+            cols.append([repr(x) for x in v.tolist()])
+        cols.append(n_ge.tolist())
+        for v in (p_val, _bh(p_val), stat0[rec_of]):
+            cols.append([repr(x) for x in v.tolist()])
+        cols.append(gene_ge[rec_of].tolist())
+        for v in (gene_p[rec_of], gene_adj[rec_of]):
+            cols.append([repr(x) for x in v.tolist()])
+        cols.append([n_perm] * len(t))
+        w.writerows(zip(*cols))
+
+    wall = _perm_run(su, n_perm, seed, device, batch, write)
     print(f"Finish {n_perm} permutations of {n1} + {n2} cells for {sum(g[1] for g in genes)} pA sites of "
           f"{len(genes)} tested records")
-    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
-    return outpath
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- diff_pa_len
+# Does one population use longer 3'UTRs than the other?  Populations, tested columns, kept rows and permutations are
+# diff_pa's (same --seed = same labellings).  Kept row i of a record has the position x_i = alpha_arr[label_i] (f64,
+# nucleotides from the UTR's 5' end along the transcript on either strand; _pa_info turns the same number into the
+# genomic loc), so larger = more distal = longer 3'UTR.  With a_i / b_i = t_i - a_i a row's sums over population 1 / 2
+# under a labelling, A = sum a_i, B = sum b_i:
+#     mean_pos.1 = sum a_i x_i / A,   mean_pos.2 = sum b_i x_i / B,   delta = mean_pos.1 - mean_pos.2
+# (delta = 0 when A = 0 or B = 0; delta > 0: population 1's reads end further out).  Two-sided on |delta|:
+# n_ge = #{p in 1..n_perm: |delta(p)| >= |delta(0)| - tol}, tol = 2^-40 span, span = max x_i - min x_i over the kept rows;
+# p_val = (1 + n_ge) / (1 + n_perm), Benjamini-Hochberg over the file's lines.  The reference's own scale (exp_pa_len's
+# 1 + 9 (a - a[0]) / (a[-1] - a[0])) is an affine map of x, so a two-sided test on it is the same test: the file carries
+# both scales and one p-value.  A record is tested when diff_pa would test it (two kept rows or more, reads in both
+# populations) and span > 0; a non-finite position of a kept row of any record with K >= 2 is a ValueError.  The device gets
+# w_i = x_i - min x and tol per record (include/scape_hip.h states its arithmetic and the bound that makes n_ge exact).
+DIFF_PA_LEN_HEADER = ["gene", "versus", "num_pa", "reads.1", "reads.2", "mean_pos.1", "mean_pos.2", "delta_pos",
+                      "exp_length.1", "exp_length.2", "delta_exp_length", "n_ge", "p_val", "p_val_adj", "n_perm"]
+
+
+def _mean_positions(x, a, b):
+    """(mean_pos.1, mean_pos.2, delta_pos) of positions x (finite f64) under the integer row sums a and b: the exact
+    rationals, each rounded once"""
+    ratios = [float(v).as_integer_ratio() for v in x]
+    D = max(d for _n, d in ratios)                       # denominators are powers of two
+    X = [n * (D // d) for n, d in ratios]
+    m1 = Fraction(sum(int(ai) * Xi for ai, Xi in zip(a, X)), int(sum(a)) * D)
+    m2 = Fraction(sum(int(bi) * Xi for bi, Xi in zip(b, X)), int(sum(b)) * D)
+    return float(m1), float(m2), float(m1 - m2)
+
+
+def _diff_pa_len_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, out, times):
+    """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
+    n_ge) per tested record to `out`"""
+    pos = {}                     # record -> positions of its kept rows (f64, finite)
+
+    def positions(r, labs):
+        x = np.asarray(recs[r].alpha_arr, dtype=np.float64)[labs]
+        if not (np.all(np.isfinite(x)) and np.isfinite(x.max() - x.min())):
+            raise ValueError(f"{recs[r].gene_info_str}: alpha_arr holds a non-finite position of a pA site with reads")
+        pos[r] = x
+    sel = _perm_rows(ctx, recs, K, row_tot, seg_off, times, positions)
+    if sel is None:
+        return
+    which, off, rows, _nz, sums = sel
+    t0 = timer()
+    rowbase = np.cumsum(K, dtype=np.int64) - K
+    tested, xs, w, tol = [], [], [], []
+    for g, r in enumerate(which.tolist()):
+        x = pos[r]
+        span = float(x.max() - x.min())
+        if span > 0:
+            tested.append(g)
+            xs.append(x)
+            w.append(x - x.min())
+            tol.append(np.ldexp(span, -40))
+    times["finish"] += timer() - t0
+    if not tested:
+        return
+    n_kept = np.diff(off)[tested]
+    pick = np.concatenate([np.arange(off[g], off[g + 1]) for g in tested])
+    which, rows, sums = which[tested], np.ascontiguousarray(rows[pick]), sums[pick]
+    off = np.zeros(len(which) + 1, dtype=np.int64)
+    np.cumsum(n_kept, out=off[1:])
+    w, tol = np.ascontiguousarray(np.concatenate(w)), np.array(tol, dtype=np.float64)
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
+    delta0, n_ge = np.zeros(len(which), np.float64), np.zeros(len(which), np.int64)
+    _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, lambda: check(
+        ctx.lib.scape_hip_report_perm_len(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(w), ptr(tol),
+                                          ptr(t, P_i64), ptr(a0, P_i64), ptr(delta0), ptr(n_ge, P_i64)),
+        "report_perm_len"))
+    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums[:, 0])):
+        raise _lib.ScapeHipError("report_perm_len: row sums differ from report_group_sums")
+    # the two populations' counts of ALL K labels of the tested records, for the reference's exp_pa_len
+    all_rows = np.concatenate([int(rowbase[r]) + np.arange(int(K[r]), dtype=np.int64) for r in which.tolist()])
+    full = np.zeros((len(all_rows), 2), dtype=np.int32)
+    full_nz = np.zeros((len(all_rows), 2), dtype=np.int32)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_group_sums(ctx.h, 2, ptr(seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
+                                              ptr(full, P_i32), ptr(full_nz, P_i32)), "report_group_sums")
+    times["render"] += timer() - t0
+    t0 = timer()
+    k0 = 0
+    for g, r in enumerate(which.tolist()):
+        sl = slice(int(off[g]), int(off[g + 1]))
+        a, b = a0[sl], t[sl] - a0[sl]
+        m1, m2, d = _mean_positions(xs[g], a.tolist(), b.tolist())
+        if not abs(float(delta0[g]) - d) <= tol[g]:
+            raise _lib.ScapeHipError(f"report_perm_len: {recs[r].gene_info_str}: the device's delta {delta0[g]!r} "
+                                     f"differs from {d!r}")
+        k = int(K[r])
+        counts = np.zeros((2, k + 1), dtype=np.int64)    # slot k: reads of no site, which never weigh
+        counts[:, :k] = full[k0:k0 + k].T
+        k0 += k
+        e = _exp_len_rows(k, recs[r].alpha_arr, counts)
+        out.append((recs[r].gene_info_str, int(off[g + 1] - off[g]), int(a.sum()), int(b.sum()), m1, m2, d,
+                    float(e[0]), float(e[1]), int(n_ge[g])))
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
+                 n_perm: int = 9999, seed: int = 1, device=None):
+    """permutation test of the mean pA position (3'UTR length) between the cells of cluster idents_1 and those of
+    idents_2 (None: every other cell that has a cluster); writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>
+    .diff_pa_len.csv in output_dir, one line per tested record, and returns its path"""
+    su = _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, "diff_pa_len")
+    out = []
+
+    def batch(ctx, recs, K, row_tot, chunk, times):
+        _diff_pa_len_batch(ctx, recs, K, row_tot, su.seg_off, n_perm, chunk, seed, out, times)
+
+    def write(w):
+        w.writerow(DIFF_PA_LEN_HEADER)
+        if not out:
+            return
+        n_ge = np.array([o[9] for o in out], dtype=np.int64)
+        p_val = (1 + n_ge) / (1 + n_perm)
+        with np.errstate(invalid="ignore"):
+            d_exp = np.array([o[7] for o in out]) - np.array([o[8] for o in out])
+        w.writerows([o[0], su.versus, o[1], o[2], o[3]] + [repr(v) for v in o[4:9]] + [repr(de), o[9], repr(p), repr(q),
+                                                                                         n_perm]
+                    for o, de, p, q in zip(out, d_exp.tolist(), p_val.tolist(), _bh(p_val).tolist()))
+
+    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    print(f"Finish {n_perm} permutations of {su.n1} + {su.n2} cells for {len(out)} tested records")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
 
 
 # ---------------------------------------------------------------- cal_exp_pa_len
@@ -1050,3 +1229,29 @@ def diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1
     """pA sites used differently by two cell populations: a permutation test of the cell labels on the pA x cell counts
     of res.gene.pkl / res.utr.pkl (the question of the reference's FindDE, DifferentialTest.R:159-196, without DEXSeq)."""
     _diff_pa(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed)
+
+
+@click.command(name="diff_pa_len")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the '
+                   'final result.')
+@click.option('--cell_cluster_file', type=str, required=True,
+              help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
+                   'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
+                   'name of the final result.')
+@click.option('--idents_1', type=str, required=True, help='The cluster of population 1.')
+@click.option('--idents_2', type=str, default=None,
+              help='The cluster of population 2. Default: every other cell that has a cluster.')
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives the same relabellings of the cells '
+                   'as in diff_pa.')
+def diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_perm: int,
+                seed: int):
+    """3'UTR lengthening or shortening between two cell populations: per gene, a two-sided permutation test of the cell
+    labels on the difference of the mean pA position (delta_pos > 0: population 1 uses longer 3'UTRs), with the
+    reference's expected pA length (cal_exp_pa_len's 1..10 scale) of both populations beside it."""
+    _diff_pa_len(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed)
