@@ -1,9 +1,13 @@
-"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa`` and ``scape diff_pa_len``: the stages after ``merge_pa`` (reference
-``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of
-``apa_core.py:1038-1063``).
+"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa`` and
+``scape diff_pa_len``: the stages after ``merge_pa`` (reference ``src/scape/utils.py:319-427`` and ``:438-553``, with
+``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of ``apa_core.py:1038-1063``).
 
-Both stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
-``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc``:
+All five stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
+``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc``.  They
+share one host core (section "shared host core" below): ``_Run`` frames a command (stage times, ``.part`` targets, the
+device context and its release), ``_read_inputs`` reads what the count-matrix commands need before the device is
+opened, ``_count`` / ``_kept_rows`` give the label rows with reads of a batch, and ``_two_slot_blocks`` overlaps the
+device's rendering of one text block with the gzip of the previous one.
 
 * ``ex_pa_cnt_mat``: the device counts (record, label < K, barcode column), flags the records whose pandas pivot would
   be complete, and renders every CSV row; the host builds the quoted ``pa_info`` prefixes and gzips finished blocks on
@@ -138,8 +142,129 @@ def _raise_bad_read(bad, recs, off, cb, what):
     raise KeyError(f"{recs[r].gene_info_str}: cell barcode id {int(cb[bad[0]])} is not in {what}")
 
 
-def _atomic_target(path):
-    return path + ".part"
+# ---------------------------------------------------------------- shared host core
+class _Run:
+    """frame of one command, a context manager: the stage times and the start timer, one .part target per final path,
+    the device context (opened by device(), after whatever the command does first) and its release.  Leaving the body
+    without an exception renames every .part file to its final path and fills LAST_TIMES; leaving it either way
+    removes the .part files that are left and releases the device"""
+
+    def __init__(self, device, finals):
+        self.finals, self.parts = list(finals), [p + ".part" for p in finals]
+        self._device, self.ctx, self.total = device, None, None
+        self.times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
+
+    def __enter__(self):
+        self.start = timer()
+        return self
+
+    def device(self):
+        self.ctx = _lib.default_context(self._device)
+        return self.ctx
+
+    def release(self):
+        if self.ctx is not None:
+            self.ctx.lib.scape_hip_report_free(self.ctx.h)
+            self.ctx = None
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            if exc_type is None:
+                for tmp, path in zip(self.parts, self.finals):
+                    os.replace(tmp, path)
+        finally:
+            for tmp in self.parts:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+            self.release()
+        if exc_type is None:
+            self.total = timer() - self.start
+            LAST_TIMES.clear()
+            LAST_TIMES.update(self.times)
+            LAST_TIMES["total"] = self.total
+
+
+def _read_inputs(output_dir, res_pkl_file, cell_cluster_file=None, idents=(None, None), with_cb=False):
+    """what ex_pa_cnt_mat and the cluster-aware commands read before the device is opened, after their own argument
+    checks: the paths, barcode_index.csv (the CB column when with_cb, the column ids, the number of columns) and,
+    with a cluster file, the populations of _populations"""
+    import pandas as pd
+    res_pkl = os.path.join(output_dir, res_pkl_file)
+    if not (os.path.exists(output_dir)):
+        raise Exception("Given output_dir folder does not exists.")
+    if not (os.path.exists(res_pkl)):
+        raise Exception(f"Invalid file {res_pkl}. Given res_pkl_file is not in output_dir.")
+    if cell_cluster_file is not None and not (os.path.exists(cell_cluster_file)):
+        raise Exception("Given cell_cluster_file file does not exists")
+    cb_df = pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")
+    cb_lst = cb_df["CB"].tolist() if with_cb else None
+    n_cols = len(cb_df)
+    if n_cols == 0:
+        raise ValueError("barcode_index.csv lists no barcode")
+    col_ids = cb_df.index.to_numpy()
+    if col_ids.dtype.kind not in "iu":
+        raise ValueError("barcode_index.csv: the index column must hold integer ids")
+    pops = None
+    if cell_cluster_file is not None:
+        col_clu, order = _column_clusters(col_ids.astype(np.int64), *_read_clusters(cell_cluster_file))
+        pops = _populations(col_clu, order, *idents)
+    return SimpleNamespace(res_pkl=res_pkl, cb_lst=cb_lst, col_ids=col_ids, n_cols=n_cols, pops=pops)
+
+
+def _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2):
+    """<output_dir>/<cluster file stem>.<gene|utr>[.<A>_vs_<B|rest>]"""
+    tag = "" if idents_1 is None else f".{idents_1}_vs_{idents_2 if idents_2 is not None else 'rest'}"
+    if os.sep in tag:
+        raise ValueError(f"an ident with {os.sep!r} cannot be part of a file name")
+    return os.path.join(output_dir, os.path.splitext(os.path.basename(cell_cluster_file))[0] + "." +
+                        res_pkl_file.replace(".pkl", "").replace("res.", "") + tag)
+
+
+def _batch_cost(n_cols, count_bytes=4):
+    """device bytes of a record: its counts (count_bytes per label and column) and its reads"""
+    return lambda p: int(p.K) * n_cols * count_bytes + len(p.label_arr) * 16 + 64
+
+
+def _count(ctx, recs, idmap, n_cols, times):
+    """a counted batch: the counts stay on the device; the records, K, the row totals and the pivot-complete flags
+    on the host"""
+    t0 = timer()
+    off, K, lab, cb = _record_arrays(recs)
+    row_tot = np.zeros(int(K.sum()), dtype=np.int64)
+    complete = np.zeros(len(recs), dtype=np.int8)
+    bad = np.zeros(2, dtype=np.int64)
+    check(ctx.lib.scape_hip_report_counts(ctx.h, len(recs), ptr(off, P_i64), ptr(K, P_i32), ptr(lab, P_i64),
+                                          ptr(cb, P_i64), idmap.id_min, idmap.span, ptr(idmap.table, P_i32), n_cols,
+                                          ptr(row_tot, P_i64), ptr(complete, P_i8), ptr(bad, P_i64)), "report_counts")
+    times["h2d_counts"] += timer() - t0
+    if bad[0] >= 0 or bad[1] >= 0:
+        _raise_bad_read(bad, recs, off, cb, "barcode_index.csv")
+    return SimpleNamespace(recs=recs, K=K, row_tot=row_tot, complete=complete)
+
+
+def _counted(ctx, res_pkl, idmap, n_cols, cost, budget, times):
+    """the counted batches of a result stream"""
+    for recs in _batches(res_pkl, cost, budget, times):
+        yield _count(ctx, recs, idmap, n_cols, times)
+
+
+def _kept_rows(bat):
+    """the label rows with reads of a counted batch: (first count row of every record, the count rows with reads
+    ascending (int64), the record of each, its label within that record)"""
+    K = bat.K.astype(np.int64)
+    rowbase = np.cumsum(K) - K
+    rows = np.nonzero(bat.row_tot > 0)[0].astype(np.int64)
+    owner = np.repeat(np.arange(len(K), dtype=np.int64), K)[rows]
+    return rowbase, rows, owner, rows - rowbase[owner]
+
+
+def _pa_infos(recs, owner, label):
+    """pa_info of kept rows, in row order (record by record, labels ascending)"""
+    out = []
+    first = np.nonzero(np.diff(owner, prepend=-1))[0].tolist() + [len(owner)]
+    for a, b in zip(first[:-1], first[1:]):
+        out.extend(_pa_info(recs[owner[a]], label[a:b]))
+    return out
 
 
 # ---------------------------------------------------------------- ex_pa_cnt_mat
@@ -185,43 +310,25 @@ class _GzipWriter:
         self.times["gzip_wait"] += timer() - t0
 
 
-def _render_batch(ctx, recs, K, row_tot, complete, n_cols, writer, times):
-    """every row of one counted batch: prefixes on the host, text on the device; block b is gzipped on the pool while
-    the device renders block b + 1 into the other slot"""
-    rows, is_int, pres = [], [], []
-    base = 0
-    for r, para in enumerate(recs):
-        k = int(K[r])
-        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
-        if len(labs):
-            rows.append(base + labs)
-            is_int.append(np.full(len(labs), complete[r], dtype=np.int8))
-            pres.extend(_csv_field(s) for s in _pa_info(para, labs))
-        base += k
-    if not rows:
-        return
-    rows = np.concatenate(rows).astype(np.int64)
-    is_int = np.concatenate(is_int)
-    pre_b = [s.encode() for s in pres]
-    plen = np.array([len(b) for b in pre_b], dtype=np.int64)
-    # rows per block from an upper bound of the row length (every field ',"<10 digits>.0"')
-    per_row = int(plen.max()) + 15 * n_cols + 2
-    step = max(1, min(1 << 20, MAX_BLOCK_BYTES // per_row))
+def _hand_over(ctx, slot, writer, times):
+    hp, nb = ctypes.c_void_p(), ctypes.c_int64(0)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_fetch(ctx.h, slot, ctypes.byref(hp), ctypes.byref(nb)), "report_fetch")
+    times["render"] += timer() - t0
+    writer.submit(memoryview((ctypes.c_char * nb.value).from_address(hp.value)).cast("B"))
+
+
+def _two_slot_blocks(ctx, writer, blocks, render, times):
+    """render(slot, a, b) for every block (a, b) of `blocks`, alternating between the device's two text slots: block
+    n is gzipped on the writer's pool while the device renders block n + 1 into the other slot"""
     queued = []                  # slots rendered, not yet handed to the pool
     gzipping = False             # some slot's pinned buffer is still read by pool threads
-    for blk, a in enumerate(range(0, len(rows), step)):
-        b, slot = min(len(rows), a + step), blk % 2
+    for blk, (a, b) in enumerate(blocks):
+        slot = blk % 2
         if gzipping and blk >= 2:
             writer.drain()       # the slot's host buffer is about to be overwritten
             gzipping = False
-        poff = np.zeros(b - a + 1, dtype=np.int64)
-        np.cumsum(plen[a:b], out=poff[1:])
-        blob = b"".join(pre_b[a:b])
-        nbytes = ctypes.c_int64(0)
-        t0 = timer()
-        check(ctx.lib.scape_hip_report_render(ctx.h, slot, b - a, ptr(rows[a:b], P_i64), ptr(is_int[a:b], P_i8),
-                                              ptr(poff, P_i64), blob, ctypes.byref(nbytes)), "report_render")
-        times["render"] += timer() - t0
+        render(slot, a, b)
         if queued:               # the previous block is complete behind this one's scan: compress it now
             _hand_over(ctx, queued.pop(0), writer, times)
             gzipping = True
@@ -231,84 +338,54 @@ def _render_batch(ctx, recs, K, row_tot, complete, n_cols, writer, times):
     writer.drain()
 
 
-def _hand_over(ctx, slot, writer, times):
-    hp, nb = ctypes.c_void_p(), ctypes.c_int64(0)
-    t0 = timer()
-    check(ctx.lib.scape_hip_report_fetch(ctx.h, slot, ctypes.byref(hp), ctypes.byref(nb)), "report_fetch")
-    times["render"] += timer() - t0
-    writer.submit(memoryview((ctypes.c_char * nb.value).from_address(hp.value)).cast("B"))
+def _render_batch(ctx, bat, n_cols, writer, times):
+    """every row of one counted batch: prefixes on the host, text on the device, in blocks of a fixed number of rows"""
+    _rowbase, rows, owner, label = _kept_rows(bat)
+    if not len(rows):
+        return
+    is_int = np.ascontiguousarray(bat.complete[owner])
+    pre_b = [_csv_field(s).encode() for s in _pa_infos(bat.recs, owner, label)]
+    plen = np.array([len(b) for b in pre_b], dtype=np.int64)
+    # rows per block from an upper bound of the row length (every field ',"<10 digits>.0"')
+    per_row = int(plen.max()) + 15 * n_cols + 2
+    step = max(1, min(1 << 20, MAX_BLOCK_BYTES // per_row))
+
+    def render(slot, a, b):
+        poff = np.zeros(b - a + 1, dtype=np.int64)
+        np.cumsum(plen[a:b], out=poff[1:])
+        blob = b"".join(pre_b[a:b])
+        nbytes = ctypes.c_int64(0)
+        t0 = timer()
+        check(ctx.lib.scape_hip_report_render(ctx.h, slot, b - a, ptr(rows[a:b], P_i64), ptr(is_int[a:b], P_i8),
+                                              ptr(poff, P_i64), blob, ctypes.byref(nbytes)), "report_render")
+        times["render"] += timer() - t0
+    _two_slot_blocks(ctx, writer, ((a, min(len(rows), a + step)) for a in range(0, len(rows), step)), render, times)
 
 
 def _ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, device=None, fmt="tsv"):
     """fmt "tsv": the reference's dense <res>.cnt.tsv.gz; "mtx": the directory <res>.cnt/ with matrix.mtx.gz,
     features.tsv.gz and barcodes.tsv.gz (_ex_pa_cnt_mtx)"""
-    import pandas as pd
     if fmt not in ("tsv", "mtx"):
         raise ValueError(f"unknown count matrix format {fmt!r} (tsv or mtx)")
-    res_pkl = os.path.join(output_dir, res_pkl_file)
-    if not (os.path.exists(output_dir)):
-        raise Exception("Given output_dir folder does not exists.")
-    if not (os.path.exists(res_pkl)):
-        raise Exception(f"Invalid file {res_pkl}. Given res_pkl_file is not in output_dir.")
-    outpath = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt.tsv.gz"))
-    cb_df = pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")
-    cb_lst = cb_df["CB"].tolist()
-    n_cols = len(cb_lst)
-    if n_cols == 0:
-        raise ValueError("barcode_index.csv lists no barcode")
-    idmap = _IdMap(cb_df.index.to_numpy(), np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
+    inp = _read_inputs(output_dir, res_pkl_file, with_cb=True)
+    n_cols = inp.n_cols
+    idmap = _IdMap(inp.col_ids, np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
     if fmt == "mtx":
-        return _ex_pa_cnt_mtx(output_dir, res_pkl_file, res_pkl, cb_lst, idmap, device)
+        return _ex_pa_cnt_mtx(output_dir, res_pkl_file, inp, idmap, device)
+    outpath = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt.tsv.gz"))
     hdr = io.StringIO()
-    csv.writer(hdr, delimiter=',', quoting=csv.QUOTE_ALL, lineterminator='\n').writerow(["pa_info"] + cb_lst)
-
-    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
-    start_t = timer()
-    tmp = _atomic_target(outpath)
-    ctx = None
-    try:
-        with open(tmp, "wb") as fh, ThreadPoolExecutor(_hostlib.host_threads()) as pool:
-            writer = _GzipWriter(fh, pool, times)
+    csv.writer(hdr, delimiter=',', quoting=csv.QUOTE_ALL, lineterminator='\n').writerow(["pa_info"] + inp.cb_lst)
+    with _Run(device, [outpath]) as run:
+        with open(run.parts[0], "wb") as fh, ThreadPoolExecutor(_hostlib.host_threads()) as pool:
+            writer = _GzipWriter(fh, pool, run.times)
             writer.submit(memoryview(hdr.getvalue().encode()))
             writer.drain()
-            ctx = _lib.default_context(device)
-            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 4 + len(p.label_arr) * 16 + 64,
-                                 _budget(ctx), times):
-                _count_and_render(ctx, recs, idmap, n_cols, writer, times)
-        os.replace(tmp, outpath)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        if ctx is not None:
-            ctx.lib.scape_hip_report_free(ctx.h)
-    end_t = timer()
-    LAST_TIMES.clear()
-    LAST_TIMES.update(times)
-    LAST_TIMES["total"] = end_t - start_t
+            ctx = run.device()
+            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
+                _render_batch(ctx, bat, n_cols, writer, run.times)
     print("Finish counting for each gene")
-    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
+    print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
     return outpath
-
-
-def _count(ctx, recs, idmap, n_cols, times):
-    """counts of one batch, kept on the device; K, the row totals and the pivot-complete flags on the host"""
-    t0 = timer()
-    off, K, lab, cb = _record_arrays(recs)
-    row_tot = np.zeros(int(K.sum()), dtype=np.int64)
-    complete = np.zeros(len(recs), dtype=np.int8)
-    bad = np.zeros(2, dtype=np.int64)
-    check(ctx.lib.scape_hip_report_counts(ctx.h, len(recs), ptr(off, P_i64), ptr(K, P_i32), ptr(lab, P_i64),
-                                          ptr(cb, P_i64), idmap.id_min, idmap.span, ptr(idmap.table, P_i32), n_cols,
-                                          ptr(row_tot, P_i64), ptr(complete, P_i8), ptr(bad, P_i64)), "report_counts")
-    times["h2d_counts"] += timer() - t0
-    if bad[0] >= 0 or bad[1] >= 0:
-        _raise_bad_read(bad, recs, off, cb, "barcode_index.csv")
-    return K, row_tot, complete
-
-
-def _count_and_render(ctx, recs, idmap, n_cols, writer, times):
-    K, row_tot, complete = _count(ctx, recs, idmap, n_cols, times)
-    _render_batch(ctx, recs, K, row_tot, complete, n_cols, writer, times)
 
 
 # ---------------------------------------------------------------- ex_pa_cnt_mat --format mtx
@@ -341,113 +418,81 @@ class _MtxSink:
         self.n_rows = self.nnz = 0
 
 
-def _ex_pa_cnt_mtx(output_dir, res_pkl_file, res_pkl, cb_lst, idmap, device):
+def _ex_pa_cnt_mtx(output_dir, res_pkl_file, inp, idmap, device):
     """the count matrix as a 10x-style directory <res>.cnt/: matrix.mtx.gz (the dense file's rows and columns, nonzero
     counts only, row-major), features.tsv.gz (per row: pa_info, pa_info, "Gene Expression"; Seurat's Read10X names rows
     from column 2, scanpy's read_10x_mtx from column 2 and keeps only "Gene Expression" rows) and barcodes.tsv.gz (the
     CB column).  The matrix header holds nnz, known only at the end: the body's gzip members go to an anonymous
     temporary file and are copied behind the header's member.  The three are renamed from .part once all are complete."""
-    n_cols = len(cb_lst)
-    bc_text = _tsv_lines([str(b) for b in cb_lst], lambda s: s + "\n", "barcode")
+    n_cols = inp.n_cols
+    bc_text = _tsv_lines([str(b) for b in inp.cb_lst], lambda s: s + "\n", "barcode")
     out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt"))
     if os.path.exists(out_dir) and not os.path.isdir(out_dir):
         raise FileExistsError(f"{out_dir} exists and is not a directory")
-
-    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
-    start_t = timer()
     made_dir = not os.path.isdir(out_dir)
-    os.makedirs(out_dir, exist_ok=True)
-    final = [os.path.join(out_dir, name) for name in MTX_FILES]
-    tmps = [_atomic_target(p) for p in final]
-    ctx, done = None, False
     try:
-        with tempfile.TemporaryFile(dir=out_dir) as body, open(tmps[1], "wb") as ffh, \
-                ThreadPoolExecutor(_hostlib.host_threads()) as pool:
-            with open(tmps[2], "wb") as bfh:
-                bw = _GzipWriter(bfh, pool, times)
-                bw.submit(memoryview(bc_text.encode()))
-                bw.drain()
-            sink = _MtxSink(_GzipWriter(body, pool, times), _GzipWriter(ffh, pool, times))
-            ctx = _lib.default_context(device)
-            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 4 + len(p.label_arr) * 16 + 64,
-                                 _budget(ctx), times):
-                K, row_tot, _complete = _count(ctx, recs, idmap, n_cols, times)
-                _render_mtx_batch(ctx, recs, K, row_tot, n_cols, sink, times)
-            t0 = timer()
-            with open(tmps[0], "wb") as mfh:
-                mfh.write(_gzip_part(f"{MTX_BANNER}{sink.n_rows} {n_cols} {sink.nnz}\n".encode()))
-                body.seek(0)
-                shutil.copyfileobj(body, mfh, 16 << 20)
-            times["finish"] += timer() - t0
-        for tmp, path in zip(tmps, final):
-            os.replace(tmp, path)
-        done = True
-    finally:
-        for tmp in tmps:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        if made_dir and not done:
+        with _Run(device, [os.path.join(out_dir, name) for name in MTX_FILES]) as run:
+            os.makedirs(out_dir, exist_ok=True)
+            with tempfile.TemporaryFile(dir=out_dir) as body, open(run.parts[1], "wb") as ffh, \
+                    ThreadPoolExecutor(_hostlib.host_threads()) as pool:
+                with open(run.parts[2], "wb") as bfh:
+                    bw = _GzipWriter(bfh, pool, run.times)
+                    bw.submit(memoryview(bc_text.encode()))
+                    bw.drain()
+                sink = _MtxSink(_GzipWriter(body, pool, run.times), _GzipWriter(ffh, pool, run.times))
+                ctx = run.device()
+                for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
+                    _render_mtx_batch(ctx, bat, n_cols, sink, run.times)
+                t0 = timer()
+                with open(run.parts[0], "wb") as mfh:
+                    mfh.write(_gzip_part(f"{MTX_BANNER}{sink.n_rows} {n_cols} {sink.nnz}\n".encode()))
+                    body.seek(0)
+                    shutil.copyfileobj(body, mfh, 16 << 20)
+                run.times["finish"] += timer() - t0
+    except BaseException:
+        if made_dir:             # nothing of this run stays behind
             try:
                 os.rmdir(out_dir)
             except OSError:
                 pass
-        if ctx is not None:
-            ctx.lib.scape_hip_report_free(ctx.h)
-    end_t = timer()
-    LAST_TIMES.clear()
-    LAST_TIMES.update(times)
-    LAST_TIMES["total"] = end_t - start_t
+        raise
     print("Finish counting for each gene")
-    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
+    print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
     return out_dir
 
 
-def _render_mtx_batch(ctx, recs, K, row_tot, n_cols, sink, times):
+def _render_mtx_batch(ctx, bat, n_cols, sink, times):
     """the rows of one counted batch, numbered on from sink.n_rows: features lines on the host, Matrix Market entries
-    on the device; block b is gzipped on the pool while the device renders block b + 1 (as in _render_batch)"""
-    rows, pa = [], []
-    base = 0
-    for r, para in enumerate(recs):
-        k = int(K[r])
-        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
-        if len(labs):
-            rows.append(base + labs)
-            pa.extend(_pa_info(para, labs))
-        base += k
-    if not rows:
+    on the device, in blocks cut by their text size"""
+    _rowbase, rows, owner, label = _kept_rows(bat)
+    if not len(rows):
         return
-    rows = np.concatenate(rows).astype(np.int64)
+    pa = _pa_infos(bat.recs, owner, label)
     sink.features.submit(memoryview(_tsv_lines(pa, lambda s: f"{s}\t{s}\tGene Expression\n", "pa_info").encode()))
     # blocks cut against an upper bound of each row's text: at most min(reads, barcodes) entries
     # "<row number> <column> <count>\n", the count at most the row's reads
     row_no0 = sink.n_rows + 1
-    tot = row_tot[rows]
+    tot = bat.row_tot[rows]
     width = len(str(row_no0 + len(rows) - 1)) + len(str(n_cols)) + 3 + _digits(tot)
     cum = np.zeros(len(rows) + 1, dtype=np.int64)
     np.cumsum(np.minimum(tot, n_cols) * width, out=cum[1:])
-    queued = []                  # slots rendered, not yet handed to the pool
-    gzipping = False             # some slot's pinned buffer is still read by pool threads
-    a = blk = 0
-    while a < len(rows):
-        b = int(np.searchsorted(cum, cum[a] + MAX_BLOCK_BYTES, side="right")) - 1
-        b, slot = min(len(rows), a + (1 << 20), max(a + 1, b)), blk % 2
-        if gzipping and blk >= 2:
-            sink.matrix.drain()  # the slot's host buffer is about to be overwritten
-            gzipping = False
+
+    def blocks():
+        a = 0
+        while a < len(rows):
+            b = int(np.searchsorted(cum, cum[a] + MAX_BLOCK_BYTES, side="right")) - 1
+            b = min(len(rows), a + (1 << 20), max(a + 1, b))
+            yield a, b
+            a = b
+
+    def render(slot, a, b):
         nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
         t0 = timer()
         check(ctx.lib.scape_hip_report_render_mtx(ctx.h, slot, b - a, ptr(rows[a:b], P_i64), row_no0 + a,
                                                   ctypes.byref(nbytes), ctypes.byref(nnz)), "report_render_mtx")
         times["render"] += timer() - t0
         sink.nnz += nnz.value
-        if queued:               # the previous block is complete behind this one's scan: compress it now
-            _hand_over(ctx, queued.pop(0), sink.matrix, times)
-            gzipping = True
-        queued.append(slot)
-        a, blk = b, blk + 1
-    for s in queued:
-        _hand_over(ctx, s, sink.matrix, times)
-    sink.matrix.drain()
+    _two_slot_blocks(ctx, sink.matrix, blocks(), render, times)
     sink.features.drain()
     sink.n_rows += len(rows)
 
@@ -520,20 +565,12 @@ def _samples(pops, num_splits, n_cols):
     return table, slot, np.array(seg_off, dtype=np.int32), np.array(seg_pop, dtype=np.int64)
 
 
-def _group_sums_batch(ctx, recs, K, row_tot, seg_off, seg_pop, n_cells, cnt_w, pct_w, times):
+def _group_sums_batch(ctx, bat, seg_off, seg_pop, n_cells, cnt_w, pct_w, times):
     """the table lines of one counted batch: segment sums on the device, pa_info and the pct division on the host"""
-    rows, pa = [], []
-    base = 0
-    for r, para in enumerate(recs):
-        k = int(K[r])
-        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
-        if len(labs):
-            rows.append(base + labs)
-            pa.extend(_pa_info(para, labs))
-        base += k
-    if not rows:
+    _rowbase, rows, owner, label = _kept_rows(bat)
+    if not len(rows):
         return 0
-    rows = np.concatenate(rows).astype(np.int64)
+    pa = _pa_infos(bat.recs, owner, label)
     n_seg = len(seg_off) - 1
     sums = np.zeros((len(rows), n_seg), dtype=np.int32)
     nz = np.zeros((len(rows), n_seg), dtype=np.int32)
@@ -559,73 +596,34 @@ def _ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str
                       idents_1=None, idents_2=None, device=None):
     """pA x pseudo-replicate counts and the per-population share of cells with a count above 0, as three csv files
     in output_dir (<prefix>.<kind>[.<A>_vs_<B>].pseudobulk.{cnt,pct,samples}.csv); returns their paths"""
-    import pandas as pd
     if num_splits < 1:
         raise ValueError(f"num_splits must be at least 1, not {num_splits}")
     if idents_2 is not None and idents_1 is None:
         raise ValueError("idents_2 needs idents_1")
     if idents_1 is not None and idents_1 == idents_2:
         raise ValueError(f"idents_1 and idents_2 are the same cluster {idents_1!r}")
-    res_pkl = os.path.join(output_dir, res_pkl_file)
-    if not (os.path.exists(output_dir)):
-        raise Exception("Given output_dir folder does not exists.")
-    if not (os.path.exists(res_pkl)):
-        raise Exception(f"Invalid file {res_pkl}. Given res_pkl_file is not in output_dir.")
-    if not (os.path.exists(cell_cluster_file)):
-        raise Exception("Given cell_cluster_file file does not exists")
-    cb_df = pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")
-    n_cols = len(cb_df)
-    if n_cols == 0:
-        raise ValueError("barcode_index.csv lists no barcode")
-    col_ids = cb_df.index.to_numpy()
-    if col_ids.dtype.kind not in "iu":
-        raise ValueError("barcode_index.csv: the index column must hold integer ids")
-    col_clu, order = _column_clusters(col_ids.astype(np.int64), *_read_clusters(cell_cluster_file))
-    pops = _populations(col_clu, order, idents_1, idents_2)
+    inp = _read_inputs(output_dir, res_pkl_file, cell_cluster_file, (idents_1, idents_2))
+    n_cols, pops = inp.n_cols, inp.pops
     table, slot, seg_off, seg_pop = _samples(pops, num_splits, n_cols)
     n_cells = np.array([len(cols) for _name, cols in pops], dtype=np.int64)
-    idmap = _IdMap(col_ids, slot, "barcode_index.csv")
-
-    tag = "" if idents_1 is None else f".{idents_1}_vs_{idents_2 if idents_2 is not None else 'rest'}"
-    if os.sep in tag:
-        raise ValueError(f"an ident with {os.sep!r} cannot be part of a file name")
-    stem = os.path.splitext(os.path.basename(cell_cluster_file))[0] + "." + \
-        res_pkl_file.replace(".pkl", "").replace("res.", "") + tag + ".pseudobulk."
-    final = [os.path.join(output_dir, stem + what + ".csv") for what in ("cnt", "pct", "samples")]
-    tmps = [_atomic_target(p) for p in final]
-
-    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
-    start_t = timer()
-    ctx = None
+    idmap = _IdMap(inp.col_ids, slot, "barcode_index.csv")
+    stem = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + ".pseudobulk."
+    final = [stem + what + ".csv" for what in ("cnt", "pct", "samples")]
     n_rows = 0
-    try:
-        with open(tmps[0], "w", newline="") as cfh, open(tmps[1], "w", newline="") as pfh, \
-                open(tmps[2], "w", newline="") as sfh:
+    with _Run(device, final) as run:
+        with open(run.parts[0], "w", newline="") as cfh, open(run.parts[1], "w", newline="") as pfh, \
+                open(run.parts[2], "w", newline="") as sfh:
             cnt_w, pct_w, smp_w = (csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n')
                                    for fh in (cfh, pfh, sfh))
             cnt_w.writerow(["pa_info"] + [row[0] for row in table])
             pct_w.writerow(["pa_info"] + [name for name, _cols in pops])
             smp_w.writerow(["sample", "population", "split", "n_cells"])
             smp_w.writerows(table)
-            ctx = _lib.default_context(device)
-            for recs in _batches(res_pkl, lambda p: int(p.K) * n_cols * 4 + len(p.label_arr) * 16 + 64,
-                                 _budget(ctx), times):
-                K, row_tot, _complete = _count(ctx, recs, idmap, n_cols, times)
-                n_rows += _group_sums_batch(ctx, recs, K, row_tot, seg_off, seg_pop, n_cells, cnt_w, pct_w, times)
-        for tmp, path in zip(tmps, final):
-            os.replace(tmp, path)
-    finally:
-        for tmp in tmps:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        if ctx is not None:
-            ctx.lib.scape_hip_report_free(ctx.h)
-    end_t = timer()
-    LAST_TIMES.clear()
-    LAST_TIMES.update(times)
-    LAST_TIMES["total"] = end_t - start_t
+            ctx = run.device()
+            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
+                n_rows += _group_sums_batch(ctx, bat, seg_off, seg_pop, n_cells, cnt_w, pct_w, run.times)
     print(f"Finish pseudo-bulk counts of {n_rows} pA sites in {len(table)} samples of {len(pops)} populations")
-    print(f"Finish {res_pkl} in {(end_t - start_t) / 60} min.")
+    print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
     return final
 
 
@@ -661,20 +659,14 @@ def _perm_masks(ctx, n1, n2, p_first, p_count, seed, times):
     times["render"] += timer() - t0
 
 
-def _perm_rows(ctx, recs, K, row_tot, seg_off, times, each_kept=None):
+def _perm_rows(ctx, bat, seg_off, times, each_kept=None):
     """the tested records of one counted batch and their kept rows: (batch indices of the tested records, row offsets
-    per tested record, count rows, cells with a count above 0 per row and population, sums per row and population),
-    or None when no record of the batch is tested.  each_kept(r, labels), when given, is called for every record of
-    K >= 2 that has a kept row, tested or not, with the labels of its kept rows"""
-    cand, owner = [], []
-    base = 0
-    for r in range(len(recs)):
-        k = int(K[r])
-        labs = np.nonzero(row_tot[base:base + k] > 0)[0]
-        cand.append(base + labs)
-        owner.append(np.full(len(labs), r, dtype=np.int64))
-        base += k
-    cand, owner = np.concatenate(cand).astype(np.int64), np.concatenate(owner)
+    per tested record, count rows, cells with a count above 0 per row and population, sums per row and population,
+    first count row of every record of the batch), or None when no record of the batch is tested.  each_kept(r,
+    labels), when given, is called for every record of K >= 2 that has a kept row, tested or not, with the labels of
+    its kept rows"""
+    recs, K = bat.recs, bat.K
+    rowbase, cand, owner, label = _kept_rows(bat)
     if not len(cand):
         return None
     sums = np.zeros((len(cand), 2), dtype=np.int32)
@@ -688,9 +680,8 @@ def _perm_rows(ctx, recs, K, row_tot, seg_off, times, each_kept=None):
     keep = sums.sum(axis=1) > 0
     n_kept = np.bincount(owner[keep], minlength=len(recs))
     if each_kept is not None:
-        rowbase = np.cumsum(K, dtype=np.int64) - K
         cut = np.cumsum(n_kept)
-        labs = cand[keep] - rowbase[owner[keep]]
+        labs = label[keep]
         for r in np.nonzero((n_kept > 0) & (K >= 2))[0].tolist():
             each_kept(r, labs[cut[r] - n_kept[r]:cut[r]])
     A = np.bincount(owner, weights=sums[:, 0], minlength=len(recs))
@@ -703,7 +694,7 @@ def _perm_rows(ctx, recs, K, row_tot, seg_off, times, each_kept=None):
         return None
     off = np.zeros(len(which) + 1, dtype=np.int64)
     np.cumsum(n_kept[which], out=off[1:])
-    return which, off, cand[keep], nz[keep], sums[keep]
+    return which, off, cand[keep], nz[keep], sums[keep], rowbase
 
 
 def _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, test):
@@ -717,13 +708,14 @@ def _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, test):
         times["render"] += timer() - t0
 
 
-def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, genes, times):
+def _diff_pa_batch(ctx, bat, seg_off, n_perm, chunk, seed, lines, genes, times):
     """one counted batch: the kept rows of its tested records go through the permutation test; appends the per-line
     integers to `lines` and the per-record ones to `genes`"""
-    sel = _perm_rows(ctx, recs, K, row_tot, seg_off, times)
+    sel = _perm_rows(ctx, bat, seg_off, times)
     if sel is None:
         return
-    which, off, rows, nz, sums = sel
+    recs = bat.recs
+    which, off, rows, nz, sums, rowbase = sel
     t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
     site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
     stat0 = np.zeros(len(which), np.float64)
@@ -734,7 +726,6 @@ def _diff_pa_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, lines, g
     t0 = timer()
     if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums[:, 0])):
         raise _lib.ScapeHipError("report_perm_test: row sums differ from report_group_sums")
-    rowbase = np.cumsum(K, dtype=np.int64) - K
     for g, r in enumerate(which.tolist()):
         a, b = int(off[g]), int(off[g + 1])
         T = int(t[a:b].sum())
@@ -752,7 +743,6 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
     """what diff_pa and diff_pa_len do before the device is opened: the argument and prerequisite checks, the two
     populations, the id -> column table that puts population 1's columns first and population 2's behind them, and the
     output path <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.<command>.csv"""
-    import pandas as pd
     if idents_1 is None:
         raise ValueError("idents_1 is required")
     if idents_1 == idents_2:
@@ -763,22 +753,8 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
         raise ValueError(f"n_perm must be below 2^31, not {n_perm}")
     if not 0 <= seed < 1 << 64:
         raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
-    res_pkl = os.path.join(output_dir, res_pkl_file)
-    if not (os.path.exists(output_dir)):
-        raise Exception("Given output_dir folder does not exists.")
-    if not (os.path.exists(res_pkl)):
-        raise Exception(f"Invalid file {res_pkl}. Given res_pkl_file is not in output_dir.")
-    if not (os.path.exists(cell_cluster_file)):
-        raise Exception("Given cell_cluster_file file does not exists")
-    cb_df = pd.read_csv(os.path.join(output_dir, "barcode_index.csv"), index_col="index")
-    n_cols = len(cb_df)
-    if n_cols == 0:
-        raise ValueError("barcode_index.csv lists no barcode")
-    col_ids = cb_df.index.to_numpy()
-    if col_ids.dtype.kind not in "iu":
-        raise ValueError("barcode_index.csv: the index column must hold integer ids")
-    col_clu, order = _column_clusters(col_ids.astype(np.int64), *_read_clusters(cell_cluster_file))
-    pops = _populations(col_clu, order, idents_1, idents_2)
+    inp = _read_inputs(output_dir, res_pkl_file, cell_cluster_file, (idents_1, idents_2))
+    n_cols, pops = inp.n_cols, inp.pops
     if len(pops) < 2:
         empty = "Population2" if pops and pops[0][0] == "Population1" else "Population1"
         raise ValueError(f"{empty} ({idents_1 if empty == 'Population1' else idents_2 or 'the rest'}) has no cell in "
@@ -787,27 +763,20 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
     n1, n2 = len(pops[0][1]), len(pops[1][1])
     if n1 + n2 >= MAX_PERM_CELLS:
         raise ValueError(f"{n1 + n2} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
-    tag = f".{idents_1}_vs_{idents_2 if idents_2 is not None else 'rest'}"
-    if os.sep in tag:
-        raise ValueError(f"an ident with {os.sep!r} cannot be part of a file name")
-    outpath = os.path.join(output_dir, os.path.splitext(os.path.basename(cell_cluster_file))[0] + "." +
-                           res_pkl_file.replace(".pkl", "").replace("res.", "") + tag + f".{command}.csv")
-    return SimpleNamespace(res_pkl=res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
-                           idmap=_IdMap(col_ids, slot, "barcode_index.csv"),
+    outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + f".{command}.csv"
+    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
+                           idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"),
                            versus=f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1))
 
 
 def _perm_run(su, n_perm, seed, device, batch, write):
     """the run both commands share: the masks (once, when all permutations fit MAX_PERM_BYTES; otherwise per chunk inside
-    every batch), batch(ctx, recs, K, row_tot, chunk, times) per counted batch, then write(csv writer) into the .part
-    file that is renamed when complete.  Returns the wall seconds; LAST_TIMES holds the stages"""
-    tmp = _atomic_target(su.outpath)
-    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
-    start_t = timer()
-    ctx = None
-    try:
-        with open(tmp, "w", newline="") as fh:
-            ctx = _lib.default_context(device)
+    every batch), batch(ctx, counted batch, chunk, times) per counted batch, then write(csv writer) into the .part file
+    that is renamed when complete.  Returns the wall seconds; LAST_TIMES holds the stages"""
+    with _Run(device, [su.outpath]) as run:
+        times = run.times
+        with open(run.parts[0], "w", newline="") as fh:
+            ctx = run.device()
             budget = _budget(ctx)
             word_bytes = (su.n1 + su.n2 + 63) // 64 * 8
             perm_bytes = int(MAX_PERM_BYTES) if MAX_PERM_BYTES is not None else budget // 2
@@ -817,24 +786,12 @@ def _perm_run(su, n_perm, seed, device, batch, write):
             if MAX_BATCH_BYTES is None:
                 budget //= 2
             # the counts of a record and, at worst, as many 8-byte nonzeros as it has tested counts
-            for recs in _batches(su.res_pkl, lambda p: int(p.K) * su.n_cols * 12 + len(p.label_arr) * 16 + 64, budget,
-                                 times):
-                K, row_tot, _complete = _count(ctx, recs, su.idmap, su.n_cols, times)
-                batch(ctx, recs, K, row_tot, chunk, times)
+            for bat in _counted(ctx, su.res_pkl, su.idmap, su.n_cols, _batch_cost(su.n_cols, 12), budget, times):
+                batch(ctx, bat, chunk, times)
             t0 = timer()
             write(csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n'))
             times["finish"] += timer() - t0
-        os.replace(tmp, su.outpath)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        if ctx is not None:
-            ctx.lib.scape_hip_report_free(ctx.h)
-    end_t = timer()
-    LAST_TIMES.clear()
-    LAST_TIMES.update(times)
-    LAST_TIMES["total"] = end_t - start_t
-    return end_t - start_t
+    return run.total
 
 
 def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
@@ -846,8 +803,8 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
     lines = {k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}
     genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
 
-    def batch(ctx, recs, K, row_tot, chunk, times):
-        _diff_pa_batch(ctx, recs, K, row_tot, su.seg_off, n_perm, chunk, seed, lines, genes, times)
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_batch(ctx, bat, su.seg_off, n_perm, chunk, seed, lines, genes, times)
 
     def write(w):
         w.writerow(DIFF_PA_HEADER)
@@ -917,9 +874,10 @@ def _mean_positions(x, a, b):
     return float(m1), float(m2), float(m1 - m2)
 
 
-def _diff_pa_len_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, out, times):
+def _diff_pa_len_batch(ctx, bat, seg_off, n_perm, chunk, seed, out, times):
     """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
     n_ge) per tested record to `out`"""
+    recs, K = bat.recs, bat.K
     pos = {}                     # record -> positions of its kept rows (f64, finite)
 
     def positions(r, labs):
@@ -927,12 +885,11 @@ def _diff_pa_len_batch(ctx, recs, K, row_tot, seg_off, n_perm, chunk, seed, out,
         if not (np.all(np.isfinite(x)) and np.isfinite(x.max() - x.min())):
             raise ValueError(f"{recs[r].gene_info_str}: alpha_arr holds a non-finite position of a pA site with reads")
         pos[r] = x
-    sel = _perm_rows(ctx, recs, K, row_tot, seg_off, times, positions)
+    sel = _perm_rows(ctx, bat, seg_off, times, positions)
     if sel is None:
         return
-    which, off, rows, _nz, sums = sel
+    which, off, rows, _nz, sums, rowbase = sel
     t0 = timer()
-    rowbase = np.cumsum(K, dtype=np.int64) - K
     tested, xs, w, tol = [], [], [], []
     for g, r in enumerate(which.tolist()):
         x = pos[r]
@@ -994,8 +951,8 @@ def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, ide
     su = _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, "diff_pa_len")
     out = []
 
-    def batch(ctx, recs, K, row_tot, chunk, times):
-        _diff_pa_len_batch(ctx, recs, K, row_tot, su.seg_off, n_perm, chunk, seed, out, times)
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_len_batch(ctx, bat, su.seg_off, n_perm, chunk, seed, out, times)
 
     def write(w):
         w.writerow(DIFF_PA_LEN_HEADER)
@@ -1067,11 +1024,8 @@ def _cal_exp_pa_len(output_dir: str, cell_cluster_file: str, res_pkl_file: str, 
         values = [vals[i] for i in first]               # one representative object per code
         idmap = _IdMap(col.index.to_numpy(), codes, cell_cluster_file)
 
-    times = ReportTimes({k: 0.0 for k in _TIMES_KEYS})
-    start_t = timer()
     exp_len_lst = []
-    ctx = None
-    try:
+    with _Run(device, [output_path]) as run:
         n_codes = len(values) if values is not None else 1
         n_words = (max(n_codes, 1) + 31) // 32
 
@@ -1079,32 +1033,19 @@ def _cal_exp_pa_len(output_dir: str, cell_cluster_file: str, res_pkl_file: str, 
             n = len(p.label_arr)
             return n * 16 + n_words * 8 + min(n, n_codes) * (int(p.K) + 1) * 4 + 64
 
-        ctx = _lib.default_context(device)
-        for recs in _batches(final_res, cost, _budget(ctx), times):
-            _hist_batch(ctx, recs, idmap, values, n_codes, exp_len_lst, times, cell_cluster_file)
-    finally:
-        if ctx is not None:
-            ctx.lib.scape_hip_report_free(ctx.h)
-    end_t = timer()
-    print(f"Done calculating expected pa length each gene in {(end_t - start_t) / 60} min.")
-    t0 = timer()
-    if cell_cluster_file == "None":
-        final_df = pd.DataFrame(exp_len_lst, columns=["gene_id", "exp_length", "num_pa"])
-    else:
-        final_df = pd.DataFrame(exp_len_lst, columns=["gene_id", "cell_cluster", "exp_length", "num_pa"])
-    tmp = _atomic_target(output_path)
-    try:
-        final_df.to_csv(tmp, header=True, index=False)
-        os.replace(tmp, output_path)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    times["finish"] += timer() - t0
-    end_t = timer()
-    LAST_TIMES.clear()
-    LAST_TIMES.update(times)
-    LAST_TIMES["total"] = end_t - start_t
-    print(f"Done in {(end_t - start_t) / 60} min. ")
+        ctx = run.device()
+        for recs in _batches(final_res, cost, _budget(ctx), run.times):
+            _hist_batch(ctx, recs, idmap, values, n_codes, exp_len_lst, run.times, cell_cluster_file)
+        run.release()
+        print(f"Done calculating expected pa length each gene in {(timer() - run.start) / 60} min.")
+        t0 = timer()
+        if cell_cluster_file == "None":
+            final_df = pd.DataFrame(exp_len_lst, columns=["gene_id", "exp_length", "num_pa"])
+        else:
+            final_df = pd.DataFrame(exp_len_lst, columns=["gene_id", "cell_cluster", "exp_length", "num_pa"])
+        final_df.to_csv(run.parts[0], header=True, index=False)
+        run.times["finish"] += timer() - t0
+    print(f"Done in {run.total / 60} min. ")
     return output_path
 
 
@@ -1209,21 +1150,30 @@ def ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str,
     _ex_pa_pseudobulk(output_dir, res_pkl_file, cell_cluster_file, num_splits, idents_1, idents_2)
 
 
+def _perm_options(f):
+    """the options diff_pa and diff_pa_len share (--seed's help differs)"""
+    for option in reversed((
+            click.option('--output_dir', type=str, required=True,
+                         help='Directory which was used in previous steps to save output by prepare_input and '
+                              'infer_pa.'),
+            click.option('--res_pkl_file', type=str, default="None",
+                         help='Name of res pickle file that contains PASs. Its name will be included in the file name '
+                              'of the final result.'),
+            click.option('--cell_cluster_file', type=str, required=True,
+                         help='An csv file containing two columns in order: cell barcode index (index) and respective '
+                              'group. Cells with an empty group, or not listed, are left out. Its name will be '
+                              'included in the file name of the final result.'),
+            click.option('--idents_1', type=str, required=True, help='The cluster of population 1.'),
+            click.option('--idents_2', type=str, default=None,
+                         help='The cluster of population 2. Default: every other cell that has a cluster.'),
+            click.option('--n_perm', type=int, default=9999, show_default=True,
+                         help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).'))):
+        f = option(f)
+    return f
+
+
 @click.command(name="diff_pa")
-@click.option('--output_dir', type=str, required=True,
-              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
-@click.option('--res_pkl_file', type=str, default="None",
-              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the '
-                   'final result.')
-@click.option('--cell_cluster_file', type=str, required=True,
-              help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
-                   'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
-                   'name of the final result.')
-@click.option('--idents_1', type=str, required=True, help='The cluster of population 1.')
-@click.option('--idents_2', type=str, default=None,
-              help='The cluster of population 2. Default: every other cell that has a cluster.')
-@click.option('--n_perm', type=int, default=9999, show_default=True,
-              help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
+@_perm_options
 @click.option('--seed', type=int, default=1, show_default=True, help='Seed of the permutations, 0 .. 2^64 - 1.')
 def diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_perm: int, seed: int):
     """pA sites used differently by two cell populations: a permutation test of the cell labels on the pA x cell counts
@@ -1232,20 +1182,7 @@ def diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1
 
 
 @click.command(name="diff_pa_len")
-@click.option('--output_dir', type=str, required=True,
-              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
-@click.option('--res_pkl_file', type=str, default="None",
-              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the '
-                   'final result.')
-@click.option('--cell_cluster_file', type=str, required=True,
-              help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
-                   'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
-                   'name of the final result.')
-@click.option('--idents_1', type=str, required=True, help='The cluster of population 1.')
-@click.option('--idents_2', type=str, default=None,
-              help='The cluster of population 2. Default: every other cell that has a cluster.')
-@click.option('--n_perm', type=int, default=9999, show_default=True,
-              help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
+@_perm_options
 @click.option('--seed', type=int, default=1, show_default=True,
               help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives the same relabellings of the cells '
                    'as in diff_pa.')

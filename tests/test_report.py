@@ -7,20 +7,14 @@ import os
 
 import numpy as np
 import pytest
-from click.testing import CliRunner
 
-from conftest import load_npz
 import report_cases as rc
-
-
-def _cli():
-    from scape.cli import cli
-    return cli
+from report_cases import no_gpu, run as _run  # noqa: F401  (no_gpu is a fixture)
 
 
 # ---------------------------------------------------------------- CPU
 def test_help_lists_both_commands():
-    r = CliRunner().invoke(_cli(), ["--help"])
+    r = _run(["--help"])
     assert r.exit_code == 0, r.output
     assert "cal_exp_pa_len" in r.output and "ex_pa_cnt_mat" in r.output
 
@@ -28,7 +22,7 @@ def test_help_lists_both_commands():
 @pytest.mark.parametrize("cmd,opts", [("cal_exp_pa_len", ["--output_dir", "--cell_cluster_file", "--res_pkl_file"]),
                                       ("ex_pa_cnt_mat", ["--output_dir", "--res_pkl_file"])])
 def test_command_help(cmd, opts):
-    r = CliRunner().invoke(_cli(), [cmd, "--help"])
+    r = _run([cmd, "--help"])
     assert r.exit_code == 0, r.output
     for o in opts:
         assert o in r.output
@@ -38,20 +32,6 @@ def test_utils_import_path():
     import scape.utils as su
     from scape_amd import report
     assert su.cal_exp_pa_len is report.cal_exp_pa_len and su.ex_pa_cnt_mat is report.ex_pa_cnt_mat
-
-
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from scape_amd import _lib
-
-    def refuse(*a, **k):
-        raise AssertionError("the GPU was touched before the prerequisite checks")
-    monkeypatch.setattr(_lib, "default_context", refuse)
-    monkeypatch.setattr(_lib, "Context", refuse)
-
-
-def _run(args):
-    return CliRunner().invoke(_cli(), args)
 
 
 def test_ex_pa_cnt_mat_prerequisites(tmp_path, no_gpu):
@@ -83,7 +63,7 @@ def test_cal_exp_pa_len_prerequisites(tmp_path, no_gpu):
 
 
 def test_fixture_decodes():
-    f = load_npz("fixture_report.npz")
+    f = rc.fixture()
     ids = rc.case_ids(f)
     assert len(ids) >= 46
     names = [rc.case(f, c)["name"] for c in ids]
@@ -103,14 +83,6 @@ def test_fixture_decodes():
 
 
 # ---------------------------------------------------------------- GPU
-def _write_case(f, cs, root):
-    from scape.apa_core import Parameters
-    bc = rc.text(f, cs["barcode"])
-    paths = rc.write_dir(str(root), cs["res"], cs["records"], bc,
-                         {fn: rc.text(f, k) for fn, k in zip(cs["clu_files"], cs["clusters"])}, Parameters)
-    return bc, paths
-
-
 def _check_outputs(cs, bc, paths, root, read_with_pandas=False):
     r = _run(["ex_pa_cnt_mat", "--output_dir", str(root), "--res_pkl_file", cs["res"]])
     assert r.exit_code == 0, (cs["name"], r.output, repr(r.exception))
@@ -133,35 +105,19 @@ def _check_outputs(cs, bc, paths, root, read_with_pandas=False):
             assert fh.read() == cs["len_texts"][j], (cs["name"], cf)
 
 
-_F = None
-
-
-def _fixture():
-    global _F
-    if _F is None:
-        _F = load_npz("fixture_report.npz")
-    return _F
-
-
-def _case_params():
-    f = _fixture()
-    return [pytest.param(c, id=rc.case(f, c)["name"].replace("/", "-")) for c in rc.case_ids(f)]
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("c", _case_params())
+@pytest.mark.parametrize("c", rc.case_params())
 def test_report_case_vs_reference(c, tmp_path, monkeypatch):
     """Every golden case.  The fuzzed ones run with a batch budget and a render block so small that records go to
     the device in several batches and rows are rendered a few at a time; the example directories run with the batch
     sized from free device memory."""
     from scape_amd import report
-    f = _fixture()
-    cs = rc.case(f, c)
+    cs = rc.fixture_case(c)
     if cs["name"].startswith("fuzz"):
         monkeypatch.setattr(report, "MAX_BATCH_BYTES", 1 << 14)
         monkeypatch.setattr(report, "MAX_BLOCK_BYTES", 1 << 12)
         monkeypatch.setattr(report, "GZIP_PART", 1 << 11)
-    bc, paths = _write_case(f, cs, tmp_path)
+    bc, paths = rc.write_case(cs, tmp_path)
     _check_outputs(cs, bc, paths, tmp_path, read_with_pandas=not cs["name"].startswith("fuzz"))
 
 
@@ -194,7 +150,6 @@ def test_chain_infer_merge_then_report_vs_reference(tmp_path):
     import merge_chain_dir as mc
     from scape_amd.apa_core import infer_all
     from scape_amd.junction_handler import _merge_pa
-    f = _fixture()
     mc.write_inputs(str(tmp_path))
     infer_all(str(tmp_path), gpus=1, rng_mode="per_utr", seed=mc.SEED, re_run_mode=True, **mc.KW)
     _merge_pa(str(tmp_path), True)
@@ -203,7 +158,7 @@ def test_chain_infer_merge_then_report_vs_reference(tmp_path):
     (tmp_path / "barcode_index.csv").write_text(bc)
     clu = tmp_path / "chain_groups.csv"
     clu.write_text(rc.chain_cluster_csv())
-    byname = {rc.case(f, c)["name"]: rc.case(f, c) for c in rc.case_ids(f)}
+    byname = {cs["name"]: cs for cs in rc.fixture_cases()}
     for tag in ("gene", "utr"):
         cs = byname[f"chain/{tag}"]
         _check_outputs(cs, bc, [str(clu)], tmp_path, read_with_pandas=True)

@@ -4,8 +4,8 @@ scape_amd/csrc/report.inc).
 
 The contract.  Populations, tested columns (population 1's, then population 2's), kept rows (labels < K with a read in a
 tested column, in label order) and permutations (permutation p >= 1 gives population 1 the n1 positions with the smallest
-key(p, j)) are `diff_pa`'s: tests/test_report_diffpa.py states them, and its mix / key / members / bh / populations are
-used here.  Kept row i has the position x_i = alpha_arr[label_i] (f64; nucleotides from the UTR's 5' end along the
+key(p, j)) are `diff_pa`'s: tests/test_report_diffpa.py states them, and the mix / key / members / bh / populations of
+tests/report_cases.py are used here.  Kept row i has the position x_i = alpha_arr[label_i] (f64; nucleotides from the UTR's 5' end along the
 transcript, so larger = more distal = longer 3'UTR).  With a_i the row's sum over population 1 under a labelling,
 b_i = t_i - a_i, A = sum a_i, B = sum b_i:
 
@@ -26,7 +26,7 @@ alone, then that the file's n_ge EQUALS lo.  No record is excused.  The device's
 up to 1,024 rows per record (include/scape_hip.h), so a labelling that reaches the observed |delta| exactly is always
 counted and one more than 2 tol below it never."""
 import csv
-import glob
+import functools
 import io
 import math
 import os
@@ -35,10 +35,9 @@ from fractions import Fraction
 
 import numpy as np
 import pytest
-from click.testing import CliRunner
 
 import report_cases as rc
-import test_report_diffpa as dp          # helpers by name through the alias; none of its tests is bound here
+from report_cases import no_gpu, parts_left as _parts_left, run as _run  # noqa: F401  (no_gpu is a fixture)
 
 HEADER = ("gene,versus,num_pa,reads.1,reads.2,mean_pos.1,mean_pos.2,delta_pos,exp_length.1,exp_length.2,"
           "delta_exp_length,n_ge,p_val,p_val_adj,n_perm")
@@ -135,7 +134,7 @@ def oracle(recs, cols1, cols2, n_perm, seed):
             live.append(r)
     for p in range(1, n_perm + 1):
         member = bytearray(n)
-        pop1 = dp.members(seed, p, n1, n)
+        pop1 = rc.members(seed, p, n1, n)
         assert len(set(pop1)) == n1
         for j in pop1:
             member[j] = 1
@@ -149,7 +148,7 @@ def oracle(recs, cols1, cols2, n_perm, seed):
             de = float(np.float64(r.e1) - np.float64(r.e2))
         lines.append(dict(gene=r.gene, num_pa=len(r.nzs), A=sum(r.a0), B=r.T - sum(r.a0), m1=m1, m2=m2, delta=m1 - m2,
                           e1=repr(r.e1), e2=repr(r.e2), de=repr(de), lo=r.lo, hi=r.hi))
-    for ln, adj in zip(lines, dp.bh([Fraction(1 + ln["lo"], 1 + n_perm) for ln in lines])):
+    for ln, adj in zip(lines, rc.bh([Fraction(1 + ln["lo"], 1 + n_perm) for ln in lines])):
         ln["p_adj"] = adj
     return lines
 
@@ -175,7 +174,7 @@ def compare(text, lines, versus, n_perm, what):
         assert got[12] == repr((1 + ln["lo"]) / (1 + n_perm)), ctx
         assert got[8:11] == [ln["e1"], ln["e2"], ln["de"]], (ctx, ln["e1"], ln["e2"], ln["de"])
         for col, want in ((5, ln["m1"]), (6, ln["m2"]), (7, ln["delta"]), (13, ln["p_adj"])):
-            assert dp._close(got[col], want), (ctx, col, float(want))
+            assert rc.close(got[col], want), (ctx, col, float(want))
 
 
 # ---------------------------------------------------------------- inputs
@@ -194,52 +193,25 @@ def read_records(path):
 
 def dense_of(records, col_ids):
     """[dict(gene, K, alpha, dense)]: per record the (label < K, matrix column) read counts"""
-    col_of = {i: j for j, i in enumerate(col_ids)}
-    out = []
-    for rec in records:
-        K = int(rec["K"])
-        m = np.zeros((K, len(col_ids)), dtype=np.int64)
-        lab, cb = np.asarray(rec["label_arr"]), np.asarray(rec["cb_id_arr"])
-        ok = lab < K
-        np.add.at(m, (lab[ok], [col_of[int(i)] for i in cb[ok]]), 1)
-        out.append(dict(gene=rec["gene_info_str"], K=K, alpha=np.asarray(rec["alpha_arr"]), dense=m))
-    return out
-
-
-def _run(args):
-    from scape.cli import cli
-    return CliRunner().invoke(cli, args)
+    return [dict(gene=rec["gene_info_str"], K=int(rec["K"]), alpha=np.asarray(rec["alpha_arr"]), dense=m)
+            for rec, m in zip(records, rc.dense_counts(records, col_ids))]
 
 
 def _args(root, clu, res="res.gene.pkl", id1=None, id2=None, n_perm=None, seed=None, cmd="diff_pa_len"):
-    a = [cmd, "--output_dir", str(root), "--res_pkl_file", res, "--cell_cluster_file", str(clu)]
-    for opt, v in (("--idents_1", id1), ("--idents_2", id2), ("--n_perm", n_perm), ("--seed", seed)):
-        if v is not None:
-            a += [opt, str(v)]
-    return a
+    return rc.perm_args(cmd, root, clu, res, id1, id2, n_perm, seed)
 
 
 def _path(root, clu, res, id1, id2):
-    kind = res[len("res."):-len(".pkl")]
-    stem = os.path.splitext(os.path.basename(str(clu)))[0]
-    return os.path.join(str(root), f"{stem}.{kind}.{id1}_vs_{id2 if id2 is not None else 'rest'}.diff_pa_len.csv")
-
-
-def _parts_left(root):
-    return glob.glob(os.path.join(str(root), "**", "*.part"), recursive=True)
+    return rc.perm_path("diff_pa_len", root, clu, res, id1, id2)
 
 
 def _command(root, clu, res, id1, id2, n_perm, seed, what=""):
-    r = _run(_args(root, clu, res, id1, id2, n_perm, seed))
-    assert r.exit_code == 0, (what, r.output, repr(r.exception))
-    assert not _parts_left(root)
-    with open(_path(root, clu, res, id1, id2), newline="") as fh:
-        return fh.read()
+    return rc.perm_command("diff_pa_len", root, clu, res, id1, id2, n_perm, seed, what)
 
 
 def check(root, clu_path, clu_text, res, recs, bc, id1, id2, n_perm, seed, what):
     """oracle first (and lo == hi on it), then the command; returns (file text, expected lines)"""
-    c1, c2 = dp.populations(bc, clu_text, id1, id2)
+    c1, c2 = rc.populations(bc, clu_text, id1, id2)
     lines = oracle(recs, c1, c2, n_perm, seed)
     assert_no_near_tie(lines, what)
     text = _command(root, clu_path, res, id1, id2, n_perm, seed, what)
@@ -300,7 +272,7 @@ def test_affine_maps_complement_and_integer_form():
     nzs = [[(j, v) for j, v in enumerate(row) if v] for row in rows]
     labellings = []
     for p in range(1, n_perm + 1):
-        pop1 = set(dp.members(seed, p, n1, n))
+        pop1 = set(rc.members(seed, p, n1, n))
         labellings.append([j in pop1 for j in range(n)])
 
     def run(xs):
@@ -353,16 +325,6 @@ def test_utils_import_path():
     assert su.diff_pa_len is _host().diff_pa_len
 
 
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from scape_amd import _lib
-
-    def refuse(*a, **k):
-        raise AssertionError("the GPU was touched before the prerequisite checks")
-    monkeypatch.setattr(_lib, "default_context", refuse)
-    monkeypatch.setattr(_lib, "Context", refuse)
-
-
 def test_prerequisites_and_argument_errors(tmp_path, no_gpu):
     """diff_pa's list of errors, each raised by both commands with the same exception before the device is opened"""
     clu = tmp_path / "groups.csv"
@@ -402,8 +364,7 @@ def test_prerequisites_and_argument_errors(tmp_path, no_gpu):
 def _golden_dense(cs, n_cols):
     """the reference's own matrix rows (tests/golden/fixture_report.npz) as per-record [K, column] counts: a record's
     rows are its labels < K that have a read, in label order; the other labels have none"""
-    rows = list(csv.reader(io.StringIO(cs["mat_body"])))
-    vals = np.array([[int(float(v)) for v in r[1:]] for r in rows], dtype=np.int64).reshape(len(rows), n_cols)
+    _pas, vals = rc.dense_of_body(cs["mat_body"], n_cols)
     out, k = [], 0
     for rec in cs["records"]:
         K = int(rec["K"])
@@ -413,43 +374,29 @@ def _golden_dense(cs, n_cols):
         m[labs] = vals[k:k + len(labs)]
         k += len(labs)
         out.append(dict(gene=rec["gene_info_str"], K=K, alpha=np.asarray(rec["alpha_arr"]), dense=m))
-    assert k == len(rows)
+    assert k == len(vals)
     return out
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("c,j", dp._golden_params())
+@pytest.mark.parametrize("c,j", rc.golden_perm_params())
 def test_golden_case_and_cluster_file(c, j, tmp_path):
     """every golden case and cluster file that gives two non-empty populations: the first such cluster against the
     rest, 199 permutations; n_ge equal to the exact oracle's (a case without a tested record gives the header alone)"""
-    from scape.apa_core import Parameters
-    f = dp._fixture()
-    cs = dp._case(c)
-    bc = rc.text(f, cs["barcode"])
-    texts = {fn: rc.text(f, k) for fn, k in zip(cs["clu_files"], cs["clusters"])}
-    paths = rc.write_dir(str(tmp_path), cs["res"], cs["records"], bc, texts, Parameters)
+    cs = rc.fixture_case(c)
+    texts = rc.cluster_texts(cs)
+    bc, paths = rc.write_case(cs, tmp_path)
     fn = cs["clu_files"][j]
-    id1 = dp._golden_ident(bc, texts[fn])
-    recs = _golden_dense(cs, len(dp._column_ids(bc)))
+    id1 = rc.golden_ident(bc, texts[fn])
+    recs = _golden_dense(cs, len(rc.column_ids(bc)))
     check(tmp_path, paths[j], texts[fn], cs["res"], recs, bc, id1, None, 199, 1, f"{cs['name']}/{fn}")
 
 
 # ---------------------------------------------------------------- GPU: the synthetic directory
-_SYN = {}
-
-
+@functools.lru_cache(maxsize=None)
 def _syn():
-    if not _SYN:
-        records, bc, clu_text = dp.synthetic()
-        _SYN.update(records=records, bc=bc, clu=clu_text, recs=dense_of(records, dp._column_ids(bc)))
-    return _SYN
-
-
-def _write_syn(root, n_rec=None):
-    from scape.apa_core import Parameters
-    s = _syn()
-    return rc.write_dir(str(root), "res.gene.pkl", s["records"][:n_rec], s["bc"], {"syn_groups.csv": s["clu"]},
-                        Parameters)[0]
+    records, bc, clu_text = rc.synthetic()
+    return dict(records=records, bc=bc, clu=clu_text, recs=dense_of(records, rc.column_ids(bc)))
 
 
 def _sense(rows, id2, what):
@@ -475,7 +422,7 @@ def test_synthetic_directory(id2, tmp_path):
     """999 permutations of 230 + 301 cells (with --idents_2) and of 230 + 341 (without): parity with the exact oracle,
     and sense, asserted on the oracle first and then on the file"""
     s = _syn()
-    path = _write_syn(tmp_path)
+    path = rc.write_synthetic(tmp_path)
     text, lines = check(tmp_path, path, s["clu"], "res.gene.pkl", s["recs"], s["bc"], "A", id2, 999, 1, f"syn/{id2}")
     assert max(ln["num_pa"] for ln in lines) == 63                        # the K = 63 record keeps all its rows
     _sense([(ln["gene"].split(":")[1], ln["lo"], ln["delta"]) for ln in lines], id2, "oracle")
@@ -489,7 +436,7 @@ def test_synthetic_directory(id2, tmp_path):
 def test_tile_edges(n_perm, tmp_path):
     """a workgroup of the kernel takes 256 permutations: one short of a tile, a full tile, one over, and one"""
     s = _syn()
-    path = _write_syn(tmp_path, 12)
+    path = rc.write_synthetic(tmp_path, 12)
     _text, lines = check(tmp_path, path, s["clu"], "res.gene.pkl", s["recs"][:12], s["bc"], "C", "A", n_perm, 5,
                          f"tile/{n_perm}")
     assert len(lines) == 10
@@ -501,8 +448,8 @@ def test_tile_edges(n_perm, tmp_path):
 def test_small_and_lopsided_populations(n_cells, n_a, tmp_path):
     """populations of 1 cell and of n - 1 cells, n = 64 exactly, one over, and the smallest n (where every labelling
     ties with the observed one exactly)"""
-    path, clu_text, bc, _rec_rows = dp._small_dir(tmp_path, n_cells, n_a, 100 + n_cells + n_a)
-    recs = dense_of(read_records(os.path.join(str(tmp_path), "res.utr.pkl")), dp._column_ids(bc))
+    path, clu_text, bc, _records, _ids = rc.small_dir(tmp_path, n_cells, n_a, 100 + n_cells + n_a)
+    recs = dense_of(read_records(os.path.join(str(tmp_path), "res.utr.pkl")), rc.column_ids(bc))
     _text, lines = check(tmp_path, path, clu_text, "res.utr.pkl", recs, bc, "A", None, 300, 9, f"small/{n_cells}/{n_a}")
     assert len(lines) == 8
     if n_cells == 2:
@@ -512,7 +459,7 @@ def test_small_and_lopsided_populations(n_cells, n_a, tmp_path):
 @pytest.mark.gpu
 def test_seeds(tmp_path):
     """the same seed gives the same bytes, another seed other counts"""
-    path = _write_syn(tmp_path)
+    path = rc.write_synthetic(tmp_path)
     a = _command(tmp_path, path, "res.gene.pkl", "A", "B", 99, 1)
     b = _command(tmp_path, path, "res.gene.pkl", "A", "B", 99, 1)
     c = _command(tmp_path, path, "res.gene.pkl", "A", "B", 99, 2)
@@ -526,7 +473,7 @@ def test_batch_and_chunk_invariance(tmp_path, monkeypatch):
     """records split over several count batches and the permutations over several chunks: the same bytes, and the
     expected sequence of masks calls"""
     from scape_amd import _lib, report
-    path = _write_syn(tmp_path)
+    path = rc.write_synthetic(tmp_path)
     big = _command(tmp_path, path, "res.gene.pkl", "A", None, 999, 1)
     lib = _lib.load_library()
     calls = {"masks": [], "len": 0}
@@ -643,7 +590,7 @@ def test_band_counts_a_tie_that_f64_rounds_below():
     first: the exact oracle has no near tie (lo == hi), and the device's own f64 arithmetic WITHOUT the band would count
     fewer labellings than lo.  Then the entry point must return lo"""
     from scape_amd import _lib
-    from scape_amd._lib import P_d, P_i8, P_i32, P_i64, check as chk, ptr
+    from scape_amd._lib import P_d, P_i64, check as chk, ptr
     n1, n, seed, n_perm = 4, 10, 77, 300
     x = np.array([0.1, 0.3, 0.7, 0.7, 1.9, 1.9])
     rng = np.random.default_rng(21)
@@ -656,7 +603,7 @@ def test_band_counts_a_tie_that_f64_rounds_below():
     plain = rounded_below = 0
     for p in range(1, n_perm + 1):
         member = bytearray(n)
-        for j in dp.members(seed, p, n1, n):
+        for j in rc.members(seed, p, n1, n):
             member[j] = 1
         o.count(member)
         a = o.row_sums(member)
@@ -668,17 +615,14 @@ def test_band_counts_a_tie_that_f64_rounds_below():
     lab, cb = np.nonzero(M)
     rep = M[lab, cb]
     lab, cb = np.repeat(lab, rep).astype(np.int64), np.repeat(cb, rep).astype(np.int64)
-    off, Ks, table = np.array([0, len(lab)], np.int64), np.array([len(x)], np.int32), np.arange(n, dtype=np.int32)
-    row_tot, complete, bad = np.zeros(len(x), np.int64), np.zeros(1, np.int8), np.zeros(2, np.int64)
+    off, Ks = np.array([0, len(lab)], np.int64), np.array([len(x)], np.int32)
     roff, rows = np.array([0, len(x)], np.int64), np.arange(len(x), dtype=np.int64)
     tol = np.array([np.ldexp(float(w.max()), -40)])
     t, a0, d0, n_ge = np.zeros(len(x), np.int64), np.zeros(len(x), np.int64), np.zeros(1), np.zeros(1, np.int64)
     ctx = _lib.default_context(None)
     lib = ctx.lib
     try:
-        chk(lib.scape_hip_report_counts(ctx.h, 1, ptr(off, P_i64), ptr(Ks, P_i32), ptr(lab, P_i64), ptr(cb, P_i64), 0, n,
-                                        ptr(table, P_i32), n, ptr(row_tot, P_i64), ptr(complete, P_i8),
-                                        ptr(bad, P_i64)), "counts")
+        rc.device_counts(ctx, Ks, off, lab, cb, n)
         chk(lib.scape_hip_report_perm_masks(ctx.h, n1, n - n1, 1, n_perm, seed), "perm_masks")
         chk(lib.scape_hip_report_perm_len(ctx.h, 1, ptr(roff, P_i64), ptr(rows, P_i64), ptr(w, P_d), ptr(tol, P_d),
                                           ptr(t, P_i64), ptr(a0, P_i64), ptr(d0, P_d), ptr(n_ge, P_i64)), "perm_len")
@@ -697,31 +641,13 @@ def test_entry_point():
     (2 R + 3) 2^-53 span; one call with 300 permutations equals three calls with 100, 156 and 44 that accumulate;
     then the error paths"""
     from scape_amd import _lib
-    from scape_amd._lib import P_d, P_i8, P_i32, P_i64, check as chk, ptr
-    rng = np.random.default_rng(8)
-    n1, n2, rest, seed, n_perm = 70, 91, 9, 77, 300
-    n, n_cols = n1 + n2, n1 + n2 + rest
-    Ks = np.array([2, 5, 70, 150], dtype=np.int32)
-    lab, cb, off = [], [], [0]
-    for K in Ks.tolist():
-        m = 40 * K + 300
-        lab.append(rng.integers(0, K + 1, m))
-        cb.append((rng.integers(0, n_cols, m) ** 2) // n_cols)
-        off.append(off[-1] + m)
-    lab, cb, off = np.concatenate(lab).astype(np.int64), np.concatenate(cb).astype(np.int64), np.array(off, np.int64)
-    rowbase = np.concatenate([[0], np.cumsum(Ks)])
-    dense = np.zeros((int(Ks.sum()), n_cols), dtype=np.int64)
-    for r, K in enumerate(Ks.tolist()):
-        l, c = lab[off[r]:off[r + 1]], cb[off[r]:off[r + 1]]
-        np.add.at(dense, (rowbase[r] + l[l < K], c[l < K]), 1)
-    kept = [np.nonzero(dense[rowbase[r]:rowbase[r + 1], :n].sum(axis=1) > 0)[0] + rowbase[r] for r in range(len(Ks))]
-    rows = np.concatenate(kept).astype(np.int64)
-    roff = np.concatenate([[0], np.cumsum([len(k) for k in kept])]).astype(np.int64)
-    assert len(kept[3]) > 128 and len(kept[2]) > 64
+    from scape_amd._lib import P_d, P_i64, check as chk, ptr
+    n1, n2, n_cols, seed, n_perm, Ks, off, lab, cb, dense, rows, roff, rng = rc.entry_point_matrix()
+    n = n1 + n2
     sub = dense[rows][:, :n]
     t_want, a0_want = sub.sum(axis=1), sub[:, :n1].sum(axis=1)
     # positions with fractional parts (exact in f64), unsorted within a record
-    x = np.concatenate([rng.permutation(rng.choice(40000, len(k), replace=False)) / 8.0 + 3.0 for k in kept])
+    x = np.concatenate([rng.permutation(rng.choice(40000, k, replace=False)) / 8.0 + 3.0 for k in np.diff(roff).tolist()])
     w = np.concatenate([x[roff[r]:roff[r + 1]] - x[roff[r]:roff[r + 1]].min() for r in range(len(Ks))])
     span = np.array([w[roff[r]:roff[r + 1]].max() for r in range(len(Ks))])
     tol = np.ldexp(span, -40)
@@ -732,23 +658,18 @@ def test_entry_point():
         assert orc[-1].tested() and orc[-1].span == Fraction(float(span[r]))
     for p in range(1, n_perm + 1):
         member = bytearray(n)
-        for j in dp.members(seed, p, n1, n):
+        for j in rc.members(seed, p, n1, n):
             member[j] = 1
         for o in orc:
             o.count(member)
     assert all(o.lo == o.hi for o in orc), [(o.lo, o.hi) for o in orc]
     ge_want = np.array([o.lo for o in orc], dtype=np.int64)
     print("n_ge of the oracle", ge_want.tolist())
-    table = np.arange(n_cols, dtype=np.int32)
     ctx = _lib.default_context(None)
     lib = ctx.lib
 
     def counts():
-        row_tot, complete, bad = np.zeros(int(Ks.sum()), np.int64), np.zeros(len(Ks), np.int8), np.zeros(2, np.int64)
-        chk(lib.scape_hip_report_counts(ctx.h, len(Ks), ptr(off, P_i64), ptr(Ks, P_i32), ptr(lab, P_i64),
-                                        ptr(cb, P_i64), 0, n_cols, ptr(table, P_i32), n_cols, ptr(row_tot, P_i64),
-                                        ptr(complete, P_i8), ptr(bad, P_i64)), "counts")
-        assert np.array_equal(row_tot, dense.sum(axis=1))
+        assert np.array_equal(rc.device_counts(ctx, Ks, off, lab, cb, n_cols), dense.sum(axis=1))
 
     def outs():
         return (np.full(len(rows), -1, np.int64), np.full(len(rows), -1, np.int64), np.full(len(Ks), -1.0),

@@ -18,7 +18,7 @@ n1 = 1, n_perm = 1, and one 4-line golden case); with `>` for `>=` in both excee
 ties with the observed one still lies above stat(0) (1 - 2^-40), so `>` differs only where the observed statistic is
 0 (four golden cases and n = 2 have such sites)."""
 import csv
-import glob
+import functools
 import io
 import math
 import os
@@ -26,49 +26,16 @@ from fractions import Fraction
 
 import numpy as np
 import pytest
-from click.testing import CliRunner
 
-from conftest import load_npz
 import report_cases as rc
+from report_cases import G, M64, bh, key, members, mix, no_gpu, populations, run as _run  # noqa: F401  (no_gpu: fixture)
 
 HEADER = ("gene,pa_info,pct.1,pct.2,versus,usage.1,usage.2,delta_usage,n_ge,p_val,p_val_adj,gene_stat,gene_n_ge,"
           "gene_p_val,gene_p_val_adj,n_perm")
-M64 = (1 << 64) - 1
-G = 0x9E3779B97F4A7C15
-RTOL = Fraction(1, 10 ** 12)
 
 
-# ---------------------------------------------------------------- the contract, restated
-def mix(z):
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return z ^ (z >> 31)
-
-
-def key(seed, p, j):
-    h = mix((mix((seed + G * p) & M64) + G * (j + 1)) & M64)
-    return (h & ~0xFFFFFF & M64) | j
-
-
-def members(seed, p, n1, n):
-    """positions of population 1 under permutation p >= 1: the n1 smallest keys (a key's low 24 bits are its position)"""
-    base = mix((seed + G * p) & M64)
-    keys = sorted((mix((base + G * (j + 1)) & M64) & ~0xFFFFFF & M64) | j for j in range(n))
-    return [k & 0xFFFFFF for k in keys[:n1]]
-
-
-def bh(ps):
-    """Benjamini-Hochberg on Fractions: adj_i = min(1, min over j with p_j >= p_i of m p_j / rank_j)"""
-    m = len(ps)
-    order = sorted(range(m), key=lambda i: ps[i])
-    out, best = [None] * m, Fraction(1)
-    for rank in range(m, 0, -1):
-        i = order[rank - 1]
-        best = min(best, ps[i] * m / rank)
-        out[i] = best
-    return out
-
-
+# ---------------------------------------------------------------- the contract, restated (mix, key, members, bh,
+# populations and the inputs' definitions: tests/report_cases.py, which imports nothing from scape_amd either)
 class _Rec:
     """a tested record: per kept row its nonzeros [(position, count)], t_i and a_i(0); integers only"""
 
@@ -160,12 +127,6 @@ def assert_no_near_tie(lines, what):
         assert ln["gene_ge"][0] == ln["gene_ge"][1], (what, ln["gene"], ln["gene_ge"])
 
 
-def _close(got_text, want):
-    got = Fraction(float(got_text))
-    assert repr(float(got_text)) == got_text
-    return abs(got - want) <= RTOL * abs(want)
-
-
 def compare(text, lines, versus, n_perm, what):
     rows = list(csv.reader(io.StringIO(text)))
     assert ",".join(rows[0]) == HEADER
@@ -182,98 +143,16 @@ def compare(text, lines, versus, n_perm, what):
         assert got[13] == repr((1 + ln["gene_ge"][0]) / (1 + n_perm)), ctx
         for col, want in ((5, ln["usage1"]), (6, ln["usage2"]), (7, ln["delta"]), (10, ln["p_adj"]), (11, ln["S0"]),
                           (14, ln["gene_p_adj"])):
-            assert _close(got[col], want), (ctx, col, float(want))
+            assert rc.close(got[col], want), (ctx, col, float(want))
 
 
-# ---------------------------------------------------------------- inputs
-def _column_ids(bc_csv):
-    rows = list(csv.reader(io.StringIO(bc_csv)))
-    ip = rows[0].index("index")
-    return [int(r[ip]) for r in rows[1:]]
-
-
-def _cluster_rows(clu_csv):
-    rows = list(csv.reader(io.StringIO(clu_csv)))
-    ip = rows[0].index("index")
-    other = [j for j in range(len(rows[0])) if j != ip][0]
-    return [(int(r[ip]), r[other]) for r in rows[1:]]
-
-
-def populations(bc_csv, clu_csv, id1, id2):
-    """(columns of population 1, columns of population 2), ascending; clusters as text, a repeated id keeps its last
-    row; without id2 population 2 is every other column that has a cluster"""
-    last = {}
-    for i, name in _cluster_rows(clu_csv):
-        last[i] = name
-    col_clu = [last.get(i, "") for i in _column_ids(bc_csv)]
-    c1 = [j for j, x in enumerate(col_clu) if x == id1]
-    c2 = [j for j, x in enumerate(col_clu) if (x == id2 if id2 is not None else x != "" and x != id1)]
-    return c1, c2
-
-
-def _first_clusters(clu_csv):
-    order = []
-    for _i, name in _cluster_rows(clu_csv):
-        if name != "" and name not in order:
-            order.append(name)
-    return order
-
-
-def pa_info(rec, lab):
-    chrom, gene, utr, st_en, strand = rec["gene_info_str"].split(":")
-    st, en = (int(v) for v in st_en.split("-"))
-    a = int(rec["alpha_arr"][lab])
-    loc = a + st if strand == "+" else en - a + 1
-    return f"{chrom}:{loc}:{float(rec['beta_arr'][lab])!r}:{strand}:{lab + 1}:{gene}:{utr}"
-
-
-def rec_rows_of(records, col_ids):
-    """[(gene, [(pa_info, counts over the columns)])]: per record the labels < K with reads, in label order"""
-    col_of = {i: j for j, i in enumerate(col_ids)}
-    out = []
-    for rec in records:
-        K = int(rec["K"])
-        m = np.zeros((K, len(col_ids)), dtype=np.int64)
-        lab, cb = np.asarray(rec["label_arr"]), np.asarray(rec["cb_id_arr"])
-        ok = lab < K
-        np.add.at(m, (lab[ok], [col_of[int(i)] for i in cb[ok]]), 1)
-        out.append((rec["gene_info_str"], [(pa_info(rec, l), m[l]) for l in range(K) if m[l].any()]))
-    return out
-
-
-def _cli():
-    from scape.cli import cli
-    return cli
-
-
-def _run(args):
-    return CliRunner().invoke(_cli(), args)
-
-
+# ---------------------------------------------------------------- the command
 def _args(root, clu, res="res.gene.pkl", id1=None, id2=None, n_perm=None, seed=None):
-    a = ["diff_pa", "--output_dir", str(root), "--res_pkl_file", res, "--cell_cluster_file", str(clu)]
-    for opt, v in (("--idents_1", id1), ("--idents_2", id2), ("--n_perm", n_perm), ("--seed", seed)):
-        if v is not None:
-            a += [opt, str(v)]
-    return a
-
-
-def _path(root, clu, res, id1, id2):
-    kind = res[len("res."):-len(".pkl")]
-    stem = os.path.splitext(os.path.basename(str(clu)))[0]
-    return os.path.join(str(root), f"{stem}.{kind}.{id1}_vs_{id2 if id2 is not None else 'rest'}.diff_pa.csv")
-
-
-def _parts_left(root):
-    return glob.glob(os.path.join(str(root), "**", "*.part"), recursive=True)
+    return rc.perm_args("diff_pa", root, clu, res, id1, id2, n_perm, seed)
 
 
 def _command(root, clu, res, id1, id2, n_perm, seed, what=""):
-    r = _run(_args(root, clu, res, id1, id2, n_perm, seed))
-    assert r.exit_code == 0, (what, r.output, repr(r.exception))
-    assert not _parts_left(root)
-    with open(_path(root, clu, res, id1, id2), newline="") as fh:
-        return fh.read()
+    return rc.perm_command("diff_pa", root, clu, res, id1, id2, n_perm, seed, what)
 
 
 def check(root, clu_path, clu_text, res, rec_rows, bc, id1, id2, n_perm, seed, what):
@@ -374,16 +253,6 @@ def test_utils_import_path():
     assert su.diff_pa is report.diff_pa
 
 
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from scape_amd import _lib
-
-    def refuse(*a, **k):
-        raise AssertionError("the GPU was touched before the prerequisite checks")
-    monkeypatch.setattr(_lib, "default_context", refuse)
-    monkeypatch.setattr(_lib, "Context", refuse)
-
-
 def test_prerequisites_and_argument_errors(tmp_path, no_gpu):
     clu = tmp_path / "groups.csv"
     r = _run(_args(tmp_path / "nope", clu, id1="A"))
@@ -416,147 +285,49 @@ def test_prerequisites_and_argument_errors(tmp_path, no_gpu):
 
 
 # ---------------------------------------------------------------- GPU: golden cases
-_F = None
-
-
-def _fixture():
-    global _F
-    if _F is None:
-        _F = load_npz("fixture_report.npz")
-    return _F
-
-
-_CASES = {}
-
-
-def _case(c):
-    if c not in _CASES:
-        _CASES[c] = rc.case(_fixture(), c)
-    return _CASES[c]
-
-
-def _golden_ident(bc, clu_text):
-    """the first cluster (in order of first appearance) that has a column and leaves another column for the rest"""
-    for name in _first_clusters(clu_text):
-        c1, c2 = populations(bc, clu_text, name, None)
-        if c1 and c2:
-            return name
-    return None
-
-
-def _golden_params():
-    f = _fixture()
-    out = []
-    for c in rc.case_ids(f):
-        cs = _case(c)
-        bc = rc.text(f, cs["barcode"])
-        for j, (fn, k) in enumerate(zip(cs["clu_files"], cs["clusters"])):
-            if _golden_ident(bc, rc.text(f, k)) is not None:
-                out.append(pytest.param(c, j, id=f"{cs['name'].replace('/', '-')}-{fn}"))
-    return out
-
-
 def _golden_rec_rows(cs, n_cols):
     """the reference's own matrix rows (tests/golden/fixture_report.npz), cut into records: a record's rows are its
     labels < K that have a read, in label order"""
-    rows = list(csv.reader(io.StringIO(cs["mat_body"])))
-    dense = np.array([[int(float(v)) for v in r[1:]] for r in rows], dtype=np.int64).reshape(len(rows), n_cols)
+    pas, dense = rc.dense_of_body(cs["mat_body"], n_cols)
     out, k = [], 0
     for rec in cs["records"]:
         lab = np.asarray(rec["label_arr"])
         n = len(np.unique(lab[lab < int(rec["K"])]))
-        out.append((rec["gene_info_str"], [(rows[k + i][0], dense[k + i]) for i in range(n)]))
+        out.append((rec["gene_info_str"], [(pas[k + i], dense[k + i]) for i in range(n)]))
         k += n
-    assert k == len(rows)
+    assert k == len(pas)
     return out
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("c,j", _golden_params())
+@pytest.mark.parametrize("c,j", rc.golden_perm_params())
 def test_golden_case_and_cluster_file(c, j, tmp_path):
     """every golden case and cluster file that gives two non-empty populations: the first such cluster against the
     rest, 199 permutations; counts equal to the exact oracle's"""
-    from scape.apa_core import Parameters
-    f = _fixture()
-    cs = _case(c)
-    bc = rc.text(f, cs["barcode"])
-    texts = {fn: rc.text(f, k) for fn, k in zip(cs["clu_files"], cs["clusters"])}
-    paths = rc.write_dir(str(tmp_path), cs["res"], cs["records"], bc, texts, Parameters)
+    cs = rc.fixture_case(c)
+    texts = rc.cluster_texts(cs)
+    bc, paths = rc.write_case(cs, tmp_path)
     fn = cs["clu_files"][j]
-    id1 = _golden_ident(bc, texts[fn])
-    rec_rows = _golden_rec_rows(cs, len(_column_ids(bc)))
+    id1 = rc.golden_ident(bc, texts[fn])
+    rec_rows = _golden_rec_rows(cs, len(rc.column_ids(bc)))
     check(tmp_path, paths[j], texts[fn], cs["res"], rec_rows, bc, id1, None, 199, 1, f"{cs['name']}/{fn}")
 
 
 def test_golden_cases_are_used():
-    ids = [p.id for p in _golden_params()]
+    ids = [p.id for p in rc.golden_perm_params()]
     assert len(ids) >= 30 and any(i.startswith("SCZ") for i in ids) and any(i.startswith("chain") for i in ids)
 
 
 # ---------------------------------------------------------------- GPU: the synthetic directory
-SYN_SEED = 11
-N_PLANTED = 4
-
-
-def synthetic(gen_seed=SYN_SEED, n_cells=600):
-    """about 40 records, K = 1..8 and one K = 63, 600 barcodes with scrambled ids: 230 cells of cluster A, 301 of B, 40
-    of C, 29 without a cluster; 95 % of the (site, cell) counts are zero.  Records 0..3 have a planted usage shift in A
-    (many reads, the first site ten times as likely there), record 4 a row with reads only in cells of no cluster,
-    record 5 reads only in A, record 6 K = 1; some reads carry the label K (no site)."""
-    rng = np.random.default_rng(gen_seed)
-    ids = (np.arange(n_cells) * 7919 + 13) % 100003                      # distinct, scrambled
-    clu = np.array(["A"] * 230 + ["B"] * 301 + ["C"] * 40 + [""] * (n_cells - 571), dtype=object)
-    clu = clu[rng.permutation(n_cells)]
-    bc = "CB,index\n" + "".join(f"CELL{j:04d}-1,{i}\n" for j, i in enumerate(ids.tolist()))
-    order = rng.permutation(n_cells)
-    clu_text = "index,group\n" + "".join(f"{ids[j]},{clu[j]}\n" for j in order.tolist() if not (clu[j] == "" and j % 2))
-    is_a, no_clu = clu == "A", clu == ""
-    records = []
-    Ks = [2, 3, 4, 5, 3, 4, 1] + [int(k) for k in rng.integers(1, 9, 32)] + [63]
-    for r, K in enumerate(Ks):
-        planted = r < N_PLANTED
-        dens = np.full((K, n_cells), 0.30 if planted else 0.05)
-        if planted:
-            dens[0, ~is_a] = 0.03
-        if r == 4:
-            dens[1, :] = 0.0
-            dens[1, no_clu] = 0.5
-        if r == 5:
-            dens[:, ~is_a] = 0.0
-        cnt = (rng.random((K, n_cells)) < dens) * rng.integers(1, 4, (K, n_cells))
-        lab, cell = np.nonzero(cnt)
-        rep = cnt[lab, cell]
-        lab, cell = np.repeat(lab, rep), np.repeat(cell, rep)
-        extra = rng.integers(0, n_cells, 5)                              # reads of no site
-        lab, cell = np.concatenate([lab, np.full(5, K)]), np.concatenate([cell, extra])
-        mixo = rng.permutation(len(lab))
-        strand = "+-"[r % 2]
-        records.append(dict(gene_info_str=f"{1 + r % 5}:GENE{r}:{1 + r % 3}:{1000 * r + 100}-{1000 * r + 900}:{strand}",
-                            K=K, alpha_arr=np.sort(rng.choice(np.arange(5, 790), K, replace=False)),
-                            beta_arr=rng.choice([5.0, 7.5, 10.0, 32.5], K), label_arr=lab[mixo].astype(np.int64),
-                            cb_id_arr=ids[cell[mixo]].astype(np.int64)))
-    return records, bc, clu_text
-
-
-_SYN = {}
-
-
+@functools.lru_cache(maxsize=None)
 def _syn():
-    if not _SYN:
-        records, bc, clu_text = synthetic()
-        _SYN.update(records=records, bc=bc, clu=clu_text, rec_rows=rec_rows_of(records, _column_ids(bc)))
-    return _SYN
-
-
-def _write_syn(root):
-    from scape.apa_core import Parameters
-    s = _syn()
-    return rc.write_dir(str(root), "res.gene.pkl", s["records"], s["bc"], {"syn_groups.csv": s["clu"]}, Parameters)[0]
+    records, bc, clu_text = rc.synthetic()
+    return dict(records=records, bc=bc, clu=clu_text, rec_rows=rc.rec_rows_of(records, rc.column_ids(bc)))
 
 
 def _sense(lines, n_perm, what):
     """planted records reach the smallest p-value, no null record does; on whatever `lines` holds (oracle or file)"""
-    planted = {f"GENE{r}" for r in range(N_PLANTED)}
+    planted = {f"GENE{r}" for r in range(rc.N_PLANTED)}
     seen = set()
     for gene, ge in lines:
         name = gene.split(":")[1]
@@ -575,7 +346,7 @@ def test_synthetic_directory(id2, tmp_path):
     parity with the exact oracle, and sense: the planted records have gene_p_val = 1 / 1000, no other record has -
     asserted on the oracle, then on the file"""
     s = _syn()
-    path = _write_syn(tmp_path)
+    path = rc.write_synthetic(tmp_path)
     c1, c2 = populations(s["bc"], s["clu"], "A", id2)
     assert (len(c1), len(c2)) == ((230, 301) if id2 else (230, 341))
     text, lines = check(tmp_path, path, s["clu"], "res.gene.pkl", s["rec_rows"], s["bc"], "A", id2, 999, 1, f"syn/{id2}")
@@ -594,30 +365,9 @@ def test_synthetic_directory(id2, tmp_path):
 @pytest.mark.parametrize("n_perm", [1, 255, 256, 257])
 def test_tile_edges(n_perm, tmp_path):
     """a workgroup of the test kernel takes 256 permutations: one short of a tile, a full tile, one over, and one"""
-    from scape.apa_core import Parameters
     s = _syn()
-    path = rc.write_dir(str(tmp_path), "res.gene.pkl", s["records"][:12], s["bc"], {"syn_groups.csv": s["clu"]},
-                        Parameters)[0]
+    path = rc.write_synthetic(tmp_path, 12)
     check(tmp_path, path, s["clu"], "res.gene.pkl", s["rec_rows"][:12], s["bc"], "C", "A", n_perm, 5, f"tile/{n_perm}")
-
-
-def _small_dir(root, n_cells, n_a, gen_seed):
-    """8 records on n_cells barcodes, the first n_a of them in cluster A, the others in B"""
-    from scape.apa_core import Parameters
-    rng = np.random.default_rng(gen_seed)
-    ids = np.arange(n_cells) * 3 + 2
-    bc = "CB,index\n" + "".join(f"S{j}-1,{i}\n" for j, i in enumerate(ids.tolist()))
-    clu_text = "index,group\n" + "".join(f"{i},{'A' if j < n_a else 'B'}\n" for j, i in enumerate(ids.tolist()))
-    records = []
-    for r in range(8):
-        K = 2 + r % 4
-        n = 400
-        records.append(dict(gene_info_str=f"2:SG{r}:1:{500 * r + 1}-{500 * r + 400}:+", K=K,
-                            alpha_arr=np.arange(K) * 40 + 10, beta_arr=np.full(K, 10.0),
-                            label_arr=rng.integers(0, K, n).astype(np.int64),
-                            cb_id_arr=ids[rng.integers(0, n_cells, n)].astype(np.int64)))
-    path = rc.write_dir(str(root), "res.utr.pkl", records, bc, {"small.csv": clu_text}, Parameters)[0]
-    return path, clu_text, bc, rec_rows_of(records, ids.tolist())
 
 
 @pytest.mark.gpu
@@ -625,7 +375,8 @@ def _small_dir(root, n_cells, n_a, gen_seed):
                          ids=["64-1", "64-63", "64-32", "65-1", "130-129", "2-1"])
 def test_small_and_lopsided_populations(n_cells, n_a, tmp_path):
     """populations of 1 cell and of n - 1 cells, n = 64 exactly, one over, and the smallest n"""
-    path, clu_text, bc, rec_rows = _small_dir(tmp_path, n_cells, n_a, 100 + n_cells + n_a)
+    path, clu_text, bc, records, ids = rc.small_dir(tmp_path, n_cells, n_a, 100 + n_cells + n_a)
+    rec_rows = rc.rec_rows_of(records, ids)
     _text, lines = check(tmp_path, path, clu_text, "res.utr.pkl", rec_rows, bc, "A", None, 300, 9, f"small/{n_cells}/{n_a}")
     assert len(lines) >= 12
 
@@ -634,7 +385,7 @@ def test_small_and_lopsided_populations(n_cells, n_a, tmp_path):
 def test_seeds(tmp_path):
     """the same seed gives the same bytes, another seed other counts"""
     s = _syn()
-    path = _write_syn(tmp_path)
+    path = rc.write_synthetic(tmp_path)
     a = _command(tmp_path, path, "res.gene.pkl", "A", "B", 99, 1)
     b = _command(tmp_path, path, "res.gene.pkl", "A", "B", 99, 1)
     c = _command(tmp_path, path, "res.gene.pkl", "A", "B", 99, 2)
@@ -648,7 +399,7 @@ def test_batch_and_chunk_invariance(tmp_path, monkeypatch):
     """records split over several count batches and the permutations over several chunks: the same bytes"""
     from scape_amd import _lib, report
     s = _syn()
-    path = _write_syn(tmp_path)
+    path = rc.write_synthetic(tmp_path)
     big = _command(tmp_path, path, "res.gene.pkl", "A", None, 999, 1)
     lib = _lib.load_library()
     calls = {"masks": [], "test": 0}
@@ -707,27 +458,9 @@ def test_entry_points():
     against a numpy restatement (every comparison at least 1e-9 away from a tie, asserted); one call with 300
     permutations equals three calls with 100, 156 and 44 that accumulate; then the error paths"""
     from scape_amd import _lib
-    from scape_amd._lib import P_d, P_i8, P_i32, P_i64, check as chk, ptr
-    rng = np.random.default_rng(8)
-    n1, n2, rest, seed, n_perm = 70, 91, 9, 77, 300
-    n, n_cols = n1 + n2, n1 + n2 + rest
-    Ks = np.array([2, 5, 70, 150], dtype=np.int32)
-    lab, cb, off = [], [], [0]
-    for K in Ks.tolist():
-        m = 40 * K + 300
-        lab.append(rng.integers(0, K + 1, m))
-        cb.append((rng.integers(0, n_cols, m) ** 2) // n_cols)
-        off.append(off[-1] + m)
-    lab, cb, off = np.concatenate(lab).astype(np.int64), np.concatenate(cb).astype(np.int64), np.array(off, np.int64)
-    rowbase = np.concatenate([[0], np.cumsum(Ks)])
-    dense = np.zeros((int(Ks.sum()), n_cols), dtype=np.int64)
-    for r, K in enumerate(Ks.tolist()):
-        l, c = lab[off[r]:off[r + 1]], cb[off[r]:off[r + 1]]
-        np.add.at(dense, (rowbase[r] + l[l < K], c[l < K]), 1)
-    kept = [np.nonzero(dense[rowbase[r]:rowbase[r + 1], :n].sum(axis=1) > 0)[0] + rowbase[r] for r in range(len(Ks))]
-    rows = np.concatenate(kept).astype(np.int64)
-    roff = np.concatenate([[0], np.cumsum([len(k) for k in kept])]).astype(np.int64)
-    assert len(kept[3]) > 128 and len(kept[2]) > 64
+    from scape_amd._lib import P_d, P_i64, check as chk, ptr
+    n1, n2, n_cols, seed, n_perm, Ks, off, lab, cb, dense, rows, roff, rng = rc.entry_point_matrix()
+    n = n1 + n2
     sub = dense[rows][:, :n]
     t_want, a0_want = sub.sum(axis=1), sub[:, :n1].sum(axis=1)
     member = np.stack([np.arange(n) < n1] + [_np_members(seed, p, n1, n) for p in range(1, n_perm + 1)])
@@ -748,16 +481,11 @@ def test_entry_points():
         site_want[sl] = (d[:, 1:] >= d[:, :1] * (1 - 2.0 ** -40)).sum(axis=1)
         gene_want[r] = (S[1:] >= S[0] * (1 - 2.0 ** -40)).sum()
         stat0_want[r] = S[0]
-    table = np.arange(n_cols, dtype=np.int32)
     ctx = _lib.default_context(None)
     lib = ctx.lib
 
     def counts():
-        row_tot, complete, bad = np.zeros(int(Ks.sum()), np.int64), np.zeros(len(Ks), np.int8), np.zeros(2, np.int64)
-        chk(lib.scape_hip_report_counts(ctx.h, len(Ks), ptr(off, P_i64), ptr(Ks, P_i32), ptr(lab, P_i64),
-                                        ptr(cb, P_i64), 0, n_cols, ptr(table, P_i32), n_cols, ptr(row_tot, P_i64),
-                                        ptr(complete, P_i8), ptr(bad, P_i64)), "counts")
-        assert np.array_equal(row_tot, dense.sum(axis=1))
+        assert np.array_equal(rc.device_counts(ctx, Ks, off, lab, cb, n_cols), dense.sum(axis=1))
 
     def outs():
         return (np.full(len(rows), -1, np.int64), np.full(len(rows), -1, np.int64), np.zeros(len(rows), np.int64),

@@ -5,8 +5,6 @@ The expected texts of the golden cases (tests/golden/fixture_report.npz) come fr
 body: its rows are the matrix rows, its first field is pa_info, its nonzero fields are the entries.  A wide synthetic
 stream is checked against an np.add.at restatement of the counts.  Every file is compared byte for byte after
 decompression, and the matrix is also read back with scipy.io.mmread."""
-import csv
-import glob
 import gzip
 import io
 import os
@@ -14,22 +12,12 @@ import os
 import numpy as np
 import pandas as pd
 import pytest
-from click.testing import CliRunner
 
-from conftest import load_npz
 import report_cases as rc
+from report_cases import no_gpu, parts_left as _parts_left, run as _run  # noqa: F401  (no_gpu is a fixture)
 
 BANNER = "%%MatrixMarket matrix coordinate integer general\n"
 FILES = ("matrix.mtx.gz", "features.tsv.gz", "barcodes.tsv.gz")
-
-
-def _cli():
-    from scape.cli import cli
-    return cli
-
-
-def _run(args):
-    return CliRunner().invoke(_cli(), args)
 
 
 def _mtx_args(root, res="res.gene.pkl"):
@@ -48,10 +36,6 @@ def _read_dir(root, res="res.gene.pkl"):
     return out
 
 
-def _parts_left(root):
-    return glob.glob(os.path.join(str(root), "**", "*.part"), recursive=True)
-
-
 def _texts(pa_info, dense, barcodes):
     """the three files of a matrix: rows named pa_info, dense [rows, barcodes] integer counts"""
     i, j = np.nonzero(dense)                      # row-major: rows ascending, columns ascending within a row
@@ -68,9 +52,8 @@ def _barcodes(bc_csv):
 def _expected_from_dense(mat_body, bc_csv):
     """the three texts and the integer matrix that a dense body (rows '"pa_info","0.0","2",...') stands for"""
     cbs = _barcodes(bc_csv)
-    rows = list(csv.reader(io.StringIO(mat_body)))
-    dense = np.array([[int(float(v)) for v in r[1:]] for r in rows], dtype=np.int64).reshape(len(rows), len(cbs))
-    return _texts([r[0] for r in rows], dense, cbs), dense
+    pa_info, dense = rc.dense_of_body(mat_body, len(cbs))
+    return _texts(pa_info, dense, cbs), dense
 
 
 def _check_mmread(root, res, dense):
@@ -100,16 +83,6 @@ def test_entry_point_format_argument(tmp_path):
         report._ex_pa_cnt_mat(str(tmp_path), "res.gene.pkl", fmt="csv")
 
 
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from scape_amd import _lib
-
-    def refuse(*a, **k):
-        raise AssertionError("the GPU was touched before the prerequisite checks")
-    monkeypatch.setattr(_lib, "default_context", refuse)
-    monkeypatch.setattr(_lib, "Context", refuse)
-
-
 def test_mtx_prerequisites(tmp_path, no_gpu):
     """the dense path's checks, messages and order, then the barcodes' own check, all before the GPU"""
     mtx = ["--format", "mtx"]
@@ -132,28 +105,6 @@ def test_mtx_prerequisites(tmp_path, no_gpu):
 
 
 # ---------------------------------------------------------------- GPU
-_F = None
-
-
-def _fixture():
-    global _F
-    if _F is None:
-        _F = load_npz("fixture_report.npz")
-    return _F
-
-
-def _case_params():
-    f = _fixture()
-    return [pytest.param(c, id=rc.case(f, c)["name"].replace("/", "-")) for c in rc.case_ids(f)]
-
-
-def _write_case(f, cs, root):
-    from scape.apa_core import Parameters
-    bc = rc.text(f, cs["barcode"])
-    rc.write_dir(str(root), cs["res"], cs["records"], bc, {}, Parameters)
-    return bc
-
-
 def _shrink(monkeypatch, block=1 << 12):
     """batches, render blocks and gzip members small enough that a case takes several of each"""
     from scape_amd import report
@@ -163,13 +114,12 @@ def _shrink(monkeypatch, block=1 << 12):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("c", _case_params())
+@pytest.mark.parametrize("c", rc.case_params())
 def test_mtx_case_vs_reference_dense(c, tmp_path, monkeypatch):
-    f = _fixture()
-    cs = rc.case(f, c)
+    cs = rc.fixture_case(c)
     if cs["name"].startswith("fuzz"):
         _shrink(monkeypatch)
-    bc = _write_case(f, cs, tmp_path)
+    bc, _paths = rc.write_case(cs, tmp_path, {})
     r = _run(_mtx_args(tmp_path, cs["res"]))
     assert r.exit_code == 0, (cs["name"], r.output, repr(r.exception))
     lines = r.output.splitlines()
@@ -189,10 +139,8 @@ def test_mtx_batch_and_block_invariance(tmp_path, monkeypatch):
     """the largest golden case with the default sizes and with one-row blocks, tiny batches and gzip members: the
     decompressed files are identical (and the tiny run did split the work)"""
     from scape_amd import _lib
-    f = _fixture()
-    cases = [rc.case(f, c) for c in rc.case_ids(f)]
-    cs = max(cases, key=lambda x: x["mat_body"].count("\n"))      # the most matrix rows
-    _write_case(f, cs, tmp_path)
+    cs = max(rc.fixture_cases(), key=lambda x: x["mat_body"].count("\n"))      # the most matrix rows
+    rc.write_case(cs, tmp_path, {})
     assert _run(_mtx_args(tmp_path, cs["res"])).exit_code == 0
     big = _read_dir(tmp_path, cs["res"])
     lib = _lib.load_library()
@@ -210,61 +158,11 @@ def test_mtx_batch_and_block_invariance(tmp_path, monkeypatch):
     assert len(calls) == n_rows > 2 and set(calls) == {1}
 
 
-def _pa_info(gene_info_str, alpha, beta, label):
-    """pa_info of the reference (utils.py:494-512), restated for the synthetic records"""
-    chrom, gene, utr, st_en, strand = gene_info_str.split(":")
-    st, en = (int(x) for x in st_en.split("-"))
-    loc = alpha + st if strand == "+" else en - alpha + 1
-    return f"{chrom}:{loc}:{beta}:{strand}:{label + 1}:{gene}:{utr}"
-
-
-def _wide_stream(seed=5):
-    """3,100 barcodes (scrambled ids with gaps, one id on two rows), records with K > 63, counts in the hundreds,
-    reads over every column, and records whose reads are all in the uniform component (label >= K)"""
-    rng = np.random.default_rng(seed)
-    n_cols = 3100
-    ids = rng.permutation(np.arange(7, 7 + 3 * n_cols, 3)).astype(np.int64)
-    ids[40] = ids[2000]                           # a repeated id keeps its last row: column 2001 gets its reads
-    bc = "CB,index\n" + "".join(f"W{j:05d}-1,{ids[j]}\n" for j in range(n_cols))
-    col_of = {int(i): j for j, i in enumerate(ids)}
-    used = np.array(sorted(set(ids.tolist())), dtype=np.int64)
-    # (K, reads, how many distinct cells, labels: "mixed" = 0..K with some >= K, "uniform" = all >= K)
-    specs = [(70, 25000, n_cols, "mixed"), (3, 30000, 40, "mixed"), (2, 500, 300, "uniform"),
-             (1, 16000, n_cols, "mixed"), (64, 4000, 900, "mixed"), (5, 0, 0, "mixed"), (1, 80, 20, "uniform")]
-    specs += [(int(rng.integers(1, 9)), int(rng.integers(50, 3000)), int(rng.integers(1, n_cols)), "mixed")
-              for _ in range(12)]
-    recs = []
-    for r, (K, n, n_cells, kind) in enumerate(specs):
-        cells = rng.choice(used, size=min(max(n_cells, 1), len(used)), replace=False)
-        cb = cells[rng.integers(0, len(cells), n)] if n else np.zeros(0, np.int64)
-        lab = rng.integers(K, K + 3, n) if kind == "uniform" else rng.integers(0, K + 1, n)
-        if K == 1 and n_cells == n_cols:
-            cb[:len(used)] = used                 # a read below K in every column that owns an id, the last one included
-            lab[:len(used)] = 0
-        alpha = np.sort(rng.choice(np.arange(50, 5000), K, replace=False)).astype(np.int64)
-        beta = rng.choice([5.0, 7.5, 30.0], K)
-        gene_info = f"{1 + r % 3}:WIDE{r:03d}:{1 + r % 2}:{10000 * r + 1}-{10000 * r + 9000}:{'+-'[r % 2]}"
-        recs.append(dict(gene_info_str=gene_info, K=K, alpha_arr=alpha, beta_arr=beta, label_arr=lab.astype(np.int64),
-                         cb_id_arr=cb.astype(np.int64)))
-    pa_info, blocks = [], []
-    for p in recs:
-        K = p["K"]
-        cnt = np.zeros((K, n_cols), dtype=np.int64)
-        m = p["label_arr"] < K
-        cols = np.array([col_of[int(i)] for i in p["cb_id_arr"][m]], dtype=np.int64)
-        np.add.at(cnt, (p["label_arr"][m], cols), 1)
-        for lb in np.nonzero(cnt.sum(axis=1) > 0)[0].tolist():
-            pa_info.append(_pa_info(p["gene_info_str"], int(p["alpha_arr"][lb]), float(p["beta_arr"][lb]), lb))
-            blocks.append(cnt[lb])
-    dense = np.array(blocks, dtype=np.int64).reshape(len(blocks), n_cols)
-    return recs, bc, pa_info, dense
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("small", [False, True], ids=["default_sizes", "small_sizes"])
 def test_mtx_wide_stream(small, tmp_path, monkeypatch):
     from scape.apa_core import Parameters
-    recs, bc, pa_info, dense = _wide_stream()
+    recs, bc, pa_info, dense = rc.wide_stream()
     assert any(p["K"] > 63 for p in recs) and dense.max() >= 100 and dense.shape[1] >= 3000
     assert (dense[:, -1] > 0).any() and not (dense[:, 40] > 0).any()
     if small:
@@ -327,14 +225,13 @@ def test_mtx_chain_both_formats(tmp_path):
     import merge_chain_dir as mc
     from scape_amd.apa_core import infer_all
     from scape_amd.junction_handler import _merge_pa
-    f = _fixture()
     mc.write_inputs(str(tmp_path))
     infer_all(str(tmp_path), gpus=1, rng_mode="per_utr", seed=mc.SEED, re_run_mode=True, **mc.KW)
     _merge_pa(str(tmp_path), True)
     _merge_pa(str(tmp_path), False)
     bc = rc.chain_barcode_csv()
     (tmp_path / "barcode_index.csv").write_text(bc)
-    byname = {rc.case(f, c)["name"]: rc.case(f, c) for c in rc.case_ids(f)}
+    byname = {cs["name"]: cs for cs in rc.fixture_cases()}
     for tag in ("gene", "utr"):
         res = f"res.{tag}.pkl"
         gz = tmp_path / f"res.{tag}.cnt.tsv.gz"

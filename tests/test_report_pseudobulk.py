@@ -16,21 +16,13 @@ import os
 
 import numpy as np
 import pytest
-from click.testing import CliRunner
 
-from conftest import load_npz
 import report_cases as rc
+from report_cases import (cluster_rows as _cluster_rows, column_ids as _column_ids, dense_of_body as _dense_of_body,
+                          first_clusters as _first_clusters, fixture_case as _case, fixture_cases as _cases, no_gpu,
+                          parts_left as _parts_left, run as _run)  # noqa: F401  (no_gpu is a fixture)
 
 KINDS = ("cnt", "pct", "samples")
-
-
-def _cli():
-    from scape.cli import cli
-    return cli
-
-
-def _run(args):
-    return CliRunner().invoke(_cli(), args)
 
 
 def _args(root, clu, res="res.gene.pkl", k=None, id1=None, id2=None):
@@ -59,10 +51,6 @@ def _read_out(root, clu, res, id1=None, id2=None):
     return out
 
 
-def _parts_left(root):
-    return glob.glob(os.path.join(str(root), "**", "*.part"), recursive=True)
-
-
 # ---------------------------------------------------------------- the definitions, restated
 def r_split_sizes(n, k):
     """chunk sizes of R's split(cells, sort(1:n %% k)), transcribed literally: build 1:n %% k, sort it, run-length it
@@ -82,20 +70,6 @@ def _csv_text(rows):
     out = io.StringIO()
     csv.writer(out, delimiter=",", quoting=csv.QUOTE_MINIMAL, lineterminator="\n").writerows(rows)
     return out.getvalue()
-
-
-def _column_ids(bc_csv):
-    rows = list(csv.reader(io.StringIO(bc_csv)))
-    ip = rows[0].index("index")
-    return [int(r[ip]) for r in rows[1:]]
-
-
-def _cluster_rows(clu_csv):
-    """(id, cluster text) of every row: index column by name, the first other column as written"""
-    rows = list(csv.reader(io.StringIO(clu_csv)))
-    ip = rows[0].index("index")
-    other = [j for j in range(len(rows[0])) if j != ip][0]
-    return [(int(r[ip]), r[other]) for r in rows[1:]]
 
 
 def expected(pa_info, dense, bc_csv, clu_csv, k=6, id1=None, id2=None):
@@ -133,20 +107,6 @@ def expected(pa_info, dense, bc_csv, clu_csv, k=6, id1=None, id2=None):
     return {"cnt": _csv_text(cnt), "pct": _csv_text(pct), "samples": _csv_text(smp)}
 
 
-def _dense_of_body(mat_body, n_cols):
-    rows = list(csv.reader(io.StringIO(mat_body)))
-    dense = np.array([[int(float(v)) for v in r[1:]] for r in rows], dtype=np.int64).reshape(len(rows), n_cols)
-    return [r[0] for r in rows], dense
-
-
-def _first_clusters(clu_csv):
-    order = []
-    for _i, name in _cluster_rows(clu_csv):
-        if name != "" and name not in order:
-            order.append(name)
-    return order
-
-
 # ---------------------------------------------------------------- CPU
 def test_help_lists_command_and_options():
     r = _run(["--help"])
@@ -162,16 +122,6 @@ def test_utils_import_path():
     import scape.utils as su
     from scape_amd import report
     assert su.ex_pa_pseudobulk is report.ex_pa_pseudobulk
-
-
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from scape_amd import _lib
-
-    def refuse(*a, **k):
-        raise AssertionError("the GPU was touched before the prerequisite checks")
-    monkeypatch.setattr(_lib, "default_context", refuse)
-    monkeypatch.setattr(_lib, "Context", refuse)
 
 
 def test_prerequisites_and_argument_errors(tmp_path, no_gpu):
@@ -254,47 +204,13 @@ def test_grouping_of_hand_written_files(tmp_path):
 
 
 # ---------------------------------------------------------------- GPU
-_F = None
-
-
-def _fixture():
-    global _F
-    if _F is None:
-        _F = load_npz("fixture_report.npz")
-    return _F
-
-
-_CASES = {}
-
-
-def _case(c):
-    if c not in _CASES:
-        _CASES[c] = rc.case(_fixture(), c)
-    return _CASES[c]
-
-
-def _cases():
-    return [_case(c) for c in rc.case_ids(_fixture())]
-
-
 def _golden_params():
     out = []
-    for c in rc.case_ids(_fixture()):
+    for c in rc.case_ids(rc.fixture()):
         cs = _case(c)
         for j, fn in enumerate(cs["clu_files"]):
             out.append(pytest.param(c, j, id=f"{cs['name'].replace('/', '-')}-{fn}"))
     return out
-
-
-def _case_params():
-    return [pytest.param(c, id=_case(c)["name"].replace("/", "-")) for c in rc.case_ids(_fixture())]
-
-
-def _write_case(cs, root, cluster_texts):
-    from scape.apa_core import Parameters
-    bc = rc.text(_fixture(), cs["barcode"])
-    paths = rc.write_dir(str(root), cs["res"], cs["records"], bc, cluster_texts, Parameters)
-    return bc, paths
 
 
 def _check(root, clu_path, clu_text, res, pa, dense, bc, k=None, id1=None, id2=None, what=""):
@@ -315,10 +231,9 @@ def _check(root, clu_path, clu_text, res, pa, dense, bc, k=None, id1=None, id2=N
 @pytest.mark.parametrize("c,j", _golden_params())
 def test_golden_case_and_cluster_file(c, j, tmp_path):
     """every golden case with each of its cluster files, num_splits default, 1 and 4"""
-    f = _fixture()
     cs = _case(c)
-    texts = {fn: rc.text(f, k) for fn, k in zip(cs["clu_files"], cs["clusters"])}
-    bc, paths = _write_case(cs, tmp_path, texts)
+    texts = rc.cluster_texts(cs)
+    bc, paths = rc.write_case(cs, tmp_path)
     fn = cs["clu_files"][j]
     pa, dense = _dense_of_body(cs["mat_body"], len(_column_ids(bc)))
     for k in (None, 1, 4):
@@ -346,13 +261,12 @@ def _own_cluster_files(col_ids):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("c", _case_params())
+@pytest.mark.parametrize("c", rc.case_params())
 def test_golden_case_with_written_cluster_files(c, tmp_path):
     cs = _case(c)
-    bc = rc.text(_fixture(), cs["barcode"])
-    col_ids = _column_ids(bc)
+    col_ids = _column_ids(rc.text(rc.fixture(), cs["barcode"]))
     texts = _own_cluster_files(col_ids)
-    _bc, paths = _write_case(cs, tmp_path, texts)
+    bc, paths = rc.write_case(cs, tmp_path, texts)
     pa, dense = _dense_of_body(cs["mat_body"], len(col_ids))
     for (fn, text), path in zip(texts.items(), paths):
         got = _check(tmp_path, path, text, cs["res"], pa, dense, bc, what=f"{cs['name']}/{fn}")
@@ -367,7 +281,7 @@ def test_golden_case_with_written_cluster_files(c, tmp_path):
 
 def _ident_cases():
     names = ["SCZ-nowa-scape/gene", "fuzz0", "fuzz4", "fuzz21"]
-    byname = {cs["name"]: c for c, cs in zip(rc.case_ids(_fixture()), _cases())}
+    byname = {cs["name"]: c for c, cs in zip(rc.case_ids(rc.fixture()), _cases())}
     return [pytest.param(byname[n], id=n.replace("/", "-")) for n in names]
 
 
@@ -375,10 +289,9 @@ def _ident_cases():
 @pytest.mark.parametrize("c", _ident_cases())
 def test_idents(c, tmp_path):
     """--idents_1 A --idents_2 B, and --idents_1 A alone (Population2 = every other cluster)"""
-    f = _fixture()
     cs = _case(c)
-    texts = {fn: rc.text(f, k) for fn, k in zip(cs["clu_files"], cs["clusters"])}
-    bc, paths = _write_case(cs, tmp_path, texts)
+    texts = rc.cluster_texts(cs)
+    bc, paths = rc.write_case(cs, tmp_path)
     pa, dense = _dense_of_body(cs["mat_body"], len(_column_ids(bc)))
     fn, path = cs["clu_files"][-1], paths[-1]
     order = _first_clusters(texts[fn])
@@ -395,10 +308,9 @@ def test_batch_invariance(tmp_path, monkeypatch):
     """the golden case with the most rows: a batch budget of 16 KiB gives the same bytes in several device calls"""
     from scape_amd import _lib, report
     cs = max(_cases(), key=lambda x: x["mat_body"].count("\n"))
-    bc = rc.text(_fixture(), cs["barcode"])
-    col_ids = _column_ids(bc)
+    col_ids = _column_ids(rc.text(rc.fixture(), cs["barcode"]))
     texts = _own_cluster_files(col_ids)
-    _bc, paths = _write_case(cs, tmp_path, texts)
+    bc, paths = rc.write_case(cs, tmp_path, texts)
     pa, dense = _dense_of_body(cs["mat_body"], len(col_ids))
     path, text = paths[0], texts["own_partial.csv"]
     big = _check(tmp_path, path, text, cs["res"], pa, dense, bc, what="default budget")
@@ -419,11 +331,10 @@ def test_batch_invariance(tmp_path, monkeypatch):
 @pytest.mark.parametrize("small", [False, True], ids=["default_sizes", "small_batches"])
 def test_wide_stream_vs_add_at(small, tmp_path, monkeypatch):
     """3,100 barcodes with scrambled ids and a repeated id, K up to 70, counts in the hundreds: expected sums from the
-    np.add.at restatement of the counts (tests/test_report_mtx.py)"""
+    np.add.at restatement of the counts (report_cases.wide_stream)"""
     from scape.apa_core import Parameters
     from scape_amd import report
-    from test_report_mtx import _wide_stream
-    recs, bc, pa, dense = _wide_stream()
+    recs, bc, pa, dense = rc.wide_stream()
     col_ids = _column_ids(bc)
     if small:
         monkeypatch.setattr(report, "MAX_BATCH_BYTES", 1 << 20)
@@ -441,7 +352,7 @@ def test_group_sums_entry_point():
     """the C entry point on its own: segments of 0, 1, 63, 64, 65 and 4,000 columns, columns before the first and
     behind the last segment, 70 rows of one record; sums and nonzero counts against numpy"""
     from scape_amd import _lib
-    from scape_amd._lib import P_i8, P_i32, P_i64, check, ptr
+    from scape_amd._lib import P_i32, P_i64, check, ptr
     rng = np.random.default_rng(3)
     lens = [0, 1, 63, 0, 64, 65, 4000, 2, 0, 129, 1, 1, 1, 300]
     lead, n_cols = 3, 3 + sum(lens) + 11
@@ -450,16 +361,11 @@ def test_group_sums_entry_point():
     lab = rng.integers(0, K + 1, n).astype(np.int64)
     cb = (rng.integers(0, n_cols, n) ** 2 // n_cols).astype(np.int64)           # skewed: many empty columns
     off, Ks = np.array([0, n], dtype=np.int64), np.array([K], dtype=np.int32)
-    table = np.arange(n_cols, dtype=np.int32)
     want = np.zeros((K, n_cols), dtype=np.int64)
     np.add.at(want, (lab[lab < K], cb[lab < K]), 1)
     ctx = _lib.default_context(None)
     try:
-        row_tot, complete, bad = np.zeros(K, np.int64), np.zeros(1, np.int8), np.zeros(2, np.int64)
-        check(ctx.lib.scape_hip_report_counts(ctx.h, 1, ptr(off, P_i64), ptr(Ks, P_i32), ptr(lab, P_i64),
-                                              ptr(cb, P_i64), 0, n_cols, ptr(table, P_i32), n_cols, ptr(row_tot, P_i64),
-                                              ptr(complete, P_i8), ptr(bad, P_i64)), "counts")
-        assert np.array_equal(row_tot, want.sum(axis=1))
+        assert np.array_equal(rc.device_counts(ctx, Ks, off, lab, cb, n_cols), want.sum(axis=1))
         rows = np.arange(K, dtype=np.int64)[::-1].copy()
         n_seg = len(lens)
         sums, nz = np.full((K, n_seg), -1, np.int32), np.full((K, n_seg), -1, np.int32)
