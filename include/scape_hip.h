@@ -211,6 +211,24 @@ int scape_hip_report_group_sums(scape_hip_ctx *ctx, int32_t n_seg, const int32_t
    earlier call and stay until scape_hip_report_free, across scape_hip_report_counts calls.  n1, n2 >= 1, n < 2^24. */
 int scape_hip_report_perm_masks(scape_hip_ctx *ctx, int32_t n1, int32_t n2, int64_t p_first, int32_t p_count,
                                 uint64_t seed);
+/* Labellings permuted within strata only (blocked permutations: cell type, donor, batch, ...).  Positions: population 1's
+   columns first, then population 2's, as above; within each population the columns are ordered by stratum.  Stratum s
+   of n_strata has m1[s] cells in population 1 and m2[s] in population 2 and so owns the position ranges
+     [o1[s], o1[s] + m1[s])  and  [n1 + o2[s], n1 + o2[s] + m2[s]),   o1 / o2 = the exclusive prefix sums of m1 / m2,
+   n1 = sum m1, n2 = sum m2, n = n1 + n2 < 2^24.  Permutation 0 is the observed labelling (positions < n1).  Permutation
+   p >= 1 gives population 1, in every stratum separately, the m1[s] positions of that stratum with the smallest
+   key(p, j) - the key above, unchanged, with j the global position, so keys are distinct.  Exactly m1[s] bits are set
+   per stratum, also when m1[s] = 0 or m2[s] = 0: such a stratum's cells never move but are still counted.  With one
+   stratum the bits are those of scape_hip_report_perm_masks, bit for bit.
+   The call fills the same buffer in the same layout and takes the place of a scape_hip_report_perm_masks call:
+   scape_hip_report_perm_test and scape_hip_report_perm_len run behind either.  It also holds p_count * n_strata * 8
+   bytes of scratch on the device.  Checked before anything is queued: n_strata >= 1, every m1[s], m2[s] >= 0 and
+   m1[s] + m2[s] >= 1, n1, n2 >= 1, n < 2^24, p_first, p_count >= 1. */
+int scape_hip_report_perm_masks_strata(scape_hip_ctx *ctx, int32_t n_strata, const int32_t *m1, const int32_t *m2,
+                                       int64_t p_first, int32_t p_count, uint64_t seed);
+/* The ceil(n / 64) membership words of permutation p_first + p (0 <= p < p_count) of the last masks call, whichever of
+   the two entry points made it: bit j % 64 of words_out[j / 64] is set when position j is in population 1. */
+int scape_hip_report_perm_bits_get(scape_hip_ctx *ctx, int32_t p, uint64_t *words_out);
 /* The test of n_rec records of the last counts call against the permutations of the last perm_masks call.  Record r owns
    the kept count rows rows[rec_row_off[r] .. rec_row_off[r+1]) (rec_row_off[0] = 0, non-decreasing).  Per row i:
    t_out[i] = its sum over the tested columns, a0_out[i] = its sum over population 1 as observed.  With T, A, B the

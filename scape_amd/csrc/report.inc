@@ -28,6 +28,10 @@
 //                   64-bit key, one workgroup per permutation), the nonzeros (position, count) of the kept count rows,
 //                   and the permutation test itself (one lane per permutation, exceedance counts per site and record);
 //                   section "permutation test" at the end of this file
+//   k_rep_perm_mask_strata
+//                   the same membership bits for labellings permuted within strata only (--strata_file): per
+//                   permutation and stratum the m1[s]-th smallest key of the stratum's cells, by one wave for a stratum
+//                   of up to 256 cells and by the workgroup's radix select for a larger one, one launch for all of them
 //   k_rep_perm_len  diff_pa_len: the same walk for the record's mean pA position in the two populations (one lane per
 //                   permutation, two f64 sums and two integer sums per lane, exceedance counts per record)
 // Cluster names, their order and the floating-point finish of exp_pa_len stay on the host (scape_amd/report.py).
@@ -53,6 +57,9 @@ struct ReportState {
     DevBuf m_bits, p_rows, p_roff, p_nnz, p_noff, p_nz, p_t, p_a0, p_recs, p_site, p_gene, p_stat0;
     DevBuf l_w, l_tol;                 // diff_pa_len: row weights and record tolerances of scape_hip_report_perm_len
     int32_t m_n1 = 0, m_n2 = 0, m_count = 0;
+    // stratified masks: (a1, m1, a2, m2) per stratum, the strata in work order, the stratum of every position and the
+    // exclusive key bound per (permutation, stratum)
+    DevBuf m_desc, m_order, m_strat, m_bound;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
@@ -78,7 +85,7 @@ static void report_release(scape_hip_ctx *c) {
                      &s->s_roff[1], &s->s_out[0], &s->s_out[1], &s->s_nnz[0], &s->s_nnz[1], &s->s_noff[0],
                      &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz, &s->m_bits, &s->p_rows,
                      &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
-                     &s->p_stat0, &s->l_w, &s->l_tol};
+                     &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;
@@ -846,6 +853,137 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_mask(int32_t n1, int32
     }
 }
 
+// ---- labellings permuted within strata ------------------------------------------------------------------------------
+// Stratum s owns the positions [a1, a1 + m1) of population 1 and [a2, a2 + m2) of population 2 (desc[s] = a1, m1, a2,
+// m2; a2 already counts from n1).  Permutation p >= 1 gives population 1 the m1 cells of the stratum with the smallest
+// key(p, j), j the global position, so with one stratum the bits are k_rep_perm_mask's.  The kernel stores, per
+// stratum, the EXCLUSIVE bound of the members' keys: 0 when m1 = 0, 2^64 - 1 when m2 = 0 (j <= 2^24 - 2, so every key
+// lies below it), otherwise the m1-th smallest key + 1; the last pass is then k_rep_perm_mask's, with
+// key < bound[stratum of j].
+#define REP_STRATA_WAVE_MAX 256   // a wave ranks a stratum of up to this many cells in registers (4 keys per lane)
+
+__device__ __forceinline__ int rep_strata_pos(int i, int4 d) { return i < d.y ? d.x + i : d.z + (i - d.y); }
+
+__device__ __forceinline__ unsigned long long rep_readlane64(unsigned long long v, int src) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// one wave, one stratum of m = d.y + d.w <= 64 KEYS cells, 0 < d.y < m: lane l holds the keys of cells l, 64 + l, ...;
+// every key is broadcast in turn and each lane counts the keys below its own.  The cell with d.y - 1 keys below it has
+// the d.y-th smallest key.  No LDS, no barrier.
+template <int KEYS>
+__device__ __forceinline__ void rep_strata_wave(unsigned long long base, int4 d, int lane,
+                                                unsigned long long *__restrict__ bound_s) {
+    const int m = d.y + d.w;
+    unsigned long long k[KEYS];
+    int below[KEYS];
+#pragma unroll
+    for (int c = 0; c < KEYS; ++c) {
+        const int i = c * 64 + lane;
+        k[c] = i < m ? rep_perm_key(base, rep_strata_pos(i, d)) : ~0ull;   // above every key of a cell
+        below[c] = 0;
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < KEYS; ++c2) {
+        const int cnt = min(64, m - c2 * 64);
+        for (int src = 0; src < cnt; ++src) {
+            const unsigned long long other = rep_readlane64(k[c2], src);
+#pragma unroll
+            for (int c = 0; c < KEYS; ++c) below[c] += other < k[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KEYS; ++c)
+        if (c * 64 + lane < m && below[c] == d.y - 1) *bound_s = k[c] + 1;
+}
+
+// one workgroup per permutation p_first + blockIdx.x.  order[0 .. n_wave) are the strata a wave settles alone (those
+// without a cell of one population, whatever their size, and those of up to REP_STRATA_WAVE_MAX cells), taken by the
+// four waves in turn; order[n_wave .. n_strata) are the larger ones, which the whole workgroup takes one after the other
+// with k_rep_perm_mask's radix select over the stratum's two ranges.  The select stops at the first byte after which one
+// candidate is left (a stratum of m cells needs about log256(m) + 1 of the 8 passes), and one more pass over the
+// stratum finds the key that carries the selected prefix.  bound = bound of this launch [permutation][stratum].
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_mask_strata(
+    int32_t n, int32_t n_strata, int32_t n_wave, const int4 *__restrict__ desc, const int32_t *__restrict__ order,
+    const int32_t *__restrict__ strat_of, unsigned long long p_first, int32_t p_count, unsigned long long seed,
+    unsigned long long *__restrict__ bound, unsigned long long *__restrict__ bits) {
+    __shared__ __align__(16) int hist[256];
+    __shared__ unsigned long long sel[2];   // prefix of the key looked for, and its rank among the keys with that prefix
+    __shared__ int sel_cnt;                 // keys that share the prefix
+    const unsigned long long base = rep_mix(seed + REP_PERM_G * (p_first + blockIdx.x));
+    unsigned long long *__restrict__ bound_p = bound + (int64_t)blockIdx.x * n_strata;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (int i = wave; i < n_wave; i += REP_WAVES) {
+        const int s = order[i];
+        const int4 d = desc[s];
+        if (d.y == 0 || d.w == 0) {
+            if (lane == 0) bound_p[s] = d.y == 0 ? 0ull : ~0ull;
+        } else if (d.y + d.w <= 64) {
+            rep_strata_wave<1>(base, d, lane, bound_p + s);
+        } else {
+            rep_strata_wave<REP_STRATA_WAVE_MAX / 64>(base, d, lane, bound_p + s);
+        }
+    }
+    for (int i = n_wave; i < n_strata; ++i) {
+        const int s = order[i];
+        const int4 d = desc[s];
+        const int m = d.y + d.w;
+        unsigned long long prefix = 0;
+        int rank = d.y - 1, cnt = m, pass = 0;
+        for (; pass < 8 && cnt > 1; ++pass) {
+            const int shift = 56 - 8 * pass;
+            hist[threadIdx.x] = 0;
+            __syncthreads();
+            for (int c = threadIdx.x; c < m; c += REP_THREADS) {
+                const unsigned long long k = rep_perm_key(base, rep_strata_pos(c, d));
+                if (pass == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
+            }
+            __syncthreads();
+            if (threadIdx.x < 64) {          // wave 0: the bin that holds the candidate of that rank
+                const int4 h = reinterpret_cast<const int4 *>(hist)[lane];
+                const int sum = h.x + h.y + h.z + h.w;
+                int incl = sum;
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int y = __shfl_up(incl, o, 64);
+                    if (lane >= o) incl += y;
+                }
+                if (incl - sum <= rank && rank < incl) {     // one lane: the bins are disjoint and hold cnt > rank keys
+                    int r = rank - (incl - sum), b = 4 * lane, in_bin = h.x;
+                    if (r >= h.x) {
+                        r -= h.x, ++b, in_bin = h.y;
+                        if (r >= h.y) {
+                            r -= h.y, ++b, in_bin = h.z;
+                            if (r >= h.z) r -= h.z, ++b, in_bin = h.w;
+                        }
+                    }
+                    sel[0] = prefix | ((unsigned long long)b << shift);
+                    sel[1] = (unsigned long long)r;
+                    sel_cnt = in_bin;
+                }
+            }
+            __syncthreads();
+            prefix = sel[0];
+            rank = (int)sel[1];
+            cnt = sel_cnt;
+        }
+        const int known = 64 - 8 * pass;     // pass >= 1: the key's bits above `known` are fixed, and one key has them
+        for (int c = threadIdx.x; c < m; c += REP_THREADS) {
+            const unsigned long long k = rep_perm_key(base, rep_strata_pos(c, d));
+            if ((k >> known) == (prefix >> known)) bound_p[s] = k + 1;
+        }
+    }
+    __syncthreads();                         // this permutation's bounds are stored
+    const int n_words = (n + 63) >> 6;
+    for (int w = wave; w < n_words; w += REP_WAVES) {
+        const int j = w * 64 + lane;
+        const unsigned long long m = __ballot(j < n && rep_perm_key(base, j) < bound_p[strat_of[j]]);
+        if (lane == 0) bits[(int64_t)w * p_count + blockIdx.x] = m;
+    }
+}
+
 // one workgroup per kept row i (count row rows[i]): nonzeros among the tested positions, their sum t and the sum over
 // positions < n1 (population 1 as observed)
 __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_rowstat(const int64_t *__restrict__ rows, int32_t n_cols,
@@ -1126,6 +1264,71 @@ int scape_hip_report_perm_masks(scape_hip_ctx *c, int32_t n1, int32_t n2, int64_
     s->m_n1 = n1;
     s->m_n2 = n2;
     s->m_count = p_count;
+    return 0;
+}
+
+int scape_hip_report_perm_masks_strata(scape_hip_ctx *c, int32_t n_strata, const int32_t *m1, const int32_t *m2,
+                                       int64_t p_first, int32_t p_count, uint64_t seed) {
+    CTX_ENTER(c);
+    if (n_strata < 1 || !m1 || !m2) return fail("at least one stratum, with m1 and m2, is needed");
+    int64_t n1 = 0, n2 = 0;
+    for (int32_t s = 0; s < n_strata; ++s) {
+        if (m1[s] < 0 || m2[s] < 0) return fail("stratum " + std::to_string(s) + ": a negative number of cells");
+        if ((int64_t)m1[s] + m2[s] < 1) return fail("stratum " + std::to_string(s) + ": no cell");
+        n1 += m1[s];
+        n2 += m2[s];
+    }
+    if (n1 < 1 || n2 < 1) return fail("both populations need at least one cell");
+    if (n1 + n2 >= REP_PERM_MAX_N) return fail("n1 + n2 must be below 2^24 (a key keeps the position in 24 bits)");
+    if (p_first < 1 || p_count < 1) return fail("p_first and p_count must be at least 1 (permutation 0 is the observed labelling)");
+    ReportState *s = report_state(c);
+    s->m_count = 0;
+    const int32_t n = (int32_t)(n1 + n2);
+    // the position ranges of every stratum, the stratum of every position, and the strata in work order
+    std::vector<int32_t> desc((size_t)n_strata * 4), order, large, strat_of((size_t)n);
+    order.reserve(n_strata);
+    int32_t a1 = 0, a2 = (int32_t)n1;
+    for (int32_t k = 0; k < n_strata; ++k) {
+        int32_t *d = &desc[(size_t)k * 4];
+        d[0] = a1, d[1] = m1[k], d[2] = a2, d[3] = m2[k];
+        std::fill(strat_of.begin() + a1, strat_of.begin() + a1 + m1[k], k);
+        std::fill(strat_of.begin() + a2, strat_of.begin() + a2 + m2[k], k);
+        a1 += m1[k];
+        a2 += m2[k];
+        const bool alone = m1[k] == 0 || m2[k] == 0 || (int64_t)m1[k] + m2[k] <= REP_STRATA_WAVE_MAX;
+        (alone ? order : large).push_back(k);
+    }
+    const int32_t n_wave = (int32_t)order.size();
+    order.insert(order.end(), large.begin(), large.end());
+    if (s->m_bits.ensure((int64_t)p_count * ((n + 63) / 64) * 8) || s->m_desc.ensure((int64_t)n_strata * 16) ||
+        s->m_order.ensure((int64_t)n_strata * 4) || s->m_strat.ensure((int64_t)n * 4) ||
+        s->m_bound.ensure((int64_t)p_count * n_strata * 8))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->m_desc.p, desc.data(), (int64_t)n_strata * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->m_order.p, order.data(), (int64_t)n_strata * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->m_strat.p, strat_of.data(), (int64_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_perm_mask_strata, dim3(p_count), dim3(REP_THREADS), 0, c->stream, n, n_strata, n_wave,
+                       s->m_desc.as<int4>(), s->m_order.as<int32_t>(), s->m_strat.as<int32_t>(),
+                       (unsigned long long)p_first, p_count, (unsigned long long)seed,
+                       s->m_bound.as<unsigned long long>(), s->m_bits.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    s->m_n1 = (int32_t)n1;
+    s->m_n2 = (int32_t)n2;
+    s->m_count = p_count;
+    return 0;
+}
+
+int scape_hip_report_perm_bits_get(scape_hip_ctx *c, int32_t p, uint64_t *words_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->m_count) return fail("scape_hip_report_perm_masks has not been called");
+    if (!words_out) return fail("bad argument");
+    if (p < 0 || p >= s->m_count) return fail("p must name a permutation of the last masks call");
+    const int32_t n_words = (s->m_n1 + s->m_n2 + 63) / 64;
+    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->m_bits.as<unsigned long long>() + p, (size_t)s->m_count * 8, 8, n_words,
+                            hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -29,6 +29,9 @@ device's rendering of one text block with the gzip of the previous one.
   label permutations as ``diff_pa`` (they share the code), tested on the difference of the mean pA position (section
   diff_pa_len below).  The device walks the same membership bits with one weighted sum per population; the host adds
   the exact means and the reference's ``exp_pa_len`` of both populations.
+  Both take ``--strata_file`` (cell type, donor, batch, ... per cell): the labels are then permuted within each
+  stratum only, which keeps a difference between strata of unequal composition out of the p-values.  Only the
+  membership bits change (one more kernel, ``k_rep_perm_mask_strata``); the statistics stay pooled over the strata.
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -40,6 +43,7 @@ from __future__ import annotations
 import csv
 import ctypes
 import io
+import math
 import os
 import shutil
 import tempfile
@@ -635,6 +639,10 @@ def _ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str
 # N_i = a_i T - t_i A:  S = sum_i N_i^2 / (t_i A B) (Pearson's chi-square of the rows x 2 table) tests the record,
 # d_i = N_i / (A B) = a_i / A - b_i / B (two-sided) the site.  Rows with t_i = 0 are dropped; a record is tested when two
 # rows or more remain and both populations have reads.  p = (1 + #{p: stat(p) >= stat(0)}) / (1 + n_perm).
+# With --strata_file the positions of each population are ordered by stratum (first appearance among the rows of the
+# strata file; columns ascending within a stratum), tested cells without a stratum are left out of both populations, and
+# permutation p gives population 1, in every stratum s separately, the m1[s] positions of that stratum with the smallest
+# key(p, j): same key, same seed, and with one stratum the same labellings.  S, d_i and delta are unchanged (pooled).
 DIFF_PA_HEADER = ["gene", "pa_info", "pct.1", "pct.2", "versus", "usage.1", "usage.2", "delta_usage", "n_ge", "p_val",
                   "p_val_adj", "gene_stat", "gene_n_ge", "gene_p_val", "gene_p_val_adj", "n_perm"]
 MAX_PERM_CELLS = 1 << 24  # a key keeps the position in its low 24 bits
@@ -653,9 +661,16 @@ def _bh(p):
     return out
 
 
-def _perm_masks(ctx, n1, n2, p_first, p_count, seed, times):
+def _perm_masks(ctx, su, p_first, p_count, seed, times):
+    """the membership bits of p_count permutations from p_first on: relabelled within su.strata = (m1, m2) when given,
+    freely otherwise"""
     t0 = timer()
-    check(ctx.lib.scape_hip_report_perm_masks(ctx.h, n1, n2, p_first, p_count, seed), "report_perm_masks")
+    if su.strata is not None:
+        m1, m2 = su.strata
+        check(ctx.lib.scape_hip_report_perm_masks_strata(ctx.h, len(m1), ptr(m1, P_i32), ptr(m2, P_i32), p_first,
+                                                         p_count, seed), "report_perm_masks_strata")
+    else:
+        check(ctx.lib.scape_hip_report_perm_masks(ctx.h, su.n1, su.n2, p_first, p_count, seed), "report_perm_masks")
     times["render"] += timer() - t0
 
 
@@ -697,21 +712,20 @@ def _perm_rows(ctx, bat, seg_off, times, each_kept=None):
     return which, off, cand[keep], nz[keep], sums[keep], rowbase
 
 
-def _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, test):
+def _perm_chunks(ctx, su, n_perm, chunk, seed, times, test):
     """test() once per chunk of permutations, behind that chunk's masks"""
-    n1, n2 = int(seg_off[1]), int(seg_off[2] - seg_off[1])
     for p_first in range(1, n_perm + 1, chunk):
         if chunk < n_perm:       # otherwise the one set of masks was built before the first batch
-            _perm_masks(ctx, n1, n2, p_first, min(chunk, n_perm + 1 - p_first), seed, times)
+            _perm_masks(ctx, su, p_first, min(chunk, n_perm + 1 - p_first), seed, times)
         t0 = timer()
         test()
         times["render"] += timer() - t0
 
 
-def _diff_pa_batch(ctx, bat, seg_off, n_perm, chunk, seed, lines, genes, times):
+def _diff_pa_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times):
     """one counted batch: the kept rows of its tested records go through the permutation test; appends the per-line
     integers to `lines` and the per-record ones to `genes`"""
-    sel = _perm_rows(ctx, bat, seg_off, times)
+    sel = _perm_rows(ctx, bat, su.seg_off, times)
     if sel is None:
         return
     recs = bat.recs
@@ -719,7 +733,7 @@ def _diff_pa_batch(ctx, bat, seg_off, n_perm, chunk, seed, lines, genes, times):
     t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
     site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
     stat0 = np.zeros(len(which), np.float64)
-    _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, lambda: check(
+    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
         ctx.lib.scape_hip_report_perm_test(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(t, P_i64),
                                            ptr(a0, P_i64), ptr(site_ge, P_i64), ptr(stat0), ptr(gene_ge, P_i64)),
         "report_perm_test"))
@@ -739,10 +753,36 @@ def _diff_pa_batch(ctx, bat, seg_off, n_perm, chunk, seed, lines, genes, times):
     times["finish"] += timer() - t0
 
 
-def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, command):
+def _strata(col_ids, pops, strata_file):
+    """the two populations restricted to the cells that have a stratum, each ordered by stratum (strata in order of
+    first appearance among the rows of the strata file, columns ascending within a stratum), and per stratum with a
+    tested cell its number of cells in population 1 and in population 2: (populations, m1, m2, cells left out)"""
+    col_stratum, order = _column_clusters(col_ids.astype(np.int64), *_read_clusters(strata_file))
+    code = {name: k for k, name in enumerate(order)}
+    col_code = np.array([code[c] if c is not None else -1 for c in col_stratum], dtype=np.int64)
+    out, counts, left_out = [], [], 0
+    for name, cols in pops:
+        c = col_code[cols]
+        left_out += int((c < 0).sum())
+        cols, c = cols[c >= 0], c[c >= 0]
+        out.append((name, cols[np.argsort(c, kind="stable")]))
+        counts.append(np.bincount(c, minlength=len(order)))
+    used = counts[0] + counts[1] > 0
+    return out, counts[0][used].astype(np.int32), counts[1][used].astype(np.int32), left_out
+
+
+def _log10_labellings(m1, m2):
+    """log10 of the number of distinct labellings: sum over the strata of log10 C(m1 + m2, m1)"""
+    return sum(math.lgamma(a + b + 1) - math.lgamma(a + 1) - math.lgamma(b + 1)
+               for a, b in zip(m1.tolist(), m2.tolist())) / math.log(10)
+
+
+def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, command,
+                strata_file=None):
     """what diff_pa and diff_pa_len do before the device is opened: the argument and prerequisite checks, the two
-    populations, the id -> column table that puts population 1's columns first and population 2's behind them, and the
-    output path <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.<command>.csv"""
+    populations, the id -> column table that puts population 1's columns first and population 2's behind them (with a
+    strata file: each ordered by stratum, cells without a stratum left out), and the output path
+    <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>[.by_<strata file stem>].<command>.csv"""
     if idents_1 is None:
         raise ValueError("idents_1 is required")
     if idents_1 == idents_2:
@@ -759,14 +799,38 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
         empty = "Population2" if pops and pops[0][0] == "Population1" else "Population1"
         raise ValueError(f"{empty} ({idents_1 if empty == 'Population1' else idents_2 or 'the rest'}) has no cell in "
                          "barcode_index.csv")
+    strata, left_out, by = None, 0, ""
+    if strata_file is not None:
+        if not os.path.exists(strata_file):
+            raise ValueError(f"Given strata_file {strata_file} does not exist")
+        pops, m1, m2, left_out = _strata(inp.col_ids, pops, strata_file)
+        for (name, cols), ident in zip(pops, (idents_1, idents_2 or "the rest")):
+            if not len(cols):
+                raise ValueError(f"{name} ({ident}) has no cell with a stratum in {strata_file}")
+        if not np.any((m1 > 0) & (m2 > 0)):
+            raise ValueError(f"no stratum of {strata_file} holds cells of both populations: the observed labelling is "
+                             "the only one")
+        strata = (m1, m2)
+        by = ".by_" + os.path.splitext(os.path.basename(strata_file))[0]
+        if os.sep in by:
+            raise ValueError(f"a strata file name with {os.sep!r} cannot be part of a file name")
     _table, slot, seg_off, _seg_pop = _samples(pops, 1, n_cols)      # population 1's columns first, then population 2's
     n1, n2 = len(pops[0][1]), len(pops[1][1])
     if n1 + n2 >= MAX_PERM_CELLS:
         raise ValueError(f"{n1 + n2} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
-    outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + f".{command}.csv"
+    outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + f"{by}.{command}.csv"
     return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
+                           strata=strata, left_out=left_out,
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"),
                            versus=f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1))
+
+
+def _print_strata(su):
+    if su.strata is not None:
+        m1, m2 = su.strata
+        print(f"Labels permuted within {len(m1)} strata ({int(((m1 > 0) & (m2 > 0)).sum())} with cells of both "
+              f"populations): 10^{_log10_labellings(m1, m2):.1f} distinct labellings; {su.left_out} cells of the two "
+              "clusters have no stratum and were left out")
 
 
 def _perm_run(su, n_perm, seed, device, batch, write):
@@ -779,10 +843,12 @@ def _perm_run(su, n_perm, seed, device, batch, write):
             ctx = run.device()
             budget = _budget(ctx)
             word_bytes = (su.n1 + su.n2 + 63) // 64 * 8
+            if su.strata is not None:
+                word_bytes += len(su.strata[0]) * 8      # the device's key bound per permutation and stratum
             perm_bytes = int(MAX_PERM_BYTES) if MAX_PERM_BYTES is not None else budget // 2
             chunk = max(1, min(n_perm, perm_bytes // word_bytes))
             if chunk == n_perm:
-                _perm_masks(ctx, su.n1, su.n2, 1, n_perm, seed, times)
+                _perm_masks(ctx, su, 1, n_perm, seed, times)
             if MAX_BATCH_BYTES is None:
                 budget //= 2
             # the counts of a record and, at worst, as many 8-byte nonzeros as it has tested counts
@@ -795,16 +861,19 @@ def _perm_run(su, n_perm, seed, device, batch, write):
 
 
 def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
-             n_perm: int = 9999, seed: int = 1, device=None):
+             n_perm: int = 9999, seed: int = 1, device=None, strata_file=None):
     """permutation test of pA usage between the cells of cluster idents_1 and those of idents_2 (None: every other cell
-    that has a cluster); writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.diff_pa.csv in output_dir, returns its path"""
-    su = _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, "diff_pa")
+    that has a cluster); writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.diff_pa.csv in output_dir, returns its path.
+    strata_file (a file like the cluster file): the labels are permuted within its strata only, cells without a stratum
+    are left out, and the file name carries .by_<strata file stem> before .diff_pa.csv"""
+    su = _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, "diff_pa",
+                     strata_file)
     n1, n2, versus = su.n1, su.n2, su.versus
     lines = {k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}
     genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
 
     def batch(ctx, bat, chunk, times):
-        _diff_pa_batch(ctx, bat, su.seg_off, n_perm, chunk, seed, lines, genes, times)
+        _diff_pa_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times)
 
     def write(w):
         w.writerow(DIFF_PA_HEADER)
@@ -841,6 +910,7 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
     wall = _perm_run(su, n_perm, seed, device, batch, write)
     print(f"Finish {n_perm} permutations of {n1} + {n2} cells for {sum(g[1] for g in genes)} pA sites of "
           f"{len(genes)} tested records")
+    _print_strata(su)
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -874,7 +944,7 @@ def _mean_positions(x, a, b):
     return float(m1), float(m2), float(m1 - m2)
 
 
-def _diff_pa_len_batch(ctx, bat, seg_off, n_perm, chunk, seed, out, times):
+def _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
     """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
     n_ge) per tested record to `out`"""
     recs, K = bat.recs, bat.K
@@ -885,7 +955,7 @@ def _diff_pa_len_batch(ctx, bat, seg_off, n_perm, chunk, seed, out, times):
         if not (np.all(np.isfinite(x)) and np.isfinite(x.max() - x.min())):
             raise ValueError(f"{recs[r].gene_info_str}: alpha_arr holds a non-finite position of a pA site with reads")
         pos[r] = x
-    sel = _perm_rows(ctx, bat, seg_off, times, positions)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, positions)
     if sel is None:
         return
     which, off, rows, _nz, sums, rowbase = sel
@@ -910,7 +980,7 @@ def _diff_pa_len_batch(ctx, bat, seg_off, n_perm, chunk, seed, out, times):
     w, tol = np.ascontiguousarray(np.concatenate(w)), np.array(tol, dtype=np.float64)
     t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
     delta0, n_ge = np.zeros(len(which), np.float64), np.zeros(len(which), np.int64)
-    _perm_chunks(ctx, seg_off, n_perm, chunk, seed, times, lambda: check(
+    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
         ctx.lib.scape_hip_report_perm_len(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(w), ptr(tol),
                                           ptr(t, P_i64), ptr(a0, P_i64), ptr(delta0), ptr(n_ge, P_i64)),
         "report_perm_len"))
@@ -921,7 +991,7 @@ def _diff_pa_len_batch(ctx, bat, seg_off, n_perm, chunk, seed, out, times):
     full = np.zeros((len(all_rows), 2), dtype=np.int32)
     full_nz = np.zeros((len(all_rows), 2), dtype=np.int32)
     t0 = timer()
-    check(ctx.lib.scape_hip_report_group_sums(ctx.h, 2, ptr(seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
+    check(ctx.lib.scape_hip_report_group_sums(ctx.h, 2, ptr(su.seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
                                               ptr(full, P_i32), ptr(full_nz, P_i32)), "report_group_sums")
     times["render"] += timer() - t0
     t0 = timer()
@@ -944,15 +1014,16 @@ def _diff_pa_len_batch(ctx, bat, seg_off, n_perm, chunk, seed, out, times):
 
 
 def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
-                 n_perm: int = 9999, seed: int = 1, device=None):
+                 n_perm: int = 9999, seed: int = 1, device=None, strata_file=None):
     """permutation test of the mean pA position (3'UTR length) between the cells of cluster idents_1 and those of
     idents_2 (None: every other cell that has a cluster); writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>
-    .diff_pa_len.csv in output_dir, one line per tested record, and returns its path"""
-    su = _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, "diff_pa_len")
+    .diff_pa_len.csv in output_dir, one line per tested record, and returns its path.  strata_file: as for _diff_pa"""
+    su = _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, "diff_pa_len",
+                     strata_file)
     out = []
 
     def batch(ctx, bat, chunk, times):
-        _diff_pa_len_batch(ctx, bat, su.seg_off, n_perm, chunk, seed, out, times)
+        _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, seed, out, times)
 
     def write(w):
         w.writerow(DIFF_PA_LEN_HEADER)
@@ -968,6 +1039,7 @@ def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, ide
 
     wall = _perm_run(su, n_perm, seed, device, batch, write)
     print(f"Finish {n_perm} permutations of {su.n1} + {su.n2} cells for {len(out)} tested records")
+    _print_strata(su)
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -1167,7 +1239,12 @@ def _perm_options(f):
             click.option('--idents_2', type=str, default=None,
                          help='The cluster of population 2. Default: every other cell that has a cluster.'),
             click.option('--n_perm', type=int, default=9999, show_default=True,
-                         help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).'))):
+                         help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).'),
+            click.option('--strata_file', type=str, default=None,
+                         help='A csv file like the cell_cluster_file, naming a stratum (cell type, donor, batch, ...) '
+                              'per cell: the labels are then permuted within each stratum only. Cells with an empty '
+                              'stratum, or not listed, are left out. Its name will be included in the file name of '
+                              'the final result.'))):
         f = option(f)
     return f
 
@@ -1175,10 +1252,11 @@ def _perm_options(f):
 @click.command(name="diff_pa")
 @_perm_options
 @click.option('--seed', type=int, default=1, show_default=True, help='Seed of the permutations, 0 .. 2^64 - 1.')
-def diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_perm: int, seed: int):
+def diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_perm: int,
+            strata_file, seed: int):
     """pA sites used differently by two cell populations: a permutation test of the cell labels on the pA x cell counts
     of res.gene.pkl / res.utr.pkl (the question of the reference's FindDE, DifferentialTest.R:159-196, without DEXSeq)."""
-    _diff_pa(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed)
+    _diff_pa(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, strata_file=strata_file)
 
 
 @click.command(name="diff_pa_len")
@@ -1187,8 +1265,8 @@ def diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1
               help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives the same relabellings of the cells '
                    'as in diff_pa.')
 def diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_perm: int,
-                seed: int):
+                strata_file, seed: int):
     """3'UTR lengthening or shortening between two cell populations: per gene, a two-sided permutation test of the cell
     labels on the difference of the mean pA position (delta_pos > 0: population 1 uses longer 3'UTRs), with the
     reference's expected pA length (cal_exp_pa_len's 1..10 scale) of both populations beside it."""
-    _diff_pa_len(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed)
+    _diff_pa_len(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, strata_file=strata_file)

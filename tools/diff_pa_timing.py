@@ -14,14 +14,20 @@ statistics; per permutation one gather over the nonzeros and one segmented sum) 
 host threads and reports that time scaled linearly to `--n_perm`, labelled as scaled.  The restatement's counts for
 its N permutations are compared with a GPU run of the same N (`numpy_equals_gpu`) unless --numpy-only is given.
 
+`--strata N` runs the command with --strata_file: N strata of unequal sizes over the same cells (stratum k of 0 .. N-1
+holds about (k + 1) / (1 + 2 + ... + N) of them, so N = 200 on 20,000 cells gives strata of 1 to 200 cells and N = 8
+strata of 555 to 4,444; N = 1 is one stratum of every cell), each with about the populations' overall mix.  The numpy
+restatement knows no strata and is not run with it.
+
     python tools/diff_pa_timing.py [--records N] [--cells N] [--n_perm N] [--dir D] [--numpy N] [--threads N]
-                                   [--gpu-only | --numpy-only]
+                                   [--gpu-only | --numpy-only] [--strata N]
 """
 import argparse
 import contextlib
 import csv
 import io
 import json
+import math
 import os
 import pickle
 import shutil
@@ -76,6 +82,20 @@ def make_dir(root, n_rec, n_cells, seed=7):
              cols=np.concatenate(cols), cnts=np.concatenate(cnts), n_a=n_a, n_cells=n_cells)
 
 
+def make_strata(root, n_cells, n_strata):
+    """strata_<N>.csv: cell i, scrambled to (7919 i) mod n_cells so that every stratum mixes the two clusters, falls
+    into stratum k by the cumulative shares (k + 1) / (N (N + 1) / 2).  Returns (path, cells per stratum)"""
+    if math.gcd(7919, n_cells) != 1:
+        raise SystemExit("--strata needs a number of cells that is no multiple of 7919")
+    total = n_strata * (n_strata + 1) // 2
+    ends = (np.cumsum(np.arange(1, n_strata + 1)) * n_cells + total - 1) // total
+    stratum = np.searchsorted(ends, (np.arange(n_cells) * 7919) % n_cells, side="right")
+    path = os.path.join(root, f"strata_{n_strata}.csv")
+    with open(path, "w") as fh:
+        fh.write("index,stratum\n" + "".join(f"{i},s{k}\n" for i, k in enumerate(stratum.tolist())))
+    return path, np.bincount(stratum, minlength=n_strata)
+
+
 def _mix(z):
     z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
     z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
@@ -125,11 +145,12 @@ def numpy_counts(root, n_perm, seed, threads):
     return site, gene, time.perf_counter() - t0
 
 
-def gpu_run(root, n_perm, seed):
+def gpu_run(root, n_perm, seed, strata_file=None):
     from scape_amd import report
     t0 = time.perf_counter()
+    kw = {} if strata_file is None else {"strata_file": strata_file}
     with contextlib.redirect_stdout(io.StringIO()):
-        path = report._diff_pa(root, "res.gene.pkl", os.path.join(root, "groups.csv"), "A", "B", n_perm, seed)
+        path = report._diff_pa(root, "res.gene.pkl", os.path.join(root, "groups.csv"), "A", "B", n_perm, seed, **kw)
     return path, time.perf_counter() - t0, dict(report.LAST_TIMES)
 
 
@@ -144,7 +165,12 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--gpu-only", action="store_true")
     ap.add_argument("--numpy-only", action="store_true")
+    ap.add_argument("--strata", type=int, default=0, help="permute within this many strata of unequal sizes (0: freely)")
     a = ap.parse_args()
+    if a.strata and (a.numpy or a.numpy_only):
+        ap.error("--strata runs the GPU command only")
+    if a.strata < 0 or a.strata > a.cells:
+        ap.error("--strata must lie in 0 .. --cells")
     root = a.dir or tempfile.mkdtemp(prefix="diff_pa_timing_")
     out = {"records": a.records, "cells": a.cells, "n_perm": a.n_perm, "density": DENSITY}
     try:
@@ -156,11 +182,16 @@ def main():
         z = np.load(os.path.join(root, "nz.npz"))
         out.update(rows=int(z["rec_rows"][-1]), nonzeros=int(z["row_off"][-1]), n1=int(z["n_a"]),
                    n2=int(z["n_cells"]) - int(z["n_a"]))
+        strata_file = None
+        if a.strata:
+            strata_file, sizes = make_strata(root, int(z["n_cells"]), a.strata)
+            out["strata"] = {"n": a.strata, "smallest": int(sizes.min()), "largest": int(sizes.max()),
+                             "up_to_64_cells": int((sizes <= 64).sum()), "up_to_256_cells": int((sizes <= 256).sum())}
         if not a.numpy_only:
             from scape_amd import _lib
             out["device"] = _lib.default_context().name()
-            _path, out["warmup_wall_s"], _ = gpu_run(root, 255, a.seed)
-            path, wall, stages = gpu_run(root, a.n_perm, a.seed)
+            _path, out["warmup_wall_s"], _ = gpu_run(root, 255, a.seed, strata_file)
+            path, wall, stages = gpu_run(root, a.n_perm, a.seed, strata_file)
             with open(path, newline="") as fh:
                 n_lines = sum(1 for _ in fh) - 1
             out["diff_pa"] = {"wall_s": wall, "stages_s": stages, "lines": n_lines,
