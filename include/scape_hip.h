@@ -261,6 +261,46 @@ int scape_hip_report_perm_test(scape_hip_ctx *ctx, int32_t n_rec, const int64_t 
 int scape_hip_report_perm_len(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                               const double *w, const double *tol, int64_t *t_out, int64_t *a0_out, double *delta0_out,
                               int64_t *n_ge_out);
+/* diff_pa_groups: the omnibus form of the permutation test, for G = n_groups populations (2 <= G <= 64) of
+   sizes[g] >= 1 cells, n = sum sizes < 2^24.  The tested columns are the first n columns of the count matrix, population
+   0's first, then population 1's, ...; position j = column j.  Permutation 0 is the observed labelling (group = the
+   population of the position).  Permutation p >= 1 ranks the n keys key(p, j) - the key of scape_hip_report_perm_masks,
+   unchanged, so keys are distinct - and gives position j of rank r(p, j) the group
+     g(p, j) = #{h in 1 .. G-1 : c_h <= r(p, j)},   c_h = sizes[0] + .. + sizes[h-1]:
+   the sizes[0] smallest keys form group 0, the next sizes[1] group 1, and so on.  With G = 2, group 0 is population 1
+   of scape_hip_report_perm_masks(n1 = sizes[0], n2 = sizes[1]) for the same seed, position for position.
+   scape_hip_report_perm_labels builds the groups of permutations p_first .. p_first + p_count - 1 on the device, one byte
+   per (position, permutation): p_count * n bytes laid out [position][permutation] (the G - 1 cut keys of a permutation
+   live in LDS only).  They replace the labels of an earlier call and stay until scape_hip_report_free, across
+   scape_hip_report_counts calls; the membership bits of scape_hip_report_perm_masks are a separate buffer.  Checked
+   before anything is queued: 2 <= n_groups <= 64, every size >= 1, n < 2^24, p_first >= 1, p_count >= 1. */
+int scape_hip_report_perm_labels(scape_hip_ctx *ctx, int32_t n_groups, const int32_t *sizes, int64_t p_first,
+                                 int32_t p_count, uint64_t seed);
+/* The n groups of permutation p_first + p (0 <= p < p_count) of the last labels call: labels_out[j] = g(p_first + p, j). */
+int scape_hip_report_perm_labels_get(scape_hip_ctx *ctx, int32_t p, uint8_t *labels_out);
+/* The test of n_rec records of the last counts call against the permutations of the last perm_labels call; records, kept
+   rows and the ADD semantics as in scape_hip_report_perm_test.  n_groups and seg_off[n_groups + 1] name the groups'
+   column ranges as observed: seg_off[0] = 0 and seg_off[g + 1] - seg_off[g] = sizes[g] of the labels call (checked).
+   Per row i: t_out[i] = its sum over the tested columns, a0_out[i * n_groups + g] = its sum over group g as observed.
+   Under a labelling with row sums a_ig, A_g = sum_i a_ig, T = sum_i t_i < 2^31 (checked) and the 64-bit integer
+   N_ig = a_ig T - t_i A_g, the device forms in f64, contraction off, groups and rows in order,
+     s_i = sum_{g : A_g > 0} N_ig^2 / A_g      and      S = sum_i s_i / (T t_i)
+   (S is Pearson's chi-square of the rows x G table; for G = 2 it equals perm_test's sum N_i^2 / (t_i A B) as a rational;
+   s_i is proportional, by factors that do not depend on the labelling, to the chi-square of the 2 x G table "row i
+   against the record's other rows") through one device function for the observed labelling and every permutation.
+   stat0_out[r] = S(0), site_stat0_out[i] = s_i(0) / (T t_i), the row's share of it.  The call ADDS to site_n_ge_out[i]
+   the number of its permutations with s_i(p) >= s_i(0) (1 - 2^-40) and to gene_n_ge_out[r] those with
+   S(p) >= S(0) (1 - 2^-40); the caller zeroes both before the first chunk of permutations.
+   Rounding: every term is positive and the sums are nested (groups within a row, rows within the record), so S of a
+   record of R rows is within (R + G + 4) 2^-53 of its rational, relatively - the error grows with R + G, not with R x G.
+   Two equal rationals always tie inside the 2^-40 slack, and a labelling at S(0) (1 - 2^-39) or below is never counted,
+   when 2 (R + G + 4) + 1 < 2^13; a record with R + G > 4,000 is refused ("record <r>: ..."), which leaves 183 * 2^-53
+   to spare (derivation: csrc/report.inc, section "G-way labellings").  s_i is within (G + 3) 2^-53 for any R.
+   LDS: 2 * n_groups KiB per workgroup of 256 permutations. */
+int scape_hip_report_perm_groups(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                 int32_t n_groups, const int32_t *seg_off, int64_t *t_out, int64_t *a0_out,
+                                 int64_t *site_n_ge_out, double *stat0_out, double *site_stat0_out,
+                                 int64_t *gene_n_ge_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

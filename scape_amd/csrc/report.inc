@@ -32,6 +32,11 @@
 //                   the same membership bits for labellings permuted within strata only (--strata_file): per
 //                   permutation and stratum the m1[s]-th smallest key of the stratum's cells, by one wave for a stratum
 //                   of up to 256 cells and by the workgroup's radix select for a larger one, one launch for all of them
+//   k_rep_perm_labels / k_rep_groups_rowstat / k_rep_groups_obs / k_rep_perm_groups
+//                   diff_pa_groups: the omnibus form of diff_pa for G = 2..64 populations.  One byte per (position,
+//                   permutation) names the group (radix select of the G - 1 cut keys, one workgroup per
+//                   permutation), and the test accumulates G sums per row and permutation in LDS; section
+//                   "G-way labellings" at the end of this file
 //   k_rep_perm_len  diff_pa_len: the same walk for the record's mean pA position in the two populations (one lane per
 //                   permutation, two f64 sums and two integer sums per lane, exceedance counts per record)
 // Cluster names, their order and the floating-point finish of exp_pa_len stay on the host (scape_amd/report.py).
@@ -60,6 +65,12 @@ struct ReportState {
     // stratified masks: (a1, m1, a2, m2) per stratum, the strata in work order, the stratum of every position and the
     // exclusive key bound per (permutation, stratum)
     DevBuf m_desc, m_order, m_strat, m_bound;
+    // diff_pa_groups: the group of every (position, permutation) of the last scape_hip_report_perm_labels call
+    // ([position][permutation], one byte each), the ranks of its cut keys, and the buffers of
+    // scape_hip_report_perm_groups that scape_hip_report_perm_test has no counterpart of
+    DevBuf q_lab, q_cut, q_seg, q_a0, q_s0, q_share;
+    std::vector<int32_t> q_sizes;      // cells per group of the last labels call
+    int32_t q_n = 0, q_count = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
@@ -85,7 +96,8 @@ static void report_release(scape_hip_ctx *c) {
                      &s->s_roff[1], &s->s_out[0], &s->s_out[1], &s->s_nnz[0], &s->s_nnz[1], &s->s_noff[0],
                      &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz, &s->m_bits, &s->p_rows,
                      &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
-                     &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound};
+                     &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound,
+                     &s->q_lab, &s->q_cut, &s->q_seg, &s->q_a0, &s->q_s0, &s->q_share};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;
@@ -1407,6 +1419,427 @@ int scape_hip_report_perm_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *re
     HIPCHK(hipMemcpyAsync(delta0_out, s->p_stat0.p, (int64_t)n_rec * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int r = 0; r < n_rec; ++r) n_ge_out[r] += ge[r];
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- G-way labellings (diff_pa_groups) --------------------------------------------------------------------------------
+// G = 2..64 populations of sizes n_0 .. n_{G-1}, n = sum n_g tested columns in front of the count matrix, population 0's
+// first.  Permutation p >= 1 ranks the n keys key(p, j) (the key of diff_pa, unchanged) and gives the n_0 smallest to
+// group 0, the next n_1 to group 1, ...: with c_h = n_0 + .. + n_{h-1} and cut_h = the key of rank c_h - 1 (the largest
+// key of the groups below h), h = 1..G-1, the group of position j is #{h : cut_h < key(p, j)}.  With G = 2, group 0 is
+// population 1 of k_rep_perm_mask.
+//
+// The statistic, per record with R kept rows: a_ig = the sum of row i over group g, A_g = sum_i a_ig, t_i = sum_g a_ig,
+// T = sum_i t_i < 2^31, N_ig = a_ig T - t_i A_g exactly in 64 bits (both products are below 2^62),
+//   s_i = sum_{g : A_g > 0} N_ig^2 / A_g   (groups in order)        the site's statistic
+//   S   = sum_i s_i / (T t_i)              (rows in order)          Pearson's chi-square of the rows x G table
+// Every term is positive or zero; no difference is formed in f64.
+// Rounding of the code below (contraction off, unit roundoff u = 2^-53, first order in u):
+//   * (double)N_ig rounds by u (|N| < 2^62), its square by 2 u + u, the division by the exact (double)A_g by u more:
+//     a term is within 4 u of N^2 / A, relatively;
+//   * the first addition of a row (0 + term) is exact, each of the other G - 1 rounds by at most u times a partial sum
+//     of positive terms: s_i is within (G + 3) u;
+//   * (double)T and (double)t_i are exact, their product rounds by u, the division by u: a row's share s_i / (T t_i) is
+//     within (G + 5) u; the first of the R additions is exact, the others round by u each: S is within
+//     e = (R + G + 4) u.
+// The sums are NESTED (groups inside a row, rows inside the record), so the error grows with R + G.  It would grow
+// with R x G only if all R x G terms went through one running sum, which neither the definition above nor this code
+// does; a bound on the product (R x G <= 4,000 or so) is sufficient but far from necessary.
+// The test counts a permutation when S(p) >= S(0) (1 - 2^-40); 1 - 2^-40 is a double and the product rounds by u.
+// Two labellings with equal rationals are both within e of it, so the permuted one is counted when
+// 1 - e >= (1 + e)(1 - 2^-40)(1 + u), and a labelling at S(0) (1 - 2^-39) or below is never counted when
+// (1 - 2^-39)(1 + e) < (1 - e)(1 - 2^-40)(1 - u): both hold when 2 e + u < 2^-40 = 8,192 u, up to terms of second
+// order (e^2 < 2^-80).  With R + G <= 4,000 (REP_GROUPS_MAX_ROWS_AND_GROUPS, checked by the entry point)
+// 2 e + u <= 8,009 u: 183 u to spare.  The site statistic s_i has the error (G + 3) u <= 67 u and needs no bound.
+#define REP_GROUPS_MAX 64
+#define REP_GROUPS_MAX_ROWS_AND_GROUPS 4000
+
+// the key of rank `rank` among key(base, j), j = 0 .. n-1, n >= 2, for the whole workgroup (every thread calls, every
+// thread gets the key): k_rep_perm_mask's radix select in the form k_rep_perm_mask_strata gives it - wave 0 finds the
+// bin, and the select stops at the first byte after which one candidate is left (about log256(n) + 1 of the 8
+// passes); one more pass finds the key that carries the selected prefix
+__device__ __forceinline__ unsigned long long rep_select_key(unsigned long long base, int n, int rank, int *hist,
+                                                             unsigned long long *sel, int *sel_cnt) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long prefix = 0;
+    int cnt = n, pass = 0;
+    for (; pass < 8 && cnt > 1; ++pass) {
+        const int shift = 56 - 8 * pass;
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (int j = threadIdx.x; j < n; j += REP_THREADS) {
+            const unsigned long long k = rep_perm_key(base, j);
+            if (pass == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {              // wave 0: the bin that holds the candidate of that rank
+            const int4 h = reinterpret_cast<const int4 *>(hist)[lane];
+            const int sum = h.x + h.y + h.z + h.w;
+            int incl = sum;
+            for (int o = 1; o < 64; o <<= 1) {
+                const int y = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += y;
+            }
+            if (incl - sum <= rank && rank < incl) {     // one lane: the bins are disjoint and hold cnt > rank keys
+                int r = rank - (incl - sum), b = 4 * lane, in_bin = h.x;
+                if (r >= h.x) {
+                    r -= h.x, ++b, in_bin = h.y;
+                    if (r >= h.y) {
+                        r -= h.y, ++b, in_bin = h.z;
+                        if (r >= h.z) r -= h.z, ++b, in_bin = h.w;
+                    }
+                }
+                sel[0] = prefix | ((unsigned long long)b << shift);
+                sel[1] = (unsigned long long)r;
+                *sel_cnt = in_bin;
+            }
+        }
+        __syncthreads();
+        prefix = sel[0];
+        rank = (int)sel[1];
+        cnt = *sel_cnt;
+    }
+    const int known = 64 - 8 * pass;         // n >= 2, so pass >= 1: the bits above `known` are fixed, one key has them
+    __syncthreads();                         // every thread holds the prefix: sel[0] may now take the key
+    for (int j = threadIdx.x; j < n; j += REP_THREADS) {
+        const unsigned long long k = rep_perm_key(base, j);
+        if ((k >> known) == (prefix >> known)) sel[0] = k;
+    }
+    __syncthreads();
+    const unsigned long long key = sel[0];
+    __syncthreads();                         // the next select writes sel again
+    return key;
+}
+
+// one workgroup per permutation p_first + blockIdx.x: the G - 1 cut keys (rank_of_cut[h] = c_{h+1} - 1, ascending, so
+// the cut keys ascend too), then one pass that counts, per position, the cut keys below its key (binary search in LDS)
+// and writes that group as the byte labels[j * p_count + blockIdx.x].  A workgroup's bytes lie p_count apart: the
+// workgroups of neighbouring permutations fill a cache line between them.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_labels(int32_t n_groups, const int32_t *__restrict__ rank_of_cut,
+                                                                 int32_t n, unsigned long long p_first, int32_t p_count,
+                                                                 unsigned long long seed, uint8_t *__restrict__ labels) {
+    __shared__ __align__(16) int hist[256];
+    __shared__ unsigned long long sel[2];
+    __shared__ int sel_cnt;
+    __shared__ unsigned long long cuts[REP_GROUPS_MAX - 1];
+    const unsigned long long base = rep_mix(seed + REP_PERM_G * (p_first + blockIdx.x));
+    const int n_cuts = n_groups - 1;
+    for (int h = 0; h < n_cuts; ++h) {
+        const unsigned long long k = rep_select_key(base, n, rank_of_cut[h], hist, sel, &sel_cnt);
+        if (threadIdx.x == 0) cuts[h] = k;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += REP_THREADS) {
+        const unsigned long long k = rep_perm_key(base, j);
+        int lo = 0, hi = n_cuts;             // lo = cut keys below k
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cuts[mid] < k) lo = mid + 1;
+            else hi = mid;
+        }
+        labels[(int64_t)j * p_count + blockIdx.x] = (uint8_t)lo;
+    }
+}
+
+// one workgroup per kept row i (count row rows[i]): a0[i * n_groups + g] = its sum over group g as observed (the columns
+// [seg_off[g], seg_off[g + 1]); wave w takes groups w, w + REP_WAVES, ...), t[i] = their sum, nnz[i] = its nonzeros
+__global__ __launch_bounds__(REP_THREADS) void k_rep_groups_rowstat(const int64_t *__restrict__ rows, int32_t n_cols,
+                                                                    const int32_t *__restrict__ cnt, int32_t n_groups,
+                                                                    const int32_t *__restrict__ seg_off,
+                                                                    int64_t *__restrict__ nnz, int64_t *__restrict__ t,
+                                                                    int64_t *__restrict__ a0) {
+    __shared__ long long sum_g[REP_GROUPS_MAX], nz_g[REP_GROUPS_MAX];
+    const int i = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int32_t *row = cnt + rows[i] * n_cols;
+    for (int g = w; g < n_groups; g += REP_WAVES) {
+        long long s = 0, z = 0;
+        for (int c = seg_off[g] + lane; c < seg_off[g + 1]; c += 64) {
+            const int v = row[c];
+            s += v;
+            z += v != 0;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            s += __shfl_xor(s, o, 64);
+            z += __shfl_xor(z, o, 64);
+        }
+        if (lane == 0) {
+            sum_g[g] = s;
+            nz_g[g] = z;
+            a0[(int64_t)i * n_groups + g] = s;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long s = 0, z = 0;
+        for (int g = 0; g < n_groups; ++g) {
+            s += sum_g[g];
+            z += nz_g[g];
+        }
+        t[i] = s;
+        nnz[i] = z;
+    }
+}
+
+// s_i of one row under one labelling: a[g * stride] = a_ig, A[g * stride] = A_g.  The observed labelling (64-bit sums
+// from global memory) and every permutation (32-bit sums in LDS) go through this function and rep_groups_share, with
+// contraction off; every operation is a correctly rounded IEEE one, so equal integers give equal doubles
+template <typename I>
+__device__ __forceinline__ double rep_groups_site(const I *a, const I *A, int stride, int n_groups, long long t,
+                                                  long long T) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int g = 0; g < n_groups; ++g) {
+        const long long Ag = A[g * stride];
+        if (Ag > 0) {
+            const double N = (double)((long long)a[g * stride] * T - t * Ag);
+            s = s + (N * N) / (double)Ag;
+        }
+    }
+    return s;
+}
+
+__device__ __forceinline__ double rep_groups_share(double s, long long t, long long T) {
+#pragma clang fp contract(off)
+    return t > 0 ? s / ((double)T * (double)t) : 0.0;
+}
+
+// one workgroup per record: the observed labelling.  s0[i] = s_i(0), share0[i] = s_i(0) / (T t_i), stat0[r] = S(0),
+// the shares added in row order by one thread, as a lane of k_rep_perm_groups adds them
+__global__ __launch_bounds__(REP_THREADS) void k_rep_groups_obs(const int64_t *__restrict__ roff,
+                                                                const int64_t *__restrict__ t,
+                                                                const int64_t *__restrict__ a0, int32_t n_groups,
+                                                                double *__restrict__ s0, double *__restrict__ share0,
+                                                                double *__restrict__ stat0) {
+#pragma clang fp contract(off)
+    __shared__ long long A0[REP_GROUPS_MAX];
+    __shared__ long long T0;
+    const int r = blockIdx.x;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    if (threadIdx.x < n_groups) {
+        long long A = 0;
+        for (int64_t i = row0; i < row1; ++i) A += a0[i * n_groups + threadIdx.x];
+        A0[threadIdx.x] = A;
+    }
+    if (threadIdx.x == REP_THREADS - 1) {
+        long long T = 0;
+        for (int64_t i = row0; i < row1; ++i) T += t[i];
+        T0 = T;
+    }
+    __syncthreads();
+    const long long T = T0;
+    for (int64_t i = row0 + threadIdx.x; i < row1; i += REP_THREADS) {
+        const double s = rep_groups_site<long long>(reinterpret_cast<const long long *>(a0) + i * n_groups, A0, 1,
+                                                    n_groups, t[i], T);
+        s0[i] = s;
+        share0[i] = rep_groups_share(s, t[i], T);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double S = 0.0;
+        for (int64_t i = row0; i < row1; ++i) S = S + share0[i];
+        stat0[r] = S;
+    }
+}
+
+// the nonzeros nz[k0 .. k1) added to acc[group][lane] under this lane's labelling (lb = the lane's byte of position 0,
+// the positions pstride bytes apart).  The nonzeros are wave-uniform.  Four at a time: their label bytes are loaded
+// before the first addition waits for one.  The addition is an LDS atomic whose result is not used - one ds_add
+// without a return value in place of a read, an add and a write that would wait for each other; no other lane touches
+// the address
+__device__ __forceinline__ void rep_groups_walk(const uint2 *__restrict__ nz, int64_t k0, int64_t k1,
+                                                const uint8_t *__restrict__ lb, int64_t pstride, int32_t *acc) {
+    int64_t k = k0;
+    for (; k + 4 <= k1; k += 4) {
+        int c[4], g[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint2 e = nz[k + u];
+            c[u] = __builtin_amdgcn_readfirstlane((int)e.y);
+            g[u] = lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) atomicAdd(&acc[g[u] * REP_THREADS], c[u]);
+    }
+    for (; k < k1; ++k) {
+        const uint2 e = nz[k];
+        const int c = __builtin_amdgcn_readfirstlane((int)e.y);
+        atomicAdd(&acc[(int)lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride] * REP_THREADS], c);
+    }
+}
+
+// workgroup = (record blockIdx.x / n_tiles, tile of 256 permutations), one lane per permutation; the nonzeros are
+// wave-uniform, the lane reads its own permutation's byte of the nonzero's position (neighbouring lanes, neighbouring
+// bytes) and adds the count to acc[group][lane] in LDS: dword address group * 256 + lane, so the bank is lane mod 32
+// whatever the group and the lanes of a 32-lane access group never meet on one; each lane owns its column and no
+// barrier is needed (rep_groups_walk).  LDS holds A_g(p) (first walk over all the record's
+// nonzeros) and a_ig(p) of the current row (second walk, row by row): 2 x n_groups x 1 KiB.  Exceedances are counted
+// per wave (ballot) and added with one atomic per wave and counter.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_groups(
+    const uint8_t *__restrict__ labels, int32_t p_count, int32_t n_tiles, int32_t n_groups,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ noff, const uint2 *__restrict__ nz,
+    const int64_t *__restrict__ t, const double *__restrict__ s0, const double *__restrict__ stat0,
+    int32_t *__restrict__ site_ge, int32_t *__restrict__ gene_ge) {
+#pragma clang fp contract(off)
+    extern __shared__ int32_t rep_acc[];
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const uint8_t *lb = labels + (valid ? p : p_count - 1);
+    int32_t *accA = rep_acc + threadIdx.x, *acca = accA + n_groups * REP_THREADS;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    long long T = 0;
+    for (int64_t i = row0; i < row1; ++i) T += t[i];
+    for (int g = 0; g < n_groups; ++g) accA[g * REP_THREADS] = 0;
+    rep_groups_walk(nz, noff[row0], noff[row1], lb, p_count, accA);
+    double S = 0.0;
+    for (int64_t i = row0; i < row1; ++i) {
+        for (int g = 0; g < n_groups; ++g) acca[g * REP_THREADS] = 0;
+        rep_groups_walk(nz, noff[i], noff[i + 1], lb, p_count, acca);
+        const long long ti = t[i];
+        const double s = rep_groups_site<int32_t>(acca, accA, REP_THREADS, n_groups, ti, T);
+        S = S + rep_groups_share(s, ti, T);
+        const unsigned long long b = __ballot(valid && s >= s0[i] * REP_PERM_SLACK);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(&site_ge[i], __popcll(b));
+    }
+    const unsigned long long b = __ballot(valid && S >= stat0[r] * REP_PERM_SLACK);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[r], __popcll(b));
+}
+
+extern "C" {
+
+int scape_hip_report_perm_labels(scape_hip_ctx *c, int32_t n_groups, const int32_t *sizes, int64_t p_first,
+                                 int32_t p_count, uint64_t seed) {
+    CTX_ENTER(c);
+    if (n_groups < 2 || n_groups > REP_GROUPS_MAX)
+        return fail("n_groups must lie in 2 .. " + std::to_string(REP_GROUPS_MAX));
+    if (!sizes) return fail("bad argument");
+    int64_t n = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        if (sizes[g] < 1) return fail("group " + std::to_string(g) + ": every group needs at least one cell");
+        n += sizes[g];
+    }
+    if (n >= REP_PERM_MAX_N) return fail("the groups' cells must number below 2^24 (a key keeps the position in 24 bits)");
+    if (p_first < 1 || p_count < 1) return fail("p_first and p_count must be at least 1 (permutation 0 is the observed labelling)");
+    ReportState *s = report_state(c);
+    s->q_count = 0;
+    std::vector<int32_t> rank_of_cut(n_groups - 1);
+    int32_t below = 0;
+    for (int32_t h = 0; h + 1 < n_groups; ++h) {
+        below += sizes[h];
+        rank_of_cut[h] = below - 1;
+    }
+    if (s->q_lab.ensure((int64_t)p_count * n) || s->q_cut.ensure((int64_t)(n_groups - 1) * 4)) return 1;
+    HIPCHK(hipMemcpyAsync(s->q_cut.p, rank_of_cut.data(), (int64_t)(n_groups - 1) * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_perm_labels, dim3(p_count), dim3(REP_THREADS), 0, c->stream, n_groups,
+                       s->q_cut.as<int32_t>(), (int32_t)n, (unsigned long long)p_first, p_count,
+                       (unsigned long long)seed, s->q_lab.as<uint8_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    s->q_sizes.assign(sizes, sizes + n_groups);
+    s->q_n = (int32_t)n;
+    s->q_count = p_count;
+    return 0;
+}
+
+int scape_hip_report_perm_labels_get(scape_hip_ctx *c, int32_t p, uint8_t *labels_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->q_count) return fail("scape_hip_report_perm_labels has not been called");
+    if (!labels_out) return fail("bad argument");
+    if (p < 0 || p >= s->q_count) return fail("p must name a permutation of the last labels call");
+    HIPCHK(hipMemcpy2DAsync(labels_out, 1, s->q_lab.as<uint8_t>() + p, (size_t)s->q_count, 1, (size_t)s->q_n,
+                            hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                 int32_t n_groups, const int32_t *seg_off, int64_t *t_out, int64_t *a0_out,
+                                 int64_t *site_n_ge_out, double *stat0_out, double *site_stat0_out,
+                                 int64_t *gene_n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
+    if (!s->q_count) return fail("scape_hip_report_perm_labels has not been called");
+    if (n_rec <= 0 || !rec_row_off || !rows || !seg_off || !t_out || !a0_out || !site_n_ge_out || !stat0_out ||
+        !site_stat0_out || !gene_n_ge_out)
+        return fail("bad argument");
+    if (n_groups != (int32_t)s->q_sizes.size()) return fail("n_groups differs from the last scape_hip_report_perm_labels call");
+    if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (seg_off[g + 1] - seg_off[g] != s->q_sizes[g])
+            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last scape_hip_report_perm_labels call");
+    const int32_t n = s->q_n;
+    if (n > s->n_cols) return fail("the count matrix has fewer columns than the labels have positions");
+    if (rec_row_off[0] != 0) return fail("rec_row_off must start at 0");
+    for (int r = 0; r < n_rec; ++r)
+        if (rec_row_off[r + 1] < rec_row_off[r]) return fail("rec_row_off must be non-decreasing");
+    const int64_t n_rows = rec_row_off[n_rec];
+    if (n_rows <= 0 || n_rows > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
+    for (int r = 0; r < n_rec; ++r)
+        if (rec_row_off[r + 1] - rec_row_off[r] + n_groups > REP_GROUPS_MAX_ROWS_AND_GROUPS)
+            return fail("record " + std::to_string(r) + ": " + std::to_string(rec_row_off[r + 1] - rec_row_off[r]) +
+                        " rows and " + std::to_string(n_groups) + " groups, together more than " +
+                        std::to_string(REP_GROUPS_MAX_ROWS_AND_GROUPS) + " (the rounding bound of the statistic)");
+    for (int64_t i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
+    const int32_t n_tiles = (s->q_count + REP_THREADS - 1) / REP_THREADS;
+    if ((int64_t)n_rec * n_tiles > INT32_MAX) return fail("too many records x permutation tiles for one call");
+
+    if (s->p_rows.ensure(n_rows * 8) || s->p_roff.ensure(((int64_t)n_rec + 1) * 8) || s->p_nnz.ensure(n_rows * 8) ||
+        s->p_noff.ensure((n_rows + 1) * 8) || s->p_t.ensure(n_rows * 8) || s->q_a0.ensure(n_rows * n_groups * 8) ||
+        s->q_seg.ensure(((int64_t)n_groups + 1) * 4) || s->q_s0.ensure(n_rows * 8) || s->q_share.ensure(n_rows * 8) ||
+        s->p_site.ensure(n_rows * 4) || s->p_gene.ensure((int64_t)n_rec * 4) || s->p_stat0.ensure((int64_t)n_rec * 8))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->p_rows.p, rows, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->p_roff.p, rec_row_off, ((int64_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->q_seg.p, seg_off, ((int64_t)n_groups + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_groups_rowstat, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
+                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n_groups, s->q_seg.as<int32_t>(),
+                       s->p_nnz.as<int64_t>(), s->p_t.as<int64_t>(), s->q_a0.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->p_nnz.as<int64_t>(),
+                       (int32_t)n_rows, s->p_noff.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, s->p_noff.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(t_out, s->p_t.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(a0_out, s->q_a0.p, n_rows * n_groups * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < n_rec; ++r) {
+        int64_t T = 0;
+        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) T += t_out[i];
+        if (T > INT32_MAX) return fail("record " + std::to_string(r) + ": 2^31 or more reads in the tested cells");
+    }
+    if (s->p_nz.ensure(std::max<int64_t>(total, 1) * 8)) return 1;
+    hipLaunchKernelGGL(k_rep_perm_fill, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
+                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n, s->p_noff.as<int64_t>(),
+                       s->p_nz.as<uint2>());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rep_groups_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream, s->p_roff.as<int64_t>(),
+                       s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_groups, s->q_s0.as<double>(),
+                       s->q_share.as<double>(), s->p_stat0.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(s->p_site.p, 0, n_rows * 4, c->stream));
+    HIPCHK(hipMemsetAsync(s->p_gene.p, 0, (int64_t)n_rec * 4, c->stream));
+    const size_t lds = (size_t)2 * n_groups * REP_THREADS * 4;   // above 64 KiB a kernel needs the attribute
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_groups),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * REP_GROUPS_MAX * REP_THREADS * 4));
+    hipLaunchKernelGGL(k_rep_perm_groups, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), lds, c->stream,
+                       s->q_lab.as<uint8_t>(), s->q_count, n_tiles, n_groups, s->p_roff.as<int64_t>(),
+                       s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->q_s0.as<double>(),
+                       s->p_stat0.as<double>(), s->p_site.as<int32_t>(), s->p_gene.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> site(n_rows), gene(n_rec);
+    HIPCHK(hipMemcpyAsync(site.data(), s->p_site.p, n_rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(gene.data(), s->p_gene.p, (int64_t)n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(stat0_out, s->p_stat0.p, (int64_t)n_rec * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(site_stat0_out, s->q_share.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n_rows; ++i) site_n_ge_out[i] += site[i];
+    for (int r = 0; r < n_rec; ++r) gene_n_ge_out[r] += gene[r];
     return 0;
 }
 

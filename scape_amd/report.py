@@ -1,8 +1,8 @@
-"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa`` and
-``scape diff_pa_len``: the stages after ``merge_pa`` (reference ``src/scape/utils.py:319-427`` and ``:438-553``, with
+"""``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa``,
+``scape diff_pa_len`` and ``scape diff_pa_groups``: the stages after ``merge_pa`` (reference ``src/scape/utils.py:319-427`` and ``:438-553``, with
 ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of ``apa_core.py:1038-1063``).
 
-All five stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
+All six stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
 ``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc``.  They
 share one host core (section "shared host core" below): ``_Run`` frames a command (stage times, ``.part`` targets, the
 device context and its release), ``_read_inputs`` reads what the count-matrix commands need before the device is
@@ -32,6 +32,10 @@ device's rendering of one text block with the gzip of the previous one.
   Both take ``--strata_file`` (cell type, donor, batch, ... per cell): the labels are then permuted within each
   stratum only, which keeps a difference between strata of unequal composition out of the p-values.  Only the
   membership bits change (one more kernel, ``k_rep_perm_mask_strata``); the statistics stay pooled over the strata.
+* ``diff_pa_groups``: the omnibus form of ``diff_pa`` for 2 to 64 populations at once (every cluster of the cluster
+  file, or the ones named): the same keys rank the cells, the device cuts the ranking into the populations' sizes (one
+  byte per cell and permutation) and accumulates one sum per row, population and permutation in LDS (section
+  diff_pa_groups below).
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -191,7 +195,7 @@ class _Run:
 def _read_inputs(output_dir, res_pkl_file, cell_cluster_file=None, idents=(None, None), with_cb=False):
     """what ex_pa_cnt_mat and the cluster-aware commands read before the device is opened, after their own argument
     checks: the paths, barcode_index.csv (the CB column when with_cb, the column ids, the number of columns) and,
-    with a cluster file, the populations of _populations"""
+    with a cluster file, the populations of _populations and the cluster names in order of first appearance"""
     import pandas as pd
     res_pkl = os.path.join(output_dir, res_pkl_file)
     if not (os.path.exists(output_dir)):
@@ -208,11 +212,11 @@ def _read_inputs(output_dir, res_pkl_file, cell_cluster_file=None, idents=(None,
     col_ids = cb_df.index.to_numpy()
     if col_ids.dtype.kind not in "iu":
         raise ValueError("barcode_index.csv: the index column must hold integer ids")
-    pops = None
+    pops = order = None
     if cell_cluster_file is not None:
         col_clu, order = _column_clusters(col_ids.astype(np.int64), *_read_clusters(cell_cluster_file))
         pops = _populations(col_clu, order, *idents)
-    return SimpleNamespace(res_pkl=res_pkl, cb_lst=cb_lst, col_ids=col_ids, n_cols=n_cols, pops=pops)
+    return SimpleNamespace(res_pkl=res_pkl, cb_lst=cb_lst, col_ids=col_ids, n_cols=n_cols, pops=pops, clusters=order)
 
 
 def _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2):
@@ -663,9 +667,12 @@ def _bh(p):
 
 def _perm_masks(ctx, su, p_first, p_count, seed, times):
     """the membership bits of p_count permutations from p_first on: relabelled within su.strata = (m1, m2) when given,
-    freely otherwise"""
+    freely otherwise; for diff_pa_groups (su.sizes = cells per group) the group bytes instead"""
     t0 = timer()
-    if su.strata is not None:
+    if su.sizes is not None:
+        check(ctx.lib.scape_hip_report_perm_labels(ctx.h, len(su.sizes), ptr(su.sizes, P_i32), p_first, p_count, seed),
+              "report_perm_labels")
+    elif su.strata is not None:
         m1, m2 = su.strata
         check(ctx.lib.scape_hip_report_perm_masks_strata(ctx.h, len(m1), ptr(m1, P_i32), ptr(m2, P_i32), p_first,
                                                          p_count, seed), "report_perm_masks_strata")
@@ -677,17 +684,19 @@ def _perm_masks(ctx, su, p_first, p_count, seed, times):
 def _perm_rows(ctx, bat, seg_off, times, each_kept=None):
     """the tested records of one counted batch and their kept rows: (batch indices of the tested records, row offsets
     per tested record, count rows, cells with a count above 0 per row and population, sums per row and population,
-    first count row of every record of the batch), or None when no record of the batch is tested.  each_kept(r,
+    first count row of every record of the batch), or None when no record of the batch is tested: a record is tested
+    when it has two kept rows or more and two populations or more (of the len(seg_off) - 1) with reads.  each_kept(r,
     labels), when given, is called for every record of K >= 2 that has a kept row, tested or not, with the labels of
     its kept rows"""
     recs, K = bat.recs, bat.K
     rowbase, cand, owner, label = _kept_rows(bat)
     if not len(cand):
         return None
-    sums = np.zeros((len(cand), 2), dtype=np.int32)
-    nz = np.zeros((len(cand), 2), dtype=np.int32)
+    n_seg = len(seg_off) - 1
+    sums = np.zeros((len(cand), n_seg), dtype=np.int32)
+    nz = np.zeros((len(cand), n_seg), dtype=np.int32)
     t0 = timer()
-    check(ctx.lib.scape_hip_report_group_sums(ctx.h, 2, ptr(seg_off, P_i32), len(cand), ptr(cand, P_i64),
+    check(ctx.lib.scape_hip_report_group_sums(ctx.h, n_seg, ptr(seg_off, P_i32), len(cand), ptr(cand, P_i64),
                                               ptr(sums, P_i32), ptr(nz, P_i32)), "report_group_sums")
     times["render"] += timer() - t0
     t0 = timer()
@@ -699,9 +708,8 @@ def _perm_rows(ctx, bat, seg_off, times, each_kept=None):
         labs = label[keep]
         for r in np.nonzero((n_kept > 0) & (K >= 2))[0].tolist():
             each_kept(r, labs[cut[r] - n_kept[r]:cut[r]])
-    A = np.bincount(owner, weights=sums[:, 0], minlength=len(recs))
-    B = np.bincount(owner, weights=sums[:, 1], minlength=len(recs))
-    tested = (n_kept >= 2) & (A > 0) & (B > 0)
+    with_reads = sum(np.bincount(owner, weights=sums[:, g], minlength=len(recs)) > 0 for g in range(n_seg))
+    tested = (n_kept >= 2) & (with_reads >= 2)           # two populations: both have reads
     keep &= tested[owner]
     which = np.nonzero(tested)[0]
     times["finish"] += timer() - t0
@@ -820,7 +828,7 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
         raise ValueError(f"{n1 + n2} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + f"{by}.{command}.csv"
     return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
-                           strata=strata, left_out=left_out,
+                           strata=strata, left_out=left_out, sizes=None,
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"),
                            versus=f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1))
 
@@ -834,7 +842,7 @@ def _print_strata(su):
 
 
 def _perm_run(su, n_perm, seed, device, batch, write):
-    """the run both commands share: the masks (once, when all permutations fit MAX_PERM_BYTES; otherwise per chunk inside
+    """the run the permutation commands share: the masks (once, when all permutations fit MAX_PERM_BYTES; otherwise per chunk inside
     every batch), batch(ctx, counted batch, chunk, times) per counted batch, then write(csv writer) into the .part file
     that is renamed when complete.  Returns the wall seconds; LAST_TIMES holds the stages"""
     with _Run(device, [su.outpath]) as run:
@@ -842,9 +850,12 @@ def _perm_run(su, n_perm, seed, device, batch, write):
         with open(run.parts[0], "w", newline="") as fh:
             ctx = run.device()
             budget = _budget(ctx)
-            word_bytes = (su.n1 + su.n2 + 63) // 64 * 8
-            if su.strata is not None:
-                word_bytes += len(su.strata[0]) * 8      # the device's key bound per permutation and stratum
+            if su.sizes is not None:
+                word_bytes = int(su.sizes.sum())         # diff_pa_groups: one byte per tested cell and permutation
+            else:
+                word_bytes = (su.n1 + su.n2 + 63) // 64 * 8
+                if su.strata is not None:
+                    word_bytes += len(su.strata[0]) * 8  # the device's key bound per permutation and stratum
             perm_bytes = int(MAX_PERM_BYTES) if MAX_PERM_BYTES is not None else budget // 2
             chunk = max(1, min(n_perm, perm_bytes // word_bytes))
             if chunk == n_perm:
@@ -1040,6 +1051,160 @@ def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, ide
     wall = _perm_run(su, n_perm, seed, device, batch, write)
     print(f"Finish {n_perm} permutations of {su.n1} + {su.n2} cells for {len(out)} tested records")
     _print_strata(su)
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- diff_pa_groups
+# The omnibus form of diff_pa: which records use their pA sites differently across G = 2..64 populations at all.  One
+# population per cluster of the cluster file (order of first appearance, clusters without a column dropped, as
+# ex_pa_pseudobulk), or the clusters named by --idents, in the order given.  Tested columns: population 0's matrix
+# columns ascending, then population 1's, ...: positions j = 0 .. n-1.  Permutation p of 1 .. n_perm ranks the keys
+# key(p, j) of diff_pa (same hash, same seed) and gives the n_0 smallest to group 0, the next n_1 to group 1, ...; p = 0
+# is the observed labelling.  Per record, with a_ig the sum of kept row i over group g, A_g = sum_i a_ig, t_i = sum_g
+# a_ig, T = sum t_i and the integer N_ig = a_ig T - t_i A_g:
+#     s_i = sum_{g: A_g > 0} N_ig^2 / A_g  tests the site,   S = sum_i s_i / (T t_i)  the record
+# (S is Pearson's chi-square of the rows x G table and, for G = 2, diff_pa's S as a rational).  A record is tested when
+# it has two kept rows or more and two populations or more with reads.  p = (1 + #{p: stat(p) >= stat(0)}) / (1 + n_perm),
+# Benjamini-Hochberg over the file's lines (sites) and over the tested records (genes).  Not part of this command:
+# --strata_file (blocked G-way relabelling needs cut points per stratum and group) and an omnibus for diff_pa_len.
+DIFF_PA_GROUPS_HEADER = ["gene", "pa_info", "num_groups", "top_group", "top_delta_usage", "site_stat", "n_ge", "p_val",
+                         "p_val_adj", "gene_stat", "gene_n_ge", "gene_p_val", "gene_p_val_adj", "n_perm"]
+MAX_GROUPS = 64                  # a group is one byte on the device, and its sums 2 KiB of LDS
+MAX_ROWS_AND_GROUPS = 4000       # kept rows + populations of a record: the rounding bound of S (include/scape_hip.h)
+
+
+def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed):
+    """what diff_pa_groups does before the device is opened: the argument and prerequisite checks, the populations, the
+    id -> column table that puts population 0's columns first, then population 1's, ..., and the output path
+    <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_groups.csv"""
+    idents = [str(i) for i in idents or ()]
+    if n_perm < 1:
+        raise ValueError(f"n_perm must be at least 1, not {n_perm}")
+    if n_perm >= 1 << 31:
+        raise ValueError(f"n_perm must be below 2^31, not {n_perm}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
+    for k, ident in enumerate(idents):
+        if ident in idents[:k]:
+            raise ValueError(f"ident {ident!r} is given twice")
+    tag = "." + "+".join(idents) if idents else ""
+    if os.sep in tag:
+        raise ValueError(f"an ident with {os.sep!r} cannot be part of a file name")
+    inp = _read_inputs(output_dir, res_pkl_file, cell_cluster_file)
+    pops = inp.pops
+    if idents:
+        with_cells = dict(pops)
+        for ident in idents:
+            if ident not in inp.clusters:
+                raise ValueError(f"ident {ident!r} names no cluster of the cell_cluster_file")
+            if ident not in with_cells:
+                raise ValueError(f"cluster {ident!r} has no cell in barcode_index.csv")
+        pops = [(ident, with_cells[ident]) for ident in idents]
+    if not 2 <= len(pops) <= MAX_GROUPS:
+        raise ValueError(f"{len(pops)} populations: diff_pa_groups takes 2 to {MAX_GROUPS}")
+    _table, slot, seg_off, _seg_pop = _samples(pops, 1, inp.n_cols)
+    sizes = np.array([len(cols) for _name, cols in pops], dtype=np.int32)
+    if int(sizes.sum()) >= MAX_PERM_CELLS:
+        raise ValueError(f"{int(sizes.sum())} tested cells: diff_pa_groups takes fewer than {MAX_PERM_CELLS}")
+    outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + ".diff_pa_groups.csv"
+    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, strata=None,
+                           names=[name for name, _cols in pops], outpath=outpath,
+                           idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
+
+
+def _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times):
+    """one counted batch: the kept rows of its tested records go through the G-way permutation test; appends the
+    per-line arrays to `lines` and (gene_info_str, lines, S(0), gene_n_ge) per tested record to `genes`"""
+    sel = _perm_rows(ctx, bat, su.seg_off, times)
+    if sel is None:
+        return
+    recs, G = bat.recs, len(su.sizes)
+    which, off, rows, nz, sums, rowbase = sel
+    for g, r in enumerate(which.tolist()):
+        if int(off[g + 1] - off[g]) + G > MAX_ROWS_AND_GROUPS:
+            raise ValueError(f"{recs[r].gene_info_str}: {int(off[g + 1] - off[g])} pA sites with reads and {G} "
+                             f"populations, together more than {MAX_ROWS_AND_GROUPS}: beyond the rounding bound of "
+                             "the statistic")
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
+    site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
+    stat0, site_stat0 = np.zeros(len(which), np.float64), np.zeros(len(rows), np.float64)
+    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
+        ctx.lib.scape_hip_report_perm_groups(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G,
+                                             ptr(su.seg_off, P_i32), ptr(t, P_i64), ptr(a0, P_i64),
+                                             ptr(site_ge, P_i64), ptr(stat0), ptr(site_stat0), ptr(gene_ge, P_i64)),
+        "report_perm_groups"))
+    t0 = timer()
+    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums)):
+        raise _lib.ScapeHipError("report_perm_groups: row sums differ from report_group_sums")
+    for g, r in enumerate(which.tolist()):
+        a, b = int(off[g]), int(off[g + 1])
+        if int(t[a:b].sum()) >= 1 << 31:
+            raise ValueError(f"{recs[r].gene_info_str}: 2^31 or more reads in the tested cells")
+        genes.append((recs[r].gene_info_str, b - a, float(stat0[g]), int(gene_ge[g])))
+        lines["pa"].extend(_pa_info(recs[r], rows[a:b] - int(rowbase[r])))
+    for key, arr in (("a", a0), ("nz", nz), ("n_ge", site_ge), ("site_stat", site_stat0)):
+        lines[key].append(np.array(arr))
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
+                    seed: int = 1, device=None):
+    """permutation test of pA usage across the populations of a cluster file (every cluster, or the clusters `idents` in
+    the order given); writes <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_groups.csv in output_dir, one line per
+    kept row of a tested record, and returns its path"""
+    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
+    names, G = su.names, len(su.sizes)
+    lines = {k: [] for k in ("pa", "a", "nz", "n_ge", "site_stat")}
+    genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
+
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times)
+
+    def write(w):
+        w.writerow(DIFF_PA_GROUPS_HEADER + [f"usage.{n}" for n in names] + [f"pct.{n}" for n in names])
+        if not genes:
+            return
+        a, nz, n_ge, site_stat = (np.concatenate(lines[k]) for k in ("a", "nz", "n_ge", "site_stat"))
+        n_lines = np.array([g[1] for g in genes], dtype=np.int64)
+        rec_of = np.repeat(np.arange(len(genes)), n_lines)
+        first = np.concatenate([[0], np.cumsum(n_lines)[:-1]])
+        A = np.add.reduceat(a, first, axis=0)            # [record][group]
+        p_val = (1 + n_ge) / (1 + n_perm)
+        gene_ge = np.array([g[3] for g in genes], dtype=np.int64)
+        gene_p = (1 + gene_ge) / (1 + n_perm)
+        gene_adj = _bh(gene_p)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            usage = a / A[rec_of]                        # nan where the population has no read in the record
+        pct = nz / su.sizes.astype(np.float64)
+        # the population with the largest N_ig^2 / A_g, compared exactly (Python ints, cross-multiplied); the first wins ties
+        top, top_delta = [], []
+        for ai, Ar in zip(a.tolist(), A[rec_of].tolist()):
+            ti, T = sum(ai), sum(Ar)
+            best = None
+            for g in range(G):
+                if Ar[g] > 0:
+                    N = ai[g] * T - ti * Ar[g]
+                    if best is None or N * N * best[2] > best[1] * best[1] * Ar[g]:
+                        best = (g, N, Ar[g])
+            top.append(names[best[0]])
+            top_delta.append(repr(best[1] / (best[2] * T)))
+        cols = [[genes[g][0] for g in rec_of.tolist()], lines["pa"], (A > 0).sum(axis=1)[rec_of].tolist(), top,
+                top_delta, [repr(x) for x in site_stat.tolist()], n_ge.tolist()]
+        stat0 = np.array([g[2] for g in genes])
+        for v in (p_val, _bh(p_val), stat0[rec_of]):
+            cols.append([repr(x) for x in v.tolist()])
+        cols.append(gene_ge[rec_of].tolist())
+        for v in (gene_p[rec_of], gene_adj[rec_of]):
+            cols.append([repr(x) for x in v.tolist()])
+        cols.append([n_perm] * len(n_ge))
+        for v in (usage, pct):
+            cols.extend([repr(x) for x in v[:, g].tolist()] for g in range(G))
+        w.writerows(zip(*cols))
+
+    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    print(f"Finish {n_perm} permutations of {int(su.sizes.sum())} cells in {G} populations for "
+          f"{sum(g[1] for g in genes)} pA sites of {len(genes)} tested records")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -1270,3 +1435,26 @@ def diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, iden
     labels on the difference of the mean pA position (delta_pos > 0: population 1 uses longer 3'UTRs), with the
     reference's expected pA length (cal_exp_pa_len's 1..10 scale) of both populations beside it."""
     _diff_pa_len(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, strata_file=strata_file)
+
+
+@click.command(name="diff_pa_groups")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the final '
+                   'result.')
+@click.option('--cell_cluster_file', type=str, required=True,
+              help='An csv file containing two columns in order: cell barcode index (index) and respective group. Cells '
+                   'with an empty group, or not listed, are left out. Its name will be included in the file name of the '
+                   'final result.')
+@click.option('--idents', type=str, multiple=True,
+              help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. Default: every '
+                   'cluster of the cell_cluster_file, in order of first appearance.')
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1 (the keys are those of diff_pa).')
+def diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents, n_perm: int, seed: int):
+    """pA sites and genes whose pA usage differs across the cell populations of a cluster file at all: the omnibus
+    form of diff_pa, a permutation test of the cell labels on Pearson's chi-square of the sites x populations table."""
+    _diff_pa_groups(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
