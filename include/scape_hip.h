@@ -199,7 +199,8 @@ int scape_hip_report_render_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows
    once both arrays are on the host. */
 int scape_hip_report_group_sums(scape_hip_ctx *ctx, int32_t n_seg, const int32_t *seg_off, int32_t n_rows,
                                 const int64_t *rows, int32_t *sum_out, int32_t *nz_out);
-/* diff_pa: permutation test of pA usage between two cell populations.  The tested columns are the first n = n1 + n2
+/* The permutation tests (perm.inc).
+   diff_pa: permutation test of pA usage between two cell populations.  The tested columns are the first n = n1 + n2
    columns of the count matrix (the caller passes scape_hip_report_counts an id2col that puts population 1's columns
    first, then population 2's); position j = column j.  Permutation 0 is the observed labelling (positions < n1).
    Permutation p >= 1 gives population 1 the n1 positions with the smallest key(p, j), all arithmetic mod 2^64:
@@ -208,7 +209,8 @@ int scape_hip_report_group_sums(scape_hip_ctx *ctx, int32_t n_seg, const int32_t
      h(p, j) = mix(mix(seed + G * p) + G * (j + 1)),  key(p, j) = (h(p, j) & ~0xFFFFFF) | j
    scape_hip_report_perm_masks builds the membership bits of permutations p_first .. p_first + p_count - 1 (p_first >= 1)
    on the device, p_count * ceil(n / 64) * 8 bytes laid out [column word][permutation]; they replace the bits of an
-   earlier call and stay until scape_hip_report_free, across scape_hip_report_counts calls.  n1, n2 >= 1, n < 2^24. */
+   earlier call and stay until scape_hip_report_free, across scape_hip_report_counts calls.  n1, n2 >= 1, n < 2^24.
+   The call is scape_hip_report_perm_masks_strata's with one stratum of every cell, p_count * 8 bytes of scratch included. */
 int scape_hip_report_perm_masks(scape_hip_ctx *ctx, int32_t n1, int32_t n2, int64_t p_first, int32_t p_count,
                                 uint64_t seed);
 /* Labellings permuted within strata only (blocked permutations: cell type, donor, batch, ...).  Positions: population 1's
@@ -255,7 +257,7 @@ int scape_hip_report_perm_test(scape_hip_ctx *ctx, int32_t n_rec, const int64_t 
    Each mean is within (R + 1) 2^-53 span of its exact value for R rows, delta within (2 R + 3) 2^-53 span, and a
    record may own at most 1,024 rows (checked), so the observed and a permuted |delta| and the threshold's subtraction
    are together off by at most 4,103 * 2^-53 span, about half of tol: a labelling whose exact |delta| reaches the observed
-   one is always counted, one more than 2 tol below it never (derivation: csrc/report.inc above k_rep_perm_len).  The
+   one is always counted, one more than 2 tol below it never (derivation: csrc/perm.inc above k_rep_perm_len).  The
    band is absolute, not relative as in perm_test, because delta is a difference of two means and can cancel.
    w and tol must be finite and not negative. */
 int scape_hip_report_perm_len(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -295,7 +297,7 @@ int scape_hip_report_perm_labels_get(scape_hip_ctx *ctx, int32_t p, uint8_t *lab
    record of R rows is within (R + G + 4) 2^-53 of its rational, relatively - the error grows with R + G, not with R x G.
    Two equal rationals always tie inside the 2^-40 slack, and a labelling at S(0) (1 - 2^-39) or below is never counted,
    when 2 (R + G + 4) + 1 < 2^13; a record with R + G > 4,000 is refused ("record <r>: ..."), which leaves 183 * 2^-53
-   to spare (derivation: csrc/report.inc, section "G-way labellings").  s_i is within (G + 3) 2^-53 for any R.
+   to spare (derivation: csrc/perm.inc, section "G-way labellings").  s_i is within (G + 3) 2^-53 for any R.
    LDS: 2 * n_groups KiB per workgroup of 256 permutations. */
 int scape_hip_report_perm_groups(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                                  int32_t n_groups, const int32_t *seg_off, int64_t *t_out, int64_t *a0_out,

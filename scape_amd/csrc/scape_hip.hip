@@ -2162,3 +2162,4 @@ int scape_hip_em_traffic(scape_hip_ctx *c, int64_t *mstep_tensor_bytes, int64_t 
 }  // extern "C"
 
 #include "report.inc"
+#include "perm.inc"

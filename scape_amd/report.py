@@ -3,7 +3,7 @@
 ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of ``apa_core.py:1038-1063``).
 
 All six stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
-``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc``.  They
+``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc`` and ``csrc/perm.inc``.  They
 share one host core (section "shared host core" below): ``_Run`` frames a command (stage times, ``.part`` targets, the
 device context and its release), ``_read_inputs`` reads what the count-matrix commands need before the device is
 opened, ``_count`` / ``_kept_rows`` give the label rows with reads of a batch, and ``_two_slot_blocks`` overlaps the
@@ -31,7 +31,8 @@ device's rendering of one text block with the gzip of the previous one.
   the exact means and the reference's ``exp_pa_len`` of both populations.
   Both take ``--strata_file`` (cell type, donor, batch, ... per cell): the labels are then permuted within each
   stratum only, which keeps a difference between strata of unequal composition out of the p-values.  Only the
-  membership bits change (one more kernel, ``k_rep_perm_mask_strata``); the statistics stay pooled over the strata.
+  membership bits change (``k_rep_perm_mask_strata`` builds them either way: without the option every cell is in one
+  stratum); the statistics stay pooled over the strata.
 * ``diff_pa_groups``: the omnibus form of ``diff_pa`` for 2 to 64 populations at once (every cluster of the cluster
   file, or the ones named): the same keys rank the cells, the device cuts the ranking into the populations' sizes (one
   byte per cell and permutation) and accumulates one sum per row, population and permutation in LDS (section
@@ -853,9 +854,8 @@ def _perm_run(su, n_perm, seed, device, batch, write):
             if su.sizes is not None:
                 word_bytes = int(su.sizes.sum())         # diff_pa_groups: one byte per tested cell and permutation
             else:
-                word_bytes = (su.n1 + su.n2 + 63) // 64 * 8
-                if su.strata is not None:
-                    word_bytes += len(su.strata[0]) * 8  # the device's key bound per permutation and stratum
+                # the bits, and the device's key bound per permutation and stratum (one stratum without --strata_file)
+                word_bytes = (su.n1 + su.n2 + 63) // 64 * 8 + (1 if su.strata is None else len(su.strata[0])) * 8
             perm_bytes = int(MAX_PERM_BYTES) if MAX_PERM_BYTES is not None else budget // 2
             chunk = max(1, min(n_perm, perm_bytes // word_bytes))
             if chunk == n_perm:

@@ -1,6 +1,6 @@
 """`scape diff_pa_groups`: the omnibus permutation test of pA usage across G = 2..64 cell populations
 (scape_amd/report.py, section diff_pa_groups; kernels k_rep_perm_labels, k_rep_groups_rowstat, k_rep_groups_obs and
-k_rep_perm_groups of scape_amd/csrc/report.inc).
+k_rep_perm_groups of scape_amd/csrc/perm.inc).
 
 The oracle below restates the command's contract in exact arithmetic and imports nothing from scape_amd: Python ints for
 keys, ranks, labels and sums, and - for the statistics - integers over a common denominator: with D = the product of the

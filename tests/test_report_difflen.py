@@ -1,6 +1,6 @@
 """`scape diff_pa_len`: the permutation test of a record's mean pA position (3'UTR length) between two cell populations
 (scape_amd/report.py, section diff_pa_len; kernel k_rep_perm_len and entry point scape_hip_report_perm_len of
-scape_amd/csrc/report.inc).
+scape_amd/csrc/perm.inc).
 
 The contract.  Populations, tested columns (population 1's, then population 2's), kept rows (labels < K with a read in a
 tested column, in label order) and permutations (permutation p >= 1 gives population 1 the n1 positions with the smallest
@@ -497,7 +497,7 @@ def test_batch_and_chunk_invariance(tmp_path, monkeypatch):
     assert calls["masks"] == [(1, 999)] and calls["len"] > 5
     n_batches = calls["len"]
     calls.update(masks=[], len=0)
-    monkeypatch.setattr(report, "MAX_PERM_BYTES", 9 * 8 * 300)           # 9 words of 64 positions: 300 permutations
+    monkeypatch.setattr(report, "MAX_PERM_BYTES", (9 + 1) * 8 * 300)     # 9 words of 64 positions, 1 key bound: 300 permutations
     assert _command(tmp_path, path, "res.gene.pkl", "A", None, 999, 1) == big
     assert calls["len"] == 4 * n_batches and calls["masks"][:4] == [(1, 300), (301, 300), (601, 300), (901, 99)]
     assert len(calls["masks"]) == 4 * n_batches

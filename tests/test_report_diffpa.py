@@ -1,5 +1,5 @@
 """`scape diff_pa`: the permutation test of pA usage between two cell populations (scape_amd/report.py, section diff_pa;
-kernels k_rep_perm_* of scape_amd/csrc/report.inc).
+kernels k_rep_perm_* of scape_amd/csrc/perm.inc).
 
 The oracle below restates the command's contract in exact arithmetic and imports nothing from scape_amd: Python ints
 for mix / key / the membership of every permutation / every sum, fractions.Fraction for the statistics S and d of the
@@ -423,7 +423,7 @@ def test_batch_and_chunk_invariance(tmp_path, monkeypatch):
     assert calls["masks"] == [(1, 999)] and calls["test"] > 5
     n_batches = calls["test"]
     calls.update(masks=[], test=0)
-    monkeypatch.setattr(report, "MAX_PERM_BYTES", 9 * 8 * 300)           # 9 words of 64 positions: 300 permutations
+    monkeypatch.setattr(report, "MAX_PERM_BYTES", (9 + 1) * 8 * 300)     # 9 words of 64 positions, 1 key bound: 300 permutations
     assert _command(tmp_path, path, "res.gene.pkl", "A", None, 999, 1) == big
     assert calls["test"] == 4 * n_batches and calls["masks"][:4] == [(1, 300), (301, 300), (601, 300), (901, 99)]
 

@@ -1,6 +1,6 @@
 """`--strata_file` of `scape diff_pa` / `scape diff_pa_len`: cell labels permuted within strata only (scape_amd/report.py;
 kernel k_rep_perm_mask_strata and the entry points scape_hip_report_perm_masks_strata / _perm_bits_get of
-scape_amd/csrc/report.inc; include/scape_hip.h states the labelling scheme).
+scape_amd/csrc/perm.inc; include/scape_hip.h states the labelling scheme).
 
 The scheme, restated here in plain Python ints (nothing below imports from scape_amd outside the tests that run it):
 population 1's positions first, then population 2's, each ordered by stratum (first appearance among the rows of the
@@ -16,7 +16,8 @@ EQUAL lo; the generator seeds were picked on a CPU so that this holds, and no ca
 Sizes: the device takes a stratum of up to 64 cells with one key per lane of a wave, one of 65..256 cells with four keys
 per lane, a larger one with the workgroup's radix select, whose number of passes grows with the stratum (about
 log256(cells) + 1); a stratum without a cell of one population takes none of them.  The layouts below put strata on
-both sides of 64 and of 256, and one of 3,000 cells (the only way to more than two select passes)."""
+both sides of 64 and of 256, and one of 3,000 cells; test_bits_behind_deep_selects pins permutations whose select needs
+three and four passes."""
 import csv
 import functools
 import io
@@ -255,6 +256,60 @@ def test_bits_at_the_path_thresholds(name):
         chk(_masks_strata(ctx, m1, m2, 1, n_perm, 3), "perm_masks_strata")
         bad = [p for p in range(1, n_perm + 1) if _bits(ctx, p - 1, n) != words_of(pick(3, p, n1, n), n)]
         print(name, "permutations with other bits:", bad)
+        assert not bad
+    finally:
+        ctx.lib.scape_hip_report_free(ctx.h)
+
+
+def select_passes(keys, rank):
+    """histogram passes of the device's radix select for the key of that rank: it stops after the first byte at which the
+    key is alone in its bin, so 1 + the larger number of leading bytes it shares with either sorted neighbour"""
+    ks = sorted(keys)
+
+    def shared(a, b):
+        n = 0
+        while n < 8 and (a >> (56 - 8 * n)) & 255 == (b >> (56 - 8 * n)) & 255:
+            n += 1
+        return n
+    return 1 + max(shared(ks[rank], ks[i]) for i in (rank - 1, rank + 1) if 0 <= i < len(ks))
+
+
+# (p_first, p_count, the labelling whose select goes deep, its passes): seed 3, 1,500 + 2,500 cells, freely or within
+# the two strata below.  Found on a CPU with select_passes: of the free permutations 1 .. 200,000, 188,055 settle in 2
+# passes, 11,894 need 3 and 51 need 4, the first of them 27 and 3,130; within the strata both chunks settle in 2, and
+# 17 is the first permutation with a stratum that needs 3
+DEEP_CHUNKS = ((25, 4, "free", 3), (3128, 4, "free", 4), (17, 4, "strata", 3))
+DEEP_STRATA = ([700, 800], [1200, 1300])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("p_first,p_count,deep,n_passes", DEEP_CHUNKS)
+def test_bits_behind_deep_selects(p_first, p_count, deep, n_passes):
+    """the one radix select past its second histogram pass: every permutation of the chunk, from
+    scape_hip_report_perm_masks and from scape_hip_report_perm_masks_strata with two strata, against the Python
+    membership; the chunk is first shown to hold a select of n_passes passes"""
+    from scape_amd import _lib
+    from scape_amd._lib import check as chk
+    seed, (m1, m2) = 3, DEEP_STRATA
+    n1, n = sum(m1), sum(m1) + sum(m2)
+    assert (n1, n) == (1500, 4000)
+    perms = range(p_first, p_first + p_count)
+    keys = {p: [rc.key(seed, p, j) for j in range(n)] for p in perms}
+    free = [select_passes(keys[p], n1 - 1) for p in perms]
+    cells = [list(range(0, 700)) + list(range(1500, 2700)), list(range(700, 1500)) + list(range(2700, 4000))]
+    strata = [max(select_passes([keys[p][j] for j in pos], a - 1) for pos, a in zip(cells, m1)) for p in perms]
+    print("chunk", p_first, p_count, "select passes, free:", free, "largest per stratum:", strata)
+    assert max(free if deep == "free" else strata) >= n_passes
+    pick = stratified_members(m1, m2)
+    ctx = _lib.default_context(None)
+    try:
+        chk(ctx.lib.scape_hip_report_perm_masks(ctx.h, n1, n - n1, p_first, p_count, seed), "perm_masks")
+        bad = [p for p in perms if _bits(ctx, p - p_first, n) != words_of(rc.members(seed, p, n1, n), n)]
+        print("free permutations with other bits:", bad)
+        assert not bad
+        chk(_masks_strata(ctx, m1, m2, p_first, p_count, seed), "perm_masks_strata")
+        bad = [p for p in perms if _bits(ctx, p - p_first, n) != words_of(pick(seed, p, n1, n), n)]
+        print("stratified permutations with other bits:", bad)
         assert not bad
     finally:
         ctx.lib.scape_hip_report_free(ctx.h)
