@@ -28,7 +28,7 @@
 #ifndef MT_DEEP
 #define MT_DEEP 2                     // register stages of the M-step's loads in passes of <= 32 jobs (measured: 3 and 4 change nothing, big calls or small)
 #endif
-// device counters (unsigned long long each): [0] rounds, [1] slab elements (v1), [2] z elements, [3] unused, then
+// device counters (unsigned long long each): [0] rounds, [1] unused, [2] z elements, [3] unused, then
 // 64-way sharded: slab elements, executed job-rounds, and the M-step's own byte tallies
 #define CNT_SLAB 4
 #define CNT_EXEC (4 + 64)

@@ -11,7 +11,6 @@
 // in lock-step rounds (em_lockstep.inc): k2_estep, one wavefront per job (responsibilities, weights, ELBO),
 // then k2_mstep, one workgroup per (UTR, 64-row tensor tile), which multiplies the tile with the v vectors of
 // every job whose window covers it on the f64 matrix cores and keeps per-(job, tile) first arg-maxes.
-// k_em below is the round-1 job-at-a-time kernel (SCAPE_HIP_EM=v1, A/B runs only).
 // All arithmetic is f64 (the reference's finite -inf sentinel overflows f32).
 #include <hip/hip_runtime.h>
 
@@ -25,6 +24,7 @@
 #include <string>
 #include <type_traits>
 #include <chrono>
+#include <utility>
 #include <vector>
 
 #include "scape_hip.h"
@@ -33,8 +33,6 @@
 #define PI_REF 3.141592653589793  // taichi_core.py:9
 #define PITCH 16                  // row pitch granule (f64 elements) -> 128-B aligned rows
 #define TILE_ROWS 64               // tensor rows per M-step tile (= MT_ROWS of em_lockstep.inc)
-#define EM_THREADS 256
-#define EM_WAVES (EM_THREADS / 64)
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -259,12 +257,6 @@ __device__ __forceinline__ double d_np_sum(const double (&a)[CMAX], int C) {
         return res;
     }
     return 0.0;
-}
-
-__device__ __forceinline__ double d_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;  // valid in lane 0
 }
 
 // ------------------------------------------------------------------------------------------
@@ -647,286 +639,6 @@ __global__ __launch_bounds__(256, 5) void k_phase_b(const UtrDesc *__restrict__ 
     }
 }
 
-#ifdef SCAPE_HIP_TOOLS   // the round-1 job-at-a-time EM kernel: A/B builds only (-DSCAPE_HIP_TOOLS), not in the product library
-// ------------------------------------------------------------------------------------------
-// EM: one workgroup per job (UTR, K, restart).  apa_core.py:714-779.
-// Column c of log_zmat is never stored: it is snap_lw[c] + M[snap_ia[c]][snap_ib[c]][:] where
-// the snapshot is what cal_z_k used the last time column c was refreshed (stale-column E-step,
-// apa_core.py:731).  Per round: one pass over the bins (responsibilities, weight sums, ELBO
-// terms, the Z[:,k]*cnt vector into LDS), then the grid arg-max over the (alpha, beta) window.
-// ------------------------------------------------------------------------------------------
-template <int CMAX>
-__global__ __launch_bounds__(EM_THREADS) void k_em(
-    const UtrDesc *__restrict__ descs, DevParams P, const double *__restrict__ cnt,
-    const double *__restrict__ M, int kmax, const int32_t *__restrict__ job_utr,
-    const int32_t *__restrict__ job_K, const int32_t *__restrict__ job_fixed,
-    const int32_t *__restrict__ a_in, const int32_t *__restrict__ b_in,
-    const double *__restrict__ ws_in, const int8_t *__restrict__ k_arr,
-    int32_t *__restrict__ a_out, int32_t *__restrict__ b_out, double *__restrict__ ws_out,
-    double *__restrict__ bic_out, int32_t *__restrict__ nlb_out, double *__restrict__ lb_out,
-    unsigned long long *__restrict__ counters) {
-    extern __shared__ double vk[];  // [Np] Z[:,k] * cnt of the component being updated
-    __shared__ double s_red[EM_WAVES][CMAX + 3];
-    __shared__ double s_tot[CMAX + 3];
-    __shared__ double s_ws[CMAX], s_snaplw[CMAX];
-    __shared__ int s_ia[CMAX], s_ib[CMAX], s_sia[CMAX], s_sib[CMAX];
-    __shared__ double s_best[EM_WAVES];
-    __shared__ int s_bestr[EM_WAVES];
-    __shared__ int s_flag;
-
-    const int job = blockIdx.x;
-    const UtrDesc d = descs[job_utr[job]];
-    const int K = job_K[job], C = K + 1;
-    const bool fixed = job_fixed[job] != 0;
-    const int B = P.B, nround = P.nround;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int N = d.N, Np = d.Np;
-    const double *Mu = M + (size_t)d.m_off;
-    const double *cu = cnt + d.bin_off;
-    const int8_t *ka = k_arr + (size_t)job * nround;
-    double *lb_arr = lb_out + (size_t)job * nround;
-
-    if (tid < C) {
-        s_ws[tid] = ws_in[(size_t)job * (kmax + 1) + tid];
-        s_snaplw[tid] = d_logw(s_ws[tid]);                                   // :722-724
-        if (tid < K) {
-            s_ia[tid] = s_sia[tid] = a_in[(size_t)job * kmax + tid];
-            s_ib[tid] = s_sib[tid] = b_in[(size_t)job * kmax + tid];
-        }
-    }
-    __syncthreads();
-
-    double lb = SENT, ell_last = 0.0;
-    int n_lb = 0;
-    unsigned long long slab_rows = 0;
-
-    for (int it = 0; it < nround; ++it) {
-        const int k = ka[it];
-        if (tid == 0) {  // cal_z_k(para, k_arr[i]) (:731): refresh the snapshot of column k
-            s_snaplw[k] = d_logw(s_ws[k]);
-            if (k < K) {
-                s_sia[k] = s_ia[k];
-                s_sib[k] = s_ib[k];
-            }
-        }
-        __syncthreads();
-
-        size_t roff[CMAX];
-        double slw[CMAX];
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            roff[c] = (c < K) ? ((size_t)s_sia[c] * B + s_sib[c]) * Np : 0;
-            slw[c] = (c < C) ? s_snaplw[c] : 0.0;
-        }
-
-        // ---- E pass (norm_z :490-495, mstep head :525-529, maximize_ws numerators :499,
-        //      exp_log_lik :570-573, entropy :560) ; second pass only if Z[:,k] += 1e-8 fires
-        double tot[CMAX + 3];
-        bool mod = false;
-        for (int pass = 0; pass < 2; ++pass) {
-            double wsum[CMAX];
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) wsum[c] = 0.0;
-            double sumk = 0.0, ell = 0.0, ent = 0.0;
-            for (int n = tid; n < Np; n += EM_THREADS) {
-                double vkn = 0.0;
-                if (n < N) {
-                    const double cn = cu[n];
-                    double lz[CMAX], z[CMAX];
-                    double mx = 0.0;
-#pragma unroll
-                    for (int c = 0; c < CMAX; ++c) {
-                        if (c < C) {
-                            lz[c] = (c < K) ? slw[c] + Mu[roff[c] + n] : slw[c] + d.unif_ll;
-                            mx = (c == 0 || lz[c] > mx) ? lz[c] : mx;
-                        } else {
-                            lz[c] = 0.0;
-                        }
-                    }
-#pragma unroll
-                    for (int c = 0; c < CMAX; ++c) z[c] = (c < C) ? exp((lz[c] - mx) * cn) : 0.0;
-                    const double s = d_np_sum<CMAX>(z, C);
-                    double zk = 0.0;
-#pragma unroll
-                    for (int c = 0; c < CMAX; ++c) {
-                        z[c] = z[c] / s;
-                        if (c == k) {
-                            sumk += z[c];
-                            if (mod) z[c] += 1e-8;
-                            zk = z[c];
-                        }
-                    }
-                    const double s2 = d_np_sum<CMAX>(z, C);
-                    double e[CMAX];
-#pragma unroll
-                    for (int c = 0; c < CMAX; ++c) {
-                        if (c < C) {
-                            wsum[c] += cn * z[c];
-                            if (z[c] != 0.0) ell += (z[c] * cn) * lz[c];
-                            const double pk = z[c] / s2;
-                            e[c] = (pk > 0.0) ? -pk * log(pk) : 0.0;
-                        } else {
-                            e[c] = 0.0;
-                        }
-                    }
-                    ent += cn * d_np_sum<CMAX>(e, C);
-                    vkn = zk * cn;
-                }
-                vk[n] = vkn;
-            }
-            // block reduction (fixed order: lane tree, then waves 0..3)
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) {
-                const double v = d_wave_sum(wsum[c]);
-                if (lane == 0) s_red[wave][c] = v;
-            }
-            {
-                double v = d_wave_sum(sumk);
-                if (lane == 0) s_red[wave][CMAX] = v;
-                v = d_wave_sum(ell);
-                if (lane == 0) s_red[wave][CMAX + 1] = v;
-                v = d_wave_sum(ent);
-                if (lane == 0) s_red[wave][CMAX + 2] = v;
-            }
-            __syncthreads();
-            if (tid < CMAX + 3) {
-                double v = 0.0;
-                for (int w = 0; w < EM_WAVES; ++w) v += s_red[w][tid];
-                s_tot[tid] = v;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int c = 0; c < CMAX + 3; ++c) tot[c] = s_tot[c];
-            if (pass == 0 && tot[CMAX] < 1e-8) {
-                mod = true;  // redo the pass with Z[:,k] += 1e-8 (apa_core.py:528-529)
-                __syncthreads();
-                continue;
-            }
-            break;
-        }
-
-        // ---- maximize_ws (:498-505), all threads redundantly (uniform) ----------------------
-        double wn[CMAX];
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) wn[c] = (c < C) ? tot[c] : 0.0;
-        {
-            const double s = d_np_sum<CMAX>(wn, C);
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) wn[c] = wn[c] / s;
-            double wK = 0.0;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c == K) wK = wn[c];
-            if (wK > P.max_unif_ws) {
-                const double sk = d_np_sum<CMAX>(wn, K);
-#pragma unroll
-                for (int c = 0; c < CMAX; ++c) {
-                    if (c < K) wn[c] = (1 - P.max_unif_ws) * wn[c] / sk;
-                    if (c == K) wn[c] = P.max_unif_ws;
-                }
-            }
-        }
-        double wk_new = 0.0;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c)
-            if (c == k) wk_new = wn[c];
-        if (tid < CMAX) {
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c == tid && c < C) s_ws[c] = wn[c];
-        }
-
-        // ---- max_alpha_beta (:507-523): first arg-max over the inclusive theta window --------
-        if (!fixed && k < K) {
-            const int lo = (k == 0) ? 0 : s_ia[k - 1];
-            const int hi = (k == K - 1) ? d.T - 1 : s_ia[k + 1];
-            const double lw = d_logw(wk_new);
-            const int r0 = lo * B, r1 = (hi + 1) * B;
-            double best = -INFINITY;
-            int best_r = r0;
-            const int nq = Np >> 1;
-            const double2 *vk2 = reinterpret_cast<const double2 *>(vk);
-            for (int rr = r0 + wave; rr < r1; rr += EM_WAVES) {
-                const double2 *row = reinterpret_cast<const double2 *>(Mu + (size_t)rr * Np);
-                double acc0 = 0.0, acc1 = 0.0;
-                for (int q = lane; q < nq; q += 64) {
-                    const double2 m = row[q];
-                    const double2 v = vk2[q];
-                    acc0 += (lw + m.x) * v.x;
-                    acc1 += (lw + m.y) * v.y;
-                }
-                const double sc = d_wave_sum(acc0 + acc1);
-                if (lane == 0 && sc > best) {
-                    best = sc;
-                    best_r = rr;
-                }
-            }
-            if (lane == 0) {
-                s_best[wave] = best;
-                s_bestr[wave] = best_r;
-            }
-            slab_rows += (unsigned long long)(r1 - r0);
-            __syncthreads();
-            if (tid == 0) {
-                double bb = s_best[0];
-                int br = s_bestr[0];
-                for (int w = 1; w < EM_WAVES; ++w)
-                    if (s_best[w] > bb || (s_best[w] == bb && s_bestr[w] < br)) {
-                        bb = s_best[w];
-                        br = s_bestr[w];
-                    }
-                if (lo <= hi) {
-                    s_ia[k] = br / B;
-                    s_ib[k] = br - (br / B) * B;
-                }
-            }
-        }
-
-        // ---- elbo (:559-561) and the stopping rule (:743-746), uniform across threads --------
-        const double lb_new = tot[CMAX + 1] + tot[CMAX + 2];
-        ell_last = tot[CMAX + 1];
-        if (tid == 0) lb_arr[n_lb] = lb_new;
-        ++n_lb;
-        const bool stop = fabs(lb_new - lb) < fabs(1e-6 * lb);
-        lb = lb_new;
-        __syncthreads();
-        if (stop) break;
-    }
-
-    // ---- cal_bic (:702-706), sort by alpha (:768-772), outputs -------------------------------
-    if (tid == 0) {
-        bic_out[job] = d_bic(ell_last, K, N);
-        nlb_out[job] = n_lb;
-        int idx[CMAX];
-        for (int i = 0; i < K; ++i) idx[i] = i;
-        for (int i = 1; i < K; ++i) {  // stable insertion sort == numpy argsort for K <= 16
-            const int v = idx[i];
-            int j = i - 1;
-            while (j >= 0 && s_ia[idx[j]] > s_ia[v]) {
-                idx[j + 1] = idx[j];
-                --j;
-            }
-            idx[j + 1] = v;
-        }
-        for (int i = 0; i < K; ++i) {
-            a_out[(size_t)job * kmax + i] = s_ia[idx[i]];
-            b_out[(size_t)job * kmax + i] = s_ib[idx[i]];
-            ws_out[(size_t)job * (kmax + 1) + i] = s_ws[idx[i]];
-        }
-        ws_out[(size_t)job * (kmax + 1) + K] = s_ws[K];
-        for (int i = K; i < kmax; ++i) {
-            a_out[(size_t)job * kmax + i] = -1;
-            b_out[(size_t)job * kmax + i] = -1;
-            ws_out[(size_t)job * (kmax + 1) + i + 1] = 0.0;
-        }
-        atomicAdd(&counters[0], (unsigned long long)n_lb);
-        atomicAdd(&counters[1], slab_rows * (unsigned long long)N);
-        atomicAdd(&counters[2], (unsigned long long)n_lb * (unsigned long long)N * (unsigned long long)C);
-    }
-}
-
-#endif
-
 #include "phase_b_split.inc"
 #include "em_lockstep.inc"
 #include "mstep_ring.inc"
@@ -1036,11 +748,40 @@ struct EventPair {
 
 struct ReportState;   // report.inc
 
-#define N_COUNTERS (4 + 5 * 64 + 16 + 48)   // (+16: ESTEP_STAMPS, +48: M4_STAMPS tools builds) rounds, slab elements (v1), z elements, unused, then five 64-way sharded counters (em_lockstep.inc)
+// Device buffers of the lock-step EM (em_lockstep.inc): the per-job state the kernels see as an EmState, the index
+// tables of a call's plan (EmPlan) and the debug histogram of SCAPE_HIP_DEBUG.
+struct EmBufs {
+    DevBuf ia, ib, sia, sib, ws, slw, lb, ell, nlb, status, rd_k, rd_lo, rd_hi, rd_m, rd_n0, rd_n1, rd_lw, rd_sv, V, Vsuf,
+        voff, pt_score, pt_row, ptoff;             // one per EmState member, in its order
+    DevBuf ujoff, ujlist, active, elist, dbg;
+    int ensure(size_t nj, size_t kmax, size_t n_utr, size_t vtot, size_t pttot) {
+        return ia.ensure(nj * kmax * 4) || ib.ensure(nj * kmax * 4) || sia.ensure(nj * kmax * 4) || sib.ensure(nj * kmax * 4) ||
+               ws.ensure(nj * (kmax + 1) * 8) || slw.ensure(nj * (kmax + 1) * 8) || lb.ensure(nj * 8) || ell.ensure(nj * 8) ||
+               nlb.ensure(nj * 4) || status.ensure(nj * 4) || rd_k.ensure(nj * 4) || rd_lo.ensure(nj * 4) ||
+               rd_hi.ensure(nj * 4) || rd_m.ensure(nj * 4) || rd_n0.ensure(nj * 4) || rd_n1.ensure(nj * 4) ||
+               rd_lw.ensure(nj * 8) || rd_sv.ensure(nj * 8) || V.ensure(vtot * 8) || Vsuf.ensure((vtot / 16 + nj + 1) * 8) ||
+               voff.ensure(nj * 8) || pt_score.ensure(pttot * 8) || pt_row.ensure(pttot * 4) || ptoff.ensure(nj * 8) ||
+               ujoff.ensure((n_utr + 1) * 8) || ujlist.ensure(nj * 4) || active.ensure(n_utr * 4);
+    }
+    EmState state() const {
+        return EmState{ia.as<int32_t>(), ib.as<int32_t>(), sia.as<int32_t>(), sib.as<int32_t>(), ws.as<double>(), slw.as<double>(),
+                       lb.as<double>(), ell.as<double>(), nlb.as<int32_t>(), status.as<int32_t>(), rd_k.as<int32_t>(),
+                       rd_lo.as<int32_t>(), rd_hi.as<int32_t>(), rd_m.as<int32_t>(), rd_n0.as<int32_t>(), rd_n1.as<int32_t>(),
+                       rd_lw.as<double>(), rd_sv.as<double>(), V.as<double>(), Vsuf.as<double>(), voff.as<int64_t>(),
+                       pt_score.as<double>(), pt_row.as<int32_t>(), ptoff.as<int64_t>()};
+    }
+    void release() {
+        for (DevBuf *b : {&ia, &ib, &sia, &sib, &ws, &slw, &lb, &ell, &nlb, &status, &rd_k, &rd_lo, &rd_hi, &rd_m, &rd_n0, &rd_n1, &rd_lw,
+                          &rd_sv, &V, &Vsuf, &voff, &pt_score, &pt_row, &ptoff, &ujoff, &ujlist, &active, &elist, &dbg})
+            b->release();
+    }
+};
+
+#define N_COUNTERS (4 + 5 * 64 + 16 + 48)   // (+16: ESTEP_STAMPS, +48: M4_STAMPS tools builds) rounds, unused, z elements, unused, then five 64-way sharded counters (em_lockstep.inc)
 struct scape_hip_ctx {
     int device = 0;
     std::atomic<bool> busy{false};   // a handle serves one host thread at a time (scape_hip.h)
-    hipStream_t stream = nullptr, stream2 = nullptr;
+    hipStream_t stream = nullptr;
     char name[256] = {0};
     DevParams prm;
     bool loaded = false, built = false;
@@ -1059,9 +800,7 @@ struct scape_hip_ctx {
     DevBuf j_utr, j_K, j_fixed, j_a, j_b, j_ws, j_karr, j_ao, j_bo, j_wso, j_bic, j_nlb, j_lb, j_sel, j_lbsel;
     int last_em_jobs = 0;     // jobs of the last completed scape_hip_batch_em call (scape_hip_batch_em_fetch_lb)
     DevBuf l_utr, l_K, l_a, l_b, l_ws, l_labels;
-    // lock-step EM state (em_lockstep.inc)
-    DevBuf e_ia, e_ib, e_sia, e_sib, e_ws, e_slw, e_lb, e_ell, e_nlb, e_status, e_rdk, e_rdlo, e_rdhi, e_rdm,
-        e_rdlw, e_rdsv, e_rdn0, e_rdn1, e_V, e_Vsuf, e_voff, e_ptscore, e_ptrow, e_ptoff, e_ujoff, e_ujlist, e_active, e_elist;
+    EmBufs em;
     std::vector<EventPair> ev[6];
     double ms_acc[6] = {0, 0, 0, 0, 0, 0};
     int n_acc[6] = {0, 0, 0, 0, 0, 0};
@@ -1201,243 +940,259 @@ static int check_err_flag(scape_hip_ctx *c, const char *what) {
     return 0;
 }
 
-// host driver of the lock-step EM (kernels in em_lockstep.inc); job tables are already on the device
-static int em_lockstep(scape_hip_ctx *c, int n_jobs, int kmax, const int32_t *job_utr, const int32_t *job_fixed) {
-    const size_t nj = n_jobs;
-    const int nround = c->prm.nround, B = c->prm.B;
-    // host-side index tables: jobs grouped by UTR, ragged offsets of V and of the per-tile partials
-    std::vector<int64_t> ujoff(c->n_utr + 1, 0), voff(nj), ptoff(nj);
-    std::vector<int32_t> ujlist(nj);
-    for (size_t j = 0; j < nj; ++j) ujoff[job_utr[j] + 1]++;
-    for (int u = 0; u < c->n_utr; ++u) ujoff[u + 1] += ujoff[u];
+// ------------------------------------------------------------------------------------------
+// host driver of the lock-step EM (kernels in em_lockstep.inc, mstep_ring.inc, mstep_multi.inc)
+// ------------------------------------------------------------------------------------------
+// Column classes: the CMAX template arguments each kernel family is instantiated for.  A call runs in the first class
+// that holds its kmax + 1 columns.
+using EstepClasses = std::integer_sequence<int, 4, 8, 12, 16, 24, 32, 64>;   // k2_estep, k2_estep_all_rounds
+using WideClasses = std::integer_sequence<int, 4, 8, 12, 16>;                // k2_estep_cs
+using LabelClasses = std::integer_sequence<int, 8, 16, 32, 64>;              // k_labels
+
+template <int... Cs>
+constexpr int last_class(std::integer_sequence<int, Cs...>) {
+    int last = 0;
+    ((last = Cs), ...);
+    return last;
+}
+static_assert(last_class(EstepClasses{}) == SCAPE_MAX_K + 1 && last_class(LabelClasses{}) == SCAPE_MAX_K + 1,
+              "the largest class holds the largest kmax a call may have");
+constexpr int WIDE_MAX_COLUMNS = last_class(WideClasses{});
+
+// f(std::integral_constant<int, C>()) for the first class C >= columns; false if there is none
+template <int... Cs, typename F>
+static bool with_column_class(std::integer_sequence<int, Cs...>, int columns, F &&f) {
+    return ((columns <= Cs && (f(std::integral_constant<int, Cs>()), true)) || ...);
+}
+
+// Index tables of one EM call: jobs grouped by UTR, the UTRs and jobs in launch order, ragged offsets of the job vectors
+// and of the per-tile partials.  Host only.
+struct EmPlan {
+    std::vector<int64_t> ujoff, voff, ptoff;     // [n_utr + 1] first job of a UTR in ujlist; [n_jobs] offsets into V / pt_*
+    std::vector<int32_t> ujlist, active, elist;  // jobs by UTR; UTRs with jobs (M-step grid order); jobs in E-step order (may be empty: ujlist)
+    size_t vtot = 0, pttot = 0;
+    int tiles_max = 1, max_jobs_utr = 1;
+    bool any_m = false;                          // fixed-inference jobs (mstep_fixed) have no grid arg-max
+};
+
+static EmPlan em_plan(const std::vector<UtrDesc> &h_desc, int B, size_t nj, const int32_t *job_utr, const int32_t *job_fixed,
+                      bool size_order) {
+    EmPlan p;
+    const int n_utr = (int)h_desc.size();
+    p.ujoff.assign(n_utr + 1, 0);
+    p.ujlist.resize(nj);
+    for (size_t j = 0; j < nj; ++j) p.ujoff[job_utr[j] + 1]++;
+    for (int u = 0; u < n_utr; ++u) p.ujoff[u + 1] += p.ujoff[u];
     {
-        std::vector<int64_t> fill(ujoff.begin(), ujoff.end() - 1);
-        for (size_t j = 0; j < nj; ++j) ujlist[fill[job_utr[j]]++] = (int32_t)j;
+        std::vector<int64_t> fill(p.ujoff.begin(), p.ujoff.end() - 1);
+        for (size_t j = 0; j < nj; ++j) p.ujlist[fill[job_utr[j]]++] = (int32_t)j;
     }
     // UTRs that have at least one job in this call, in index order: the M-step grid runs over this list, so a call
     // that touches a few UTRs of a large resident batch (reference-stream mode) still uses every XCD
-    std::vector<int32_t> active;
-    for (int u = 0; u < c->n_utr; ++u)
-        if (ujoff[u + 1] > ujoff[u]) active.push_back(u);
+    for (int u = 0; u < n_utr; ++u)
+        if (p.ujoff[u + 1] > p.ujoff[u]) p.active.push_back(u);
     // Blocks are dealt round-robin over the 8 XCDs and the M-step gives XCD x the UTRs at positions x, x + 8, ... of this
     // list: sorted by tensor size, the 8 UTRs that are in flight side by side are of one size class (their tiles take
     // alike) and every XCD gets the same mix - in index order an XCD that drew the large UTRs finishes last while
     // the others idle.  Placement only: a UTR's results do not depend on where or next to what it runs.
-    const bool size_order = !getenv("SCAPE_HIP_NO_SIZE_ORDER") && !getenv("SCAPE_HIP_TWO_STREAMS");
     if (size_order)
-        std::stable_sort(active.begin(), active.end(), [&](int32_t a, int32_t b) {
-            const UtrDesc &da = c->h_desc[a], &db = c->h_desc[b];
+        std::stable_sort(p.active.begin(), p.active.end(), [&](int32_t a, int32_t b) {
+            const UtrDesc &da = h_desc[a], &db = h_desc[b];
             return (int64_t)da.T * da.Np > (int64_t)db.T * db.Np;
         });
-    const int n_active = (int)active.size();
-    int max_jobs_utr = 1;
-    for (int u : active) max_jobs_utr = std::max<int>(max_jobs_utr, (int)(ujoff[u + 1] - ujoff[u]));
-    int tiles_max = 1;
-    for (int u : active) tiles_max = std::max(tiles_max, (c->h_desc[u].T * B + MT_ROWS - 1) / MT_ROWS);
+    const int n_active = (int)p.active.size();
+    for (int u : p.active) {
+        p.max_jobs_utr = std::max<int>(p.max_jobs_utr, (int)(p.ujoff[u + 1] - p.ujoff[u]));
+        p.tiles_max = std::max(p.tiles_max, (h_desc[u].T * B + MT_ROWS - 1) / MT_ROWS);
+    }
+    p.voff.resize(nj);
+    p.ptoff.resize(nj);
+    for (size_t j = 0; j < nj; ++j) {
+        const UtrDesc &d = h_desc[job_utr[j]];
+        p.voff[j] = (int64_t)p.vtot;
+        p.ptoff[j] = (int64_t)p.pttot;
+        p.vtot += (size_t)d.Np;
+        p.pttot += (size_t)((d.T * B + MT_ROWS - 1) / MT_ROWS);
+        p.any_m = p.any_m || job_fixed[j] == 0;
+    }
+    // The E-step gives XCD x the x-th eighth of its job list: with the jobs of UTR active[x], active[x + 8], ... there,
+    // every XCD gets the same mix of sizes, and the v vectors a UTR's jobs write are read by the M-step tiles of the same
+    // UTR on the same XCD (L2; speed only).
+    if (size_order && n_active >= 8) {
+        p.elist.reserve(nj);
+        for (int x = 0; x < 8; ++x)
+            for (int k = x; k < n_active; k += 8)
+                for (int64_t q = p.ujoff[p.active[k]]; q < p.ujoff[p.active[k] + 1]; ++q) p.elist.push_back(p.ujlist[q]);
+    }
+    return p;
+}
+
+// the environment switches of the EM driver (diagnostics; none changes results: DESIGN.md section 7)
+struct EmSwitches {
+    bool size_order, debug, fine, mstep_v2, mstep_v3;
+    int split_maxtiles, wide_maxjobs;
+};
+static EmSwitches em_switches() {
+    const char *env_m = getenv("SCAPE_HIP_MSTEP"), *env_r = getenv("SCAPE_HIP_SPLIT_MAXTILES"), *env_w = getenv("SCAPE_HIP_WIDE_MAXJOBS");
+    EmSwitches s;
+    s.size_order = !getenv("SCAPE_HIP_NO_SIZE_ORDER");
+    s.debug = getenv("SCAPE_HIP_DEBUG") != nullptr;           // the tile / job histograms are k2 / k3 only
+    s.fine = getenv("SCAPE_HIP_ROUND_TIMING") != nullptr;
+    s.mstep_v2 = env_m && strcmp(env_m, "v2") == 0;
+    s.mstep_v3 = env_m && strcmp(env_m, "v3") == 0;
+    s.split_maxtiles = env_r ? atoi(env_r) : 1024;
+    s.wide_maxjobs = env_w ? atoi(env_w) : 1024;
+    return s;
+}
+
+struct EmKernels {
+    bool wide;          // E-step: 4 wavefronts per job (k2_estep_cs)
+    bool job_split;     // M-step: a tile's jobs cut into passes of 16 that separate workgroups take
+    bool ring_mstep;    // k3_mstep (LDS-DMA rings, mstep_ring.inc) instead of the register-staged k2_mstep
+    bool multi_mstep;   // k4_mstep (several tiles per workgroup, mstep_multi.inc) instead of k3_mstep
+};
+static int em_choose(const EmPlan &p, const EmSwitches &sw, int n_jobs, int kmax, EmKernels &k) {
     // Small calls (the ~100 jobs of one UTR, or of a few streams' current UTRs) leave most of the GPU idle and an
     // M-step round takes as long as ONE workgroup needs for its pass over a tile: the jobs of a tile are then cut
     // into passes of 16 that separate workgroups take (k2_mstep).  Every score is the same MFMA chain either way,
     // so a UTR's result does not depend on the size of the call it is part of.
-    const char *env_r = getenv("SCAPE_HIP_SPLIT_MAXTILES"), *env_w = getenv("SCAPE_HIP_WIDE_MAXJOBS");
-    const int split_maxtiles = env_r ? atoi(env_r) : 1024, wide_maxjobs = env_w ? atoi(env_w) : 1024;
-    const bool wide = n_jobs <= wide_maxjobs && kmax + 1 <= 16;   // E-step: 4 wavefronts per job (k2_estep_cs)
-    const bool job_split = (long long)n_active * tiles_max <= split_maxtiles;
-    // M-step kernel: k3_mstep (LDS-DMA rings, mstep_ring.inc) unless SCAPE_HIP_MSTEP=v2 asks for the register-staged
-    // k2_mstep (A/B runs; identical bits).  k3's DMA source offsets are 32-bit byte offsets from the start of the job vectors.
-    const bool debug_env = getenv("SCAPE_HIP_DEBUG") != nullptr;     // the tile / job histograms are k2 / k3 only
-    const char *env_m = getenv("SCAPE_HIP_MSTEP");
-    bool ring_mstep = !(env_m && strcmp(env_m, "v2") == 0);
-    constexpr int pt_rows = MT_ROWS;
-    size_t vtot = 0, pttot = 0;
-    for (size_t j = 0; j < nj; ++j) {
-        const UtrDesc &d = c->h_desc[job_utr[j]];
-        const int nt = (d.T * B + pt_rows - 1) / pt_rows;
-        voff[j] = (int64_t)vtot;
-        ptoff[j] = (int64_t)pttot;
-        vtot += (size_t)d.Np;
-        pttot += (size_t)nt;
-    }
-    if (c->e_ia.ensure(nj * kmax * 4) || c->e_ib.ensure(nj * kmax * 4) || c->e_sia.ensure(nj * kmax * 4) ||
-        c->e_sib.ensure(nj * kmax * 4) || c->e_ws.ensure(nj * (kmax + 1) * 8) || c->e_slw.ensure(nj * (kmax + 1) * 8) ||
-        c->e_lb.ensure(nj * 8) || c->e_ell.ensure(nj * 8) || c->e_nlb.ensure(nj * 4) || c->e_status.ensure(nj * 4) ||
-        c->e_rdk.ensure(nj * 4) || c->e_rdlo.ensure(nj * 4) || c->e_rdhi.ensure(nj * 4) || c->e_rdm.ensure(nj * 4) ||
-        c->e_rdlw.ensure(nj * 8) || c->e_rdsv.ensure(nj * 8) || c->e_rdn0.ensure(nj * 4) || c->e_rdn1.ensure(nj * 4) || c->e_V.ensure(vtot * 8) || c->e_Vsuf.ensure((vtot / 16 + nj + 1) * 8) || c->e_voff.ensure(nj * 8) ||
-        c->e_ptscore.ensure(pttot * 8) || c->e_ptrow.ensure(pttot * 4) || c->e_ptoff.ensure(nj * 8) ||
-        c->e_ujoff.ensure((c->n_utr + 1) * 8) || c->e_ujlist.ensure(nj * 4) || c->e_active.ensure((size_t)c->n_utr * 4))
-        return 1;
-    if (vtot * 8 >= ((size_t)1 << 31)) ring_mstep = false;
-    // k4_mstep (mstep_multi.inc): several tiles per workgroup, set-up and epilogue off the critical path - the kernel of
-    // wave-sized calls; calls with few live tiles keep k3_mstep with a tile's jobs cut into passes for several workgroups
-    const bool multi_mstep = ring_mstep && !job_split && !debug_env && pttot < ((size_t)1 << 31) && !(env_m && strcmp(env_m, "v3") == 0);
-    if (multi_mstep && M4_LDS_BYTES > 64 * 1024)
+    k.wide = n_jobs <= sw.wide_maxjobs && kmax + 1 <= WIDE_MAX_COLUMNS;
+    k.job_split = (long long)p.active.size() * p.tiles_max <= sw.split_maxtiles;
+    // k3_mstep unless SCAPE_HIP_MSTEP=v2 asks for k2_mstep (A/B runs; identical bits).  k3's DMA source offsets are
+    // 32-bit byte offsets from the start of the job vectors.
+    k.ring_mstep = !sw.mstep_v2 && p.vtot * 8 < ((size_t)1 << 31);
+    // k4_mstep: set-up and epilogue off the critical path - the kernel of wave-sized calls; calls with few live tiles
+    // keep k3_mstep with a tile's jobs cut into passes for several workgroups
+    k.multi_mstep = k.ring_mstep && !k.job_split && !sw.debug && p.pttot < ((size_t)1 << 31) && !sw.mstep_v3;
+    if (k.multi_mstep && M4_LDS_BYTES > 64 * 1024)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k4_mstep), hipFuncAttributeMaxDynamicSharedMemorySize, M4_LDS_BYTES));
-    if (ring_mstep && M3_LDS_BYTES > 64 * 1024)   // per device; a few microseconds
+    if (k.ring_mstep && M3_LDS_BYTES > 64 * 1024)   // per device; a few microseconds
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k3_mstep), hipFuncAttributeMaxDynamicSharedMemorySize, M3_LDS_BYTES));
-    // The E-step gives XCD x the x-th eighth of its job list: with the jobs of UTR active[x], active[x + 8], ... there,
-    // every XCD gets the same mix of sizes, and the v vectors a UTR's jobs write are read by the M-step tiles of the same
-    // UTR on the same XCD (L2; speed only).
-    std::vector<int32_t> elist;
-    if (size_order && n_active >= 8) {
-        elist.reserve(nj);
-        for (int x = 0; x < 8; ++x)
-            for (int k = x; k < n_active; k += 8)
-                for (int64_t q = ujoff[active[k]]; q < ujoff[active[k] + 1]; ++q) elist.push_back(ujlist[q]);
-        if (c->e_elist.ensure(nj * 4)) return 1;
-        HIPCHK(hipMemcpyAsync(c->e_elist.p, elist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+static int em_upload(scape_hip_ctx *c, const EmPlan &p, size_t nj, int kmax) {
+    EmBufs &e = c->em;
+    if (e.ensure(nj, kmax, c->n_utr, p.vtot, p.pttot)) return 1;
+    if (!p.elist.empty()) {
+        if (e.elist.ensure(nj * 4)) return 1;
+        HIPCHK(hipMemcpyAsync(e.elist.p, p.elist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
     }
-    if (n_active) HIPCHK(hipMemcpyAsync(c->e_active.p, active.data(), (size_t)n_active * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->e_voff.p, voff.data(), nj * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->e_ptoff.p, ptoff.data(), nj * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->e_ujoff.p, ujoff.data(), (c->n_utr + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->e_ujlist.p, ujlist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));  // the host vectors go out of scope
-    EmState S;
-    S.ia = c->e_ia.as<int32_t>();
-    S.ib = c->e_ib.as<int32_t>();
-    S.sia = c->e_sia.as<int32_t>();
-    S.sib = c->e_sib.as<int32_t>();
-    S.ws = c->e_ws.as<double>();
-    S.slw = c->e_slw.as<double>();
-    S.lb = c->e_lb.as<double>();
-    S.ell = c->e_ell.as<double>();
-    S.nlb = c->e_nlb.as<int32_t>();
-    S.status = c->e_status.as<int32_t>();
-    S.rd_k = c->e_rdk.as<int32_t>();
-    S.rd_lo = c->e_rdlo.as<int32_t>();
-    S.rd_hi = c->e_rdhi.as<int32_t>();
-    S.rd_m = c->e_rdm.as<int32_t>();
-    S.rd_lw = c->e_rdlw.as<double>();
-    S.rd_sv = c->e_rdsv.as<double>();
-    S.rd_n0 = c->e_rdn0.as<int32_t>();
-    S.rd_n1 = c->e_rdn1.as<int32_t>();
-    S.V = c->e_V.as<double>();
-    S.Vsuf = c->e_Vsuf.as<double>();
-    S.voff = c->e_voff.as<int64_t>();
-    S.pt_score = c->e_ptscore.as<double>();
-    S.pt_row = c->e_ptrow.as<int32_t>();
-    S.ptoff = c->e_ptoff.as<int64_t>();
-    unsigned long long *dbg = nullptr;
-    const bool debug = getenv("SCAPE_HIP_DEBUG") != nullptr;
-    if (debug) {
-        HIPCHK(hipMalloc((void **)&dbg, 24 * sizeof(unsigned long long)));
+    if (!p.active.empty())
+        HIPCHK(hipMemcpyAsync(e.active.p, p.active.data(), p.active.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.voff.p, p.voff.data(), nj * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.ptoff.p, p.ptoff.data(), nj * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.ujoff.p, p.ujoff.data(), p.ujoff.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.ujlist.p, p.ujlist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // the host vectors are pageable: the copies have left them now
+    return 0;
+}
+
+// One E-step launch.  The three kernels share their arguments up to the round number, which k2_estep_all_rounds
+// (it loops over the rounds itself) does not take.
+template <typename Kernel, typename... Round>
+static void launch_estep(scape_hip_ctx *c, Kernel kernel, unsigned threads, const EmState &S, int kmax, const int32_t *job_list,
+                         int n_jobs, Round... round) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(((n_jobs + 7) / 8) * 8)), dim3(threads), 0, c->stream, c->d_desc.as<UtrDesc>(),
+                       c->prm, c->d_cnt.as<double>(), c->d_M.as<double>(), kmax, c->j_utr.as<int32_t>(), c->j_K.as<int32_t>(),
+                       c->j_fixed.as<int32_t>(), c->j_a.as<int32_t>(), c->j_b.as<int32_t>(), c->j_ws.as<double>(),
+                       c->j_karr.as<int8_t>(), S, c->j_ao.as<int32_t>(), c->j_bo.as<int32_t>(), c->j_wso.as<double>(),
+                       c->j_bic.as<double>(), c->j_nlb.as<int32_t>(), c->j_lb.as<double>(),
+                       c->d_counters.as<unsigned long long>(), round..., job_list, n_jobs);
+}
+
+// One M-step launch.  `extent` is the second factor of the grid (tiles, or k4_mstep's tile groups, of the largest UTR);
+// `tail` are the two arguments k2_mstep / k3_mstep take beyond k4_mstep's.
+template <typename Kernel, typename... Tail>
+static void launch_mstep(scape_hip_ctx *c, Kernel kernel, unsigned grid_y, unsigned threads, size_t lds, const EmState &S,
+                         int n_active, int extent, Tail... tail) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(((n_active + 7) / 8) * 8 * extent), grid_y), dim3(threads), lds, c->stream,
+                       c->d_desc.as<UtrDesc>(), c->prm, c->d_M.as<double>(), c->em.active.as<int32_t>(), n_active, extent,
+                       c->em.ujoff.as<int64_t>(), c->em.ujlist.as<int32_t>(), S.V, S.Vsuf, S.voff, S.rd_m, S.rd_lo, S.rd_hi,
+                       S.rd_lw, S.rd_sv, S.rd_n0, S.rd_n1, S.ptoff, S.pt_score, S.pt_row, c->d_tile_nend.as<int32_t>(),
+                       c->d_counters.as<unsigned long long>(), tail...);
+}
+
+// SCAPE_HIP_DEBUG: what the M-step of round r did, on stderr
+static int em_debug_round(scape_hip_ctx *c, int r, int nround) {
+    unsigned long long *dbg = c->em.dbg.as<unsigned long long>();
+    if (r < nround) {      // cumulative tensor bytes the M-step has asked for (its own tally), per round
+        unsigned long long shard[64], tb = 0;
+        HIPCHK(hipMemcpy(shard, c->d_counters.as<unsigned long long>() + CNT_MSTEP_TENSOR, sizeof(shard), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 64; ++i) tb += shard[i];
+        fprintf(stderr, "[em bytes %d] %llu\n", r, tb);
+    }
+    if (r == 0 || r == 10 || r == 25 || r == nround - 1) {
+        unsigned long long h[24];
+        HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+        // k3_mstep only: k-steps x jobs if every job stopped at its own support / as run (16-job groups over the union)
+        fprintf(stderr, "[em round %d] job-halfchunks own-support %llu, union %llu, padded to groups %llu; sorted-by-n1 groups %llu\n", r, h[16], h[17], h[18], h[19]);
+        fprintf(stderr, "[em round %d] tiles %llu active %llu sum_cnt %llu passes %llu | G-hist:", r, h[0], h[1], h[2], h[3]);
+        for (int i = 4; i < 16; ++i) fprintf(stderr, " %llu", h[i]);
+        fprintf(stderr, "\n");
         HIPCHK(hipMemsetAsync(dbg, 0, 24 * sizeof(unsigned long long), c->stream));
     }
-    const bool fine = getenv("SCAPE_HIP_ROUND_TIMING") != nullptr;
-    bool any_m = false;   // fixed-inference jobs (mstep_fixed) have no grid arg-max
-    for (size_t j = 0; j < nj && !any_m; ++j) any_m = job_fixed[j] == 0;
-    // Two halves of the UTRs advance on two streams: the E-step is f64-VALU work, the M-step an HBM stream,
-    // so one half's E-step overlaps the other half's M-step.  (Per-kernel event timing and the debug
-    // counters use a single stream.)
-    // Measured (512 UTRs x 2k reads): no gain - the M-step needs 256 VGPRs x 2 waves/SIMD to stream at full
-    // rate, which leaves no room for E-step waves on the same SIMD - so it is off unless requested.
-    const bool split = any_m && !fine && !debug && c->n_utr >= 16 && n_jobs >= 2048 && getenv("SCAPE_HIP_TWO_STREAMS");
-    const int n_grp = split ? 2 : 1;
-    // groups are halves of the ACTIVE list; g_u0 holds the UTR index bounds of each half for the job ranges
-    const int a_half = split ? n_active / 2 : n_active;
-    int g_a0[3] = {0, a_half, n_active};
-    int g_u0[3] = {0, (split && a_half < n_active) ? active[a_half] : c->n_utr, c->n_utr};
-    hipStream_t g_stream[2] = {c->stream, c->stream2};
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    if (split) {
-        HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(ev_fork, c->stream));
-        HIPCHK(hipStreamWaitEvent(c->stream2, ev_fork, 0));
+    return 0;
+}
+
+// the rounds of one call: E-step, M-step, ... and a last E-step that finishes the jobs still running
+static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, const EmKernels &k, int n_jobs, int kmax) {
+    const EmState S = c->em.state();
+    const int nround = c->prm.nround, n_active = (int)p.active.size();
+    const int32_t *jl = p.elist.empty() ? c->em.ujlist.as<int32_t>() : c->em.elist.as<int32_t>();
+    unsigned long long *dbg = nullptr;
+    if (sw.debug) {
+        if (c->em.dbg.ensure(24 * sizeof(unsigned long long))) return 1;
+        dbg = c->em.dbg.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(dbg, 0, 24 * sizeof(unsigned long long), c->stream));
     }
-    if (!any_m) {
+    if (!p.any_m) {
         // only fixed-inference jobs (the ws-only re-fits of rm_component): all rounds in one launch
-        const int ngj = (int)nj;
-        const int32_t *jl = c->e_ujlist.as<int32_t>();
-        if (fine && ev_begin(c, 4)) return 1;
-#define LAUNCH_ALL(CM)                                                                                         \
-    hipLaunchKernelGGL(k2_estep_all_rounds<CM>, dim3((unsigned)(((ngj + 7) / 8) * 8)), dim3(64), 0, c->stream, \
-                       c->d_desc.as<UtrDesc>(), c->prm, c->d_cnt.as<double>(), c->d_M.as<double>(), kmax,      \
-                       c->j_utr.as<int32_t>(), c->j_K.as<int32_t>(), c->j_fixed.as<int32_t>(),                 \
-                       c->j_a.as<int32_t>(), c->j_b.as<int32_t>(), c->j_ws.as<double>(), c->j_karr.as<int8_t>(), \
-                       S, c->j_ao.as<int32_t>(), c->j_bo.as<int32_t>(), c->j_wso.as<double>(),                 \
-                       c->j_bic.as<double>(), c->j_nlb.as<int32_t>(), c->j_lb.as<double>(),                    \
-                       c->d_counters.as<unsigned long long>(), jl, ngj)
-        if (kmax + 1 <= 4) LAUNCH_ALL(4);
-        else if (kmax + 1 <= 8) LAUNCH_ALL(8);
-        else if (kmax + 1 <= 12) LAUNCH_ALL(12);
-        else if (kmax + 1 <= 16) LAUNCH_ALL(16);
-        else if (kmax + 1 <= 24) LAUNCH_ALL(24);
-        else if (kmax + 1 <= 32) LAUNCH_ALL(32);
-        else LAUNCH_ALL(64);
-#undef LAUNCH_ALL
+        if (sw.fine && ev_begin(c, 4)) return 1;
+        if (!with_column_class(EstepClasses{}, kmax + 1, [&](auto cm) {
+                launch_estep(c, k2_estep_all_rounds<decltype(cm)::value>, 64, S, kmax, c->em.ujlist.as<int32_t>(), n_jobs);
+            }))
+            return fail("no E-step kernel for kmax " + std::to_string(kmax));
         HIPCHK(hipGetLastError());
-        if (fine && ev_end(c, 4)) return 1;
-        if (dbg) (void)hipFree(dbg);
+        if (sw.fine && ev_end(c, 4)) return 1;
         return 0;
     }
+    // few live tiles: passes of 16 jobs, one workgroup each (gridDim.y covers the longest job list of a UTR)
+    const int jobs_per_pass = k.job_split ? 16 : MT_MAXJ;
+    const unsigned psplit = k.job_split ? (unsigned)std::min(64, (p.max_jobs_utr + 15) / 16) : 1u;
     unsigned long long executed_prev = 0;
     const int probe_mask = (n_jobs >= 8192) ? 7 : 3;
-    int rc = 0;
-    for (int r = 0; r <= nround && !rc; ++r) {
-        for (int g = 0; g < n_grp && !rc; ++g) {
-            const int u0 = g_u0[g], u1 = g_u0[g + 1];
-            const int64_t j0 = ujoff[u0], j1 = ujoff[u1];
-            const int ngj = (int)(j1 - j0);
-            if (ngj == 0) continue;
-            hipStream_t st = g_stream[g];
-            const int32_t *jl = elist.empty() ? c->e_ujlist.as<int32_t>() + j0 : c->e_elist.as<int32_t>();
-            if (fine && ev_begin(c, 4)) return 1;
-#define LAUNCH_E(KERNEL, CM, THREADS)                                                                          \
-    hipLaunchKernelGGL(KERNEL<CM>, dim3((unsigned)(((ngj + 7) / 8) * 8)), dim3(THREADS), 0, st,                \
-                       c->d_desc.as<UtrDesc>(), c->prm, c->d_cnt.as<double>(), c->d_M.as<double>(), kmax,      \
-                       c->j_utr.as<int32_t>(), c->j_K.as<int32_t>(), c->j_fixed.as<int32_t>(),                 \
-                       c->j_a.as<int32_t>(), c->j_b.as<int32_t>(), c->j_ws.as<double>(), c->j_karr.as<int8_t>(), \
-                       S, c->j_ao.as<int32_t>(), c->j_bo.as<int32_t>(), c->j_wso.as<double>(),                 \
-                       c->j_bic.as<double>(), c->j_nlb.as<int32_t>(), c->j_lb.as<double>(),                    \
-                       c->d_counters.as<unsigned long long>(), r, jl, ngj)
-            if (wide) {
-                if (kmax + 1 <= 4) LAUNCH_E(k2_estep_cs, 4, 256);
-                else if (kmax + 1 <= 8) LAUNCH_E(k2_estep_cs, 8, 256);
-                else if (kmax + 1 <= 12) LAUNCH_E(k2_estep_cs, 12, 256);
-                else LAUNCH_E(k2_estep_cs, 16, 256);
-            } else if (kmax + 1 <= 4) LAUNCH_E(k2_estep, 4, 64);
-            else if (kmax + 1 <= 8) LAUNCH_E(k2_estep, 8, 64);
-            else if (kmax + 1 <= 12) LAUNCH_E(k2_estep, 12, 64);
-            else if (kmax + 1 <= 16) LAUNCH_E(k2_estep, 16, 64);
-            else if (kmax + 1 <= 24) LAUNCH_E(k2_estep, 24, 64);
-            else if (kmax + 1 <= 32) LAUNCH_E(k2_estep, 32, 64);
-            else LAUNCH_E(k2_estep, 64, 64);      // K up to 63: the column arrays live in scratch there - slow, and rare (a re-run loop that keeps growing, apa_core.py:1023-1030)
-#undef LAUNCH_E
+    for (int r = 0; r <= nround; ++r) {
+        if (sw.fine && ev_begin(c, 4)) return 1;
+        // K up to 63: the column arrays of the 64-column class live in scratch - slow, and rare (a re-run loop that keeps
+        // growing, apa_core.py:1023-1030)
+        const bool launched =
+            k.wide ? with_column_class(WideClasses{}, kmax + 1, [&](auto cm) {
+                         launch_estep(c, k2_estep_cs<decltype(cm)::value>, 256, S, kmax, jl, n_jobs, r);
+                     })
+                   : with_column_class(EstepClasses{}, kmax + 1, [&](auto cm) {
+                         launch_estep(c, k2_estep<decltype(cm)::value>, 64, S, kmax, jl, n_jobs, r);
+                     });
+        if (!launched) return fail("no E-step kernel for kmax " + std::to_string(kmax));
+        HIPCHK(hipGetLastError());
+        if (sw.fine && ev_end(c, 4)) return 1;
+        if (r < nround) {
+            if (sw.fine && ev_begin(c, 5)) return 1;
+            if (k.multi_mstep)
+                launch_mstep(c, k4_mstep, 1u, 64 * M4_NW, M4_LDS_BYTES, S, n_active, (p.tiles_max + M4_TPW - 1) / M4_TPW);
+            else if (k.ring_mstep)
+                launch_mstep(c, k3_mstep, psplit, 256, M3_LDS_BYTES, S, n_active, p.tiles_max, jobs_per_pass, dbg);
+            else
+                launch_mstep(c, k2_mstep, psplit, 256, 0, S, n_active, p.tiles_max, jobs_per_pass, dbg);
+            c->h_traffic[3] += 1;
             HIPCHK(hipGetLastError());
-            if (fine && ev_end(c, 4)) return 1;
-            if (r < nround && any_m) {
-                if (fine && ev_begin(c, 5)) return 1;
-                const int nu = g_a0[g + 1] - g_a0[g];
-                // few live tiles: passes of 16 jobs, one workgroup each (gridDim.y covers the longest job list of a UTR)
-                const int jobs_per_pass = job_split ? 16 : MT_MAXJ;
-                const unsigned psplit = job_split ? (unsigned)std::min(64, (max_jobs_utr + 15) / 16) : 1u;
-#define MSTEP_ARGS c->d_desc.as<UtrDesc>(), c->prm, c->d_M.as<double>(), c->e_active.as<int32_t>() + g_a0[g], nu, tiles_max,           \
-                   c->e_ujoff.as<int64_t>(), c->e_ujlist.as<int32_t>(), S.V, S.Vsuf, S.voff, S.rd_m, S.rd_lo, S.rd_hi, S.rd_lw,  \
-                   S.rd_sv, S.rd_n0, S.rd_n1, S.ptoff, S.pt_score, S.pt_row, c->d_tile_nend.as<int32_t>(),                    \
-                   c->d_counters.as<unsigned long long>(), jobs_per_pass, dbg
-                if (multi_mstep) {
-                    const int groups_max = (tiles_max + M4_TPW - 1) / M4_TPW;
-                    hipLaunchKernelGGL(k4_mstep, dim3((unsigned)(((nu + 7) / 8) * 8 * groups_max)), dim3(64 * M4_NW), M4_LDS_BYTES, st,
-                                       c->d_desc.as<UtrDesc>(), c->prm, c->d_M.as<double>(), c->e_active.as<int32_t>() + g_a0[g], nu, groups_max,
-                                       c->e_ujoff.as<int64_t>(), c->e_ujlist.as<int32_t>(), S.V, S.Vsuf, S.voff, S.rd_m, S.rd_lo, S.rd_hi, S.rd_lw,
-                                       S.rd_sv, S.rd_n0, S.rd_n1, S.ptoff, S.pt_score, S.pt_row, c->d_tile_nend.as<int32_t>(),
-                                       c->d_counters.as<unsigned long long>());
-                } else if (ring_mstep)
-                    hipLaunchKernelGGL(k3_mstep, dim3((unsigned)(((nu + 7) / 8) * 8 * tiles_max), psplit), dim3(256), M3_LDS_BYTES, st, MSTEP_ARGS);
-                else
-                    hipLaunchKernelGGL(k2_mstep, dim3((unsigned)(((nu + 7) / 8) * 8 * tiles_max), psplit), dim3(256), 0, st, MSTEP_ARGS);
-#undef MSTEP_ARGS
-                c->h_traffic[3] += 1;
-                HIPCHK(hipGetLastError());
-                if (fine && ev_end(c, 5)) return 1;
-            }
+            if (sw.fine && ev_end(c, 5)) return 1;
         }
         // early exit: no job executed a round since the last probe -> every job has been finalised.  The probe waits for
         // the stream (a bubble of a few tens of microseconds): every 4 rounds for small calls, whose jobs all finish
         // early and whose rounds are short, every 8 for wave-sized ones, which run to the last round anyway
         if (r < nround && (r & probe_mask) == probe_mask) {
             unsigned long long executed = 0, shard[64];
-            if (split) HIPCHK(hipStreamSynchronize(c->stream2));
             HIPCHK(hipMemcpyAsync(shard, c->d_counters.as<unsigned long long>() + CNT_EXEC, sizeof(shard),
                                   hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -1445,32 +1200,18 @@ static int em_lockstep(scape_hip_ctx *c, int n_jobs, int kmax, const int32_t *jo
             if (executed == executed_prev) break;
             executed_prev = executed;
         }
-        if (debug && r < nround) {      // cumulative tensor bytes the M-step has asked for (its own tally), per round
-            unsigned long long shard[64], tb = 0;
-            HIPCHK(hipMemcpy(shard, c->d_counters.as<unsigned long long>() + CNT_MSTEP_TENSOR, sizeof(shard), hipMemcpyDeviceToHost));
-            for (int i = 0; i < 64; ++i) tb += shard[i];
-            fprintf(stderr, "[em bytes %d] %llu\n", r, tb);
-        }
-        if (debug && (r == 0 || r == 10 || r == 25 || r == nround - 1)) {
-            unsigned long long h[24];
-            HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-            // k3_mstep only: k-steps x jobs if every job stopped at its own support / as run (16-job groups over the union)
-            fprintf(stderr, "[em round %d] job-halfchunks own-support %llu, union %llu, padded to groups %llu; sorted-by-n1 groups %llu\n", r, h[16], h[17], h[18], h[19]);
-            fprintf(stderr, "[em round %d] tiles %llu active %llu sum_cnt %llu passes %llu | G-hist:", r, h[0], h[1], h[2], h[3]);
-            for (int i = 4; i < 16; ++i) fprintf(stderr, " %llu", h[i]);
-            fprintf(stderr, "\n");
-            HIPCHK(hipMemsetAsync(dbg, 0, 24 * sizeof(unsigned long long), c->stream));
-        }
+        if (sw.debug && em_debug_round(c, r, nround)) return 1;
     }
-    if (split) {
-        HIPCHK(hipEventRecord(ev_join, c->stream2));
-        HIPCHK(hipStreamWaitEvent(c->stream, ev_join, 0));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        (void)hipEventDestroy(ev_fork);
-        (void)hipEventDestroy(ev_join);
-    }
-    if (dbg) (void)hipFree(dbg);
     return 0;
+}
+
+// job tables are already on the device
+static int em_lockstep(scape_hip_ctx *c, int n_jobs, int kmax, const int32_t *job_utr, const int32_t *job_fixed) {
+    const EmSwitches sw = em_switches();
+    const EmPlan plan = em_plan(c->h_desc, c->prm.B, (size_t)n_jobs, job_utr, job_fixed, sw.size_order);
+    EmKernels kernels;
+    if (em_choose(plan, sw, n_jobs, kmax, kernels) || em_upload(c, plan, (size_t)n_jobs, kmax)) return 1;
+    return em_rounds(c, plan, sw, kernels, n_jobs, kmax);
 }
 
 static void report_release(scape_hip_ctx *c);   // report.inc
@@ -1498,7 +1239,6 @@ int scape_hip_create(int device, scape_hip_ctx **out) {
     HIPCHK(hipGetDeviceProperties(&prop, device));
     snprintf(c->name, sizeof(c->name), "%s (%s, %d CUs)", prop.name, prop.gcnArchName, prop.multiProcessorCount);
     HIPCHK(hipStreamCreate(&c->stream));
-    HIPCHK(hipStreamCreate(&c->stream2));
     if (c->d_counters.ensure(N_COUNTERS * sizeof(unsigned long long))) return 1;
     *out = c;
     return 0;
@@ -1516,11 +1256,9 @@ int scape_hip_batch_free(scape_hip_ctx *c) {
     DevBuf *all[] = {&c->d_tbi, &c->d_tbG, &c->d_tbpm, &c->d_mlog, &c->d_logbin, &c->d_tile_nend, &c->d_x, &c->d_l, &c->d_r, &c->d_pa, &c->d_cnt, &c->d_theta, &c->d_desc, &c->d_loglist,
                      &c->d_AT, &c->d_V, &c->d_M, &c->j_utr, &c->j_K, &c->j_fixed, &c->j_a, &c->j_b, &c->j_ws,
                      &c->j_karr, &c->j_ao, &c->j_bo, &c->j_wso, &c->j_bic, &c->j_nlb, &c->j_lb, &c->l_utr,
-                     &c->l_K, &c->l_a, &c->l_b, &c->l_ws, &c->l_labels, &c->e_ia, &c->e_ib, &c->e_sia, &c->e_sib,
-                     &c->e_ws, &c->e_slw, &c->e_lb, &c->e_ell, &c->e_nlb, &c->e_status, &c->e_rdk, &c->e_rdlo,
-                     &c->e_rdhi, &c->e_rdm, &c->e_rdlw, &c->e_rdsv, &c->e_rdn0, &c->e_rdn1, &c->e_V, &c->e_Vsuf, &c->e_voff, &c->e_ptscore,
-                     &c->e_ptrow, &c->e_ptoff, &c->e_ujoff, &c->e_ujlist, &c->e_active, &c->e_elist, &c->j_sel, &c->j_lbsel};
+                     &c->l_K, &c->l_a, &c->l_b, &c->l_ws, &c->l_labels, &c->j_sel, &c->j_lbsel};
     for (DevBuf *b : all) b->release();
+    c->em.release();
     c->last_em_jobs = 0;
     c->loaded = c->built = c->build_unchecked = false;
     c->n_utr = 0;
@@ -1541,7 +1279,6 @@ int scape_hip_destroy(scape_hip_ctx *c) {
             (void)hipEventDestroy(e.b);
         }
     (void)hipStreamDestroy(c->stream);
-    (void)hipStreamDestroy(c->stream2);
     delete c;
     return 0;
 }
@@ -1938,27 +1675,6 @@ int scape_hip_batch_em(scape_hip_ctx *c, int32_t n_jobs, int32_t kmax, const int
     HIPCHK(hipMemsetAsync(c->j_lb.p, 0, nj * nround * 8, c->stream));
     c->h_traffic[3] = 0;
     if (ev_begin(c, 2)) return 1;
-#ifdef SCAPE_HIP_TOOLS
-    const char *mode = getenv("SCAPE_HIP_EM");
-    if (mode && strcmp(mode, "v1") == 0) {
-        const size_t lds = (size_t)c->Np_max * sizeof(double);
-        if (lds > 150 * 1024) return fail("n_frag too large for the LDS-resident v1 EM kernel (use the default lock-step EM)");
-        if (kmax + 1 > 32) return fail("v1 EM kernel: K <= 31");
-#define LAUNCH_EM(CM)                                                                                         \
-    hipLaunchKernelGGL(k_em<CM>, dim3(n_jobs), dim3(EM_THREADS), lds, c->stream, c->d_desc.as<UtrDesc>(),     \
-                       c->prm, c->d_cnt.as<double>(), c->d_M.as<double>(), kmax, c->j_utr.as<int32_t>(),      \
-                       c->j_K.as<int32_t>(), c->j_fixed.as<int32_t>(), c->j_a.as<int32_t>(),                  \
-                       c->j_b.as<int32_t>(), c->j_ws.as<double>(), c->j_karr.as<int8_t>(),                    \
-                       c->j_ao.as<int32_t>(), c->j_bo.as<int32_t>(), c->j_wso.as<double>(),                   \
-                       c->j_bic.as<double>(), c->j_nlb.as<int32_t>(), c->j_lb.as<double>(),                   \
-                       c->d_counters.as<unsigned long long>())
-        if (kmax + 1 <= 8) LAUNCH_EM(8);
-        else if (kmax + 1 <= 16) LAUNCH_EM(16);
-        else LAUNCH_EM(32);
-#undef LAUNCH_EM
-        HIPCHK(hipGetLastError());
-    } else
-#endif
     if (em_lockstep(c, n_jobs, kmax, job_utr, job_fixed)) return 1;
     if (ev_end(c, 2)) return 1;
     HIPCHK(hipMemcpyAsync(alpha_idx_out, c->j_ao.p, nj * kmax * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2059,16 +1775,12 @@ int scape_hip_batch_labels(scape_hip_ctx *c, int32_t n_sel, int32_t kmax, const 
     HIPCHK(hipMemcpyAsync(c->l_b.p, beta_idx, ns * kmax * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->l_ws.p, ws, ns * (kmax + 1) * 8, hipMemcpyHostToDevice, c->stream));
     if (ev_begin(c, 3)) return 1;
-#define LAUNCH_LAB(CM)                                                                                         \
-    hipLaunchKernelGGL(k_labels<CM>, dim3(n_sel), dim3(256), 0, c->stream, c->d_desc.as<UtrDesc>(), c->prm,    \
-                       c->d_cnt.as<double>(), c->d_M.as<double>(), kmax, c->l_utr.as<int32_t>(),               \
-                       c->l_K.as<int32_t>(), c->l_a.as<int32_t>(), c->l_b.as<int32_t>(), c->l_ws.as<double>(), \
-                       c->l_labels.as<int32_t>())
-    if (kmax + 1 <= 8) LAUNCH_LAB(8);
-    else if (kmax + 1 <= 16) LAUNCH_LAB(16);
-    else if (kmax + 1 <= 32) LAUNCH_LAB(32);
-    else LAUNCH_LAB(64);
-#undef LAUNCH_LAB
+    if (!with_column_class(LabelClasses{}, kmax + 1, [&](auto cm) {
+            hipLaunchKernelGGL(k_labels<decltype(cm)::value>, dim3(n_sel), dim3(256), 0, c->stream, c->d_desc.as<UtrDesc>(), c->prm,
+                               c->d_cnt.as<double>(), c->d_M.as<double>(), kmax, c->l_utr.as<int32_t>(), c->l_K.as<int32_t>(),
+                               c->l_a.as<int32_t>(), c->l_b.as<int32_t>(), c->l_ws.as<double>(), c->l_labels.as<int32_t>());
+        }))
+        return fail("no label kernel for kmax " + std::to_string(kmax));
     HIPCHK(hipGetLastError());
     if (ev_end(c, 3)) return 1;
     // copy back only the selected UTRs' bins; contiguous runs of selected UTRs go in one transfer

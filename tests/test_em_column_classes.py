@@ -1,7 +1,7 @@
 """Every column class of the EM and label kernels against the CPU oracle, K = 0..63.
 
 The E-step kernels are compiled once per column class and the host picks the class from `kmax`, the largest K of a
-scape_hip_batch_em / scape_hip_batch_labels call (scape_hip.hip: LAUNCH_E, LAUNCH_ALL, LAUNCH_LAB; em_lockstep.inc:
+scape_hip_batch_em / scape_hip_batch_labels call (scape_hip.hip: EstepClasses, WideClasses, LabelClasses; em_lockstep.inc:
 ESTEP_DISPATCH).  Up to 16 columns a job runs the code variant of its exact K + 1; the 24 / 32 / 64-column kernels
 run one generic body with runtime predication for every job of the call.  `kmax` belongs to the CALL, so which
 instantiation a job runs depends on what shares its launch - and its result must not.

@@ -527,21 +527,31 @@ def test_find_peaks_equals_scipy():
 
 def test_column_class_ladder_covers_every_dispatch_threshold():
     """tests/test_em_column_classes.py runs the EM and label kernels at the K values of its LADDER.  The column classes
-    are read here from the launch lines of scape_hip.hip: every class boundary (kmax + 1 <= C) must have its last K
+    are read here from the class lists of scape_hip.hip: every class boundary (kmax + 1 <= C) must have its last K
     (C - 1) and the first K of the next class (C) on the ladder, and so must SCAPE_MAX_K - whoever adds a class has
     to extend the ladder."""
     from test_em_column_classes import FIXED_CAPS, LADDER, MIXED_CAPS
     src = open(os.path.join(ROOT, "scape_amd", "csrc", "scape_hip.hip")).read()
     hdr = open(os.path.join(ROOT, "include", "scape_hip.h")).read()
     max_k = int(re.search(r"#define\s+SCAPE_MAX_K\s+(\d+)", hdr).group(1))
-    fam = {
-        "k2_estep": [int(c) for c in re.findall(r"LAUNCH_E\(k2_estep,\s*(\d+),", src)],
-        "k2_estep_cs": [int(c) for c in re.findall(r"LAUNCH_E\(k2_estep_cs,\s*(\d+),", src)],
-        "k2_estep_all_rounds": [int(c) for c in re.findall(r"LAUNCH_ALL\((\d+)\)", src)],
-        "k_labels": [int(c) for c in re.findall(r"LAUNCH_LAB\((\d+)\)", src)],
-    }
-    assert len(re.findall(r"LAUNCH_(?:E|ALL|LAB)\([^)]*\d+[^)]*\)", src)) == sum(len(v) for v in fam.values())
-    wide_cap = int(re.search(r"const bool wide = .*kmax \+ 1 <= (\d+);", src).group(1))
+
+    def class_list(name):
+        found = re.findall(r"using %s = std::integer_sequence<int,([\d,\s]+)>;" % name, src)
+        assert len(found) == 1 and len(re.findall(r"\b%s\b\s*=" % name, src)) == 1, (name, "defined exactly once")
+        return [int(c) for c in found[0].split(",")]
+    estep = class_list("EstepClasses")       # k2_estep and k2_estep_all_rounds share it
+    fam = {"k2_estep": estep, "k2_estep_cs": class_list("WideClasses"), "k2_estep_all_rounds": estep,
+           "k_labels": class_list("LabelClasses")}
+    # each family's kernels are dispatched over its list and nowhere else: no launch macro is left, one dispatch per kernel
+    assert "LAUNCH_" not in src
+    for kernel, lst in (("k2_estep", "EstepClasses"), ("k2_estep_cs", "WideClasses"),
+                        ("k2_estep_all_rounds", "EstepClasses"), ("k_labels", "LabelClasses")):
+        assert len(re.findall(r"\b%s<" % kernel, src)) == 1, kernel
+        assert re.search(r"with_column_class\(%s\{\}, kmax \+ 1, \[&\]\(auto cm\) \{\s*[^;]*\b%s<decltype\(cm\)::value>" % (lst, kernel), src), kernel
+    # the wide E-step's cap is derived from its list, not a second literal
+    cap_name = re.search(r"wide = .*kmax \+ 1 <= (\w+);", src).group(1)
+    assert re.search(r"constexpr int %s = last_class\(WideClasses\{\}\);" % cap_name, src), cap_name
+    wide_cap = fam["k2_estep_cs"][-1]
     assert max_k in LADDER and max(LADDER) == max_k and min(LADDER) == 1
     for name, classes in fam.items():
         assert len(classes) >= 4 and classes == sorted(set(classes)), (name, classes)
