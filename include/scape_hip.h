@@ -303,6 +303,38 @@ int scape_hip_report_perm_groups(scape_hip_ctx *ctx, int32_t n_rec, const int64_
                                  int32_t n_groups, const int32_t *seg_off, int64_t *t_out, int64_t *a0_out,
                                  int64_t *site_n_ge_out, double *stat0_out, double *site_stat0_out,
                                  int64_t *gene_n_ge_out);
+/* diff_pa_len_groups: the omnibus form of scape_hip_report_perm_len, on the counts call, the labels call, the kept rows
+   and the ADD semantics of scape_hip_report_perm_groups (n_groups / seg_off checked against the labels call in the same
+   way; same seed = same labellings).  Kept row i carries the INTEGER position q[i], 0 <= q[i] <= 2^22 (checked): the
+   caller scales x_i - min x of the record by the power of two that puts qspan = max q into 2^21 .. 2^22 and rounds.
+   tol_stat[r] = 2^-40 T qspan^2 and tol_delta[r] = 2^-40 qspan of record r (finite, not negative: checked).  Under a
+   labelling with a_ig the sum of row i over group g, the device forms the exact integers
+     A_g = sum_i a_ig,   Q_g = sum_i a_ig q_i   (32- and 64-bit LDS adds, any order),   T = sum_g A_g < 2^31 (checked),
+     Q = sum_g Q_g <= 2^53
+   and from them in f64, contraction off, through one pair of device functions for the observed labelling and every
+   permutation, with m = (double)Q / (double)T formed once per record,
+     D   = sum_{g : A_g > 0} A_g (Q_g / A_g - m)^2            (groups in order)
+     d_g = Q_g / A_g - (Q - Q_g) / (T - A_g)                  (0 when A_g = 0 or A_g = T).
+   D is the between-group sum of squares of the position weighted by reads (as a rational sum Q_g^2 / A_g - Q^2 / T; for
+   G = 2 it is (A_0 A_1 / T) d_0^2), d_g the mean position of group g against that of all the others.  t_out[i] and
+   a0_out[i * n_groups + g] as for perm_groups; stat0_out[r] = D(0), delta0_out[r * n_groups + g] = d_g(0).  The call
+   ADDS to n_ge_out[r] the number of its permutations with D(p) >= D(0) - tol_stat[r] and to
+   group_n_ge_out[r * n_groups + g] those with |d_g(p)| >= |d_g(0)| - tol_delta[r] (two-sided; for a group whose observed
+   A_g is 0 or T, d_g(0) = 0 and every permutation counts: the caller reports no test for it).
+   Rounding (u = 2^-53): every integer converted is below 2^53, so nothing depends on the number of rows or nonzeros.  Each
+   mean is within u qspan, the difference Q_g / A_g - m within 3 u qspan, a term of D within A_g (6 u qspan |e| + 2 u e^2),
+   all terms within 8 u T qspan^2, and the G - 1 roundings of the sum add (G - 1) u T qspan^2:
+     |D - exact| <= (G + 8) u T qspan^2,     |d_g - exact| <= 3 u qspan.
+   Observed value, permuted value and the threshold's own subtraction are together off by at most (2 G + 17) u T qspan^2
+   <= 145 u T qspan^2 and 7 u qspan, against bands of 2^-40 = 8,192 u: a labelling whose exact statistic reaches the
+   observed one is always counted, one more than twice the band below it never (derivation: csrc/perm.inc, section
+   "diff_pa_len_groups").  No cap beyond G <= 64, q <= 2^22 and T < 2^31 is needed.
+   LDS: 12 bytes per lane and group, 3 KiB per group; above 32 groups they are taken in equal slices of at most 32 (96
+   KiB), one walk over the record's nonzeros per slice, with the same result whatever the slice. */
+int scape_hip_report_perm_len_groups(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                     int32_t n_groups, const int32_t *seg_off, const int32_t *q, const double *tol_stat,
+                                     const double *tol_delta, int64_t *t_out, int64_t *a0_out, double *stat0_out,
+                                     double *delta0_out, int64_t *n_ge_out, int64_t *group_n_ge_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

@@ -1,16 +1,16 @@
 """click group exposing ``infer_pa``, its consumer ``merge_pa`` and the stages after it, ``cal_exp_pa_len``,
 ``ex_pa_cnt_mat``, ``ex_pa_pseudobulk`` (the sums the reference's DEXSeq script starts from), ``diff_pa`` (a
 permutation test of pA usage between two cell populations), ``diff_pa_len`` (the same test on the mean pA position:
-3'UTR lengthening or shortening) and ``diff_pa_groups`` (diff_pa's omnibus form across all clusters; the three are
-this build's own last steps; reference cli.py:7-31
+3'UTR lengthening or shortening), ``diff_pa_groups`` (diff_pa's omnibus form across all clusters) and
+``diff_pa_len_groups`` (diff_pa_len's; the four are this build's own last steps; reference cli.py:7-31
 registers six commands; ``gen_utr_annotation`` and ``prepare_input`` are outside this build's scope, SURVEY.md
 section 8)."""
 import click
 
 from scape_amd.apa_core import infer_pa, infer_pa_all, prebin
 from scape_amd.junction_handler import merge_pa
-from scape_amd.report import (cal_exp_pa_len, diff_pa, diff_pa_groups, diff_pa_len, ex_pa_cnt_mat,
-                              ex_pa_pseudobulk)
+from scape_amd.report import (cal_exp_pa_len, diff_pa, diff_pa_groups, diff_pa_len, diff_pa_len_groups,
+                              ex_pa_cnt_mat, ex_pa_pseudobulk)
 
 
 @click.group()
@@ -35,3 +35,4 @@ cli.add_command(ex_pa_pseudobulk)
 cli.add_command(diff_pa)
 cli.add_command(diff_pa_len)
 cli.add_command(diff_pa_groups)
+cli.add_command(diff_pa_len_groups)

@@ -1,5 +1,5 @@
-// perm.inc - the permutation tests on merge_pa's count matrix: diff_pa and diff_pa_len (freely or within strata) and
-// diff_pa_groups (included by scape_hip.hip after report.inc, whose ReportState, block helpers and k_rep_scan it uses).
+// perm.inc - the permutation tests on merge_pa's count matrix: diff_pa and diff_pa_len (freely or within strata),
+// diff_pa_groups and diff_pa_len_groups (included by scape_hip.hip after report.inc, whose ReportState, block helpers and k_rep_scan it uses).
 //
 // A test is two calls.  The first builds the labellings of a chunk of permutations, in exact integers:
 //   rep_select_key  the one radix select of the file: the key of a given rank among the hashed 64-bit keys of a set of
@@ -21,6 +21,9 @@
 //                   per lane), exceedance counts per record
 //   k_rep_groups_obs / k_rep_perm_groups
 //                   diff_pa_groups: the observed statistic, and the test with G sums per row and permutation in LDS
+//   k_rep_len_groups_obs / k_rep_perm_len_groups
+//                   diff_pa_len_groups: the same for the mean pA position, G pairs of exact integer sums per permutation
+//                   in LDS, the groups in slices of at most 32
 // The exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
 // stay on the host (scape_amd/report.py).
 
@@ -632,6 +635,176 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_groups(
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[r], __popcll(b));
 }
 
+// ---- diff_pa_len_groups: mean pA position across the G groups ---------------------------------------------------------
+// The labellings are the G-way ones above.  Kept row i of a record carries the INTEGER position q_i, 0 <= q_i <= qspan,
+// 2^21 <= qspan = max q_i <= 2^22 (the host scales x_i - min x by a power of two and rounds).  Under a labelling with
+// a_ig the sum of row i over group g:
+//   A_g = sum_i a_ig (32-bit),  Q_g = sum_i a_ig q_i (64-bit),  T = sum_g A_g < 2^31,  Q = sum_g Q_g <= T qspan < 2^53
+// Q and T belong to the record; A_g and Q_g are exact integers whatever the order in which the nonzeros arrive.
+//   D   = sum_{g : A_g > 0} A_g (Q_g / A_g - Q / T)^2         (groups in order)  the between-group sum of squares
+//   d_g = Q_g / A_g - (Q - Q_g) / (T - A_g),  0 when A_g = 0 or A_g = T          group g against all the others
+// Rounding of the code below (contraction off, unit roundoff u = 2^-53, first order in u; every mean lies in 0 .. qspan):
+//   * (double) of Q_g, A_g, Q - Q_g, T - A_g, Q and T is exact (all below 2^53): the error does not depend on the
+//     number of rows or nonzeros;
+//   * m = fl(Q / T) and fl(Q_g / A_g) are each within u qspan of the exact mean and their difference e rounds by at most
+//     u qspan more: e is within 3 u qspan of mu_g - mu;
+//   * e e is within 2 |e| 3 u qspan + u e^2 of (mu_g - mu)^2 and the product with the exact (double)A_g rounds by u more:
+//     the term is within A_g (6 u qspan |e| + 2 u e^2), and over the groups, with |e| <= qspan and sum A_g = T, all terms
+//     together are within 8 u T qspan^2;
+//   * the first addition (0 + term) is exact, each of the other G - 1 rounds by at most u times a partial sum of positive
+//     terms that is at most D <= T qspan^2:  |D - exact| <= (G + 7) u T qspan^2 <= (G + 8) u T qspan^2 =: eD;
+//   * each of the two means of d_g is within u qspan and the subtraction rounds by at most u qspan:
+//     |d_g - exact| <= 3 u qspan =: ed.
+// A permutation is counted when D(p) >= D(0) - tolD, tolD = 2^-40 T qspan^2, and when |d_g(p)| >= |d_g(0)| - told,
+// told = 2^-40 qspan; the thresholds' own subtractions round by at most u T qspan^2 and u qspan.  A labelling whose exact
+// statistic reaches the observed one is counted whatever the rounding, and one more than twice the band below it never
+// is, as long as 2 eD + u T qspan^2 <= tolD and 2 ed + u qspan <= told: (2 G + 17) u <= 145 u for G <= 64, and 7 u,
+// against 2^-40 = 8,192 u.  Nothing has to be capped beyond G <= 64, q_i <= 2^22 and T < 2^31, which the entry point checks.
+#define REP_LEN_GROUPS_SLICE 32        // groups whose sums are in LDS at once: 12 bytes per lane and group, 96 KiB
+#define REP_LEN_GROUPS_MAX_Q (1 << 22)
+
+// one group's term of D and its d_g under a labelling, from the exact integers; m = (double)Q / (double)T of the record.
+// The observed labelling and every permutation go through these two functions, with contraction off; every operation is
+// a correctly rounded IEEE one, so equal integers give equal doubles
+__device__ __forceinline__ double rep_len_groups_term(long long Qg, long long Ag, double m) {
+#pragma clang fp contract(off)
+    if (Ag == 0) return 0.0;
+    const double e = (double)Qg / (double)Ag - m;
+    return (double)Ag * (e * e);
+}
+
+__device__ __forceinline__ double rep_len_groups_delta(long long Qg, long long Ag, long long Q, long long T) {
+#pragma clang fp contract(off)
+    if (Ag == 0 || Ag == T) return 0.0;
+    return (double)Qg / (double)Ag - (double)(Q - Qg) / (double)(T - Ag);
+}
+
+// one workgroup per record: the observed labelling.  qt[2 r], qt[2 r + 1] = Q, T and mean[r] = (double)Q / (double)T,
+// formed once for every permutation of the record; d0[r * n_groups + g] = d_g(0) by thread g; stat0[r] = D(0), the
+// groups' terms added in order by one thread, as a lane of k_rep_perm_len_groups adds them
+__global__ __launch_bounds__(REP_THREADS) void k_rep_len_groups_obs(const int64_t *__restrict__ roff,
+                                                                    const int64_t *__restrict__ t,
+                                                                    const int64_t *__restrict__ a0, int32_t n_groups,
+                                                                    const int32_t *__restrict__ q,
+                                                                    long long *__restrict__ qt, double *__restrict__ mean,
+                                                                    double *__restrict__ d0, double *__restrict__ stat0) {
+#pragma clang fp contract(off)
+    __shared__ long long A0[REP_GROUPS_MAX], Q0[REP_GROUPS_MAX];
+    __shared__ long long QT[2];
+    const int r = blockIdx.x;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    if (threadIdx.x < n_groups) {
+        long long A = 0, Q = 0;
+        for (int64_t i = row0; i < row1; ++i) {
+            const long long a = a0[i * n_groups + threadIdx.x];
+            A += a;
+            Q += a * q[i];
+        }
+        A0[threadIdx.x] = A;
+        Q0[threadIdx.x] = Q;
+    }
+    if (threadIdx.x == REP_THREADS - 1) {
+        long long T = 0, Q = 0;
+        for (int64_t i = row0; i < row1; ++i) {
+            T += t[i];
+            Q += t[i] * q[i];
+        }
+        QT[0] = Q;
+        QT[1] = T;
+    }
+    __syncthreads();
+    const long long Q = QT[0], T = QT[1];
+    const double m = (double)Q / (double)T;
+    if (threadIdx.x < n_groups)
+        d0[(int64_t)r * n_groups + threadIdx.x] = rep_len_groups_delta(Q0[threadIdx.x], A0[threadIdx.x], Q, T);
+    if (threadIdx.x == 0) {
+        double D = 0.0;
+        for (int g = 0; g < n_groups; ++g) D = D + rep_len_groups_term(Q0[g], A0[g], m);
+        qt[2 * r] = Q;
+        qt[2 * r + 1] = T;
+        mean[r] = m;
+        stat0[r] = D;
+    }
+}
+
+// the nonzeros nz[k0 .. k1) of one row with the position qi added to accA[group - g0][lane] (the count) and
+// accQ[group - g0][lane] (count x qi, wave-uniform) under this lane's labelling, as rep_groups_walk adds: four label
+// bytes in flight, LDS atomics whose results are not used.  A lane whose label lies outside [g0, g0 + ng) adds nothing
+__device__ __forceinline__ void rep_len_groups_walk(const uint2 *__restrict__ nz, int64_t k0, int64_t k1,
+                                                    const uint8_t *__restrict__ lb, int64_t pstride, long long qi, int g0,
+                                                    int ng, int32_t *accA, unsigned long long *accQ) {
+    int64_t k = k0;
+    for (; k + 4 <= k1; k += 4) {
+        int c[4], g[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint2 e = nz[k + u];
+            c[u] = __builtin_amdgcn_readfirstlane((int)e.y);
+            g[u] = (int)lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride] - g0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if ((unsigned)g[u] < (unsigned)ng) {
+                atomicAdd(&accA[g[u] * REP_THREADS], c[u]);
+                atomicAdd(&accQ[g[u] * REP_THREADS], (unsigned long long)(c[u] * qi));
+            }
+    }
+    for (; k < k1; ++k) {
+        const uint2 e = nz[k];
+        const int c = __builtin_amdgcn_readfirstlane((int)e.y);
+        const int g = (int)lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride] - g0;
+        if ((unsigned)g < (unsigned)ng) {
+            atomicAdd(&accA[g * REP_THREADS], c);
+            atomicAdd(&accQ[g * REP_THREADS], (unsigned long long)(c * qi));
+        }
+    }
+}
+
+// workgroup = (record blockIdx.x / n_tiles, tile of 256 permutations), one lane per permutation, as k_rep_perm_groups.
+// The groups are taken in slices of `slice` <= REP_LEN_GROUPS_SLICE: LDS holds Q_g(p) as accQ[group][lane] (8 bytes;
+// a 16-lane access group covers all 32 banks whatever the groups) and behind them A_g(p) as accA[group][lane]: 12 x
+// slice x 256 bytes.  One walk over the record's nonzeros per slice forms both; each lane owns its column and no
+// barrier is needed.  D and the counters are additive over the groups, and the terms of D are added in group order in a
+// register that lives across the slices, so the result does not depend on the slice size.  Exceedances are counted per
+// wave (ballot) and added with one atomic per wave and counter: grp_ge[r * n_groups + g] for |d_g|, rec_ge[r] for D.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_groups(
+    const uint8_t *__restrict__ labels, int32_t p_count, int32_t n_tiles, int32_t n_groups, int32_t slice,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ noff, const uint2 *__restrict__ nz,
+    const int32_t *__restrict__ q, const long long *__restrict__ qt, const double *__restrict__ mean,
+    const double *__restrict__ d0, const double *__restrict__ stat0, const double *__restrict__ tol,
+    int32_t *__restrict__ grp_ge, int32_t *__restrict__ rec_ge) {
+#pragma clang fp contract(off)
+    extern __shared__ unsigned long long rep_accq[];
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const uint8_t *lb = labels + (valid ? p : p_count - 1);
+    unsigned long long *accQ = rep_accq + threadIdx.x;
+    int32_t *accA = reinterpret_cast<int32_t *>(rep_accq + slice * REP_THREADS) + threadIdx.x;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    const long long Q = qt[2 * r], T = qt[2 * r + 1];
+    const double m = mean[r], tolD = tol[2 * r], told = tol[2 * r + 1];
+    double D = 0.0;
+    for (int g0 = 0; g0 < n_groups; g0 += slice) {
+        const int ng = min(slice, n_groups - g0);
+        for (int g = 0; g < ng; ++g) {
+            accQ[g * REP_THREADS] = 0;
+            accA[g * REP_THREADS] = 0;
+        }
+        for (int64_t i = row0; i < row1; ++i)
+            rep_len_groups_walk(nz, noff[i], noff[i + 1], lb, p_count, q[i], g0, ng, accA, accQ);
+        for (int g = 0; g < ng; ++g) {
+            const long long Qg = (long long)accQ[g * REP_THREADS], Ag = accA[g * REP_THREADS];
+            D = D + rep_len_groups_term(Qg, Ag, m);
+            const double d = rep_len_groups_delta(Qg, Ag, Q, T);
+            const unsigned long long b = __ballot(valid && fabs(d) >= fabs(d0[(int64_t)r * n_groups + g0 + g]) - told);
+            if ((threadIdx.x & 63) == 0 && b) atomicAdd(&grp_ge[(int64_t)r * n_groups + g0 + g], __popcll(b));
+        }
+    }
+    const unsigned long long b = __ballot(valid && D >= stat0[r] - tolD);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&rec_ge[r], __popcll(b));
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
 
@@ -699,9 +872,21 @@ static int rep_perm_ready(const ReportState *s, int32_t p_count, const char *bui
     return 0;
 }
 
-// the part the three tests share, behind rep_perm_ready.  n = the tested positions and p_count = the permutations of the
+// the groups of a G-way test are those of the last labels call
+static int rep_groups_match(const ReportState *s, int32_t n_groups, const int32_t *seg_off) {
+    if (!seg_off) return fail("bad argument");
+    if (n_groups != (int32_t)s->q_sizes.size()) return fail("n_groups differs from the last scape_hip_report_perm_labels call");
+    if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (seg_off[g + 1] - seg_off[g] != s->q_sizes[g])
+            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last scape_hip_report_perm_labels call");
+    return 0;
+}
+
+// the part the four tests share, behind rep_perm_ready.  n = the tested positions and p_count = the permutations of the
 // labellings (`what`: "masks" or "labels").  First the checks (outs_ok = the caller's own other pointers are there;
-// max_rec_rows > 0: a record may own at most that many rows; w / tol, when given, must be finite and not negative),
+// max_rec_rows > 0: a record may own at most that many rows; w / tol / tol2, when given, must be finite and not negative
+// and the integer positions q, when given, lie in 0 .. REP_LEN_GROUPS_MAX_Q),
 // all of them before anything is queued on the device, then the upload of rows and offsets and the compaction of the
 // kept rows to their nonzeros (p_noff / p_nz), with t and a0 of every row on the host.  Two populations (seg_off =
 // nullptr): a0 = the row's sum over the positions below n1, in p_a0.  n_groups populations in the column segments
@@ -709,7 +894,8 @@ static int rep_perm_ready(const ReportState *s, int32_t p_count, const char *bui
 static int rep_perm_prepare(scape_hip_ctx *c, int32_t n, int32_t p_count, const char *what, int32_t n1, int32_t n_groups,
                             const int32_t *seg_off, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                             int64_t *t_out, int64_t *a0_out, bool outs_ok, int64_t max_rec_rows, const double *w,
-                            const double *tol, int64_t *n_rows_out, int32_t *n_tiles_out) {
+                            const double *tol, const double *tol2, const int32_t *q, int64_t *n_rows_out,
+                            int32_t *n_tiles_out) {
     ReportState *s = c->rep;
     if (n_rec <= 0 || !rec_row_off || !rows || !t_out || !a0_out || !outs_ok) return fail("bad argument");
     if (n > s->n_cols)
@@ -729,8 +915,11 @@ static int rep_perm_prepare(scape_hip_ctx *c, int32_t n, int32_t p_count, const 
     if ((int64_t)n_rec * n_tiles > INT32_MAX) return fail("too many records x permutation tiles for one call");
     for (int64_t i = 0; w && i < n_rows; ++i)
         if (!(w[i] >= 0.0) || std::isinf(w[i])) return fail("row weights must be finite and not negative");
-    for (int r = 0; tol && r < n_rec; ++r)
-        if (!(tol[r] >= 0.0) || std::isinf(tol[r])) return fail("tolerances must be finite and not negative");
+    for (const double *tl : {tol, tol2})
+        for (int r = 0; tl && r < n_rec; ++r)
+            if (!(tl[r] >= 0.0) || std::isinf(tl[r])) return fail("tolerances must be finite and not negative");
+    for (int64_t i = 0; q && i < n_rows; ++i)
+        if (q[i] < 0 || q[i] > REP_LEN_GROUPS_MAX_Q) return fail("row positions must lie in 0 .. 2^22");
 
     DevBuf &a0 = seg_off ? s->q_a0 : s->p_a0;
     const int64_t a0_bytes = n_rows * (seg_off ? n_groups : 1) * 8;
@@ -775,7 +964,7 @@ static int rep_perm_prepare(scape_hip_ctx *c, int32_t n, int32_t p_count, const 
     return 0;
 }
 
-// the tail of the three tests: the exceedance counters p_site (n_site of them; none when 0) and p_gene (n_rec) are
+// the tail of the four tests: the exceedance counters p_site (n_site of them; none when 0) and p_gene (n_rec) are
 // zeroed, launch() queues the test, and the counts of this chunk of permutations are added to the caller's running
 // totals; stat0_out gets p_stat0
 template <typename Launch>
@@ -837,7 +1026,8 @@ int scape_hip_report_perm_test(scape_hip_ctx *c, int32_t n_rec, const int64_t *r
     int64_t n_rows = 0;
     int32_t n_tiles = 0;
     if (rep_perm_prepare(c, s->m_n1 + s->m_n2, s->m_count, "masks", s->m_n1, 0, nullptr, n_rec, rec_row_off, rows, t_out,
-                         a0_out, site_n_ge_out && stat0_out && gene_n_ge_out, 0, nullptr, nullptr, &n_rows, &n_tiles))
+                         a0_out, site_n_ge_out && stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr, nullptr, &n_rows,
+                         &n_tiles))
         return 1;
     if (s->p_recs.ensure((int64_t)n_rec * 4)) return 1;
 
@@ -883,7 +1073,8 @@ int scape_hip_report_perm_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *re
     int64_t n_rows = 0;
     int32_t n_tiles = 0;
     if (rep_perm_prepare(c, s->m_n1 + s->m_n2, s->m_count, "masks", s->m_n1, 0, nullptr, n_rec, rec_row_off, rows, t_out,
-                         a0_out, w && tol && delta0_out && n_ge_out, REP_LEN_MAX_ROWS, w, tol, &n_rows, &n_tiles))
+                         a0_out, w && tol && delta0_out && n_ge_out, REP_LEN_MAX_ROWS, w, tol, nullptr, nullptr, &n_rows,
+                         &n_tiles))
         return 1;
     if (s->l_w.ensure(n_rows * 8) || s->l_tol.ensure((int64_t)n_rec * 8)) return 1;
     return rep_perm_count(c, 0, n_rec, nullptr, n_ge_out, delta0_out, [&]() -> int {
@@ -951,12 +1142,8 @@ int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t 
     CTX_ENTER(c);
     ReportState *s = c->rep;
     if (rep_perm_ready(s, s ? s->q_count : 0, "scape_hip_report_perm_labels")) return 1;
-    if (n_rec <= 0 || !rec_row_off || !seg_off) return fail("bad argument");   // what the checks below read
-    if (n_groups != (int32_t)s->q_sizes.size()) return fail("n_groups differs from the last scape_hip_report_perm_labels call");
-    if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
-    for (int32_t g = 0; g < n_groups; ++g)
-        if (seg_off[g + 1] - seg_off[g] != s->q_sizes[g])
-            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last scape_hip_report_perm_labels call");
+    if (n_rec <= 0 || !rec_row_off) return fail("bad argument");   // what the check of the rounding bound reads
+    if (rep_groups_match(s, n_groups, seg_off)) return 1;
     for (int r = 0; r < n_rec; ++r)
         if (rec_row_off[r + 1] - rec_row_off[r] + n_groups > REP_GROUPS_MAX_ROWS_AND_GROUPS)
             return fail("record " + std::to_string(r) + ": " + std::to_string(rec_row_off[r + 1] - rec_row_off[r]) +
@@ -965,8 +1152,8 @@ int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t 
     int64_t n_rows = 0;
     int32_t n_tiles = 0;
     if (rep_perm_prepare(c, s->q_n, s->q_count, "labels", 0, n_groups, seg_off, n_rec, rec_row_off, rows, t_out, a0_out,
-                         site_n_ge_out && stat0_out && site_stat0_out && gene_n_ge_out, 0, nullptr, nullptr, &n_rows,
-                         &n_tiles))
+                         site_n_ge_out && stat0_out && site_stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr,
+                         nullptr, &n_rows, &n_tiles))
         return 1;
     if (s->q_s0.ensure(n_rows * 8) || s->q_share.ensure(n_rows * 8)) return 1;
     return rep_perm_count(c, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
@@ -983,6 +1170,56 @@ int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t 
                            s->p_stat0.as<double>(), s->p_site.as<int32_t>(), s->p_gene.as<int32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(site_stat0_out, s->q_share.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    });
+}
+
+int scape_hip_report_perm_len_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                     int32_t n_groups, const int32_t *seg_off, const int32_t *q, const double *tol_stat,
+                                     const double *tol_delta, int64_t *t_out, int64_t *a0_out, double *stat0_out,
+                                     double *delta0_out, int64_t *n_ge_out, int64_t *group_n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (rep_perm_ready(s, s ? s->q_count : 0, "scape_hip_report_perm_labels")) return 1;
+    if (rep_groups_match(s, n_groups, seg_off)) return 1;
+    int64_t n_rows = 0;
+    int32_t n_tiles = 0;
+    if (rep_perm_prepare(c, s->q_n, s->q_count, "labels", 0, n_groups, seg_off, n_rec, rec_row_off, rows, t_out, a0_out,
+                         q && tol_stat && tol_delta && stat0_out && delta0_out && n_ge_out && group_n_ge_out, 0, nullptr,
+                         tol_stat, tol_delta, q, &n_rows, &n_tiles))
+        return 1;
+    const int64_t n_pairs = (int64_t)n_rec * n_groups;
+    if (s->v_q.ensure(n_rows * 4) || s->v_tol.ensure((int64_t)n_rec * 16) || s->v_qt.ensure((int64_t)n_rec * 16) ||
+        s->v_mean.ensure((int64_t)n_rec * 8) || s->v_d0.ensure(n_pairs * 8))
+        return 1;
+    std::vector<double> tol((size_t)n_rec * 2);       // alive until rep_perm_count has waited for the stream
+    for (int r = 0; r < n_rec; ++r) {
+        tol[2 * (size_t)r] = tol_stat[r];
+        tol[2 * (size_t)r + 1] = tol_delta[r];
+    }
+    // equal slices of at most REP_LEN_GROUPS_SLICE groups: 33 groups take 17 + 16, not 32 + 1
+    const int32_t n_slices = (n_groups + REP_LEN_GROUPS_SLICE - 1) / REP_LEN_GROUPS_SLICE;
+    const int32_t slice = (n_groups + n_slices - 1) / n_slices;
+    return rep_perm_count(c, n_pairs, n_rec, group_n_ge_out, n_ge_out, stat0_out, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(s->v_q.p, q, n_rows * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(s->v_tol.p, tol.data(), (int64_t)n_rec * 16, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_rep_len_groups_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream,
+                           s->p_roff.as<int64_t>(), s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_groups,
+                           s->v_q.as<int32_t>(), s->v_qt.as<long long>(), s->v_mean.as<double>(), s->v_d0.as<double>(),
+                           s->p_stat0.as<double>());
+        HIPCHK(hipGetLastError());
+        const size_t lds = (size_t)slice * REP_THREADS * 12;         // above 64 KiB a kernel needs the attribute
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_len_groups),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   REP_LEN_GROUPS_SLICE * REP_THREADS * 12));
+        hipLaunchKernelGGL(k_rep_perm_len_groups, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), lds,
+                           c->stream, s->q_lab.as<uint8_t>(), s->q_count, n_tiles, n_groups, slice,
+                           s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->v_q.as<int32_t>(),
+                           s->v_qt.as<long long>(), s->v_mean.as<double>(), s->v_d0.as<double>(),
+                           s->p_stat0.as<double>(), s->v_tol.as<double>(), s->p_site.as<int32_t>(),
+                           s->p_gene.as<int32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(delta0_out, s->v_d0.p, n_pairs * 8, hipMemcpyDeviceToHost, c->stream));
         return 0;
     });
 }

@@ -56,6 +56,9 @@ struct ReportState {
     // scape_hip_report_perm_groups that scape_hip_report_perm_test has no counterpart of
     DevBuf q_lab, q_cut, q_seg, q_a0, q_s0, q_share;
     std::vector<int32_t> q_sizes;      // cells per group of the last labels call
+    // diff_pa_len_groups: the integer row positions and (tolD, told) per record of scape_hip_report_perm_len_groups,
+    // and per record (Q, T), (double)Q / (double)T and the G observed d_g
+    DevBuf v_q, v_tol, v_qt, v_mean, v_d0;
     int32_t q_n = 0, q_count = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
@@ -83,7 +86,8 @@ static void report_release(scape_hip_ctx *c) {
                      &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz, &s->m_bits, &s->p_rows,
                      &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
                      &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound,
-                     &s->q_lab, &s->q_cut, &s->q_seg, &s->q_a0, &s->q_s0, &s->q_share};
+                     &s->q_lab, &s->q_cut, &s->q_seg, &s->q_a0, &s->q_s0, &s->q_share, &s->v_q, &s->v_tol, &s->v_qt,
+                     &s->v_mean, &s->v_d0};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;

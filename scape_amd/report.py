@@ -668,7 +668,7 @@ def _bh(p):
 
 def _perm_masks(ctx, su, p_first, p_count, seed, times):
     """the membership bits of p_count permutations from p_first on: relabelled within su.strata = (m1, m2) when given,
-    freely otherwise; for diff_pa_groups (su.sizes = cells per group) the group bytes instead"""
+    freely otherwise; for diff_pa_groups and diff_pa_len_groups (su.sizes = cells per group) the group bytes instead"""
     t0 = timer()
     if su.sizes is not None:
         check(ctx.lib.scape_hip_report_perm_labels(ctx.h, len(su.sizes), ptr(su.sizes, P_i32), p_first, p_count, seed),
@@ -852,7 +852,7 @@ def _perm_run(su, n_perm, seed, device, batch, write):
             ctx = run.device()
             budget = _budget(ctx)
             if su.sizes is not None:
-                word_bytes = int(su.sizes.sum())         # diff_pa_groups: one byte per tested cell and permutation
+                word_bytes = int(su.sizes.sum())         # the G-way commands: one byte per tested cell and permutation
             else:
                 # the bits, and the device's key bound per permutation and stratum (one stratum without --strata_file)
                 word_bytes = (su.n1 + su.n2 + 63) // 64 * 8 + (1 if su.strata is None else len(su.strata[0])) * 8
@@ -955,40 +955,47 @@ def _mean_positions(x, a, b):
     return float(m1), float(m2), float(m1 - m2)
 
 
-def _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
-    """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
-    n_ge) per tested record to `out`"""
-    recs, K = bat.recs, bat.K
-    pos = {}                     # record -> positions of its kept rows (f64, finite)
-
+def _finite_positions(recs, pos):
+    """the each_kept callback of _perm_rows for the tests of the pA position: pos[r] = the positions of record r's kept
+    rows (f64); a non-finite one is a ValueError naming the record"""
     def positions(r, labs):
         x = np.asarray(recs[r].alpha_arr, dtype=np.float64)[labs]
         if not (np.all(np.isfinite(x)) and np.isfinite(x.max() - x.min())):
             raise ValueError(f"{recs[r].gene_info_str}: alpha_arr holds a non-finite position of a pA site with reads")
         pos[r] = x
-    sel = _perm_rows(ctx, bat, su.seg_off, times, positions)
-    if sel is None:
-        return
+    return positions
+
+
+def _with_span(sel, pos, times):
+    """the records of _perm_rows' result whose kept rows lie at two positions or more (span = max x - min x > 0): (batch
+    indices, row offsets, count rows, sums per row and population, first count row of every record of the batch,
+    positions of the kept rows per record), or None when none is left"""
     which, off, rows, _nz, sums, rowbase = sel
     t0 = timer()
-    tested, xs, w, tol = [], [], [], []
-    for g, r in enumerate(which.tolist()):
-        x = pos[r]
-        span = float(x.max() - x.min())
-        if span > 0:
-            tested.append(g)
-            xs.append(x)
-            w.append(x - x.min())
-            tol.append(np.ldexp(span, -40))
+    tested = [g for g, r in enumerate(which.tolist()) if float(pos[r].max() - pos[r].min()) > 0]
     times["finish"] += timer() - t0
     if not tested:
-        return
+        return None
     n_kept = np.diff(off)[tested]
     pick = np.concatenate([np.arange(off[g], off[g + 1]) for g in tested])
-    which, rows, sums = which[tested], np.ascontiguousarray(rows[pick]), sums[pick]
+    which = which[tested]
     off = np.zeros(len(which) + 1, dtype=np.int64)
     np.cumsum(n_kept, out=off[1:])
-    w, tol = np.ascontiguousarray(np.concatenate(w)), np.array(tol, dtype=np.float64)
+    return which, off, np.ascontiguousarray(rows[pick]), sums[pick], rowbase, [pos[r] for r in which.tolist()]
+
+
+def _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
+    """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
+    n_ge) per tested record to `out`"""
+    recs, K = bat.recs, bat.K
+    pos = {}                     # record -> positions of its kept rows (f64, finite)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos))
+    sel = sel and _with_span(sel, pos, times)
+    if sel is None:
+        return
+    which, off, rows, sums, rowbase, xs = sel
+    w = np.ascontiguousarray(np.concatenate([x - x.min() for x in xs]))
+    tol = np.array([np.ldexp(float(x.max() - x.min()), -40) for x in xs], dtype=np.float64)
     t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
     delta0, n_ge = np.zeros(len(which), np.float64), np.zeros(len(which), np.int64)
     _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
@@ -1067,17 +1074,18 @@ def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, ide
 # (S is Pearson's chi-square of the rows x G table and, for G = 2, diff_pa's S as a rational).  A record is tested when
 # it has two kept rows or more and two populations or more with reads.  p = (1 + #{p: stat(p) >= stat(0)}) / (1 + n_perm),
 # Benjamini-Hochberg over the file's lines (sites) and over the tested records (genes).  Not part of this command:
-# --strata_file (blocked G-way relabelling needs cut points per stratum and group) and an omnibus for diff_pa_len.
+# --strata_file (blocked G-way relabelling needs cut points per stratum and group).  The omnibus form of diff_pa_len is
+# diff_pa_len_groups, below.
 DIFF_PA_GROUPS_HEADER = ["gene", "pa_info", "num_groups", "top_group", "top_delta_usage", "site_stat", "n_ge", "p_val",
                          "p_val_adj", "gene_stat", "gene_n_ge", "gene_p_val", "gene_p_val_adj", "n_perm"]
 MAX_GROUPS = 64                  # a group is one byte on the device, and its sums 2 KiB of LDS
 MAX_ROWS_AND_GROUPS = 4000       # kept rows + populations of a record: the rounding bound of S (include/scape_hip.h)
 
 
-def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed):
-    """what diff_pa_groups does before the device is opened: the argument and prerequisite checks, the populations, the
-    id -> column table that puts population 0's columns first, then population 1's, ..., and the output path
-    <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_groups.csv"""
+def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, command="diff_pa_groups"):
+    """what diff_pa_groups and diff_pa_len_groups do before the device is opened: the argument and prerequisite checks,
+    the populations, the id -> column table that puts population 0's columns first, then population 1's, ..., and the
+    output path <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv"""
     idents = [str(i) for i in idents or ()]
     if n_perm < 1:
         raise ValueError(f"n_perm must be at least 1, not {n_perm}")
@@ -1102,12 +1110,12 @@ def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, s
                 raise ValueError(f"cluster {ident!r} has no cell in barcode_index.csv")
         pops = [(ident, with_cells[ident]) for ident in idents]
     if not 2 <= len(pops) <= MAX_GROUPS:
-        raise ValueError(f"{len(pops)} populations: diff_pa_groups takes 2 to {MAX_GROUPS}")
+        raise ValueError(f"{len(pops)} populations: {command} takes 2 to {MAX_GROUPS}")
     _table, slot, seg_off, _seg_pop = _samples(pops, 1, inp.n_cols)
     sizes = np.array([len(cols) for _name, cols in pops], dtype=np.int32)
     if int(sizes.sum()) >= MAX_PERM_CELLS:
-        raise ValueError(f"{int(sizes.sum())} tested cells: diff_pa_groups takes fewer than {MAX_PERM_CELLS}")
-    outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + ".diff_pa_groups.csv"
+        raise ValueError(f"{int(sizes.sum())} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
+    outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + f".{command}.csv"
     return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, strata=None,
                            names=[name for name, _cols in pops], outpath=outpath,
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
@@ -1205,6 +1213,157 @@ def _diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     wall = _perm_run(su, n_perm, seed, device, batch, write)
     print(f"Finish {n_perm} permutations of {int(su.sizes.sum())} cells in {G} populations for "
           f"{sum(g[1] for g in genes)} pA sites of {len(genes)} tested records")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- diff_pa_len_groups
+# The omnibus form of diff_pa_len: which records change their mean pA position (3'UTR length) across G = 2..64
+# populations at all, and which population has the longer or shorter 3'UTRs against all the others.  Options,
+# populations, tested columns, permutations and output naming are diff_pa_groups's (same --seed = same labellings; with
+# two populations, population 0 is diff_pa_len's population 1); kept rows, positions x_i = alpha_arr[label_i] and the
+# refusal of a non-finite position are diff_pa_len's.  A record is tested when diff_pa_groups would test it and
+# span = max x - min x > 0.  The G sums per permutation are exact integers on the device, so per record the positions
+# become integers first:  w_i = fl(x_i - min x),  frexp(span) = (m, e),  s = 22 - e,  q_i = rint(ldexp(w_i, s)) (half to
+# even), so 2^21 <= qspan = max q_i <= 2^22.  Positions that are multiples of 2^-s (integers: the theta grid) are exact,
+# others are rounded at about span 2^-22; the p-values are those of the test on the q_i, the position columns of the
+# file come from the exact x_i.  With a_ig the sum of kept row i over group g under a labelling:
+#     A_g = sum_i a_ig,  T = sum_g A_g < 2^31,  Q_g = sum_i a_ig q_i,  Q = sum_g Q_g
+#     D   = sum_{g: A_g > 0} A_g (Q_g / A_g - Q / T)^2 = sum Q_g^2 / A_g - Q^2 / T     tests the record
+#     d_g = Q_g / A_g - (Q - Q_g) / (T - A_g)   (0 when A_g = 0 or A_g = T)            tests group g against the others
+# D is the between-cluster sum of squares of the position weighted by reads (for G = 2: (A_0 A_1 / T) d_0^2); d_g is
+# two-sided.  n_ge = #{p: D(p) >= D(0) - 2^-40 T qspan^2},  n_ge.<g> = #{p: |d_g(p)| >= |d_g(0)| - 2^-40 qspan}, reported
+# for the groups whose observed A_g is neither 0 nor T (the others get empty fields);  p = (1 + n_ge) / (1 + n_perm).
+# Benjamini-Hochberg over the file's lines for the record, and once over all reported (record, group) pairs of the file
+# for the groups.  eta2 = D / sum_i t_i (q_i - Q / T)^2, the share of the position's variance that lies between the
+# clusters.  No --strata_file and no exp_length columns.  (include/scape_hip.h states the device's arithmetic and the
+# bound that makes the counts exact.)
+DIFF_PA_LEN_GROUPS_HEADER = ["gene", "num_pa", "num_groups", "reads", "mean_pos", "eta2", "n_ge", "p_val", "p_val_adj",
+                             "top_group", "top_delta_pos", "n_perm"]
+DIFF_PA_LEN_GROUPS_PER_GROUP = ["reads", "mean_pos", "delta_pos", "n_ge", "p_val", "p_val_adj"]
+LEN_GROUPS_Q_BITS = 22           # qspan lies in 2^21 .. 2^22: T qspan < 2^53, the sums stay exact as integers and in f64
+
+
+def _quantise_positions(x):
+    """the integer positions q_i (int32) of a record's kept rows at x (finite f64, span > 0)"""
+    w = x - x.min()
+    _m, e = math.frexp(float(x.max() - x.min()))
+    return np.rint(np.ldexp(w, LEN_GROUPS_Q_BITS - e)).astype(np.int32)
+
+
+def _mean_positions_groups(x, a):
+    """(mean_pos, [mean_pos.<g>], [delta_pos.<g>]) of positions x (finite f64) under the integer sums a[row][group]:
+    delta_pos.<g> = mean_pos.<g> - the mean position of all other groups' reads; the exact rationals, each rounded
+    once; None where a group has no read, or every read"""
+    ratios = [float(v).as_integer_ratio() for v in x]
+    D = max(d for _n, d in ratios)                       # denominators are powers of two
+    X = [n * (D // d) for n, d in ratios]
+    G = len(a[0])
+    A = [sum(int(row[g]) for row in a) for g in range(G)]
+    S = [sum(int(row[g]) * Xi for row, Xi in zip(a, X)) for g in range(G)]
+    T, St = sum(A), sum(S)
+    mean = [float(Fraction(S[g], A[g] * D)) if A[g] else None for g in range(G)]
+    delta = [float(Fraction(S[g], A[g] * D) - Fraction(St - S[g], (T - A[g]) * D)) if 0 < A[g] < T else None
+             for g in range(G)]
+    return float(Fraction(St, T * D)), mean, delta
+
+
+def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
+    """one counted batch: appends (gene, num_pa, [A_g], mean_pos, eta2, n_ge, top group, [mean_pos.<g>],
+    [delta_pos.<g>], [n_ge.<g>]) per tested record to `out`"""
+    recs, G = bat.recs, len(su.sizes)
+    pos = {}                     # record -> positions of its kept rows (f64, finite)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos))
+    sel = sel and _with_span(sel, pos, times)
+    if sel is None:
+        return
+    which, off, rows, sums, _rowbase, xs = sel
+    t0 = timer()
+    qs = [_quantise_positions(x) for x in xs]
+    q = np.ascontiguousarray(np.concatenate(qs))
+    T = np.add.reduceat(sums.sum(axis=1), off[:-1])
+    for g, r in enumerate(which.tolist()):
+        if int(T[g]) >= 1 << 31:
+            raise ValueError(f"{recs[r].gene_info_str}: 2^31 or more reads in the tested cells")
+    qspan = [int(qi.max()) for qi in qs]
+    tol_stat = np.array([math.ldexp(float(int(Tr) * sp * sp), -40) for Tr, sp in zip(T.tolist(), qspan)])
+    tol_delta = np.array([math.ldexp(float(sp), -40) for sp in qspan])
+    times["finish"] += timer() - t0
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
+    stat0, delta0 = np.zeros(len(which), np.float64), np.zeros((len(which), G), np.float64)
+    n_ge, group_ge = np.zeros(len(which), np.int64), np.zeros((len(which), G), np.int64)
+    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
+        ctx.lib.scape_hip_report_perm_len_groups(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G,
+                                                 ptr(su.seg_off, P_i32), ptr(q, P_i32), ptr(tol_stat), ptr(tol_delta),
+                                                 ptr(t, P_i64), ptr(a0, P_i64), ptr(stat0), ptr(delta0),
+                                                 ptr(n_ge, P_i64), ptr(group_ge, P_i64)), "report_perm_len_groups"))
+    t0 = timer()
+    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums)):
+        raise _lib.ScapeHipError("report_perm_len_groups: row sums differ from report_group_sums")
+    for g, r in enumerate(which.tolist()):
+        sl = slice(int(off[g]), int(off[g + 1]))
+        a, qi = a0[sl].tolist(), qs[g].tolist()
+        # the statistics of the observed labelling, exactly, in Python ints on the q_i
+        A = [sum(row[k] for row in a) for k in range(G)]
+        Qg = [sum(row[k] * v for row, v in zip(a, qi)) for k in range(G)]
+        Tr, Q = sum(A), sum(Qg)
+        D = sum(Fraction(Qg[k] * Qg[k], A[k]) for k in range(G) if A[k]) - Fraction(Q * Q, Tr)
+        if not abs(Fraction(float(stat0[g])) - D) <= Fraction(float(tol_stat[g])):
+            raise _lib.ScapeHipError(f"report_perm_len_groups: {recs[r].gene_info_str}: the device's statistic "
+                                     f"{stat0[g]!r} differs from {float(D)!r}")
+        # d_k = N_k / M_k with N_k = Q_k T - Q A_k and M_k = A_k (T - A_k) > 0 for a reported group
+        N = [Qg[k] * Tr - Q * A[k] for k in range(G)]
+        M = [A[k] * (Tr - A[k]) for k in range(G)]
+        top = None
+        for k in range(G):
+            if M[k] == 0:
+                continue
+            if not abs(Fraction(float(delta0[g, k])) - Fraction(N[k], M[k])) <= Fraction(float(tol_delta[g])):
+                raise _lib.ScapeHipError(f"report_perm_len_groups: {recs[r].gene_info_str}: the device's delta "
+                                         f"{delta0[g, k]!r} of population {su.names[k]!r} differs from "
+                                         f"{N[k] / M[k]!r}")
+            if top is None or abs(N[k]) * M[top] > abs(N[top]) * M[k]:       # the first wins ties
+                top = k
+        ss_total = sum(int(ti) * v * v for ti, v in zip(t[sl].tolist(), qi)) - Fraction(Q * Q, Tr)
+        mean, mean_g, delta_g = _mean_positions_groups(xs[g], a)
+        out.append((recs[r].gene_info_str, len(qi), A, mean, float(D / ss_total), int(n_ge[g]), top, mean_g, delta_g,
+                    group_ge[g].tolist()))
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
+                        seed: int = 1, device=None):
+    """permutation test of the mean pA position (3'UTR length) across the populations of a cluster file (every cluster,
+    or the clusters `idents` in the order given), and of every population against all the others; writes <cluster file
+    stem>.<gene|utr>[.<A>+<B>+...].diff_pa_len_groups.csv in output_dir, one line per tested record, and returns its
+    path"""
+    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_len_groups")
+    names, G = su.names, len(su.sizes)
+    out = []
+
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, seed, out, times)
+
+    def write(w):
+        w.writerow(DIFF_PA_LEN_GROUPS_HEADER + [f"{c}.{n}" for n in names for c in DIFF_PA_LEN_GROUPS_PER_GROUP])
+        if not out:
+            return
+        p_val = (1 + np.array([o[5] for o in out], dtype=np.int64)) / (1 + n_perm)
+        # one family for the groups: every reported (record, group) pair of the file
+        pairs = [(k, g) for k, o in enumerate(out) for g in range(G) if o[8][g] is not None]
+        pair_p = (1 + np.array([out[k][9][g] for k, g in pairs], dtype=np.int64)) / (1 + n_perm)
+        group_p = {pair: (repr(p), repr(adj)) for pair, p, adj in zip(pairs, pair_p.tolist(), _bh(pair_p).tolist())}
+        for k, (o, p, adj) in enumerate(zip(out, p_val.tolist(), _bh(p_val).tolist())):
+            gene, num_pa, A, mean, eta2, n_ge, top, mean_g, delta_g, group_ge = o
+            line = [gene, num_pa, sum(Ag > 0 for Ag in A), sum(A), repr(mean), repr(eta2), n_ge, repr(p), repr(adj),
+                    names[top], repr(delta_g[top]), n_perm]
+            for g in range(G):
+                line += [A[g], repr(mean_g[g]) if A[g] else ""]
+                line += [repr(delta_g[g]), group_ge[g], *group_p[(k, g)]] if (k, g) in group_p else [""] * 4
+            w.writerow(line)
+
+    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    print(f"Finish {n_perm} permutations of {int(su.sizes.sum())} cells in {G} populations for {len(out)} tested records")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -1458,3 +1617,28 @@ def diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, i
     """pA sites and genes whose pA usage differs across the cell populations of a cluster file at all: the omnibus
     form of diff_pa, a permutation test of the cell labels on Pearson's chi-square of the sites x populations table."""
     _diff_pa_groups(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
+
+
+@click.command(name="diff_pa_len_groups")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the final '
+                   'result.')
+@click.option('--cell_cluster_file', type=str, required=True,
+              help='An csv file containing two columns in order: cell barcode index (index) and respective group. Cells '
+                   'with an empty group, or not listed, are left out. Its name will be included in the file name of the '
+                   'final result.')
+@click.option('--idents', type=str, multiple=True,
+              help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. Default: every '
+                   'cluster of the cell_cluster_file, in order of first appearance.')
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives the same relabellings of the cells '
+                   'as in diff_pa_groups.')
+def diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents, n_perm: int, seed: int):
+    """Genes whose 3'UTR length differs across the cell populations of a cluster file at all, and the populations with
+    longer or shorter 3'UTRs than all the others: the omnibus form of diff_pa_len, a permutation test of the cell labels
+    on the between-population sum of squares of the mean pA position, and on every population's mean against the rest."""
+    _diff_pa_len_groups(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
