@@ -21,6 +21,14 @@
 #define MT_VPITCH (MT_NC + 2)         // stores, and (2*row + k) mod 32 distinct within every 32-lane read group
                                       // (ds_read_b64 banking, MI355X_MICROARCH.md section LDS): conflict-free fragments
 #define MT_MAXJ 64
+// Run-ahead: between two M-step launches (one PASS over the tensor) a job executes up to EM_DEPTH consecutive rounds, as
+// long as the next round's component is neither equal nor adjacent to one whose grid arg-max is still pending (see
+// k2_estep), and publishes one M-step column (v vector, window, log w_k) per round.  Everything the M-step reads or
+// writes is per COLUMN, column id = job * depth + slot; depth is the call's runtime cap <= EM_DEPTH (SCAPE_HIP_EM_DEPTH).
+#ifndef EM_DEPTH
+#define EM_DEPTH 3
+#endif
+static_assert(EM_DEPTH >= 1 && EM_DEPTH <= 8, "column slots per job");
 #ifndef MT_DV1
 #define MT_DV1 1      // the job vectors (L2-resident) are requested one chunk ahead, the tensor tile two: frees 4 G registers (-3 % launch time)
 #endif
@@ -42,16 +50,19 @@ struct EmState {
     int32_t *ia, *ib, *sia, *sib;     // [n_jobs*kmax] current / snapshot grid indices
     double *ws, *slw;                 // [n_jobs*(kmax+1)] weights / snapshot log-weights
     double *lb, *ell;                 // [n_jobs]
-    int32_t *nlb, *status;            // [n_jobs]   status: 0 running, 1 stop after pending M-step, 2 done
+    int32_t *nlb, *status;            // [n_jobs]   rounds executed; status: 0 running, 1 stop after pending M-step, 2 done
+    unsigned long long *pend;         // [n_jobs]   run-ahead state of the current pass: bit c + 1 = component c has a column published
+                                      //            in it, bit 0 = the job runs its next round in the pass's next E-step launch
+    // per column (= job * depth + slot; [n_jobs * depth]) from here on
     int32_t *rd_k, *rd_lo, *rd_hi, *rd_m;   // round descriptor: component, row window [lo,hi), has M-step
     int32_t *rd_n0, *rd_n1;           // bins [n0,n1) outside which v is exactly 0
     double *rd_lw, *rd_sv;            // log w_k (new), sum_n v[n]
-    double *V;                        // ragged [job][Np]
-    double *Vsuf;                     // ragged [job][Np/16 + 1]: Vsuf[b] = sum_{n >= 16 b} V[n] (summed from the end)
-    const int64_t *voff;              // [n_jobs]
-    double *pt_score;                 // ragged [job][n_tiles(utr)]
+    double *V;                        // ragged [column][Np]
+    double *Vsuf;                     // ragged [column][Np/16 + 1]: Vsuf[b] = sum_{n >= 16 b} V[n] (summed from the end)
+    const int64_t *voff;              // [columns]
+    double *pt_score;                 // ragged [column][n_tiles(utr)]
     int32_t *pt_row;
-    const int64_t *ptoff;             // [n_jobs]
+    const int64_t *ptoff;             // [columns]
 };
 
 __device__ __forceinline__ double d_wave_allsum(double v) {
@@ -75,8 +86,15 @@ __device__ __forceinline__ double d_wave_allsum(double v) {
 // their lane reductions of component c belong to wavefront c mod 4, the row sums are recomputed by every wavefront
 // from the exchanged values, the ELBO / entropy chains stay on wavefront 0.  Every sum keeps the operand order of the
 // one-wavefront kernel, so both return identical bits.
+struct EstepNext {      // what one call of estep_body tells its kernel about the job (wave-uniform)
+    int status;         // the job's status now: 0 running, 1 stop after the pending M-step, 2 finalised
+    int nlb;            // rounds the job has executed
+    int pub_k;          // component whose M-step column this round published, -1: none
+    int k_next;         // component of round nlb (meaningful while nlb < nround)
+};
+
 template <int CA, int CX, int NW = 1>
-__device__ __forceinline__ void estep_body(
+__device__ __forceinline__ EstepNext estep_body(
     const UtrDesc *__restrict__ descs, const DevParams &P, const double *__restrict__ cnt,
     const double *__restrict__ M, int kmax, const int32_t *__restrict__ job_utr,
     const int32_t *__restrict__ job_K, const int32_t *__restrict__ job_fixed,
@@ -84,7 +102,7 @@ __device__ __forceinline__ void estep_body(
     const double *__restrict__ ws_in, const int8_t *__restrict__ k_arr, const EmState &S,
     int32_t *__restrict__ a_out, int32_t *__restrict__ b_out, double *__restrict__ ws_out,
     double *__restrict__ bic_out, int32_t *__restrict__ nlb_out, double *__restrict__ lb_out,
-    unsigned long long *__restrict__ counters, int round, int job, int lane, int status,
+    unsigned long long *__restrict__ counters, int launch, int slot, int depth, int job, int lane, int status,
     unsigned long long *s_roff, double *s_lwc, double *s_wsum /* [CA][64] per-lane weight numerators */,
     const double2 *s_exptab /* d_load_exptab */, int wave = 0, double *s_xz = nullptr /* [2][CA][64] */,
     double *s_tot = nullptr /* [CA + 4] */) {
@@ -107,13 +125,38 @@ __device__ __forceinline__ void estep_body(
     int32_t *ia = S.ia + (size_t)job * kmax, *ib = S.ib + (size_t)job * kmax;
     int32_t *sia = S.sia + (size_t)job * kmax, *sib = S.sib + (size_t)job * kmax;
     double *ws = S.ws + (size_t)job * (kmax + 1), *slw = S.slw + (size_t)job * (kmax + 1);
-    const bool r0 = round == 0;
-    const int rdm = r0 ? 0 : S.rd_m[job];
-    const int pre_lo = r0 ? 0 : S.rd_lo[job], pre_hi = r0 ? 0 : S.rd_hi[job], pre_k = r0 ? 0 : S.rd_k[job];
-    const int64_t pre_ptoff = S.ptoff[job], pre_voff = S.voff[job];
-    const int k_now = (round < nround) ? (int)k_arr[(size_t)job * nround + round] : 0;
+    // The job's round is its own counter S.nlb, not the launch index.  Call `slot` of pass `launch` publishes into column
+    // col0 + slot; the first call of a pass (slot 0) finishes the grid arg-maxes of every column the previous pass
+    // published - their components are pairwise neither equal nor adjacent (k2_estep), so the order is immaterial;
+    // slot order = round order.
+    const bool r0 = launch == 0 && slot == 0;
+    const bool resolve = slot == 0 && launch > 0;
+    const size_t col0 = (size_t)job * depth, col = col0 + slot;
+    int pre_m[EM_DEPTH], pre_lo[EM_DEPTH], pre_hi[EM_DEPTH], pre_k[EM_DEPTH];
+    int64_t pre_ptoff[EM_DEPTH];
+    bool rdm = false;
+#pragma unroll
+    for (int q = 0; q < EM_DEPTH; ++q) {
+        const bool on = resolve && q < depth;
+        pre_m[q] = on ? S.rd_m[col0 + q] : 0;
+        pre_lo[q] = on ? S.rd_lo[col0 + q] : 0;
+        pre_hi[q] = on ? S.rd_hi[col0 + q] : 0;
+        pre_k[q] = on ? S.rd_k[col0 + q] : 0;
+        pre_ptoff[q] = on ? S.ptoff[col0 + q] : 0;
+        rdm = rdm || pre_m[q] != 0;
+    }
+    const int64_t pre_voff = S.voff[col];
+    // the job's component order sits in lanes 0 .. nround - 1 (one request with the rest of this batch; indexed by the
+    // round counter it would be one more dependent trip)
+    const int k_lane = (lane < nround) ? (int)k_arr[(size_t)job * nround + lane] : 0;
     const double lb_prev = r0 ? SENT : S.lb[job];       // (read after the bin loop these two were one more trip at the end)
     const int nlb_prev = r0 ? 0 : S.nlb[job];
+    auto k_of_round = [&](int i) {
+        const int ii = min(i, nround - 1);
+        return (nround <= 64) ? __shfl(k_lane, ii, 64) : (int)k_arr[(size_t)job * nround + ii];
+    };
+    const int k_now = k_of_round(nlb_prev);
+    const int k_next = __builtin_amdgcn_readfirstlane(k_of_round(nlb_prev + 1));
     double my_ws = 0.0, my_slw = 0.0;                    // lane c < C: weight / snapshot log-weight of column c
     int my_ia = 0, my_ib = 0, my_sia = 0, my_sib = 0;    // lane c < K: current / snapshot grid indices
     if (lane < C) {
@@ -128,16 +171,21 @@ __device__ __forceinline__ void estep_body(
     }
     // second batch
     const UtrDesc d = descs[u_job];
-    double pt_best = -INFINITY;
-    int pt_best_r = pre_lo;
-    if (rdm) {   // per-tile partials of the previous round's grid arg-max (wave-uniform condition)
-        const int t0 = pre_lo / MT_ROWS, t1 = (pre_hi - 1) / MT_ROWS;
-        for (int t = t0 + lane; t <= t1; t += 64) {
-            const double sc = S.pt_score[pre_ptoff + t];
-            const int rr = S.pt_row[pre_ptoff + t];
-            if (sc > pt_best) {
-                pt_best = sc;
-                pt_best_r = rr;
+    double pt_best[EM_DEPTH];
+    int pt_best_r[EM_DEPTH];
+#pragma unroll
+    for (int q = 0; q < EM_DEPTH; ++q) {
+        pt_best[q] = -INFINITY;
+        pt_best_r[q] = pre_lo[q];
+        if (pre_m[q]) {   // per-tile partials of a pending grid arg-max (wave-uniform condition)
+            const int t0 = pre_lo[q] / MT_ROWS, t1 = (pre_hi[q] - 1) / MT_ROWS;
+            for (int t = t0 + lane; t <= t1; t += 64) {
+                const double sc = S.pt_score[pre_ptoff[q] + t];
+                const int rr = S.pt_row[pre_ptoff[q] + t];
+                if (sc > pt_best[q]) {
+                    pt_best[q] = sc;
+                    pt_best_r[q] = rr;
+                }
             }
         }
     }
@@ -159,40 +207,56 @@ __device__ __forceinline__ void estep_body(
             S.lb[job] = SENT;
             S.nlb[job] = 0;
             S.ell[job] = 0.0;
-            S.rd_m[job] = 0;
         }
     }
-    int upd_k = -1, upd_a = 0, upd_b = 0;   // alpha/beta index just decided (not yet re-read from memory)
-    if (rdm) {
-        // finish max_alpha_beta of the previous round: first maximum over the tiles, in row order
-        double best = pt_best;
-        int best_r = pt_best_r;
+    int upd_k[EM_DEPTH], upd_a[EM_DEPTH], upd_b[EM_DEPTH];   // alpha/beta indices just decided (not yet re-read from memory)
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ob = __shfl_xor(best, off, 64);
-            const int orr = __shfl_xor(best_r, off, 64);
-            if (ob > best || (ob == best && orr < best_r)) {
-                best = ob;
-                best_r = orr;
+    for (int q = 0; q < EM_DEPTH; ++q) {
+        upd_k[q] = -1;
+        upd_a[q] = upd_b[q] = 0;
+        if (pre_m[q]) {
+            // finish max_alpha_beta of a published round: first maximum over the tiles, in row order
+            double best = pt_best[q];
+            int best_r = pt_best_r[q];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ob = __shfl_xor(best, off, 64);
+                const int orr = __shfl_xor(best_r, off, 64);
+                if (ob > best || (ob == best && orr < best_r)) {
+                    best = ob;
+                    best_r = orr;
+                }
+            }
+            upd_k[q] = pre_k[q];
+            upd_a[q] = best_r / B;
+            upd_b[q] = best_r - upd_a[q] * B;
+            if (lead && lane == 0) {
+                ia[upd_k[q]] = upd_a[q];
+                ib[upd_k[q]] = upd_b[q];
+            }
+            if (lane == upd_k[q]) {      // lane c keeps column c's current indices
+                my_ia = upd_a[q];
+                my_ib = upd_b[q];
             }
         }
-        upd_k = pre_k;
-        upd_a = best_r / B;
-        upd_b = best_r - upd_a * B;
-        if (lead && lane == 0) {
-            ia[upd_k] = upd_a;
-            ib[upd_k] = upd_b;
-            S.rd_m[job] = 0;
-        }
-        if (lane == upd_k) {      // lane c keeps column c's current indices
-            my_ia = upd_a;
-            my_ib = upd_b;
-        }
     }
-    auto cur_ia = [&](int i) { return (i == upd_k) ? upd_a : ia[i]; };     // (memory forms: the once-per-job finalisation on lane 0)
-    auto cur_ib = [&](int i) { return (i == upd_k) ? upd_b : ib[i]; };
+    // every slot of the job is free again (slot 0 only: later calls of a pass keep what the earlier ones published)
+    if (slot == 0 && lead && lane == 0 && (r0 || rdm))
+        for (int q = 0; q < depth; ++q) S.rd_m[col0 + q] = 0;
+    auto cur_ia = [&](int i) {     // (memory forms: the once-per-job finalisation on lane 0)
+        int v = ia[i];
+#pragma unroll
+        for (int q = 0; q < EM_DEPTH; ++q) v = (i == upd_k[q]) ? upd_a[q] : v;
+        return v;
+    };
+    auto cur_ib = [&](int i) {
+        int v = ib[i];
+#pragma unroll
+        for (int q = 0; q < EM_DEPTH; ++q) v = (i == upd_k[q]) ? upd_b[q] : v;
+        return v;
+    };
 
-    if (status == 1 || round >= nround) {
+    if (status == 1 || nlb_prev >= nround) {
         // cal_bic (:702-706), sort by alpha (:768-772), outputs
         if (lead && lane == 0) {
             const int n_lb = S.nlb[job];
@@ -224,10 +288,10 @@ __device__ __forceinline__ void estep_body(
             atomicAdd(&counters[0], (unsigned long long)n_lb);
             atomicAdd(&counters[2], (unsigned long long)n_lb * (unsigned long long)N * (unsigned long long)C);
         }
-        return;
+        return EstepNext{2, nlb_prev, -1, 0};
     }
 
-    // ---- round `round` of em_algo (:726-746) --------------------------------------------------
+    // ---- round nlb_prev of em_algo (:726-746) --------------------------------------------------
     // executed job-rounds (host early-exit probe); the two per-job-round counters are kept in 64 shards each
     // (counters[4..67] slab elements, counters[68..131] executed) - one address would take 51,200 adds per launch
     if (lead && lane == 0) atomicAdd(&counters[CNT_EXEC + (job & 63)], 1ull);
@@ -553,7 +617,7 @@ __device__ __forceinline__ void estep_body(
             }
             break;
         }
-        if (!lead) return;
+        if (!lead) return EstepNext{0, 0, -1, 0};
     }
 
     ESTEP_STAMP(st2);
@@ -598,7 +662,7 @@ __device__ __forceinline__ void estep_body(
     if (!fixed && k < K) {
         // suffix sums of v at 16-bin boundaries, accumulated from the last bin backwards (a tail of 1e-100
         // next to a head of 1e3 must come out as 1e-100: the M-step multiplies it by the sentinel)
-        double *Sj = S.Vsuf + (pre_voff >> 4) + job;
+        double *Sj = S.Vsuf + (pre_voff >> 4) + col;
         double carry = 0.0;
         // v is read back in batches of 8 groups of 64 bins (one round trip to L2 per batch instead of one per group:
         // the 17-34 dependent trips of a group-at-a-time loop were a quarter of a wavefront's lifetime); the sums
@@ -634,27 +698,27 @@ __device__ __forceinline__ void estep_body(
     }
     ESTEP_STAMP(st4);
     // elbo (:559-561), stopping rule (:743-746), this round's M-step descriptor (:507-523)
-    const double lb_new = t_ell + t_ent;
+    const double lb_new = t_ell + t_ent;                 // (the wavefront sums are identical in every lane)
+    const int status_new = (fabs(lb_new - lb_prev) < fabs(1e-6 * lb_prev)) ? 1 : 0;
+    const bool has_m = (!fixed && k < K);
     if (lane == 0) {
-        const double lb = lb_prev;
         const int n_lb = nlb_prev;
         lb_out[(size_t)job * nround + n_lb] = lb_new;
         S.nlb[job] = n_lb + 1;
         S.ell[job] = t_ell;
         S.lb[job] = lb_new;
-        S.status[job] = (fabs(lb_new - lb) < fabs(1e-6 * lb)) ? 1 : 0;
-        const bool has_m = (!fixed && k < K);
-        S.rd_m[job] = has_m ? 1 : 0;
+        S.status[job] = status_new;
+        S.rd_m[col] = has_m ? 1 : 0;
         if (has_m) {
             const int lo = (k == 0) ? 0 : ia_km1;
             const int hi = (k == K - 1) ? d.T - 1 : ia_kp1;
-            S.rd_k[job] = k;
-            S.rd_lo[job] = lo * B;
-            S.rd_hi[job] = (hi + 1) * B;
-            S.rd_lw[job] = d_logw(wk_new);
-            S.rd_sv[job] = sv;
-            S.rd_n0[job] = (nz_hi >= 0) ? nz_lo : 0;
-            S.rd_n1[job] = (nz_hi >= 0) ? nz_hi + 1 : 0;
+            S.rd_k[col] = k;
+            S.rd_lo[col] = lo * B;
+            S.rd_hi[col] = (hi + 1) * B;
+            S.rd_lw[col] = d_logw(wk_new);
+            S.rd_sv[col] = sv;
+            S.rd_n0[col] = (nz_hi >= 0) ? nz_lo : 0;
+            S.rd_n1[col] = (nz_hi >= 0) ? nz_hi + 1 : 0;
             atomicAdd(&counters[CNT_SLAB + (job & 63)], (unsigned long long)(hi + 1 - lo) * B * (unsigned long long)N);
         }
     }
@@ -671,14 +735,16 @@ __device__ __forceinline__ void estep_body(
     }
 #endif
 #undef ESTEP_STAMP
+    return EstepNext{status_new, nlb_prev + 1, has_m ? k : -1, k_next};
 }
 
 // one code variant per exact column count K+1 <= 16 (every `c < C` test folds away), selected per job - a
 // wave-uniform branch; kernels built for more columns (CM = 24, 32) run the generic body with runtime predication
+// (ROUND = launch index; `slot`, `depth` and the result `nx` are variables of the calling scope)
 #define ESTEP_ARGS(ROUND, STATUS) descs, P, cnt, M, kmax, job_utr, job_K, job_fixed, a_in, b_in, ws_in, k_arr, S, a_out, \
-                   b_out, ws_out, bic_out, nlb_out, lb_out, counters, ROUND, job, lane, STATUS, s_roff, s_lwc, s_wsum, s_exptab
+                   b_out, ws_out, bic_out, nlb_out, lb_out, counters, ROUND, slot, depth, job, lane, STATUS, s_roff, s_lwc, s_wsum, s_exptab
 #define ESTEP_CASE(C, ROUND, STATUS) \
-    case C: estep_body<C, C, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;
+    case C: nx = estep_body<C, C, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;
 #define ESTEP_DISPATCH(CM, ROUND, STATUS)                                                         \
     do {                                                                                          \
         if constexpr (CM <= 16) {                                                                 \
@@ -688,7 +754,7 @@ __device__ __forceinline__ void estep_body(
                     switch (c_exact) {                                                            \
                         ESTEP_CASE(13, ROUND, STATUS) ESTEP_CASE(14, ROUND, STATUS)               \
                         ESTEP_CASE(15, ROUND, STATUS)                                             \
-                        default: estep_body<16, 16, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;            \
+                        default: nx = estep_body<16, 16, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;            \
                     }                                                                             \
                     break;                                                                        \
                 }                                                                                 \
@@ -698,7 +764,7 @@ __device__ __forceinline__ void estep_body(
                     switch (c_exact) {                                                            \
                         ESTEP_CASE(9, ROUND, STATUS) ESTEP_CASE(10, ROUND, STATUS)                \
                         ESTEP_CASE(11, ROUND, STATUS)                                             \
-                        default: estep_body<12, 12, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;            \
+                        default: nx = estep_body<12, 12, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;            \
                     }                                                                             \
                     break;                                                                        \
                 }                                                                                 \
@@ -708,20 +774,27 @@ __device__ __forceinline__ void estep_body(
                     switch (c_exact) {                                                            \
                         ESTEP_CASE(5, ROUND, STATUS) ESTEP_CASE(6, ROUND, STATUS)                 \
                         ESTEP_CASE(7, ROUND, STATUS)                                              \
-                        default: estep_body<8, 8, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;              \
+                        default: nx = estep_body<8, 8, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;              \
                     }                                                                             \
                     break;                                                                        \
                 }                                                                                 \
             }                                                                                     \
             switch (c_exact) {                                                                    \
                 ESTEP_CASE(1, ROUND, STATUS) ESTEP_CASE(2, ROUND, STATUS) ESTEP_CASE(3, ROUND, STATUS) \
-                default: estep_body<4, 4, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;                      \
+                default: nx = estep_body<4, 4, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA); break;                      \
             }                                                                                     \
         } else {                                                                                  \
-            estep_body<CM, 0, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA);                                         \
+            nx = estep_body<CM, 0, ESTEP_NW>(ESTEP_ARGS(ROUND, STATUS) ESTEP_EXTRA);                                       \
         }                                                                                         \
     } while (0)
 
+// The schedule rule of the run-ahead (host and device; tools/em_schedule_check.cpp restates and checks it): after a round
+// that left the job at `status` with `nlb` rounds executed, does the pass stop in front of round nlb, whose component
+// is k_next?  pend: bit c + 1 set = component c has a column published in this pass.  (The slot count is the host's:
+// it launches `depth` slots per pass.)
+__host__ __device__ inline bool em_run_ahead_stops(int status, int nlb, int nround, int k_next, unsigned long long pend) {
+    return status != 0 || nlb >= nround || (pend & (7ull << k_next)) != 0ull;
+}
 #define ESTEP_NW 1
 #ifndef ESTEP_WPS
 #define ESTEP_WPS 3      // wavefronts per SIMD the throughput E-step is compiled for (4 was measured: see DESIGN.md)
@@ -737,7 +810,8 @@ __global__ __launch_bounds__(64, (CMAX > 12 ? 2 : ESTEP_WPS)) void k2_estep(
     const double *__restrict__ ws_in, const int8_t *__restrict__ k_arr, EmState S,
     int32_t *__restrict__ a_out, int32_t *__restrict__ b_out, double *__restrict__ ws_out,
     double *__restrict__ bic_out, int32_t *__restrict__ nlb_out, double *__restrict__ lb_out,
-    unsigned long long *__restrict__ counters, int round, const int32_t *__restrict__ job_list, int n_jobs) {
+    unsigned long long *__restrict__ counters, int launch, int slot, int depth, const int32_t *__restrict__ job_list,
+    int n_jobs) {
     // jobs are ordered UTR-major; blocks b and b+8 share an XCD, so give each XCD a contiguous job range:
     // the jobs of one UTR (which re-read the same few tensor rows) then meet in one L2.  Speed only.
     const int chunk = (n_jobs + 7) >> 3;
@@ -745,8 +819,23 @@ __global__ __launch_bounds__(64, (CMAX > 12 ? 2 : ESTEP_WPS)) void k2_estep(
     if (jidx >= n_jobs) return;
     const int job = job_list[jidx];
     const int lane = threadIdx.x;
-    const int status = (round == 0) ? 0 : S.status[job];
+    const int status = (launch == 0 && slot == 0) ? 0 : S.status[job];
     if (status == 2) return;
+    // Run-ahead.  A pass is `depth` launches of this kernel (slot 0, 1, ...) and one M-step launch.  A round reads the
+    // alpha / beta of its own component c (column refresh, apa_core.py:731) and the alpha of c - 1 and c + 1 (its M-step
+    // window, :511-514) and nothing else of the grid arg-max, so a job goes on to its next round in the same pass unless
+    // that round's component is equal or adjacent to one whose arg-max is pending, i.e. published earlier in the pass.  It
+    // also stops after the round that meets the stopping rule and after round nround - 1.  A round's arithmetic is
+    // estep_body's whichever slot it runs in, so the job's bits do not depend on depth.  (One launch per slot and not a
+    // loop over the slots in here: with the loop the compiler keeps 25-35 more VGPRs live across the bin loop - what
+    // k2_estep_all_rounds shows against this kernel - and the 12-column variants spill inside it; a wavefront that has
+    // nothing to do in a slot leaves right here.)
+    unsigned long long pend = 0ull;
+    if (slot > 0) {
+        pend = S.pend[job];
+        if (!(pend & 1ull)) return;
+        pend &= ~1ull;
+    }
     // column descriptors (tensor row offset, snapshot log-weight) and the per-lane weight numerators live in
     // LDS, not in registers: what matters here is how many wavefronts fit on a SIMD
     __shared__ unsigned long long s_roff[CMAX];
@@ -754,7 +843,14 @@ __global__ __launch_bounds__(64, (CMAX > 12 ? 2 : ESTEP_WPS)) void k2_estep(
     __shared__ double s_wsum[CMAX * 64];
     __shared__ double2 s_exptab[128];
     d_load_exptab(s_exptab, lane, 64);
-    ESTEP_DISPATCH(CMAX, round, status);
+    EstepNext nx;
+    ESTEP_DISPATCH(CMAX, launch, status);
+    if (depth > 1 && lane == 0) {
+        if (nx.pub_k >= 0) pend |= 2ull << nx.pub_k;
+        // fixed-inference jobs have no M-step, nothing to share a tensor pass for: one round per pass, as before
+        const bool stop = em_run_ahead_stops(nx.status, nx.nlb, P.nround, nx.k_next, pend) || job_fixed[job] != 0;
+        S.pend[job] = pend | (stop ? 0ull : 1ull);
+    }
 }
 
 // Jobs that never need an M-step (fixed inference, the ws-only re-fit of rm_component, apa_core.py:708-711) have
@@ -781,10 +877,13 @@ __global__ __launch_bounds__(64, (CMAX > 12 ? 2 : 3)) void k2_estep_all_rounds(
     __shared__ double s_wsum[CMAX * 64];
     __shared__ double2 s_exptab[128];
     d_load_exptab(s_exptab, lane, 64);
-    for (int round = 0; round <= P.nround; ++round) {
+    for (int round = 0; round <= P.nround; ++round) {     // (a call of fixed-inference jobs has one column slot per job)
         const int status = (round == 0) ? 0 : S.status[job];
         if (status == 2) return;
+        constexpr int slot = 0, depth = 1;
+        EstepNext nx;
         ESTEP_DISPATCH(CMAX, round, status);
+        (void)nx;
         __threadfence();
         __syncthreads();
     }
@@ -820,13 +919,19 @@ __global__ __launch_bounds__(256, 1) void k2_estep_cs(
     __shared__ double s_tot[CMAX + 4];
     __shared__ double2 s_exptab[128];
     d_load_exptab(s_exptab, threadIdx.x, 256);
+    constexpr int slot = 0, depth = 1;   // one round per launch, one column slot per job (the host runs small calls at depth 1)
+    EstepNext nx;
     ESTEP_DISPATCH(CMAX, round, status);
+    (void)nx;
 }
 #undef ESTEP_NW
 #undef ESTEP_EXTRA
 #undef ESTEP_DISPATCH
 #undef ESTEP_CASE
 
+
+// (With run-ahead the entries of ujob_list are COLUMNS - job * depth + slot, one v vector, window and partial table
+// each - and every per-"job" array of the three M-step kernels is indexed by column; "job" below reads "column".)
 // one workgroup per (UTR, MT_ROWS-row tile).  D[rows x jobs] = Mtile[rows x n] * V[n x jobs] on the f64
 // matrix cores (v_mfma_f64_16x16x4_f64): wave w owns MT_RB blocks of 16 rows, job columns come in groups
 // of 16.  Operand maps (cdna_hip_programming.md section 3): A lane l = A[row l&15][k l>>4],

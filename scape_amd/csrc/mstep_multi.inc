@@ -16,7 +16,9 @@
 //   - tile i + 1's first ring slots are requested as soon as tile i's last k-step has been multiplied, BEFORE tile i's
 //     arg-max epilogue, which works from LDS tables and an exchange area of its own: no round trip, the DMA latency of
 //     the next tile hides behind it.
-// A tile that holds more jobs than one pass (> 64, rare) gets its further passes at the end, one after the other, each
+// "Job" here is an M-step COLUMN: the list entries are column ids (job * depth + slot, em_lockstep.inc), a job that ran
+// ahead has up to EM_DEPTH of them in a launch, each with its own v vector, window and partial table.
+// A tile that holds more jobs than one pass (> 64: rare at one round per pass, not in the early passes of a call that runs ahead) gets its further passes at the end, one after the other, each
 // with a scan and table of its own.  Calls with few live tiles (job lists cut into passes for several workgroups,
 // gridDim.y > 1) run k3_mstep instead (the host picks the kernel).
 

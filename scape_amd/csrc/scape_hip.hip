@@ -751,27 +751,29 @@ struct ReportState;   // report.inc
 // Device buffers of the lock-step EM (em_lockstep.inc): the per-job state the kernels see as an EmState, the index
 // tables of a call's plan (EmPlan) and the debug histogram of SCAPE_HIP_DEBUG.
 struct EmBufs {
-    DevBuf ia, ib, sia, sib, ws, slw, lb, ell, nlb, status, rd_k, rd_lo, rd_hi, rd_m, rd_n0, rd_n1, rd_lw, rd_sv, V, Vsuf,
+    DevBuf ia, ib, sia, sib, ws, slw, lb, ell, nlb, status, pend, rd_k, rd_lo, rd_hi, rd_m, rd_n0, rd_n1, rd_lw, rd_sv, V, Vsuf,
         voff, pt_score, pt_row, ptoff;             // one per EmState member, in its order
     DevBuf ujoff, ujlist, active, elist, dbg;
-    int ensure(size_t nj, size_t kmax, size_t n_utr, size_t vtot, size_t pttot) {
+    // nc = column slots of the call (jobs x depth): what the M-step reads and writes is per column
+    int ensure(size_t nj, size_t nc, size_t kmax, size_t n_utr, size_t vtot, size_t pttot) {
         return ia.ensure(nj * kmax * 4) || ib.ensure(nj * kmax * 4) || sia.ensure(nj * kmax * 4) || sib.ensure(nj * kmax * 4) ||
                ws.ensure(nj * (kmax + 1) * 8) || slw.ensure(nj * (kmax + 1) * 8) || lb.ensure(nj * 8) || ell.ensure(nj * 8) ||
-               nlb.ensure(nj * 4) || status.ensure(nj * 4) || rd_k.ensure(nj * 4) || rd_lo.ensure(nj * 4) ||
-               rd_hi.ensure(nj * 4) || rd_m.ensure(nj * 4) || rd_n0.ensure(nj * 4) || rd_n1.ensure(nj * 4) ||
-               rd_lw.ensure(nj * 8) || rd_sv.ensure(nj * 8) || V.ensure(vtot * 8) || Vsuf.ensure((vtot / 16 + nj + 1) * 8) ||
-               voff.ensure(nj * 8) || pt_score.ensure(pttot * 8) || pt_row.ensure(pttot * 4) || ptoff.ensure(nj * 8) ||
-               ujoff.ensure((n_utr + 1) * 8) || ujlist.ensure(nj * 4) || active.ensure(n_utr * 4);
+               nlb.ensure(nj * 4) || status.ensure(nj * 4) || pend.ensure(nj * 8) || rd_k.ensure(nc * 4) || rd_lo.ensure(nc * 4) ||
+               rd_hi.ensure(nc * 4) || rd_m.ensure(nc * 4) || rd_n0.ensure(nc * 4) || rd_n1.ensure(nc * 4) ||
+               rd_lw.ensure(nc * 8) || rd_sv.ensure(nc * 8) || V.ensure(vtot * 8) || Vsuf.ensure((vtot / 16 + nc + 1) * 8) ||
+               voff.ensure(nc * 8) || pt_score.ensure(pttot * 8) || pt_row.ensure(pttot * 4) || ptoff.ensure(nc * 8) ||
+               ujoff.ensure((n_utr + 1) * 8) || ujlist.ensure(nc * 4) || active.ensure(n_utr * 4) || elist.ensure(nj * 4);
     }
     EmState state() const {
         return EmState{ia.as<int32_t>(), ib.as<int32_t>(), sia.as<int32_t>(), sib.as<int32_t>(), ws.as<double>(), slw.as<double>(),
-                       lb.as<double>(), ell.as<double>(), nlb.as<int32_t>(), status.as<int32_t>(), rd_k.as<int32_t>(),
+                       lb.as<double>(), ell.as<double>(), nlb.as<int32_t>(), status.as<int32_t>(), pend.as<unsigned long long>(),
+                       rd_k.as<int32_t>(),
                        rd_lo.as<int32_t>(), rd_hi.as<int32_t>(), rd_m.as<int32_t>(), rd_n0.as<int32_t>(), rd_n1.as<int32_t>(),
                        rd_lw.as<double>(), rd_sv.as<double>(), V.as<double>(), Vsuf.as<double>(), voff.as<int64_t>(),
                        pt_score.as<double>(), pt_row.as<int32_t>(), ptoff.as<int64_t>()};
     }
     void release() {
-        for (DevBuf *b : {&ia, &ib, &sia, &sib, &ws, &slw, &lb, &ell, &nlb, &status, &rd_k, &rd_lo, &rd_hi, &rd_m, &rd_n0, &rd_n1, &rd_lw,
+        for (DevBuf *b : {&ia, &ib, &sia, &sib, &ws, &slw, &lb, &ell, &nlb, &status, &pend, &rd_k, &rd_lo, &rd_hi, &rd_m, &rd_n0, &rd_n1, &rd_lw,
                           &rd_sv, &V, &Vsuf, &voff, &pt_score, &pt_row, &ptoff, &ujoff, &ujlist, &active, &elist, &dbg})
             b->release();
     }
@@ -965,27 +967,31 @@ static bool with_column_class(std::integer_sequence<int, Cs...>, int columns, F 
     return ((columns <= Cs && (f(std::integral_constant<int, Cs>()), true)) || ...);
 }
 
-// Index tables of one EM call: jobs grouped by UTR, the UTRs and jobs in launch order, ragged offsets of the job vectors
-// and of the per-tile partials.  Host only.
+// Index tables of one EM call: the M-step columns (job j owns columns j * depth .. j * depth + depth - 1, one per round it
+// may run in a launch) grouped by UTR, the UTRs and jobs in launch order, ragged offsets of the column vectors and of the
+// per-tile partials.  Host only.
 struct EmPlan {
-    std::vector<int64_t> ujoff, voff, ptoff;     // [n_utr + 1] first job of a UTR in ujlist; [n_jobs] offsets into V / pt_*
-    std::vector<int32_t> ujlist, active, elist;  // jobs by UTR; UTRs with jobs (M-step grid order); jobs in E-step order (may be empty: ujlist)
+    std::vector<int64_t> ujoff, voff, ptoff;     // [n_utr + 1] first column of a UTR in ujlist; [columns] offsets into V / pt_*
+    std::vector<int32_t> ujlist, active, elist;  // columns by UTR; UTRs with jobs (M-step grid order); jobs in E-step order
     size_t vtot = 0, pttot = 0;
-    int tiles_max = 1, max_jobs_utr = 1;
+    int depth = 1;                               // column slots per job
+    int tiles_max = 1, max_cols_utr = 1;
     bool any_m = false;                          // fixed-inference jobs (mstep_fixed) have no grid arg-max
 };
 
 static EmPlan em_plan(const std::vector<UtrDesc> &h_desc, int B, size_t nj, const int32_t *job_utr, const int32_t *job_fixed,
-                      bool size_order) {
+                      bool size_order, int depth) {
     EmPlan p;
     const int n_utr = (int)h_desc.size();
+    p.depth = depth;
     p.ujoff.assign(n_utr + 1, 0);
-    p.ujlist.resize(nj);
-    for (size_t j = 0; j < nj; ++j) p.ujoff[job_utr[j] + 1]++;
+    p.ujlist.resize(nj * depth);
+    for (size_t j = 0; j < nj; ++j) p.ujoff[job_utr[j] + 1] += depth;
     for (int u = 0; u < n_utr; ++u) p.ujoff[u + 1] += p.ujoff[u];
     {
         std::vector<int64_t> fill(p.ujoff.begin(), p.ujoff.end() - 1);
-        for (size_t j = 0; j < nj; ++j) p.ujlist[fill[job_utr[j]]++] = (int32_t)j;
+        for (size_t j = 0; j < nj; ++j)
+            for (int q = 0; q < depth; ++q) p.ujlist[fill[job_utr[j]]++] = (int32_t)(j * depth + q);
     }
     // UTRs that have at least one job in this call, in index order: the M-step grid runs over this list, so a call
     // that touches a few UTRs of a large resident batch (reference-stream mode) still uses every XCD
@@ -1002,27 +1008,34 @@ static EmPlan em_plan(const std::vector<UtrDesc> &h_desc, int B, size_t nj, cons
         });
     const int n_active = (int)p.active.size();
     for (int u : p.active) {
-        p.max_jobs_utr = std::max<int>(p.max_jobs_utr, (int)(p.ujoff[u + 1] - p.ujoff[u]));
+        p.max_cols_utr = std::max<int>(p.max_cols_utr, (int)(p.ujoff[u + 1] - p.ujoff[u]));
         p.tiles_max = std::max(p.tiles_max, (h_desc[u].T * B + MT_ROWS - 1) / MT_ROWS);
     }
-    p.voff.resize(nj);
-    p.ptoff.resize(nj);
+    p.voff.resize(nj * depth);
+    p.ptoff.resize(nj * depth);
     for (size_t j = 0; j < nj; ++j) {
         const UtrDesc &d = h_desc[job_utr[j]];
-        p.voff[j] = (int64_t)p.vtot;
-        p.ptoff[j] = (int64_t)p.pttot;
-        p.vtot += (size_t)d.Np;
-        p.pttot += (size_t)((d.T * B + MT_ROWS - 1) / MT_ROWS);
+        for (int q = 0; q < depth; ++q) {
+            p.voff[j * depth + q] = (int64_t)p.vtot;
+            p.ptoff[j * depth + q] = (int64_t)p.pttot;
+            p.vtot += (size_t)d.Np;
+            p.pttot += (size_t)((d.T * B + MT_ROWS - 1) / MT_ROWS);
+        }
         p.any_m = p.any_m || job_fixed[j] == 0;
     }
     // The E-step gives XCD x the x-th eighth of its job list: with the jobs of UTR active[x], active[x + 8], ... there,
     // every XCD gets the same mix of sizes, and the v vectors a UTR's jobs write are read by the M-step tiles of the same
     // UTR on the same XCD (L2; speed only).
+    // Otherwise: the jobs by UTR.
+    p.elist.reserve(nj);
+    auto jobs_of = [&](int u) {
+        for (int64_t q = p.ujoff[u]; q < p.ujoff[u + 1]; q += depth) p.elist.push_back(p.ujlist[q] / depth);
+    };
     if (size_order && n_active >= 8) {
-        p.elist.reserve(nj);
         for (int x = 0; x < 8; ++x)
-            for (int k = x; k < n_active; k += 8)
-                for (int64_t q = p.ujoff[p.active[k]]; q < p.ujoff[p.active[k] + 1]; ++q) p.elist.push_back(p.ujlist[q]);
+            for (int k = x; k < n_active; k += 8) jobs_of(p.active[k]);
+    } else {
+        for (int u = 0; u < n_utr; ++u) jobs_of(u);
     }
     return p;
 }
@@ -1031,6 +1044,7 @@ static EmPlan em_plan(const std::vector<UtrDesc> &h_desc, int B, size_t nj, cons
 struct EmSwitches {
     bool size_order, debug, fine, mstep_v2, mstep_v3;
     int split_maxtiles, wide_maxjobs;
+    int depth;          // SCAPE_HIP_EM_DEPTH: cap on the rounds a job runs per launch (1 = one round per tensor pass)
 };
 static EmSwitches em_switches() {
     const char *env_m = getenv("SCAPE_HIP_MSTEP"), *env_r = getenv("SCAPE_HIP_SPLIT_MAXTILES"), *env_w = getenv("SCAPE_HIP_WIDE_MAXJOBS");
@@ -1042,6 +1056,8 @@ static EmSwitches em_switches() {
     s.mstep_v3 = env_m && strcmp(env_m, "v3") == 0;
     s.split_maxtiles = env_r ? atoi(env_r) : 1024;
     s.wide_maxjobs = env_w ? atoi(env_w) : 1024;
+    const char *env_d = getenv("SCAPE_HIP_EM_DEPTH");
+    s.depth = std::min(EM_DEPTH, std::max(1, env_d ? atoi(env_d) : EM_DEPTH));
     return s;
 }
 
@@ -1051,16 +1067,45 @@ struct EmKernels {
     bool ring_mstep;    // k3_mstep (LDS-DMA rings, mstep_ring.inc) instead of the register-staged k2_mstep
     bool multi_mstep;   // k4_mstep (several tiles per workgroup, mstep_multi.inc) instead of k3_mstep
 };
+// Small calls run the 4-wavefront E-step, which keeps one round per launch (its arithmetic is the same template body)
+static bool em_wide(const EmSwitches &sw, int n_jobs, int kmax) {
+    const bool wide = n_jobs <= sw.wide_maxjobs && kmax + 1 <= WIDE_MAX_COLUMNS;
+    return wide;
+}
+
+// Column slots per job of a call: the switch's cap, 1 where nothing runs ahead (the 4-wavefront E-step of small calls,
+// calls of fixed-inference jobs only), and no more than keeps the call inside the M-step kernels' limits - the 1,024
+// list entries per UTR of k2_mstep / k3_mstep and the 32-bit offsets of the LDS-DMA kernels (em_choose).
+static int em_depth(const std::vector<UtrDesc> &h_desc, int B, const EmSwitches &sw, int n_jobs, int kmax, const int32_t *job_utr,
+                    const int32_t *job_fixed) {
+    bool any_m = false;
+    size_t v1 = 0, pt1 = 0;
+    std::vector<int> per_utr(h_desc.size(), 0);
+    int max_jobs_utr = 1;
+    for (int j = 0; j < n_jobs; ++j) {
+        const UtrDesc &d = h_desc[job_utr[j]];
+        any_m = any_m || job_fixed[j] == 0;
+        v1 += (size_t)d.Np;
+        pt1 += (size_t)((d.T * B + MT_ROWS - 1) / MT_ROWS);
+        max_jobs_utr = std::max(max_jobs_utr, ++per_utr[job_utr[j]]);
+    }
+    if (!any_m || em_wide(sw, n_jobs, kmax)) return 1;
+    int depth = sw.depth;
+    while (depth > 1 && ((size_t)max_jobs_utr * depth > 1024 || v1 * depth * 8 >= ((size_t)1 << 31) || pt1 * depth >= ((size_t)1 << 31)))
+        --depth;
+    return depth;
+}
+
 static int em_choose(const EmPlan &p, const EmSwitches &sw, int n_jobs, int kmax, EmKernels &k) {
     // Small calls (the ~100 jobs of one UTR, or of a few streams' current UTRs) leave most of the GPU idle and an
     // M-step round takes as long as ONE workgroup needs for its pass over a tile: the jobs of a tile are then cut
     // into passes of 16 that separate workgroups take (k2_mstep).  Every score is the same MFMA chain either way,
     // so a UTR's result does not depend on the size of the call it is part of.
-    k.wide = n_jobs <= sw.wide_maxjobs && kmax + 1 <= WIDE_MAX_COLUMNS;
+    k.wide = em_wide(sw, n_jobs, kmax);
     k.job_split = (long long)p.active.size() * p.tiles_max <= sw.split_maxtiles;
     // k3_mstep unless SCAPE_HIP_MSTEP=v2 asks for k2_mstep (A/B runs; identical bits).  k3's DMA source offsets are
     // 32-bit byte offsets from the start of the job vectors.
-    k.ring_mstep = !sw.mstep_v2 && p.vtot * 8 < ((size_t)1 << 31);
+    k.ring_mstep = !sw.mstep_v2 && p.vtot * 8 < ((size_t)1 << 31);   // (totals over all column slots)
     // k4_mstep: set-up and epilogue off the critical path - the kernel of wave-sized calls; calls with few live tiles
     // keep k3_mstep with a tile's jobs cut into passes for several workgroups
     k.multi_mstep = k.ring_mstep && !k.job_split && !sw.debug && p.pttot < ((size_t)1 << 31) && !sw.mstep_v3;
@@ -1073,17 +1118,15 @@ static int em_choose(const EmPlan &p, const EmSwitches &sw, int n_jobs, int kmax
 
 static int em_upload(scape_hip_ctx *c, const EmPlan &p, size_t nj, int kmax) {
     EmBufs &e = c->em;
-    if (e.ensure(nj, kmax, c->n_utr, p.vtot, p.pttot)) return 1;
-    if (!p.elist.empty()) {
-        if (e.elist.ensure(nj * 4)) return 1;
-        HIPCHK(hipMemcpyAsync(e.elist.p, p.elist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
-    }
+    const size_t nc = nj * p.depth;
+    if (e.ensure(nj, nc, kmax, c->n_utr, p.vtot, p.pttot)) return 1;
+    HIPCHK(hipMemcpyAsync(e.elist.p, p.elist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
     if (!p.active.empty())
         HIPCHK(hipMemcpyAsync(e.active.p, p.active.data(), p.active.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(e.voff.p, p.voff.data(), nj * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(e.ptoff.p, p.ptoff.data(), nj * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.voff.p, p.voff.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.ptoff.p, p.ptoff.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(e.ujoff.p, p.ujoff.data(), p.ujoff.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(e.ujlist.p, p.ujlist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.ujlist.p, p.ujlist.data(), nc * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // the host vectors are pageable: the copies have left them now
     return 0;
 }
@@ -1099,6 +1142,13 @@ static void launch_estep(scape_hip_ctx *c, Kernel kernel, unsigned threads, cons
                        c->j_karr.as<int8_t>(), S, c->j_ao.as<int32_t>(), c->j_bo.as<int32_t>(), c->j_wso.as<double>(),
                        c->j_bic.as<double>(), c->j_nlb.as<int32_t>(), c->j_lb.as<double>(),
                        c->d_counters.as<unsigned long long>(), round..., job_list, n_jobs);
+}
+
+// The E-step launches of pass r of a call that runs ahead: one per column slot (the last pass only finalises: one).
+template <typename Kernel>
+static void launch_estep_slots(scape_hip_ctx *c, Kernel kernel, const EmState &S, int kmax, const int32_t *job_list, int n_jobs,
+                               int r, int slots, int depth) {
+    for (int slot = 0; slot < slots; ++slot) launch_estep(c, kernel, 64, S, kmax, job_list, n_jobs, r, slot, depth);
 }
 
 // One M-step launch.  `extent` is the second factor of the grid (tiles, or k4_mstep's tile groups, of the largest UTR);
@@ -1135,11 +1185,12 @@ static int em_debug_round(scape_hip_ctx *c, int r, int nround) {
     return 0;
 }
 
-// the rounds of one call: E-step, M-step, ... and a last E-step that finishes the jobs still running
+// the passes of one call: E-step, M-step, ... and a last E-step that finishes the jobs still running.  A job runs up
+// to p.depth rounds per pass (one k2_estep launch per slot) and at least one, so nround + 1 passes always do.
 static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, const EmKernels &k, int n_jobs, int kmax) {
     const EmState S = c->em.state();
     const int nround = c->prm.nround, n_active = (int)p.active.size();
-    const int32_t *jl = p.elist.empty() ? c->em.ujlist.as<int32_t>() : c->em.elist.as<int32_t>();
+    const int32_t *jl = c->em.elist.as<int32_t>();
     unsigned long long *dbg = nullptr;
     if (sw.debug) {
         if (c->em.dbg.ensure(24 * sizeof(unsigned long long))) return 1;
@@ -1147,7 +1198,7 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
         HIPCHK(hipMemsetAsync(dbg, 0, 24 * sizeof(unsigned long long), c->stream));
     }
     if (!p.any_m) {
-        // only fixed-inference jobs (the ws-only re-fits of rm_component): all rounds in one launch
+        // only fixed-inference jobs (the ws-only re-fits of rm_component): all rounds in one launch (depth 1: columns = jobs)
         if (sw.fine && ev_begin(c, 4)) return 1;
         if (!with_column_class(EstepClasses{}, kmax + 1, [&](auto cm) {
                 launch_estep(c, k2_estep_all_rounds<decltype(cm)::value>, 64, S, kmax, c->em.ujlist.as<int32_t>(), n_jobs);
@@ -1159,9 +1210,9 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
     }
     // few live tiles: passes of 16 jobs, one workgroup each (gridDim.y covers the longest job list of a UTR)
     const int jobs_per_pass = k.job_split ? 16 : MT_MAXJ;
-    const unsigned psplit = k.job_split ? (unsigned)std::min(64, (p.max_jobs_utr + 15) / 16) : 1u;
+    const unsigned psplit = k.job_split ? (unsigned)std::min(64, (p.max_cols_utr + 15) / 16) : 1u;
     unsigned long long executed_prev = 0;
-    const int probe_mask = (n_jobs >= 8192) ? 7 : 3;
+    const int probe_mask = (n_jobs >= 8192 && p.depth == 1) ? 7 : 3;
     for (int r = 0; r <= nround; ++r) {
         if (sw.fine && ev_begin(c, 4)) return 1;
         // K up to 63: the column arrays of the 64-column class live in scratch - slow, and rare (a re-run loop that keeps
@@ -1171,7 +1222,7 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
                          launch_estep(c, k2_estep_cs<decltype(cm)::value>, 256, S, kmax, jl, n_jobs, r);
                      })
                    : with_column_class(EstepClasses{}, kmax + 1, [&](auto cm) {
-                         launch_estep(c, k2_estep<decltype(cm)::value>, 64, S, kmax, jl, n_jobs, r);
+                         launch_estep_slots(c, k2_estep<decltype(cm)::value>, S, kmax, jl, n_jobs, r, r < nround ? p.depth : 1, p.depth);
                      });
         if (!launched) return fail("no E-step kernel for kmax " + std::to_string(kmax));
         HIPCHK(hipGetLastError());
@@ -1189,8 +1240,9 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
             if (sw.fine && ev_end(c, 5)) return 1;
         }
         // early exit: no job executed a round since the last probe -> every job has been finalised.  The probe waits for
-        // the stream (a bubble of a few tens of microseconds): every 4 rounds for small calls, whose jobs all finish
-        // early and whose rounds are short, every 8 for wave-sized ones, which run to the last round anyway
+        // the stream (a bubble of a few tens of microseconds): every 4 launches for small calls, whose jobs all finish
+        // early and whose rounds are short, and for calls that run ahead, which end well before launch nround; every 8
+        // for wave-sized ones at one round per launch, which run to the last round anyway
         if (r < nround && (r & probe_mask) == probe_mask) {
             unsigned long long executed = 0, shard[64];
             HIPCHK(hipMemcpyAsync(shard, c->d_counters.as<unsigned long long>() + CNT_EXEC, sizeof(shard),
@@ -1208,7 +1260,8 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
 // job tables are already on the device
 static int em_lockstep(scape_hip_ctx *c, int n_jobs, int kmax, const int32_t *job_utr, const int32_t *job_fixed) {
     const EmSwitches sw = em_switches();
-    const EmPlan plan = em_plan(c->h_desc, c->prm.B, (size_t)n_jobs, job_utr, job_fixed, sw.size_order);
+    const int depth = em_depth(c->h_desc, c->prm.B, sw, n_jobs, kmax, job_utr, job_fixed);
+    const EmPlan plan = em_plan(c->h_desc, c->prm.B, (size_t)n_jobs, job_utr, job_fixed, sw.size_order, depth);
     EmKernels kernels;
     if (em_choose(plan, sw, n_jobs, kmax, kernels) || em_upload(c, plan, (size_t)n_jobs, kmax)) return 1;
     return em_rounds(c, plan, sw, kernels, n_jobs, kmax);
@@ -1538,7 +1591,11 @@ int scape_hip_batch_bytes(scape_hip_ctx *c, int64_t *bytes_batch, int64_t *bytes
     CTX_ENTER(c);
     size_t f = 0, t = 0;
     HIPCHK(hipMemGetInfo(&f, &t));
-    if (bytes_batch) *bytes_batch = c->loaded ? (int64_t)((2 * c->at_total + c->m_total) * 8 + c->n_bins * 40) : 0;
+    // (+ the column vectors and per-tile partials of the batch's EM calls so far: EM_DEPTH slots per job, EmBufs)
+    if (bytes_batch)
+        *bytes_batch = c->loaded ? (int64_t)((2 * c->at_total + c->m_total) * 8 + c->n_bins * 40 + c->em.V.cap + c->em.Vsuf.cap +
+                                             c->em.pt_score.cap + c->em.pt_row.cap)
+                                 : 0;
     if (bytes_free) *bytes_free = (int64_t)f;
     if (bytes_total) *bytes_total = (int64_t)t;
     return 0;

@@ -27,7 +27,7 @@ import numpy as np
 from . import _lib
 from ._lib import Params, check, f64, i32, ptr, P_i32, P_i64, P_i8
 from . import _hostlib
-from .host import N_ROUND, N_TRIAL, FastSampler, Sampler, UtrPrep
+from .host import MODEL_DEFAULTS, N_ROUND, N_TRIAL, FastSampler, Sampler, UtrPrep
 
 
 @dataclass
@@ -423,10 +423,16 @@ class Engine:
               "batch_bytes")
         return int(fb.value * self.mem_fraction)
 
+    EM_DEPTH = 3     # column slots per job of an EM call (em_lockstep.inc: EM_DEPTH)
+
     @staticmethod
     def utr_bytes(q):
+        """Device bytes a UTR adds to a wave: its tensors, and the column vectors its sweep's jobs hold beyond one per
+        job (a job publishes up to EM_DEPTH M-step columns per launch: v and its suffix sums, 8.5 bytes per bin)."""
         npad = (q.N + 15) // 16 * 16
-        return 8 * npad * q.T * (len(q.betas) + 2) + 48 * q.N
+        p = getattr(q, "p", None) or MODEL_DEFAULTS
+        jobs = N_TRIAL * max(1, p["n_max_apa"] - p["n_min_apa"] + 1)
+        return 8 * npad * q.T * (len(q.betas) + 2) + 48 * q.N + (Engine.EM_DEPTH - 1) * jobs * npad * 17 // 2
 
     def close(self):
         """Release a private library handle (no-op for the shared per-device handle)."""
