@@ -335,6 +335,41 @@ int scape_hip_report_perm_len_groups(scape_hip_ctx *ctx, int32_t n_rec, const in
                                      int32_t n_groups, const int32_t *seg_off, const int32_t *q, const double *tol_stat,
                                      const double *tol_delta, int64_t *t_out, int64_t *a0_out, double *stat0_out,
                                      double *delta0_out, int64_t *n_ge_out, int64_t *group_n_ge_out);
+/* diff_pa_pairs: every pair of G = n_groups populations (2 <= G <= 64, sizes[g] >= 1 cells) tested as diff_pa tests two,
+   from one counts call.  The populations sit in the column segments seg_off in front of the count matrix, population 0's
+   columns first, as for scape_hip_report_perm_labels.  Pair k of n_pairs (1 .. 2016) is (pair_g[k], pair_h[k]),
+   0 <= g < h < G, population g against population h.  Its local positions are 0 .. sizes[g] - 1 for g's columns in order
+   and sizes[g] .. sizes[g] + sizes[h] - 1 for h's; permutation p >= 1 gives g the sizes[g] local positions with the
+   smallest key(p, local position), the key above, unchanged: the bits of pair k are those of
+   scape_hip_report_perm_masks(sizes[g], sizes[h], p_first, p_count, seed), bit for bit.
+   scape_hip_report_perm_pair_masks builds them for permutations p_first .. p_first + p_count - 1 on the device: per
+   pair ceil((sizes[g] + sizes[h]) / 64) words per permutation, laid out [pair's word offset + word][permutation], and one
+   8-byte key bound per (pair, permutation).  They are a buffer of their own, replace those of an earlier call and stay
+   until scape_hip_report_free.  Checked before anything is queued or released: 2 <= n_groups <= 64, every size >= 1,
+   1 <= n_pairs <= 2016, every pair 0 <= g < h < n_groups with fewer than 2^24 cells, p_first >= 1, p_count >= 1, fewer
+   than 2^31 words over all pairs; a call refused by a check keeps the earlier bits. */
+int scape_hip_report_perm_pair_masks(scape_hip_ctx *ctx, int32_t n_groups, const int32_t *sizes, int32_t n_pairs,
+                                     const int32_t *pair_g, const int32_t *pair_h, int64_t p_first, int32_t p_count,
+                                     uint64_t seed);
+/* The membership words of pair `pair` under permutation p_first + p (0 <= p < p_count) of the last pair masks call: bit
+   j % 64 of words_out[j / 64] is set when local position j is in the pair's first population. */
+int scape_hip_report_perm_pair_bits_get(scape_hip_ctx *ctx, int32_t pair, int32_t p, uint64_t *words_out);
+/* The test of n_rec records of the last counts call by the pairs pair_first .. pair_first + pair_count - 1 of the last
+   pair masks call; records, kept rows and the ADD semantics as in scape_hip_report_perm_test, n_groups / seg_off checked
+   against the pair masks call as scape_hip_report_perm_groups checks them against the labels call.  The rows are those
+   kept over ALL groups.  t_out[i] = the row's sum over the tested columns, a0_out[i * n_groups + g] = its sum over group
+   g, so for pair (g, h) t_i = a0[i][g] + a0[i][h].  The pair tests record r when at least two of its rows have t_i > 0
+   and both populations have reads; then, over the rows with t_i > 0 in order, S and d_i are those of
+   scape_hip_report_perm_test (one device function, contraction off, the same 1 - 2^-40 slack; a row with t_i = 0 adds
+   exactly 0.0), so stat0_out[k * n_rec + r] has the bits, and site_n_ge_out[k * n_rows + i] (ADDED to; rows with t_i = 0
+   are left alone) and gene_n_ge_out[k * n_rec + r] (ADDED to) the values, of a scape_hip_report_perm_test call on the
+   pair's own two populations, k counting from pair_first.  For a record the pair does not test stat0_out is 0 and nothing
+   is added.  pair_count * n_rec < 2^31.
+   LDS: 1 KiB per row of a record held at once, in the classes 4 .. 64 rows of scape_hip_report_perm_test. */
+int scape_hip_report_perm_pairs(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                int32_t n_groups, const int32_t *seg_off, int32_t pair_first, int32_t pair_count,
+                                int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
+                                int64_t *gene_n_ge_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

@@ -1,5 +1,6 @@
 // perm.inc - the permutation tests on merge_pa's count matrix: diff_pa and diff_pa_len (freely or within strata),
-// diff_pa_groups and diff_pa_len_groups (included by scape_hip.hip after report.inc, whose ReportState, block helpers and k_rep_scan it uses).
+// diff_pa_groups, diff_pa_len_groups and diff_pa_pairs (included by scape_hip.hip after report.inc, whose ReportState,
+// block helpers and k_rep_scan it uses).
 //
 // A test is two calls.  The first builds the labellings of a chunk of permutations, in exact integers:
 //   rep_select_key  the one radix select of the file: the key of a given rank among the hashed 64-bit keys of a set of
@@ -24,6 +25,10 @@
 //   k_rep_len_groups_obs / k_rep_perm_len_groups
 //                   diff_pa_len_groups: the same for the mean pA position, G pairs of exact integer sums per permutation
 //                   in LDS, the groups in slices of at most 32
+//   k_rep_perm_pair_masks / k_rep_pair_segidx / k_rep_perm_pairs
+//                   diff_pa_pairs: the membership bits of every (pair of populations, permutation), per kept row the
+//                   first nonzero of every population's column segment, and diff_pa's test for every pair from the one
+//                   compaction, a pair walking the nonzeros of its two segments only
 // The exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
 // stay on the host (scape_amd/report.py).
 
@@ -805,6 +810,166 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_groups(
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&rec_ge[r], __popcll(b));
 }
 
+// ---- diff_pa_pairs: every pair of the G populations, each as diff_pa --------------------------------------------------
+// The G populations sit in the column segments seg_off in front of the count matrix, as for the G-way tests.  Pair
+// (g, h) is diff_pa of population g against population h: its local positions are 0 .. n_g - 1 for g's columns in
+// order and n_g .. n_g + n_h - 1 for h's, permutation p >= 1 gives g the n_g local positions with the smallest
+// key(p, local position) - the key, the seed and so the labellings of scape_hip_report_perm_masks(n_g, n_h) - and the
+// statistics are rep_perm_row's, rows in order.  The kept rows are compacted ONCE over all n positions; a row without a
+// read in the pair has t_i = 0 there, adds exactly 0.0 to S (rep_perm_row) and owns no counter the host reads, so S has
+// the bits that scape_hip_report_perm_test forms from the pair's own rows.
+struct RepPair {
+    int32_t g, h, n_g, n_h;       // the two populations and their cells
+    int32_t woff, pad[3];         // first mask word of the pair (the words of all pairs together stay below 2^31)
+};
+
+// one workgroup per (permutation p_first + blockIdx.x, pair blockIdx.y): the n_g-th smallest key among the pair's local
+// positions, by wave 0 alone for up to REP_STRATA_WAVE_MAX cells (one "stratum" of every cell: position i = cell i) and
+// by rep_select_key for more; bound[pair][permutation] = that key + 1; then bit j = (key(j) < bound) of
+// bits[(woff + j / 64) * p_count + blockIdx.x], the layout k_rep_perm_test reads.  The branch is uniform over the
+// workgroup (it depends on the pair only).
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_pair_masks(const RepPair *__restrict__ pairs,
+                                                                     unsigned long long p_first, int32_t p_count,
+                                                                     unsigned long long seed, unsigned long long *bound,
+                                                                     unsigned long long *__restrict__ bits) {
+    __shared__ RepSelectLds lds;
+    const RepPair pr = pairs[blockIdx.y];
+    const int n = pr.n_g + pr.n_h;
+    const unsigned long long base = rep_mix(seed + REP_PERM_G * (p_first + blockIdx.x));
+    unsigned long long *bound_p = bound + (int64_t)blockIdx.y * p_count + blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (n <= REP_STRATA_WAVE_MAX) {
+        const int4 d = make_int4(0, pr.n_g, pr.n_g, pr.n_h);
+        if (wave == 0) {
+            if (n <= 64) rep_strata_wave<1>(base, d, lane, bound_p);
+            else rep_strata_wave<REP_STRATA_WAVE_MAX / 64>(base, d, lane, bound_p);
+        }
+    } else {
+        unsigned long long k;
+        if (rep_select_key(base, RepAllCells{n}, pr.n_g - 1, &lds, &k)) *bound_p = k + 1;
+    }
+    __syncthreads();                         // this labelling's bound is stored
+    const unsigned long long b = *bound_p;
+    const int n_words = (n + 63) >> 6;
+    for (int w = wave; w < n_words; w += REP_WAVES) {
+        const int j = w * 64 + lane;
+        const unsigned long long m = __ballot(j < n && rep_perm_key(base, j) < b);
+        if (lane == 0) bits[((int64_t)pr.woff + w) * p_count + blockIdx.x] = m;
+    }
+}
+
+// one thread per (kept row i, g = 0 .. n_groups): seg[i * (n_groups + 1) + g] = the first nonzero of the row at or beyond
+// column seg_off[g] (binary search; the row's positions ascend), so the nonzeros of group g are seg[..g] .. seg[..g + 1]
+__global__ __launch_bounds__(REP_THREADS) void k_rep_pair_segidx(const int64_t *__restrict__ noff,
+                                                                 const uint2 *__restrict__ nz,
+                                                                 const int32_t *__restrict__ seg_off, int32_t n_groups,
+                                                                 int64_t n_rows, int64_t *__restrict__ seg) {
+    const int64_t idx = (int64_t)blockIdx.x * REP_THREADS + threadIdx.x;
+    if (idx >= n_rows * (n_groups + 1)) return;
+    const int64_t i = idx / (n_groups + 1);
+    const uint32_t col = (uint32_t)seg_off[idx % (n_groups + 1)];
+    int64_t lo = noff[i], hi = noff[i + 1];
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (nz[mid].x < col) lo = mid + 1;
+        else hi = mid;
+    }
+    seg[idx] = lo;
+}
+
+// the nonzeros nz[k0 .. k1) of one segment, at the local positions column + shift, added under this lane's labelling as
+// rep_perm_rowsum adds them: wave-uniform nonzeros, a mask word loaded once for the nonzeros that fall into it
+__device__ __forceinline__ int rep_pair_segsum(const uint2 *__restrict__ nz, int64_t k0, int64_t k1, int shift,
+                                               const unsigned long long *__restrict__ mb, int64_t pstride) {
+    int a = 0, cur = -1;
+    unsigned long long w = 0;
+    for (int64_t k = k0; k < k1; ++k) {
+        const uint2 e = nz[k];
+        const int pos = __builtin_amdgcn_readfirstlane((int)e.x) + shift, c = __builtin_amdgcn_readfirstlane((int)e.y);
+        if ((pos >> 6) != cur) {
+            cur = pos >> 6;
+            w = mb[(int64_t)cur * pstride];
+        }
+        a += ((w >> (pos & 63)) & 1) ? c : 0;
+    }
+    return a;
+}
+
+// workgroup = (pair pair_first + blockIdx.y, record recs[blockIdx.x / n_tiles], tile of 256 permutations), one lane per
+// permutation, as k_rep_perm_test: a_i(p) of the record's rows in LDS as acc[row][lane] (each lane its own column, no
+// barrier), a record with more than `cap` rows in groups of cap rows behind one extra walk that forms A(p).  sg[i] =
+// the row's G + 1 segment starts, a0[i * n_groups + g] its observed sum over group g: t_i, T and A(0) of the pair come
+// from them.  The pair tests the record when two rows or more have a read in it and both populations have reads;
+// otherwise the workgroup stores S(0) = 0 and leaves (uniform: the decision reads the record's sums only).  A row with
+// t_i = 0 is passed over: its share of S is exactly 0.0.  Counters: site_ge[pair in range][row], gene_ge and
+// stat0[pair in range][record], one atomic per wave and counter.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_pairs(
+    const unsigned long long *__restrict__ bits, int32_t p_count, int32_t n_tiles, const int32_t *__restrict__ recs,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
+    const int64_t *__restrict__ a0, int32_t n_groups, const int32_t *__restrict__ seg_off,
+    const RepPair *__restrict__ pairs, int64_t n_rows, int32_t n_rec, int32_t cap, int32_t *__restrict__ site_ge,
+    int32_t *__restrict__ gene_ge, double *__restrict__ stat0) {
+#pragma clang fp contract(off)
+    extern __shared__ int32_t rep_acc[];
+    const RepPair pr = pairs[blockIdx.y];
+    const int g = pr.g, h = pr.h, sh_g = -seg_off[g], sh_h = pr.n_g - seg_off[h];
+    const int r = recs[blockIdx.x / n_tiles], tile = blockIdx.x % n_tiles;
+    const int64_t out_r = (int64_t)blockIdx.y * n_rec + r;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    long long T = 0, A0 = 0;
+    int with_reads = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        const long long ag = a0[i * n_groups + g], ah = a0[i * n_groups + h];
+        T += ag + ah;
+        A0 += ag;
+        with_reads += ag + ah > 0;
+    }
+    if (with_reads < 2 || A0 == 0 || A0 == T) {
+        if (tile == 0 && threadIdx.x == 0) stat0[out_r] = 0.0;
+        return;
+    }
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const unsigned long long *mb = bits + (int64_t)pr.woff * p_count + (valid ? p : p_count - 1);
+    int32_t *acc = rep_acc + threadIdx.x;
+    int32_t *site = site_ge + (int64_t)blockIdx.y * n_rows;
+    const int stride = n_groups + 1;
+    long long A = 0;
+    const bool one = row1 - row0 <= cap;
+    if (!one)
+        for (int64_t i = row0; i < row1; ++i) {
+            const int64_t *si = sg + i * stride;
+            A += rep_pair_segsum(nz, si[g], si[g + 1], sh_g, mb, p_count) +
+                 rep_pair_segsum(nz, si[h], si[h + 1], sh_h, mb, p_count);
+        }
+    double S = 0.0, S0 = 0.0;
+    for (int64_t g0 = row0; g0 < row1; g0 += cap) {
+        const int64_t g1 = g0 + cap < row1 ? g0 + cap : row1;
+        long long Ag = 0;
+        for (int64_t i = g0; i < g1; ++i) {
+            const int64_t *si = sg + i * stride;
+            const int a = rep_pair_segsum(nz, si[g], si[g + 1], sh_g, mb, p_count) +
+                          rep_pair_segsum(nz, si[h], si[h + 1], sh_h, mb, p_count);
+            acc[(i - g0) * REP_THREADS] = a;
+            Ag += a;
+        }
+        if (one) A = Ag;
+        for (int64_t i = g0; i < g1; ++i) {
+            const long long a0i = a0[i * n_groups + g], ti = a0i + a0[i * n_groups + h];
+            if (ti == 0) continue;
+            double d, d0;
+            S = S + rep_perm_row(acc[(i - g0) * REP_THREADS], ti, A, T, &d);
+            S0 = S0 + rep_perm_row(a0i, ti, A0, T, &d0);
+            const unsigned long long b = __ballot(valid && fabs(d) >= fabs(d0) * REP_PERM_SLACK);
+            if ((threadIdx.x & 63) == 0 && b) atomicAdd(&site[i], __popcll(b));
+        }
+    }
+    const unsigned long long b = __ballot(valid && S >= S0 * REP_PERM_SLACK);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[out_r], __popcll(b));
+    if (tile == 0 && threadIdx.x == 0) stat0[out_r] = S0;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
 
@@ -1220,6 +1385,132 @@ int scape_hip_report_perm_len_groups(scape_hip_ctx *c, int32_t n_rec, const int6
                            s->p_gene.as<int32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(delta0_out, s->v_d0.p, n_pairs * 8, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    });
+}
+
+int scape_hip_report_perm_pair_masks(scape_hip_ctx *c, int32_t n_groups, const int32_t *sizes, int32_t n_pairs,
+                                     const int32_t *pair_g, const int32_t *pair_h, int64_t p_first, int32_t p_count,
+                                     uint64_t seed) {
+    CTX_ENTER(c);
+    if (n_groups < 2 || n_groups > REP_GROUPS_MAX)
+        return fail("n_groups must lie in 2 .. " + std::to_string(REP_GROUPS_MAX));
+    if (n_pairs < 1 || n_pairs > REP_GROUPS_MAX * (REP_GROUPS_MAX - 1) / 2)
+        return fail("n_pairs must lie in 1 .. " + std::to_string(REP_GROUPS_MAX * (REP_GROUPS_MAX - 1) / 2));
+    if (!sizes || !pair_g || !pair_h) return fail("bad argument");
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (sizes[g] < 1) return fail("group " + std::to_string(g) + ": every group needs at least one cell");
+    std::vector<int32_t> pairs((size_t)n_pairs * 8, 0);
+    int64_t words = 0;
+    for (int32_t k = 0; k < n_pairs; ++k) {
+        const int32_t g = pair_g[k], h = pair_h[k];
+        if (g < 0 || h >= n_groups || g >= h)
+            return fail("pair " + std::to_string(k) + ": the groups must satisfy 0 <= g < h < n_groups");
+        const int64_t n = (int64_t)sizes[g] + sizes[h];
+        if (rep_perm_chunk_ok(n, "a pair's cells must number", p_first, p_count)) return 1;
+        int32_t *d = &pairs[(size_t)k * 8];
+        d[0] = g, d[1] = h, d[2] = sizes[g], d[3] = sizes[h], d[4] = (int32_t)words;
+        words += (n + 63) / 64;
+        if (words > INT32_MAX) return fail("the pairs' mask words together must number below 2^31");
+    }
+    ReportState *s = report_state(c);
+    s->x_count = 0;
+    if (s->x_bits.ensure(words * p_count * 8) || s->x_bound.ensure((int64_t)n_pairs * p_count * 8) ||
+        s->x_desc.ensure((int64_t)n_pairs * 32))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->x_desc.p, pairs.data(), (int64_t)n_pairs * 32, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_perm_pair_masks, dim3(p_count, n_pairs), dim3(REP_THREADS), 0, c->stream,
+                       s->x_desc.as<RepPair>(), (unsigned long long)p_first, p_count, (unsigned long long)seed,
+                       s->x_bound.as<unsigned long long>(), s->x_bits.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    s->x_pairs.swap(pairs);
+    s->x_sizes.assign(sizes, sizes + n_groups);
+    s->x_count = p_count;
+    return 0;
+}
+
+int scape_hip_report_perm_pair_bits_get(scape_hip_ctx *c, int32_t pair, int32_t p, uint64_t *words_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->x_count) return fail("scape_hip_report_perm_pair_masks has not been called");
+    if (!words_out) return fail("bad argument");
+    if (pair < 0 || pair >= (int32_t)(s->x_pairs.size() / 8)) return fail("pair must name a pair of the last pair masks call");
+    if (p < 0 || p >= s->x_count) return fail("p must name a permutation of the last pair masks call");
+    const int32_t *d = &s->x_pairs[(size_t)pair * 8];
+    const int32_t n_words = (d[2] + d[3] + 63) / 64;
+    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->x_bits.as<unsigned long long>() + (int64_t)d[4] * s->x_count + p,
+                            (size_t)s->x_count * 8, 8, n_words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int scape_hip_report_perm_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                int32_t n_groups, const int32_t *seg_off, int32_t pair_first, int32_t pair_count,
+                                int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
+                                int64_t *gene_n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (rep_perm_ready(s, s ? s->x_count : 0, "scape_hip_report_perm_pair_masks")) return 1;
+    if (!seg_off) return fail("bad argument");
+    if (n_groups != (int32_t)s->x_sizes.size())
+        return fail("n_groups differs from the last scape_hip_report_perm_pair_masks call");
+    if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (seg_off[g + 1] - seg_off[g] != s->x_sizes[g])
+            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last scape_hip_report_perm_pair_masks call");
+    const int32_t n_pairs = (int32_t)(s->x_pairs.size() / 8);
+    if (pair_first < 0 || pair_count < 1 || pair_first > n_pairs - pair_count)
+        return fail("pair_first and pair_count must name pairs of the last scape_hip_report_perm_pair_masks call");
+    if (n_rec > 0 && rec_row_off && ((int64_t)pair_count * n_rec > INT32_MAX ||
+                                     rec_row_off[n_rec] > INT64_MAX / 8 / pair_count))
+        return fail("too many pairs x records or pairs x rows for one call: take the pairs in ranges");
+    int64_t n_rows = 0;
+    int32_t n_tiles = 0;
+    if (rep_perm_prepare(c, seg_off[n_groups], s->x_count, "pair masks", 0, n_groups, seg_off, n_rec, rec_row_off, rows,
+                         t_out, a0_out, site_n_ge_out && stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr,
+                         nullptr, &n_rows, &n_tiles))
+        return 1;
+    const int64_t n_seg = n_rows * (n_groups + 1), n_out = (int64_t)pair_count * n_rec;
+    if ((n_seg + REP_THREADS - 1) / REP_THREADS > INT32_MAX) return fail("too many rows x groups for one call");
+    if (s->p_recs.ensure((int64_t)n_rec * 4) || s->x_seg.ensure(n_seg * 8) || s->p_gene.ensure(n_out * 4) ||
+        s->p_stat0.ensure(n_out * 8))
+        return 1;
+
+    // records by LDS class, as scape_hip_report_perm_test takes them, on the rows kept over all groups
+    const int n_caps = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
+    std::vector<std::vector<int32_t>> by_cap(n_caps);
+    for (int r = 0; r < n_rec; ++r) {
+        const int64_t k = rec_row_off[r + 1] - rec_row_off[r];
+        int q = 0;
+        while (q < n_caps - 1 && k > REP_PERM_CAPS[q]) ++q;
+        by_cap[q].push_back(r);
+    }
+    std::vector<int32_t> recs;
+    for (auto &v : by_cap) recs.insert(recs.end(), v.begin(), v.end());
+    return rep_perm_count(c, pair_count * n_rows, (int32_t)n_out, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(s->p_recs.p, recs.data(), (int64_t)n_rec * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_rep_pair_segidx, dim3((uint32_t)((n_seg + REP_THREADS - 1) / REP_THREADS)),
+                           dim3(REP_THREADS), 0, c->stream, s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
+                           s->q_seg.as<int32_t>(), n_groups, n_rows, s->x_seg.as<int64_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_pairs),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   REP_PERM_CAPS[n_caps - 1] * REP_THREADS * 4));
+        int64_t first = 0;
+        for (int q = 0; q < n_caps; ++q) {
+            const int64_t m = (int64_t)by_cap[q].size();
+            if (!m) continue;
+            const int32_t cap = REP_PERM_CAPS[q];
+            hipLaunchKernelGGL(k_rep_perm_pairs, dim3((uint32_t)(m * n_tiles), (uint32_t)pair_count), dim3(REP_THREADS),
+                               (size_t)cap * REP_THREADS * 4, c->stream, s->x_bits.as<unsigned long long>(), s->x_count,
+                               n_tiles, s->p_recs.as<int32_t>() + first, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(),
+                               s->p_nz.as<uint2>(), s->q_a0.as<int64_t>(), n_groups, s->q_seg.as<int32_t>(),
+                               s->x_desc.as<RepPair>() + pair_first, n_rows, n_rec, cap, s->p_site.as<int32_t>(),
+                               s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
+            HIPCHK(hipGetLastError());
+            first += m;
+        }
         return 0;
     });
 }

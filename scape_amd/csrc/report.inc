@@ -60,6 +60,13 @@ struct ReportState {
     // and per record (Q, T), (double)Q / (double)T and the G observed d_g
     DevBuf v_q, v_tol, v_qt, v_mean, v_d0;
     int32_t q_n = 0, q_count = 0;
+    // diff_pa_pairs: the membership bits of every (pair, permutation) of the last scape_hip_report_perm_pair_masks call
+    // ([pair's word offset + word][permutation]), the exclusive key bound per (pair, permutation), (g, h, n_g, word
+    // offset) per pair on the device and on the host, and per kept row and group the first nonzero at or beyond the
+    // group's segment (scape_hip_report_perm_pairs)
+    DevBuf x_bits, x_bound, x_desc, x_seg;
+    std::vector<int32_t> x_pairs, x_sizes;
+    int32_t x_count = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
@@ -87,7 +94,7 @@ static void report_release(scape_hip_ctx *c) {
                      &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
                      &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound,
                      &s->q_lab, &s->q_cut, &s->q_seg, &s->q_a0, &s->q_s0, &s->q_share, &s->v_q, &s->v_tol, &s->v_qt,
-                     &s->v_mean, &s->v_d0};
+                     &s->v_mean, &s->v_d0, &s->x_bits, &s->x_bound, &s->x_desc, &s->x_seg};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;

@@ -37,6 +37,8 @@ device's rendering of one text block with the gzip of the previous one.
   file, or the ones named): the same keys rank the cells, the device cuts the ranking into the populations' sizes (one
   byte per cell and permutation) and accumulates one sum per row, population and permutation in LDS (section
   diff_pa_groups below).
+* ``diff_pa_pairs``: ``diff_pa`` for every pair of those populations from one pass over the result file, the p-values
+  adjusted over all pairs (section diff_pa_pairs below).
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -668,9 +670,15 @@ def _bh(p):
 
 def _perm_masks(ctx, su, p_first, p_count, seed, times):
     """the membership bits of p_count permutations from p_first on: relabelled within su.strata = (m1, m2) when given,
-    freely otherwise; for diff_pa_groups and diff_pa_len_groups (su.sizes = cells per group) the group bytes instead"""
+    freely otherwise; for diff_pa_groups and diff_pa_len_groups (su.sizes = cells per group) the group bytes instead;
+    for diff_pa_pairs (su.pairs = the two groups of every pair) the membership bits of every pair"""
     t0 = timer()
-    if su.sizes is not None:
+    if su.pairs is not None:
+        pair_g, pair_h = su.pairs
+        check(ctx.lib.scape_hip_report_perm_pair_masks(ctx.h, len(su.sizes), ptr(su.sizes, P_i32), len(pair_g),
+                                                       ptr(pair_g, P_i32), ptr(pair_h, P_i32), p_first, p_count, seed),
+              "report_perm_pair_masks")
+    elif su.sizes is not None:
         check(ctx.lib.scape_hip_report_perm_labels(ctx.h, len(su.sizes), ptr(su.sizes, P_i32), p_first, p_count, seed),
               "report_perm_labels")
     elif su.strata is not None:
@@ -829,7 +837,7 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
         raise ValueError(f"{n1 + n2} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + f"{by}.{command}.csv"
     return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
-                           strata=strata, left_out=left_out, sizes=None,
+                           strata=strata, left_out=left_out, sizes=None, pairs=None,
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"),
                            versus=f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1))
 
@@ -851,7 +859,10 @@ def _perm_run(su, n_perm, seed, device, batch, write):
         with open(run.parts[0], "w", newline="") as fh:
             ctx = run.device()
             budget = _budget(ctx)
-            if su.sizes is not None:
+            if su.pairs is not None:
+                # diff_pa_pairs: per pair its bits and the device's key bound per permutation
+                word_bytes = int(sum((int(su.sizes[g]) + int(su.sizes[h]) + 63) // 64 * 8 + 8 for g, h in zip(*su.pairs)))
+            elif su.sizes is not None:
                 word_bytes = int(su.sizes.sum())         # the G-way commands: one byte per tested cell and permutation
             else:
                 # the bits, and the device's key bound per permutation and stratum (one stratum without --strata_file)
@@ -869,6 +880,32 @@ def _perm_run(su, n_perm, seed, device, batch, write):
             write(csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n'))
             times["finish"] += timer() - t0
     return run.total
+
+
+def _reprs(v):
+    return [repr(x) for x in v.tolist()]
+
+
+def _diff_pa_columns(genes, lines, n1, n2, n_perm):
+    """what diff_pa's lines hold apart from the adjusted p-values, from the per-line integers `lines` and `genes` =
+    (gene_info_str, lines, S(0), gene_n_ge) per tested record of populations with n1 and n2 cells: the text columns
+    gene, pa, pct1, pct2, usage (usage.1, usage.2, delta_usage), n_ge, stat0 and gene_ge per line, the p-values p_val
+    per line and gene_p per record as arrays, and rec_of = the record of every line"""
+    t, a, nz1, nz2, n_ge = (np.concatenate(lines[k]) for k in ("t", "a", "nz1", "nz2", "n_ge"))
+    n_lines = np.array([g[1] for g in genes], dtype=np.int64)
+    rec_of = np.repeat(np.arange(len(genes)), n_lines)
+    first = np.concatenate([[0], np.cumsum(n_lines)[:-1]])
+    A, T = np.add.reduceat(a, first), np.add.reduceat(t, first)
+    Al, Tl = A[rec_of], T[rec_of]
+    Bl = Tl - Al
+    N = (a * Tl - t * Al).astype(np.float64)
+    ab = Al.astype(np.float64) * Bl.astype(np.float64)
+    gene_ge = np.array([g[3] for g in genes], dtype=np.int64)
+    stat0 = np.array([g[2] for g in genes])
+    return SimpleNamespace(gene=[genes[g][0] for g in rec_of.tolist()], pa=lines["pa"], pct1=_reprs(nz1 / n1),
+                           pct2=_reprs(nz2 / n2), usage=[_reprs(v) for v in (a / Al, (t - a) / Bl, N / ab)],
+                           n_ge=n_ge.tolist(), p_val=(1 + n_ge) / (1 + n_perm), stat0=_reprs(stat0[rec_of]),
+                           gene_ge=gene_ge[rec_of].tolist(), gene_p=(1 + gene_ge) / (1 + n_perm), rec_of=rec_of)
 
 
 def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
@@ -890,33 +927,11 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
         w.writerow(DIFF_PA_HEADER)
         if not genes:
             return
-        t, a, nz1, nz2, n_ge = (np.concatenate(lines[k]) for k in ("t", "a", "nz1", "nz2", "n_ge"))
-        n_lines = np.array([g[1] for g in genes], dtype=np.int64)
-        rec_of = np.repeat(np.arange(len(genes)), n_lines)
-        first = np.concatenate([[0], np.cumsum(n_lines)[:-1]])
-        A, T = np.add.reduceat(a, first), np.add.reduceat(t, first)
-        Al, Tl = A[rec_of], T[rec_of]
-        Bl = Tl - Al
-        N = (a * Tl - t * Al).astype(np.float64)
-        ab = Al.astype(np.float64) * Bl.astype(np.float64)
-        p_val = (1 + n_ge) / (1 + n_perm)
-        gene_ge = np.array([g[3] for g in genes], dtype=np.int64)
-        gene_p = (1 + gene_ge) / (1 + n_perm)
-        gene_adj = _bh(gene_p)
-        cols = [[genes[g][0] for g in rec_of.tolist()], lines["pa"],
-                [repr(v) for v in (nz1 / n1).tolist()], [repr(v) for v in (nz2 / n2).tolist()],
-                [versus] * len(t)]
-        stat0 = np.array([g[2] for g in genes])
-        for v in (a / Al, (t - a) / Bl, N / ab):
-            cols.append([repr(x) for x in v.tolist()])
-        cols.append(n_ge.tolist())
-        for v in (p_val, _bh(p_val), stat0[rec_of]):
-            cols.append([repr(x) for x in v.tolist()])
-        cols.append(gene_ge[rec_of].tolist())
-        for v in (gene_p[rec_of], gene_adj[rec_of]):
-            cols.append([repr(x) for x in v.tolist()])
-        cols.append([n_perm] * len(t))
-        w.writerows(zip(*cols))
+        c = _diff_pa_columns(genes, lines, n1, n2, n_perm)
+        gene_adj = _bh(c.gene_p)
+        w.writerows(zip(c.gene, c.pa, c.pct1, c.pct2, [versus] * len(c.pa), *c.usage, c.n_ge, _reprs(c.p_val),
+                        _reprs(_bh(c.p_val)), c.stat0, c.gene_ge, _reprs(c.gene_p[c.rec_of]), _reprs(gene_adj[c.rec_of]),
+                        [n_perm] * len(c.pa)))
 
     wall = _perm_run(su, n_perm, seed, device, batch, write)
     print(f"Finish {n_perm} permutations of {n1} + {n2} cells for {sum(g[1] for g in genes)} pA sites of "
@@ -1116,7 +1131,7 @@ def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, s
     if int(sizes.sum()) >= MAX_PERM_CELLS:
         raise ValueError(f"{int(sizes.sum())} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + f".{command}.csv"
-    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, strata=None,
+    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, strata=None, pairs=None,
                            names=[name for name, _cols in pops], outpath=outpath,
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
 
@@ -1213,6 +1228,109 @@ def _diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     wall = _perm_run(su, n_perm, seed, device, batch, write)
     print(f"Finish {n_perm} permutations of {int(su.sizes.sum())} cells in {G} populations for "
           f"{sum(g[1] for g in genes)} pA sites of {len(genes)} tested records")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- diff_pa_pairs
+# What lies behind a significant diff_pa_groups: every pair of the populations tested as diff_pa tests two, in one run.
+# Options, populations, checks, column layout and file naming are diff_pa_groups's.  The pairs are all (g, h), g < h in
+# population order, in lexicographic order; that is also the order of the file's blocks.  Pair (A, B) is exactly
+# `diff_pa --idents_1 A --idents_2 B` with the same --seed and --n_perm: local positions 0 .. n_A - 1 for A's columns
+# ascending, then n_A .. n_A + n_B - 1 for B's, permutation p gives A the n_A local positions with the smallest
+# key(p, local position), the kept rows are the record's label rows with a read in a cell of A or B, the pair tests a
+# record when two such rows or more remain and both A and B have reads, and S and d_i go through the device function of
+# diff_pa with its slack: t, a, n_ge, gene_n_ge and the bits of gene_stat are diff_pa's.  One line per (pair, kept row
+# of a record that the pair tests).  p_val_adj is Benjamini-Hochberg over ALL lines of the file, gene_p_val_adj over all
+# tested (pair, record) combinations of the file: the correction across the G (G - 1) / 2 runs.  The counts are read and
+# counted once; the device holds, per permutation, the sum over the pairs of (mask words x 8 + one 8-byte key bound).
+DIFF_PA_PAIRS_HEADER = DIFF_PA_HEADER[:2] + ["group_1", "group_2"] + DIFF_PA_HEADER[2:]
+MAX_PAIR_RESULT_BYTES = 256 << 20     # host and device bytes of the counters of one call: more pairs are taken in ranges
+
+
+def _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, seed, blocks, times):
+    """one counted batch: the rows kept over all populations of the records that two populations or more have reads in
+    go through every pair's test, the pairs in ranges of at most MAX_PAIR_RESULT_BYTES of counters; appends to
+    blocks[k] = (lines, genes) of pair k what _diff_pa_batch appends for the two populations of that pair"""
+    sel = _perm_rows(ctx, bat, su.seg_off, times)
+    if sel is None:
+        return
+    recs, G = bat.recs, len(su.sizes)
+    which, off, rows, nz, sums, rowbase = sel
+    pair_g, pair_h = su.pairs
+    n_pairs, n_rows, n_rec = len(pair_g), len(rows), len(which)
+    t, a0 = np.zeros(n_rows, np.int64), np.zeros((n_rows, G), np.int64)
+    site_ge, gene_ge = np.zeros((n_pairs, n_rows), np.int64), np.zeros((n_pairs, n_rec), np.int64)
+    stat0 = np.zeros((n_pairs, n_rec), np.float64)
+    step = int(max(1, min(n_pairs, MAX_PAIR_RESULT_BYTES // (12 * n_rows + 20 * n_rec))))
+
+    def test():
+        for k in range(0, n_pairs, step):
+            m = min(step, n_pairs - k)
+            check(ctx.lib.scape_hip_report_perm_pairs(ctx.h, n_rec, ptr(off, P_i64), ptr(rows, P_i64), G,
+                                                      ptr(su.seg_off, P_i32), k, m, ptr(t, P_i64), ptr(a0, P_i64),
+                                                      ptr(site_ge[k:k + m], P_i64), ptr(stat0[k:k + m]),
+                                                      ptr(gene_ge[k:k + m], P_i64)), "report_perm_pairs")
+    _perm_chunks(ctx, su, n_perm, chunk, seed, times, test)
+    t0 = timer()
+    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums)):
+        raise _lib.ScapeHipError("report_perm_pairs: row sums differ from report_group_sums")
+    pa = np.array(_pa_infos(recs, np.repeat(which, np.diff(off)), rows - rowbase[np.repeat(which, np.diff(off))]),
+                  dtype=object)
+    rec_of = np.repeat(np.arange(n_rec), np.diff(off))
+    for k, (g, h) in enumerate(zip(pair_g.tolist(), pair_h.tolist())):
+        tk = sums[:, g] + sums[:, h]
+        A, T = np.add.reduceat(sums[:, g], off[:-1]), np.add.reduceat(tk, off[:-1])
+        tested = (np.bincount(rec_of[tk > 0], minlength=n_rec) >= 2) & (A > 0) & (A < T)
+        keep = (tk > 0) & tested[rec_of]
+        if not keep.any():
+            continue
+        lines, genes = blocks[k]
+        n_lines = np.bincount(rec_of[keep], minlength=n_rec)
+        for r in np.nonzero(tested)[0].tolist():
+            genes.append((recs[which[r]].gene_info_str, int(n_lines[r]), float(stat0[k, r]), int(gene_ge[k, r])))
+        lines["pa"].extend(pa[keep].tolist())
+        for key, arr in (("t", tk), ("a", sums[:, g]), ("nz1", nz[:, g]), ("nz2", nz[:, h]), ("n_ge", site_ge[k])):
+            lines[key].append(np.asarray(arr[keep], dtype=np.int64))
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
+                   seed: int = 1, device=None):
+    """diff_pa for every pair of the populations of a cluster file (every cluster, or the clusters `idents` in the order
+    given) from one pass over the result file; writes <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_pairs.csv in
+    output_dir, one block per pair, the p-values adjusted over the whole file, and returns its path"""
+    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_pairs")
+    names, G = su.names, len(su.sizes)
+    pairs = [(g, h) for g in range(G) for h in range(g + 1, G)]
+    su.pairs = (np.array([g for g, _h in pairs], dtype=np.int32), np.array([h for _g, h in pairs], dtype=np.int32))
+    blocks = [({k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}, []) for _ in pairs]
+
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, seed, blocks, times)
+
+    def write(w):
+        w.writerow(DIFF_PA_PAIRS_HEADER)
+        cols = [(names[g], names[h], _diff_pa_columns(genes, lines, int(su.sizes[g]), int(su.sizes[h]), n_perm))
+                for (g, h), (lines, genes) in zip(pairs, blocks) if genes]
+        if not cols:
+            return
+        p_adj = _bh(np.concatenate([c.p_val for _a, _b, c in cols]))
+        gene_adj = _bh(np.concatenate([c.gene_p for _a, _b, c in cols]))
+        line0 = gene0 = 0
+        for a, b, c in cols:
+            n = len(c.pa)
+            adj = gene_adj[gene0:gene0 + len(c.gene_p)]
+            w.writerows(zip(c.gene, c.pa, [a] * n, [b] * n, c.pct1, c.pct2, [f"{a}_Vs_{b}"] * n, *c.usage, c.n_ge,
+                            _reprs(c.p_val), _reprs(p_adj[line0:line0 + n]), c.stat0, c.gene_ge,
+                            _reprs(c.gene_p[c.rec_of]), _reprs(adj[c.rec_of]), [n_perm] * n))
+            line0 += n
+            gene0 += len(c.gene_p)
+
+    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    print(f"Finish {n_perm} permutations of {len(pairs)} pairs of {G} populations ({int(su.sizes.sum())} cells) for "
+          f"{sum(g[1] for _l, genes in blocks for g in genes)} lines of {sum(len(genes) for _l, genes in blocks)} tested "
+          "(pair, record) combinations")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -1642,3 +1760,27 @@ def diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: st
     longer or shorter 3'UTRs than all the others: the omnibus form of diff_pa_len, a permutation test of the cell labels
     on the between-population sum of squares of the mean pA position, and on every population's mean against the rest."""
     _diff_pa_len_groups(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
+
+
+@click.command(name="diff_pa_pairs")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the final '
+                   'result.')
+@click.option('--cell_cluster_file', type=str, required=True,
+              help='An csv file containing two columns in order: cell barcode index (index) and respective group. Cells '
+                   'with an empty group, or not listed, are left out. Its name will be included in the file name of the '
+                   'final result.')
+@click.option('--idents', type=str, multiple=True,
+              help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. Default: every '
+                   'cluster of the cell_cluster_file, in order of first appearance.')
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels per pair; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives every pair the relabellings of diff_pa '
+                   'on its two clusters.')
+def diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents, n_perm: int, seed: int):
+    """Every pair of the cell populations of a cluster file tested as diff_pa tests two, in one run over the result
+    file: the post-hoc tests behind diff_pa_groups, with the p-values adjusted over all pairs (Benjamini-Hochberg)."""
+    _diff_pa_pairs(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
