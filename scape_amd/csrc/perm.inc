@@ -17,9 +17,11 @@
 //   k_rep_perm_rowstat or k_rep_groups_rowstat / k_rep_scan / k_rep_perm_fill
 //                   per kept row its nonzeros and its sums per population as observed, their scan, and the (position,
 //                   count) pairs (rep_perm_prepare)
+//   rep_perm_segsum the one walk over mask words: a run of nonzeros summed over the lane's population 1
 //   k_rep_perm_test diff_pa: exceedance counts per site and record
 //   k_rep_perm_len  diff_pa_len: the record's mean pA position in the two populations (two f64 sums and two integer sums
 //                   per lane), exceedance counts per record
+//   rep_groups_walk the one walk over label bytes, four in flight: (group, count) of every nonzero to the caller's LDS adds
 //   k_rep_groups_obs / k_rep_perm_groups
 //                   diff_pa_groups: the observed statistic, and the test with G sums per row and permutation in LDS
 //   k_rep_len_groups_obs / k_rep_perm_len_groups
@@ -29,7 +31,8 @@
 //                   diff_pa_pairs: the membership bits of every (pair of populations, permutation), per kept row the
 //                   first nonzero of every population's column segment, and diff_pa's test for every pair from the one
 //                   compaction, a pair walking the nonzeros of its two segments only
-// The exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
+// On the host rep_perm_classes / rep_perm_launch_classes launch the two-population test per LDS class of records, and
+// the exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
 // stay on the host (scape_amd/report.py).
 
 // ---- keys and the radix select ----------------------------------------------------------------------------------------
@@ -282,15 +285,17 @@ __device__ __forceinline__ double rep_perm_row(long long a, long long t, long lo
     return (N * N) / ((double)t * Ad * Bd);
 }
 
-// a row's sum over this lane's population 1: the nonzeros are wave-uniform, the lane tests its own permutation's bit.
-// Positions ascend within a row, so a mask word is loaded once for all the nonzeros that fall into it
-__device__ __forceinline__ int rep_perm_rowsum(const uint2 *__restrict__ nz, int64_t k0, int64_t k1,
+// the sum of the nonzeros nz[k0 .. k1), at the positions column + shift, over this lane's population 1: the nonzeros are
+// wave-uniform, the lane tests its own permutation's bit.  Positions ascend, so a mask word is loaded once for all the
+// nonzeros that fall into it.  shift = 0 for a row of diff_pa and diff_pa_len; a pair of diff_pa_pairs moves each of its
+// two column segments to the pair's local positions
+__device__ __forceinline__ int rep_perm_segsum(const uint2 *__restrict__ nz, int64_t k0, int64_t k1, int shift,
                                                const unsigned long long *__restrict__ mb, int64_t pstride) {
     int a = 0, cur = -1;
     unsigned long long w = 0;
     for (int64_t k = k0; k < k1; ++k) {
         const uint2 e = nz[k];
-        const int pos = __builtin_amdgcn_readfirstlane((int)e.x), c = __builtin_amdgcn_readfirstlane((int)e.y);
+        const int pos = __builtin_amdgcn_readfirstlane((int)e.x) + shift, c = __builtin_amdgcn_readfirstlane((int)e.y);
         if ((pos >> 6) != cur) {
             cur = pos >> 6;
             w = mb[(int64_t)cur * pstride];
@@ -324,13 +329,13 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_test(
     }
     const bool one = row1 - row0 <= cap;
     if (!one)
-        for (int64_t i = row0; i < row1; ++i) A += rep_perm_rowsum(nz, noff[i], noff[i + 1], mb, p_count);
+        for (int64_t i = row0; i < row1; ++i) A += rep_perm_segsum(nz, noff[i], noff[i + 1], 0, mb, p_count);
     double S = 0.0, S0 = 0.0;
     for (int64_t g0 = row0; g0 < row1; g0 += cap) {
         const int64_t g1 = g0 + cap < row1 ? g0 + cap : row1;
         long long Ag = 0;
         for (int64_t i = g0; i < g1; ++i) {
-            const int a = rep_perm_rowsum(nz, noff[i], noff[i + 1], mb, p_count);
+            const int a = rep_perm_segsum(nz, noff[i], noff[i + 1], 0, mb, p_count);
             acc[(i - g0) * REP_THREADS] = a;
             Ag += a;
         }
@@ -407,7 +412,7 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len(
     for (int64_t i = row0; i < row1; ++i) {
         const int ti = (int)t[i];
         const double wi = w[i];
-        rep_len_row(rep_perm_rowsum(nz, noff[i], noff[i + 1], mb, p_count), ti, wi, &W1, &W2, &A, &B);
+        rep_len_row(rep_perm_segsum(nz, noff[i], noff[i + 1], 0, mb, p_count), ti, wi, &W1, &W2, &A, &B);
         rep_len_row((int)a0[i], ti, wi, &V1, &V2, &A0, &B0);
     }
     const double d = rep_len_delta(W1, W2, A, B), d0 = rep_len_delta(V1, V2, A0, B0);
@@ -576,13 +581,14 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_groups_obs(const int64_t *_
     }
 }
 
-// the nonzeros nz[k0 .. k1) added to acc[group][lane] under this lane's labelling (lb = the lane's byte of position 0,
-// the positions pstride bytes apart).  The nonzeros are wave-uniform.  Four at a time: their label bytes are loaded
-// before the first addition waits for one.  The addition is an LDS atomic whose result is not used - one ds_add
-// without a return value in place of a read, an add and a write that would wait for each other; no other lane touches
-// the address
+// the walk of the G-way tests: add(group, count) for every nonzero nz[k0 .. k1), the group under this lane's labelling
+// (lb = the lane's byte of position 0, the positions pstride bytes apart).  The nonzeros are wave-uniform.  Four at a
+// time: their label bytes are loaded before the first addition waits for one.  add() adds into the lane's own column of
+// LDS with atomics whose results are not used - one ds_add without a return value in place of a read, an add and a
+// write that would wait for each other; no other lane touches the address
+template <typename Add>
 __device__ __forceinline__ void rep_groups_walk(const uint2 *__restrict__ nz, int64_t k0, int64_t k1,
-                                                const uint8_t *__restrict__ lb, int64_t pstride, int32_t *acc) {
+                                                const uint8_t *__restrict__ lb, int64_t pstride, Add add) {
     int64_t k = k0;
     for (; k + 4 <= k1; k += 4) {
         int c[4], g[4];
@@ -593,12 +599,12 @@ __device__ __forceinline__ void rep_groups_walk(const uint2 *__restrict__ nz, in
             g[u] = lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride];
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) atomicAdd(&acc[g[u] * REP_THREADS], c[u]);
+        for (int u = 0; u < 4; ++u) add(g[u], c[u]);
     }
     for (; k < k1; ++k) {
         const uint2 e = nz[k];
         const int c = __builtin_amdgcn_readfirstlane((int)e.y);
-        atomicAdd(&acc[(int)lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride] * REP_THREADS], c);
+        add((int)lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride], c);
     }
 }
 
@@ -625,11 +631,13 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_groups(
     long long T = 0;
     for (int64_t i = row0; i < row1; ++i) T += t[i];
     for (int g = 0; g < n_groups; ++g) accA[g * REP_THREADS] = 0;
-    rep_groups_walk(nz, noff[row0], noff[row1], lb, p_count, accA);
+    rep_groups_walk(nz, noff[row0], noff[row1], lb, p_count,
+                    [=](int g, int c) { atomicAdd(&accA[g * REP_THREADS], c); });
     double S = 0.0;
     for (int64_t i = row0; i < row1; ++i) {
         for (int g = 0; g < n_groups; ++g) acca[g * REP_THREADS] = 0;
-        rep_groups_walk(nz, noff[i], noff[i + 1], lb, p_count, acca);
+        rep_groups_walk(nz, noff[i], noff[i + 1], lb, p_count,
+                        [=](int g, int c) { atomicAdd(&acca[g * REP_THREADS], c); });
         const long long ti = t[i];
         const double s = rep_groups_site<int32_t>(acca, accA, REP_THREADS, n_groups, ti, T);
         S = S + rep_groups_share(s, ti, T);
@@ -732,39 +740,6 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_len_groups_obs(const int64_
     }
 }
 
-// the nonzeros nz[k0 .. k1) of one row with the position qi added to accA[group - g0][lane] (the count) and
-// accQ[group - g0][lane] (count x qi, wave-uniform) under this lane's labelling, as rep_groups_walk adds: four label
-// bytes in flight, LDS atomics whose results are not used.  A lane whose label lies outside [g0, g0 + ng) adds nothing
-__device__ __forceinline__ void rep_len_groups_walk(const uint2 *__restrict__ nz, int64_t k0, int64_t k1,
-                                                    const uint8_t *__restrict__ lb, int64_t pstride, long long qi, int g0,
-                                                    int ng, int32_t *accA, unsigned long long *accQ) {
-    int64_t k = k0;
-    for (; k + 4 <= k1; k += 4) {
-        int c[4], g[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint2 e = nz[k + u];
-            c[u] = __builtin_amdgcn_readfirstlane((int)e.y);
-            g[u] = (int)lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride] - g0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if ((unsigned)g[u] < (unsigned)ng) {
-                atomicAdd(&accA[g[u] * REP_THREADS], c[u]);
-                atomicAdd(&accQ[g[u] * REP_THREADS], (unsigned long long)(c[u] * qi));
-            }
-    }
-    for (; k < k1; ++k) {
-        const uint2 e = nz[k];
-        const int c = __builtin_amdgcn_readfirstlane((int)e.y);
-        const int g = (int)lb[(int64_t)__builtin_amdgcn_readfirstlane((int)e.x) * pstride] - g0;
-        if ((unsigned)g < (unsigned)ng) {
-            atomicAdd(&accA[g * REP_THREADS], c);
-            atomicAdd(&accQ[g * REP_THREADS], (unsigned long long)(c * qi));
-        }
-    }
-}
-
 // workgroup = (record blockIdx.x / n_tiles, tile of 256 permutations), one lane per permutation, as k_rep_perm_groups.
 // The groups are taken in slices of `slice` <= REP_LEN_GROUPS_SLICE: LDS holds Q_g(p) as accQ[group][lane] (8 bytes;
 // a 16-lane access group covers all 32 banks whatever the groups) and behind them A_g(p) as accA[group][lane]: 12 x
@@ -796,8 +771,15 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_groups(
             accQ[g * REP_THREADS] = 0;
             accA[g * REP_THREADS] = 0;
         }
-        for (int64_t i = row0; i < row1; ++i)
-            rep_len_groups_walk(nz, noff[i], noff[i + 1], lb, p_count, q[i], g0, ng, accA, accQ);
+        for (int64_t i = row0; i < row1; ++i) {
+            const long long qi = q[i];       // wave-uniform, and so is count x qi
+            rep_groups_walk(nz, noff[i], noff[i + 1], lb, p_count, [=](int g, int c) {
+                if ((unsigned)(g - g0) < (unsigned)ng) {     // a label outside the slice adds nothing
+                    atomicAdd(&accA[(g - g0) * REP_THREADS], c);
+                    atomicAdd(&accQ[(g - g0) * REP_THREADS], (unsigned long long)(c * qi));
+                }
+            });
+        }
         for (int g = 0; g < ng; ++g) {
             const long long Qg = (long long)accQ[g * REP_THREADS], Ag = accA[g * REP_THREADS];
             D = D + rep_len_groups_term(Qg, Ag, m);
@@ -878,24 +860,6 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_pair_segidx(const int64_t *
     seg[idx] = lo;
 }
 
-// the nonzeros nz[k0 .. k1) of one segment, at the local positions column + shift, added under this lane's labelling as
-// rep_perm_rowsum adds them: wave-uniform nonzeros, a mask word loaded once for the nonzeros that fall into it
-__device__ __forceinline__ int rep_pair_segsum(const uint2 *__restrict__ nz, int64_t k0, int64_t k1, int shift,
-                                               const unsigned long long *__restrict__ mb, int64_t pstride) {
-    int a = 0, cur = -1;
-    unsigned long long w = 0;
-    for (int64_t k = k0; k < k1; ++k) {
-        const uint2 e = nz[k];
-        const int pos = __builtin_amdgcn_readfirstlane((int)e.x) + shift, c = __builtin_amdgcn_readfirstlane((int)e.y);
-        if ((pos >> 6) != cur) {
-            cur = pos >> 6;
-            w = mb[(int64_t)cur * pstride];
-        }
-        a += ((w >> (pos & 63)) & 1) ? c : 0;
-    }
-    return a;
-}
-
 // workgroup = (pair pair_first + blockIdx.y, record recs[blockIdx.x / n_tiles], tile of 256 permutations), one lane per
 // permutation, as k_rep_perm_test: a_i(p) of the record's rows in LDS as acc[row][lane] (each lane its own column, no
 // barrier), a record with more than `cap` rows in groups of cap rows behind one extra walk that forms A(p).  sg[i] =
@@ -940,8 +904,8 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_pairs(
     if (!one)
         for (int64_t i = row0; i < row1; ++i) {
             const int64_t *si = sg + i * stride;
-            A += rep_pair_segsum(nz, si[g], si[g + 1], sh_g, mb, p_count) +
-                 rep_pair_segsum(nz, si[h], si[h + 1], sh_h, mb, p_count);
+            A += rep_perm_segsum(nz, si[g], si[g + 1], sh_g, mb, p_count) +
+                 rep_perm_segsum(nz, si[h], si[h + 1], sh_h, mb, p_count);
         }
     double S = 0.0, S0 = 0.0;
     for (int64_t g0 = row0; g0 < row1; g0 += cap) {
@@ -949,8 +913,8 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_pairs(
         long long Ag = 0;
         for (int64_t i = g0; i < g1; ++i) {
             const int64_t *si = sg + i * stride;
-            const int a = rep_pair_segsum(nz, si[g], si[g + 1], sh_g, mb, p_count) +
-                          rep_pair_segsum(nz, si[h], si[h + 1], sh_h, mb, p_count);
+            const int a = rep_perm_segsum(nz, si[g], si[g + 1], sh_g, mb, p_count) +
+                          rep_perm_segsum(nz, si[h], si[h + 1], sh_h, mb, p_count);
             acc[(i - g0) * REP_THREADS] = a;
             Ag += a;
         }
@@ -972,6 +936,49 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_pairs(
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
+static const int REP_PERM_N_CAPS = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
+
+// the records by LDS class, for k_rep_perm_test and k_rep_perm_pairs: the smallest cap that holds all of a record's rows
+// (the largest cap takes the rest, in groups).  recs = the records in class order, count[q] = those of class q
+struct RepPermClasses {
+    std::vector<int32_t> recs;
+    int64_t count[REP_PERM_N_CAPS];
+};
+
+static RepPermClasses rep_perm_classes(int32_t n_rec, const int64_t *rec_row_off) {
+    std::vector<std::vector<int32_t>> by_cap(REP_PERM_N_CAPS);
+    for (int r = 0; r < n_rec; ++r) {
+        const int64_t k = rec_row_off[r + 1] - rec_row_off[r];
+        int q = 0;
+        while (q < REP_PERM_N_CAPS - 1 && k > REP_PERM_CAPS[q]) ++q;
+        by_cap[q].push_back(r);
+    }
+    RepPermClasses cl;
+    for (int q = 0; q < REP_PERM_N_CAPS; ++q) {
+        cl.recs.insert(cl.recs.end(), by_cap[q].begin(), by_cap[q].end());
+        cl.count[q] = (int64_t)by_cap[q].size();
+    }
+    return cl;
+}
+
+// one launch of `kernel` per class that has records: launch(records of the class on the device, their number, cap,
+// bytes of dynamic LDS) queues it.  cl stays alive until the caller has waited for the stream (the upload of recs)
+template <typename Kernel, typename Launch>
+static int rep_perm_launch_classes(scape_hip_ctx *c, const RepPermClasses &cl, Kernel kernel, Launch launch) {
+    ReportState *s = c->rep;
+    HIPCHK(hipMemcpyAsync(s->p_recs.p, cl.recs.data(), (int64_t)cl.recs.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               REP_PERM_CAPS[REP_PERM_N_CAPS - 1] * REP_THREADS * 4));
+    int64_t first = 0;
+    for (int q = 0; q < REP_PERM_N_CAPS; ++q) {
+        if (!cl.count[q]) continue;
+        const int32_t cap = REP_PERM_CAPS[q];
+        launch(s->p_recs.as<int32_t>() + first, cl.count[q], cap, (size_t)cap * REP_THREADS * 4);
+        HIPCHK(hipGetLastError());
+        first += cl.count[q];
+    }
+    return 0;
+}
 
 // what every builder of labellings asks of its n positions (`cells_must` names them: "... must [be]") and its chunk
 static int rep_perm_chunk_ok(int64_t n, const char *cells_must, int64_t p_first, int32_t p_count) {
@@ -1037,14 +1044,28 @@ static int rep_perm_ready(const ReportState *s, int32_t p_count, const char *bui
     return 0;
 }
 
-// the groups of a G-way test are those of the last labels call
-static int rep_groups_match(const ReportState *s, int32_t n_groups, const int32_t *seg_off) {
+// the groups of a test on column segments are those of the last call of `builder`, which remembered their sizes
+static int rep_groups_match(const std::vector<int32_t> &sizes, const char *builder, int32_t n_groups,
+                            const int32_t *seg_off) {
     if (!seg_off) return fail("bad argument");
-    if (n_groups != (int32_t)s->q_sizes.size()) return fail("n_groups differs from the last scape_hip_report_perm_labels call");
+    if (n_groups != (int32_t)sizes.size()) return fail("n_groups differs from the last " + std::string(builder) + " call");
     if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
     for (int32_t g = 0; g < n_groups; ++g)
-        if (seg_off[g + 1] - seg_off[g] != s->q_sizes[g])
-            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last scape_hip_report_perm_labels call");
+        if (seg_off[g + 1] - seg_off[g] != sizes[g])
+            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last " + builder + " call");
+    return 0;
+}
+
+// what the builders of G-way labellings and of pair masks ask of the groups: their number, and (sizes is there) their cells
+static int rep_n_groups_ok(int32_t n_groups) {
+    if (n_groups < 2 || n_groups > REP_GROUPS_MAX)
+        return fail("n_groups must lie in 2 .. " + std::to_string(REP_GROUPS_MAX));
+    return 0;
+}
+
+static int rep_group_sizes_ok(int32_t n_groups, const int32_t *sizes) {
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (sizes[g] < 1) return fail("group " + std::to_string(g) + ": every group needs at least one cell");
     return 0;
 }
 
@@ -1195,37 +1216,15 @@ int scape_hip_report_perm_test(scape_hip_ctx *c, int32_t n_rec, const int64_t *r
                          &n_tiles))
         return 1;
     if (s->p_recs.ensure((int64_t)n_rec * 4)) return 1;
-
-    // records by LDS class: the smallest cap that holds all their rows (the largest cap takes the rest, in groups)
-    const int n_caps = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
-    std::vector<std::vector<int32_t>> by_cap(n_caps);
-    for (int r = 0; r < n_rec; ++r) {
-        const int64_t k = rec_row_off[r + 1] - rec_row_off[r];
-        int q = 0;
-        while (q < n_caps - 1 && k > REP_PERM_CAPS[q]) ++q;
-        by_cap[q].push_back(r);
-    }
-    std::vector<int32_t> recs;
-    for (auto &v : by_cap) recs.insert(recs.end(), v.begin(), v.end());
+    const RepPermClasses cl = rep_perm_classes(n_rec, rec_row_off);
     return rep_perm_count(c, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
-        HIPCHK(hipMemcpyAsync(s->p_recs.p, recs.data(), (int64_t)n_rec * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_test),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   REP_PERM_CAPS[n_caps - 1] * REP_THREADS * 4));
-        int64_t first = 0;
-        for (int q = 0; q < n_caps; ++q) {
-            const int64_t m = (int64_t)by_cap[q].size();
-            if (!m) continue;
-            const int32_t cap = REP_PERM_CAPS[q];
-            hipLaunchKernelGGL(k_rep_perm_test, dim3((uint32_t)(m * n_tiles)), dim3(REP_THREADS),
-                               (size_t)cap * REP_THREADS * 4, c->stream, s->m_bits.as<unsigned long long>(), s->m_count,
-                               n_tiles, s->p_recs.as<int32_t>() + first, s->p_roff.as<int64_t>(),
+        return rep_perm_launch_classes(c, cl, k_rep_perm_test, [&](const int32_t *recs, int64_t m, int32_t cap,
+                                                                   size_t lds) {
+            hipLaunchKernelGGL(k_rep_perm_test, dim3((uint32_t)(m * n_tiles)), dim3(REP_THREADS), lds, c->stream,
+                               s->m_bits.as<unsigned long long>(), s->m_count, n_tiles, recs, s->p_roff.as<int64_t>(),
                                s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->p_a0.as<int64_t>(),
                                cap, s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
-            HIPCHK(hipGetLastError());
-            first += m;
-        }
-        return 0;
+        });
     });
 }
 
@@ -1258,14 +1257,11 @@ int scape_hip_report_perm_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *re
 int scape_hip_report_perm_labels(scape_hip_ctx *c, int32_t n_groups, const int32_t *sizes, int64_t p_first,
                                  int32_t p_count, uint64_t seed) {
     CTX_ENTER(c);
-    if (n_groups < 2 || n_groups > REP_GROUPS_MAX)
-        return fail("n_groups must lie in 2 .. " + std::to_string(REP_GROUPS_MAX));
+    if (rep_n_groups_ok(n_groups)) return 1;
     if (!sizes) return fail("bad argument");
+    if (rep_group_sizes_ok(n_groups, sizes)) return 1;
     int64_t n = 0;
-    for (int32_t g = 0; g < n_groups; ++g) {
-        if (sizes[g] < 1) return fail("group " + std::to_string(g) + ": every group needs at least one cell");
-        n += sizes[g];
-    }
+    for (int32_t g = 0; g < n_groups; ++g) n += sizes[g];
     if (rep_perm_chunk_ok(n, "the groups' cells must number", p_first, p_count)) return 1;
     ReportState *s = report_state(c);
     s->q_count = 0;
@@ -1308,7 +1304,7 @@ int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t 
     ReportState *s = c->rep;
     if (rep_perm_ready(s, s ? s->q_count : 0, "scape_hip_report_perm_labels")) return 1;
     if (n_rec <= 0 || !rec_row_off) return fail("bad argument");   // what the check of the rounding bound reads
-    if (rep_groups_match(s, n_groups, seg_off)) return 1;
+    if (rep_groups_match(s->q_sizes, "scape_hip_report_perm_labels", n_groups, seg_off)) return 1;
     for (int r = 0; r < n_rec; ++r)
         if (rec_row_off[r + 1] - rec_row_off[r] + n_groups > REP_GROUPS_MAX_ROWS_AND_GROUPS)
             return fail("record " + std::to_string(r) + ": " + std::to_string(rec_row_off[r + 1] - rec_row_off[r]) +
@@ -1346,7 +1342,7 @@ int scape_hip_report_perm_len_groups(scape_hip_ctx *c, int32_t n_rec, const int6
     CTX_ENTER(c);
     ReportState *s = c->rep;
     if (rep_perm_ready(s, s ? s->q_count : 0, "scape_hip_report_perm_labels")) return 1;
-    if (rep_groups_match(s, n_groups, seg_off)) return 1;
+    if (rep_groups_match(s->q_sizes, "scape_hip_report_perm_labels", n_groups, seg_off)) return 1;
     int64_t n_rows = 0;
     int32_t n_tiles = 0;
     if (rep_perm_prepare(c, s->q_n, s->q_count, "labels", 0, n_groups, seg_off, n_rec, rec_row_off, rows, t_out, a0_out,
@@ -1393,13 +1389,11 @@ int scape_hip_report_perm_pair_masks(scape_hip_ctx *c, int32_t n_groups, const i
                                      const int32_t *pair_g, const int32_t *pair_h, int64_t p_first, int32_t p_count,
                                      uint64_t seed) {
     CTX_ENTER(c);
-    if (n_groups < 2 || n_groups > REP_GROUPS_MAX)
-        return fail("n_groups must lie in 2 .. " + std::to_string(REP_GROUPS_MAX));
+    if (rep_n_groups_ok(n_groups)) return 1;
     if (n_pairs < 1 || n_pairs > REP_GROUPS_MAX * (REP_GROUPS_MAX - 1) / 2)
         return fail("n_pairs must lie in 1 .. " + std::to_string(REP_GROUPS_MAX * (REP_GROUPS_MAX - 1) / 2));
     if (!sizes || !pair_g || !pair_h) return fail("bad argument");
-    for (int32_t g = 0; g < n_groups; ++g)
-        if (sizes[g] < 1) return fail("group " + std::to_string(g) + ": every group needs at least one cell");
+    if (rep_group_sizes_ok(n_groups, sizes)) return 1;
     std::vector<int32_t> pairs((size_t)n_pairs * 8, 0);
     int64_t words = 0;
     for (int32_t k = 0; k < n_pairs; ++k) {
@@ -1452,13 +1446,7 @@ int scape_hip_report_perm_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *
     CTX_ENTER(c);
     ReportState *s = c->rep;
     if (rep_perm_ready(s, s ? s->x_count : 0, "scape_hip_report_perm_pair_masks")) return 1;
-    if (!seg_off) return fail("bad argument");
-    if (n_groups != (int32_t)s->x_sizes.size())
-        return fail("n_groups differs from the last scape_hip_report_perm_pair_masks call");
-    if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
-    for (int32_t g = 0; g < n_groups; ++g)
-        if (seg_off[g + 1] - seg_off[g] != s->x_sizes[g])
-            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last scape_hip_report_perm_pair_masks call");
+    if (rep_groups_match(s->x_sizes, "scape_hip_report_perm_pair_masks", n_groups, seg_off)) return 1;
     const int32_t n_pairs = (int32_t)(s->x_pairs.size() / 8);
     if (pair_first < 0 || pair_count < 1 || pair_first > n_pairs - pair_count)
         return fail("pair_first and pair_count must name pairs of the last scape_hip_report_perm_pair_masks call");
@@ -1476,42 +1464,21 @@ int scape_hip_report_perm_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *
     if (s->p_recs.ensure((int64_t)n_rec * 4) || s->x_seg.ensure(n_seg * 8) || s->p_gene.ensure(n_out * 4) ||
         s->p_stat0.ensure(n_out * 8))
         return 1;
-
-    // records by LDS class, as scape_hip_report_perm_test takes them, on the rows kept over all groups
-    const int n_caps = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
-    std::vector<std::vector<int32_t>> by_cap(n_caps);
-    for (int r = 0; r < n_rec; ++r) {
-        const int64_t k = rec_row_off[r + 1] - rec_row_off[r];
-        int q = 0;
-        while (q < n_caps - 1 && k > REP_PERM_CAPS[q]) ++q;
-        by_cap[q].push_back(r);
-    }
-    std::vector<int32_t> recs;
-    for (auto &v : by_cap) recs.insert(recs.end(), v.begin(), v.end());
+    const RepPermClasses cl = rep_perm_classes(n_rec, rec_row_off);      // on the rows kept over all groups
     return rep_perm_count(c, pair_count * n_rows, (int32_t)n_out, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
-        HIPCHK(hipMemcpyAsync(s->p_recs.p, recs.data(), (int64_t)n_rec * 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_rep_pair_segidx, dim3((uint32_t)((n_seg + REP_THREADS - 1) / REP_THREADS)),
                            dim3(REP_THREADS), 0, c->stream, s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
                            s->q_seg.as<int32_t>(), n_groups, n_rows, s->x_seg.as<int64_t>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_pairs),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   REP_PERM_CAPS[n_caps - 1] * REP_THREADS * 4));
-        int64_t first = 0;
-        for (int q = 0; q < n_caps; ++q) {
-            const int64_t m = (int64_t)by_cap[q].size();
-            if (!m) continue;
-            const int32_t cap = REP_PERM_CAPS[q];
+        return rep_perm_launch_classes(c, cl, k_rep_perm_pairs, [&](const int32_t *recs, int64_t m, int32_t cap,
+                                                                    size_t lds) {
             hipLaunchKernelGGL(k_rep_perm_pairs, dim3((uint32_t)(m * n_tiles), (uint32_t)pair_count), dim3(REP_THREADS),
-                               (size_t)cap * REP_THREADS * 4, c->stream, s->x_bits.as<unsigned long long>(), s->x_count,
-                               n_tiles, s->p_recs.as<int32_t>() + first, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(),
-                               s->p_nz.as<uint2>(), s->q_a0.as<int64_t>(), n_groups, s->q_seg.as<int32_t>(),
+                               lds, c->stream, s->x_bits.as<unsigned long long>(), s->x_count, n_tiles, recs,
+                               s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
+                               s->q_a0.as<int64_t>(), n_groups, s->q_seg.as<int32_t>(),
                                s->x_desc.as<RepPair>() + pair_first, n_rows, n_rec, cap, s->p_site.as<int32_t>(),
                                s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
-            HIPCHK(hipGetLastError());
-            first += m;
-        }
-        return 0;
+        });
     });
 }
 

@@ -668,25 +668,31 @@ def _bh(p):
     return out
 
 
-def _perm_masks(ctx, su, p_first, p_count, seed, times):
-    """the membership bits of p_count permutations from p_first on: relabelled within su.strata = (m1, m2) when given,
-    freely otherwise; for diff_pa_groups and diff_pa_len_groups (su.sizes = cells per group) the group bytes instead;
-    for diff_pa_pairs (su.pairs = the two groups of every pair) the membership bits of every pair"""
+def _check_perm_args(n_perm, seed):
+    if n_perm < 1:
+        raise ValueError(f"n_perm must be at least 1, not {n_perm}")
+    if n_perm >= 1 << 31:
+        raise ValueError(f"n_perm must be below 2^31, not {n_perm}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
+
+
+def _check_row_sums(call, t, a0, sums, a0_sums):
+    """the device's row sums t and a0 against report_group_sums' `sums` and the part of them that a0 restates"""
+    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, a0_sums)):
+        raise _lib.ScapeHipError(f"{call}: row sums differ from report_group_sums")
+
+
+def _check_reads(rec, T):
+    if int(T) >= 1 << 31:
+        raise ValueError(f"{rec.gene_info_str}: 2^31 or more reads in the tested cells")
+
+
+def _perm_masks(ctx, su, p_first, p_count, times):
+    """the labellings of p_count permutations from p_first on, as the run's setup function describes them:
+    su.labellings(ctx, p_first, p_count) is its one library call"""
     t0 = timer()
-    if su.pairs is not None:
-        pair_g, pair_h = su.pairs
-        check(ctx.lib.scape_hip_report_perm_pair_masks(ctx.h, len(su.sizes), ptr(su.sizes, P_i32), len(pair_g),
-                                                       ptr(pair_g, P_i32), ptr(pair_h, P_i32), p_first, p_count, seed),
-              "report_perm_pair_masks")
-    elif su.sizes is not None:
-        check(ctx.lib.scape_hip_report_perm_labels(ctx.h, len(su.sizes), ptr(su.sizes, P_i32), p_first, p_count, seed),
-              "report_perm_labels")
-    elif su.strata is not None:
-        m1, m2 = su.strata
-        check(ctx.lib.scape_hip_report_perm_masks_strata(ctx.h, len(m1), ptr(m1, P_i32), ptr(m2, P_i32), p_first,
-                                                         p_count, seed), "report_perm_masks_strata")
-    else:
-        check(ctx.lib.scape_hip_report_perm_masks(ctx.h, su.n1, su.n2, p_first, p_count, seed), "report_perm_masks")
+    su.labellings(ctx, p_first, p_count)
     times["render"] += timer() - t0
 
 
@@ -729,17 +735,17 @@ def _perm_rows(ctx, bat, seg_off, times, each_kept=None):
     return which, off, cand[keep], nz[keep], sums[keep], rowbase
 
 
-def _perm_chunks(ctx, su, n_perm, chunk, seed, times, test):
+def _perm_chunks(ctx, su, n_perm, chunk, times, test):
     """test() once per chunk of permutations, behind that chunk's masks"""
     for p_first in range(1, n_perm + 1, chunk):
         if chunk < n_perm:       # otherwise the one set of masks was built before the first batch
-            _perm_masks(ctx, su, p_first, min(chunk, n_perm + 1 - p_first), seed, times)
+            _perm_masks(ctx, su, p_first, min(chunk, n_perm + 1 - p_first), times)
         t0 = timer()
         test()
         times["render"] += timer() - t0
 
 
-def _diff_pa_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times):
+def _diff_pa_batch(ctx, bat, su, n_perm, chunk, lines, genes, times):
     """one counted batch: the kept rows of its tested records go through the permutation test; appends the per-line
     integers to `lines` and the per-record ones to `genes`"""
     sel = _perm_rows(ctx, bat, su.seg_off, times)
@@ -750,18 +756,15 @@ def _diff_pa_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times):
     t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
     site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
     stat0 = np.zeros(len(which), np.float64)
-    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
+    _perm_chunks(ctx, su, n_perm, chunk, times, lambda: check(
         ctx.lib.scape_hip_report_perm_test(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(t, P_i64),
                                            ptr(a0, P_i64), ptr(site_ge, P_i64), ptr(stat0), ptr(gene_ge, P_i64)),
         "report_perm_test"))
     t0 = timer()
-    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums[:, 0])):
-        raise _lib.ScapeHipError("report_perm_test: row sums differ from report_group_sums")
+    _check_row_sums("report_perm_test", t, a0, sums, sums[:, 0])
     for g, r in enumerate(which.tolist()):
         a, b = int(off[g]), int(off[g + 1])
-        T = int(t[a:b].sum())
-        if T >= 1 << 31:
-            raise ValueError(f"{recs[r].gene_info_str}: 2^31 or more reads in the tested cells")
+        _check_reads(recs[r], t[a:b].sum())
         labs = rows[a:b] - int(rowbase[r])
         genes.append((recs[r].gene_info_str, b - a, float(stat0[g]), int(gene_ge[g])))
         lines["pa"].extend(_pa_info(recs[r], labs))
@@ -804,12 +807,7 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
         raise ValueError("idents_1 is required")
     if idents_1 == idents_2:
         raise ValueError(f"idents_1 and idents_2 are the same cluster {idents_1!r}")
-    if n_perm < 1:
-        raise ValueError(f"n_perm must be at least 1, not {n_perm}")
-    if n_perm >= 1 << 31:
-        raise ValueError(f"n_perm must be below 2^31, not {n_perm}")
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
+    _check_perm_args(n_perm, seed)
     inp = _read_inputs(output_dir, res_pkl_file, cell_cluster_file, (idents_1, idents_2))
     n_cols, pops = inp.n_cols, inp.pops
     if len(pops) < 2:
@@ -836,8 +834,17 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
     if n1 + n2 >= MAX_PERM_CELLS:
         raise ValueError(f"{n1 + n2} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + f"{by}.{command}.csv"
+    if strata is None:
+        def labellings(ctx, p_first, p_count):
+            check(ctx.lib.scape_hip_report_perm_masks(ctx.h, n1, n2, p_first, p_count, seed), "report_perm_masks")
+    else:
+        def labellings(ctx, p_first, p_count):
+            check(ctx.lib.scape_hip_report_perm_masks_strata(ctx.h, len(m1), ptr(m1, P_i32), ptr(m2, P_i32), p_first,
+                                                             p_count, seed), "report_perm_masks_strata")
+    # per permutation the device holds the bits, and its key bound per stratum (one stratum without --strata_file)
+    perm_bytes = (n1 + n2 + 63) // 64 * 8 + (1 if strata is None else len(m1)) * 8
     return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
-                           strata=strata, left_out=left_out, sizes=None, pairs=None,
+                           strata=strata, left_out=left_out, labellings=labellings, perm_bytes=perm_bytes,
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"),
                            versus=f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1))
 
@@ -850,27 +857,20 @@ def _print_strata(su):
               "clusters have no stratum and were left out")
 
 
-def _perm_run(su, n_perm, seed, device, batch, write):
-    """the run the permutation commands share: the masks (once, when all permutations fit MAX_PERM_BYTES; otherwise per chunk inside
-    every batch), batch(ctx, counted batch, chunk, times) per counted batch, then write(csv writer) into the .part file
-    that is renamed when complete.  Returns the wall seconds; LAST_TIMES holds the stages"""
+def _perm_run(su, n_perm, device, batch, write):
+    """the run the permutation commands share: the masks (once, when all permutations, at su.perm_bytes device bytes
+    each, fit MAX_PERM_BYTES; otherwise per chunk inside every batch), batch(ctx, counted batch, chunk, times) per
+    counted batch, then write(csv writer) into the .part file that is renamed when complete.  Returns the wall seconds;
+    LAST_TIMES holds the stages"""
     with _Run(device, [su.outpath]) as run:
         times = run.times
         with open(run.parts[0], "w", newline="") as fh:
             ctx = run.device()
             budget = _budget(ctx)
-            if su.pairs is not None:
-                # diff_pa_pairs: per pair its bits and the device's key bound per permutation
-                word_bytes = int(sum((int(su.sizes[g]) + int(su.sizes[h]) + 63) // 64 * 8 + 8 for g, h in zip(*su.pairs)))
-            elif su.sizes is not None:
-                word_bytes = int(su.sizes.sum())         # the G-way commands: one byte per tested cell and permutation
-            else:
-                # the bits, and the device's key bound per permutation and stratum (one stratum without --strata_file)
-                word_bytes = (su.n1 + su.n2 + 63) // 64 * 8 + (1 if su.strata is None else len(su.strata[0])) * 8
             perm_bytes = int(MAX_PERM_BYTES) if MAX_PERM_BYTES is not None else budget // 2
-            chunk = max(1, min(n_perm, perm_bytes // word_bytes))
+            chunk = max(1, min(n_perm, perm_bytes // su.perm_bytes))
             if chunk == n_perm:
-                _perm_masks(ctx, su, 1, n_perm, seed, times)
+                _perm_masks(ctx, su, 1, n_perm, times)
             if MAX_BATCH_BYTES is None:
                 budget //= 2
             # the counts of a record and, at worst, as many 8-byte nonzeros as it has tested counts
@@ -921,7 +921,7 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
     genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
 
     def batch(ctx, bat, chunk, times):
-        _diff_pa_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times)
+        _diff_pa_batch(ctx, bat, su, n_perm, chunk, lines, genes, times)
 
     def write(w):
         w.writerow(DIFF_PA_HEADER)
@@ -933,7 +933,7 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
                         _reprs(_bh(c.p_val)), c.stat0, c.gene_ge, _reprs(c.gene_p[c.rec_of]), _reprs(gene_adj[c.rec_of]),
                         [n_perm] * len(c.pa)))
 
-    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    wall = _perm_run(su, n_perm, device, batch, write)
     print(f"Finish {n_perm} permutations of {n1} + {n2} cells for {sum(g[1] for g in genes)} pA sites of "
           f"{len(genes)} tested records")
     _print_strata(su)
@@ -961,13 +961,9 @@ DIFF_PA_LEN_HEADER = ["gene", "versus", "num_pa", "reads.1", "reads.2", "mean_po
 
 def _mean_positions(x, a, b):
     """(mean_pos.1, mean_pos.2, delta_pos) of positions x (finite f64) under the integer row sums a and b: the exact
-    rationals, each rounded once"""
-    ratios = [float(v).as_integer_ratio() for v in x]
-    D = max(d for _n, d in ratios)                       # denominators are powers of two
-    X = [n * (D // d) for n, d in ratios]
-    m1 = Fraction(sum(int(ai) * Xi for ai, Xi in zip(a, X)), int(sum(a)) * D)
-    m2 = Fraction(sum(int(bi) * Xi for bi, Xi in zip(b, X)), int(sum(b)) * D)
-    return float(m1), float(m2), float(m1 - m2)
+    rationals, each rounded once (both populations have reads)"""
+    _mean, (m1, m2), (delta, _delta2) = _mean_positions_groups(x, list(zip(a, b)))
+    return m1, m2, delta
 
 
 def _finite_positions(recs, pos):
@@ -999,7 +995,7 @@ def _with_span(sel, pos, times):
     return which, off, np.ascontiguousarray(rows[pick]), sums[pick], rowbase, [pos[r] for r in which.tolist()]
 
 
-def _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
+def _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, out, times):
     """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
     n_ge) per tested record to `out`"""
     recs, K = bat.recs, bat.K
@@ -1013,12 +1009,11 @@ def _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
     tol = np.array([np.ldexp(float(x.max() - x.min()), -40) for x in xs], dtype=np.float64)
     t, a0 = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int64)
     delta0, n_ge = np.zeros(len(which), np.float64), np.zeros(len(which), np.int64)
-    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
+    _perm_chunks(ctx, su, n_perm, chunk, times, lambda: check(
         ctx.lib.scape_hip_report_perm_len(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(w), ptr(tol),
                                           ptr(t, P_i64), ptr(a0, P_i64), ptr(delta0), ptr(n_ge, P_i64)),
         "report_perm_len"))
-    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums[:, 0])):
-        raise _lib.ScapeHipError("report_perm_len: row sums differ from report_group_sums")
+    _check_row_sums("report_perm_len", t, a0, sums, sums[:, 0])
     # the two populations' counts of ALL K labels of the tested records, for the reference's exp_pa_len
     all_rows = np.concatenate([int(rowbase[r]) + np.arange(int(K[r]), dtype=np.int64) for r in which.tolist()])
     full = np.zeros((len(all_rows), 2), dtype=np.int32)
@@ -1056,7 +1051,7 @@ def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, ide
     out = []
 
     def batch(ctx, bat, chunk, times):
-        _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, seed, out, times)
+        _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, out, times)
 
     def write(w):
         w.writerow(DIFF_PA_LEN_HEADER)
@@ -1070,7 +1065,7 @@ def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, ide
                                                                                          n_perm]
                     for o, de, p, q in zip(out, d_exp.tolist(), p_val.tolist(), _bh(p_val).tolist()))
 
-    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    wall = _perm_run(su, n_perm, device, batch, write)
     print(f"Finish {n_perm} permutations of {su.n1} + {su.n2} cells for {len(out)} tested records")
     _print_strata(su)
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
@@ -1097,17 +1092,15 @@ MAX_GROUPS = 64                  # a group is one byte on the device, and its su
 MAX_ROWS_AND_GROUPS = 4000       # kept rows + populations of a record: the rounding bound of S (include/scape_hip.h)
 
 
-def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, command="diff_pa_groups"):
-    """what diff_pa_groups and diff_pa_len_groups do before the device is opened: the argument and prerequisite checks,
-    the populations, the id -> column table that puts population 0's columns first, then population 1's, ..., and the
-    output path <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv"""
+def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, command="diff_pa_groups",
+                  pairs=False):
+    """what diff_pa_groups, diff_pa_len_groups and diff_pa_pairs (pairs=True: su.pairs = the two groups of every pair,
+    all (g, h) with g < h in lexicographic order, and the labellings are every pair's membership bits, not the group
+    bytes) do before the device is opened: the argument and prerequisite checks, the populations, the id -> column
+    table that puts population 0's columns first, then population 1's, ..., and the output path
+    <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv"""
     idents = [str(i) for i in idents or ()]
-    if n_perm < 1:
-        raise ValueError(f"n_perm must be at least 1, not {n_perm}")
-    if n_perm >= 1 << 31:
-        raise ValueError(f"n_perm must be below 2^31, not {n_perm}")
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
+    _check_perm_args(n_perm, seed)
     for k, ident in enumerate(idents):
         if ident in idents[:k]:
             raise ValueError(f"ident {ident!r} is given twice")
@@ -1131,12 +1124,32 @@ def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, s
     if int(sizes.sum()) >= MAX_PERM_CELLS:
         raise ValueError(f"{int(sizes.sum())} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + f".{command}.csv"
-    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, strata=None, pairs=None,
-                           names=[name for name, _cols in pops], outpath=outpath,
-                           idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
+    su = SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes,
+                         names=[name for name, _cols in pops], outpath=outpath,
+                         idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
+    if pairs:
+        G = len(sizes)
+        pair_g = np.array([g for g in range(G) for _h in range(g + 1, G)], dtype=np.int32)
+        pair_h = np.array([h for g in range(G) for h in range(g + 1, G)], dtype=np.int32)
+        su.pairs = (pair_g, pair_h)
+        # per permutation and pair the device holds the pair's bits and its key bound
+        su.perm_bytes = int(sum((int(sizes[g]) + int(sizes[h]) + 63) // 64 * 8 + 8 for g, h in zip(pair_g, pair_h)))
+
+        def labellings(ctx, p_first, p_count):
+            check(ctx.lib.scape_hip_report_perm_pair_masks(ctx.h, G, ptr(sizes, P_i32), len(pair_g), ptr(pair_g, P_i32),
+                                                           ptr(pair_h, P_i32), p_first, p_count, seed),
+                  "report_perm_pair_masks")
+    else:
+        su.perm_bytes = int(sizes.sum())                 # one byte per tested cell and permutation
+
+        def labellings(ctx, p_first, p_count):
+            check(ctx.lib.scape_hip_report_perm_labels(ctx.h, len(sizes), ptr(sizes, P_i32), p_first, p_count, seed),
+                  "report_perm_labels")
+    su.labellings = labellings
+    return su
 
 
-def _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times):
+def _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, lines, genes, times):
     """one counted batch: the kept rows of its tested records go through the G-way permutation test; appends the
     per-line arrays to `lines` and (gene_info_str, lines, S(0), gene_n_ge) per tested record to `genes`"""
     sel = _perm_rows(ctx, bat, su.seg_off, times)
@@ -1152,18 +1165,16 @@ def _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times
     t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
     site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
     stat0, site_stat0 = np.zeros(len(which), np.float64), np.zeros(len(rows), np.float64)
-    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
+    _perm_chunks(ctx, su, n_perm, chunk, times, lambda: check(
         ctx.lib.scape_hip_report_perm_groups(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G,
                                              ptr(su.seg_off, P_i32), ptr(t, P_i64), ptr(a0, P_i64),
                                              ptr(site_ge, P_i64), ptr(stat0), ptr(site_stat0), ptr(gene_ge, P_i64)),
         "report_perm_groups"))
     t0 = timer()
-    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums)):
-        raise _lib.ScapeHipError("report_perm_groups: row sums differ from report_group_sums")
+    _check_row_sums("report_perm_groups", t, a0, sums, sums)
     for g, r in enumerate(which.tolist()):
         a, b = int(off[g]), int(off[g + 1])
-        if int(t[a:b].sum()) >= 1 << 31:
-            raise ValueError(f"{recs[r].gene_info_str}: 2^31 or more reads in the tested cells")
+        _check_reads(recs[r], t[a:b].sum())
         genes.append((recs[r].gene_info_str, b - a, float(stat0[g]), int(gene_ge[g])))
         lines["pa"].extend(_pa_info(recs[r], rows[a:b] - int(rowbase[r])))
     for key, arr in (("a", a0), ("nz", nz), ("n_ge", site_ge), ("site_stat", site_stat0)):
@@ -1182,7 +1193,7 @@ def _diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
 
     def batch(ctx, bat, chunk, times):
-        _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, seed, lines, genes, times)
+        _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, lines, genes, times)
 
     def write(w):
         w.writerow(DIFF_PA_GROUPS_HEADER + [f"usage.{n}" for n in names] + [f"pct.{n}" for n in names])
@@ -1225,7 +1236,7 @@ def _diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
             cols.extend([repr(x) for x in v[:, g].tolist()] for g in range(G))
         w.writerows(zip(*cols))
 
-    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    wall = _perm_run(su, n_perm, device, batch, write)
     print(f"Finish {n_perm} permutations of {int(su.sizes.sum())} cells in {G} populations for "
           f"{sum(g[1] for g in genes)} pA sites of {len(genes)} tested records")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
@@ -1248,7 +1259,7 @@ DIFF_PA_PAIRS_HEADER = DIFF_PA_HEADER[:2] + ["group_1", "group_2"] + DIFF_PA_HEA
 MAX_PAIR_RESULT_BYTES = 256 << 20     # host and device bytes of the counters of one call: more pairs are taken in ranges
 
 
-def _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, seed, blocks, times):
+def _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, blocks, times):
     """one counted batch: the rows kept over all populations of the records that two populations or more have reads in
     go through every pair's test, the pairs in ranges of at most MAX_PAIR_RESULT_BYTES of counters; appends to
     blocks[k] = (lines, genes) of pair k what _diff_pa_batch appends for the two populations of that pair"""
@@ -1271,10 +1282,9 @@ def _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, seed, blocks, times):
                                                       ptr(su.seg_off, P_i32), k, m, ptr(t, P_i64), ptr(a0, P_i64),
                                                       ptr(site_ge[k:k + m], P_i64), ptr(stat0[k:k + m]),
                                                       ptr(gene_ge[k:k + m], P_i64)), "report_perm_pairs")
-    _perm_chunks(ctx, su, n_perm, chunk, seed, times, test)
+    _perm_chunks(ctx, su, n_perm, chunk, times, test)
     t0 = timer()
-    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums)):
-        raise _lib.ScapeHipError("report_perm_pairs: row sums differ from report_group_sums")
+    _check_row_sums("report_perm_pairs", t, a0, sums, sums)
     pa = np.array(_pa_infos(recs, np.repeat(which, np.diff(off)), rows - rowbase[np.repeat(which, np.diff(off))]),
                   dtype=object)
     rec_of = np.repeat(np.arange(n_rec), np.diff(off))
@@ -1300,14 +1310,13 @@ def _diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, i
     """diff_pa for every pair of the populations of a cluster file (every cluster, or the clusters `idents` in the order
     given) from one pass over the result file; writes <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_pairs.csv in
     output_dir, one block per pair, the p-values adjusted over the whole file, and returns its path"""
-    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_pairs")
+    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_pairs", pairs=True)
     names, G = su.names, len(su.sizes)
-    pairs = [(g, h) for g in range(G) for h in range(g + 1, G)]
-    su.pairs = (np.array([g for g, _h in pairs], dtype=np.int32), np.array([h for _g, h in pairs], dtype=np.int32))
+    pairs = list(zip(su.pairs[0].tolist(), su.pairs[1].tolist()))
     blocks = [({k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}, []) for _ in pairs]
 
     def batch(ctx, bat, chunk, times):
-        _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, seed, blocks, times)
+        _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, blocks, times)
 
     def write(w):
         w.writerow(DIFF_PA_PAIRS_HEADER)
@@ -1327,7 +1336,7 @@ def _diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, i
             line0 += n
             gene0 += len(c.gene_p)
 
-    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    wall = _perm_run(su, n_perm, device, batch, write)
     print(f"Finish {n_perm} permutations of {len(pairs)} pairs of {G} populations ({int(su.sizes.sum())} cells) for "
           f"{sum(g[1] for _l, genes in blocks for g in genes)} lines of {sum(len(genes) for _l, genes in blocks)} tested "
           "(pair, record) combinations")
@@ -1386,7 +1395,7 @@ def _mean_positions_groups(x, a):
     return float(Fraction(St, T * D)), mean, delta
 
 
-def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
+def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, out, times):
     """one counted batch: appends (gene, num_pa, [A_g], mean_pos, eta2, n_ge, top group, [mean_pos.<g>],
     [delta_pos.<g>], [n_ge.<g>]) per tested record to `out`"""
     recs, G = bat.recs, len(su.sizes)
@@ -1401,8 +1410,7 @@ def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
     q = np.ascontiguousarray(np.concatenate(qs))
     T = np.add.reduceat(sums.sum(axis=1), off[:-1])
     for g, r in enumerate(which.tolist()):
-        if int(T[g]) >= 1 << 31:
-            raise ValueError(f"{recs[r].gene_info_str}: 2^31 or more reads in the tested cells")
+        _check_reads(recs[r], T[g])
     qspan = [int(qi.max()) for qi in qs]
     tol_stat = np.array([math.ldexp(float(int(Tr) * sp * sp), -40) for Tr, sp in zip(T.tolist(), qspan)])
     tol_delta = np.array([math.ldexp(float(sp), -40) for sp in qspan])
@@ -1410,14 +1418,13 @@ def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, seed, out, times):
     t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
     stat0, delta0 = np.zeros(len(which), np.float64), np.zeros((len(which), G), np.float64)
     n_ge, group_ge = np.zeros(len(which), np.int64), np.zeros((len(which), G), np.int64)
-    _perm_chunks(ctx, su, n_perm, chunk, seed, times, lambda: check(
+    _perm_chunks(ctx, su, n_perm, chunk, times, lambda: check(
         ctx.lib.scape_hip_report_perm_len_groups(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G,
                                                  ptr(su.seg_off, P_i32), ptr(q, P_i32), ptr(tol_stat), ptr(tol_delta),
                                                  ptr(t, P_i64), ptr(a0, P_i64), ptr(stat0), ptr(delta0),
                                                  ptr(n_ge, P_i64), ptr(group_ge, P_i64)), "report_perm_len_groups"))
     t0 = timer()
-    if not (np.array_equal(t, sums.sum(axis=1)) and np.array_equal(a0, sums)):
-        raise _lib.ScapeHipError("report_perm_len_groups: row sums differ from report_group_sums")
+    _check_row_sums("report_perm_len_groups", t, a0, sums, sums)
     for g, r in enumerate(which.tolist()):
         sl = slice(int(off[g]), int(off[g + 1]))
         a, qi = a0[sl].tolist(), qs[g].tolist()
@@ -1460,7 +1467,7 @@ def _diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: s
     out = []
 
     def batch(ctx, bat, chunk, times):
-        _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, seed, out, times)
+        _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, out, times)
 
     def write(w):
         w.writerow(DIFF_PA_LEN_GROUPS_HEADER + [f"{c}.{n}" for n in names for c in DIFF_PA_LEN_GROUPS_PER_GROUP])
@@ -1480,7 +1487,7 @@ def _diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: s
                 line += [repr(delta_g[g]), group_ge[g], *group_p[(k, g)]] if (k, g) in group_p else [""] * 4
             w.writerow(line)
 
-    wall = _perm_run(su, n_perm, seed, device, batch, write)
+    wall = _perm_run(su, n_perm, device, batch, write)
     print(f"Finish {n_perm} permutations of {int(su.sizes.sum())} cells in {G} populations for {len(out)} tested records")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
@@ -1691,6 +1698,26 @@ def _perm_options(f):
     return f
 
 
+def _groups_options(f):
+    """the options diff_pa_groups, diff_pa_len_groups and diff_pa_pairs share (the help of --n_perm and --seed differs)"""
+    for option in reversed((
+            click.option('--output_dir', type=str, required=True,
+                         help='Directory which was used in previous steps to save output by prepare_input and '
+                              'infer_pa.'),
+            click.option('--res_pkl_file', type=str, default="None",
+                         help='Name of res pickle file that contains PASs. Its name will be included in the file name '
+                              'of the final result.'),
+            click.option('--cell_cluster_file', type=str, required=True,
+                         help='An csv file containing two columns in order: cell barcode index (index) and respective '
+                              'group. Cells with an empty group, or not listed, are left out. Its name will be '
+                              'included in the file name of the final result.'),
+            click.option('--idents', type=str, multiple=True,
+                         help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. '
+                              'Default: every cluster of the cell_cluster_file, in order of first appearance.'))):
+        f = option(f)
+    return f
+
+
 @click.command(name="diff_pa")
 @_perm_options
 @click.option('--seed', type=int, default=1, show_default=True, help='Seed of the permutations, 0 .. 2^64 - 1.')
@@ -1715,18 +1742,7 @@ def diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, iden
 
 
 @click.command(name="diff_pa_groups")
-@click.option('--output_dir', type=str, required=True,
-              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
-@click.option('--res_pkl_file', type=str, default="None",
-              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the final '
-                   'result.')
-@click.option('--cell_cluster_file', type=str, required=True,
-              help='An csv file containing two columns in order: cell barcode index (index) and respective group. Cells '
-                   'with an empty group, or not listed, are left out. Its name will be included in the file name of the '
-                   'final result.')
-@click.option('--idents', type=str, multiple=True,
-              help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. Default: every '
-                   'cluster of the cell_cluster_file, in order of first appearance.')
+@_groups_options
 @click.option('--n_perm', type=int, default=9999, show_default=True,
               help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
 @click.option('--seed', type=int, default=1, show_default=True,
@@ -1738,18 +1754,7 @@ def diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, i
 
 
 @click.command(name="diff_pa_len_groups")
-@click.option('--output_dir', type=str, required=True,
-              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
-@click.option('--res_pkl_file', type=str, default="None",
-              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the final '
-                   'result.')
-@click.option('--cell_cluster_file', type=str, required=True,
-              help='An csv file containing two columns in order: cell barcode index (index) and respective group. Cells '
-                   'with an empty group, or not listed, are left out. Its name will be included in the file name of the '
-                   'final result.')
-@click.option('--idents', type=str, multiple=True,
-              help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. Default: every '
-                   'cluster of the cell_cluster_file, in order of first appearance.')
+@_groups_options
 @click.option('--n_perm', type=int, default=9999, show_default=True,
               help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).')
 @click.option('--seed', type=int, default=1, show_default=True,
@@ -1763,18 +1768,7 @@ def diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: st
 
 
 @click.command(name="diff_pa_pairs")
-@click.option('--output_dir', type=str, required=True,
-              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
-@click.option('--res_pkl_file', type=str, default="None",
-              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the final '
-                   'result.')
-@click.option('--cell_cluster_file', type=str, required=True,
-              help='An csv file containing two columns in order: cell barcode index (index) and respective group. Cells '
-                   'with an empty group, or not listed, are left out. Its name will be included in the file name of the '
-                   'final result.')
-@click.option('--idents', type=str, multiple=True,
-              help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. Default: every '
-                   'cluster of the cell_cluster_file, in order of first appearance.')
+@_groups_options
 @click.option('--n_perm', type=int, default=9999, show_default=True,
               help='Permutations of the cell labels per pair; the smallest p-value is 1 / (1 + n_perm).')
 @click.option('--seed', type=int, default=1, show_default=True,

@@ -487,6 +487,48 @@ def test_entry_point(G):
         lib.scape_hip_report_free(ctx.h)
 
 
+@pytest.mark.gpu
+def test_single_pair_is_perm_test_bit_for_bit():
+    """rc.entry_point_matrix() as it stands, 70 + 91 cells, 300 permutations in one chunk: scape_hip_report_perm_test
+    behind scape_hip_report_perm_masks(70, 91) and scape_hip_report_perm_pairs behind the pair masks of the single pair
+    (0, 1), on the same rows, offsets and seed, return the same t, a0, counters and the same bits of S(0).  No row is
+    passed over and no record skipped: every kept row has a read in the 161 columns, every record two such rows or more
+    and reads in both populations (checked on the dense matrix first)"""
+    from scape_amd import _lib
+    from scape_amd._lib import P_d, P_i32, P_i64, check as chk, ptr
+    n1, n2, n_cols, seed, n_perm, Ks, off, lab, cb, dense, rows, roff, _rng = rc.entry_point_matrix()
+    sub = dense[rows]
+    assert np.all(sub[:, :n1 + n2].sum(axis=1) > 0) and np.all(np.diff(roff) >= 2)
+    A0, B0 = np.add.reduceat(sub[:, :n1].sum(axis=1), roff[:-1]), np.add.reduceat(sub[:, n1:n1 + n2].sum(axis=1), roff[:-1])
+    assert np.all(A0 > 0) and np.all(B0 > 0)
+    n_rows, n_rec = len(rows), len(Ks)
+    seg = np.array([0, n1, n1 + n2], dtype=np.int32)
+    ctx = _lib.default_context(None)
+    lib = ctx.lib
+    try:
+        assert np.array_equal(rc.device_counts(ctx, Ks, off, lab, cb, n_cols), dense.sum(axis=1))
+        t, a0, site, gene = (np.full(n_rows, -1, np.int64), np.full(n_rows, -1, np.int64), np.zeros(n_rows, np.int64),
+                             np.zeros(n_rec, np.int64))
+        stat = np.full(n_rec, -1.0)
+        chk(lib.scape_hip_report_perm_masks(ctx.h, n1, n2, 1, n_perm, seed), "perm_masks")
+        chk(lib.scape_hip_report_perm_test(ctx.h, n_rec, ptr(roff, P_i64), ptr(rows, P_i64), ptr(t, P_i64), ptr(a0, P_i64),
+                                           ptr(site, P_i64), ptr(stat, P_d), ptr(gene, P_i64)), "perm_test")
+        pt, pa0, psite, pgene = (np.full(n_rows, -1, np.int64), np.full((n_rows, 2), -1, np.int64),
+                                 np.zeros((1, n_rows), np.int64), np.zeros((1, n_rec), np.int64))
+        pstat = np.full((1, n_rec), -1.0)
+        chk(_pair_masks(ctx, (n1, n2), [(0, 1)], 1, n_perm, seed), "pair_masks")
+        chk(lib.scape_hip_report_perm_pairs(ctx.h, n_rec, ptr(roff, P_i64), ptr(rows, P_i64), 2, ptr(seg, P_i32), 0, 1,
+                                            ptr(pt, P_i64), ptr(pa0, P_i64), ptr(psite, P_i64), ptr(pstat, P_d),
+                                            ptr(pgene, P_i64)), "perm_pairs")
+        assert np.array_equal(pt, t) and np.array_equal(t, sub[:, :n1 + n2].sum(axis=1))
+        assert np.array_equal(pa0[:, 0], a0)
+        assert np.array_equal(psite[0], site)
+        assert np.array_equal(pgene[0], gene)
+        assert np.array_equal(pstat[0].view(np.uint64), stat.view(np.uint64)) and np.all(stat > 0)
+    finally:
+        lib.scape_hip_report_free(ctx.h)
+
+
 # ---------------------------------------------------------------- GPU: the command
 def _blocks(text):
     """header check; {(group_1, group_2): the lines of that block}, the blocks in file order"""
