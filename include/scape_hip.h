@@ -370,6 +370,44 @@ int scape_hip_report_perm_pairs(scape_hip_ctx *ctx, int32_t n_rec, const int64_t
                                 int32_t n_groups, const int32_t *seg_off, int32_t pair_first, int32_t pair_count,
                                 int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                 int64_t *gene_n_ge_out);
+/* diff_pa_markers: each of n_markers populations (1 .. 64, sizes[g] >= 1 cells) tested, as diff_pa tests two, against ALL
+   other tested cells, from one counts call.  The tested columns are the first n = sum sizes + n_others columns of the
+   count matrix: marker 0's columns first, then marker 1's, ..., then a segment of n_others >= 0 "others" (tested cells of
+   no marker); slot j is that position.  orig_rank[j] is the rank of slot j's column among the n tested columns in the
+   caller's own column order, a permutation of 0 .. n - 1 that ascends within every segment.  Marker g is
+   scape_hip_report_perm_masks(sizes[g], n - sizes[g], p_first, p_count, seed) on the layout that puts g's columns first
+   and every other tested column behind them in the caller's order: slot j has the local position
+     local_g(j) = j - (sizes[0] + .. + sizes[g-1])                                  in g's own segment,
+     local_g(j) = sizes[g] + orig_rank[j] - #{cells of g with a smaller orig_rank}    anywhere else,
+   and permutation p >= 1 gives g the sizes[g] local positions with the smallest key(p, local position), the key above,
+   unchanged.  scape_hip_report_perm_marker_masks builds the bits of permutations p_first .. p_first + p_count - 1 on the
+   device IN SLOT ORDER: ceil(n / 64) words per marker and permutation, laid out [marker * words + word][permutation], and
+   one 8-byte key bound per (marker, permutation); local_g is found by a search in g's ranks, no table is kept.  They are
+   a buffer of their own, replace those of an earlier call and stay until scape_hip_report_free.  Checked before anything
+   is queued or released: 1 <= n_markers <= 64, every size >= 1, n_others >= 0, 2 <= n < 2^24, every marker smaller than
+   n, orig_rank as stated, p_first >= 1, p_count >= 1, fewer than 2^31 words over all markers; a call refused by a check
+   keeps the earlier bits. */
+int scape_hip_report_perm_marker_masks(scape_hip_ctx *ctx, int32_t n_markers, const int32_t *sizes, int32_t n_others,
+                                       const int32_t *orig_rank, int64_t p_first, int32_t p_count, uint64_t seed);
+/* The ceil(n / 64) membership words of marker `marker` under permutation p_first + p (0 <= p < p_count) of the last
+   marker masks call: bit j % 64 of words_out[j / 64] is set when SLOT j is in the marker's population. */
+int scape_hip_report_perm_marker_bits_get(scape_hip_ctx *ctx, int32_t marker, int32_t p, uint64_t *words_out);
+/* The test of n_rec records of the last counts call by the markers marker_first .. marker_first + marker_count - 1 of the
+   last marker masks call; records, kept rows and the ADD semantics as in scape_hip_report_perm_test.  n_seg = n_markers
+   + 1 and seg_off[n_seg + 1] name the column ranges of the markers and of the others (the last segment, which may be
+   empty), checked against the marker masks call as scape_hip_report_perm_groups checks its groups.  t_out[i] = the row's
+   sum over the n tested columns, a0_out[i * n_seg + g] = its sum over segment g: t_i and T are the same for every
+   marker.  Marker g tests record r when at least two of its rows have t_i > 0 and 0 < A_g(0) < T; then S and d_i are those
+   of scape_hip_report_perm_test (one device function, contraction off, the same 1 - 2^-40 slack, rows in order), so
+   stat0_out[k * n_rec + r] has the bits, and site_n_ge_out[k * n_rows + i] and gene_n_ge_out[k * n_rec + r] (both ADDED
+   to) the values, of a scape_hip_report_perm_test call on the marker's population against all other tested cells, k
+   counting from marker_first.  For a record the marker does not test stat0_out is 0 and nothing is added.
+   marker_count * n_rec < 2^31.
+   LDS: 1 KiB per row of a record held at once, in the classes 4 .. 64 rows of scape_hip_report_perm_test. */
+int scape_hip_report_perm_markers(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                  int32_t n_seg, const int32_t *seg_off, int32_t marker_first, int32_t marker_count,
+                                  int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
+                                  int64_t *gene_n_ge_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

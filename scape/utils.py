@@ -1,7 +1,7 @@
 """``scape.utils`` import path of the reference's two reporting commands (utils.py:319-427, :438-553) and of
 ``ex_pa_pseudobulk``, which sums their count matrix over cell groups, and ``diff_pa`` / ``diff_pa_len``, which test
 it between two (per pA site, and per gene for a shift of the 3'UTR length), and ``diff_pa_groups`` /
-``diff_pa_len_groups``, which test the same two questions across all clusters at once, and ``diff_pa_pairs``, which
-runs ``diff_pa`` on every pair of clusters."""
+``diff_pa_len_groups``, which test the same two questions across all clusters at once, and ``diff_pa_pairs`` and
+``diff_pa_markers``, which run ``diff_pa`` on every pair of clusters and on every cluster against all other cells."""
 from scape_amd.report import (cal_exp_pa_len, diff_pa, diff_pa_groups, diff_pa_len, diff_pa_len_groups,  # noqa: F401
-                              diff_pa_pairs, ex_pa_cnt_mat, ex_pa_pseudobulk)
+                              diff_pa_markers, diff_pa_pairs, ex_pa_cnt_mat, ex_pa_pseudobulk)

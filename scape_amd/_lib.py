@@ -82,6 +82,10 @@ SIGNATURES = {
     "scape_hip_report_perm_pair_bits_get": (c_i, [P_void, c_i32, c_i32, ctypes.POINTER(ctypes.c_uint64)]),
     "scape_hip_report_perm_pairs": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, c_i32, c_i32, P_i64, P_i64, P_i64,
                                           P_d, P_i64]),
+    "scape_hip_report_perm_marker_masks": (c_i, [P_void, c_i32, P_i32, c_i32, P_i32, c_i64, c_i32, ctypes.c_uint64]),
+    "scape_hip_report_perm_marker_bits_get": (c_i, [P_void, c_i32, c_i32, ctypes.POINTER(ctypes.c_uint64)]),
+    "scape_hip_report_perm_markers": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, c_i32, c_i32, P_i64, P_i64, P_i64,
+                                            P_d, P_i64]),
     "scape_hip_report_fetch": (c_i, [P_void, c_i32, ctypes.POINTER(P_void), P_i64]),
     "scape_hip_report_hist": (c_i, [P_void, c_i32, P_i64, P_i32, P_i64, P_i64, c_i64, c_i64, P_i32, c_i32,
                                     P_i64, P_i64]),

@@ -1,6 +1,6 @@
 // perm.inc - the permutation tests on merge_pa's count matrix: diff_pa and diff_pa_len (freely or within strata),
-// diff_pa_groups, diff_pa_len_groups and diff_pa_pairs (included by scape_hip.hip after report.inc, whose ReportState,
-// block helpers and k_rep_scan it uses).
+// diff_pa_groups, diff_pa_len_groups, diff_pa_pairs and diff_pa_markers (included by scape_hip.hip after report.inc, whose
+// ReportState, block helpers and k_rep_scan it uses).
 //
 // A test is two calls.  The first builds the labellings of a chunk of permutations, in exact integers:
 //   rep_select_key  the one radix select of the file: the key of a given rank among the hashed 64-bit keys of a set of
@@ -31,6 +31,10 @@
 //                   diff_pa_pairs: the membership bits of every (pair of populations, permutation), per kept row the
 //                   first nonzero of every population's column segment, and diff_pa's test for every pair from the one
 //                   compaction, a pair walking the nonzeros of its two segments only
+//   k_rep_perm_marker_masks / k_rep_perm_markers
+//                   diff_pa_markers: the membership bits of every (marker population, permutation) in the order of the
+//                   count matrix's columns, each marker's own local positions found by a search in its ranks, and
+//                   diff_pa's test of every marker against all other tested cells from the one compaction
 // On the host rep_perm_classes / rep_perm_launch_classes launch the two-population test per LDS class of records, and
 // the exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
 // stay on the host (scape_amd/report.py).
@@ -287,8 +291,8 @@ __device__ __forceinline__ double rep_perm_row(long long a, long long t, long lo
 
 // the sum of the nonzeros nz[k0 .. k1), at the positions column + shift, over this lane's population 1: the nonzeros are
 // wave-uniform, the lane tests its own permutation's bit.  Positions ascend, so a mask word is loaded once for all the
-// nonzeros that fall into it.  shift = 0 for a row of diff_pa and diff_pa_len; a pair of diff_pa_pairs moves each of its
-// two column segments to the pair's local positions
+// nonzeros that fall into it.  shift = 0 for a row of diff_pa, diff_pa_len and diff_pa_markers (whose bits lie in column
+// order); a pair of diff_pa_pairs moves each of its two column segments to the pair's local positions
 __device__ __forceinline__ int rep_perm_segsum(const uint2 *__restrict__ nz, int64_t k0, int64_t k1, int shift,
                                                const unsigned long long *__restrict__ mb, int64_t pstride) {
     int a = 0, cur = -1;
@@ -482,13 +486,14 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_labels(int32_t n_group
 }
 
 // one workgroup per kept row i (count row rows[i]): a0[i * n_groups + g] = its sum over group g as observed (the columns
-// [seg_off[g], seg_off[g + 1]); wave w takes groups w, w + REP_WAVES, ...), t[i] = their sum, nnz[i] = its nonzeros
+// [seg_off[g], seg_off[g + 1]); wave w takes groups w, w + REP_WAVES, ...), t[i] = their sum, nnz[i] = its nonzeros.
+// n_groups <= REP_GROUPS_MAX + 1: diff_pa_markers has a segment of other cells behind its 64 markers at most
 __global__ __launch_bounds__(REP_THREADS) void k_rep_groups_rowstat(const int64_t *__restrict__ rows, int32_t n_cols,
                                                                     const int32_t *__restrict__ cnt, int32_t n_groups,
                                                                     const int32_t *__restrict__ seg_off,
                                                                     int64_t *__restrict__ nnz, int64_t *__restrict__ t,
                                                                     int64_t *__restrict__ a0) {
-    __shared__ long long sum_g[REP_GROUPS_MAX], nz_g[REP_GROUPS_MAX];
+    __shared__ long long sum_g[REP_GROUPS_MAX + 1], nz_g[REP_GROUPS_MAX + 1];
     const int i = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int32_t *row = cnt + rows[i] * n_cols;
     for (int g = w; g < n_groups; g += REP_WAVES) {
@@ -934,11 +939,136 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_pairs(
     if (tile == 0 && threadIdx.x == 0) stat0[out_r] = S0;
 }
 
+// ---- diff_pa_markers: every marker population against all other tested cells, each as diff_pa ------------------------
+// The count matrix is laid out as for the G-way tests: marker 0's columns first, then marker 1's, ..., then a segment of
+// "others" (tested cells of no marker; it may be empty), columns ascending within a segment; slot j is that position and
+// n the tested cells.  Marker g is diff_pa of its population against the n - n_g other tested cells.  diff_pa would put
+// g's columns at the local positions 0 .. n_g - 1 and all others, ascending, at n_g .. n - 1: with rank[j] the rank of
+// slot j's column among the n tested columns ascending (it ascends within a segment),
+//   local_g(j) = j - seg_off[g]                                           for a slot of g's own segment
+//   local_g(j) = n_g + rank[j] - #{cells of g with a smaller rank}         for any other slot,
+// the count a lower bound in g's ascending slice of rank.  Permutation p >= 1 gives g the n_g local positions with the
+// smallest key(p, local position): key, seed and labellings of scape_hip_report_perm_masks(n_g, n - n_g).  The bits are
+// stored in SLOT order, so the test walks the one compaction of a row with shift 0, as k_rep_perm_test does, and t_i,
+// the kept rows and T are the same for every marker.
+__device__ __forceinline__ int rep_marker_local(int j, int s0, int s1, const int32_t *__restrict__ rank) {
+    if (j >= s0 && j < s1) return j - s0;
+    const int r = rank[j];
+    int lo = s0, hi = s1;                    // lo - s0 = cells of the marker whose rank is smaller
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rank[mid] < r) lo = mid + 1;
+        else hi = mid;
+    }
+    return (s1 - s0) + r - (lo - s0);
+}
+
+// one workgroup per (permutation p_first + blockIdx.x, marker blockIdx.y): the n_g-th smallest of the n keys key(p, i),
+// i < n, by wave 0 alone for n up to REP_STRATA_WAVE_MAX and by rep_select_key for more, as k_rep_perm_pair_masks;
+// bound[marker][permutation] = that key + 1; then bit of slot j = (key(p, local_g(j)) < bound) of
+// bits[(marker * n_words + j / 64) * p_count + blockIdx.x].  The marker's slice of rank is read by every lane's search
+// and stays in cache; the search is 4.7 ms of the launch's 12.2 ms for 12 markers of 20,000 cells and 9,999 permutations
+// (profiles/diff_pa_markers_timing.txt, which also says why no table of local positions is kept).  The branch is
+// uniform over the workgroup (n is the launch's).
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_marker_masks(const int32_t *__restrict__ seg_off,
+                                                                       const int32_t *__restrict__ rank, int32_t n,
+                                                                       unsigned long long p_first, int32_t p_count,
+                                                                       unsigned long long seed, unsigned long long *bound,
+                                                                       unsigned long long *__restrict__ bits) {
+    __shared__ RepSelectLds lds;
+    const int s0 = seg_off[blockIdx.y], s1 = seg_off[blockIdx.y + 1], n_g = s1 - s0;
+    const unsigned long long base = rep_mix(seed + REP_PERM_G * (p_first + blockIdx.x));
+    unsigned long long *bound_p = bound + (int64_t)blockIdx.y * p_count + blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (n <= REP_STRATA_WAVE_MAX) {
+        const int4 d = make_int4(0, n_g, n_g, n - n_g);
+        if (wave == 0) {
+            if (n <= 64) rep_strata_wave<1>(base, d, lane, bound_p);
+            else rep_strata_wave<REP_STRATA_WAVE_MAX / 64>(base, d, lane, bound_p);
+        }
+    } else {
+        unsigned long long k;
+        if (rep_select_key(base, RepAllCells{n}, n_g - 1, &lds, &k)) *bound_p = k + 1;
+    }
+    __syncthreads();                         // this labelling's bound is stored
+    const unsigned long long b = *bound_p;
+    const int n_words = (n + 63) >> 6;
+    for (int w = wave; w < n_words; w += REP_WAVES) {
+        const int j = w * 64 + lane;
+        const unsigned long long m = __ballot(j < n && rep_perm_key(base, rep_marker_local(j, s0, s1, rank)) < b);
+        if (lane == 0) bits[((int64_t)blockIdx.y * n_words + w) * p_count + blockIdx.x] = m;
+    }
+}
+
+// workgroup = (marker marker_first + blockIdx.y, record recs[blockIdx.x / n_tiles], tile of 256 permutations), one lane
+// per permutation, as k_rep_perm_test: a_i(p) of the record's rows in LDS as acc[row][lane] (each lane its own column, no
+// barrier), a record with more than `cap` rows in groups of cap rows behind one extra walk that forms A(p).  t[i] = the
+// row's sum over all n tested cells, a0[i * n_seg + g] its observed sum over segment g.  The marker tests the record when
+// two rows or more have a read and both the marker and its rest have reads; otherwise the workgroup stores S(0) = 0 and
+// leaves (uniform: the decision reads the record's sums only).  Counters: site_ge[marker in range][row], gene_ge and
+// stat0[marker in range][record], one atomic per wave and counter.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_markers(
+    const unsigned long long *__restrict__ bits, int32_t p_count, int32_t n_tiles, int32_t n_words,
+    const int32_t *__restrict__ recs, const int64_t *__restrict__ roff, const int64_t *__restrict__ noff,
+    const uint2 *__restrict__ nz, const int64_t *__restrict__ t, const int64_t *__restrict__ a0, int32_t n_seg,
+    int32_t marker_first, int64_t n_rows, int32_t n_rec, int32_t cap, int32_t *__restrict__ site_ge,
+    int32_t *__restrict__ gene_ge, double *__restrict__ stat0) {
+#pragma clang fp contract(off)
+    extern __shared__ int32_t rep_acc[];
+    const int g = marker_first + blockIdx.y;
+    const int r = recs[blockIdx.x / n_tiles], tile = blockIdx.x % n_tiles;
+    const int64_t out_r = (int64_t)blockIdx.y * n_rec + r;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    const int64_t *a0g = a0 + g;
+    long long T = 0, A0 = 0;
+    int with_reads = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        T += t[i];
+        A0 += a0g[i * n_seg];
+        with_reads += t[i] > 0;
+    }
+    if (with_reads < 2 || A0 == 0 || A0 == T) {
+        if (tile == 0 && threadIdx.x == 0) stat0[out_r] = 0.0;
+        return;
+    }
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const unsigned long long *mb = bits + (int64_t)g * n_words * p_count + (valid ? p : p_count - 1);
+    int32_t *acc = rep_acc + threadIdx.x;
+    int32_t *site = site_ge + (int64_t)blockIdx.y * n_rows;
+    long long A = 0;
+    const bool one = row1 - row0 <= cap;
+    if (!one)
+        for (int64_t i = row0; i < row1; ++i) A += rep_perm_segsum(nz, noff[i], noff[i + 1], 0, mb, p_count);
+    double S = 0.0, S0 = 0.0;
+    for (int64_t g0 = row0; g0 < row1; g0 += cap) {
+        const int64_t g1 = g0 + cap < row1 ? g0 + cap : row1;
+        long long Ag = 0;
+        for (int64_t i = g0; i < g1; ++i) {
+            const int a = rep_perm_segsum(nz, noff[i], noff[i + 1], 0, mb, p_count);
+            acc[(i - g0) * REP_THREADS] = a;
+            Ag += a;
+        }
+        if (one) A = Ag;
+        for (int64_t i = g0; i < g1; ++i) {
+            double d, d0;
+            S = S + rep_perm_row(acc[(i - g0) * REP_THREADS], t[i], A, T, &d);
+            S0 = S0 + rep_perm_row(a0g[i * n_seg], t[i], A0, T, &d0);
+            const unsigned long long b = __ballot(valid && fabs(d) >= fabs(d0) * REP_PERM_SLACK);
+            if ((threadIdx.x & 63) == 0 && b) atomicAdd(&site[i], __popcll(b));
+        }
+    }
+    const unsigned long long b = __ballot(valid && S >= S0 * REP_PERM_SLACK);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[out_r], __popcll(b));
+    if (tile == 0 && threadIdx.x == 0) stat0[out_r] = S0;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
 static const int REP_PERM_N_CAPS = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
 
-// the records by LDS class, for k_rep_perm_test and k_rep_perm_pairs: the smallest cap that holds all of a record's rows
+// the records by LDS class, for k_rep_perm_test, k_rep_perm_pairs and k_rep_perm_markers: the smallest cap that holds all of a record's rows
 // (the largest cap takes the rest, in groups).  recs = the records in class order, count[q] = those of class q
 struct RepPermClasses {
     std::vector<int32_t> recs;
@@ -1478,6 +1608,108 @@ int scape_hip_report_perm_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *
                                s->q_a0.as<int64_t>(), n_groups, s->q_seg.as<int32_t>(),
                                s->x_desc.as<RepPair>() + pair_first, n_rows, n_rec, cap, s->p_site.as<int32_t>(),
                                s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
+        });
+    });
+}
+
+int scape_hip_report_perm_marker_masks(scape_hip_ctx *c, int32_t n_markers, const int32_t *sizes, int32_t n_others,
+                                       const int32_t *orig_rank, int64_t p_first, int32_t p_count, uint64_t seed) {
+    CTX_ENTER(c);
+    if (n_markers < 1 || n_markers > REP_GROUPS_MAX)
+        return fail("n_markers must lie in 1 .. " + std::to_string(REP_GROUPS_MAX));
+    if (!sizes || !orig_rank) return fail("bad argument");
+    if (rep_group_sizes_ok(n_markers, sizes)) return 1;
+    if (n_others < 0) return fail("n_others must not be negative");
+    std::vector<int32_t> seg((size_t)n_markers + 2, 0);      // the markers' segments, then the others'
+    int64_t n = n_others;
+    for (int32_t g = 0; g < n_markers; ++g) n += sizes[g];
+    if (n < 2) return fail("the tested cells must number at least 2");
+    if (rep_perm_chunk_ok(n, "the tested cells must number", p_first, p_count)) return 1;
+    for (int32_t g = 0; g < n_markers; ++g) {
+        if (sizes[g] >= n)
+            return fail("marker " + std::to_string(g) + " holds every tested cell: its rest needs at least one");
+        seg[(size_t)g + 1] = seg[g] + sizes[g];
+    }
+    seg[(size_t)n_markers + 1] = (int32_t)n;
+    std::vector<bool> seen((size_t)n, false);
+    for (int32_t g = 0; g <= n_markers; ++g)
+        for (int32_t j = seg[g]; j < seg[(size_t)g + 1]; ++j) {
+            const int32_t r = orig_rank[j];
+            if (r < 0 || r >= n || seen[r]) return fail("orig_rank must be a permutation of 0 .. n - 1");
+            seen[r] = true;
+            if (j > seg[g] && r < orig_rank[j - 1]) return fail("orig_rank must ascend within every segment");
+        }
+    const int64_t n_words = (n + 63) / 64, words = n_words * n_markers;
+    if (words > INT32_MAX) return fail("the markers' mask words together must number below 2^31");
+    ReportState *s = report_state(c);
+    s->k_count = 0;
+    if (s->k_bits.ensure(words * p_count * 8) || s->k_bound.ensure((int64_t)n_markers * p_count * 8) ||
+        s->k_seg.ensure(((int64_t)n_markers + 2) * 4) || s->k_rank.ensure(n * 4))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->k_seg.p, seg.data(), ((int64_t)n_markers + 2) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->k_rank.p, orig_rank, n * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_perm_marker_masks, dim3(p_count, n_markers), dim3(REP_THREADS), 0, c->stream,
+                       s->k_seg.as<int32_t>(), s->k_rank.as<int32_t>(), (int32_t)n, (unsigned long long)p_first, p_count,
+                       (unsigned long long)seed, s->k_bound.as<unsigned long long>(),
+                       s->k_bits.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    s->k_sizes.assign(sizes, sizes + n_markers);
+    s->k_sizes.push_back(n_others);
+    s->k_count = p_count;
+    return 0;
+}
+
+int scape_hip_report_perm_marker_bits_get(scape_hip_ctx *c, int32_t marker, int32_t p, uint64_t *words_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->k_count) return fail("scape_hip_report_perm_marker_masks has not been called");
+    if (!words_out) return fail("bad argument");
+    if (marker < 0 || marker >= (int32_t)s->k_sizes.size() - 1)
+        return fail("marker must name a marker of the last marker masks call");
+    if (p < 0 || p >= s->k_count) return fail("p must name a permutation of the last marker masks call");
+    int64_t n = 0;
+    for (const int32_t m : s->k_sizes) n += m;
+    const int64_t n_words = (n + 63) / 64;
+    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->k_bits.as<unsigned long long>() + marker * n_words * s->k_count + p,
+                            (size_t)s->k_count * 8, 8, (size_t)n_words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int scape_hip_report_perm_markers(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                  int32_t n_seg, const int32_t *seg_off, int32_t marker_first, int32_t marker_count,
+                                  int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
+                                  int64_t *gene_n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (rep_perm_ready(s, s ? s->k_count : 0, "scape_hip_report_perm_marker_masks")) return 1;
+    if (rep_groups_match(s->k_sizes, "scape_hip_report_perm_marker_masks", n_seg, seg_off)) return 1;
+    const int32_t n_markers = n_seg - 1;
+    if (marker_first < 0 || marker_count < 1 || marker_first > n_markers - marker_count)
+        return fail("marker_first and marker_count must name markers of the last scape_hip_report_perm_marker_masks call");
+    if (n_rec > 0 && rec_row_off && ((int64_t)marker_count * n_rec > INT32_MAX ||
+                                     rec_row_off[n_rec] > INT64_MAX / 8 / marker_count))
+        return fail("too many markers x records or markers x rows for one call: take the markers in ranges");
+    int64_t n_rows = 0;
+    int32_t n_tiles = 0;
+    const int32_t n = seg_off[n_seg];
+    if (rep_perm_prepare(c, n, s->k_count, "marker masks", 0, n_seg, seg_off, n_rec, rec_row_off, rows, t_out, a0_out,
+                         site_n_ge_out && stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr, nullptr, &n_rows,
+                         &n_tiles))
+        return 1;
+    const int64_t n_out = (int64_t)marker_count * n_rec;
+    if (s->p_recs.ensure((int64_t)n_rec * 4) || s->p_gene.ensure(n_out * 4) || s->p_stat0.ensure(n_out * 8)) return 1;
+    const RepPermClasses cl = rep_perm_classes(n_rec, rec_row_off);
+    return rep_perm_count(c, marker_count * n_rows, (int32_t)n_out, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
+        return rep_perm_launch_classes(c, cl, k_rep_perm_markers, [&](const int32_t *recs, int64_t m, int32_t cap,
+                                                                      size_t lds) {
+            hipLaunchKernelGGL(k_rep_perm_markers, dim3((uint32_t)(m * n_tiles), (uint32_t)marker_count),
+                               dim3(REP_THREADS), lds, c->stream, s->k_bits.as<unsigned long long>(), s->k_count, n_tiles,
+                               (n + 63) / 64, recs, s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(),
+                               s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_seg, marker_first,
+                               n_rows, n_rec, cap, s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(),
+                               s->p_stat0.as<double>());
         });
     });
 }

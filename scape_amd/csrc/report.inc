@@ -67,6 +67,13 @@ struct ReportState {
     DevBuf x_bits, x_bound, x_desc, x_seg;
     std::vector<int32_t> x_pairs, x_sizes;
     int32_t x_count = 0;
+    // diff_pa_markers: the membership bits of every (marker, permutation) of the last scape_hip_report_perm_marker_masks
+    // call ([marker * words + word][permutation], the bits in column order), the exclusive key bound per (marker,
+    // permutation), the segment offsets and the rank of every position's column on the device, and the sizes of the
+    // markers with the number of other cells behind them
+    DevBuf k_bits, k_bound, k_seg, k_rank;
+    std::vector<int32_t> k_sizes;
+    int32_t k_count = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
@@ -94,7 +101,8 @@ static void report_release(scape_hip_ctx *c) {
                      &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
                      &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound,
                      &s->q_lab, &s->q_cut, &s->q_seg, &s->q_a0, &s->q_s0, &s->q_share, &s->v_q, &s->v_tol, &s->v_qt,
-                     &s->v_mean, &s->v_d0, &s->x_bits, &s->x_bound, &s->x_desc, &s->x_seg};
+                     &s->v_mean, &s->v_d0, &s->x_bits, &s->x_bound, &s->x_desc, &s->x_seg, &s->k_bits,
+                     &s->k_bound, &s->k_seg, &s->k_rank};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;

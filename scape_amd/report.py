@@ -1,8 +1,9 @@
 """``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa``,
-``scape diff_pa_len`` and ``scape diff_pa_groups``: the stages after ``merge_pa`` (reference ``src/scape/utils.py:319-427`` and ``:438-553``, with
+``scape diff_pa_len``, ``scape diff_pa_groups``, ``scape diff_pa_len_groups``, ``scape diff_pa_pairs`` and
+``scape diff_pa_markers``: the stages after ``merge_pa`` (reference ``src/scape/utils.py:319-427`` and ``:438-553``, with
 ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of ``apa_core.py:1038-1063``).
 
-All six stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
+All of them stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
 ``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc`` and ``csrc/perm.inc``.  They
 share one host core (section "shared host core" below): ``_Run`` frames a command (stage times, ``.part`` targets, the
 device context and its release), ``_read_inputs`` reads what the count-matrix commands need before the device is
@@ -39,6 +40,8 @@ device's rendering of one text block with the gzip of the previous one.
   diff_pa_groups below).
 * ``diff_pa_pairs``: ``diff_pa`` for every pair of those populations from one pass over the result file, the p-values
   adjusted over all pairs (section diff_pa_pairs below).
+* ``diff_pa_markers``: ``diff_pa --idents_1 X`` for every cluster X against all other clustered cells from one pass
+  over the result file, the p-values adjusted over all markers (section diff_pa_markers below).
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -1093,11 +1096,14 @@ MAX_ROWS_AND_GROUPS = 4000       # kept rows + populations of a record: the roun
 
 
 def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, command="diff_pa_groups",
-                  pairs=False):
-    """what diff_pa_groups, diff_pa_len_groups and diff_pa_pairs (pairs=True: su.pairs = the two groups of every pair,
+                  pairs=False, markers=False):
+    """what diff_pa_groups, diff_pa_len_groups, diff_pa_pairs (pairs=True: su.pairs = the two groups of every pair,
     all (g, h) with g < h in lexicographic order, and the labellings are every pair's membership bits, not the group
-    bytes) do before the device is opened: the argument and prerequisite checks, the populations, the id -> column
-    table that puts population 0's columns first, then population 1's, ..., and the output path
+    bytes) and diff_pa_markers (markers=True: 1 to 64 populations, each against every other cell that has a cluster;
+    those of no population follow the populations as one more column segment, su.seg_off has that segment even when it
+    is empty, su.n counts all tested cells, and the labellings are every marker's membership bits) do before the device
+    is opened: the argument and prerequisite checks, the populations, the id -> column table that puts population 0's
+    columns first, then population 1's, ..., and the output path
     <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv"""
     idents = [str(i) for i in idents or ()]
     _check_perm_args(n_perm, seed)
@@ -1117,17 +1123,43 @@ def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, s
             if ident not in with_cells:
                 raise ValueError(f"cluster {ident!r} has no cell in barcode_index.csv")
         pops = [(ident, with_cells[ident]) for ident in idents]
-    if not 2 <= len(pops) <= MAX_GROUPS:
-        raise ValueError(f"{len(pops)} populations: {command} takes 2 to {MAX_GROUPS}")
-    _table, slot, seg_off, _seg_pop = _samples(pops, 1, inp.n_cols)
+    if markers and not idents and len(pops) > MAX_GROUPS:
+        raise ValueError(f"{len(pops)} clusters: {command} takes at most {MAX_GROUPS} at once, name them with --idents")
+    if not (1 if markers else 2) <= len(pops) <= MAX_GROUPS:
+        raise ValueError(f"{len(pops)} populations: {command} takes {1 if markers else 2} to {MAX_GROUPS}")
     sizes = np.array([len(cols) for _name, cols in pops], dtype=np.int32)
-    if int(sizes.sum()) >= MAX_PERM_CELLS:
-        raise ValueError(f"{int(sizes.sum())} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
+    n = int(sizes.sum())
+    segments = pops
+    if markers:
+        tested = np.sort(np.concatenate([cols for _name, cols in inp.pops]))
+        others = np.setdiff1d(tested, np.concatenate([cols for _name, cols in pops]))
+        n = len(tested)
+        for name, cols in pops:
+            if len(cols) == n:
+                raise ValueError(f"cluster {name!r} holds every cell that has a cluster: the rest has no cell in "
+                                 "barcode_index.csv")
+        segments = pops + [("", others)]
+    _table, slot, seg_off, _seg_pop = _samples(segments, 1, inp.n_cols)
+    if n >= MAX_PERM_CELLS:
+        raise ValueError(f"{n} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + f".{command}.csv"
     su = SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes,
                          names=[name for name, _cols in pops], outpath=outpath,
                          idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
-    if pairs:
+    if markers:
+        if not len(others):
+            su.seg_off = np.append(seg_off, seg_off[-1])     # _samples drops an empty segment
+        su.n = n
+        # the rank of every slot's column among the tested columns ascending: diff_pa's order of a marker's rest
+        orig_rank = np.searchsorted(tested, np.concatenate([cols for _name, cols in segments])).astype(np.int32)
+        # per permutation and marker the device holds the marker's bits over all tested cells and its key bound
+        su.perm_bytes = len(sizes) * ((n + 63) // 64 * 8 + 8)
+
+        def labellings(ctx, p_first, p_count):
+            check(ctx.lib.scape_hip_report_perm_marker_masks(ctx.h, len(sizes), ptr(sizes, P_i32), len(others),
+                                                             ptr(orig_rank, P_i32), p_first, p_count, seed),
+                  "report_perm_marker_masks")
+    elif pairs:
         G = len(sizes)
         pair_g = np.array([g for g in range(G) for _h in range(g + 1, G)], dtype=np.int32)
         pair_h = np.array([h for g in range(G) for h in range(g + 1, G)], dtype=np.int32)
@@ -1259,6 +1291,26 @@ DIFF_PA_PAIRS_HEADER = DIFF_PA_HEADER[:2] + ["group_1", "group_2"] + DIFF_PA_HEA
 MAX_PAIR_RESULT_BYTES = 256 << 20     # host and device bytes of the counters of one call: more pairs are taken in ranges
 
 
+def _write_diff_pa_blocks(w, header, blocks, n_perm):
+    """the file of diff_pa_pairs and diff_pa_markers: one block of diff_pa lines per entry of blocks = (the group fields
+    behind pa_info, versus, the block's _diff_pa_columns), p_val_adj Benjamini-Hochberg over all lines of the file and
+    gene_p_val_adj over all tested (block, record) combinations"""
+    w.writerow(header)
+    if not blocks:
+        return
+    p_adj = _bh(np.concatenate([c.p_val for _groups, _versus, c in blocks]))
+    gene_adj = _bh(np.concatenate([c.gene_p for _groups, _versus, c in blocks]))
+    line0 = gene0 = 0
+    for groups, versus, c in blocks:
+        n = len(c.pa)
+        adj = gene_adj[gene0:gene0 + len(c.gene_p)]
+        w.writerows(zip(c.gene, c.pa, *([g] * n for g in groups), c.pct1, c.pct2, [versus] * n, *c.usage, c.n_ge,
+                        _reprs(c.p_val), _reprs(p_adj[line0:line0 + n]), c.stat0, c.gene_ge,
+                        _reprs(c.gene_p[c.rec_of]), _reprs(adj[c.rec_of]), [n_perm] * n))
+        line0 += n
+        gene0 += len(c.gene_p)
+
+
 def _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, blocks, times):
     """one counted batch: the rows kept over all populations of the records that two populations or more have reads in
     go through every pair's test, the pairs in ranges of at most MAX_PAIR_RESULT_BYTES of counters; appends to
@@ -1319,27 +1371,107 @@ def _diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, i
         _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, blocks, times)
 
     def write(w):
-        w.writerow(DIFF_PA_PAIRS_HEADER)
-        cols = [(names[g], names[h], _diff_pa_columns(genes, lines, int(su.sizes[g]), int(su.sizes[h]), n_perm))
-                for (g, h), (lines, genes) in zip(pairs, blocks) if genes]
-        if not cols:
-            return
-        p_adj = _bh(np.concatenate([c.p_val for _a, _b, c in cols]))
-        gene_adj = _bh(np.concatenate([c.gene_p for _a, _b, c in cols]))
-        line0 = gene0 = 0
-        for a, b, c in cols:
-            n = len(c.pa)
-            adj = gene_adj[gene0:gene0 + len(c.gene_p)]
-            w.writerows(zip(c.gene, c.pa, [a] * n, [b] * n, c.pct1, c.pct2, [f"{a}_Vs_{b}"] * n, *c.usage, c.n_ge,
-                            _reprs(c.p_val), _reprs(p_adj[line0:line0 + n]), c.stat0, c.gene_ge,
-                            _reprs(c.gene_p[c.rec_of]), _reprs(adj[c.rec_of]), [n_perm] * n))
-            line0 += n
-            gene0 += len(c.gene_p)
+        _write_diff_pa_blocks(w, DIFF_PA_PAIRS_HEADER, [
+            ((names[g], names[h]), f"{names[g]}_Vs_{names[h]}",
+             _diff_pa_columns(genes, lines, int(su.sizes[g]), int(su.sizes[h]), n_perm))
+            for (g, h), (lines, genes) in zip(pairs, blocks) if genes], n_perm)
 
     wall = _perm_run(su, n_perm, device, batch, write)
     print(f"Finish {n_perm} permutations of {len(pairs)} pairs of {G} populations ({int(su.sizes.sum())} cells) for "
           f"{sum(g[1] for _l, genes in blocks for g in genes)} lines of {sum(len(genes) for _l, genes in blocks)} tested "
           "(pair, record) combinations")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- diff_pa_markers
+# For every cluster, which pA sites does it use differently from all other cells (the FindAllMarkers question): every
+# marker population tested as diff_pa tests idents_1 without idents_2, in one run.  Options, ident checks and file naming
+# are diff_pa_groups's; the markers are every cluster of the file that has a cell (at most 64), or the 1 to 64 named
+# ones in the order given, and that is the order of the file's blocks.  Marker X is exactly `diff_pa --idents_1 X` with
+# the same --seed and --n_perm.  The tested cells are every column that has a cluster, n of them, the same for every
+# marker, and the rest of X is every other tested cell, whether its cluster was named or not.  X's columns ascending
+# take the local positions 0 .. n_X - 1, all other tested columns ascending n_X .. n - 1, and permutation p gives X the
+# n_X local positions with the smallest key(p, local position): the labellings of diff_pa's masks call for (n_X, n - n_X).
+# The kept rows are a record's label rows with a read in any tested cell, the same for every marker; X tests a record
+# when two such rows or more remain and both X and its rest have reads; S and d_i go through the device function of
+# diff_pa with its slack: t, a, n_ge, gene_n_ge and the bits of gene_stat are diff_pa's.  One line per (marker, kept row
+# of a record that the marker tests), `group` = `versus` = the marker.  p_val_adj is Benjamini-Hochberg over ALL lines
+# of the file, gene_p_val_adj over all tested (marker, record) combinations: the correction across the runs of the loop.
+# The count matrix puts the markers' columns first, segment by segment, then the other tested cells; the device keeps
+# every marker's bits in that order and finds a column's local position from its rank among the tested columns
+# (include/scape_hip.h), so the counts are read, counted and compacted once for all markers.  No --strata_file.
+DIFF_PA_MARKERS_HEADER = DIFF_PA_HEADER[:2] + ["group"] + DIFF_PA_HEADER[2:]
+MAX_MARKER_RESULT_BYTES = 256 << 20   # host and device bytes of the counters of one call: more markers are taken in ranges
+
+
+def _diff_pa_markers_batch(ctx, bat, su, n_perm, chunk, blocks, times):
+    """one counted batch: the kept rows of the records that two segments or more have reads in go through every
+    marker's test, the markers in ranges of at most MAX_MARKER_RESULT_BYTES of counters; appends to blocks[g] = (lines,
+    genes) of marker g what _diff_pa_batch appends for the marker and its rest"""
+    sel = _perm_rows(ctx, bat, su.seg_off, times)
+    if sel is None:
+        return
+    recs, M, n_seg = bat.recs, len(su.sizes), len(su.seg_off) - 1
+    which, off, rows, nz, sums, rowbase = sel
+    n_rows, n_rec = len(rows), len(which)
+    t, a0 = np.zeros(n_rows, np.int64), np.zeros((n_rows, n_seg), np.int64)
+    site_ge, gene_ge = np.zeros((M, n_rows), np.int64), np.zeros((M, n_rec), np.int64)
+    stat0 = np.zeros((M, n_rec), np.float64)
+    step = int(max(1, min(M, MAX_MARKER_RESULT_BYTES // (12 * n_rows + 20 * n_rec))))
+
+    def test():
+        for k in range(0, M, step):
+            m = min(step, M - k)
+            check(ctx.lib.scape_hip_report_perm_markers(ctx.h, n_rec, ptr(off, P_i64), ptr(rows, P_i64), n_seg,
+                                                        ptr(su.seg_off, P_i32), k, m, ptr(t, P_i64), ptr(a0, P_i64),
+                                                        ptr(site_ge[k:k + m], P_i64), ptr(stat0[k:k + m]),
+                                                        ptr(gene_ge[k:k + m], P_i64)), "report_perm_markers")
+    _perm_chunks(ctx, su, n_perm, chunk, times, test)
+    t0 = timer()
+    _check_row_sums("report_perm_markers", t, a0, sums, sums)
+    rec_of = np.repeat(np.arange(n_rec), np.diff(off))
+    pa = np.array(_pa_infos(recs, which[rec_of], rows - rowbase[which[rec_of]]), dtype=object)
+    nz_all = nz.astype(np.int64).sum(axis=1)
+    T = np.add.reduceat(t, off[:-1])
+    for g, (lines, genes) in enumerate(blocks):
+        A = np.add.reduceat(sums[:, g], off[:-1])
+        tested = (A > 0) & (A < T)       # every record here has two kept rows or more
+        keep = tested[rec_of]
+        if not keep.any():
+            continue
+        for r in np.nonzero(tested)[0].tolist():
+            genes.append((recs[which[r]].gene_info_str, int(off[r + 1] - off[r]), float(stat0[g, r]),
+                          int(gene_ge[g, r])))
+        lines["pa"].extend(pa[keep].tolist())
+        for key, arr in (("t", t), ("a", sums[:, g]), ("nz1", nz[:, g]), ("nz2", nz_all - nz[:, g]),
+                         ("n_ge", site_ge[g])):
+            lines[key].append(np.asarray(arr[keep], dtype=np.int64))
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
+                     seed: int = 1, device=None):
+    """diff_pa of every cluster of a cluster file (or of the clusters `idents`, in the order given) against all other
+    cells that have a cluster, from one pass over the result file; writes
+    <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_markers.csv in output_dir, one block per marker, the p-values
+    adjusted over the whole file, and returns its path"""
+    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_markers", markers=True)
+    names = su.names
+    blocks = [({k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}, []) for _ in names]
+
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_markers_batch(ctx, bat, su, n_perm, chunk, blocks, times)
+
+    def write(w):
+        _write_diff_pa_blocks(w, DIFF_PA_MARKERS_HEADER, [
+            ((name,), name, _diff_pa_columns(genes, lines, int(n_g), su.n - int(n_g), n_perm))
+            for name, n_g, (lines, genes) in zip(names, su.sizes, blocks) if genes], n_perm)
+
+    wall = _perm_run(su, n_perm, device, batch, write)
+    print(f"Finish {n_perm} permutations of {len(names)} markers among {su.n} cells for "
+          f"{sum(g[1] for _l, genes in blocks for g in genes)} lines of {sum(len(genes) for _l, genes in blocks)} tested "
+          "(marker, record) combinations")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -1698,8 +1830,10 @@ def _perm_options(f):
     return f
 
 
-def _groups_options(f):
-    """the options diff_pa_groups, diff_pa_len_groups and diff_pa_pairs share (the help of --n_perm and --seed differs)"""
+def _groups_options(f, idents_help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. '
+                                    'Default: every cluster of the cell_cluster_file, in order of first appearance.'):
+    """the options diff_pa_groups, diff_pa_len_groups, diff_pa_pairs and diff_pa_markers share (the help of --n_perm and
+    --seed differs, and diff_pa_markers has its own for --idents)"""
     for option in reversed((
             click.option('--output_dir', type=str, required=True,
                          help='Directory which was used in previous steps to save output by prepare_input and '
@@ -1711,9 +1845,7 @@ def _groups_options(f):
                          help='An csv file containing two columns in order: cell barcode index (index) and respective '
                               'group. Cells with an empty group, or not listed, are left out. Its name will be '
                               'included in the file name of the final result.'),
-            click.option('--idents', type=str, multiple=True,
-                         help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. '
-                              'Default: every cluster of the cell_cluster_file, in order of first appearance.'))):
+            click.option('--idents', type=str, multiple=True, help=idents_help))):
         f = option(f)
     return f
 
@@ -1778,3 +1910,23 @@ def diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, id
     """Every pair of the cell populations of a cluster file tested as diff_pa tests two, in one run over the result
     file: the post-hoc tests behind diff_pa_groups, with the p-values adjusted over all pairs (Benjamini-Hochberg)."""
     _diff_pa_pairs(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
+
+
+def _markers_options(f):
+    return _groups_options(f, 'A cluster to test against all other cells that have a cluster, whether named or not; give '
+                              'the option once per cluster (1 to 64), the order is kept. Default: every cluster of the '
+                              'cell_cluster_file (at most 64), in order of first appearance.')
+
+
+@click.command(name="diff_pa_markers")
+@_markers_options
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels per marker; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives every marker the relabellings of '
+                   'diff_pa on that cluster against the rest.')
+def diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents, n_perm: int, seed: int):
+    """Every cell population of a cluster file (or each of the 1 to 64 named with --idents) tested against all other
+    cells that have a cluster, as diff_pa tests one cluster against the rest, in one run over the result file: the
+    markers of every cluster, with the p-values adjusted over all of them (Benjamini-Hochberg)."""
+    _diff_pa_markers(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
