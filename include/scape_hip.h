@@ -408,6 +408,48 @@ int scape_hip_report_perm_markers(scape_hip_ctx *ctx, int32_t n_rec, const int64
                                   int32_t n_seg, const int32_t *seg_off, int32_t marker_first, int32_t marker_count,
                                   int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                   int64_t *gene_n_ge_out);
+/* diff_pa_trend: the test of pA usage ALONG an integer score of the cells, on the keys of scape_hip_report_perm_masks.
+   (ABI 4 gains the three entry points below; nothing that was there changes.)  The tested columns are the first n
+   columns of the count matrix, position j = column j, 2 <= n < 2^24; q[j] is the observed score of position j, 0 <= q[j]
+   <= 32,768.  Permutation 0 is the observed assignment.  Permutation p >= 1 ranks the positions by the unchanged key(p, j)
+   - rho_p(j) = #{i : key(p, i) < key(p, j)}, a bijection because keys are distinct - and position j receives the score
+     z_p(j) = q[rho_p(j)].
+   When q[j] is the group index of column segments (non-decreasing in j), z_p(j) is the byte that
+   scape_hip_report_perm_labels writes for the same sizes and seed.  The call builds the scores of permutations
+   p_first .. p_first + p_count - 1 on the device, a halfword per (position, permutation) laid out [position][permutation],
+   by ranking EVERY key: per permutation the positions are sorted into buckets of the keys' leading bits (2^10 .. 2^14
+   counters in LDS, chosen from n; n int32 of scratch per permutation of the call) and a position's rank is its bucket's
+   start plus the number of the bucket's members with a smaller key, a count that does not depend on the order in which
+   the members arrived.  6 n bytes per permutation in all.  The scores replace those of an earlier call and stay, with q,
+   until scape_hip_report_free.  Checked before anything is queued: n, every q[j], p_first >= 1, p_count >= 1. */
+int scape_hip_report_perm_scores(scape_hip_ctx *ctx, int32_t n, const uint16_t *q, int64_t p_first, int32_t p_count,
+                                 uint64_t seed);
+/* The n scores of permutation p_first + p (0 <= p < p_count) of the last scores call: scores_out[j] = z(p_first + p, j). */
+int scape_hip_report_perm_scores_get(scape_hip_ctx *ctx, int32_t p, uint16_t *scores_out);
+/* The test of n_rec records of the last counts call against the permutations of the last perm_scores call; records, kept
+   rows and the ADD semantics as in scape_hip_report_perm_test.  With c_ij the count of kept row i at position j, under
+   scores z the device forms the exact integers
+     t_i = sum_j c_ij,   T = sum_i t_i < 2^31 (checked),   s_i = sum_j c_ij z(j) < 2^46,   S = sum_i s_i
+   (64-bit registers; S first, in a walk over all the record's nonzeros, then s_i row by row) and from them in f64,
+   contraction off, through the pair of device functions of scape_hip_report_perm_len_groups for the observed scores and
+   every permutation, with m = (double)S / (double)T formed once per labelling,
+     D   = sum_i t_i (s_i / t_i - m)^2                    (rows in order)
+     d_i = s_i / t_i - (S - s_i) / (T - t_i).
+   D is the between-site sum of squares of the score over the record's reads (as a rational sum s_i^2 / t_i - S^2 / T),
+   d_i the mean score of site i's reads against that of the record's other reads.  t_out[i], s0_out[i] = s_i(0) and
+   sq0_out[i] = sum_j c_ij q_j^2 (below 2^61) per kept row, d0_out[i] = d_i(0), stat0_out[r] = D(0).  The call ADDS to
+   site_n_ge_out[i] the number of its permutations with |d_i(p)| >= |d_i(0)| - 2^-40 qspan (two-sided; qspan = max q of the
+   scores call) and to gene_n_ge_out[r] those with D(p) >= D(0) - 2^-40 T qspan^2; the caller zeroes both before the
+   first chunk of permutations.
+   Rounding (u = 2^-53): the analysis of scape_hip_report_perm_len_groups with the kept rows in the place of the groups,
+     |D - exact| <= (R + 8) u T qspan^2,     |d_i - exact| <= 3 u qspan     for a record of R rows.
+   Observed value, permuted value and the threshold's own subtraction are together off by at most (2 R + 17) u T qspan^2,
+   which stays below the band of 2^-40 = 8,192 u for R <= 4,000: a record with more kept rows is refused ("record <r>:
+   ..."), which leaves 175 u to spare; then a labelling whose exact statistic reaches the observed one is always counted,
+   one more than twice the band below it never (derivation: csrc/perm.inc, section "diff_pa_trend").  No LDS. */
+int scape_hip_report_perm_trend(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                int64_t *t_out, int64_t *s0_out, int64_t *sq0_out, int64_t *site_n_ge_out,
+                                double *d0_out, double *stat0_out, int64_t *gene_n_ge_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

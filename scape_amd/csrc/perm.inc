@@ -1,6 +1,6 @@
 // perm.inc - the permutation tests on merge_pa's count matrix: diff_pa and diff_pa_len (freely or within strata),
-// diff_pa_groups, diff_pa_len_groups, diff_pa_pairs and diff_pa_markers (included by scape_hip.hip after report.inc, whose
-// ReportState, block helpers and k_rep_scan it uses).
+// diff_pa_groups, diff_pa_len_groups, diff_pa_pairs, diff_pa_markers and diff_pa_trend (included by scape_hip.hip after
+// report.inc, whose ReportState, block helpers and k_rep_scan it uses).
 //
 // A test is two calls.  The first builds the labellings of a chunk of permutations, in exact integers:
 //   rep_select_key  the one radix select of the file: the key of a given rank among the hashed 64-bit keys of a set of
@@ -35,6 +35,11 @@
 //                   diff_pa_markers: the membership bits of every (marker population, permutation) in the order of the
 //                   count matrix's columns, each marker's own local positions found by a search in its ranks, and
 //                   diff_pa's test of every marker against all other tested cells from the one compaction
+//   k_rep_perm_scores / k_rep_trend_obs / k_rep_perm_trend
+//                   diff_pa_trend: the rank of EVERY key of a permutation by LDS buckets, so that position j gets the
+//                   score q[rank of key(p, j)] as a halfword; the observed sums per kept row; and the test of the
+//                   between-site sum of squares of the score and of every site against the record's other reads, the
+//                   sums in registers
 // On the host rep_perm_classes / rep_perm_launch_classes launch the two-population test per LDS class of records, and
 // the exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
 // stay on the host (scape_amd/report.py).
@@ -586,14 +591,15 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_groups_obs(const int64_t *_
     }
 }
 
-// the walk of the G-way tests: add(group, count) for every nonzero nz[k0 .. k1), the group under this lane's labelling
-// (lb = the lane's byte of position 0, the positions pstride bytes apart).  The nonzeros are wave-uniform.  Four at a
-// time: their label bytes are loaded before the first addition waits for one.  add() adds into the lane's own column of
-// LDS with atomics whose results are not used - one ds_add without a return value in place of a read, an add and a
-// write that would wait for each other; no other lane touches the address
-template <typename Add>
+// the walk of the G-way tests and of the trend test: add(group, count) for every nonzero nz[k0 .. k1), the group under
+// this lane's labelling (lb = the lane's element of position 0, the positions pstride elements apart: a byte per group
+// label, a halfword per score of diff_pa_trend).  The nonzeros are wave-uniform.  Four at a time: their labels are
+// loaded before the first addition waits for one.  The G-way add() adds into the lane's own column of LDS with atomics
+// whose results are not used - one ds_add without a return value in place of a read, an add and a write that would
+// wait for each other; no other lane touches the address
+template <typename Label, typename Add>
 __device__ __forceinline__ void rep_groups_walk(const uint2 *__restrict__ nz, int64_t k0, int64_t k1,
-                                                const uint8_t *__restrict__ lb, int64_t pstride, Add add) {
+                                                const Label *__restrict__ lb, int64_t pstride, Add add) {
     int64_t k = k0;
     for (; k + 4 <= k1; k += 4) {
         int c[4], g[4];
@@ -1062,6 +1068,205 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_markers(
     const unsigned long long b = __ballot(valid && S >= S0 * REP_PERM_SLACK);
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[out_r], __popcll(b));
     if (tile == 0 && threadIdx.x == 0) stat0[out_r] = S0;
+}
+
+// ---- diff_pa_trend: pA usage along a per-cell score ---------------------------------------------------------------------
+// The contract extends the G-way one.  The tested columns are the first n columns of the count matrix, position j =
+// column j, 2 <= n < 2^24; q[0 .. n) are the observed integer scores of the positions, 0 <= q <= 32,768.  Permutation
+// p >= 1 ranks the positions by the unchanged key(p, j): rho_p(j) = #{i : key(p, i) < key(p, j)} is a bijection, because
+// keys are distinct, and position j receives the score z_p(j) = q[rho_p(j)].  When q[j] is the observed group index
+// (non-decreasing in j), z_p(j) is byte for byte the label that k_rep_perm_labels writes.
+#define REP_SCORE_MAX 32768
+#define REP_SCORE_MIN_BUCKETS 1024     // a wave scans its quarter of the buckets in tiles of 64 x 4
+#define REP_SCORE_MAX_BUCKETS 16384    // 64 KiB of LDS counters
+#define REP_TREND_MAX_ROWS 4000
+
+// one workgroup per permutation p_first + blockIdx.x: the rank of EVERY key, by buckets of the keys' top `bits` bits (B =
+// 2^bits counters in LDS, chosen by the host: the smallest power of two that reaches n, within REP_SCORE_MIN_BUCKETS ..
+// REP_SCORE_MAX_BUCKETS; the top 40 bits of a key are hash bits, so a bucket expects n / B positions).  Four passes over
+// the n positions, the keys recomputed in every pass as rep_select_key does:
+//   1  cnt[bucket of key(j)] += 1 (LDS atomics whose results are not used);
+//   2  the exclusive scan of cnt in place: wave w adds up its quarter of the buckets, and behind a barrier scans it in
+//      tiles of 256 buckets (an int4 per lane, the carry in a register) from the sum of the quarters before it;
+//   3  slot = cnt[bucket]++ (a returning LDS atomic), members[slot] = j: every bucket's positions lie in its own slice
+//      [start, end) of the permutation's n-int32 scratch slice, and behind the pass cnt[b] = end of bucket b = start of
+//      bucket b + 1, so one array serves;
+//   4  behind a barrier, rank(j) = start + #{members m of the bucket of j : key(m) < key(j)}, and the halfword
+//      scores[j * p_count + blockIdx.x] = q[rank(j)]: the layout of the label bytes, lanes that own neighbouring
+//      permutations read neighbouring halfwords.
+// The order in which pass 3's atomics arrive decides where in its slice a member lies and nothing else: pass 4 reads the
+// whole slice and COUNTS, and a count does not depend on the order of what is counted, so the ranks and the scores are
+// the same in every run.  The barriers: cnt is zeroed, counted, scanned and filled behind one barrier each; the barrier
+// between passes 3 and 4 also orders the workgroup's own global writes to `members` before its reads (a workgroup-scope
+// release and acquire, which is what __syncthreads is), and no other workgroup touches the slice.  Every slot is below n
+// (the counts add up to n) and so is every rank.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_scores(int32_t n, int32_t bits, const uint16_t *__restrict__ q,
+                                                                 unsigned long long p_first, int32_t p_count,
+                                                                 unsigned long long seed, int32_t *members_all,
+                                                                 uint16_t *__restrict__ scores) {
+    extern __shared__ int32_t rep_cnt[];     // the B counters, then the waves' sums of the scan
+    const unsigned long long base = rep_mix(seed + REP_PERM_G * (p_first + blockIdx.x));
+    int32_t *members = members_all + (int64_t)blockIdx.x * n;
+    const int n_buckets = 1 << bits, shift = 64 - bits;
+    int32_t *wtot = rep_cnt + n_buckets;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int4 *cnt4 = reinterpret_cast<int4 *>(rep_cnt);
+    for (int i = threadIdx.x; i < n_buckets / 4; i += REP_THREADS) cnt4[i] = make_int4(0, 0, 0, 0);
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += REP_THREADS) atomicAdd(&rep_cnt[rep_perm_key(base, j) >> shift], 1);
+    __syncthreads();
+    const int quarter4 = n_buckets / (4 * REP_WAVES);      // int4s per wave: a multiple of 64
+    int4 *mine = cnt4 + wave * quarter4;
+    int sum = 0;
+    for (int i = lane; i < quarter4; i += 64) {
+        const int4 h = mine[i];
+        sum += h.x + h.y + h.z + h.w;
+    }
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0) wtot[wave] = sum;
+    __syncthreads();
+    int run = 0;
+    for (int w = 0; w < wave; ++w) run += wtot[w];
+    for (int i = lane; i < quarter4; i += 64) {
+        const int4 h = mine[i];
+        const int tile = h.x + h.y + h.z + h.w;
+        int incl = tile;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += y;
+        }
+        const int ex = run + incl - tile;
+        mine[i] = make_int4(ex, ex + h.x, ex + h.x + h.y, ex + h.x + h.y + h.z);
+        run += __shfl(incl, 63, 64);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += REP_THREADS) members[atomicAdd(&rep_cnt[rep_perm_key(base, j) >> shift], 1)] = j;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += REP_THREADS) {
+        const unsigned long long k = rep_perm_key(base, j);
+        const int b = (int)(k >> shift);
+        const int start = b ? rep_cnt[b - 1] : 0, end = rep_cnt[b];
+        int rank = start;
+        for (int m = start; m < end; ++m) rank += rep_perm_key(base, members[m]) < k;
+        scores[(int64_t)j * p_count + blockIdx.x] = q[rank];
+    }
+}
+
+// one permutation's column of the scores, gathered for scape_hip_report_perm_scores_get: a strided copy of n halfwords
+// to the host takes a transfer per halfword
+__global__ __launch_bounds__(REP_THREADS) void k_rep_scores_column(const uint16_t *__restrict__ scores, int32_t n,
+                                                                   int32_t p_count, int32_t p, uint16_t *__restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * REP_THREADS + threadIdx.x;
+    if (j < n) out[j] = scores[j * p_count + p];
+}
+
+// The statistic, per record with R kept rows, c_ij the count of row i at position j, under scores z:
+//   t_i = sum_j c_ij (fixed),  T = sum_i t_i < 2^31,  s_i = sum_j c_ij z(j) (64-bit, exact, < 2^46),  S = sum_i s_i
+//   D   = sum_i t_i (s_i / t_i - S / T)^2     (rows in order)  the between-site sum of squares of the score
+//   d_i = s_i / t_i - (S - s_i) / (T - t_i)                    the mean score of site i's reads against the other reads'
+// This is diff_pa_len_groups's arithmetic with the roles exchanged - site for group, score for position - and both the
+// observed and the permuted scores go through rep_len_groups_term and rep_len_groups_delta (contraction off, equal
+// integers give equal doubles), with m = (double)S / (double)T formed per labelling, since S now depends on it.  Their
+// rounding analysis carries over with G -> R and qspan = max q <= 2^15: every integer converted is below 2^53,
+//   |D - exact| <= (R + 8) u T qspan^2,     |d_i - exact| <= 3 u qspan     (u = 2^-53).
+// A permutation is counted when D(p) >= D(0) - tolD, tolD = 2^-40 T qspan^2, and when |d_i(p)| >= |d_i(0)| - told, told =
+// 2^-40 qspan.  A labelling whose exact statistic reaches the observed one is counted whatever the rounding, and one more
+// than twice the band below it never is, as long as 2 eD + u T qspan^2 <= tolD: (2 R + 17) u <= 2^-40 = 8,192 u.  Here R
+// is not bounded by 64 as G is, so a record may own at most REP_TREND_MAX_ROWS = 4,000 kept rows (checked by the entry
+// point): 8,017 u, 175 u to spare.  d_i needs 7 u.  tolD = (double)(T qspan^2) 2^-40 rounds the integer (below 2^61) by
+// at most u of itself, 2^-53 of the band.
+
+// one workgroup per record: the observed scores q.  Wave w takes rows w, w + REP_WAVES, ...: s0[i] = s_i(0) and sq0[i] =
+// sum_j c_ij q_j^2 (below 2^61; the host's eta2 needs their sum).  Then qt[2 r], qt[2 r + 1] = S(0), T; tol[2 r], tol[2
+// r + 1] = tolD, told; d0[i] = d_i(0) by thread i, i + 256, ...; stat0[r] = D(0), the rows' terms added in order by one
+// thread, as a lane of k_rep_perm_trend adds them
+__global__ __launch_bounds__(REP_THREADS) void k_rep_trend_obs(const int64_t *__restrict__ roff,
+                                                               const int64_t *__restrict__ noff,
+                                                               const uint2 *__restrict__ nz,
+                                                               const int64_t *__restrict__ t,
+                                                               const uint16_t *__restrict__ q, int32_t qspan,
+                                                               long long *s0, long long *__restrict__ sq0,
+                                                               long long *__restrict__ qt, double *__restrict__ tol,
+                                                               double *__restrict__ d0, double *__restrict__ stat0) {
+#pragma clang fp contract(off)
+    __shared__ long long ST[2];
+    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    for (int64_t i = row0 + wave; i < row1; i += REP_WAVES) {
+        long long s = 0, sq = 0;
+        for (int64_t k = noff[i] + lane; k < noff[i + 1]; k += 64) {
+            const uint2 e = nz[k];
+            const long long v = (long long)e.y * q[e.x];
+            s += v;
+            sq += v * q[e.x];
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            s += __shfl_xor(s, o, 64);
+            sq += __shfl_xor(sq, o, 64);
+        }
+        if (lane == 0) {
+            s0[i] = s;
+            sq0[i] = sq;
+        }
+    }
+    __syncthreads();                         // the record's s0 are stored (this workgroup wrote them)
+    if (threadIdx.x == 0) {
+        long long S = 0, T = 0;
+        for (int64_t i = row0; i < row1; ++i) {
+            S += s0[i];
+            T += t[i];
+        }
+        ST[0] = S;
+        ST[1] = T;
+    }
+    __syncthreads();
+    const long long S = ST[0], T = ST[1];
+    for (int64_t i = row0 + threadIdx.x; i < row1; i += REP_THREADS) d0[i] = rep_len_groups_delta(s0[i], t[i], S, T);
+    if (threadIdx.x == 0) {
+        const double m = (double)S / (double)T;
+        double D = 0.0;
+        for (int64_t i = row0; i < row1; ++i) D = D + rep_len_groups_term(s0[i], t[i], m);
+        qt[2 * r] = S;
+        qt[2 * r + 1] = T;
+        tol[2 * r] = ldexp((double)(T * qspan * qspan), -40);
+        tol[2 * r + 1] = ldexp((double)qspan, -40);
+        stat0[r] = D;
+    }
+}
+
+// workgroup = (record blockIdx.x / n_tiles, tile of 256 permutations), one lane per permutation; the nonzeros are
+// wave-uniform, the lane reads its own permutation's halfword of the nonzero's position (neighbouring lanes,
+// neighbouring halfwords).  A first walk over all the record's nonzeros forms S(p) in a 64-bit register; a second walk,
+// row by row, forms s_i(p) in a register and adds the row's term: no LDS, so any number of rows in one launch and no
+// classes of records.  Exceedances are counted per wave (ballot) and added with one atomic per wave and counter.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_trend(
+    const uint16_t *__restrict__ scores, int32_t p_count, int32_t n_tiles, const int64_t *__restrict__ roff,
+    const int64_t *__restrict__ noff, const uint2 *__restrict__ nz, const int64_t *__restrict__ t,
+    const long long *__restrict__ qt, const double *__restrict__ tol, const double *__restrict__ d0,
+    const double *__restrict__ stat0, int32_t *__restrict__ site_ge, int32_t *__restrict__ gene_ge) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const uint16_t *sc = scores + (valid ? p : p_count - 1);
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    const long long T = qt[2 * r + 1];
+    const double tolD = tol[2 * r], told = tol[2 * r + 1];
+    long long S = 0;
+    rep_groups_walk(nz, noff[row0], noff[row1], sc, p_count, [&](int z, int c) { S += (long long)z * c; });
+    const double m = (double)S / (double)T;
+    double D = 0.0;
+    for (int64_t i = row0; i < row1; ++i) {
+        long long s = 0;
+        rep_groups_walk(nz, noff[i], noff[i + 1], sc, p_count, [&](int z, int c) { s += (long long)z * c; });
+        const long long ti = t[i];
+        D = D + rep_len_groups_term(s, ti, m);
+        const double d = rep_len_groups_delta(s, ti, S, T);
+        const unsigned long long b = __ballot(valid && fabs(d) >= fabs(d0[i]) - told);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(&site_ge[i], __popcll(b));
+    }
+    const unsigned long long b = __ballot(valid && D >= stat0[r] - tolD);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[r], __popcll(b));
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -1711,6 +1916,95 @@ int scape_hip_report_perm_markers(scape_hip_ctx *c, int32_t n_rec, const int64_t
                                n_rows, n_rec, cap, s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(),
                                s->p_stat0.as<double>());
         });
+    });
+}
+
+int scape_hip_report_perm_scores(scape_hip_ctx *c, int32_t n, const uint16_t *q, int64_t p_first, int32_t p_count,
+                                 uint64_t seed) {
+    CTX_ENTER(c);
+    if (!q) return fail("bad argument");
+    if (n < 2) return fail("the scored cells must number 2 or more");
+    if (rep_perm_chunk_ok(n, "the scored cells must number", p_first, p_count)) return 1;
+    int32_t qspan = 0;
+    for (int32_t j = 0; j < n; ++j) {
+        if (q[j] > REP_SCORE_MAX) return fail("position " + std::to_string(j) + ": scores must lie in 0 .. 32,768");
+        qspan = std::max<int32_t>(qspan, q[j]);
+    }
+    ReportState *s = report_state(c);
+    s->t_count = 0;
+    int32_t bits = 0;                        // B = 2^bits: the smallest power of two that reaches n, within the limits
+    while ((1 << bits) < REP_SCORE_MIN_BUCKETS || ((1 << bits) < n && (1 << bits) < REP_SCORE_MAX_BUCKETS)) ++bits;
+    // a halfword per (position, permutation), and one scratch slice of n int32 per permutation of the chunk
+    if (s->t_scores.ensure((int64_t)p_count * n * 2) || s->t_members.ensure((int64_t)p_count * n * 4) ||
+        s->t_q.ensure((int64_t)n * 2))
+        return 1;
+    HIPCHK(hipMemcpyAsync(s->t_q.p, q, (int64_t)n * 2, hipMemcpyHostToDevice, c->stream));
+    // the counters and, behind them, the four waves' sums of the scan: 16 bytes above 64 KiB at the most buckets
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_scores),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, REP_SCORE_MAX_BUCKETS * 4 + REP_WAVES * 4));
+    hipLaunchKernelGGL(k_rep_perm_scores, dim3(p_count), dim3(REP_THREADS), ((size_t)4 << bits) + REP_WAVES * 4, c->stream, n, bits,
+                       s->t_q.as<uint16_t>(), (unsigned long long)p_first, p_count, (unsigned long long)seed,
+                       s->t_members.as<int32_t>(), s->t_scores.as<uint16_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    s->t_n = n;
+    s->t_qspan = qspan;
+    s->t_count = p_count;
+    return 0;
+}
+
+int scape_hip_report_perm_scores_get(scape_hip_ctx *c, int32_t p, uint16_t *scores_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (!s || !s->t_count) return fail("scape_hip_report_perm_scores has not been called");
+    if (!scores_out) return fail("bad argument");
+    if (p < 0 || p >= s->t_count) return fail("p must name a permutation of the last scores call");
+    // the builder's scratch (4 n bytes per permutation) is idle between two scores calls: the column is gathered there
+    hipLaunchKernelGGL(k_rep_scores_column, dim3((uint32_t)((s->t_n + REP_THREADS - 1) / REP_THREADS)), dim3(REP_THREADS),
+                       0, c->stream, s->t_scores.as<uint16_t>(), s->t_n, s->t_count, p, s->t_members.as<uint16_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(scores_out, s->t_members.p, (int64_t)s->t_n * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int scape_hip_report_perm_trend(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                int64_t *t_out, int64_t *s0_out, int64_t *sq0_out, int64_t *site_n_ge_out,
+                                double *d0_out, double *stat0_out, int64_t *gene_n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (rep_perm_ready(s, s ? s->t_count : 0, "scape_hip_report_perm_scores")) return 1;
+    if (n_rec <= 0 || !rec_row_off || !rows) return fail("bad argument");
+    const int64_t n_all = rec_row_off[n_rec];
+    if (n_all <= 0 || n_all > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
+    // one segment [0, n): the row's sum over it restates t, and lands in a buffer of the call's own
+    std::vector<int64_t> a0((size_t)n_all);
+    int64_t n_rows = 0;
+    int32_t n_tiles = 0;
+    if (rep_perm_prepare(c, s->t_n, s->t_count, "scores", s->t_n, 0, nullptr, n_rec, rec_row_off, rows, t_out, a0.data(),
+                         s0_out && sq0_out && site_n_ge_out && d0_out && stat0_out && gene_n_ge_out, REP_TREND_MAX_ROWS,
+                         nullptr, nullptr, nullptr, nullptr, &n_rows, &n_tiles))
+        return 1;
+    if (s->t_s0.ensure(n_rows * 8) || s->t_sq0.ensure(n_rows * 8) || s->v_qt.ensure((int64_t)n_rec * 16) ||
+        s->v_tol.ensure((int64_t)n_rec * 16) || s->v_d0.ensure(n_rows * 8))
+        return 1;
+    return rep_perm_count(c, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
+        hipLaunchKernelGGL(k_rep_trend_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream,
+                           s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(),
+                           s->t_q.as<uint16_t>(), s->t_qspan, s->t_s0.as<long long>(), s->t_sq0.as<long long>(),
+                           s->v_qt.as<long long>(), s->v_tol.as<double>(), s->v_d0.as<double>(),
+                           s->p_stat0.as<double>());
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_rep_perm_trend, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), 0,
+                           c->stream, s->t_scores.as<uint16_t>(), s->t_count, n_tiles, s->p_roff.as<int64_t>(),
+                           s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->v_qt.as<long long>(),
+                           s->v_tol.as<double>(), s->v_d0.as<double>(), s->p_stat0.as<double>(),
+                           s->p_site.as<int32_t>(), s->p_gene.as<int32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(s0_out, s->t_s0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(sq0_out, s->t_sq0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(d0_out, s->v_d0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+        return 0;
     });
 }
 

@@ -699,13 +699,13 @@ def _perm_masks(ctx, su, p_first, p_count, times):
     times["render"] += timer() - t0
 
 
-def _perm_rows(ctx, bat, seg_off, times, each_kept=None):
+def _perm_rows(ctx, bat, seg_off, times, each_kept=None, min_pops=2):
     """the tested records of one counted batch and their kept rows: (batch indices of the tested records, row offsets
     per tested record, count rows, cells with a count above 0 per row and population, sums per row and population,
     first count row of every record of the batch), or None when no record of the batch is tested: a record is tested
-    when it has two kept rows or more and two populations or more (of the len(seg_off) - 1) with reads.  each_kept(r,
-    labels), when given, is called for every record of K >= 2 that has a kept row, tested or not, with the labels of
-    its kept rows"""
+    when it has two kept rows or more and min_pops populations or more (of the len(seg_off) - 1) with reads; diff_pa_trend,
+    whose scored cells are one segment, asks for one.  each_kept(r, labels), when given, is called for every record of
+    K >= 2 that has a kept row, tested or not, with the labels of its kept rows"""
     recs, K = bat.recs, bat.K
     rowbase, cand, owner, label = _kept_rows(bat)
     if not len(cand):
@@ -727,7 +727,7 @@ def _perm_rows(ctx, bat, seg_off, times, each_kept=None):
         for r in np.nonzero((n_kept > 0) & (K >= 2))[0].tolist():
             each_kept(r, labs[cut[r] - n_kept[r]:cut[r]])
     with_reads = sum(np.bincount(owner, weights=sums[:, g], minlength=len(recs)) > 0 for g in range(n_seg))
-    tested = (n_kept >= 2) & (with_reads >= 2)           # two populations: both have reads
+    tested = (n_kept >= 2) & (with_reads >= min_pops)    # two populations: both have reads
     keep &= tested[owner]
     which = np.nonzero(tested)[0]
     times["finish"] += timer() - t0
@@ -1625,6 +1625,185 @@ def _diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: s
     return su.outpath
 
 
+# ---------------------------------------------------------------- diff_pa_trend
+# Does pA usage shift ALONG a per-cell score (pseudotime, a differentiation, cell-cycle or activation score)?  The score
+# file has the cluster file's format; its first other column is parsed with float(), and a cell with an empty field, NA
+# or nan has no score and is left out (the pseudotime of another lineage).  The tested columns are the scored cells,
+# ascending, in front of the count matrix; kept rows are the labels < K with a read in a scored cell, a record is tested
+# when it has two or more.  --rank replaces the score x_j by r_j = #{x < x_j} + #{x <= x_j} = 2 x mid-rank - 1.  The
+# scores are made integers as diff_pa_len_groups makes positions, at 15 bits: w_j = x_j - min x, frexp(span) = (m, e),
+# s = 15 - e, q_j = rint(ldexp(w_j, s)), so 2^14 <= qspan = max q <= 2^15; the test is the test on the q_j, and the
+# file's score columns are in units of the quantised scores min x + q 2^-s.  Permutation p >= 1 ranks the cells by
+# diff_pa's key(p, j) and gives cell j the score z_p(j) = q[rank of key(p, j)].  Per record, with c_ij the count of kept
+# row i in cell j, t_i = sum_j c_ij, T = sum t_i, s_i = sum_j c_ij z(j), S = sum s_i:
+#     D   = sum_i t_i (s_i / t_i - S / T)^2                 the gene statistic: between-site sum of squares of the score
+#     d_i = s_i / t_i - (S - s_i) / (T - t_i)               site i's reads against the record's other reads (two-sided)
+# n_ge = #{p: |d_i(p)| >= |d_i(0)| - 2^-40 qspan}, gene_n_ge = #{p: D(p) >= D(0) - 2^-40 T qspan^2}, p = (1 + n_ge) /
+# (1 + n_perm), Benjamini-Hochberg over the file's lines for the sites and over the tested records for the genes.
+# mean_score = min x + (s_i / t_i) 2^-s, delta_score = d_i 2^-s (> 0: the site is used by cells further along), eta2 =
+# D / (sum_j C_j q_j^2 - S^2 / T), the share of the score's variance over the record's reads that lies between its sites
+# (empty when that variance is 0).  (include/scape_hip.h states the device's arithmetic and the bound that makes the
+# counts exact: at most 4,000 kept rows per record.)
+DIFF_PA_TREND_HEADER = ["gene", "pa_info", "reads", "pct", "mean_score", "delta_score", "n_ge", "p_val", "p_val_adj",
+                        "num_pa", "gene_reads", "eta2", "gene_n_ge", "gene_p_val", "gene_p_val_adj", "n_perm"]
+TREND_Q_BITS = 15                # qspan lies in 2^14 .. 2^15: a score is a halfword, s_i < 2^46 and S stay exact
+MAX_TREND_ROWS = 4000            # kept rows of a record: the rounding bound of D (include/scape_hip.h)
+
+
+def _read_scores(cell_score_file):
+    """{id: score (finite float) or None} of the rows of a score file; a repeated id keeps its last row"""
+    ids, texts = _read_clusters(cell_score_file)
+    out = {}
+    for k, (i, field) in enumerate(zip(ids.tolist(), texts)):
+        field = field.strip()
+        if field == "" or field.lower() in ("na", "nan"):
+            out[i] = None
+            continue
+        try:
+            v = float(field)
+        except ValueError:
+            raise ValueError(f"{cell_score_file}: row {k + 1} (id {i}): {field!r} is not a number") from None
+        if math.isinf(v):
+            raise ValueError(f"{cell_score_file}: row {k + 1} (id {i}): the score {field!r} is not finite")
+        out[i] = None if math.isnan(v) else v
+    return out
+
+
+def _rank_scores(x):
+    """r_j = #{x < x_j} + #{x <= x_j} (f64 holding integers): twice the mid-rank minus one, so ties share a value"""
+    srt = np.sort(x)
+    return (np.searchsorted(srt, x, side="left") + np.searchsorted(srt, x, side="right")).astype(np.float64)
+
+
+def _quantise_scores(x):
+    """(q_j (uint16), s) of the scores x (finite f64, span > 0): q_j = rint((x_j - min x) 2^s), half to even"""
+    w = x - x.min()
+    _m, e = math.frexp(float(x.max() - x.min()))
+    return np.rint(np.ldexp(w, TREND_Q_BITS - e)).astype(np.uint16), TREND_Q_BITS - e
+
+
+def _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed):
+    """what diff_pa_trend does before the device is opened: the argument and prerequisite checks, the scored cells and
+    their integer scores, the id -> column table that puts the scored columns first, ascending, and the output path
+    <score file stem>.<gene|utr>[.rank].diff_pa_trend.csv"""
+    _check_perm_args(n_perm, seed)
+    inp = _read_inputs(output_dir, res_pkl_file)
+    if not os.path.exists(cell_score_file):
+        raise Exception("Given cell_score_file file does not exists")
+    score = _read_scores(cell_score_file)
+    col_score = [score.get(i) for i in inp.col_ids.tolist()]
+    cols = np.array([j for j, v in enumerate(col_score) if v is not None], dtype=np.int64)
+    n = len(cols)
+    if n < 2:
+        raise ValueError(f"{n} cells of barcode_index.csv have a score in {cell_score_file}: diff_pa_trend takes 2 or more")
+    if n >= MAX_PERM_CELLS:
+        raise ValueError(f"{n} tested cells: diff_pa_trend takes fewer than {MAX_PERM_CELLS}")
+    x = np.array([col_score[j] for j in cols.tolist()], dtype=np.float64)
+    if not float(x.max() - x.min()) > 0:
+        raise ValueError(f"every scored cell of {cell_score_file} has the score {x[0]!r}: there is no trend to test")
+    if not np.isfinite(x.max() - x.min()):
+        raise ValueError(f"the scores of {cell_score_file} span more than a float holds")
+    if rank:
+        x = _rank_scores(x)
+    q, shift = _quantise_scores(x)
+    _table, slot, seg_off, _seg_pop = _samples([("scored", cols)], 1, inp.n_cols)
+    outpath = _out_stem(output_dir, res_pkl_file, cell_score_file, None, None) + (".rank" if rank else "") + \
+        ".diff_pa_trend.csv"
+
+    def labellings(ctx, p_first, p_count):
+        check(ctx.lib.scape_hip_report_perm_scores(ctx.h, n, ptr(q, _lib.P_u16), p_first, p_count, seed),
+              "report_perm_scores")
+    # per permutation the device holds a halfword per cell, and the cells sorted into key buckets (an int32 each)
+    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, n=n, q=q, shift=shift,
+                           lo=float(x.min()), outpath=outpath, labellings=labellings, perm_bytes=6 * n,
+                           idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
+
+
+def _diff_pa_trend_batch(ctx, bat, su, n_perm, chunk, lines, genes, times):
+    """one counted batch: the kept rows of its tested records go through the trend test; appends the per-line integers
+    to `lines` and (gene_info_str, lines, T, S, eta2, gene_n_ge) per tested record to `genes`"""
+    sel = _perm_rows(ctx, bat, su.seg_off, times, min_pops=1)
+    if sel is None:
+        return
+    recs = bat.recs
+    which, off, rows, nz, sums, rowbase = sel
+    for g, r in enumerate(which.tolist()):
+        if int(off[g + 1] - off[g]) > MAX_TREND_ROWS:
+            raise ValueError(f"{recs[r].gene_info_str}: {int(off[g + 1] - off[g])} pA sites with reads, more than "
+                             f"{MAX_TREND_ROWS}: beyond the rounding bound of the statistic")
+    t, s0, sq0 = (np.zeros(len(rows), np.int64) for _ in range(3))
+    site_ge, gene_ge = np.zeros(len(rows), np.int64), np.zeros(len(which), np.int64)
+    d0, stat0 = np.zeros(len(rows), np.float64), np.zeros(len(which), np.float64)
+    _perm_chunks(ctx, su, n_perm, chunk, times, lambda: check(
+        ctx.lib.scape_hip_report_perm_trend(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(t, P_i64),
+                                            ptr(s0, P_i64), ptr(sq0, P_i64), ptr(site_ge, P_i64), ptr(d0), ptr(stat0),
+                                            ptr(gene_ge, P_i64)), "report_perm_trend"))
+    t0 = timer()
+    if not np.array_equal(t, sums[:, 0]):
+        raise _lib.ScapeHipError("report_perm_trend: row sums differ from report_group_sums")
+    qspan = int(su.q.max())
+    for g, r in enumerate(which.tolist()):
+        a, b = int(off[g]), int(off[g + 1])
+        ti, si = t[a:b].tolist(), s0[a:b].tolist()
+        T, S = sum(ti), sum(si)
+        _check_reads(recs[r], T)
+        # the statistics of the observed scores, exactly, in Python ints on the q_j
+        D = sum(Fraction(s * s, tt) for s, tt in zip(si, ti)) - Fraction(S * S, T)
+        if not abs(Fraction(float(stat0[g])) - D) <= Fraction(T * qspan * qspan, 1 << 40):
+            raise _lib.ScapeHipError(f"report_perm_trend: {recs[r].gene_info_str}: the device's statistic {stat0[g]!r} "
+                                     f"differs from {float(D)!r}")
+        for k, (s, tt) in enumerate(zip(si, ti)):
+            if not abs(Fraction(float(d0[a + k])) - Fraction(s * T - S * tt, tt * (T - tt))) <= Fraction(qspan, 1 << 40):
+                raise _lib.ScapeHipError(f"report_perm_trend: {recs[r].gene_info_str}: the device's delta "
+                                         f"{d0[a + k]!r} of kept row {k} differs from the exact one")
+        ss_total = int(sq0[a:b].sum()) - Fraction(S * S, T)
+        genes.append((recs[r].gene_info_str, b - a, T, S, float(D / ss_total) if ss_total else None, int(gene_ge[g])))
+        lines["pa"].extend(_pa_info(recs[r], rows[a:b] - int(rowbase[r])))
+    for key, arr in (("t", t), ("s", s0), ("nz", nz[:, 0]), ("n_ge", site_ge)):
+        lines[key].append(np.asarray(arr, dtype=np.int64).copy())
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, rank: bool = False, n_perm: int = 9999,
+                   seed: int = 1, device=None):
+    """permutation test of pA usage along the per-cell score of a score file (its ranks with rank=True); writes <score
+    file stem>.<gene|utr>[.rank].diff_pa_trend.csv in output_dir, one line per kept row of a tested record, and
+    returns its path"""
+    su = _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed)
+    lines = {k: [] for k in ("pa", "t", "s", "nz", "n_ge")}
+    genes = []                   # (gene_info_str, lines, T, S, eta2, gene_n_ge) per tested record
+
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_trend_batch(ctx, bat, su, n_perm, chunk, lines, genes, times)
+
+    def write(w):
+        w.writerow(DIFF_PA_TREND_HEADER)
+        if not genes:
+            return
+        t, s, nz, n_ge = (np.concatenate(lines[k]) for k in ("t", "s", "nz", "n_ge"))
+        p_val = (1 + n_ge) / (1 + n_perm)
+        gene_p = (1 + np.array([g[5] for g in genes], dtype=np.int64)) / (1 + n_perm)
+        p_adj, gene_adj = _bh(p_val).tolist(), _bh(gene_p).tolist()
+        # a score of the file is min x + q 2^-s: exact rationals, each rounded once
+        lo, unit = Fraction(su.lo), Fraction(2) ** -su.shift
+        k = 0
+        for g, (gene, n_lines, T, S, eta2, gene_ge) in enumerate(genes):
+            tail = [n_lines, T, "" if eta2 is None else repr(eta2), gene_ge, repr(float(gene_p[g])), repr(gene_adj[g]),
+                    n_perm]
+            for _ in range(n_lines):
+                ti, si = int(t[k]), int(s[k])
+                w.writerow([gene, lines["pa"][k], ti, repr(float(nz[k] / su.n)), repr(float(lo + Fraction(si, ti) * unit)),
+                            repr(float(Fraction(si * T - S * ti, ti * (T - ti)) * unit)), int(n_ge[k]),
+                            repr(float(p_val[k])), repr(p_adj[k])] + tail)
+                k += 1
+
+    wall = _perm_run(su, n_perm, device, batch, write)
+    print(f"Finish {n_perm} permutations of the scores of {su.n} cells for {sum(g[1] for g in genes)} pA sites of "
+          f"{len(genes)} tested records")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
 # ---------------------------------------------------------------- cal_exp_pa_len
 def _exp_len_rows(K, alpha_arr, counts):
     """exp_pa_len (apa_core.py:1038-1052) for every row of counts [groups, K + 1] (slot K: reads with label >= K);
@@ -1930,3 +2109,26 @@ def diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     cells that have a cluster, as diff_pa tests one cluster against the rest, in one run over the result file: the
     markers of every cluster, with the p-values adjusted over all of them (Benjamini-Hochberg)."""
     _diff_pa_markers(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
+
+
+@click.command(name="diff_pa_trend")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the '
+                   'final result.')
+@click.option('--cell_score_file', type=str, required=True,
+              help='An csv file containing two columns in order: cell barcode index (index) and the score of the cell '
+                   '(pseudotime, a differentiation, cell-cycle or activation score). Cells with an empty score, NA or '
+                   'nan, or not listed, are left out. Its name will be included in the file name of the final result.')
+@click.option('--rank', is_flag=True, default=False,
+              help='Test along the ranks of the scores (ties share their mid-rank), not the scores themselves.')
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell scores; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1 (the keys are those of diff_pa).')
+def diff_pa_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, rank: bool, n_perm: int, seed: int):
+    """pA sites and genes whose pA usage shifts along a per-cell score such as pseudotime: a permutation test of the
+    cell scores on the mean score of every site's reads against the gene's other reads, and on the between-site sum of
+    squares of the score (delta_score > 0: the site is used by cells further along)."""
+    _diff_pa_trend(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed)
