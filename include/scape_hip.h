@@ -450,6 +450,30 @@ int scape_hip_report_perm_scores_get(scape_hip_ctx *ctx, int32_t p, uint16_t *sc
 int scape_hip_report_perm_trend(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                                 int64_t *t_out, int64_t *s0_out, int64_t *sq0_out, int64_t *site_n_ge_out,
                                 double *d0_out, double *stat0_out, int64_t *gene_n_ge_out);
+/* diff_pa_len_trend: the test of the pA POSITION (3'UTR length) along the scores, for n_rec records of the last counts
+   call against the permutations of the last perm_scores call; records, kept rows and the ADD semantics as in
+   scape_hip_report_perm_trend.  (ABI 4 gains this entry point; nothing that was there changes.)  x[i] is the integer
+   position of kept row i, 0 <= x[i] <= 2^22.  With c_ij the count of kept row i at position j, under scores z the device
+   forms the exact integers
+     t_i = sum_j c_ij,   T = sum_i t_i < 2^31,   Sx = sum_i t_i x_i                               (fixed)
+     s_i = sum_j c_ij z(j) < 2^46,   Sz = sum_i s_i < 2^46,   Sxz = sum_i x_i s_i < 2^63          (per labelling)
+     C   = T Sxz - Sx Sz
+   in signed 64-bit registers and, for C, as two 64 x 64 -> 128-bit products (each below 2^94) and their difference.  C
+   is T^2 times the covariance of position and score over the record's reads; T, Sx and sum_i t_i x_i^2 are the same
+   under every labelling, so |C| orders the labellings as the absolute slope of the score regressed on the position
+   does.  t_out[i], s0_out[i] = s_i(0) and sq0_out[i] = sum_j c_ij q_j^2 (below 2^61) per kept row; c0_out[2 r] and
+   c0_out[2 r + 1] = the low and the high 64 bits of the two's-complement C(0).  The call ADDS to n_ge_out[r] the number
+   of its permutations with |C(p)| >= |C(0)| (two-sided), compared as 128-bit integers: there is no rounding, no band
+   and no bound on a record's rows; the caller zeroes n_ge_out before the first chunk of permutations.
+   Checked before anything is queued: a scores call exists, the offsets and rows, every x[i].  T comes from the device,
+   so the two checks on it are made per record ("record <r>: ...") once the row sums are back - t_out is written by
+   then, and for the second the compaction of the rows is queued - and before the test's own kernels are queued: T <
+   2^31, and T max_i x_i < 2^48, which with scores of at most 2^15 keeps Sxz below 2^63 and Sx below 2^48.  No LDS, no
+   f64, no division. */
+int scape_hip_report_perm_len_trend(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                    const int32_t *x, int64_t *t_out, int64_t *s0_out, int64_t *sq0_out,
+                                    int64_t *c0_out /* [2 r] low, [2 r + 1] high 64 bits of C(0) */,
+                                    int64_t *n_ge_out /* ADDED to */);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

@@ -1,6 +1,6 @@
 // perm.inc - the permutation tests on merge_pa's count matrix: diff_pa and diff_pa_len (freely or within strata),
-// diff_pa_groups, diff_pa_len_groups, diff_pa_pairs, diff_pa_markers and diff_pa_trend (included by scape_hip.hip after
-// report.inc, whose ReportState, block helpers and k_rep_scan it uses).
+// diff_pa_groups, diff_pa_len_groups, diff_pa_pairs, diff_pa_markers, diff_pa_trend and diff_pa_len_trend (included by
+// scape_hip.hip after report.inc, whose ReportState, block helpers and k_rep_scan it uses).
 //
 // A test is two calls.  The first builds the labellings of a chunk of permutations, in exact integers:
 //   rep_select_key  the one radix select of the file: the key of a given rank among the hashed 64-bit keys of a set of
@@ -40,6 +40,9 @@
 //                   score q[rank of key(p, j)] as a halfword; the observed sums per kept row; and the test of the
 //                   between-site sum of squares of the score and of every site against the record's other reads, the
 //                   sums in registers
+//   k_rep_len_trend_obs / k_rep_perm_len_trend
+//                   diff_pa_len_trend: on the same scores, the covariance of the pA position and the score over a
+//                   record's reads as a 128-bit integer, compared exactly; one walk of the nonzeros, no f64
 // On the host rep_perm_classes / rep_perm_launch_classes launch the two-population test per LDS class of records, and
 // the exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
 // stay on the host (scape_amd/report.py).
@@ -1269,6 +1272,105 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_trend(
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[r], __popcll(b));
 }
 
+// ---- diff_pa_len_trend: 3'UTR length along a per-cell score -----------------------------------------------------------
+// The scores, their permutations and the kept rows are diff_pa_trend's; kept row i also has an integer position x_i,
+// 0 <= x_i <= 2^22 (the host quantises alpha_arr per record).  Per record, under scores z:
+//   t_i = sum_j c_ij,  T = sum_i t_i < 2^31,  Sx = sum_i t_i x_i                       (fixed)
+//   s_i = sum_j c_ij z(j) < 2^46,  Sz = sum_i s_i,  Sxz = sum_i x_i s_i                (per labelling)
+//   C   = T Sxz - Sx Sz     = T^2 x the covariance of position and score over the record's reads
+// T, Sx and sum_i t_i x_i^2 do not depend on the labelling, so |C| orders the labellings as the absolute slope of the
+// score regressed on the position does, and a permutation is counted when |C(p)| >= |C(0)|, compared as integers: no
+// f64, no band.  The ranges: the entry point checks T max x < 2^48 per record, so Sx < 2^48, and with z <= 2^15 Sz <=
+// 2^15 T < 2^46 and Sxz <= 2^15 T max x < 2^63: all of them fit signed 64-bit registers.  C is two 64 x 64 -> 128-bit
+// products, each below 2^94, and their difference, in __int128; no division anywhere.
+#define REP_LEN_TREND_MAX_TX ((long long)1 << 48)    // T max x of a record stays below it (x_i <= REP_LEN_GROUPS_MAX_Q)
+#define REP_LEN_TREND_REC 6             // per record: T, Sx, Sz(0), Sxz(0), the low and the high 64 bits of C(0)
+
+__device__ __forceinline__ unsigned __int128 rep_len_trend_abs(long long T, long long Sx, long long Sz, long long Sxz,
+                                                               __int128 *C_out) {
+    const __int128 C = (__int128)T * Sxz - (__int128)Sx * Sz;
+    if (C_out) *C_out = C;
+    return C < 0 ? (unsigned __int128)(-C) : (unsigned __int128)C;
+}
+
+// one workgroup per record: the observed scores q.  Wave w takes rows w, w + REP_WAVES, ...: s0[i] = s_i(0) and sq0[i] =
+// sum_j c_ij q_j^2 (below 2^61; the host's slope and r need their sum), as k_rep_trend_obs.  Then one thread adds the
+// rows up in order: rec[6 r ..] = T, Sx, Sz(0), Sxz(0), C(0) low, C(0) high
+__global__ __launch_bounds__(REP_THREADS) void k_rep_len_trend_obs(const int64_t *__restrict__ roff,
+                                                                   const int64_t *__restrict__ noff,
+                                                                   const uint2 *__restrict__ nz,
+                                                                   const int64_t *__restrict__ t,
+                                                                   const int32_t *__restrict__ x,
+                                                                   const uint16_t *__restrict__ q, long long *s0,
+                                                                   long long *__restrict__ sq0,
+                                                                   long long *__restrict__ rec) {
+    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    for (int64_t i = row0 + wave; i < row1; i += REP_WAVES) {
+        long long s = 0, sq = 0;
+        for (int64_t k = noff[i] + lane; k < noff[i + 1]; k += 64) {
+            const uint2 e = nz[k];
+            const long long v = (long long)e.y * q[e.x];
+            s += v;
+            sq += v * q[e.x];
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            s += __shfl_xor(s, o, 64);
+            sq += __shfl_xor(sq, o, 64);
+        }
+        if (lane == 0) {
+            s0[i] = s;
+            sq0[i] = sq;
+        }
+    }
+    __syncthreads();                         // the record's s0 are stored (this workgroup wrote them)
+    if (threadIdx.x == 0) {
+        long long T = 0, Sx = 0, Sz = 0, Sxz = 0;
+        for (int64_t i = row0; i < row1; ++i) {
+            T += t[i];
+            Sx += t[i] * x[i];
+            Sz += s0[i];
+            Sxz += x[i] * s0[i];
+        }
+        __int128 C;
+        rep_len_trend_abs(T, Sx, Sz, Sxz, &C);
+        long long *o = rec + (int64_t)REP_LEN_TREND_REC * r;
+        o[0] = T;
+        o[1] = Sx;
+        o[2] = Sz;
+        o[3] = Sxz;
+        o[4] = (long long)(unsigned long long)(unsigned __int128)C;
+        o[5] = (long long)(C >> 64);
+    }
+}
+
+// workgroup = (record blockIdx.x / n_tiles, tile of 256 permutations), one lane per permutation, as k_rep_perm_trend; one
+// walk over the record's rows: s_i(p) in a 64-bit register, then Sz += s_i and Sxz += x_i s_i.  Behind the last row the
+// lane forms C(p), and the exceedances |C(p)| >= |C(0)| are counted per wave (ballot) and added with one atomic per
+// wave.  No LDS, no f64.
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_trend(
+    const uint16_t *__restrict__ scores, int32_t p_count, int32_t n_tiles, const int64_t *__restrict__ roff,
+    const int64_t *__restrict__ noff, const uint2 *__restrict__ nz, const int32_t *__restrict__ x,
+    const long long *__restrict__ rec, int32_t *__restrict__ gene_ge) {
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const uint16_t *sc = scores + (valid ? p : p_count - 1);
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    const long long *o = rec + (int64_t)REP_LEN_TREND_REC * r;
+    const long long T = o[0], Sx = o[1];
+    const unsigned __int128 C0 = rep_len_trend_abs(T, Sx, o[2], o[3], nullptr);
+    long long Sz = 0, Sxz = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        long long s = 0;
+        rep_groups_walk(nz, noff[i], noff[i + 1], sc, p_count, [&](int z, int c) { s += (long long)z * c; });
+        Sz += s;
+        Sxz += x[i] * s;
+    }
+    const unsigned long long b = __ballot(valid && rep_len_trend_abs(T, Sx, Sz, Sxz, nullptr) >= C0);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&gene_ge[r], __popcll(b));
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
 static const int REP_PERM_N_CAPS = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
@@ -1487,7 +1589,7 @@ static int rep_perm_prepare(scape_hip_ctx *c, int32_t n, int32_t p_count, const 
 
 // the tail of the four tests: the exceedance counters p_site (n_site of them; none when 0) and p_gene (n_rec) are
 // zeroed, launch() queues the test, and the counts of this chunk of permutations are added to the caller's running
-// totals; stat0_out gets p_stat0
+// totals; stat0_out, when given, gets p_stat0
 template <typename Launch>
 static int rep_perm_count(scape_hip_ctx *c, int64_t n_site, int32_t n_rec, int64_t *site_n_ge_out, int64_t *gene_n_ge_out,
                           double *stat0_out, Launch launch) {
@@ -1499,7 +1601,7 @@ static int rep_perm_count(scape_hip_ctx *c, int64_t n_site, int32_t n_rec, int64
     std::vector<int32_t> site(n_site), gene(n_rec);
     if (n_site) HIPCHK(hipMemcpyAsync(site.data(), s->p_site.p, n_site * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(gene.data(), s->p_gene.p, (int64_t)n_rec * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(stat0_out, s->p_stat0.p, (int64_t)n_rec * 8, hipMemcpyDeviceToHost, c->stream));
+    if (stat0_out) HIPCHK(hipMemcpyAsync(stat0_out, s->p_stat0.p, (int64_t)n_rec * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n_site; ++i) site_n_ge_out[i] += site[i];
     for (int r = 0; r < n_rec; ++r) gene_n_ge_out[r] += gene[r];
@@ -2006,6 +2108,67 @@ int scape_hip_report_perm_trend(scape_hip_ctx *c, int32_t n_rec, const int64_t *
         HIPCHK(hipMemcpyAsync(d0_out, s->v_d0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
         return 0;
     });
+}
+
+int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                    const int32_t *x, int64_t *t_out, int64_t *s0_out, int64_t *sq0_out,
+                                    int64_t *c0_out, int64_t *n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = c->rep;
+    if (rep_perm_ready(s, s ? s->t_count : 0, "scape_hip_report_perm_scores")) return 1;
+    if (n_rec <= 0 || !rec_row_off || !rows) return fail("bad argument");
+    const int64_t n_all = rec_row_off[n_rec];
+    if (n_all <= 0 || n_all > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
+    // one segment [0, n): the row's sum over it restates t, and lands in a buffer of the call's own
+    std::vector<int64_t> a0((size_t)n_all);
+    int64_t n_rows = 0;
+    int32_t n_tiles = 0;
+    if (rep_perm_prepare(c, s->t_n, s->t_count, "scores", s->t_n, 0, nullptr, n_rec, rec_row_off, rows, t_out, a0.data(),
+                         x && s0_out && sq0_out && c0_out && n_ge_out, 0, nullptr, nullptr, nullptr, x, &n_rows, &n_tiles))
+        return 1;
+    // T < 2^31 holds (rep_perm_prepare); T max x < 2^48 keeps Sxz, at scores of up to 2^15, below 2^63.  The row sums
+    // are back and nothing of the test is queued yet
+    for (int r = 0; r < n_rec; ++r) {
+        int64_t T = 0, max_x = 0;
+        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) {
+            T += t_out[i];
+            max_x = std::max<int64_t>(max_x, x[i]);
+        }
+        if (T * max_x >= REP_LEN_TREND_MAX_TX)
+            return fail("record " + std::to_string(r) + ": reads x largest position must stay below 2^48");
+    }
+    if (s->t_s0.ensure(n_rows * 8) || s->t_sq0.ensure(n_rows * 8) || s->v_q.ensure(n_rows * 4) ||
+        s->t_lrec.ensure((int64_t)n_rec * REP_LEN_TREND_REC * 8))
+        return 1;
+    // the target of a copy queued below: rep_perm_count waits for the stream before it returns 0; where it returns early,
+    // the wait is made here, before rec goes
+    std::vector<int64_t> rec((size_t)n_rec * REP_LEN_TREND_REC);
+    if (rep_perm_count(c, 0, n_rec, nullptr, n_ge_out, nullptr, [&]() -> int {
+            HIPCHK(hipMemcpyAsync(s->v_q.p, x, n_rows * 4, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_rep_len_trend_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream,
+                               s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
+                               s->p_t.as<int64_t>(), s->v_q.as<int32_t>(), s->t_q.as<uint16_t>(),
+                               s->t_s0.as<long long>(), s->t_sq0.as<long long>(), s->t_lrec.as<long long>());
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_rep_perm_len_trend, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), 0,
+                               c->stream, s->t_scores.as<uint16_t>(), s->t_count, n_tiles, s->p_roff.as<int64_t>(),
+                               s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->v_q.as<int32_t>(),
+                               s->t_lrec.as<long long>(), s->p_gene.as<int32_t>());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(s0_out, s->t_s0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(sq0_out, s->t_sq0.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(rec.data(), s->t_lrec.p, (int64_t)n_rec * REP_LEN_TREND_REC * 8, hipMemcpyDeviceToHost,
+                                  c->stream));
+            return 0;
+        })) {
+        (void)hipStreamSynchronize(c->stream);
+        return 1;
+    }
+    for (int r = 0; r < n_rec; ++r) {
+        c0_out[2 * (size_t)r] = rec[(size_t)r * REP_LEN_TREND_REC + 4];
+        c0_out[2 * (size_t)r + 1] = rec[(size_t)r * REP_LEN_TREND_REC + 5];
+    }
+    return 0;
 }
 
 }  // extern "C"

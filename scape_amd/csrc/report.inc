@@ -76,8 +76,9 @@ struct ReportState {
     int32_t k_count = 0;
     // diff_pa_trend: the score of every (position, permutation) of the last scape_hip_report_perm_scores call
     // ([position][permutation], a halfword each), per permutation of that call the positions sorted into key buckets, the
-    // observed scores, their largest, and per kept row of scape_hip_report_perm_trend s_i(0) and sum_j c_ij q_j^2
-    DevBuf t_scores, t_members, t_q, t_s0, t_sq0;
+    // observed scores, their largest, and per kept row of scape_hip_report_perm_trend s_i(0) and sum_j c_ij q_j^2;
+    // diff_pa_len_trend: per record of scape_hip_report_perm_len_trend T, Sx, Sz(0), Sxz(0) and the two halves of C(0)
+    DevBuf t_scores, t_members, t_q, t_s0, t_sq0, t_lrec;
     int32_t t_n = 0, t_qspan = 0, t_count = 0;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
@@ -107,7 +108,8 @@ static void report_release(scape_hip_ctx *c) {
                      &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound,
                      &s->q_lab, &s->q_cut, &s->q_seg, &s->q_a0, &s->q_s0, &s->q_share, &s->v_q, &s->v_tol, &s->v_qt,
                      &s->v_mean, &s->v_d0, &s->x_bits, &s->x_bound, &s->x_desc, &s->x_seg, &s->k_bits,
-                     &s->k_bound, &s->k_seg, &s->k_rank, &s->t_scores, &s->t_members, &s->t_q, &s->t_s0, &s->t_sq0};
+                     &s->k_bound, &s->k_seg, &s->k_rank, &s->t_scores, &s->t_members, &s->t_q, &s->t_s0, &s->t_sq0,
+                     &s->t_lrec};
     for (DevBuf *b : all) b->release();
     delete s;
     c->rep = nullptr;

@@ -1503,11 +1503,12 @@ DIFF_PA_LEN_GROUPS_PER_GROUP = ["reads", "mean_pos", "delta_pos", "n_ge", "p_val
 LEN_GROUPS_Q_BITS = 22           # qspan lies in 2^21 .. 2^22: T qspan < 2^53, the sums stay exact as integers and in f64
 
 
-def _quantise_positions(x):
-    """the integer positions q_i (int32) of a record's kept rows at x (finite f64, span > 0)"""
+def _quantise_positions(x, bits=LEN_GROUPS_Q_BITS):
+    """the integer positions q_i (int32) of a record's kept rows at x (finite f64, span > 0), at `bits` bits: 2^(bits - 1)
+    <= max q_i <= 2^bits"""
     w = x - x.min()
     _m, e = math.frexp(float(x.max() - x.min()))
-    return np.rint(np.ldexp(w, LEN_GROUPS_Q_BITS - e)).astype(np.int32)
+    return np.rint(np.ldexp(w, bits - e)).astype(np.int32)
 
 
 def _mean_positions_groups(x, a):
@@ -1682,10 +1683,10 @@ def _quantise_scores(x):
     return np.rint(np.ldexp(w, TREND_Q_BITS - e)).astype(np.uint16), TREND_Q_BITS - e
 
 
-def _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed):
-    """what diff_pa_trend does before the device is opened: the argument and prerequisite checks, the scored cells and
-    their integer scores, the id -> column table that puts the scored columns first, ascending, and the output path
-    <score file stem>.<gene|utr>[.rank].diff_pa_trend.csv"""
+def _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed, command="diff_pa_trend"):
+    """what diff_pa_trend and diff_pa_len_trend do before the device is opened: the argument and prerequisite checks, the
+    scored cells and their integer scores, the id -> column table that puts the scored columns first, ascending, and the
+    output path <score file stem>.<gene|utr>[.rank].<command>.csv"""
     _check_perm_args(n_perm, seed)
     inp = _read_inputs(output_dir, res_pkl_file)
     if not os.path.exists(cell_score_file):
@@ -1695,9 +1696,9 @@ def _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed):
     cols = np.array([j for j, v in enumerate(col_score) if v is not None], dtype=np.int64)
     n = len(cols)
     if n < 2:
-        raise ValueError(f"{n} cells of barcode_index.csv have a score in {cell_score_file}: diff_pa_trend takes 2 or more")
+        raise ValueError(f"{n} cells of barcode_index.csv have a score in {cell_score_file}: {command} takes 2 or more")
     if n >= MAX_PERM_CELLS:
-        raise ValueError(f"{n} tested cells: diff_pa_trend takes fewer than {MAX_PERM_CELLS}")
+        raise ValueError(f"{n} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     x = np.array([col_score[j] for j in cols.tolist()], dtype=np.float64)
     if not float(x.max() - x.min()) > 0:
         raise ValueError(f"every scored cell of {cell_score_file} has the score {x[0]!r}: there is no trend to test")
@@ -1708,7 +1709,7 @@ def _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed):
     q, shift = _quantise_scores(x)
     _table, slot, seg_off, _seg_pop = _samples([("scored", cols)], 1, inp.n_cols)
     outpath = _out_stem(output_dir, res_pkl_file, cell_score_file, None, None) + (".rank" if rank else "") + \
-        ".diff_pa_trend.csv"
+        f".{command}.csv"
 
     def labellings(ctx, p_first, p_count):
         check(ctx.lib.scape_hip_report_perm_scores(ctx.h, n, ptr(q, _lib.P_u16), p_first, p_count, seed),
@@ -1800,6 +1801,114 @@ def _diff_pa_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, ran
     wall = _perm_run(su, n_perm, device, batch, write)
     print(f"Finish {n_perm} permutations of the scores of {su.n} cells for {sum(g[1] for g in genes)} pA sites of "
           f"{len(genes)} tested records")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- diff_pa_len_trend
+# Do 3'UTRs lengthen or shorten ALONG a per-cell score?  The length form of diff_pa_trend, as diff_pa_len is diff_pa's:
+# options, score file, scored cells, integer scores q_j and permutations are diff_pa_trend's (same --seed = same permuted
+# scores); kept rows, positions x_i = alpha_arr[label_i] and the refusal of a non-finite position are diff_pa_len's.  A
+# record is tested when it has two kept rows or more in scored cells and they lie at two positions or more.  Per record
+# the positions become integers by diff_pa_len_groups's rule at B = min(22, 48 - T.bit_length()) bits (22 bits below 2^26
+# reads, 17 at the limit of 2^31 - 1), and the scores z under a labelling give, with c_ij the count of kept row i in
+# cell j:
+#     t_i = sum_j c_ij,  T = sum t_i < 2^31,  Sx = sum t_i x_i < 2^48                                   (fixed)
+#     s_i = sum_j c_ij z(j),  Sz = sum s_i < 2^46,  Sxz = sum x_i s_i < 2^63                            (per labelling)
+#     C   = T Sxz - Sx Sz     = T^2 x the covariance of position and score over the record's reads
+# T, Sx and sum t_i x_i^2 are fixed, so |C| orders the labellings as the absolute slope of the score regressed on the
+# position does: diff_pa_trend's reading (the score as the response), carried from sites to positions.  n_ge = #{p in
+# 1..n_perm: |C(p)| >= |C(0)|}, two-sided and compared as 128-bit integers on the device: no rounding, no band.  p =
+# (1 + n_ge) / (1 + n_perm), Benjamini-Hochberg over the file's lines.  With Vz = T sum_j C_j q_j^2 - Sz^2 and Vx = T sum
+# t_i x_i^2 - Sx^2 (T^2 x the variances over the reads):  slope = C / Vz in nucleotides per unit of score, delta_pos =
+# slope x the span of the quantised scores (the shift from the first to the last cell; > 0: 3'UTRs lengthen along the
+# score - the column to read beside diff_pa_len's), r = C / sqrt(Vz Vx) (Pearson); the three are empty when Vz = 0, where
+# C(0) = 0, every permutation is counted and p = 1.  mean_pos comes from the exact x_i, mean_score = min x + (Sz / T)
+# 2^-s.  No --strata_file, no exp_length columns, and no per-site lines: the test is per gene.
+DIFF_PA_LEN_TREND_HEADER = ["gene", "num_pa", "reads", "mean_pos", "mean_score", "slope", "delta_pos", "r", "n_ge",
+                            "p_val", "p_val_adj", "n_perm"]
+LEN_TREND_MAX_Q_BITS = 22        # the device takes positions of up to 2^22
+LEN_TREND_TX_BITS = 48           # T max x < 2^48: at scores of up to 2^15, Sxz stays below 2^63
+
+
+def _len_trend_bits(T):
+    """the bits of a record's integer positions: T < 2^T.bit_length() and max x <= 2^B give T max x < 2^48"""
+    return min(LEN_TREND_MAX_Q_BITS, LEN_TREND_TX_BITS - int(T).bit_length())
+
+
+def _diff_pa_len_trend_batch(ctx, bat, su, n_perm, chunk, out, times):
+    """one counted batch: appends (gene, num_pa, T, mean_pos, mean_score, slope, delta_pos, r, n_ge) per tested record
+    to `out`; slope, delta_pos and r are None when the score has no variance over the record's reads"""
+    recs = bat.recs
+    pos = {}                     # record -> positions of its kept rows (f64, finite)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos), min_pops=1)
+    sel = sel and _with_span(sel, pos, times)
+    if sel is None:
+        return
+    which, off, rows, sums, _rowbase, xs = sel
+    t0 = timer()
+    Ts = np.add.reduceat(sums[:, 0], off[:-1]).tolist()
+    for g, r in enumerate(which.tolist()):
+        _check_reads(recs[r], Ts[g])
+    bits = [_len_trend_bits(T) for T in Ts]
+    qs = [_quantise_positions(x, b) for x, b in zip(xs, bits)]
+    q = np.ascontiguousarray(np.concatenate(qs))
+    times["finish"] += timer() - t0
+    t, s0, sq0 = (np.zeros(len(rows), np.int64) for _ in range(3))
+    c0, n_ge = np.zeros(2 * len(which), np.int64), np.zeros(len(which), np.int64)
+    _perm_chunks(ctx, su, n_perm, chunk, times, lambda: check(
+        ctx.lib.scape_hip_report_perm_len_trend(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), ptr(q, P_i32),
+                                                ptr(t, P_i64), ptr(s0, P_i64), ptr(sq0, P_i64), ptr(c0, P_i64),
+                                                ptr(n_ge, P_i64)), "report_perm_len_trend"))
+    t0 = timer()
+    if not np.array_equal(t, sums[:, 0]):
+        raise _lib.ScapeHipError("report_perm_len_trend: row sums differ from report_group_sums")
+    lo, unit_z, qspan = Fraction(su.lo), Fraction(2) ** -su.shift, int(su.q.max())
+    for g, r in enumerate(which.tolist()):
+        sl = slice(int(off[g]), int(off[g + 1]))
+        ti, si, xi = t[sl].tolist(), s0[sl].tolist(), qs[g].tolist()
+        # the statistic of the observed scores, exactly, in Python ints
+        T, Sx, Sz = Ts[g], sum(a * b for a, b in zip(ti, xi)), sum(si)
+        C = T * sum(a * b for a, b in zip(xi, si)) - Sx * Sz
+        if (int(c0[2 * g + 1]) << 64) + (int(c0[2 * g]) & ((1 << 64) - 1)) != C:
+            raise _lib.ScapeHipError(f"report_perm_len_trend: {recs[r].gene_info_str}: the device's C(0), halves "
+                                     f"{int(c0[2 * g])} and {int(c0[2 * g + 1])}, differs from {C}")
+        Vz = T * sum(sq0[sl].tolist()) - Sz * Sz
+        Vx = T * sum(a * b * b for a, b in zip(ti, xi)) - Sx * Sx
+        _m, e = math.frexp(float(xs[g].max() - xs[g].min()))
+        unit_x = Fraction(2) ** (e - bits[g])
+        slope = delta = corr = None
+        if Vz:
+            slope = float(Fraction(C, Vz) * unit_x / unit_z)
+            delta = float(Fraction(C * qspan, Vz) * unit_x)
+            corr = math.copysign(math.sqrt(float(Fraction(C * C, Vz * Vx))), C)
+        mean_pos, _mean_g, _delta_g = _mean_positions_groups(xs[g], [[a] for a in ti])
+        out.append((recs[r].gene_info_str, len(ti), T, mean_pos, float(lo + Fraction(Sz, T) * unit_z), slope, delta,
+                    corr, int(n_ge[g])))
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_len_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, rank: bool = False, n_perm: int = 9999,
+                       seed: int = 1, device=None):
+    """permutation test of the pA position (3'UTR length) along the per-cell score of a score file (its ranks with
+    rank=True); writes <score file stem>.<gene|utr>[.rank].diff_pa_len_trend.csv in output_dir, one line per tested
+    record, and returns its path"""
+    su = _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed, "diff_pa_len_trend")
+    out = []
+
+    def batch(ctx, bat, chunk, times):
+        _diff_pa_len_trend_batch(ctx, bat, su, n_perm, chunk, out, times)
+
+    def write(w):
+        w.writerow(DIFF_PA_LEN_TREND_HEADER)
+        if not out:
+            return
+        p_val = (1 + np.array([o[8] for o in out], dtype=np.int64)) / (1 + n_perm)
+        w.writerows(list(o[:3]) + [repr(o[3]), repr(o[4])] + ["" if v is None else repr(v) for v in o[5:8]] +
+                    [o[8], repr(p), repr(adj), n_perm] for o, p, adj in zip(out, p_val.tolist(), _bh(p_val).tolist()))
+
+    wall = _perm_run(su, n_perm, device, batch, write)
+    print(f"Finish {n_perm} permutations of the scores of {su.n} cells for {len(out)} tested records")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -2111,24 +2220,44 @@ def diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     _diff_pa_markers(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
 
 
+def _trend_options(f):
+    """the options diff_pa_trend and diff_pa_len_trend share"""
+    for option in reversed((
+            click.option('--output_dir', type=str, required=True,
+                         help='Directory which was used in previous steps to save output by prepare_input and '
+                              'infer_pa.'),
+            click.option('--res_pkl_file', type=str, default="None",
+                         help='Name of res pickle file that contains PASs. Its name will be included in the file name '
+                              'of the final result.'),
+            click.option('--cell_score_file', type=str, required=True,
+                         help='An csv file containing two columns in order: cell barcode index (index) and the score '
+                              'of the cell (pseudotime, a differentiation, cell-cycle or activation score). Cells with '
+                              'an empty score, NA or nan, or not listed, are left out. Its name will be included in '
+                              'the file name of the final result.'),
+            click.option('--rank', is_flag=True, default=False,
+                         help='Test along the ranks of the scores (ties share their mid-rank), not the scores '
+                              'themselves.'),
+            click.option('--n_perm', type=int, default=9999, show_default=True,
+                         help='Permutations of the cell scores; the smallest p-value is 1 / (1 + n_perm).'),
+            click.option('--seed', type=int, default=1, show_default=True,
+                         help='Seed of the permutations, 0 .. 2^64 - 1 (the keys are those of diff_pa).'))):
+        f = option(f)
+    return f
+
+
 @click.command(name="diff_pa_trend")
-@click.option('--output_dir', type=str, required=True,
-              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
-@click.option('--res_pkl_file', type=str, default="None",
-              help='Name of res pickle file that contains PASs. Its name will be included in the file name of the '
-                   'final result.')
-@click.option('--cell_score_file', type=str, required=True,
-              help='An csv file containing two columns in order: cell barcode index (index) and the score of the cell '
-                   '(pseudotime, a differentiation, cell-cycle or activation score). Cells with an empty score, NA or '
-                   'nan, or not listed, are left out. Its name will be included in the file name of the final result.')
-@click.option('--rank', is_flag=True, default=False,
-              help='Test along the ranks of the scores (ties share their mid-rank), not the scores themselves.')
-@click.option('--n_perm', type=int, default=9999, show_default=True,
-              help='Permutations of the cell scores; the smallest p-value is 1 / (1 + n_perm).')
-@click.option('--seed', type=int, default=1, show_default=True,
-              help='Seed of the permutations, 0 .. 2^64 - 1 (the keys are those of diff_pa).')
+@_trend_options
 def diff_pa_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, rank: bool, n_perm: int, seed: int):
     """pA sites and genes whose pA usage shifts along a per-cell score such as pseudotime: a permutation test of the
     cell scores on the mean score of every site's reads against the gene's other reads, and on the between-site sum of
     squares of the score (delta_score > 0: the site is used by cells further along)."""
     _diff_pa_trend(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed)
+
+
+@click.command(name="diff_pa_len_trend")
+@_trend_options
+def diff_pa_len_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, rank: bool, n_perm: int, seed: int):
+    """Genes whose 3'UTRs lengthen or shorten along a per-cell score such as pseudotime: an exact permutation test of
+    the cell scores on the covariance of the pA position and the score over the gene's reads, the score's permutations
+    those of diff_pa_trend (delta_pos > 0: longer 3'UTRs in cells further along)."""
+    _diff_pa_len_trend(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed)
