@@ -43,9 +43,12 @@
 //   k_rep_len_trend_obs / k_rep_perm_len_trend
 //                   diff_pa_len_trend: on the same scores, the covariance of the pA position and the score over a
 //                   record's reads as a 128-bit integer, compared exactly; one walk of the nonzeros, no f64
-// On the host rep_perm_classes / rep_perm_launch_classes launch the two-population test per LDS class of records, and
-// the exceedance counters come back through rep_perm_count.  Cluster names, strata files, p-values and their adjustment
-// stay on the host (scape_amd/report.py).
+// On the host a builder leaves a RepLabellings in ReportState (what it built, for the checks of the tests and of the
+// `_get` entry points).  A test fills a RepPermCall, the one frame of its call: rep_perm_prepare checks and compacts from
+// it, rep_perm_launch_classes launches a two-population test per LDS class of records, rep_perm_count brings the
+// exceedance counters back, rep_perm_ranged is the body that diff_pa_pairs and diff_pa_markers share and
+// rep_trend_prepare the head of the two tests on scores.  No entry point returns with work queued on the stream
+// (StreamDrain).  Cluster names, strata files, p-values and their adjustment stay on the host (scape_amd/report.py).
 
 // ---- keys and the radix select ----------------------------------------------------------------------------------------
 // The tested columns are the first n columns of the count matrix (population 1, then population 2, ...: the caller's
@@ -1372,6 +1375,20 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_trend(
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
+// One rule for every entry point below: once it has queued anything on the stream it returns, with 0 or with 1, only
+// after the stream has been waited for.  StreamDrain keeps it: armed before the first queueing, it waits when it goes
+// out of scope unless wait() has done so.  Host memory that a queued copy reads or writes outlives that wait: it sits in
+// the base of a test's frame (RepPermHost goes after RepPermCall's drain) or is declared ahead of a builder's drain.
+struct StreamDrain {
+    hipStream_t stream;
+    bool armed;
+    explicit StreamDrain(hipStream_t s, bool a = true) : stream(s), armed(a) {}
+    StreamDrain(const StreamDrain &) = delete;
+    StreamDrain &operator=(const StreamDrain &) = delete;
+    int wait() { armed = false; HIPCHK(hipStreamSynchronize(stream)); return 0; }
+    ~StreamDrain() { if (armed) (void)hipStreamSynchronize(stream); }
+};
+
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
 static const int REP_PERM_N_CAPS = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));
 
@@ -1398,25 +1415,6 @@ static RepPermClasses rep_perm_classes(int32_t n_rec, const int64_t *rec_row_off
     return cl;
 }
 
-// one launch of `kernel` per class that has records: launch(records of the class on the device, their number, cap,
-// bytes of dynamic LDS) queues it.  cl stays alive until the caller has waited for the stream (the upload of recs)
-template <typename Kernel, typename Launch>
-static int rep_perm_launch_classes(scape_hip_ctx *c, const RepPermClasses &cl, Kernel kernel, Launch launch) {
-    ReportState *s = c->rep;
-    HIPCHK(hipMemcpyAsync(s->p_recs.p, cl.recs.data(), (int64_t)cl.recs.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               REP_PERM_CAPS[REP_PERM_N_CAPS - 1] * REP_THREADS * 4));
-    int64_t first = 0;
-    for (int q = 0; q < REP_PERM_N_CAPS; ++q) {
-        if (!cl.count[q]) continue;
-        const int32_t cap = REP_PERM_CAPS[q];
-        launch(s->p_recs.as<int32_t>() + first, cl.count[q], cap, (size_t)cap * REP_THREADS * 4);
-        HIPCHK(hipGetLastError());
-        first += cl.count[q];
-    }
-    return 0;
-}
-
 // what every builder of labellings asks of its n positions (`cells_must` names them: "... must [be]") and its chunk
 static int rep_perm_chunk_ok(int64_t n, const char *cells_must, int64_t p_first, int32_t p_count) {
     if (n >= REP_PERM_MAX_N) return fail(std::string(cells_must) + " below 2^24 (a key keeps the position in 24 bits)");
@@ -1424,9 +1422,17 @@ static int rep_perm_chunk_ok(int64_t n, const char *cells_must, int64_t p_first,
     return 0;
 }
 
+// A builder call refused by a check keeps the earlier labellings.  Behind its checks a builder sets count = 0 and arms
+// its drain: from the first allocation on they are gone until rep_built() has waited for the kernel and recorded the new
+static int rep_built(StreamDrain &drain, RepLabellings &l, int64_t n, int32_t p_count) {
+    HIPCHK(hipGetLastError());
+    if (drain.wait()) return 1;
+    l.n = (int32_t)n, l.count = p_count;
+    return 0;
+}
+
 // the membership bits of permutations p_first .. p_first + p_count - 1 for strata of m1[k] + m2[k] >= 1 cells (the
-// entry points have checked each stratum).  A call refused by a check keeps the earlier masks; from the first
-// allocation on they are gone until this call has succeeded.
+// entry points have checked each stratum)
 static int rep_build_masks(scape_hip_ctx *c, int32_t n_strata, const int32_t *m1, const int32_t *m2, int64_t p_first,
                            int32_t p_count, uint64_t seed) {
     int64_t n1 = 0, n2 = 0;
@@ -1437,7 +1443,6 @@ static int rep_build_masks(scape_hip_ctx *c, int32_t n_strata, const int32_t *m1
     if (n1 < 1 || n2 < 1) return fail("both populations need at least one cell");
     if (rep_perm_chunk_ok(n1 + n2, "n1 + n2 must be", p_first, p_count)) return 1;
     ReportState *s = report_state(c);
-    s->m_count = 0;
     const int32_t n = (int32_t)(n1 + n2);
     // the position ranges of every stratum, the stratum of every position, and the strata in work order
     std::vector<int32_t> desc((size_t)n_strata * 4), order, large, strat_of((size_t)n);
@@ -1455,6 +1460,8 @@ static int rep_build_masks(scape_hip_ctx *c, int32_t n_strata, const int32_t *m1
     }
     const int32_t n_wave = (int32_t)order.size();
     order.insert(order.end(), large.begin(), large.end());
+    s->masks.count = 0;
+    StreamDrain drain(c->stream);
     if (s->m_bits.ensure((int64_t)p_count * ((n + 63) / 64) * 8) || s->m_desc.ensure((int64_t)n_strata * 16) ||
         s->m_order.ensure((int64_t)n_strata * 4) || s->m_strat.ensure((int64_t)n * 4) ||
         s->m_bound.ensure((int64_t)p_count * n_strata * 8))
@@ -1466,30 +1473,18 @@ static int rep_build_masks(scape_hip_ctx *c, int32_t n_strata, const int32_t *m1
                        s->m_desc.as<int4>(), s->m_order.as<int32_t>(), s->m_strat.as<int32_t>(),
                        (unsigned long long)p_first, p_count, (unsigned long long)seed,
                        s->m_bound.as<unsigned long long>(), s->m_bits.as<unsigned long long>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
     s->m_n1 = (int32_t)n1;
-    s->m_n2 = (int32_t)n2;
-    s->m_count = p_count;
-    return 0;
+    return rep_built(drain, s->masks, n, p_count);
 }
 
-// a test entry point starts here: the counts are on the device and `builder` has left p_count labellings
-static int rep_perm_ready(const ReportState *s, int32_t p_count, const char *builder) {
-    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
-    if (!p_count) return fail(std::string(builder) + " has not been called");
-    return 0;
-}
-
-// the groups of a test on column segments are those of the last call of `builder`, which remembered their sizes
-static int rep_groups_match(const std::vector<int32_t> &sizes, const char *builder, int32_t n_groups,
-                            const int32_t *seg_off) {
+// the groups of a test on column segments are those of the builder's last call, which remembered their sizes
+static int rep_groups_match(const RepLabellings &l, int32_t n_groups, const int32_t *seg_off) {
     if (!seg_off) return fail("bad argument");
-    if (n_groups != (int32_t)sizes.size()) return fail("n_groups differs from the last " + std::string(builder) + " call");
+    if (n_groups != (int32_t)l.sizes.size()) return fail("n_groups differs from the last " + std::string(l.builder) + " call");
     if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
     for (int32_t g = 0; g < n_groups; ++g)
-        if (seg_off[g + 1] - seg_off[g] != sizes[g])
-            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last " + builder + " call");
+        if (seg_off[g + 1] - seg_off[g] != l.sizes[g])
+            return fail("group " + std::to_string(g) + ": seg_off differs from the sizes of the last " + l.builder + " call");
     return 0;
 }
 
@@ -1506,106 +1501,192 @@ static int rep_group_sizes_ok(int32_t n_groups, const int32_t *sizes) {
     return 0;
 }
 
-// the part the four tests share, behind rep_perm_ready.  n = the tested positions and p_count = the permutations of the
-// labellings (`what`: "masks" or "labels").  First the checks (outs_ok = the caller's own other pointers are there;
-// max_rec_rows > 0: a record may own at most that many rows; w / tol / tol2, when given, must be finite and not negative
-// and the integer positions q, when given, lie in 0 .. REP_LEN_GROUPS_MAX_Q),
-// all of them before anything is queued on the device, then the upload of rows and offsets and the compaction of the
-// kept rows to their nonzeros (p_noff / p_nz), with t and a0 of every row on the host.  Two populations (seg_off =
-// nullptr): a0 = the row's sum over the positions below n1, in p_a0.  n_groups populations in the column segments
-// seg_off: a0 = the n_groups sums of the row, in q_a0.
-static int rep_perm_prepare(scape_hip_ctx *c, int32_t n, int32_t p_count, const char *what, int32_t n1, int32_t n_groups,
-                            const int32_t *seg_off, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
-                            int64_t *t_out, int64_t *a0_out, bool outs_ok, int64_t max_rec_rows, const double *w,
-                            const double *tol, const double *tol2, const int32_t *q, int64_t *n_rows_out,
-                            int32_t *n_tiles_out) {
+// a `_get` entry point starts here; item_refused = the message where the pair or marker it names is none, else nullptr
+static int rep_get_ok(const RepLabellings &l, const void *out, const char *item_refused, int32_t p) {
+    if (l.built()) return 1;
+    if (!out) return fail("bad argument");
+    if (item_refused) return fail(item_refused);
+    return l.holds(p);
+}
+
+// The frame of a test call behind RepLabellings::ready; an entry point sets what it uses.  n = the tested positions and
+// p_count = the permutations of the labellings `what`.  Two populations (seg_off = nullptr): a0 = the row's sum over the
+// positions below n1, in p_a0.  n_groups populations in the column segments seg_off: a0 = the n_groups sums of the row,
+// in q_a0.  outs_ok = the caller's own other pointers are there; max_rec_rows > 0: a record may own at most that many
+// rows; w / tol / tol2, when given, must be finite and not negative; the positions q, when given, lie in 0 .. 2^22.
+struct RepPermHost {                   // the call's host memory that queued copies read or write
+    RepPermClasses classes;            // rep_perm_launch_classes
+    std::vector<int32_t> site, gene;   // rep_perm_count: the counters of this chunk
+    std::vector<int64_t> own_a0, lrec; // what single tests fetch for themselves: the trend tests' a0, len_trend's records
+    std::vector<double> tols;          // len_groups: (tolD, told) per record, uploaded
+};
+struct RepPermCall : RepPermHost {
+    int32_t n, p_count, n_rec, n1 = 0, n_groups = 0;
+    const char *what;
+    const int64_t *rec_row_off, *rows;
+    int64_t *t_out, *a0_out = nullptr;
+    const int32_t *seg_off = nullptr, *q = nullptr;
+    const double *w = nullptr, *tol = nullptr, *tol2 = nullptr;
+    bool outs_ok = false;
+    int64_t max_rec_rows = 0;
+    int64_t n_rows = 0, nnz = 0;       // results of rep_perm_prepare: the kept rows, their nonzeros and the tiles of
+    int32_t n_tiles = 0;               // REP_THREADS permutations
+    StreamDrain drain;                 // waits, where armed, before the base goes
+    RepPermCall(scape_hip_ctx *c, const RepLabellings &l, int32_t n_rec_, const int64_t *rec_row_off_, const int64_t *rows_,
+                int64_t *t_out_)
+        : n(l.n), p_count(l.count), n_rec(n_rec_), what(l.what), rec_row_off(rec_row_off_), rows(rows_), t_out(t_out_),
+          drain(c->stream, false) {}
+};
+
+// the part the tests share: the checks, all of them before anything is queued on the device, then the upload of rows and
+// offsets and the compaction of the kept rows to their nonzeros (p_noff / p_nz), with t and a0 of every row on the host
+static int rep_perm_prepare(scape_hip_ctx *c, RepPermCall &k) {
     ReportState *s = c->rep;
-    if (n_rec <= 0 || !rec_row_off || !rows || !t_out || !a0_out || !outs_ok) return fail("bad argument");
-    if (n > s->n_cols)
-        return fail("the count matrix has fewer columns than the " + std::string(what) + " have positions");
+    const int32_t n_rec = k.n_rec;
+    const int64_t *rec_row_off = k.rec_row_off;
+    if (n_rec <= 0 || !rec_row_off || !k.rows || !k.t_out || !k.a0_out || !k.outs_ok) return fail("bad argument");
+    if (k.n > s->n_cols)
+        return fail("the count matrix has fewer columns than the " + std::string(k.what) + " have positions");
     if (rec_row_off[0] != 0) return fail("rec_row_off must start at 0");
     for (int r = 0; r < n_rec; ++r)
         if (rec_row_off[r + 1] < rec_row_off[r]) return fail("rec_row_off must be non-decreasing");
     const int64_t n_rows = rec_row_off[n_rec];
     if (n_rows <= 0 || n_rows > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
-    if (max_rec_rows > 0)
+    if (k.max_rec_rows > 0)
         for (int r = 0; r < n_rec; ++r)
-            if (rec_row_off[r + 1] - rec_row_off[r] > max_rec_rows)
-                return fail("record " + std::to_string(r) + ": more than " + std::to_string(max_rec_rows) + " rows");
+            if (rec_row_off[r + 1] - rec_row_off[r] > k.max_rec_rows)
+                return fail("record " + std::to_string(r) + ": more than " + std::to_string(k.max_rec_rows) + " rows");
     for (int64_t i = 0; i < n_rows; ++i)
-        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
-    const int32_t n_tiles = (p_count + REP_THREADS - 1) / REP_THREADS;
+        if (k.rows[i] < 0 || k.rows[i] >= s->n_cnt_rows) return fail("row index out of range");
+    const int32_t n_tiles = (k.p_count + REP_THREADS - 1) / REP_THREADS;
     if ((int64_t)n_rec * n_tiles > INT32_MAX) return fail("too many records x permutation tiles for one call");
-    for (int64_t i = 0; w && i < n_rows; ++i)
-        if (!(w[i] >= 0.0) || std::isinf(w[i])) return fail("row weights must be finite and not negative");
-    for (const double *tl : {tol, tol2})
+    for (int64_t i = 0; k.w && i < n_rows; ++i)
+        if (!(k.w[i] >= 0.0) || std::isinf(k.w[i])) return fail("row weights must be finite and not negative");
+    for (const double *tl : {k.tol, k.tol2})
         for (int r = 0; tl && r < n_rec; ++r)
             if (!(tl[r] >= 0.0) || std::isinf(tl[r])) return fail("tolerances must be finite and not negative");
-    for (int64_t i = 0; q && i < n_rows; ++i)
-        if (q[i] < 0 || q[i] > REP_LEN_GROUPS_MAX_Q) return fail("row positions must lie in 0 .. 2^22");
+    for (int64_t i = 0; k.q && i < n_rows; ++i)
+        if (k.q[i] < 0 || k.q[i] > REP_LEN_GROUPS_MAX_Q) return fail("row positions must lie in 0 .. 2^22");
 
-    DevBuf &a0 = seg_off ? s->q_a0 : s->p_a0;
-    const int64_t a0_bytes = n_rows * (seg_off ? n_groups : 1) * 8;
+    DevBuf &a0 = k.seg_off ? s->q_a0 : s->p_a0;
+    const int64_t a0_bytes = n_rows * (k.seg_off ? k.n_groups : 1) * 8;
     if (s->p_rows.ensure(n_rows * 8) || s->p_roff.ensure(((int64_t)n_rec + 1) * 8) || s->p_nnz.ensure(n_rows * 8) ||
         s->p_noff.ensure((n_rows + 1) * 8) || s->p_t.ensure(n_rows * 8) || a0.ensure(a0_bytes) ||
         s->p_gene.ensure((int64_t)n_rec * 4) || s->p_stat0.ensure((int64_t)n_rec * 8))
         return 1;
-    HIPCHK(hipMemcpyAsync(s->p_rows.p, rows, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    k.drain.armed = true;
+    HIPCHK(hipMemcpyAsync(s->p_rows.p, k.rows, n_rows * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(s->p_roff.p, rec_row_off, ((int64_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (seg_off) {
-        if (s->q_seg.ensure(((int64_t)n_groups + 1) * 4)) return 1;
-        HIPCHK(hipMemcpyAsync(s->q_seg.p, seg_off, ((int64_t)n_groups + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (k.seg_off) {
+        if (s->q_seg.ensure(((int64_t)k.n_groups + 1) * 4)) return 1;
+        HIPCHK(hipMemcpyAsync(s->q_seg.p, k.seg_off, ((int64_t)k.n_groups + 1) * 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_rep_groups_rowstat, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
-                           s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n_groups, s->q_seg.as<int32_t>(),
+                           s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), k.n_groups, s->q_seg.as<int32_t>(),
                            s->p_nnz.as<int64_t>(), s->p_t.as<int64_t>(), a0.as<int64_t>());
     } else {
         hipLaunchKernelGGL(k_rep_perm_rowstat, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
-                           s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n1, n, s->p_nnz.as<int64_t>(),
+                           s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), k.n1, k.n, s->p_nnz.as<int64_t>(),
                            s->p_t.as<int64_t>(), a0.as<int64_t>());
     }
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->p_nnz.as<int64_t>(),
                        (int32_t)n_rows, s->p_noff.as<int64_t>());
     HIPCHK(hipGetLastError());
-    int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, s->p_noff.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(t_out, s->p_t.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(a0_out, a0.p, a0_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&k.nnz, s->p_noff.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(k.t_out, s->p_t.p, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(k.a0_out, a0.p, a0_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int r = 0; r < n_rec; ++r) {
         int64_t T = 0;
-        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) T += t_out[i];
+        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) T += k.t_out[i];
         if (T > INT32_MAX) return fail("record " + std::to_string(r) + ": 2^31 or more reads in the tested cells");
     }
-    if (s->p_nz.ensure(std::max<int64_t>(total, 1) * 8)) return 1;
+    if (s->p_nz.ensure(std::max<int64_t>(k.nnz, 1) * 8)) return 1;
     hipLaunchKernelGGL(k_rep_perm_fill, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
-                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), n, s->p_noff.as<int64_t>(),
+                       s->p_rows.as<int64_t>(), s->n_cols, s->r_cnt.as<int32_t>(), k.n, s->p_noff.as<int64_t>(),
                        s->p_nz.as<uint2>());
     HIPCHK(hipGetLastError());
-    *n_rows_out = n_rows;
-    *n_tiles_out = n_tiles;
+    k.n_rows = n_rows, k.n_tiles = n_tiles;
     return 0;
 }
 
-// the tail of the four tests: the exceedance counters p_site (n_site of them; none when 0) and p_gene (n_rec) are
-// zeroed, launch() queues the test, and the counts of this chunk of permutations are added to the caller's running
-// totals; stat0_out, when given, gets p_stat0
+// the tail of the tests: the exceedance counters p_site (n_site of them; none when 0) and p_gene (n_out) are zeroed,
+// launch() queues the test, and the counts of this chunk of permutations are added to the caller's running totals;
+// stat0_out, when given, gets p_stat0
 template <typename Launch>
-static int rep_perm_count(scape_hip_ctx *c, int64_t n_site, int32_t n_rec, int64_t *site_n_ge_out, int64_t *gene_n_ge_out,
-                          double *stat0_out, Launch launch) {
+static int rep_perm_count(scape_hip_ctx *c, RepPermCall &k, int64_t n_site, int32_t n_out, int64_t *site_n_ge_out,
+                          int64_t *gene_n_ge_out, double *stat0_out, Launch launch) {
     ReportState *s = c->rep;
     if (n_site && s->p_site.ensure(n_site * 4)) return 1;
     if (n_site) HIPCHK(hipMemsetAsync(s->p_site.p, 0, n_site * 4, c->stream));
-    HIPCHK(hipMemsetAsync(s->p_gene.p, 0, (int64_t)n_rec * 4, c->stream));
+    HIPCHK(hipMemsetAsync(s->p_gene.p, 0, (int64_t)n_out * 4, c->stream));
     if (launch()) return 1;
-    std::vector<int32_t> site(n_site), gene(n_rec);
-    if (n_site) HIPCHK(hipMemcpyAsync(site.data(), s->p_site.p, n_site * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(gene.data(), s->p_gene.p, (int64_t)n_rec * 4, hipMemcpyDeviceToHost, c->stream));
-    if (stat0_out) HIPCHK(hipMemcpyAsync(stat0_out, s->p_stat0.p, (int64_t)n_rec * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int64_t i = 0; i < n_site; ++i) site_n_ge_out[i] += site[i];
-    for (int r = 0; r < n_rec; ++r) gene_n_ge_out[r] += gene[r];
+    k.site.resize(n_site), k.gene.resize(n_out);
+    if (n_site) HIPCHK(hipMemcpyAsync(k.site.data(), s->p_site.p, n_site * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(k.gene.data(), s->p_gene.p, (int64_t)n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    if (stat0_out) HIPCHK(hipMemcpyAsync(stat0_out, s->p_stat0.p, (int64_t)n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    if (k.drain.wait()) return 1;
+    for (int64_t i = 0; i < n_site; ++i) site_n_ge_out[i] += k.site[i];
+    for (int r = 0; r < n_out; ++r) gene_n_ge_out[r] += k.gene[r];
     return 0;
+}
+
+// one launch of `kernel` per class of the call's records that has any: launch(records of the class on the device, their
+// number, cap, bytes of dynamic LDS) queues it
+template <typename Kernel, typename Launch>
+static int rep_perm_launch_classes(scape_hip_ctx *c, RepPermCall &k, Kernel kernel, Launch launch) {
+    ReportState *s = c->rep;
+    const RepPermClasses &cl = k.classes = rep_perm_classes(k.n_rec, k.rec_row_off);
+    HIPCHK(hipMemcpyAsync(s->p_recs.p, cl.recs.data(), (int64_t)cl.recs.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               REP_PERM_CAPS[REP_PERM_N_CAPS - 1] * REP_THREADS * 4));
+    int64_t first = 0;
+    for (int q = 0; q < REP_PERM_N_CAPS; ++q) {
+        if (!cl.count[q]) continue;
+        const int32_t cap = REP_PERM_CAPS[q];
+        launch(s->p_recs.as<int32_t>() + first, cl.count[q], cap, (size_t)cap * REP_THREADS * 4);
+        HIPCHK(hipGetLastError());
+        first += cl.count[q];
+    }
+    return 0;
+}
+
+// The two tests of every item (pair, marker) of a range against the one compaction, by LDS class of records: behind
+// ready and the groups' match, the range [first, first + count) of the builder's n_items, prepare, the counters of
+// count x n_rec; pre(k) checks, allocates and queues what the kernel needs first, launch(k, recs, m, cap, lds) one class
+template <typename Kernel, typename Pre, typename Launch>
+static int rep_perm_ranged(scape_hip_ctx *c, const RepLabellings &l, const std::string &noun, int32_t n_items,
+                           int32_t first, int32_t count, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                           int32_t n_groups, const int32_t *seg_off, int64_t *t_out, int64_t *a0_out,
+                           int64_t *site_n_ge_out, double *stat0_out, int64_t *gene_n_ge_out, Kernel kernel, Pre pre,
+                           Launch launch) {
+    ReportState *s = c->rep;
+    if (l.ready(s->n_cnt_rows) || rep_groups_match(l, n_groups, seg_off)) return 1;
+    if (first < 0 || count < 1 || first > n_items - count)
+        return fail(noun + "_first and " + noun + "_count must name " + noun + "s of the last " + l.builder + " call");
+    if (n_rec > 0 && rec_row_off && ((int64_t)count * n_rec > INT32_MAX || rec_row_off[n_rec] > INT64_MAX / 8 / count))
+        return fail("too many " + noun + "s x records or " + noun + "s x rows for one call: take the " + noun +
+                    "s in ranges");
+    RepPermCall k(c, l, n_rec, rec_row_off, rows, t_out);
+    k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off, k.outs_ok = site_n_ge_out && stat0_out && gene_n_ge_out;
+    if (rep_perm_prepare(c, k) || pre(k)) return 1;
+    const int64_t n_out = (int64_t)count * n_rec;
+    if (s->p_recs.ensure((int64_t)n_rec * 4) || s->p_gene.ensure(n_out * 4) || s->p_stat0.ensure(n_out * 8)) return 1;
+    return rep_perm_count(c, k, count * k.n_rows, (int32_t)n_out, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
+        return rep_perm_launch_classes(c, k, kernel, [&](const int32_t *recs, int64_t m, int32_t cap, size_t lds) {
+            launch(k, recs, m, cap, lds);
+        });
+    });
+}
+
+// the head of the two tests on scores: one segment [0, n), whose row sums restate t and land in the call's own buffer
+static int rep_trend_prepare(scape_hip_ctx *c, RepPermCall &k) {
+    if (k.n_rec <= 0 || !k.rec_row_off || !k.rows) return fail("bad argument");
+    const int64_t n_all = k.rec_row_off[k.n_rec];
+    if (n_all <= 0 || n_all > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
+    k.own_a0.resize((size_t)n_all);
+    k.a0_out = k.own_a0.data(), k.n1 = k.n;
+    return rep_perm_prepare(c, k);
 }
 
 extern "C" {
@@ -1629,36 +1710,29 @@ int scape_hip_report_perm_masks_strata(scape_hip_ctx *c, int32_t n_strata, const
 
 int scape_hip_report_perm_bits_get(scape_hip_ctx *c, int32_t p, uint64_t *words_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->m_count) return fail("scape_hip_report_perm_masks has not been called");
-    if (!words_out) return fail("bad argument");
-    if (p < 0 || p >= s->m_count) return fail("p must name a permutation of the last masks call");
-    const int32_t n_words = (s->m_n1 + s->m_n2 + 63) / 64;
-    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->m_bits.as<unsigned long long>() + p, (size_t)s->m_count * 8, 8, n_words,
+    ReportState *s = report_state(c);
+    const RepLabellings &l = s->masks;
+    if (rep_get_ok(l, words_out, nullptr, p)) return 1;
+    StreamDrain drain(c->stream);
+    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->m_bits.as<unsigned long long>() + p, (size_t)l.count * 8, 8, (l.n + 63) / 64,
                             hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return drain.wait();
 }
 
 int scape_hip_report_perm_test(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                                int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                int64_t *gene_n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->m_count : 0, "scape_hip_report_perm_masks")) return 1;
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    if (rep_perm_prepare(c, s->m_n1 + s->m_n2, s->m_count, "masks", s->m_n1, 0, nullptr, n_rec, rec_row_off, rows, t_out,
-                         a0_out, site_n_ge_out && stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr, nullptr, &n_rows,
-                         &n_tiles))
-        return 1;
-    if (s->p_recs.ensure((int64_t)n_rec * 4)) return 1;
-    const RepPermClasses cl = rep_perm_classes(n_rec, rec_row_off);
-    return rep_perm_count(c, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
-        return rep_perm_launch_classes(c, cl, k_rep_perm_test, [&](const int32_t *recs, int64_t m, int32_t cap,
+    ReportState *s = report_state(c);
+    if (s->masks.ready(s->n_cnt_rows)) return 1;
+    RepPermCall k(c, s->masks, n_rec, rec_row_off, rows, t_out);
+    k.a0_out = a0_out, k.n1 = s->m_n1, k.outs_ok = site_n_ge_out && stat0_out && gene_n_ge_out;
+    if (rep_perm_prepare(c, k) || s->p_recs.ensure((int64_t)n_rec * 4)) return 1;
+    return rep_perm_count(c, k, k.n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
+        return rep_perm_launch_classes(c, k, k_rep_perm_test, [&](const int32_t *recs, int64_t m, int32_t cap,
                                                                    size_t lds) {
-            hipLaunchKernelGGL(k_rep_perm_test, dim3((uint32_t)(m * n_tiles)), dim3(REP_THREADS), lds, c->stream,
-                               s->m_bits.as<unsigned long long>(), s->m_count, n_tiles, recs, s->p_roff.as<int64_t>(),
+            hipLaunchKernelGGL(k_rep_perm_test, dim3((uint32_t)(m * k.n_tiles)), dim3(REP_THREADS), lds, c->stream,
+                               s->m_bits.as<unsigned long long>(), k.p_count, k.n_tiles, recs, s->p_roff.as<int64_t>(),
                                s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->p_a0.as<int64_t>(),
                                cap, s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
         });
@@ -1669,20 +1743,17 @@ int scape_hip_report_perm_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *re
                               const double *w, const double *tol, int64_t *t_out, int64_t *a0_out, double *delta0_out,
                               int64_t *n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->m_count : 0, "scape_hip_report_perm_masks")) return 1;
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    if (rep_perm_prepare(c, s->m_n1 + s->m_n2, s->m_count, "masks", s->m_n1, 0, nullptr, n_rec, rec_row_off, rows, t_out,
-                         a0_out, w && tol && delta0_out && n_ge_out, REP_LEN_MAX_ROWS, w, tol, nullptr, nullptr, &n_rows,
-                         &n_tiles))
-        return 1;
-    if (s->l_w.ensure(n_rows * 8) || s->l_tol.ensure((int64_t)n_rec * 8)) return 1;
-    return rep_perm_count(c, 0, n_rec, nullptr, n_ge_out, delta0_out, [&]() -> int {
-        HIPCHK(hipMemcpyAsync(s->l_w.p, w, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    ReportState *s = report_state(c);
+    if (s->masks.ready(s->n_cnt_rows)) return 1;
+    RepPermCall k(c, s->masks, n_rec, rec_row_off, rows, t_out);
+    k.a0_out = a0_out, k.n1 = s->m_n1, k.max_rec_rows = REP_LEN_MAX_ROWS, k.w = w, k.tol = tol;
+    k.outs_ok = w && tol && delta0_out && n_ge_out;
+    if (rep_perm_prepare(c, k) || s->l_w.ensure(k.n_rows * 8) || s->l_tol.ensure((int64_t)n_rec * 8)) return 1;
+    return rep_perm_count(c, k, 0, n_rec, nullptr, n_ge_out, delta0_out, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(s->l_w.p, w, k.n_rows * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(s->l_tol.p, tol, (int64_t)n_rec * 8, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_rep_perm_len, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), 0, c->stream,
-                           s->m_bits.as<unsigned long long>(), s->m_count, n_tiles, s->p_roff.as<int64_t>(),
+        hipLaunchKernelGGL(k_rep_perm_len, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), 0, c->stream,
+                           s->m_bits.as<unsigned long long>(), k.p_count, k.n_tiles, s->p_roff.as<int64_t>(),
                            s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->p_a0.as<int64_t>(),
                            s->l_w.as<double>(), s->l_tol.as<double>(), s->p_gene.as<int32_t>(),
                            s->p_stat0.as<double>());
@@ -1701,36 +1772,32 @@ int scape_hip_report_perm_labels(scape_hip_ctx *c, int32_t n_groups, const int32
     for (int32_t g = 0; g < n_groups; ++g) n += sizes[g];
     if (rep_perm_chunk_ok(n, "the groups' cells must number", p_first, p_count)) return 1;
     ReportState *s = report_state(c);
-    s->q_count = 0;
     std::vector<int32_t> rank_of_cut(n_groups - 1);
     int32_t below = 0;
     for (int32_t h = 0; h + 1 < n_groups; ++h) {
         below += sizes[h];
         rank_of_cut[h] = below - 1;
     }
+    s->labels.count = 0;
+    StreamDrain drain(c->stream);
     if (s->q_lab.ensure((int64_t)p_count * n) || s->q_cut.ensure((int64_t)(n_groups - 1) * 4)) return 1;
     HIPCHK(hipMemcpyAsync(s->q_cut.p, rank_of_cut.data(), (int64_t)(n_groups - 1) * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_rep_perm_labels, dim3(p_count), dim3(REP_THREADS), 0, c->stream, n_groups,
                        s->q_cut.as<int32_t>(), (int32_t)n, (unsigned long long)p_first, p_count,
                        (unsigned long long)seed, s->q_lab.as<uint8_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    s->q_sizes.assign(sizes, sizes + n_groups);
-    s->q_n = (int32_t)n;
-    s->q_count = p_count;
-    return 0;
+    s->labels.sizes.assign(sizes, sizes + n_groups);
+    return rep_built(drain, s->labels, n, p_count);
 }
 
 int scape_hip_report_perm_labels_get(scape_hip_ctx *c, int32_t p, uint8_t *labels_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->q_count) return fail("scape_hip_report_perm_labels has not been called");
-    if (!labels_out) return fail("bad argument");
-    if (p < 0 || p >= s->q_count) return fail("p must name a permutation of the last labels call");
-    HIPCHK(hipMemcpy2DAsync(labels_out, 1, s->q_lab.as<uint8_t>() + p, (size_t)s->q_count, 1, (size_t)s->q_n,
+    ReportState *s = report_state(c);
+    const RepLabellings &l = s->labels;
+    if (rep_get_ok(l, labels_out, nullptr, p)) return 1;
+    StreamDrain drain(c->stream);
+    HIPCHK(hipMemcpy2DAsync(labels_out, 1, s->q_lab.as<uint8_t>() + p, (size_t)l.count, 1, (size_t)l.n,
                             hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return drain.wait();
 }
 
 int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -1738,23 +1805,22 @@ int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t 
                                  int64_t *site_n_ge_out, double *stat0_out, double *site_stat0_out,
                                  int64_t *gene_n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->q_count : 0, "scape_hip_report_perm_labels")) return 1;
+    ReportState *s = report_state(c);
+    if (s->labels.ready(s->n_cnt_rows)) return 1;
     if (n_rec <= 0 || !rec_row_off) return fail("bad argument");   // what the check of the rounding bound reads
-    if (rep_groups_match(s->q_sizes, "scape_hip_report_perm_labels", n_groups, seg_off)) return 1;
+    if (rep_groups_match(s->labels, n_groups, seg_off)) return 1;
     for (int r = 0; r < n_rec; ++r)
         if (rec_row_off[r + 1] - rec_row_off[r] + n_groups > REP_GROUPS_MAX_ROWS_AND_GROUPS)
             return fail("record " + std::to_string(r) + ": " + std::to_string(rec_row_off[r + 1] - rec_row_off[r]) +
                         " rows and " + std::to_string(n_groups) + " groups, together more than " +
                         std::to_string(REP_GROUPS_MAX_ROWS_AND_GROUPS) + " (the rounding bound of the statistic)");
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    if (rep_perm_prepare(c, s->q_n, s->q_count, "labels", 0, n_groups, seg_off, n_rec, rec_row_off, rows, t_out, a0_out,
-                         site_n_ge_out && stat0_out && site_stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr,
-                         nullptr, &n_rows, &n_tiles))
-        return 1;
+    RepPermCall k(c, s->labels, n_rec, rec_row_off, rows, t_out);
+    k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off;
+    k.outs_ok = site_n_ge_out && stat0_out && site_stat0_out && gene_n_ge_out;
+    if (rep_perm_prepare(c, k)) return 1;
+    const int64_t n_rows = k.n_rows;
     if (s->q_s0.ensure(n_rows * 8) || s->q_share.ensure(n_rows * 8)) return 1;
-    return rep_perm_count(c, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
+    return rep_perm_count(c, k, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
         hipLaunchKernelGGL(k_rep_groups_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream,
                            s->p_roff.as<int64_t>(), s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_groups,
                            s->q_s0.as<double>(), s->q_share.as<double>(), s->p_stat0.as<double>());
@@ -1762,8 +1828,8 @@ int scape_hip_report_perm_groups(scape_hip_ctx *c, int32_t n_rec, const int64_t 
         const size_t lds = (size_t)2 * n_groups * REP_THREADS * 4;   // above 64 KiB a kernel needs the attribute
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_groups),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * REP_GROUPS_MAX * REP_THREADS * 4));
-        hipLaunchKernelGGL(k_rep_perm_groups, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), lds,
-                           c->stream, s->q_lab.as<uint8_t>(), s->q_count, n_tiles, n_groups, s->p_roff.as<int64_t>(),
+        hipLaunchKernelGGL(k_rep_perm_groups, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), lds,
+                           c->stream, s->q_lab.as<uint8_t>(), k.p_count, k.n_tiles, n_groups, s->p_roff.as<int64_t>(),
                            s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->q_s0.as<double>(),
                            s->p_stat0.as<double>(), s->p_site.as<int32_t>(), s->p_gene.as<int32_t>());
         HIPCHK(hipGetLastError());
@@ -1777,30 +1843,23 @@ int scape_hip_report_perm_len_groups(scape_hip_ctx *c, int32_t n_rec, const int6
                                      const double *tol_delta, int64_t *t_out, int64_t *a0_out, double *stat0_out,
                                      double *delta0_out, int64_t *n_ge_out, int64_t *group_n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->q_count : 0, "scape_hip_report_perm_labels")) return 1;
-    if (rep_groups_match(s->q_sizes, "scape_hip_report_perm_labels", n_groups, seg_off)) return 1;
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    if (rep_perm_prepare(c, s->q_n, s->q_count, "labels", 0, n_groups, seg_off, n_rec, rec_row_off, rows, t_out, a0_out,
-                         q && tol_stat && tol_delta && stat0_out && delta0_out && n_ge_out && group_n_ge_out, 0, nullptr,
-                         tol_stat, tol_delta, q, &n_rows, &n_tiles))
-        return 1;
-    const int64_t n_pairs = (int64_t)n_rec * n_groups;
+    ReportState *s = report_state(c);
+    if (s->labels.ready(s->n_cnt_rows) || rep_groups_match(s->labels, n_groups, seg_off)) return 1;
+    RepPermCall k(c, s->labels, n_rec, rec_row_off, rows, t_out);
+    k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off, k.tol = tol_stat, k.tol2 = tol_delta, k.q = q;
+    k.outs_ok = q && tol_stat && tol_delta && stat0_out && delta0_out && n_ge_out && group_n_ge_out;
+    if (rep_perm_prepare(c, k)) return 1;
+    const int64_t n_rows = k.n_rows, n_pairs = (int64_t)n_rec * n_groups;
     if (s->v_q.ensure(n_rows * 4) || s->v_tol.ensure((int64_t)n_rec * 16) || s->v_qt.ensure((int64_t)n_rec * 16) ||
         s->v_mean.ensure((int64_t)n_rec * 8) || s->v_d0.ensure(n_pairs * 8))
         return 1;
-    std::vector<double> tol((size_t)n_rec * 2);       // alive until rep_perm_count has waited for the stream
-    for (int r = 0; r < n_rec; ++r) {
-        tol[2 * (size_t)r] = tol_stat[r];
-        tol[2 * (size_t)r + 1] = tol_delta[r];
-    }
+    for (int r = 0; r < n_rec; ++r) k.tols.insert(k.tols.end(), {tol_stat[r], tol_delta[r]});
     // equal slices of at most REP_LEN_GROUPS_SLICE groups: 33 groups take 17 + 16, not 32 + 1
     const int32_t n_slices = (n_groups + REP_LEN_GROUPS_SLICE - 1) / REP_LEN_GROUPS_SLICE;
     const int32_t slice = (n_groups + n_slices - 1) / n_slices;
-    return rep_perm_count(c, n_pairs, n_rec, group_n_ge_out, n_ge_out, stat0_out, [&]() -> int {
+    return rep_perm_count(c, k, n_pairs, n_rec, group_n_ge_out, n_ge_out, stat0_out, [&]() -> int {
         HIPCHK(hipMemcpyAsync(s->v_q.p, q, n_rows * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(s->v_tol.p, tol.data(), (int64_t)n_rec * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(s->v_tol.p, k.tols.data(), (int64_t)n_rec * 16, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_rep_len_groups_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream,
                            s->p_roff.as<int64_t>(), s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_groups,
                            s->v_q.as<int32_t>(), s->v_qt.as<long long>(), s->v_mean.as<double>(), s->v_d0.as<double>(),
@@ -1810,8 +1869,8 @@ int scape_hip_report_perm_len_groups(scape_hip_ctx *c, int32_t n_rec, const int6
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rep_perm_len_groups),
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                    REP_LEN_GROUPS_SLICE * REP_THREADS * 12));
-        hipLaunchKernelGGL(k_rep_perm_len_groups, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), lds,
-                           c->stream, s->q_lab.as<uint8_t>(), s->q_count, n_tiles, n_groups, slice,
+        hipLaunchKernelGGL(k_rep_perm_len_groups, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), lds,
+                           c->stream, s->q_lab.as<uint8_t>(), k.p_count, k.n_tiles, n_groups, slice,
                            s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->v_q.as<int32_t>(),
                            s->v_qt.as<long long>(), s->v_mean.as<double>(), s->v_d0.as<double>(),
                            s->p_stat0.as<double>(), s->v_tol.as<double>(), s->p_site.as<int32_t>(),
@@ -1845,7 +1904,8 @@ int scape_hip_report_perm_pair_masks(scape_hip_ctx *c, int32_t n_groups, const i
         if (words > INT32_MAX) return fail("the pairs' mask words together must number below 2^31");
     }
     ReportState *s = report_state(c);
-    s->x_count = 0;
+    s->pair_masks.count = 0;
+    StreamDrain drain(c->stream);
     if (s->x_bits.ensure(words * p_count * 8) || s->x_bound.ensure((int64_t)n_pairs * p_count * 8) ||
         s->x_desc.ensure((int64_t)n_pairs * 32))
         return 1;
@@ -1853,27 +1913,25 @@ int scape_hip_report_perm_pair_masks(scape_hip_ctx *c, int32_t n_groups, const i
     hipLaunchKernelGGL(k_rep_perm_pair_masks, dim3(p_count, n_pairs), dim3(REP_THREADS), 0, c->stream,
                        s->x_desc.as<RepPair>(), (unsigned long long)p_first, p_count, (unsigned long long)seed,
                        s->x_bound.as<unsigned long long>(), s->x_bits.as<unsigned long long>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    s->x_pairs.swap(pairs);
-    s->x_sizes.assign(sizes, sizes + n_groups);
-    s->x_count = p_count;
-    return 0;
+    s->pair_masks.sizes.assign(sizes, sizes + n_groups);
+    int64_t n_all = 0;                       // the positions of a test on these masks: every group's cells
+    for (int32_t g = 0; g < n_groups; ++g) n_all += sizes[g];
+    s->x_pairs.swap(pairs);                  // the upload reads them where they now live
+    return rep_built(drain, s->pair_masks, n_all, p_count);
 }
 
 int scape_hip_report_perm_pair_bits_get(scape_hip_ctx *c, int32_t pair, int32_t p, uint64_t *words_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->x_count) return fail("scape_hip_report_perm_pair_masks has not been called");
-    if (!words_out) return fail("bad argument");
-    if (pair < 0 || pair >= (int32_t)(s->x_pairs.size() / 8)) return fail("pair must name a pair of the last pair masks call");
-    if (p < 0 || p >= s->x_count) return fail("p must name a permutation of the last pair masks call");
+    ReportState *s = report_state(c);
+    const RepLabellings &l = s->pair_masks;
+    const bool pair_ok = pair >= 0 && pair < (int32_t)(s->x_pairs.size() / 8);
+    if (rep_get_ok(l, words_out, pair_ok ? nullptr : "pair must name a pair of the last pair masks call", p)) return 1;
     const int32_t *d = &s->x_pairs[(size_t)pair * 8];
     const int32_t n_words = (d[2] + d[3] + 63) / 64;
-    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->x_bits.as<unsigned long long>() + (int64_t)d[4] * s->x_count + p,
-                            (size_t)s->x_count * 8, 8, n_words, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    StreamDrain drain(c->stream);
+    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->x_bits.as<unsigned long long>() + (int64_t)d[4] * l.count + p,
+                            (size_t)l.count * 8, 8, n_words, hipMemcpyDeviceToHost, c->stream));
+    return drain.wait();
 }
 
 int scape_hip_report_perm_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -1881,42 +1939,28 @@ int scape_hip_report_perm_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *
                                 int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                 int64_t *gene_n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->x_count : 0, "scape_hip_report_perm_pair_masks")) return 1;
-    if (rep_groups_match(s->x_sizes, "scape_hip_report_perm_pair_masks", n_groups, seg_off)) return 1;
-    const int32_t n_pairs = (int32_t)(s->x_pairs.size() / 8);
-    if (pair_first < 0 || pair_count < 1 || pair_first > n_pairs - pair_count)
-        return fail("pair_first and pair_count must name pairs of the last scape_hip_report_perm_pair_masks call");
-    if (n_rec > 0 && rec_row_off && ((int64_t)pair_count * n_rec > INT32_MAX ||
-                                     rec_row_off[n_rec] > INT64_MAX / 8 / pair_count))
-        return fail("too many pairs x records or pairs x rows for one call: take the pairs in ranges");
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    if (rep_perm_prepare(c, seg_off[n_groups], s->x_count, "pair masks", 0, n_groups, seg_off, n_rec, rec_row_off, rows,
-                         t_out, a0_out, site_n_ge_out && stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr,
-                         nullptr, &n_rows, &n_tiles))
-        return 1;
-    const int64_t n_seg = n_rows * (n_groups + 1), n_out = (int64_t)pair_count * n_rec;
-    if ((n_seg + REP_THREADS - 1) / REP_THREADS > INT32_MAX) return fail("too many rows x groups for one call");
-    if (s->p_recs.ensure((int64_t)n_rec * 4) || s->x_seg.ensure(n_seg * 8) || s->p_gene.ensure(n_out * 4) ||
-        s->p_stat0.ensure(n_out * 8))
-        return 1;
-    const RepPermClasses cl = rep_perm_classes(n_rec, rec_row_off);      // on the rows kept over all groups
-    return rep_perm_count(c, pair_count * n_rows, (int32_t)n_out, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
-        hipLaunchKernelGGL(k_rep_pair_segidx, dim3((uint32_t)((n_seg + REP_THREADS - 1) / REP_THREADS)),
-                           dim3(REP_THREADS), 0, c->stream, s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
-                           s->q_seg.as<int32_t>(), n_groups, n_rows, s->x_seg.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        return rep_perm_launch_classes(c, cl, k_rep_perm_pairs, [&](const int32_t *recs, int64_t m, int32_t cap,
-                                                                    size_t lds) {
-            hipLaunchKernelGGL(k_rep_perm_pairs, dim3((uint32_t)(m * n_tiles), (uint32_t)pair_count), dim3(REP_THREADS),
-                               lds, c->stream, s->x_bits.as<unsigned long long>(), s->x_count, n_tiles, recs,
+    ReportState *s = report_state(c);
+    return rep_perm_ranged(
+        c, s->pair_masks, "pair", (int32_t)(s->x_pairs.size() / 8), pair_first, pair_count, n_rec, rec_row_off, rows,
+        n_groups, seg_off, t_out, a0_out, site_n_ge_out, stat0_out, gene_n_ge_out, k_rep_perm_pairs,
+        [&](const RepPermCall &k) -> int {   // per kept row and group the first nonzero of the group's segment
+            const int64_t n_seg = k.n_rows * (n_groups + 1);
+            if ((n_seg + REP_THREADS - 1) / REP_THREADS > INT32_MAX) return fail("too many rows x groups for one call");
+            if (s->x_seg.ensure(n_seg * 8)) return 1;
+            hipLaunchKernelGGL(k_rep_pair_segidx, dim3((uint32_t)((n_seg + REP_THREADS - 1) / REP_THREADS)),
+                               dim3(REP_THREADS), 0, c->stream, s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
+                               s->q_seg.as<int32_t>(), n_groups, k.n_rows, s->x_seg.as<int64_t>());
+            HIPCHK(hipGetLastError());
+            return 0;
+        },
+        [&](const RepPermCall &k, const int32_t *recs, int64_t m, int32_t cap, size_t lds) {
+            hipLaunchKernelGGL(k_rep_perm_pairs, dim3((uint32_t)(m * k.n_tiles), (uint32_t)pair_count), dim3(REP_THREADS),
+                               lds, c->stream, s->x_bits.as<unsigned long long>(), k.p_count, k.n_tiles, recs,
                                s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
                                s->q_a0.as<int64_t>(), n_groups, s->q_seg.as<int32_t>(),
-                               s->x_desc.as<RepPair>() + pair_first, n_rows, n_rec, cap, s->p_site.as<int32_t>(),
+                               s->x_desc.as<RepPair>() + pair_first, k.n_rows, n_rec, cap, s->p_site.as<int32_t>(),
                                s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
         });
-    });
 }
 
 int scape_hip_report_perm_marker_masks(scape_hip_ctx *c, int32_t n_markers, const int32_t *sizes, int32_t n_others,
@@ -1949,7 +1993,8 @@ int scape_hip_report_perm_marker_masks(scape_hip_ctx *c, int32_t n_markers, cons
     const int64_t n_words = (n + 63) / 64, words = n_words * n_markers;
     if (words > INT32_MAX) return fail("the markers' mask words together must number below 2^31");
     ReportState *s = report_state(c);
-    s->k_count = 0;
+    s->marker_masks.count = 0;
+    StreamDrain drain(c->stream);
     if (s->k_bits.ensure(words * p_count * 8) || s->k_bound.ensure((int64_t)n_markers * p_count * 8) ||
         s->k_seg.ensure(((int64_t)n_markers + 2) * 4) || s->k_rank.ensure(n * 4))
         return 1;
@@ -1959,29 +2004,23 @@ int scape_hip_report_perm_marker_masks(scape_hip_ctx *c, int32_t n_markers, cons
                        s->k_seg.as<int32_t>(), s->k_rank.as<int32_t>(), (int32_t)n, (unsigned long long)p_first, p_count,
                        (unsigned long long)seed, s->k_bound.as<unsigned long long>(),
                        s->k_bits.as<unsigned long long>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    s->k_sizes.assign(sizes, sizes + n_markers);
-    s->k_sizes.push_back(n_others);
-    s->k_count = p_count;
-    return 0;
+    s->marker_masks.sizes.assign(sizes, sizes + n_markers);
+    s->marker_masks.sizes.push_back(n_others);
+    return rep_built(drain, s->marker_masks, n, p_count);
 }
 
 int scape_hip_report_perm_marker_bits_get(scape_hip_ctx *c, int32_t marker, int32_t p, uint64_t *words_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->k_count) return fail("scape_hip_report_perm_marker_masks has not been called");
-    if (!words_out) return fail("bad argument");
-    if (marker < 0 || marker >= (int32_t)s->k_sizes.size() - 1)
-        return fail("marker must name a marker of the last marker masks call");
-    if (p < 0 || p >= s->k_count) return fail("p must name a permutation of the last marker masks call");
-    int64_t n = 0;
-    for (const int32_t m : s->k_sizes) n += m;
-    const int64_t n_words = (n + 63) / 64;
-    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->k_bits.as<unsigned long long>() + marker * n_words * s->k_count + p,
-                            (size_t)s->k_count * 8, 8, (size_t)n_words, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    ReportState *s = report_state(c);
+    const RepLabellings &l = s->marker_masks;
+    const bool marker_ok = marker >= 0 && marker < (int32_t)l.sizes.size() - 1;
+    if (rep_get_ok(l, words_out, marker_ok ? nullptr : "marker must name a marker of the last marker masks call", p))
+        return 1;
+    const int64_t n_words = ((int64_t)l.n + 63) / 64;
+    StreamDrain drain(c->stream);
+    HIPCHK(hipMemcpy2DAsync(words_out, 8, s->k_bits.as<unsigned long long>() + marker * n_words * l.count + p,
+                            (size_t)l.count * 8, 8, (size_t)n_words, hipMemcpyDeviceToHost, c->stream));
+    return drain.wait();
 }
 
 int scape_hip_report_perm_markers(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -1989,36 +2028,19 @@ int scape_hip_report_perm_markers(scape_hip_ctx *c, int32_t n_rec, const int64_t
                                   int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                   int64_t *gene_n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->k_count : 0, "scape_hip_report_perm_marker_masks")) return 1;
-    if (rep_groups_match(s->k_sizes, "scape_hip_report_perm_marker_masks", n_seg, seg_off)) return 1;
-    const int32_t n_markers = n_seg - 1;
-    if (marker_first < 0 || marker_count < 1 || marker_first > n_markers - marker_count)
-        return fail("marker_first and marker_count must name markers of the last scape_hip_report_perm_marker_masks call");
-    if (n_rec > 0 && rec_row_off && ((int64_t)marker_count * n_rec > INT32_MAX ||
-                                     rec_row_off[n_rec] > INT64_MAX / 8 / marker_count))
-        return fail("too many markers x records or markers x rows for one call: take the markers in ranges");
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    const int32_t n = seg_off[n_seg];
-    if (rep_perm_prepare(c, n, s->k_count, "marker masks", 0, n_seg, seg_off, n_rec, rec_row_off, rows, t_out, a0_out,
-                         site_n_ge_out && stat0_out && gene_n_ge_out, 0, nullptr, nullptr, nullptr, nullptr, &n_rows,
-                         &n_tiles))
-        return 1;
-    const int64_t n_out = (int64_t)marker_count * n_rec;
-    if (s->p_recs.ensure((int64_t)n_rec * 4) || s->p_gene.ensure(n_out * 4) || s->p_stat0.ensure(n_out * 8)) return 1;
-    const RepPermClasses cl = rep_perm_classes(n_rec, rec_row_off);
-    return rep_perm_count(c, marker_count * n_rows, (int32_t)n_out, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
-        return rep_perm_launch_classes(c, cl, k_rep_perm_markers, [&](const int32_t *recs, int64_t m, int32_t cap,
-                                                                      size_t lds) {
-            hipLaunchKernelGGL(k_rep_perm_markers, dim3((uint32_t)(m * n_tiles), (uint32_t)marker_count),
-                               dim3(REP_THREADS), lds, c->stream, s->k_bits.as<unsigned long long>(), s->k_count, n_tiles,
-                               (n + 63) / 64, recs, s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(),
+    ReportState *s = report_state(c);
+    return rep_perm_ranged(
+        c, s->marker_masks, "marker", n_seg - 1, marker_first, marker_count, n_rec, rec_row_off, rows, n_seg, seg_off,
+        t_out, a0_out, site_n_ge_out, stat0_out, gene_n_ge_out, k_rep_perm_markers,
+        [](const RepPermCall &) -> int { return 0; },
+        [&](const RepPermCall &k, const int32_t *recs, int64_t m, int32_t cap, size_t lds) {
+            hipLaunchKernelGGL(k_rep_perm_markers, dim3((uint32_t)(m * k.n_tiles), (uint32_t)marker_count),
+                               dim3(REP_THREADS), lds, c->stream, s->k_bits.as<unsigned long long>(), k.p_count,
+                               k.n_tiles, (k.n + 63) / 64, recs, s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(),
                                s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_seg, marker_first,
-                               n_rows, n_rec, cap, s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(),
+                               k.n_rows, n_rec, cap, s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(),
                                s->p_stat0.as<double>());
         });
-    });
 }
 
 int scape_hip_report_perm_scores(scape_hip_ctx *c, int32_t n, const uint16_t *q, int64_t p_first, int32_t p_count,
@@ -2033,7 +2055,8 @@ int scape_hip_report_perm_scores(scape_hip_ctx *c, int32_t n, const uint16_t *q,
         qspan = std::max<int32_t>(qspan, q[j]);
     }
     ReportState *s = report_state(c);
-    s->t_count = 0;
+    s->scores.count = 0;
+    StreamDrain drain(c->stream);
     int32_t bits = 0;                        // B = 2^bits: the smallest power of two that reaches n, within the limits
     while ((1 << bits) < REP_SCORE_MIN_BUCKETS || ((1 << bits) < n && (1 << bits) < REP_SCORE_MAX_BUCKETS)) ++bits;
     // a halfword per (position, permutation), and one scratch slice of n int32 per permutation of the chunk
@@ -2047,58 +2070,47 @@ int scape_hip_report_perm_scores(scape_hip_ctx *c, int32_t n, const uint16_t *q,
     hipLaunchKernelGGL(k_rep_perm_scores, dim3(p_count), dim3(REP_THREADS), ((size_t)4 << bits) + REP_WAVES * 4, c->stream, n, bits,
                        s->t_q.as<uint16_t>(), (unsigned long long)p_first, p_count, (unsigned long long)seed,
                        s->t_members.as<int32_t>(), s->t_scores.as<uint16_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    s->t_n = n;
     s->t_qspan = qspan;
-    s->t_count = p_count;
-    return 0;
+    return rep_built(drain, s->scores, n, p_count);
 }
 
 int scape_hip_report_perm_scores_get(scape_hip_ctx *c, int32_t p, uint16_t *scores_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->t_count) return fail("scape_hip_report_perm_scores has not been called");
-    if (!scores_out) return fail("bad argument");
-    if (p < 0 || p >= s->t_count) return fail("p must name a permutation of the last scores call");
+    ReportState *s = report_state(c);
+    const RepLabellings &l = s->scores;
+    if (rep_get_ok(l, scores_out, nullptr, p)) return 1;
+    StreamDrain drain(c->stream);
     // the builder's scratch (4 n bytes per permutation) is idle between two scores calls: the column is gathered there
-    hipLaunchKernelGGL(k_rep_scores_column, dim3((uint32_t)((s->t_n + REP_THREADS - 1) / REP_THREADS)), dim3(REP_THREADS),
-                       0, c->stream, s->t_scores.as<uint16_t>(), s->t_n, s->t_count, p, s->t_members.as<uint16_t>());
+    hipLaunchKernelGGL(k_rep_scores_column, dim3((uint32_t)((l.n + REP_THREADS - 1) / REP_THREADS)), dim3(REP_THREADS),
+                       0, c->stream, s->t_scores.as<uint16_t>(), l.n, l.count, p, s->t_members.as<uint16_t>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(scores_out, s->t_members.p, (int64_t)s->t_n * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    HIPCHK(hipMemcpyAsync(scores_out, s->t_members.p, (int64_t)l.n * 2, hipMemcpyDeviceToHost, c->stream));
+    return drain.wait();
 }
 
 int scape_hip_report_perm_trend(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                                 int64_t *t_out, int64_t *s0_out, int64_t *sq0_out, int64_t *site_n_ge_out,
                                 double *d0_out, double *stat0_out, int64_t *gene_n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->t_count : 0, "scape_hip_report_perm_scores")) return 1;
-    if (n_rec <= 0 || !rec_row_off || !rows) return fail("bad argument");
-    const int64_t n_all = rec_row_off[n_rec];
-    if (n_all <= 0 || n_all > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
-    // one segment [0, n): the row's sum over it restates t, and lands in a buffer of the call's own
-    std::vector<int64_t> a0((size_t)n_all);
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    if (rep_perm_prepare(c, s->t_n, s->t_count, "scores", s->t_n, 0, nullptr, n_rec, rec_row_off, rows, t_out, a0.data(),
-                         s0_out && sq0_out && site_n_ge_out && d0_out && stat0_out && gene_n_ge_out, REP_TREND_MAX_ROWS,
-                         nullptr, nullptr, nullptr, nullptr, &n_rows, &n_tiles))
-        return 1;
+    ReportState *s = report_state(c);
+    if (s->scores.ready(s->n_cnt_rows)) return 1;
+    RepPermCall k(c, s->scores, n_rec, rec_row_off, rows, t_out);
+    k.outs_ok = s0_out && sq0_out && site_n_ge_out && d0_out && stat0_out && gene_n_ge_out;
+    k.max_rec_rows = REP_TREND_MAX_ROWS;
+    if (rep_trend_prepare(c, k)) return 1;
+    const int64_t n_rows = k.n_rows;
     if (s->t_s0.ensure(n_rows * 8) || s->t_sq0.ensure(n_rows * 8) || s->v_qt.ensure((int64_t)n_rec * 16) ||
         s->v_tol.ensure((int64_t)n_rec * 16) || s->v_d0.ensure(n_rows * 8))
         return 1;
-    return rep_perm_count(c, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
+    return rep_perm_count(c, k, n_rows, n_rec, site_n_ge_out, gene_n_ge_out, stat0_out, [&]() -> int {
         hipLaunchKernelGGL(k_rep_trend_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream,
                            s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(),
                            s->t_q.as<uint16_t>(), s->t_qspan, s->t_s0.as<long long>(), s->t_sq0.as<long long>(),
                            s->v_qt.as<long long>(), s->v_tol.as<double>(), s->v_d0.as<double>(),
                            s->p_stat0.as<double>());
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_rep_perm_trend, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), 0,
-                           c->stream, s->t_scores.as<uint16_t>(), s->t_count, n_tiles, s->p_roff.as<int64_t>(),
+        hipLaunchKernelGGL(k_rep_perm_trend, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), 0,
+                           c->stream, s->t_scores.as<uint16_t>(), k.p_count, k.n_tiles, s->p_roff.as<int64_t>(),
                            s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->v_qt.as<long long>(),
                            s->v_tol.as<double>(), s->v_d0.as<double>(), s->p_stat0.as<double>(),
                            s->p_site.as<int32_t>(), s->p_gene.as<int32_t>());
@@ -2114,20 +2126,12 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
                                     const int32_t *x, int64_t *t_out, int64_t *s0_out, int64_t *sq0_out,
                                     int64_t *c0_out, int64_t *n_ge_out) {
     CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (rep_perm_ready(s, s ? s->t_count : 0, "scape_hip_report_perm_scores")) return 1;
-    if (n_rec <= 0 || !rec_row_off || !rows) return fail("bad argument");
-    const int64_t n_all = rec_row_off[n_rec];
-    if (n_all <= 0 || n_all > INT32_MAX) return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
-    // one segment [0, n): the row's sum over it restates t, and lands in a buffer of the call's own
-    std::vector<int64_t> a0((size_t)n_all);
-    int64_t n_rows = 0;
-    int32_t n_tiles = 0;
-    if (rep_perm_prepare(c, s->t_n, s->t_count, "scores", s->t_n, 0, nullptr, n_rec, rec_row_off, rows, t_out, a0.data(),
-                         x && s0_out && sq0_out && c0_out && n_ge_out, 0, nullptr, nullptr, nullptr, x, &n_rows, &n_tiles))
-        return 1;
-    // T < 2^31 holds (rep_perm_prepare); T max x < 2^48 keeps Sxz, at scores of up to 2^15, below 2^63.  The row sums
-    // are back and nothing of the test is queued yet
+    ReportState *s = report_state(c);
+    if (s->scores.ready(s->n_cnt_rows)) return 1;
+    RepPermCall k(c, s->scores, n_rec, rec_row_off, rows, t_out);
+    k.q = x, k.outs_ok = x && s0_out && sq0_out && c0_out && n_ge_out;
+    if (rep_trend_prepare(c, k)) return 1;
+    // T < 2^31 holds (rep_perm_prepare); T max x < 2^48 keeps Sxz, at scores of up to 2^15, below 2^63
     for (int r = 0; r < n_rec; ++r) {
         int64_t T = 0, max_x = 0;
         for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) {
@@ -2137,21 +2141,21 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
         if (T * max_x >= REP_LEN_TREND_MAX_TX)
             return fail("record " + std::to_string(r) + ": reads x largest position must stay below 2^48");
     }
+    const int64_t n_rows = k.n_rows;
     if (s->t_s0.ensure(n_rows * 8) || s->t_sq0.ensure(n_rows * 8) || s->v_q.ensure(n_rows * 4) ||
         s->t_lrec.ensure((int64_t)n_rec * REP_LEN_TREND_REC * 8))
         return 1;
-    // the target of a copy queued below: rep_perm_count waits for the stream before it returns 0; where it returns early,
-    // the wait is made here, before rec goes
-    std::vector<int64_t> rec((size_t)n_rec * REP_LEN_TREND_REC);
-    if (rep_perm_count(c, 0, n_rec, nullptr, n_ge_out, nullptr, [&]() -> int {
+    std::vector<int64_t> &rec = k.lrec;               // T, Sx, Sz(0), Sxz(0) and the halves of C(0) per record
+    rec.resize((size_t)n_rec * REP_LEN_TREND_REC);
+    if (rep_perm_count(c, k, 0, n_rec, nullptr, n_ge_out, nullptr, [&]() -> int {
             HIPCHK(hipMemcpyAsync(s->v_q.p, x, n_rows * 4, hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(k_rep_len_trend_obs, dim3((uint32_t)n_rec), dim3(REP_THREADS), 0, c->stream,
                                s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
                                s->p_t.as<int64_t>(), s->v_q.as<int32_t>(), s->t_q.as<uint16_t>(),
                                s->t_s0.as<long long>(), s->t_sq0.as<long long>(), s->t_lrec.as<long long>());
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_rep_perm_len_trend, dim3((uint32_t)((int64_t)n_rec * n_tiles)), dim3(REP_THREADS), 0,
-                               c->stream, s->t_scores.as<uint16_t>(), s->t_count, n_tiles, s->p_roff.as<int64_t>(),
+            hipLaunchKernelGGL(k_rep_perm_len_trend, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), 0,
+                               c->stream, s->t_scores.as<uint16_t>(), k.p_count, k.n_tiles, s->p_roff.as<int64_t>(),
                                s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->v_q.as<int32_t>(),
                                s->t_lrec.as<long long>(), s->p_gene.as<int32_t>());
             HIPCHK(hipGetLastError());
@@ -2160,10 +2164,8 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
             HIPCHK(hipMemcpyAsync(rec.data(), s->t_lrec.p, (int64_t)n_rec * REP_LEN_TREND_REC * 8, hipMemcpyDeviceToHost,
                                   c->stream));
             return 0;
-        })) {
-        (void)hipStreamSynchronize(c->stream);
+        }))
         return 1;
-    }
     for (int r = 0; r < n_rec; ++r) {
         c0_out[2 * (size_t)r] = rec[(size_t)r * REP_LEN_TREND_REC + 4];
         c0_out[2 * (size_t)r + 1] = rec[(size_t)r * REP_LEN_TREND_REC + 5];

@@ -32,6 +32,19 @@
 #define REP_SCAN_THREADS 1024
 #define REP_ZERO_FIELD 6   // ,"0.0"
 
+// What a builder of perm.inc left: its entry point and its noun for messages, the positions, the permutations of the
+// chunk (0 until a call has succeeded) and, for a test on groups, their sizes.  ready() opens a test entry point
+struct RepLabellings {
+    const char *builder, *what;
+    int32_t n = 0, count = 0;
+    std::vector<int32_t> sizes;
+    int built() const { return count ? 0 : fail(std::string(builder) + " has not been called"); }
+    int ready(int64_t cnt_rows) const { return cnt_rows ? built() : fail("scape_hip_report_counts has not been called"); }
+    int holds(int32_t p) const {
+        return p >= 0 && p < count ? 0 : fail("p must name a permutation of the last " + std::string(what) + " call");
+    }
+};
+
 struct ReportState {
     // counts of the last scape_hip_report_counts call
     DevBuf r_lab, r_cb, r_off, r_K, r_rowbase, r_map, r_cnt, r_tot, r_cflag, r_err;
@@ -43,43 +56,42 @@ struct ReportState {
     int64_t h_groups = 0, h_hist_n = 0;
     // segment sums of the last scape_hip_report_group_sums call
     DevBuf g_rows, g_off, g_sum, g_nz;
-    // the permutation tests (perm.inc).  diff_pa: membership bits of the last scape_hip_report_perm_masks[_strata] call
-    // ([column word][permutation]) and the buffers of scape_hip_report_perm_test
-    DevBuf m_bits, p_rows, p_roff, p_nnz, p_noff, p_nz, p_t, p_a0, p_recs, p_site, p_gene, p_stat0;
+    // the permutation tests (perm.inc), per builder what it left.  First the buffers of rep_perm_prepare / rep_perm_count
+    DevBuf p_rows, p_roff, p_nnz, p_noff, p_nz, p_t, p_a0, p_recs, p_site, p_gene, p_stat0;
+    // diff_pa, diff_pa_len: membership bits of the last scape_hip_report_perm_masks[_strata] call ([column word]
+    // [permutation]); what they are built from: (a1, m1, a2, m2) per stratum, the strata in work order, the stratum of
+    // every position and the exclusive key bound per (permutation, stratum)
+    RepLabellings masks{"scape_hip_report_perm_masks", "masks"};
+    DevBuf m_bits, m_desc, m_order, m_strat, m_bound;
     DevBuf l_w, l_tol;                 // diff_pa_len: row weights and record tolerances of scape_hip_report_perm_len
-    int32_t m_n1 = 0, m_n2 = 0, m_count = 0;
-    // what the masks are built from: (a1, m1, a2, m2) per stratum, the strata in work order, the stratum of every
-    // position and the exclusive key bound per (permutation, stratum)
-    DevBuf m_desc, m_order, m_strat, m_bound;
     // diff_pa_groups: the group of every (position, permutation) of the last scape_hip_report_perm_labels call
     // ([position][permutation], one byte each), the ranks of its cut keys, and the buffers of
     // scape_hip_report_perm_groups that scape_hip_report_perm_test has no counterpart of
+    RepLabellings labels{"scape_hip_report_perm_labels", "labels"};
     DevBuf q_lab, q_cut, q_seg, q_a0, q_s0, q_share;
-    std::vector<int32_t> q_sizes;      // cells per group of the last labels call
     // diff_pa_len_groups: the integer row positions and (tolD, told) per record of scape_hip_report_perm_len_groups,
     // and per record (Q, T), (double)Q / (double)T and the G observed d_g
     DevBuf v_q, v_tol, v_qt, v_mean, v_d0;
-    int32_t q_n = 0, q_count = 0;
     // diff_pa_pairs: the membership bits of every (pair, permutation) of the last scape_hip_report_perm_pair_masks call
     // ([pair's word offset + word][permutation]), the exclusive key bound per (pair, permutation), (g, h, n_g, word
     // offset) per pair on the device and on the host, and per kept row and group the first nonzero at or beyond the
     // group's segment (scape_hip_report_perm_pairs)
+    RepLabellings pair_masks{"scape_hip_report_perm_pair_masks", "pair masks"};
     DevBuf x_bits, x_bound, x_desc, x_seg;
-    std::vector<int32_t> x_pairs, x_sizes;
-    int32_t x_count = 0;
+    std::vector<int32_t> x_pairs;
     // diff_pa_markers: the membership bits of every (marker, permutation) of the last scape_hip_report_perm_marker_masks
     // call ([marker * words + word][permutation], the bits in column order), the exclusive key bound per (marker,
-    // permutation), the segment offsets and the rank of every position's column on the device, and the sizes of the
+    // permutation), the segment offsets and the rank of every position's column on the device; sizes = those of the
     // markers with the number of other cells behind them
+    RepLabellings marker_masks{"scape_hip_report_perm_marker_masks", "marker masks"};
     DevBuf k_bits, k_bound, k_seg, k_rank;
-    std::vector<int32_t> k_sizes;
-    int32_t k_count = 0;
     // diff_pa_trend: the score of every (position, permutation) of the last scape_hip_report_perm_scores call
     // ([position][permutation], a halfword each), per permutation of that call the positions sorted into key buckets, the
     // observed scores, their largest, and per kept row of scape_hip_report_perm_trend s_i(0) and sum_j c_ij q_j^2;
     // diff_pa_len_trend: per record of scape_hip_report_perm_len_trend T, Sx, Sz(0), Sxz(0) and the two halves of C(0)
+    RepLabellings scores{"scape_hip_report_perm_scores", "scores"};
     DevBuf t_scores, t_members, t_q, t_s0, t_sq0, t_lrec;
-    int32_t t_n = 0, t_qspan = 0, t_count = 0;
+    int32_t m_n1 = 0, t_qspan = 0;     // population 1's cells of the masks; the largest observed score
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
@@ -98,20 +110,7 @@ static void report_release(scape_hip_ctx *c) {
         if (s->done[k]) (void)hipEventDestroy(s->done[k]);
         if (s->host_out[k]) (void)hipHostFree(s->host_out[k]);
     }
-    DevBuf *all[] = {&s->r_lab, &s->r_cb, &s->r_off, &s->r_K, &s->r_rowbase, &s->r_map, &s->r_cnt, &s->r_tot,
-                     &s->r_cflag, &s->r_err, &s->h_bits, &s->h_wpre, &s->h_nloc, &s->h_goff, &s->h_hoff, &s->h_codes,
-                     &s->h_hist, &s->s_rows[0], &s->s_rows[1], &s->s_int[0], &s->s_int[1], &s->s_poff[0],
-                     &s->s_poff[1], &s->s_pre[0], &s->s_pre[1], &s->s_len[0], &s->s_len[1], &s->s_roff[0],
-                     &s->s_roff[1], &s->s_out[0], &s->s_out[1], &s->s_nnz[0], &s->s_nnz[1], &s->s_noff[0],
-                     &s->s_noff[1], &s->g_rows, &s->g_off, &s->g_sum, &s->g_nz, &s->m_bits, &s->p_rows,
-                     &s->p_roff, &s->p_nnz, &s->p_noff, &s->p_nz, &s->p_t, &s->p_a0, &s->p_recs, &s->p_site, &s->p_gene,
-                     &s->p_stat0, &s->l_w, &s->l_tol, &s->m_desc, &s->m_order, &s->m_strat, &s->m_bound,
-                     &s->q_lab, &s->q_cut, &s->q_seg, &s->q_a0, &s->q_s0, &s->q_share, &s->v_q, &s->v_tol, &s->v_qt,
-                     &s->v_mean, &s->v_d0, &s->x_bits, &s->x_bound, &s->x_desc, &s->x_seg, &s->k_bits,
-                     &s->k_bound, &s->k_seg, &s->k_rank, &s->t_scores, &s->t_members, &s->t_q, &s->t_s0, &s->t_sq0,
-                     &s->t_lrec};
-    for (DevBuf *b : all) b->release();
-    delete s;
+    delete s;                          // every DevBuf frees itself
     c->rep = nullptr;
 }
 

@@ -703,9 +703,14 @@ __global__ __launch_bounds__(256) void k_labels(const UtrDesc *__restrict__ desc
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// owns its device memory: freed when the buffer goes, so whoever holds one by value needs no release list
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap && p) return 0;
         // a buffer that has to grow gets 1/8 headroom: successive batches of a stream differ by a few per cent in
@@ -741,6 +746,8 @@ struct DevBuf {
         return reinterpret_cast<T *>(p);
     }
 };
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value,
+              "a copy of a DevBuf would free its memory twice");
 
 struct EventPair {
     hipEvent_t a, b;
@@ -1318,6 +1325,8 @@ int scape_hip_batch_free(scape_hip_ctx *c) {
     return 0;
 }
 
+// every DevBuf of the handle must be gone or empty while the device is current and before the stream is destroyed:
+// `delete c` at the end finds nothing left to free
 int scape_hip_destroy(scape_hip_ctx *c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
@@ -1430,25 +1439,14 @@ int scape_hip_get_loglik_marginal_tensor(scape_hip_ctx *c, const double *all_the
     d.T = T;
     DevBuf dAT, dM, dth, ddesc;
     int rc = 0;
-    auto cleanup = [&]() {
-        dAT.release();
-        dM.release();
-        dth.release();
-        ddesc.release();
-    };
     if (dAT.ensure(at.size() * sizeof(double)) || dM.ensure((size_t)T * B * Np * sizeof(double)) ||
-        dth.ensure((size_t)T * sizeof(double)) || ddesc.ensure(sizeof(UtrDesc))) {
-        cleanup();
+        dth.ensure((size_t)T * sizeof(double)) || ddesc.ensure(sizeof(UtrDesc)))
         return 1;
-    }
     hipError_t e;
     e = hipMemcpyAsync(dAT.p, at.data(), at.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dth.p, all_theta, (size_t)T * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ddesc.p, &d, sizeof(d), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-        cleanup();
-        return fail(std::string("upload: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(std::string("upload: ") + hipGetErrorString(e));
     rc = launch_phase_b(c, P, 1, T, Wmax, ddesc.as<UtrDesc>(), nullptr, nullptr, dth.as<double>(), nullptr,
                         dAT.as<double>(), nullptr, dM.as<double>(), 1, nullptr);
     if (!rc) rc = check_err_flag(c, "get_loglik_marginal_tensor");
@@ -1458,7 +1456,6 @@ int scape_hip_get_loglik_marginal_tensor(scape_hip_ctx *c, const double *all_the
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(std::string("copy back: ") + hipGetErrorString(e));
     }
-    cleanup();
     return rc;
 }
 

@@ -1,7 +1,8 @@
 """``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa``,
-``scape diff_pa_len``, ``scape diff_pa_groups``, ``scape diff_pa_len_groups``, ``scape diff_pa_pairs`` and
-``scape diff_pa_markers``: the stages after ``merge_pa`` (reference ``src/scape/utils.py:319-427`` and ``:438-553``, with
-``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of ``apa_core.py:1038-1063``).
+``scape diff_pa_len``, ``scape diff_pa_groups``, ``scape diff_pa_len_groups``, ``scape diff_pa_pairs``,
+``scape diff_pa_markers``, ``scape diff_pa_trend`` and ``scape diff_pa_len_trend``: the stages after ``merge_pa``
+(reference ``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of
+``apa_core.py:1038-1063``).
 
 All of them stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
 ``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc`` and ``csrc/perm.inc``.  They
@@ -38,10 +39,14 @@ device's rendering of one text block with the gzip of the previous one.
   file, or the ones named): the same keys rank the cells, the device cuts the ranking into the populations' sizes (one
   byte per cell and permutation) and accumulates one sum per row, population and permutation in LDS (section
   diff_pa_groups below).
+* ``diff_pa_len_groups``: the omnibus form of ``diff_pa_len`` on the labellings of ``diff_pa_groups``, and every
+  population's mean pA position against all the others (section diff_pa_len_groups below).
 * ``diff_pa_pairs``: ``diff_pa`` for every pair of those populations from one pass over the result file, the p-values
   adjusted over all pairs (section diff_pa_pairs below).
 * ``diff_pa_markers``: ``diff_pa --idents_1 X`` for every cluster X against all other clustered cells from one pass
   over the result file, the p-values adjusted over all markers (section diff_pa_markers below).
+* ``diff_pa_trend`` and ``diff_pa_len_trend``: pA usage and 3'UTR length along a per-cell score such as pseudotime, by
+  permuting the scores (sections diff_pa_trend and diff_pa_len_trend below).
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -52,6 +57,7 @@ from __future__ import annotations
 
 import csv
 import ctypes
+import functools
 import io
 import math
 import os
@@ -686,6 +692,15 @@ def _check_row_sums(call, t, a0, sums, a0_sums):
         raise _lib.ScapeHipError(f"{call}: row sums differ from report_group_sums")
 
 
+def _check_exact(call, rec, what, got, exact, tol, shown=None):
+    """the device's f64 `got` lies within tol of the exact Fraction, else ScapeHipError naming call, gene and quantity:
+    what = (the quantity's name, then, where it is one of several, whose kind and which)"""
+    if not abs(Fraction(float(got)) - exact) <= tol:
+        whose = f" of {what[1]} {what[2]!r}" if len(what) > 1 else ""
+        raise _lib.ScapeHipError(f"{call}: {rec.gene_info_str}: the device's {what[0]} {got!r}{whose} differs from "
+                                 f"{shown or repr(float(exact))}")
+
+
 def _check_reads(rec, T):
     if int(T) >= 1 << 31:
         raise ValueError(f"{rec.gene_info_str}: 2^31 or more reads in the tested cells")
@@ -748,7 +763,7 @@ def _perm_chunks(ctx, su, n_perm, chunk, times, test):
         times["render"] += timer() - t0
 
 
-def _diff_pa_batch(ctx, bat, su, n_perm, chunk, lines, genes, times):
+def _diff_pa_batch(su, n_perm, lines, genes, ctx, bat, chunk, times):
     """one counted batch: the kept rows of its tested records go through the permutation test; appends the per-line
     integers to `lines` and the per-record ones to `genes`"""
     sel = _perm_rows(ctx, bat, su.seg_off, times)
@@ -923,8 +938,7 @@ def _diff_pa(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_
     lines = {k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}
     genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
 
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_batch(ctx, bat, su, n_perm, chunk, lines, genes, times)
+    batch = functools.partial(_diff_pa_batch, su, n_perm, lines, genes)
 
     def write(w):
         w.writerow(DIFF_PA_HEADER)
@@ -998,7 +1012,7 @@ def _with_span(sel, pos, times):
     return which, off, np.ascontiguousarray(rows[pick]), sums[pick], rowbase, [pos[r] for r in which.tolist()]
 
 
-def _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, out, times):
+def _diff_pa_len_batch(su, n_perm, out, ctx, bat, chunk, times):
     """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
     n_ge) per tested record to `out`"""
     recs, K = bat.recs, bat.K
@@ -1053,8 +1067,7 @@ def _diff_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file: str, ide
                      strata_file)
     out = []
 
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_len_batch(ctx, bat, su, n_perm, chunk, out, times)
+    batch = functools.partial(_diff_pa_len_batch, su, n_perm, out)
 
     def write(w):
         w.writerow(DIFF_PA_LEN_HEADER)
@@ -1181,7 +1194,7 @@ def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, s
     return su
 
 
-def _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, lines, genes, times):
+def _diff_pa_groups_batch(su, n_perm, lines, genes, ctx, bat, chunk, times):
     """one counted batch: the kept rows of its tested records go through the G-way permutation test; appends the
     per-line arrays to `lines` and (gene_info_str, lines, S(0), gene_n_ge) per tested record to `genes`"""
     sel = _perm_rows(ctx, bat, su.seg_off, times)
@@ -1224,8 +1237,7 @@ def _diff_pa_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     lines = {k: [] for k in ("pa", "a", "nz", "n_ge", "site_stat")}
     genes = []                   # (gene_info_str, lines, S(0), gene_n_ge) per tested record
 
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_groups_batch(ctx, bat, su, n_perm, chunk, lines, genes, times)
+    batch = functools.partial(_diff_pa_groups_batch, su, n_perm, lines, genes)
 
     def write(w):
         w.writerow(DIFF_PA_GROUPS_HEADER + [f"usage.{n}" for n in names] + [f"pct.{n}" for n in names])
@@ -1311,50 +1323,84 @@ def _write_diff_pa_blocks(w, header, blocks, n_perm):
         gene0 += len(c.gene_p)
 
 
-def _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, blocks, times):
-    """one counted batch: the rows kept over all populations of the records that two populations or more have reads in
-    go through every pair's test, the pairs in ranges of at most MAX_PAIR_RESULT_BYTES of counters; appends to
-    blocks[k] = (lines, genes) of pair k what _diff_pa_batch appends for the two populations of that pair"""
+def _pair_items(su, sums, nz):
+    """per pair (g, h), in the file's order: g, every row's reads in the two populations (a row that has none is not the
+    pair's, and a record of fewer than two such rows not tested) and its cells with a read in h"""
+    return [(g, sums[:, g] + sums[:, h], nz[:, h]) for g, h in zip(su.pairs[0].tolist(), su.pairs[1].tolist())]
+
+
+def _marker_items(su, sums, nz):
+    """per marker g: g, every row's reads in the tested cells and its cells with a read in the marker's rest"""
+    t, nz_all = sums.sum(axis=1), nz.astype(np.int64).sum(axis=1)
+    return [(g, t, nz_all - nz[:, g]) for g in range(len(su.sizes))]
+
+
+# what diff_pa_pairs and diff_pa_markers test in blocks, by the blocks' noun: the entry point, the cap on one call's
+# counters (read at the call) and the items
+_BLOCK_TESTS = {"pair": ("scape_hip_report_perm_pairs", lambda: MAX_PAIR_RESULT_BYTES, _pair_items),
+                "marker": ("scape_hip_report_perm_markers", lambda: MAX_MARKER_RESULT_BYTES, _marker_items)}
+
+
+def _diff_pa_blocks_batch(su, n_perm, noun, blocks, ctx, bat, chunk, times):
+    """one counted batch: the rows kept over all segments of the records that two segments or more have reads in go
+    through the test of every item (pair, marker), the items in ranges of at most the cap's bytes of counters; appends to
+    blocks[k] = (lines, genes) of item k what _diff_pa_batch appends for the item's two populations.  An item tests a
+    record when two of its rows or more have reads in the item's cells, and both of its populations have reads"""
     sel = _perm_rows(ctx, bat, su.seg_off, times)
     if sel is None:
         return
-    recs, G = bat.recs, len(su.sizes)
+    entry, cap, items = _BLOCK_TESTS[noun]
+    call = entry[len("scape_hip_"):]
+    recs, n_seg, n_items = bat.recs, len(su.seg_off) - 1, len(blocks)
     which, off, rows, nz, sums, rowbase = sel
-    pair_g, pair_h = su.pairs
-    n_pairs, n_rows, n_rec = len(pair_g), len(rows), len(which)
-    t, a0 = np.zeros(n_rows, np.int64), np.zeros((n_rows, G), np.int64)
-    site_ge, gene_ge = np.zeros((n_pairs, n_rows), np.int64), np.zeros((n_pairs, n_rec), np.int64)
-    stat0 = np.zeros((n_pairs, n_rec), np.float64)
-    step = int(max(1, min(n_pairs, MAX_PAIR_RESULT_BYTES // (12 * n_rows + 20 * n_rec))))
+    n_rows, n_rec = len(rows), len(which)
+    t, a0 = np.zeros(n_rows, np.int64), np.zeros((n_rows, n_seg), np.int64)
+    site_ge, gene_ge = np.zeros((n_items, n_rows), np.int64), np.zeros((n_items, n_rec), np.int64)
+    stat0 = np.zeros((n_items, n_rec), np.float64)
+    step = int(max(1, min(n_items, cap() // (12 * n_rows + 20 * n_rec))))
 
     def test():
-        for k in range(0, n_pairs, step):
-            m = min(step, n_pairs - k)
-            check(ctx.lib.scape_hip_report_perm_pairs(ctx.h, n_rec, ptr(off, P_i64), ptr(rows, P_i64), G,
-                                                      ptr(su.seg_off, P_i32), k, m, ptr(t, P_i64), ptr(a0, P_i64),
-                                                      ptr(site_ge[k:k + m], P_i64), ptr(stat0[k:k + m]),
-                                                      ptr(gene_ge[k:k + m], P_i64)), "report_perm_pairs")
+        for k in range(0, n_items, step):
+            m = min(step, n_items - k)
+            check(getattr(ctx.lib, entry)(ctx.h, n_rec, ptr(off, P_i64), ptr(rows, P_i64), n_seg, ptr(su.seg_off, P_i32),
+                                          k, m, ptr(t, P_i64), ptr(a0, P_i64), ptr(site_ge[k:k + m], P_i64),
+                                          ptr(stat0[k:k + m]), ptr(gene_ge[k:k + m], P_i64)), call)
     _perm_chunks(ctx, su, n_perm, chunk, times, test)
     t0 = timer()
-    _check_row_sums("report_perm_pairs", t, a0, sums, sums)
-    pa = np.array(_pa_infos(recs, np.repeat(which, np.diff(off)), rows - rowbase[np.repeat(which, np.diff(off))]),
-                  dtype=object)
+    _check_row_sums(call, t, a0, sums, sums)
     rec_of = np.repeat(np.arange(n_rec), np.diff(off))
-    for k, (g, h) in enumerate(zip(pair_g.tolist(), pair_h.tolist())):
-        tk = sums[:, g] + sums[:, h]
+    pa = np.array(_pa_infos(recs, which[rec_of], rows - rowbase[which[rec_of]]), dtype=object)
+    for k, ((g, tk, nz2), (lines, genes)) in enumerate(zip(items(su, sums, nz), blocks)):
         A, T = np.add.reduceat(sums[:, g], off[:-1]), np.add.reduceat(tk, off[:-1])
         tested = (np.bincount(rec_of[tk > 0], minlength=n_rec) >= 2) & (A > 0) & (A < T)
         keep = (tk > 0) & tested[rec_of]
         if not keep.any():
             continue
-        lines, genes = blocks[k]
         n_lines = np.bincount(rec_of[keep], minlength=n_rec)
         for r in np.nonzero(tested)[0].tolist():
             genes.append((recs[which[r]].gene_info_str, int(n_lines[r]), float(stat0[k, r]), int(gene_ge[k, r])))
         lines["pa"].extend(pa[keep].tolist())
-        for key, arr in (("t", tk), ("a", sums[:, g]), ("nz1", nz[:, g]), ("nz2", nz[:, h]), ("n_ge", site_ge[k])):
+        for key, arr in (("t", tk), ("a", sums[:, g]), ("nz1", nz[:, g]), ("nz2", nz2), ("n_ge", site_ge[k])):
             lines[key].append(np.asarray(arr[keep], dtype=np.int64))
     times["finish"] += timer() - t0
+
+
+def _diff_pa_blocks(su, n_perm, device, noun, header, block_ids, tested_among):
+    """the run of diff_pa_pairs and diff_pa_markers: one block of the file per entry of block_ids = (the group fields,
+    versus, cells of population 1, cells of population 2); returns the file's path"""
+    blocks = [({k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}, []) for _ in block_ids]
+
+    def write(w):
+        _write_diff_pa_blocks(w, header, [
+            (groups, versus, _diff_pa_columns(genes, lines, n1, n2, n_perm))
+            for (groups, versus, n1, n2), (lines, genes) in zip(block_ids, blocks) if genes], n_perm)
+
+    wall = _perm_run(su, n_perm, device, functools.partial(_diff_pa_blocks_batch, su, n_perm, noun, blocks), write)
+    print(f"Finish {n_perm} permutations of {len(blocks)} {noun}s {tested_among} for "
+          f"{sum(g[1] for _l, genes in blocks for g in genes)} lines of {sum(len(genes) for _l, genes in blocks)} tested "
+          f"({noun}, record) combinations")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
 
 
 def _diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
@@ -1363,25 +1409,11 @@ def _diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, i
     given) from one pass over the result file; writes <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_pairs.csv in
     output_dir, one block per pair, the p-values adjusted over the whole file, and returns its path"""
     su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_pairs", pairs=True)
-    names, G = su.names, len(su.sizes)
-    pairs = list(zip(su.pairs[0].tolist(), su.pairs[1].tolist()))
-    blocks = [({k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}, []) for _ in pairs]
-
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_pairs_batch(ctx, bat, su, n_perm, chunk, blocks, times)
-
-    def write(w):
-        _write_diff_pa_blocks(w, DIFF_PA_PAIRS_HEADER, [
-            ((names[g], names[h]), f"{names[g]}_Vs_{names[h]}",
-             _diff_pa_columns(genes, lines, int(su.sizes[g]), int(su.sizes[h]), n_perm))
-            for (g, h), (lines, genes) in zip(pairs, blocks) if genes], n_perm)
-
-    wall = _perm_run(su, n_perm, device, batch, write)
-    print(f"Finish {n_perm} permutations of {len(pairs)} pairs of {G} populations ({int(su.sizes.sum())} cells) for "
-          f"{sum(g[1] for _l, genes in blocks for g in genes)} lines of {sum(len(genes) for _l, genes in blocks)} tested "
-          "(pair, record) combinations")
-    print(f"Finish {su.res_pkl} in {wall / 60} min.")
-    return su.outpath
+    names, sizes = su.names, su.sizes.tolist()
+    return _diff_pa_blocks(su, n_perm, device, "pair", DIFF_PA_PAIRS_HEADER,
+                           [((names[g], names[h]), f"{names[g]}_Vs_{names[h]}", sizes[g], sizes[h])
+                            for g, h in zip(su.pairs[0].tolist(), su.pairs[1].tolist())],
+                           f"of {len(sizes)} populations ({sum(sizes)} cells)")
 
 
 # ---------------------------------------------------------------- diff_pa_markers
@@ -1405,51 +1437,6 @@ DIFF_PA_MARKERS_HEADER = DIFF_PA_HEADER[:2] + ["group"] + DIFF_PA_HEADER[2:]
 MAX_MARKER_RESULT_BYTES = 256 << 20   # host and device bytes of the counters of one call: more markers are taken in ranges
 
 
-def _diff_pa_markers_batch(ctx, bat, su, n_perm, chunk, blocks, times):
-    """one counted batch: the kept rows of the records that two segments or more have reads in go through every
-    marker's test, the markers in ranges of at most MAX_MARKER_RESULT_BYTES of counters; appends to blocks[g] = (lines,
-    genes) of marker g what _diff_pa_batch appends for the marker and its rest"""
-    sel = _perm_rows(ctx, bat, su.seg_off, times)
-    if sel is None:
-        return
-    recs, M, n_seg = bat.recs, len(su.sizes), len(su.seg_off) - 1
-    which, off, rows, nz, sums, rowbase = sel
-    n_rows, n_rec = len(rows), len(which)
-    t, a0 = np.zeros(n_rows, np.int64), np.zeros((n_rows, n_seg), np.int64)
-    site_ge, gene_ge = np.zeros((M, n_rows), np.int64), np.zeros((M, n_rec), np.int64)
-    stat0 = np.zeros((M, n_rec), np.float64)
-    step = int(max(1, min(M, MAX_MARKER_RESULT_BYTES // (12 * n_rows + 20 * n_rec))))
-
-    def test():
-        for k in range(0, M, step):
-            m = min(step, M - k)
-            check(ctx.lib.scape_hip_report_perm_markers(ctx.h, n_rec, ptr(off, P_i64), ptr(rows, P_i64), n_seg,
-                                                        ptr(su.seg_off, P_i32), k, m, ptr(t, P_i64), ptr(a0, P_i64),
-                                                        ptr(site_ge[k:k + m], P_i64), ptr(stat0[k:k + m]),
-                                                        ptr(gene_ge[k:k + m], P_i64)), "report_perm_markers")
-    _perm_chunks(ctx, su, n_perm, chunk, times, test)
-    t0 = timer()
-    _check_row_sums("report_perm_markers", t, a0, sums, sums)
-    rec_of = np.repeat(np.arange(n_rec), np.diff(off))
-    pa = np.array(_pa_infos(recs, which[rec_of], rows - rowbase[which[rec_of]]), dtype=object)
-    nz_all = nz.astype(np.int64).sum(axis=1)
-    T = np.add.reduceat(t, off[:-1])
-    for g, (lines, genes) in enumerate(blocks):
-        A = np.add.reduceat(sums[:, g], off[:-1])
-        tested = (A > 0) & (A < T)       # every record here has two kept rows or more
-        keep = tested[rec_of]
-        if not keep.any():
-            continue
-        for r in np.nonzero(tested)[0].tolist():
-            genes.append((recs[which[r]].gene_info_str, int(off[r + 1] - off[r]), float(stat0[g, r]),
-                          int(gene_ge[g, r])))
-        lines["pa"].extend(pa[keep].tolist())
-        for key, arr in (("t", t), ("a", sums[:, g]), ("nz1", nz[:, g]), ("nz2", nz_all - nz[:, g]),
-                         ("n_ge", site_ge[g])):
-            lines[key].append(np.asarray(arr[keep], dtype=np.int64))
-    times["finish"] += timer() - t0
-
-
 def _diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
                      seed: int = 1, device=None):
     """diff_pa of every cluster of a cluster file (or of the clusters `idents`, in the order given) against all other
@@ -1457,23 +1444,9 @@ def _diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str,
     <cluster file stem>.<gene|utr>[.<A>+<B>+...].diff_pa_markers.csv in output_dir, one block per marker, the p-values
     adjusted over the whole file, and returns its path"""
     su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_markers", markers=True)
-    names = su.names
-    blocks = [({k: [] for k in ("pa", "t", "a", "nz1", "nz2", "n_ge")}, []) for _ in names]
-
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_markers_batch(ctx, bat, su, n_perm, chunk, blocks, times)
-
-    def write(w):
-        _write_diff_pa_blocks(w, DIFF_PA_MARKERS_HEADER, [
-            ((name,), name, _diff_pa_columns(genes, lines, int(n_g), su.n - int(n_g), n_perm))
-            for name, n_g, (lines, genes) in zip(names, su.sizes, blocks) if genes], n_perm)
-
-    wall = _perm_run(su, n_perm, device, batch, write)
-    print(f"Finish {n_perm} permutations of {len(names)} markers among {su.n} cells for "
-          f"{sum(g[1] for _l, genes in blocks for g in genes)} lines of {sum(len(genes) for _l, genes in blocks)} tested "
-          "(marker, record) combinations")
-    print(f"Finish {su.res_pkl} in {wall / 60} min.")
-    return su.outpath
+    return _diff_pa_blocks(su, n_perm, device, "marker", DIFF_PA_MARKERS_HEADER,
+                           [((name,), name, n_g, su.n - n_g) for name, n_g in zip(su.names, su.sizes.tolist())],
+                           f"among {su.n} cells")
 
 
 # ---------------------------------------------------------------- diff_pa_len_groups
@@ -1528,7 +1501,7 @@ def _mean_positions_groups(x, a):
     return float(Fraction(St, T * D)), mean, delta
 
 
-def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, out, times):
+def _diff_pa_len_groups_batch(su, n_perm, out, ctx, bat, chunk, times):
     """one counted batch: appends (gene, num_pa, [A_g], mean_pos, eta2, n_ge, top group, [mean_pos.<g>],
     [delta_pos.<g>], [n_ge.<g>]) per tested record to `out`"""
     recs, G = bat.recs, len(su.sizes)
@@ -1566,9 +1539,7 @@ def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, out, times):
         Qg = [sum(row[k] * v for row, v in zip(a, qi)) for k in range(G)]
         Tr, Q = sum(A), sum(Qg)
         D = sum(Fraction(Qg[k] * Qg[k], A[k]) for k in range(G) if A[k]) - Fraction(Q * Q, Tr)
-        if not abs(Fraction(float(stat0[g])) - D) <= Fraction(float(tol_stat[g])):
-            raise _lib.ScapeHipError(f"report_perm_len_groups: {recs[r].gene_info_str}: the device's statistic "
-                                     f"{stat0[g]!r} differs from {float(D)!r}")
+        _check_exact("report_perm_len_groups", recs[r], ("statistic",), stat0[g], D, Fraction(float(tol_stat[g])))
         # d_k = N_k / M_k with N_k = Q_k T - Q A_k and M_k = A_k (T - A_k) > 0 for a reported group
         N = [Qg[k] * Tr - Q * A[k] for k in range(G)]
         M = [A[k] * (Tr - A[k]) for k in range(G)]
@@ -1576,10 +1547,8 @@ def _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, out, times):
         for k in range(G):
             if M[k] == 0:
                 continue
-            if not abs(Fraction(float(delta0[g, k])) - Fraction(N[k], M[k])) <= Fraction(float(tol_delta[g])):
-                raise _lib.ScapeHipError(f"report_perm_len_groups: {recs[r].gene_info_str}: the device's delta "
-                                         f"{delta0[g, k]!r} of population {su.names[k]!r} differs from "
-                                         f"{N[k] / M[k]!r}")
+            _check_exact("report_perm_len_groups", recs[r], ("delta", "population", su.names[k]), delta0[g, k],
+                         Fraction(N[k], M[k]), Fraction(float(tol_delta[g])))
             if top is None or abs(N[k]) * M[top] > abs(N[top]) * M[k]:       # the first wins ties
                 top = k
         ss_total = sum(int(ti) * v * v for ti, v in zip(t[sl].tolist(), qi)) - Fraction(Q * Q, Tr)
@@ -1599,8 +1568,7 @@ def _diff_pa_len_groups(output_dir: str, res_pkl_file: str, cell_cluster_file: s
     names, G = su.names, len(su.sizes)
     out = []
 
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_len_groups_batch(ctx, bat, su, n_perm, chunk, out, times)
+    batch = functools.partial(_diff_pa_len_groups_batch, su, n_perm, out)
 
     def write(w):
         w.writerow(DIFF_PA_LEN_GROUPS_HEADER + [f"{c}.{n}" for n in names for c in DIFF_PA_LEN_GROUPS_PER_GROUP])
@@ -1720,7 +1688,7 @@ def _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed, 
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
 
 
-def _diff_pa_trend_batch(ctx, bat, su, n_perm, chunk, lines, genes, times):
+def _diff_pa_trend_batch(su, n_perm, lines, genes, ctx, bat, chunk, times):
     """one counted batch: the kept rows of its tested records go through the trend test; appends the per-line integers
     to `lines` and (gene_info_str, lines, T, S, eta2, gene_n_ge) per tested record to `genes`"""
     sel = _perm_rows(ctx, bat, su.seg_off, times, min_pops=1)
@@ -1750,13 +1718,10 @@ def _diff_pa_trend_batch(ctx, bat, su, n_perm, chunk, lines, genes, times):
         _check_reads(recs[r], T)
         # the statistics of the observed scores, exactly, in Python ints on the q_j
         D = sum(Fraction(s * s, tt) for s, tt in zip(si, ti)) - Fraction(S * S, T)
-        if not abs(Fraction(float(stat0[g])) - D) <= Fraction(T * qspan * qspan, 1 << 40):
-            raise _lib.ScapeHipError(f"report_perm_trend: {recs[r].gene_info_str}: the device's statistic {stat0[g]!r} "
-                                     f"differs from {float(D)!r}")
+        _check_exact("report_perm_trend", recs[r], ("statistic",), stat0[g], D, Fraction(T * qspan * qspan, 1 << 40))
         for k, (s, tt) in enumerate(zip(si, ti)):
-            if not abs(Fraction(float(d0[a + k])) - Fraction(s * T - S * tt, tt * (T - tt))) <= Fraction(qspan, 1 << 40):
-                raise _lib.ScapeHipError(f"report_perm_trend: {recs[r].gene_info_str}: the device's delta "
-                                         f"{d0[a + k]!r} of kept row {k} differs from the exact one")
+            _check_exact("report_perm_trend", recs[r], ("delta", "kept row", k), d0[a + k],
+                         Fraction(s * T - S * tt, tt * (T - tt)), Fraction(qspan, 1 << 40), "the exact one")
         ss_total = int(sq0[a:b].sum()) - Fraction(S * S, T)
         genes.append((recs[r].gene_info_str, b - a, T, S, float(D / ss_total) if ss_total else None, int(gene_ge[g])))
         lines["pa"].extend(_pa_info(recs[r], rows[a:b] - int(rowbase[r])))
@@ -1774,8 +1739,7 @@ def _diff_pa_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, ran
     lines = {k: [] for k in ("pa", "t", "s", "nz", "n_ge")}
     genes = []                   # (gene_info_str, lines, T, S, eta2, gene_n_ge) per tested record
 
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_trend_batch(ctx, bat, su, n_perm, chunk, lines, genes, times)
+    batch = functools.partial(_diff_pa_trend_batch, su, n_perm, lines, genes)
 
     def write(w):
         w.writerow(DIFF_PA_TREND_HEADER)
@@ -1836,7 +1800,7 @@ def _len_trend_bits(T):
     return min(LEN_TREND_MAX_Q_BITS, LEN_TREND_TX_BITS - int(T).bit_length())
 
 
-def _diff_pa_len_trend_batch(ctx, bat, su, n_perm, chunk, out, times):
+def _diff_pa_len_trend_batch(su, n_perm, out, ctx, bat, chunk, times):
     """one counted batch: appends (gene, num_pa, T, mean_pos, mean_score, slope, delta_pos, r, n_ge) per tested record
     to `out`; slope, delta_pos and r are None when the score has no variance over the record's reads"""
     recs = bat.recs
@@ -1896,8 +1860,7 @@ def _diff_pa_len_trend(output_dir: str, res_pkl_file: str, cell_score_file: str,
     su = _trend_setup(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed, "diff_pa_len_trend")
     out = []
 
-    def batch(ctx, bat, chunk, times):
-        _diff_pa_len_trend_batch(ctx, bat, su, n_perm, chunk, out, times)
+    batch = functools.partial(_diff_pa_len_trend_batch, su, n_perm, out)
 
     def write(w):
         w.writerow(DIFF_PA_LEN_TREND_HEADER)
@@ -2091,51 +2054,69 @@ def ex_pa_pseudobulk(output_dir: str, res_pkl_file: str, cell_cluster_file: str,
     _ex_pa_pseudobulk(output_dir, res_pkl_file, cell_cluster_file, num_splits, idents_1, idents_2)
 
 
-def _perm_options(f):
-    """the options diff_pa and diff_pa_len share (--seed's help differs)"""
-    for option in reversed((
-            click.option('--output_dir', type=str, required=True,
-                         help='Directory which was used in previous steps to save output by prepare_input and '
-                              'infer_pa.'),
-            click.option('--res_pkl_file', type=str, default="None",
-                         help='Name of res pickle file that contains PASs. Its name will be included in the file name '
-                              'of the final result.'),
-            click.option('--cell_cluster_file', type=str, required=True,
-                         help='An csv file containing two columns in order: cell barcode index (index) and respective '
-                              'group. Cells with an empty group, or not listed, are left out. Its name will be '
-                              'included in the file name of the final result.'),
-            click.option('--idents_1', type=str, required=True, help='The cluster of population 1.'),
-            click.option('--idents_2', type=str, default=None,
-                         help='The cluster of population 2. Default: every other cell that has a cluster.'),
-            click.option('--n_perm', type=int, default=9999, show_default=True,
-                         help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).'),
-            click.option('--strata_file', type=str, default=None,
-                         help='A csv file like the cell_cluster_file, naming a stratum (cell type, donor, batch, ...) '
-                              'per cell: the labels are then permuted within each stratum only. Cells with an empty '
-                              'stratum, or not listed, are left out. Its name will be included in the file name of '
-                              'the final result.'))):
-        f = option(f)
-    return f
+# the options every command below starts with, and the cluster file of those that take one
+_OUTPUT_OPTIONS = (
+    click.option('--output_dir', type=str, required=True,
+                 help='Directory which was used in previous steps to save output by prepare_input and infer_pa.'),
+    click.option('--res_pkl_file', type=str, default="None",
+                 help='Name of res pickle file that contains PASs. Its name will be included in the file name of the '
+                      'final result.'))
+_CLUSTER_FILE_OPTION = click.option(
+    '--cell_cluster_file', type=str, required=True,
+    help='An csv file containing two columns in order: cell barcode index (index) and respective group. Cells with an '
+         'empty group, or not listed, are left out. Its name will be included in the file name of the final result.')
 
 
-def _groups_options(f, idents_help='A cluster to test; give the option once per cluster (2 to 64), the order is kept. '
-                                    'Default: every cluster of the cell_cluster_file, in order of first appearance.'):
-    """the options diff_pa_groups, diff_pa_len_groups, diff_pa_pairs and diff_pa_markers share (the help of --n_perm and
-    --seed differs, and diff_pa_markers has its own for --idents)"""
-    for option in reversed((
-            click.option('--output_dir', type=str, required=True,
-                         help='Directory which was used in previous steps to save output by prepare_input and '
-                              'infer_pa.'),
-            click.option('--res_pkl_file', type=str, default="None",
-                         help='Name of res pickle file that contains PASs. Its name will be included in the file name '
-                              'of the final result.'),
-            click.option('--cell_cluster_file', type=str, required=True,
-                         help='An csv file containing two columns in order: cell barcode index (index) and respective '
-                              'group. Cells with an empty group, or not listed, are left out. Its name will be '
-                              'included in the file name of the final result.'),
-            click.option('--idents', type=str, multiple=True, help=idents_help))):
-        f = option(f)
-    return f
+def _options(*options):
+    """a decorator that adds the options, in their order"""
+    def decorate(f):
+        for option in reversed(options):
+            f = option(f)
+        return f
+    return decorate
+
+
+# diff_pa and diff_pa_len (--seed's help differs)
+_perm_options = _options(
+    *_OUTPUT_OPTIONS, _CLUSTER_FILE_OPTION,
+    click.option('--idents_1', type=str, required=True, help='The cluster of population 1.'),
+    click.option('--idents_2', type=str, default=None,
+                 help='The cluster of population 2. Default: every other cell that has a cluster.'),
+    click.option('--n_perm', type=int, default=9999, show_default=True,
+                 help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).'),
+    click.option('--strata_file', type=str, default=None,
+                 help='A csv file like the cell_cluster_file, naming a stratum (cell type, donor, batch, ...) per cell: '
+                      'the labels are then permuted within each stratum only. Cells with an empty stratum, or not '
+                      'listed, are left out. Its name will be included in the file name of the final result.'))
+
+
+def _idents_options(idents_help):
+    """diff_pa_groups, diff_pa_len_groups, diff_pa_pairs and diff_pa_markers (the help of --n_perm and --seed differs, and
+    diff_pa_markers has its own for --idents)"""
+    return _options(*_OUTPUT_OPTIONS, _CLUSTER_FILE_OPTION,
+                    click.option('--idents', type=str, multiple=True, help=idents_help))
+
+
+_groups_options = _idents_options('A cluster to test; give the option once per cluster (2 to 64), the order is kept. '
+                                  'Default: every cluster of the cell_cluster_file, in order of first appearance.')
+_markers_options = _idents_options(
+    'A cluster to test against all other cells that have a cluster, whether named or not; give the option once per '
+    'cluster (1 to 64), the order is kept. Default: every cluster of the cell_cluster_file (at most 64), in order of '
+    'first appearance.')
+# diff_pa_trend and diff_pa_len_trend
+_trend_options = _options(
+    *_OUTPUT_OPTIONS,
+    click.option('--cell_score_file', type=str, required=True,
+                 help='An csv file containing two columns in order: cell barcode index (index) and the score of the cell '
+                      '(pseudotime, a differentiation, cell-cycle or activation score). Cells with an empty score, NA or '
+                      'nan, or not listed, are left out. Its name will be included in the file name of the final '
+                      'result.'),
+    click.option('--rank', is_flag=True, default=False,
+                 help='Test along the ranks of the scores (ties share their mid-rank), not the scores themselves.'),
+    click.option('--n_perm', type=int, default=9999, show_default=True,
+                 help='Permutations of the cell scores; the smallest p-value is 1 / (1 + n_perm).'),
+    click.option('--seed', type=int, default=1, show_default=True,
+                 help='Seed of the permutations, 0 .. 2^64 - 1 (the keys are those of diff_pa).'))
 
 
 @click.command(name="diff_pa")
@@ -2200,12 +2181,6 @@ def diff_pa_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, id
     _diff_pa_pairs(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
 
 
-def _markers_options(f):
-    return _groups_options(f, 'A cluster to test against all other cells that have a cluster, whether named or not; give '
-                              'the option once per cluster (1 to 64), the order is kept. Default: every cluster of the '
-                              'cell_cluster_file (at most 64), in order of first appearance.')
-
-
 @click.command(name="diff_pa_markers")
 @_markers_options
 @click.option('--n_perm', type=int, default=9999, show_default=True,
@@ -2218,31 +2193,6 @@ def diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     cells that have a cluster, as diff_pa tests one cluster against the rest, in one run over the result file: the
     markers of every cluster, with the p-values adjusted over all of them (Benjamini-Hochberg)."""
     _diff_pa_markers(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
-
-
-def _trend_options(f):
-    """the options diff_pa_trend and diff_pa_len_trend share"""
-    for option in reversed((
-            click.option('--output_dir', type=str, required=True,
-                         help='Directory which was used in previous steps to save output by prepare_input and '
-                              'infer_pa.'),
-            click.option('--res_pkl_file', type=str, default="None",
-                         help='Name of res pickle file that contains PASs. Its name will be included in the file name '
-                              'of the final result.'),
-            click.option('--cell_score_file', type=str, required=True,
-                         help='An csv file containing two columns in order: cell barcode index (index) and the score '
-                              'of the cell (pseudotime, a differentiation, cell-cycle or activation score). Cells with '
-                              'an empty score, NA or nan, or not listed, are left out. Its name will be included in '
-                              'the file name of the final result.'),
-            click.option('--rank', is_flag=True, default=False,
-                         help='Test along the ranks of the scores (ties share their mid-rank), not the scores '
-                              'themselves.'),
-            click.option('--n_perm', type=int, default=9999, show_default=True,
-                         help='Permutations of the cell scores; the smallest p-value is 1 / (1 + n_perm).'),
-            click.option('--seed', type=int, default=1, show_default=True,
-                         help='Seed of the permutations, 0 .. 2^64 - 1 (the keys are those of diff_pa).'))):
-        f = option(f)
-    return f
 
 
 @click.command(name="diff_pa_trend")
