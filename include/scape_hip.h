@@ -408,6 +408,40 @@ int scape_hip_report_perm_markers(scape_hip_ctx *ctx, int32_t n_rec, const int64
                                   int32_t n_seg, const int32_t *seg_off, int32_t marker_first, int32_t marker_count,
                                   int64_t *t_out, int64_t *a0_out, int64_t *site_n_ge_out, double *stat0_out,
                                   int64_t *gene_n_ge_out);
+/* diff_pa_len_pairs: every pair of the last pair masks call tested as scape_hip_report_perm_len tests two populations,
+   from the counts call, the bits and the one compaction of scape_hip_report_perm_pairs.  (ABI 4 gains this entry point
+   and the next; nothing that was there changes.)  Records, kept rows (those kept
+   over ALL groups), the range pair_first / pair_count, t_out and a0_out [row][group], the checks of n_groups / seg_off
+   and of the range, and the ADD semantics are those of that call.  x[i] is the pA position of kept row i (alpha_arr[label],
+   f64, NOT yet shifted).  Pair (g, h) owns the rows of a record with t_i = a0[i][g] + a0[i][h] > 0 and tests the record
+   when two such rows or more remain, both populations have reads and span = max x - min x over THOSE rows is > 0.  Then
+   the device forms, over those rows in order, w_i = x_i - min x (one f64 subtraction) and tol = 2^-40 span, and W1, W2
+   and delta through the device functions of scape_hip_report_perm_len, contraction off.  A row without a read in the
+   pair is passed over, not multiplied by 0: its w would lie outside 0 .. span.  So delta0_out[k * n_rec + r] has the
+   bits, and n_ge_out[k * n_rec + r] (ADDED to: the permutations with |delta(p)| >= |delta(0)| - tol) the value, of a
+   scape_hip_report_perm_len call behind scape_hip_report_perm_masks on the pair's own two populations and rows, k
+   counting from pair_first.  For a record the pair does not test delta0_out is 0.0 and nothing is added.  The rounding
+   bound of scape_hip_report_perm_len holds: a pair's rows are a subset of the record's, of which there may be at most
+   1,024.  Checked before anything is queued, beside the checks of scape_hip_report_perm_pairs: x and the outputs are
+   there, every x is finite and so is max x - min x of every record, no record owns more than 1,024 rows; a refused call
+   leaves masks and counts in place.  pair_count * n_rec < 2^31.  No LDS: any number of rows in one launch. */
+int scape_hip_report_perm_len_pairs(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                    int32_t n_groups, const int32_t *seg_off, int32_t pair_first, int32_t pair_count,
+                                    const double *x, int64_t *t_out, int64_t *a0_out, double *delta0_out,
+                                    int64_t *n_ge_out);
+/* diff_pa_len_markers: every marker of the last marker masks call tested as scape_hip_report_perm_len tests a population
+   against all other tested cells, from the counts call, the bits (in slot order) and the one compaction of
+   scape_hip_report_perm_markers; records, kept rows, the range marker_first / marker_count, n_seg / seg_off and their
+   checks, t_out and a0_out [row][segment] and the ADD semantics are those of that call, x and its checks those of
+   scape_hip_report_perm_len_pairs.  The kept rows with t_i > 0, min x, w_i and tol = 2^-40 span are the same for every
+   marker.  Marker g tests record r when two rows or more have t_i > 0, 0 < A_g(0) < T and span > 0; then
+   delta0_out[k * n_rec + r] has the bits, and n_ge_out[k * n_rec + r] (ADDED to) the value, of a
+   scape_hip_report_perm_len call on the marker's population against all other tested cells, k counting from
+   marker_first; otherwise delta0_out is 0.0 and nothing is added.  marker_count * n_rec < 2^31.  No LDS. */
+int scape_hip_report_perm_len_markers(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                      int32_t n_seg, const int32_t *seg_off, int32_t marker_first, int32_t marker_count,
+                                      const double *x, int64_t *t_out, int64_t *a0_out, double *delta0_out,
+                                      int64_t *n_ge_out);
 /* diff_pa_trend: the test of pA usage ALONG an integer score of the cells, on the keys of scape_hip_report_perm_masks.
    (ABI 4 gains the three entry points below; nothing that was there changes.)  The tested columns are the first n
    columns of the count matrix, position j = column j, 2 <= n < 2^24; q[j] is the observed score of position j, 0 <= q[j]

@@ -87,6 +87,10 @@ SIGNATURES = {
     "scape_hip_report_perm_marker_bits_get": (c_i, [P_void, c_i32, c_i32, ctypes.POINTER(ctypes.c_uint64)]),
     "scape_hip_report_perm_markers": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, c_i32, c_i32, P_i64, P_i64, P_i64,
                                             P_d, P_i64]),
+    "scape_hip_report_perm_len_pairs": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, c_i32, c_i32, P_d, P_i64, P_i64,
+                                              P_d, P_i64]),
+    "scape_hip_report_perm_len_markers": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, c_i32, c_i32, P_d, P_i64,
+                                                P_i64, P_d, P_i64]),
     "scape_hip_report_perm_scores": (c_i, [P_void, c_i32, P_u16, c_i64, c_i32, ctypes.c_uint64]),
     "scape_hip_report_perm_scores_get": (c_i, [P_void, c_i32, P_u16]),
     "scape_hip_report_perm_trend": (c_i, [P_void, c_i32, P_i64, P_i64, P_i64, P_i64, P_i64, P_i64, P_d, P_d, P_i64]),

@@ -1,5 +1,6 @@
 // perm.inc - the permutation tests on merge_pa's count matrix: diff_pa and diff_pa_len (freely or within strata),
-// diff_pa_groups, diff_pa_len_groups, diff_pa_pairs, diff_pa_markers, diff_pa_trend and diff_pa_len_trend (included by
+// diff_pa_groups, diff_pa_len_groups, diff_pa_pairs, diff_pa_markers, diff_pa_len_pairs, diff_pa_len_markers,
+// diff_pa_trend and diff_pa_len_trend (included by
 // scape_hip.hip after report.inc, whose ReportState, block helpers and k_rep_scan it uses).
 //
 // A test is two calls.  The first builds the labellings of a chunk of permutations, in exact integers:
@@ -35,6 +36,10 @@
 //                   diff_pa_markers: the membership bits of every (marker population, permutation) in the order of the
 //                   count matrix's columns, each marker's own local positions found by a search in its ranks, and
 //                   diff_pa's test of every marker against all other tested cells from the one compaction
+//   k_rep_perm_len_pairs / k_rep_perm_len_markers
+//                   diff_pa_len_pairs, diff_pa_len_markers: diff_pa_len's test of every pair and of every marker against
+//                   the same bits and the same one compaction, one body (rep_perm_len_item), an item walking its own
+//                   rows only and finding min x, span and tol over them
 //   k_rep_perm_scores / k_rep_trend_obs / k_rep_perm_trend
 //                   diff_pa_trend: the rank of EVERY key of a permutation by LDS buckets, so that position j gets the
 //                   score q[rank of key(p, j)] as a halfword; the observed sums per kept row; and the test of the
@@ -46,7 +51,8 @@
 // On the host a builder leaves a RepLabellings in ReportState (what it built, for the checks of the tests and of the
 // `_get` entry points).  A test fills a RepPermCall, the one frame of its call: rep_perm_prepare checks and compacts from
 // it, rep_perm_launch_classes launches a two-population test per LDS class of records, rep_perm_count brings the
-// exceedance counters back, rep_perm_ranged is the body that diff_pa_pairs and diff_pa_markers share and
+// exceedance counters back, rep_perm_ranged is the body that diff_pa_pairs and diff_pa_markers share,
+// rep_perm_len_ranged that of diff_pa_len_pairs and diff_pa_len_markers behind the same checks (rep_ranged_ok), and
 // rep_trend_prepare the head of the two tests on scores.  No entry point returns with work queued on the stream
 // (StreamDrain).  Cluster names, strata files, p-values and their adjustment stay on the host (scape_amd/report.py).
 
@@ -1076,6 +1082,117 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_markers(
     if (tile == 0 && threadIdx.x == 0) stat0[out_r] = S0;
 }
 
+// ---- diff_pa_len_pairs / diff_pa_len_markers: every pair, every marker, each as diff_pa_len ---------------------------
+// The items, their bits and the one compaction over all n positions are those of diff_pa_pairs and diff_pa_markers
+// above; the test is k_rep_perm_len's on the item's OWN rows: the rows of the record with t_i > 0 in the item, in order,
+// with w_i = x_i - min x and tol = 2^-40 (max x - min x) over those rows, x the rows' positions as passed.  A row
+// without a read in the item is passed over, not multiplied by 0: its x may lie outside [min x, max x] of the item, its
+// w outside [0, span].  Every sum goes through rep_len_row and rep_len_delta, so n_ge and the bits of delta(0) are those
+// of k_rep_perm_len on the item's two populations.  The rounding comment above k_rep_perm_len (at most
+// REP_LEN_MAX_ROWS rows, (4 R + 7) u span <= tol / 2) covers both kernels: an item's rows are a subset of the record's,
+// at most 1,024 of them (checked by the entry points), and span is the item's own.
+//
+// How an item gets t_i, a_i(0) and a_i(p) of kept row i.  A pair: the two groups' columns of a0 [row][group], and the
+// nonzeros of the two segments moved to the pair's local positions (the shifts of k_rep_perm_pairs)
+struct RepLenPairRows {
+    const int64_t *__restrict__ a0, *__restrict__ sg;
+    const uint2 *__restrict__ nz;
+    int n_groups, g, h, sh_g, sh_h;
+    __device__ __forceinline__ int obs(int64_t i) const { return (int)a0[i * n_groups + g]; }
+    __device__ __forceinline__ int reads(int64_t i) const { return obs(i) + (int)a0[i * n_groups + h]; }
+    __device__ __forceinline__ int perm(int64_t i, const unsigned long long *__restrict__ mb, int64_t pstride) const {
+        const int64_t *si = sg + i * (n_groups + 1);
+        return rep_perm_segsum(nz, si[g], si[g + 1], sh_g, mb, pstride) +
+               rep_perm_segsum(nz, si[h], si[h + 1], sh_h, mb, pstride);
+    }
+};
+// a marker: t of the row over all tested cells, column g of a0 [row][segment], the whole row's nonzeros in slot order
+struct RepLenMarkerRows {
+    const int64_t *__restrict__ t, *__restrict__ a0, *__restrict__ noff;
+    const uint2 *__restrict__ nz;
+    int n_seg, g;
+    __device__ __forceinline__ int obs(int64_t i) const { return (int)a0[i * n_seg + g]; }
+    __device__ __forceinline__ int reads(int64_t i) const { return (int)t[i]; }
+    __device__ __forceinline__ int perm(int64_t i, const unsigned long long *__restrict__ mb, int64_t pstride) const {
+        return rep_perm_segsum(nz, noff[i], noff[i + 1], 0, mb, pstride);
+    }
+};
+
+// The body of both kernels.  Workgroup = (item blockIdx.y of the range, record blockIdx.x / n_tiles, tile of 256
+// permutations), one lane per permutation, registers only as k_rep_perm_len: no LDS, any number of rows in one launch.
+// bits = the first mask word of the item.  Pass 1 reads the record's observed sums only (wave-uniform): T, A(0), the
+// rows with t_i > 0 and min x, max x over them; the item does not test the record when fewer than two such rows remain,
+// one of its populations has no read or span = 0, and then the workgroup stores delta(0) = 0.0 and leaves (uniform;
+// no counter is touched).  Pass 2 walks each row with t_i > 0 once.  Exceedances by ballot, one atomic per wave into
+// n_ge[item in range][record]; delta0 likewise, from tile 0.
+template <typename Rows>
+__device__ __forceinline__ void rep_perm_len_item(const Rows &rows, const unsigned long long *__restrict__ bits,
+                                                  int32_t p_count, int32_t n_tiles, const int64_t *__restrict__ roff,
+                                                  const double *__restrict__ x, int32_t n_rec,
+                                                  int32_t *__restrict__ n_ge, double *__restrict__ delta0) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int64_t out_r = (int64_t)blockIdx.y * n_rec + r;
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    long long T = 0, A0 = 0;
+    int with_reads = 0;
+    double xmin = 0.0, xmax = 0.0;
+    for (int64_t i = row0; i < row1; ++i) {
+        const int ti = rows.reads(i);
+        if (ti == 0) continue;
+        const double xi = x[i];
+        xmin = with_reads && xmin <= xi ? xmin : xi;
+        xmax = with_reads && xmax >= xi ? xmax : xi;
+        T += ti;
+        A0 += rows.obs(i);
+        ++with_reads;
+    }
+    if (with_reads < 2 || A0 == 0 || A0 == T || !(xmax > xmin)) {
+        if (tile == 0 && threadIdx.x == 0) delta0[out_r] = 0.0;
+        return;
+    }
+    const double tol = (xmax - xmin) * 0x1p-40;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < p_count;
+    const unsigned long long *mb = bits + (valid ? p : p_count - 1);
+    double W1 = 0.0, W2 = 0.0, V1 = 0.0, V2 = 0.0;
+    long long A = 0, B = 0, B0 = 0;
+    A0 = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        const int ti = rows.reads(i);
+        if (ti == 0) continue;
+        const double wi = x[i] - xmin;
+        rep_len_row(rows.perm(i, mb, p_count), ti, wi, &W1, &W2, &A, &B);
+        rep_len_row(rows.obs(i), ti, wi, &V1, &V2, &A0, &B0);
+    }
+    const double d = rep_len_delta(W1, W2, A, B), d0 = rep_len_delta(V1, V2, A0, B0);
+    const unsigned long long b = __ballot(valid && fabs(d) >= fabs(d0) - tol);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&n_ge[out_r], __popcll(b));
+    if (tile == 0 && threadIdx.x == 0) delta0[out_r] = d0;
+}
+
+// pairs = the descriptors from pair_first on; sg[i] = the row's G + 1 segment starts (k_rep_pair_segidx)
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_pairs(
+    const unsigned long long *__restrict__ bits, int32_t p_count, int32_t n_tiles, const int64_t *__restrict__ roff,
+    const int64_t *__restrict__ sg, const uint2 *__restrict__ nz, const int64_t *__restrict__ a0, int32_t n_groups,
+    const int32_t *__restrict__ seg_off, const RepPair *__restrict__ pairs, const double *__restrict__ x, int32_t n_rec,
+    int32_t *__restrict__ n_ge, double *__restrict__ delta0) {
+    const RepPair pr = pairs[blockIdx.y];
+    const RepLenPairRows rows{a0, sg, nz, n_groups, pr.g, pr.h, -seg_off[pr.g], pr.n_g - seg_off[pr.h]};
+    rep_perm_len_item(rows, bits + (int64_t)pr.woff * p_count, p_count, n_tiles, roff, x, n_rec, n_ge, delta0);
+}
+
+// marker marker_first + blockIdx.y; n_words = the mask words of a marker and permutation
+__global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_markers(
+    const unsigned long long *__restrict__ bits, int32_t p_count, int32_t n_tiles, int32_t n_words,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ noff, const uint2 *__restrict__ nz,
+    const int64_t *__restrict__ t, const int64_t *__restrict__ a0, int32_t n_seg, int32_t marker_first,
+    const double *__restrict__ x, int32_t n_rec, int32_t *__restrict__ n_ge, double *__restrict__ delta0) {
+    const int g = marker_first + blockIdx.y;
+    const RepLenMarkerRows rows{t, a0, noff, nz, n_seg, g};
+    rep_perm_len_item(rows, bits + (int64_t)g * n_words * p_count, p_count, n_tiles, roff, x, n_rec, n_ge, delta0);
+}
+
 // ---- diff_pa_trend: pA usage along a per-cell score ---------------------------------------------------------------------
 // The contract extends the G-way one.  The tested columns are the first n columns of the count matrix, position j =
 // column j, 2 <= n < 2^24; q[0 .. n) are the observed integer scores of the positions, 0 <= q <= 32,768.  Permutation
@@ -1513,7 +1630,8 @@ static int rep_get_ok(const RepLabellings &l, const void *out, const char *item_
 // p_count = the permutations of the labellings `what`.  Two populations (seg_off = nullptr): a0 = the row's sum over the
 // positions below n1, in p_a0.  n_groups populations in the column segments seg_off: a0 = the n_groups sums of the row,
 // in q_a0.  outs_ok = the caller's own other pointers are there; max_rec_rows > 0: a record may own at most that many
-// rows; w / tol / tol2, when given, must be finite and not negative; the positions q, when given, lie in 0 .. 2^22.
+// rows; w / tol / tol2, when given, must be finite and not negative; the positions q, when given, lie in 0 .. 2^22; the
+// positions x, when given, are finite and so is max x - min x of every record.
 struct RepPermHost {                   // the call's host memory that queued copies read or write
     RepPermClasses classes;            // rep_perm_launch_classes
     std::vector<int32_t> site, gene;   // rep_perm_count: the counters of this chunk
@@ -1526,7 +1644,7 @@ struct RepPermCall : RepPermHost {
     const int64_t *rec_row_off, *rows;
     int64_t *t_out, *a0_out = nullptr;
     const int32_t *seg_off = nullptr, *q = nullptr;
-    const double *w = nullptr, *tol = nullptr, *tol2 = nullptr;
+    const double *w = nullptr, *tol = nullptr, *tol2 = nullptr, *x = nullptr;
     bool outs_ok = false;
     int64_t max_rec_rows = 0;
     int64_t n_rows = 0, nnz = 0;       // results of rep_perm_prepare: the kept rows, their nonzeros and the tiles of
@@ -1567,6 +1685,15 @@ static int rep_perm_prepare(scape_hip_ctx *c, RepPermCall &k) {
             if (!(tl[r] >= 0.0) || std::isinf(tl[r])) return fail("tolerances must be finite and not negative");
     for (int64_t i = 0; k.q && i < n_rows; ++i)
         if (k.q[i] < 0 || k.q[i] > REP_LEN_GROUPS_MAX_Q) return fail("row positions must lie in 0 .. 2^22");
+    for (int r = 0; k.x && r < n_rec; ++r) {
+        double lo = INFINITY, hi = -INFINITY;
+        for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) {
+            if (!std::isfinite(k.x[i])) return fail("record " + std::to_string(r) + ": row positions must be finite");
+            lo = std::min(lo, k.x[i]), hi = std::max(hi, k.x[i]);
+        }
+        if (rec_row_off[r + 1] > rec_row_off[r] && !std::isfinite(hi - lo))
+            return fail("record " + std::to_string(r) + ": the span of the row positions must be finite");
+    }
 
     DevBuf &a0 = k.seg_off ? s->q_a0 : s->p_a0;
     const int64_t a0_bytes = n_rows * (k.seg_off ? k.n_groups : 1) * 8;
@@ -1651,9 +1778,23 @@ static int rep_perm_launch_classes(scape_hip_ctx *c, RepPermCall &k, Kernel kern
     return 0;
 }
 
+// what a test of a range of items (pairs, markers) checks first: ready, the groups' match and the range
+// [first, first + count) of the builder's n_items
+static int rep_ranged_ok(scape_hip_ctx *c, const RepLabellings &l, const std::string &noun, int32_t n_items,
+                         int32_t first, int32_t count, int32_t n_rec, const int64_t *rec_row_off, int32_t n_groups,
+                         const int32_t *seg_off) {
+    if (l.ready(c->rep->n_cnt_rows) || rep_groups_match(l, n_groups, seg_off)) return 1;
+    if (first < 0 || count < 1 || first > n_items - count)
+        return fail(noun + "_first and " + noun + "_count must name " + noun + "s of the last " + l.builder + " call");
+    if (n_rec > 0 && rec_row_off && ((int64_t)count * n_rec > INT32_MAX || rec_row_off[n_rec] > INT64_MAX / 8 / count))
+        return fail("too many " + noun + "s x records or " + noun + "s x rows for one call: take the " + noun +
+                    "s in ranges");
+    return 0;
+}
+
 // The two tests of every item (pair, marker) of a range against the one compaction, by LDS class of records: behind
-// ready and the groups' match, the range [first, first + count) of the builder's n_items, prepare, the counters of
-// count x n_rec; pre(k) checks, allocates and queues what the kernel needs first, launch(k, recs, m, cap, lds) one class
+// rep_ranged_ok, prepare, the counters of count x n_rec; pre(k) checks, allocates and queues what the kernel needs
+// first, launch(k, recs, m, cap, lds) one class
 template <typename Kernel, typename Pre, typename Launch>
 static int rep_perm_ranged(scape_hip_ctx *c, const RepLabellings &l, const std::string &noun, int32_t n_items,
                            int32_t first, int32_t count, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -1661,12 +1802,7 @@ static int rep_perm_ranged(scape_hip_ctx *c, const RepLabellings &l, const std::
                            int64_t *site_n_ge_out, double *stat0_out, int64_t *gene_n_ge_out, Kernel kernel, Pre pre,
                            Launch launch) {
     ReportState *s = c->rep;
-    if (l.ready(s->n_cnt_rows) || rep_groups_match(l, n_groups, seg_off)) return 1;
-    if (first < 0 || count < 1 || first > n_items - count)
-        return fail(noun + "_first and " + noun + "_count must name " + noun + "s of the last " + l.builder + " call");
-    if (n_rec > 0 && rec_row_off && ((int64_t)count * n_rec > INT32_MAX || rec_row_off[n_rec] > INT64_MAX / 8 / count))
-        return fail("too many " + noun + "s x records or " + noun + "s x rows for one call: take the " + noun +
-                    "s in ranges");
+    if (rep_ranged_ok(c, l, noun, n_items, first, count, n_rec, rec_row_off, n_groups, seg_off)) return 1;
     RepPermCall k(c, l, n_rec, rec_row_off, rows, t_out);
     k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off, k.outs_ok = site_n_ge_out && stat0_out && gene_n_ge_out;
     if (rep_perm_prepare(c, k) || pre(k)) return 1;
@@ -1677,6 +1813,44 @@ static int rep_perm_ranged(scape_hip_ctx *c, const RepLabellings &l, const std::
             launch(k, recs, m, cap, lds);
         });
     });
+}
+
+// The test of the mean pA position by every item of a range, on the item's own rows: the checks of rep_perm_ranged and,
+// in prepare, those of the positions x and of REP_LEN_MAX_ROWS, all before anything is queued; no LDS classes and no
+// site counters; pre(k) as above, launch(k) queues the one kernel
+template <typename Pre, typename Launch>
+static int rep_perm_len_ranged(scape_hip_ctx *c, const RepLabellings &l, const std::string &noun, int32_t n_items,
+                               int32_t first, int32_t count, int32_t n_rec, const int64_t *rec_row_off,
+                               const int64_t *rows, int32_t n_groups, const int32_t *seg_off, const double *x,
+                               int64_t *t_out, int64_t *a0_out, double *delta0_out, int64_t *n_ge_out, Pre pre,
+                               Launch launch) {
+    ReportState *s = c->rep;
+    if (rep_ranged_ok(c, l, noun, n_items, first, count, n_rec, rec_row_off, n_groups, seg_off)) return 1;
+    RepPermCall k(c, l, n_rec, rec_row_off, rows, t_out);
+    k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off, k.x = x, k.max_rec_rows = REP_LEN_MAX_ROWS;
+    k.outs_ok = x && delta0_out && n_ge_out;
+    if (rep_perm_prepare(c, k) || pre(k)) return 1;
+    const int64_t n_out = (int64_t)count * n_rec;
+    if (s->l_w.ensure(k.n_rows * 8) || s->p_gene.ensure(n_out * 4) || s->p_stat0.ensure(n_out * 8)) return 1;
+    return rep_perm_count(c, k, 0, (int32_t)n_out, nullptr, n_ge_out, delta0_out, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(s->l_w.p, x, k.n_rows * 8, hipMemcpyHostToDevice, c->stream));
+        launch(k);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
+// per kept row and group the first nonzero of the group's segment, in x_seg, for the tests of pairs
+static int rep_pair_segments(scape_hip_ctx *c, const RepPermCall &k, int32_t n_groups) {
+    ReportState *s = c->rep;
+    const int64_t n_seg = k.n_rows * (n_groups + 1);
+    if ((n_seg + REP_THREADS - 1) / REP_THREADS > INT32_MAX) return fail("too many rows x groups for one call");
+    if (s->x_seg.ensure(n_seg * 8)) return 1;
+    hipLaunchKernelGGL(k_rep_pair_segidx, dim3((uint32_t)((n_seg + REP_THREADS - 1) / REP_THREADS)), dim3(REP_THREADS),
+                       0, c->stream, s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(), s->q_seg.as<int32_t>(), n_groups,
+                       k.n_rows, s->x_seg.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // the head of the two tests on scores: one segment [0, n), whose row sums restate t and land in the call's own buffer
@@ -1943,16 +2117,7 @@ int scape_hip_report_perm_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *
     return rep_perm_ranged(
         c, s->pair_masks, "pair", (int32_t)(s->x_pairs.size() / 8), pair_first, pair_count, n_rec, rec_row_off, rows,
         n_groups, seg_off, t_out, a0_out, site_n_ge_out, stat0_out, gene_n_ge_out, k_rep_perm_pairs,
-        [&](const RepPermCall &k) -> int {   // per kept row and group the first nonzero of the group's segment
-            const int64_t n_seg = k.n_rows * (n_groups + 1);
-            if ((n_seg + REP_THREADS - 1) / REP_THREADS > INT32_MAX) return fail("too many rows x groups for one call");
-            if (s->x_seg.ensure(n_seg * 8)) return 1;
-            hipLaunchKernelGGL(k_rep_pair_segidx, dim3((uint32_t)((n_seg + REP_THREADS - 1) / REP_THREADS)),
-                               dim3(REP_THREADS), 0, c->stream, s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
-                               s->q_seg.as<int32_t>(), n_groups, k.n_rows, s->x_seg.as<int64_t>());
-            HIPCHK(hipGetLastError());
-            return 0;
-        },
+        [&](const RepPermCall &k) -> int { return rep_pair_segments(c, k, n_groups); },
         [&](const RepPermCall &k, const int32_t *recs, int64_t m, int32_t cap, size_t lds) {
             hipLaunchKernelGGL(k_rep_perm_pairs, dim3((uint32_t)(m * k.n_tiles), (uint32_t)pair_count), dim3(REP_THREADS),
                                lds, c->stream, s->x_bits.as<unsigned long long>(), k.p_count, k.n_tiles, recs,
@@ -2040,6 +2205,45 @@ int scape_hip_report_perm_markers(scape_hip_ctx *c, int32_t n_rec, const int64_t
                                s->p_nz.as<uint2>(), s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_seg, marker_first,
                                k.n_rows, n_rec, cap, s->p_site.as<int32_t>(), s->p_gene.as<int32_t>(),
                                s->p_stat0.as<double>());
+        });
+}
+
+int scape_hip_report_perm_len_pairs(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                    int32_t n_groups, const int32_t *seg_off, int32_t pair_first, int32_t pair_count,
+                                    const double *x, int64_t *t_out, int64_t *a0_out, double *delta0_out,
+                                    int64_t *n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = report_state(c);
+    return rep_perm_len_ranged(
+        c, s->pair_masks, "pair", (int32_t)(s->x_pairs.size() / 8), pair_first, pair_count, n_rec, rec_row_off, rows,
+        n_groups, seg_off, x, t_out, a0_out, delta0_out, n_ge_out,
+        [&](const RepPermCall &k) -> int { return rep_pair_segments(c, k, n_groups); },
+        [&](const RepPermCall &k) {
+            hipLaunchKernelGGL(k_rep_perm_len_pairs, dim3((uint32_t)((int64_t)n_rec * k.n_tiles), (uint32_t)pair_count),
+                               dim3(REP_THREADS), 0, c->stream, s->x_bits.as<unsigned long long>(), k.p_count, k.n_tiles,
+                               s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
+                               s->q_a0.as<int64_t>(), n_groups, s->q_seg.as<int32_t>(),
+                               s->x_desc.as<RepPair>() + pair_first, s->l_w.as<double>(), n_rec,
+                               s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
+        });
+}
+
+int scape_hip_report_perm_len_markers(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                      int32_t n_seg, const int32_t *seg_off, int32_t marker_first, int32_t marker_count,
+                                      const double *x, int64_t *t_out, int64_t *a0_out, double *delta0_out,
+                                      int64_t *n_ge_out) {
+    CTX_ENTER(c);
+    ReportState *s = report_state(c);
+    return rep_perm_len_ranged(
+        c, s->marker_masks, "marker", n_seg - 1, marker_first, marker_count, n_rec, rec_row_off, rows, n_seg, seg_off, x,
+        t_out, a0_out, delta0_out, n_ge_out, [](const RepPermCall &) -> int { return 0; },
+        [&](const RepPermCall &k) {
+            hipLaunchKernelGGL(k_rep_perm_len_markers,
+                               dim3((uint32_t)((int64_t)n_rec * k.n_tiles), (uint32_t)marker_count), dim3(REP_THREADS), 0,
+                               c->stream, s->k_bits.as<unsigned long long>(), k.p_count, k.n_tiles, (k.n + 63) / 64,
+                               s->p_roff.as<int64_t>(), s->p_noff.as<int64_t>(), s->p_nz.as<uint2>(),
+                               s->p_t.as<int64_t>(), s->q_a0.as<int64_t>(), n_seg, marker_first, s->l_w.as<double>(),
+                               n_rec, s->p_gene.as<int32_t>(), s->p_stat0.as<double>());
         });
 }
 

@@ -1449,6 +1449,177 @@ def _diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str,
                            f"among {su.n} cells")
 
 
+# ---------------------------------------------------------------- diff_pa_len_pairs, diff_pa_len_markers
+# What lies behind a significant diff_pa_len_groups, as diff_pa_pairs and diff_pa_markers lie behind diff_pa_groups: every
+# pair of the populations, or every population against all other cells that have a cluster, tested as diff_pa_len tests
+# two, in one run.  Options, ident checks, populations, their order, column layout, labellings and file naming are
+# diff_pa_pairs's and diff_pa_markers's (_groups_setup).  Pair (A, B) is exactly `diff_pa_len --idents_1 A --idents_2 B`
+# and marker X exactly `diff_pa_len --idents_1 X` with the same --seed and --n_perm: the item's kept rows are the
+# record's label rows with a read in one of its cells (for a marker: in any tested cell, the same for every marker), it
+# tests a record when K > 1, two such rows or more remain, both of its populations have reads and span = max x - min x
+# over THOSE rows is > 0, and w_i = x_i - min x, tol = 2^-40 span, delta and n_ge are diff_pa_len's over those rows (the
+# device walks the one compaction and passes a row without a read in the item over; include/scape_hip.h).  One line per
+# (item, record the item tests); every field is diff_pa_len's on that pair or marker as text, p_val_adj aside, which is
+# Benjamini-Hochberg over ALL lines of the file: the correction across the runs of the loop.  A non-finite position of a
+# row with a read in any tested cell, in any record of K > 1, is diff_pa_len's ValueError.  No --strata_file.
+DIFF_PA_LEN_PAIRS_HEADER = DIFF_PA_LEN_HEADER[:1] + ["group_1", "group_2"] + DIFF_PA_LEN_HEADER[1:]
+DIFF_PA_LEN_MARKERS_HEADER = DIFF_PA_LEN_HEADER[:1] + ["group"] + DIFF_PA_LEN_HEADER[1:]
+MAX_LEN_BLOCK_RESULT_BYTES = 256 << 20    # host and device bytes of the counters of one call: more items are taken in ranges
+
+
+def _len_pair_items(su, sums):
+    """per pair (g, h), in the file's order: g, every row's reads in the two populations, and the two rows of the
+    record's exp_length table (below) that are its populations"""
+    G = len(su.sizes)
+    return [(g, sums[:, g] + sums[:, h], g, h) for g, h in zip(su.pairs[0].tolist(), su.pairs[1].tolist())], \
+        lambda cnt: cnt[:G]
+
+
+def _len_marker_items(su, sums):
+    """per marker g: g, every row's reads in the tested cells, and the rows of the record's exp_length table: the
+    markers' reads per label first, then those of every marker's rest"""
+    M = len(su.sizes)
+    t = sums.sum(axis=1)
+    return [(g, t, g, M + g) for g in range(M)], lambda cnt: np.concatenate([cnt[:M], cnt.sum(axis=0) - cnt[:M]])
+
+
+_LEN_BLOCK_TESTS = {"pair": ("scape_hip_report_perm_len_pairs", _len_pair_items),
+                    "marker": ("scape_hip_report_perm_len_markers", _len_marker_items)}
+
+
+def _diff_pa_len_blocks_batch(su, n_perm, noun, blocks, ctx, bat, chunk, times):
+    """one counted batch: the rows kept over all segments of its records with two segments or more with reads and a
+    span go through diff_pa_len's test of every item (pair, marker), the items in ranges of at most
+    MAX_LEN_BLOCK_RESULT_BYTES of counters; appends to blocks[k] what _diff_pa_len_batch appends for the two populations
+    of item k, per record that the item tests (decided here, from the sums and the positions)"""
+    recs, K = bat.recs, bat.K
+    pos = {}                     # record -> positions of its kept rows (f64, finite)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos))
+    sel = sel and _with_span(sel, pos, times)
+    if sel is None:
+        return
+    entry, items = _LEN_BLOCK_TESTS[noun]
+    call = entry[len("scape_hip_"):]
+    which, off, rows, sums, rowbase, xs = sel
+    n_seg, n_items, n_rows, n_rec = len(su.seg_off) - 1, len(blocks), len(rows), len(which)
+    x = np.ascontiguousarray(np.concatenate(xs))
+    t, a0 = np.zeros(n_rows, np.int64), np.zeros((n_rows, n_seg), np.int64)
+    delta0, n_ge = np.zeros((n_items, n_rec), np.float64), np.zeros((n_items, n_rec), np.int64)
+    step = int(max(1, min(n_items, MAX_LEN_BLOCK_RESULT_BYTES // (28 * n_rec))))
+
+    def test():
+        for k in range(0, n_items, step):
+            m = min(step, n_items - k)
+            check(getattr(ctx.lib, entry)(ctx.h, n_rec, ptr(off, P_i64), ptr(rows, P_i64), n_seg, ptr(su.seg_off, P_i32),
+                                          k, m, ptr(x), ptr(t, P_i64), ptr(a0, P_i64), ptr(delta0[k:k + m]),
+                                          ptr(n_ge[k:k + m], P_i64)), call)
+    _perm_chunks(ctx, su, n_perm, chunk, times, test)
+    t0 = timer()
+    _check_row_sums(call, t, a0, sums, sums)
+    rec_of = np.repeat(np.arange(n_rec), np.diff(off))
+    item_list, exp_rows = items(su, sums)
+    tested = np.zeros((n_items, n_rec), dtype=bool)
+    for k, (g, tk, _e1, _e2) in enumerate(item_list):
+        own = tk > 0
+        A, T = np.add.reduceat(sums[:, g], off[:-1]), np.add.reduceat(tk, off[:-1])
+        lo = np.minimum.reduceat(np.where(own, x, np.inf), off[:-1])
+        hi = np.maximum.reduceat(np.where(own, x, -np.inf), off[:-1])
+        with np.errstate(invalid="ignore"):
+            tested[k] = (np.bincount(rec_of[own], minlength=n_rec) >= 2) & (A > 0) & (A < T) & (hi - lo > 0)
+        if not np.all(delta0[k][~tested[k]] == 0.0):
+            r = int(np.nonzero(~tested[k] & (delta0[k] != 0.0))[0][0])
+            raise _lib.ScapeHipError(f"{call}: {recs[which[r]].gene_info_str}: the device's delta {delta0[k, r]!r} of a "
+                                     f"record that {noun} {k} does not test")
+    times["finish"] += timer() - t0
+    any_item = np.nonzero(tested.any(axis=0))[0]
+    if not len(any_item):
+        return
+    # the segments' counts of ALL K labels of the records that any item tests, for the reference's exp_pa_len
+    all_rows = np.concatenate([int(rowbase[r]) + np.arange(int(K[r]), dtype=np.int64) for r in which[any_item].tolist()])
+    full = np.zeros((len(all_rows), n_seg), dtype=np.int32)
+    full_nz = np.zeros((len(all_rows), n_seg), dtype=np.int32)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_group_sums(ctx.h, n_seg, ptr(su.seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
+                                              ptr(full, P_i32), ptr(full_nz, P_i32)), "report_group_sums")
+    times["render"] += timer() - t0
+    t0 = timer()
+    exp_len, k0 = {}, 0          # record -> exp_length of every population an item may name
+    for g in any_item.tolist():
+        r = which[g]
+        k = int(K[r])
+        cnt = exp_rows(full[k0:k0 + k].T.astype(np.int64))
+        counts = np.zeros((len(cnt), k + 1), dtype=np.int64)     # slot k: reads of no site, which never weigh
+        counts[:, :k] = cnt
+        k0 += k
+        exp_len[g] = _exp_len_rows(k, recs[r].alpha_arr, counts)
+    for k, (g, tk, e1, e2) in enumerate(item_list):
+        for j in np.nonzero(tested[k])[0].tolist():
+            r = which[j]
+            own = np.nonzero(tk[off[j]:off[j + 1]] > 0)[0]
+            xk = xs[j][own]
+            a = sums[off[j]:off[j + 1], g][own]
+            b = tk[off[j]:off[j + 1]][own] - a
+            m1, m2, d = _mean_positions(xk, a.tolist(), b.tolist())
+            if not abs(float(delta0[k, j]) - d) <= np.ldexp(float(xk.max() - xk.min()), -40):
+                raise _lib.ScapeHipError(f"{call}: {recs[r].gene_info_str}: the device's delta {delta0[k, j]!r} "
+                                         f"differs from {d!r}")
+            e = exp_len[j]
+            blocks[k].append((recs[r].gene_info_str, len(own), int(a.sum()), int(b.sum()), m1, m2, d, float(e[e1]),
+                              float(e[e2]), int(n_ge[k, j])))
+    times["finish"] += timer() - t0
+
+
+def _diff_pa_len_blocks(su, n_perm, device, noun, header, block_ids, tested_among):
+    """the run of diff_pa_len_pairs and diff_pa_len_markers: one block of the file per entry of block_ids = (the group
+    fields, versus); returns the file's path"""
+    blocks = [[] for _ in block_ids]
+
+    def write(w):
+        w.writerow(header)
+        out = [o for block in blocks for o in block]
+        if not out:
+            return
+        p_val = (1 + np.array([o[9] for o in out], dtype=np.int64)) / (1 + n_perm)
+        with np.errstate(invalid="ignore"):
+            d_exp = np.array([o[7] for o in out]) - np.array([o[8] for o in out])
+        ids = [ident for ident, block in zip(block_ids, blocks) for _o in block]
+        w.writerows([o[0], *groups, versus, o[1], o[2], o[3]] + [repr(v) for v in o[4:9]] + [repr(de), o[9], repr(p),
+                                                                                              repr(q), n_perm]
+                    for (groups, versus), o, de, p, q in zip(ids, out, d_exp.tolist(), p_val.tolist(),
+                                                             _bh(p_val).tolist()))
+
+    wall = _perm_run(su, n_perm, device, functools.partial(_diff_pa_len_blocks_batch, su, n_perm, noun, blocks), write)
+    print(f"Finish {n_perm} permutations of {len(blocks)} {noun}s {tested_among} for "
+          f"{sum(len(block) for block in blocks)} tested ({noun}, record) combinations")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+def _diff_pa_len_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
+                       seed: int = 1, device=None):
+    """diff_pa_len for every pair of the populations of a cluster file (every cluster, or the clusters `idents` in the
+    order given) from one pass over the result file; writes <cluster file stem>.<gene|utr>[.<A>+<B>+...]
+    .diff_pa_len_pairs.csv in output_dir, one block per pair, p_val_adj over the whole file, and returns its path"""
+    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_len_pairs", pairs=True)
+    names, sizes = su.names, su.sizes.tolist()
+    return _diff_pa_len_blocks(su, n_perm, device, "pair", DIFF_PA_LEN_PAIRS_HEADER,
+                               [((names[g], names[h]), f"{names[g]}_Vs_{names[h]}")
+                                for g, h in zip(su.pairs[0].tolist(), su.pairs[1].tolist())],
+                               f"of {len(sizes)} populations ({sum(sizes)} cells)")
+
+
+def _diff_pa_len_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents=(), n_perm: int = 9999,
+                         seed: int = 1, device=None):
+    """diff_pa_len of every cluster of a cluster file (or of the clusters `idents`, in the order given) against all
+    other cells that have a cluster, from one pass over the result file; writes <cluster file stem>.<gene|utr>
+    [.<A>+<B>+...].diff_pa_len_markers.csv in output_dir, one block per marker, p_val_adj over the whole file, and
+    returns its path"""
+    su = _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, "diff_pa_len_markers",
+                       markers=True)
+    return _diff_pa_len_blocks(su, n_perm, device, "marker", DIFF_PA_LEN_MARKERS_HEADER,
+                               [((name,), name) for name in su.names], f"among {su.n} cells")
+
+
 # ---------------------------------------------------------------- diff_pa_len_groups
 # The omnibus form of diff_pa_len: which records change their mean pA position (3'UTR length) across G = 2..64
 # populations at all, and which population has the longer or shorter 3'UTRs against all the others.  Options,
@@ -2091,8 +2262,8 @@ _perm_options = _options(
 
 
 def _idents_options(idents_help):
-    """diff_pa_groups, diff_pa_len_groups, diff_pa_pairs and diff_pa_markers (the help of --n_perm and --seed differs, and
-    diff_pa_markers has its own for --idents)"""
+    """diff_pa_groups, diff_pa_len_groups, diff_pa_pairs, diff_pa_markers, diff_pa_len_pairs and diff_pa_len_markers (the
+    help of --n_perm and --seed differs, and the two markers commands have their own for --idents)"""
     return _options(*_OUTPUT_OPTIONS, _CLUSTER_FILE_OPTION,
                     click.option('--idents', type=str, multiple=True, help=idents_help))
 
@@ -2193,6 +2364,34 @@ def diff_pa_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, 
     cells that have a cluster, as diff_pa tests one cluster against the rest, in one run over the result file: the
     markers of every cluster, with the p-values adjusted over all of them (Benjamini-Hochberg)."""
     _diff_pa_markers(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
+
+
+@click.command(name="diff_pa_len_pairs")
+@_groups_options
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels per pair; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives every pair the relabellings of '
+                   'diff_pa_len on its two clusters.')
+def diff_pa_len_pairs(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents, n_perm: int, seed: int):
+    """Every pair of the cell populations of a cluster file tested as diff_pa_len tests two, in one run over the result
+    file: the post-hoc tests behind diff_pa_len_groups, with the p-values adjusted over all pairs (Benjamini-Hochberg)."""
+    _diff_pa_len_pairs(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
+
+
+@click.command(name="diff_pa_len_markers")
+@_markers_options
+@click.option('--n_perm', type=int, default=9999, show_default=True,
+              help='Permutations of the cell labels per marker; the smallest p-value is 1 / (1 + n_perm).')
+@click.option('--seed', type=int, default=1, show_default=True,
+              help='Seed of the permutations, 0 .. 2^64 - 1. The same seed gives every marker the relabellings of '
+                   'diff_pa_len on that cluster against the rest.')
+def diff_pa_len_markers(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents, n_perm: int, seed: int):
+    """Every cell population of a cluster file (or each of the 1 to 64 named with --idents) tested against all other
+    cells that have a cluster, as diff_pa_len tests one cluster against the rest, in one run over the result file: the
+    clusters with longer or shorter 3'UTRs than the rest, with the p-values adjusted over all of them
+    (Benjamini-Hochberg)."""
+    _diff_pa_len_markers(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed)
 
 
 @click.command(name="diff_pa_trend")
