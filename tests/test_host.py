@@ -566,3 +566,125 @@ def test_column_class_ladder_covers_every_dispatch_threshold():
     generic = [c for c in fam["k2_estep"] if c > 16]            # ESTEP_DISPATCH: exact variants up to 16 columns
     assert "if constexpr (CM <= 16)" in open(os.path.join(ROOT, "scape_amd", "csrc", "em_lockstep.inc")).read()
     assert {cls(k) for k in MIXED_CAPS} == set(generic) and max_k in MIXED_CAPS
+
+
+def test_tensor_ladder_covers_every_boundary_of_the_tensor_build():
+    """tests/test_tensor_ladder.py runs Phase A and the three forms of Phase B on the batches of tests/tensor_ladder.py.
+    The boundaries are read here from the sources - row pitch, wavefront / workgroup / launch widths, PA_TT, TILE_ROWS,
+    PB_LOGCAP, PB_RING, PB_STEPS, the n_beta <= 16 of the form choice, the 8 of the XCD placement, the T_max cap - and
+    the ladder must have a value on both sides of each (whoever moves one has to move the ladder).  The form each case
+    expects is recomputed from those constants."""
+    import tensor_ladder as tl
+    src = open(os.path.join(ROOT, "scape_amd", "csrc", "scape_hip.hip")).read()
+    inc = open(os.path.join(ROOT, "scape_amd", "csrc", "phase_b_split.inc")).read()
+
+    def define(text, name):
+        found = re.findall(r"#define\s+%s\s+(\d+)\b" % name, text)
+        assert len(found) == 1, name
+        return int(found[0])
+    PITCH, TILE_ROWS, PA_TT = (define(src, n) for n in ("PITCH", "TILE_ROWS", "PA_TT"))
+    LOGCAP, RING, STEPS = (define(inc, n) for n in ("PB_LOGCAP", "PB_RING", "PB_STEPS"))
+    b_cap = {int(v) for v in re.findall(r"bool pb_slide = p->n_beta <= (\d+);", src) + re.findall(r"c->prm\.B <= (\d+) && !pb_v2", src)
+             + re.findall(r"if \(p->n_beta <= (\d+)\) \{   // the three-kernel Phase B", src)}
+    assert b_cap == {16}, b_cap
+    cap = re.search(r"c->pb_slide = pb_slide && W_max <= 4 \* PB_STEPS && T_max <= (\d+);", src)
+    assert cap and int(cap.group(1)) == 4096            # the cap exists; a 4097-point grid is not part of the ladder
+    xcd = re.findall(r"\(slot / (?:T_max|blocks_max)\) \* (\d+) \+ \(id & (\d+)\)", src + inc)
+    assert len(xcd) == 3 and set(xcd) == {("8", "7")}, xcd
+    wave_bins, wg_bins = re.search(r"const int n0 = (\d+) \* bb \+ (\d+) \* wave", inc).groups()[::-1]
+    wave_bins, wg_bins = int(wave_bins), int(wg_bins)
+    pa_lanes = int(re.search(r"__launch_bounds__\((\d+)\) void k_phase_a\(", src).group(1))
+    assert (wave_bins, wg_bins, pa_lanes) == (PITCH, 4 * PITCH, 256) and "(c->Np_max + 255) / 256, (c->T_max + PA_TT - 1) / PA_TT" in src
+
+    cases = {c.name: c for c in tl.cases()}
+    utrs = [q for c in cases.values() for q in c.preps]
+    assert all(q.N <= 257 and q.T <= 130 for q in utrs)
+    for q in utrs:
+        assert np.all(np.diff(q.x) >= 0) and np.all(np.diff(q.theta) >= 0)
+    # ---- N: one batch, a UTR on, below and above every bin-count boundary; unequal T, the largest not first
+    nc = cases["N"]
+    Ns, Ts = [q.N for q in nc.preps], [q.T for q in nc.preps]
+    assert Ns == list(tl.N_LADDER) and 1 in Ns
+    for b in (PITCH, wg_bins, pa_lanes):
+        assert {b - 1, b, b + 1} <= set(Ns), b
+    assert len(set(Ts)) == len(Ts) and Ts.index(max(Ts)) > 0
+    # ---- T: PA_TT and the ring, the interior range
+    all_T = {q.T for q in utrs}
+    for b in (PA_TT, RING):
+        assert {b - 1, b, b + 1} <= all_T, b
+    assert {1, 2} <= all_T
+
+    def interior(q):
+        step = q.theta[1] - q.theta[0] if q.T > 1 else 0.0
+        if not (step > 0 and np.all(np.floor(q.theta) == q.theta) and np.all(np.diff(q.theta) == step)):
+            return None
+        rmax = int(np.floor(3 * q.betas.max() / step)) + 1
+        return (q.T - 2 - rmax) - (rmax + 1) + 1
+    counts = {(c.name, q.T): interior(q) for c in cases.values() for q in c.preps}
+    assert counts[("T46", 46)] == 0 and cases["T46"].form == 0
+    assert [counts[("Tdef", t)] for t in tl.T_DEFAULT] == [1, 4, 5, 7] and cases["Tdef"].form == 2
+    assert [counts[("T12", t)] for t in tl.T_BETAS12] == [1, 3, 4, 5, 59, 60, 61, 64] and cases["T12"].form == 2
+    assert counts[("T12none", 1)] is None and counts[("T12none", 2)] < 1 and cases["T12none"].form == 0
+    assert {v % 4 for v in counts.values() if v is not None and v >= 4} == {0, 1, 2, 3}
+
+    def widest(q):
+        lo = np.searchsorted(q.theta, q.theta - 3 * q.betas.max(), "left")
+        hi = np.searchsorted(q.theta, q.theta + 3 * q.betas.max(), "right") - 1
+        return int((hi - lo + 1).max())
+    # ---- window width: the (PB_STEPS - 1)- and PB_STEPS-step instantiations, one grid too wide (demoted)
+    w = {taps: widest(cases[f"W{taps}"].preps[0]) for taps in tl.WIDTHS}
+    assert all(k == v for k, v in w.items()), w
+    steps = {taps: (taps + 3) // 4 for taps in w}
+    assert sorted(steps.values()) == [STEPS - 1, STEPS, STEPS, STEPS + 1]
+    assert max(t for t in w if t <= 4 * STEPS) >= 4 * STEPS - 1 and min(t for t in w if t > 4 * STEPS) == 4 * STEPS + 1
+    assert cases["W49"].form == 0 and all(cases[f"W{t}"].form == 2 for t in (43, 45, 47))
+    rw = cases["ringwrap"].preps[0]
+    assert rw.T > RING and widest(rw) >= 4 * (STEPS - 2) and cases["ringwrap"].form == 2
+    # inclusive window ends: on the default grid theta_i -+ 3 beta is a grid point at beta = 15, 30, 45, 60
+    q = cases["Tdef"].preps[-1]
+    i = q.T // 2
+    on = [b for b in q.betas if q.theta[i] - 3 * b in q.theta and q.theta[i] + 3 * b in q.theta]
+    assert on == [15.0, 30.0, 45.0, 60.0]
+    # ---- n_beta: both sides of the form choice, the guards below 16, tile crossings
+    assert {1, 3, 4, 5, 13} <= set(tl.N_BETA) and {max(b_cap), max(b_cap) + 1} <= set(tl.N_BETA)
+    for B in tl.N_BETA:
+        c = cases[f"B{B}"]
+        assert len(c.preps[0].betas) == B and c.form == (2 if B <= 16 else 0) and c.forms["split"] == (1 if B <= 16 else 0)
+        crosses = [i for i in range(c.preps[0].T) if (i * B) % TILE_ROWS + B > TILE_ROWS]       # an alpha's rows lie in two tiles
+        if B in (13, 16):
+            assert bool(crosses) == (B == 13), (B, crosses)
+    # ---- n_log: both sides of PB_LOGCAP, none, one, every bin; at n = 0, PITCH - 1, PITCH, N - 1; both kinds
+    lg = [(q.N, np.flatnonzero(~np.isnan(q.pa) | ~np.isnan(q.r))) for q in cases["nlog"].preps]
+    n_log = [len(b) for _, b in lg]
+    assert {0, 1, LOGCAP, LOGCAP + 1} <= set(n_log) and any(len(b) == N for N, b in lg)
+    singles = sorted(int(b[0]) for N, b in lg if len(b) == 1)
+    assert singles == [0, PITCH - 1, PITCH, 99]
+    for q in utrs:
+        if q.N > PITCH:
+            assert {0, PITCH - 1, PITCH, q.N - 1} <= set(np.flatnonzero(~np.isnan(q.pa) | ~np.isnan(q.r))) or any(q is p for p in cases["nlog"].preps)
+    assert any((~np.isnan(q.pa)).any() and (~np.isnan(q.r)).any() for q in cases["nlog"].preps)
+    # ---- n_utr: both sides of the XCD placement's 8, unequal T
+    xcds = int(xcd[0][0])
+    assert {1, xcds - 1, xcds, xcds + 1} <= set(tl.N_UTR)
+    for n in tl.N_UTR:
+        ps = cases[f"U{n}"].preps
+        assert len(ps) == n and (n == 1 or len({q.T for q in ps}) > 1)
+    # ---- grids
+    fr, rp = cases["fractional"].preps[0].theta, cases["repeated"].preps[0].theta
+    assert np.any(np.floor(fr) != fr) and len(set(np.diff(fr))) > 1 and np.all(fr * 4 == np.floor(fr * 4))
+    assert np.any(np.diff(rp) == 0) and np.all(np.diff(rp) >= 0)
+    assert cases["fractional"].form == 0 and cases["repeated"].form == 0 and cases["fractional"].forms["split"] == 1
+    # ---- values
+    for q in (cases["N"].preps[-1], cases["cut"].preps[0]):
+        u = q.theta[None, :] - q.x[:, None]
+        assert np.any(q.l[:, None] == u) and np.any(u < 0)
+        assert np.any(np.isin(q.pa[~np.isnan(q.pa)], q.theta)) and not np.all(np.isin(q.pa[~np.isnan(q.pa)], q.theta))
+    rs = np.concatenate([q.r[~np.isnan(q.r)] for q in utrs])
+    s = tl.S_DIS
+    assert rs.max() <= s.max() and np.any(rs < s[0]) and np.any(np.isin(rs, s)) and np.any(~np.isin(rs, s) & (rs > s[0]))
+    assert cases["cut"].preps[0].p["sigma_f"] == 10
+    # ---- the form every case expects, recomputed from the constants read above
+    for c in cases.values():
+        want = 2 if tl.expected_slide(c.preps, b_cap=max(b_cap), steps=STEPS, t_cap=int(cap.group(1))) else 0
+        assert c.form == want, (c.name, c.form, want)
+    assert {c.form for c in cases.values()} == {0, 2}
