@@ -1492,19 +1492,9 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_perm_len_trend(
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// One rule for every entry point below: once it has queued anything on the stream it returns, with 0 or with 1, only
-// after the stream has been waited for.  StreamDrain keeps it: armed before the first queueing, it waits when it goes
-// out of scope unless wait() has done so.  Host memory that a queued copy reads or writes outlives that wait: it sits in
-// the base of a test's frame (RepPermHost goes after RepPermCall's drain) or is declared ahead of a builder's drain.
-struct StreamDrain {
-    hipStream_t stream;
-    bool armed;
-    explicit StreamDrain(hipStream_t s, bool a = true) : stream(s), armed(a) {}
-    StreamDrain(const StreamDrain &) = delete;
-    StreamDrain &operator=(const StreamDrain &) = delete;
-    int wait() { armed = false; HIPCHK(hipStreamSynchronize(stream)); return 0; }
-    ~StreamDrain() { if (armed) (void)hipStreamSynchronize(stream); }
-};
+// Every entry point below keeps the drain rule (StreamDrain, scape_hip.hip): the host memory its queued copies read or
+// write sits in the base of a test's frame (RepPermHost goes after RepPermCall's drain) or is declared ahead of a
+// builder's drain.
 
 static const int32_t REP_PERM_CAPS[] = {4, 8, 16, 32, 64};   // rows of a record held in LDS at once (1 KiB each)
 static const int REP_PERM_N_CAPS = (int)(sizeof(REP_PERM_CAPS) / sizeof(REP_PERM_CAPS[0]));

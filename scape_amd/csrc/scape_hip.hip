@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <chrono>
@@ -703,6 +704,13 @@ __global__ __launch_bounds__(256) void k_labels(const UtrDesc *__restrict__ desc
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// scape_hip_ctx is the handle: stream, error word, counters, timing events, report state.  What lives as long as a loaded
+// batch is one BatchState that the handle owns and scape_hip_batch_free / scape_hip_destroy reset; its buffers are
+// DevBufs, which free themselves, so nothing keeps a release list.  The entry points are built from host-only halves
+// that make no HIP call (batch_plan, phase_b_choose, em_jobs_check, labels_check, em_plan: tools/batch_plan_check.cpp and
+// tools/em_schedule_check.cpp drive them on the CPU) and from the steps allocate / upload / launch / download; the ones
+// that queue copies on the caller's memory keep the drain rule (StreamDrain below).
+//
 // owns its device memory: freed when the buffer goes, so whoever holds one by value needs no release list
 struct DevBuf {
     void *p = nullptr;
@@ -749,6 +757,22 @@ struct DevBuf {
 static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value,
               "a copy of a DevBuf would free its memory twice");
 
+// One rule for every entry point that queues a copy from or into memory it does not own (the caller's arrays, host
+// vectors of its own): once it has queued anything on the stream it returns, with 0 or with 1, only after the stream has
+// been waited for.  StreamDrain keeps it: armed before the first queueing, it waits when it goes out of scope unless
+// wait() has done so.  Host memory that a queued copy reads or writes outlives that wait: it is the caller's, or it is
+// declared ahead of the drain (in perm.inc: in the base of a test's frame, RepPermHost goes after RepPermCall's drain).
+// The one exception is scape_hip_batch_build: it queues by design, touches no caller memory, and finish_build reads its flag.
+struct StreamDrain {
+    hipStream_t stream;
+    bool armed;
+    explicit StreamDrain(hipStream_t s, bool a = true) : stream(s), armed(a) {}
+    StreamDrain(const StreamDrain &) = delete;
+    StreamDrain &operator=(const StreamDrain &) = delete;
+    int wait() { armed = false; HIPCHK(hipStreamSynchronize(stream)); return 0; }
+    ~StreamDrain() { if (armed) (void)hipStreamSynchronize(stream); }
+};
+
 struct EventPair {
     hipEvent_t a, b;
 };
@@ -779,37 +803,66 @@ struct EmBufs {
                        rd_lw.as<double>(), rd_sv.as<double>(), V.as<double>(), Vsuf.as<double>(), voff.as<int64_t>(),
                        pt_score.as<double>(), pt_row.as<int32_t>(), ptoff.as<int64_t>()};
     }
-    void release() {
-        for (DevBuf *b : {&ia, &ib, &sia, &sib, &ws, &slw, &lb, &ell, &nlb, &status, &pend, &rd_k, &rd_lo, &rd_hi, &rd_m, &rd_n0, &rd_n1, &rd_lw,
-                          &rd_sv, &V, &Vsuf, &voff, &pt_score, &pt_row, &ptoff, &ujoff, &ujlist, &active, &elist, &dbg})
-            b->release();
-    }
+};
+
+// one queued copy to / from a DevBuf
+static int to_dev(hipStream_t s, const DevBuf &d, const void *src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, s));
+    return 0;
+}
+static int to_host(hipStream_t s, void *dst, const DevBuf &d, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, d.p, bytes, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// The job tables of scape_hip_batch_em, which sizes, uploads and downloads them: what the caller hands in, what it gets
+// back, and the rows that scape_hip_batch_em_fetch_lb gathers from lb afterwards.
+struct JobBufs {
+    DevBuf utr, K, fixed, a, b, ws, karr, ao, bo, wso, bic, nlb, lb, sel, lbsel;
+};
+// The model tables of scape_hip_batch_labels and the labels of every bin of the batch.
+struct LabelBufs {
+    DevBuf utr, K, a, b, ws, labels;
+};
+
+// What batch_plan (host only) works out of a batch's arrays: the per-UTR descriptors and the totals, maxima and Phase B
+// facts that the allocation, the build and the EM driver size themselves by.
+struct BatchShape {
+    int n_utr = 0, T_max = 0, Np_max = 0, W_max = 1, tiles_max_all = 1;
+    int64_t n_bins = 0;
+    std::vector<UtrDesc> h_desc;
+    size_t at_total = 0, m_total = 0, tiles_total = 0, n_theta_total = 0, mlog_total = 0, n_logbins = 0;
+    bool pb_slide = false;            // every UTR of the batch has a uniform theta grid with interior points: k_pb_logcol / k_pb_slide
+};
+struct BatchPlan : BatchShape {
+    std::vector<int32_t> loglist, logbin_utr;   // uploaded by the load, not kept: log-domain bins by UTR, and the UTR of each
+};
+
+// Everything with the lifetime of a loaded batch.  The handle owns one (scape_hip_ctx::batch): scape_hip_batch_load
+// makes it on first use and reuses its buffers from then on (DevBuf::ensure's headroom is there for the engine's wave
+// after wave), scape_hip_batch_free and scape_hip_destroy reset it, and every DevBuf in it frees itself.
+struct BatchState : BatchShape {
+    DevParams prm;
+    bool loaded = false, built = false;
+    bool build_unchecked = false;     // Phase A/B are queued, their device-side consistency flag has not been read yet
+    int pb_form = 0;                  // Phase B form of the last batch_build (scape_hip_batch_phase_b_form)
+    int last_em_jobs = 0;             // jobs of the last completed scape_hip_batch_em call (scape_hip_batch_em_fetch_lb)
+    DevBuf d_x, d_l, d_r, d_pa, d_cnt, d_theta, d_desc, d_loglist, d_AT, d_V, d_M, d_tile_nend;
+    DevBuf d_tbi, d_tbG, d_tbpm, d_mlog, d_logbin;   // Phase B: window tables, compact log-domain values, log bin -> UTR
+    JobBufs job;
+    LabelBufs lab;
+    EmBufs em;
 };
 
 #define N_COUNTERS (4 + 5 * 64 + 16 + 48)   // (+16: ESTEP_STAMPS, +48: M4_STAMPS tools builds) rounds, unused, z elements, unused, then five 64-way sharded counters (em_lockstep.inc)
+// What lives as long as the handle; the batch hangs off it.
 struct scape_hip_ctx {
     int device = 0;
     std::atomic<bool> busy{false};   // a handle serves one host thread at a time (scape_hip.h)
     hipStream_t stream = nullptr;
     char name[256] = {0};
-    DevParams prm;
-    bool loaded = false, built = false;
-    bool build_unchecked = false;     // Phase A/B are queued, their device-side consistency flag has not been read yet
-    int n_utr = 0, T_max = 0, Np_max = 0, W_max = 1;
-    int64_t n_bins = 0;
-    std::vector<UtrDesc> h_desc;
-    size_t at_total = 0, m_total = 0;
-    DevBuf d_x, d_l, d_r, d_pa, d_cnt, d_theta, d_desc, d_loglist, d_AT, d_V, d_M, d_err, d_counters, d_tile_nend;
-    DevBuf d_tbi, d_tbG, d_tbpm, d_mlog, d_logbin;   // Phase B: window tables, compact log-domain values, log bin -> UTR
-    size_t n_theta_total = 0, mlog_total = 0, n_logbins = 0;
-    int pb_form = 0;                  // Phase B form of the last batch_build (scape_hip_batch_phase_b_form)
-    bool pb_slide = false;            // every UTR of the batch has a uniform theta grid with interior points: k_pb_logcol / k_pb_slide
-    int tiles_max_all = 1;
-    size_t tiles_total = 0;
-    DevBuf j_utr, j_K, j_fixed, j_a, j_b, j_ws, j_karr, j_ao, j_bo, j_wso, j_bic, j_nlb, j_lb, j_sel, j_lbsel;
-    int last_em_jobs = 0;     // jobs of the last completed scape_hip_batch_em call (scape_hip_batch_em_fetch_lb)
-    DevBuf l_utr, l_K, l_a, l_b, l_ws, l_labels;
-    EmBufs em;
+    std::unique_ptr<BatchState> batch;   // null until the first scape_hip_batch_load and after scape_hip_batch_free
+    DevBuf d_err, d_counters;
     std::vector<EventPair> ev[6];
     double ms_acc[6] = {0, 0, 0, 0, 0, 0};
     int n_acc[6] = {0, 0, 0, 0, 0, 0};
@@ -872,6 +925,11 @@ struct BusyGuard {
 #define CTX_ENTER(c)                                                                                      \
     CTX_GUARD(c);                                                                                         \
     if (set_device(c)) return 1
+// the first lines of an entry point that works on the built batch: the guard, then `b`, the handle's batch
+#define BUILT_BATCH(c, b)                                                                                 \
+    CTX_GUARD(c);                                                                                         \
+    if (!(c)->batch || !(c)->batch->built) return fail("batch_build has not run");                        \
+    BatchState &b = *(c)->batch
 
 static void fill_params(DevParams &d, double mu_f, double sigma_f, double max_unif_ws, int B,
                         const double *betas, int S, const double *s, const double *pmf, int nround) {
@@ -903,41 +961,83 @@ static int max_window(const double *th, int T, double beta) {
     return best;
 }
 
-static int launch_phase_b(scape_hip_ctx *c, const DevParams &prm, int n_utr, int T_max, int Wmax,
-                          const UtrDesc *d_desc, const double *d_r, const double *d_pa,
-                          const double *d_theta, const int32_t *d_loglist, const double *d_AT,
-                          const double *d_V, double *d_M, int all_log, int32_t *d_tile_nend) {
-    if (c->d_err.ensure(sizeof(int))) return 1;
-    HIPCHK(hipMemsetAsync(c->d_err.p, 0, sizeof(int), c->stream));
-    const size_t lds = ((size_t)2 * prm.B * Wmax + prm.B) * sizeof(double) + (size_t)2 * (prm.B + 1) * sizeof(int) +
-                       (size_t)16 * (((Wmax + 3) & ~3) + 1) * sizeof(double);
-    if (lds > 150 * 1024) return fail("Phase B: window table does not fit LDS (n_beta x window too large)");
-    dim3 grid((unsigned)(((n_utr + 7) / 8) * 8 * T_max));
-#ifdef SCAPE_HIP_TOOLS   // tools-only builds (-DSCAPE_HIP_TOOLS): timing probe that switches parts of Phase B off - results are wrong with it
-    const char *pe = getenv("SCAPE_HIP_PB_PROBE");   // 1 no log path, 2 no linear path, 4 no G exps
-    const int probe = pe ? atoi(pe) : 0;
-#else
-    const int probe = 0;
-#endif
-    if (prm.B <= 16)
-        hipLaunchKernelGGL(k_phase_b<16>, grid, dim3(256), lds, c->stream, d_desc, prm, d_r, d_pa, d_theta,
-                           d_loglist, d_AT, d_V, d_M, Wmax, all_log, c->d_err.as<int>(), n_utr, T_max, d_tile_nend, probe);
-    else
-        hipLaunchKernelGGL(k_phase_b<1>, grid, dim3(256), lds, c->stream, d_desc, prm, d_r, d_pa, d_theta,
-                           d_loglist, d_AT, d_V, d_M, Wmax, all_log, c->d_err.as<int>(), n_utr, T_max, d_tile_nend, probe);
-    HIPCHK(hipGetLastError());
+// The Phase B a build queues and what its kernels need.  Form 0: k_phase_b (one kernel).  Form 1: tables + log bins,
+// then the matrix path per alpha (measured, round 3: 10.2 + 10.9 ms against 15.0 for k_phase_b - the log path's gather of
+// A[w][n] at a row pitch of 8.5 KB keeps the texture addresser busy).  Form 2: tables, log-bin columns, sliding windows.
+// The three give the same bits.
+struct PhaseB {
+    int form, Wmax, WP;
+    size_t lds;                          // form 0: k_phase_b
+    size_t lds_t, lds_l, lds_c, lds_s;   // forms 1 and 2: k_pb_tables, k_phase_b_lin, k_pb_logcol, k_pb_slide
+};
+// `mode` is SCAPE_HIP_PHASE_B: "v2" asks for form 0, "split" for form 1; otherwise form 2 where every theta grid of the
+// batch is uniform (slide), and form 0 where not or where n_beta > 16.  Host only.
+static int phase_b_choose(int B, int W_max, int T_max, bool slide, const char *mode, PhaseB &ch) {
+    const bool v2 = mode && strcmp(mode, "v2") == 0, split = mode && strcmp(mode, "split") == 0;
+    const int Wmax = W_max, WP = ((Wmax + 3) & ~3) + 1;
+    ch = PhaseB{0, Wmax, WP, 0, 0, 0, 0, 0};
+    if (B <= 16 && !v2 && (split || slide)) {
+        ch.form = split ? 1 : 2;
+        ch.lds_t = ((size_t)B * Wmax + 16) * sizeof(double) + 32 * sizeof(int);
+        ch.lds_l = ((size_t)16 * WP + 16 * PB_LOGCAP) * sizeof(double) + PB_LOGCAP * sizeof(int);
+        ch.lds_c = ((size_t)((T_max + 1) & ~1) + (size_t)B * Wmax) * sizeof(double) + 16 * sizeof(int);
+        ch.lds_s = ((size_t)16 * WP + 4 * PB_RING * 16) * sizeof(double);
+        if (ch.lds_t > 60 * 1024 || ch.lds_l > 60 * 1024) return fail("Phase B: window table does not fit LDS (n_beta x window too large)");
+        return 0;
+    }
+    ch.lds = ((size_t)2 * B * Wmax + B) * sizeof(double) + (size_t)2 * (B + 1) * sizeof(int) + (size_t)16 * WP * sizeof(double);
+    if (ch.lds > 150 * 1024) return fail("Phase B: window table does not fit LDS (n_beta x window too large)");
     return 0;
 }
 
-static int check_err_flag(scape_hip_ctx *c, const char *what);
-// reads the consistency flag of a queued batch_build (synchronises the stream)
-static int finish_build(scape_hip_ctx *c) {
-    if (!c->build_unchecked) return 0;
-    c->build_unchecked = false;
-    if (check_err_flag(c, "batch_build")) {
-        c->built = false;
-        return 1;
+// Queues the chosen Phase B on the buffers of `b`: a loaded batch, or the one UTR that
+// scape_hip_get_loglik_marginal_tensor sets up for itself (all_log: every bin takes the log-domain path; only d_desc,
+// d_theta, d_AT and d_M are there, the other pointers are null).
+static int queue_phase_b(scape_hip_ctx *c, const BatchState &b, const PhaseB &ch, int all_log = 0) {
+    const UtrDesc *desc = b.d_desc.as<UtrDesc>();
+    const double *r = b.d_r.as<double>(), *pa = b.d_pa.as<double>(), *theta = b.d_theta.as<double>(), *AT = b.d_AT.as<double>(),
+                 *V = b.d_V.as<double>();
+    const int32_t *loglist = b.d_loglist.as<int32_t>();
+    double *M = b.d_M.as<double>(), *mlog = b.d_mlog.as<double>(), *tbG = b.d_tbG.as<double>(), *tbpm = b.d_tbpm.as<double>();
+    int32_t *tbi = b.d_tbi.as<int32_t>(), *tile_nend = b.d_tile_nend.as<int32_t>();
+    if (c->d_err.ensure(sizeof(int))) return 1;
+    HIPCHK(hipMemsetAsync(c->d_err.p, 0, sizeof(int), c->stream));
+    const dim3 by_alpha((unsigned)(((b.n_utr + 7) / 8) * 8 * b.T_max));
+    if (ch.form == 0) {
+#ifdef SCAPE_HIP_TOOLS   // tools-only builds (-DSCAPE_HIP_TOOLS): timing probe that switches parts of Phase B off - results are wrong with it
+        const char *pe = getenv("SCAPE_HIP_PB_PROBE");   // 1 no log path, 2 no linear path, 4 no G exps
+        const int probe = pe ? atoi(pe) : 0;
+#else
+        const int probe = 0;
+#endif
+        if (b.prm.B <= 16)
+            hipLaunchKernelGGL(k_phase_b<16>, by_alpha, dim3(256), ch.lds, c->stream, desc, b.prm, r, pa, theta, loglist, AT, V, M,
+                               ch.Wmax, all_log, c->d_err.as<int>(), b.n_utr, b.T_max, tile_nend, probe);
+        else
+            hipLaunchKernelGGL(k_phase_b<1>, by_alpha, dim3(256), ch.lds, c->stream, desc, b.prm, r, pa, theta, loglist, AT, V, M,
+                               ch.Wmax, all_log, c->d_err.as<int>(), b.n_utr, b.T_max, tile_nend, probe);
+        HIPCHK(hipGetLastError());
+        return 0;
     }
+    const bool slide = ch.form == 2;
+    hipLaunchKernelGGL(k_pb_tables<16>, dim3((unsigned)b.T_max, (unsigned)b.n_utr), dim3(PB_TAB_THREADS), ch.lds_t, c->stream, desc,
+                       b.prm, theta, ch.Wmax, ch.WP, tbi, tbG, tbpm, c->d_err.as<int>(), b.T_max, slide ? nullptr : loglist, AT, M, mlog,
+                       tile_nend);
+    HIPCHK(hipGetLastError());
+    if (slide) {
+        if (b.n_logbins) {
+            hipLaunchKernelGGL(k_pb_logcol, dim3((unsigned)b.n_logbins), dim3(256), ch.lds_c, c->stream, desc, b.prm, theta, loglist,
+                               b.d_logbin.as<int32_t>(), AT, tbi, tbG, M, mlog, tile_nend, ch.Wmax);
+            HIPCHK(hipGetLastError());
+        }
+        const int blocks_max = (b.Np_max + 63) / 64;
+        hipLaunchKernelGGL(k_pb_slide, dim3((unsigned)(((b.n_utr + 7) / 8) * 8 * blocks_max)), dim3(256), ch.lds_s, c->stream, desc,
+                           b.prm, r, pa, loglist, V, M, mlog, ch.WP, tbi, tbpm, b.n_utr, blocks_max, tile_nend);
+    } else {
+        hipLaunchKernelGGL(k_phase_b_lin, by_alpha, dim3(256), ch.lds_l, c->stream, desc, b.prm, r, pa, loglist, V, M, mlog, ch.WP, tbi,
+                           tbpm, b.n_utr, b.T_max, tile_nend);
+    }
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -947,6 +1047,15 @@ static int check_err_flag(scape_hip_ctx *c, const char *what) {
     HIPCHK(hipStreamSynchronize(c->stream));
     if (flag) return fail(std::string(what) + ": device-side consistency check failed (flag " + std::to_string(flag) + ")");
     return 0;
+}
+
+// reads the consistency flag of a queued batch_build (synchronises the stream); a build that failed it is no build
+static int finish_build(scape_hip_ctx *c) {
+    BatchState *b = c->batch.get();
+    if (!b || !b->build_unchecked) return 0;
+    b->build_unchecked = false;
+    b->built = check_err_flag(c, "batch_build") == 0;
+    return !b->built;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1124,18 +1233,16 @@ static int em_choose(const EmPlan &p, const EmSwitches &sw, int n_jobs, int kmax
 }
 
 static int em_upload(scape_hip_ctx *c, const EmPlan &p, size_t nj, int kmax) {
-    EmBufs &e = c->em;
+    EmBufs &e = c->batch->em;
     const size_t nc = nj * p.depth;
-    if (e.ensure(nj, nc, kmax, c->n_utr, p.vtot, p.pttot)) return 1;
-    HIPCHK(hipMemcpyAsync(e.elist.p, p.elist.data(), nj * 4, hipMemcpyHostToDevice, c->stream));
-    if (!p.active.empty())
-        HIPCHK(hipMemcpyAsync(e.active.p, p.active.data(), p.active.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(e.voff.p, p.voff.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(e.ptoff.p, p.ptoff.data(), nc * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(e.ujoff.p, p.ujoff.data(), p.ujoff.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(e.ujlist.p, p.ujlist.data(), nc * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));  // the host vectors are pageable: the copies have left them now
-    return 0;
+    if (e.ensure(nj, nc, kmax, c->batch->n_utr, p.vtot, p.pttot)) return 1;
+    StreamDrain drain(c->stream);             // the plan's vectors are the caller's: they outlive this wait
+    hipStream_t s = c->stream;
+    if (to_dev(s, e.elist, p.elist.data(), nj * 4) || (!p.active.empty() && to_dev(s, e.active, p.active.data(), p.active.size() * 4)) ||
+        to_dev(s, e.voff, p.voff.data(), nc * 8) || to_dev(s, e.ptoff, p.ptoff.data(), nc * 8) ||
+        to_dev(s, e.ujoff, p.ujoff.data(), p.ujoff.size() * 8) || to_dev(s, e.ujlist, p.ujlist.data(), nc * 4))
+        return 1;
+    return drain.wait();                      // the host vectors are pageable: the copies have left them now
 }
 
 // One E-step launch.  The three kernels share their arguments up to the round number, which k2_estep_all_rounds
@@ -1143,12 +1250,13 @@ static int em_upload(scape_hip_ctx *c, const EmPlan &p, size_t nj, int kmax) {
 template <typename Kernel, typename... Round>
 static void launch_estep(scape_hip_ctx *c, Kernel kernel, unsigned threads, const EmState &S, int kmax, const int32_t *job_list,
                          int n_jobs, Round... round) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(((n_jobs + 7) / 8) * 8)), dim3(threads), 0, c->stream, c->d_desc.as<UtrDesc>(),
-                       c->prm, c->d_cnt.as<double>(), c->d_M.as<double>(), kmax, c->j_utr.as<int32_t>(), c->j_K.as<int32_t>(),
-                       c->j_fixed.as<int32_t>(), c->j_a.as<int32_t>(), c->j_b.as<int32_t>(), c->j_ws.as<double>(),
-                       c->j_karr.as<int8_t>(), S, c->j_ao.as<int32_t>(), c->j_bo.as<int32_t>(), c->j_wso.as<double>(),
-                       c->j_bic.as<double>(), c->j_nlb.as<int32_t>(), c->j_lb.as<double>(),
-                       c->d_counters.as<unsigned long long>(), round..., job_list, n_jobs);
+    const BatchState &b = *c->batch;
+    const JobBufs &j = b.job;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(((n_jobs + 7) / 8) * 8)), dim3(threads), 0, c->stream, b.d_desc.as<UtrDesc>(),
+                       b.prm, b.d_cnt.as<double>(), b.d_M.as<double>(), kmax, j.utr.as<int32_t>(), j.K.as<int32_t>(),
+                       j.fixed.as<int32_t>(), j.a.as<int32_t>(), j.b.as<int32_t>(), j.ws.as<double>(), j.karr.as<int8_t>(), S,
+                       j.ao.as<int32_t>(), j.bo.as<int32_t>(), j.wso.as<double>(), j.bic.as<double>(), j.nlb.as<int32_t>(),
+                       j.lb.as<double>(), c->d_counters.as<unsigned long long>(), round..., job_list, n_jobs);
 }
 
 // The E-step launches of pass r of a call that runs ahead: one per column slot (the last pass only finalises: one).
@@ -1163,16 +1271,17 @@ static void launch_estep_slots(scape_hip_ctx *c, Kernel kernel, const EmState &S
 template <typename Kernel, typename... Tail>
 static void launch_mstep(scape_hip_ctx *c, Kernel kernel, unsigned grid_y, unsigned threads, size_t lds, const EmState &S,
                          int n_active, int extent, Tail... tail) {
+    const BatchState &b = *c->batch;
     hipLaunchKernelGGL(kernel, dim3((unsigned)(((n_active + 7) / 8) * 8 * extent), grid_y), dim3(threads), lds, c->stream,
-                       c->d_desc.as<UtrDesc>(), c->prm, c->d_M.as<double>(), c->em.active.as<int32_t>(), n_active, extent,
-                       c->em.ujoff.as<int64_t>(), c->em.ujlist.as<int32_t>(), S.V, S.Vsuf, S.voff, S.rd_m, S.rd_lo, S.rd_hi,
-                       S.rd_lw, S.rd_sv, S.rd_n0, S.rd_n1, S.ptoff, S.pt_score, S.pt_row, c->d_tile_nend.as<int32_t>(),
+                       b.d_desc.as<UtrDesc>(), b.prm, b.d_M.as<double>(), b.em.active.as<int32_t>(), n_active, extent,
+                       b.em.ujoff.as<int64_t>(), b.em.ujlist.as<int32_t>(), S.V, S.Vsuf, S.voff, S.rd_m, S.rd_lo, S.rd_hi,
+                       S.rd_lw, S.rd_sv, S.rd_n0, S.rd_n1, S.ptoff, S.pt_score, S.pt_row, b.d_tile_nend.as<int32_t>(),
                        c->d_counters.as<unsigned long long>(), tail...);
 }
 
 // SCAPE_HIP_DEBUG: what the M-step of round r did, on stderr
 static int em_debug_round(scape_hip_ctx *c, int r, int nround) {
-    unsigned long long *dbg = c->em.dbg.as<unsigned long long>();
+    unsigned long long *dbg = c->batch->em.dbg.as<unsigned long long>();
     if (r < nround) {      // cumulative tensor bytes the M-step has asked for (its own tally), per round
         unsigned long long shard[64], tb = 0;
         HIPCHK(hipMemcpy(shard, c->d_counters.as<unsigned long long>() + CNT_MSTEP_TENSOR, sizeof(shard), hipMemcpyDeviceToHost));
@@ -1195,20 +1304,21 @@ static int em_debug_round(scape_hip_ctx *c, int r, int nround) {
 // the passes of one call: E-step, M-step, ... and a last E-step that finishes the jobs still running.  A job runs up
 // to p.depth rounds per pass (one k2_estep launch per slot) and at least one, so nround + 1 passes always do.
 static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, const EmKernels &k, int n_jobs, int kmax) {
-    const EmState S = c->em.state();
-    const int nround = c->prm.nround, n_active = (int)p.active.size();
-    const int32_t *jl = c->em.elist.as<int32_t>();
+    EmBufs &em = c->batch->em;
+    const EmState S = em.state();
+    const int nround = c->batch->prm.nround, n_active = (int)p.active.size();
+    const int32_t *jl = em.elist.as<int32_t>();
     unsigned long long *dbg = nullptr;
     if (sw.debug) {
-        if (c->em.dbg.ensure(24 * sizeof(unsigned long long))) return 1;
-        dbg = c->em.dbg.as<unsigned long long>();
+        if (em.dbg.ensure(24 * sizeof(unsigned long long))) return 1;
+        dbg = em.dbg.as<unsigned long long>();
         HIPCHK(hipMemsetAsync(dbg, 0, 24 * sizeof(unsigned long long), c->stream));
     }
     if (!p.any_m) {
         // only fixed-inference jobs (the ws-only re-fits of rm_component): all rounds in one launch (depth 1: columns = jobs)
         if (sw.fine && ev_begin(c, 4)) return 1;
         if (!with_column_class(EstepClasses{}, kmax + 1, [&](auto cm) {
-                launch_estep(c, k2_estep_all_rounds<decltype(cm)::value>, 64, S, kmax, c->em.ujlist.as<int32_t>(), n_jobs);
+                launch_estep(c, k2_estep_all_rounds<decltype(cm)::value>, 64, S, kmax, em.ujlist.as<int32_t>(), n_jobs);
             }))
             return fail("no E-step kernel for kmax " + std::to_string(kmax));
         HIPCHK(hipGetLastError());
@@ -1267,11 +1377,124 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
 // job tables are already on the device
 static int em_lockstep(scape_hip_ctx *c, int n_jobs, int kmax, const int32_t *job_utr, const int32_t *job_fixed) {
     const EmSwitches sw = em_switches();
-    const int depth = em_depth(c->h_desc, c->prm.B, sw, n_jobs, kmax, job_utr, job_fixed);
-    const EmPlan plan = em_plan(c->h_desc, c->prm.B, (size_t)n_jobs, job_utr, job_fixed, sw.size_order, depth);
+    const BatchState &b = *c->batch;
+    const int depth = em_depth(b.h_desc, b.prm.B, sw, n_jobs, kmax, job_utr, job_fixed);
+    const EmPlan plan = em_plan(b.h_desc, b.prm.B, (size_t)n_jobs, job_utr, job_fixed, sw.size_order, depth);
     EmKernels kernels;
     if (em_choose(plan, sw, n_jobs, kmax, kernels) || em_upload(c, plan, (size_t)n_jobs, kmax)) return 1;
     return em_rounds(c, plan, sw, kernels, n_jobs, kmax);
+}
+
+// ------------------------------------------------------------------------------------------
+// host-only halves of the batch entry points: no HIP call, no handle (tools/batch_plan_check.cpp drives them on the CPU)
+// ------------------------------------------------------------------------------------------
+// The descriptor walk of scape_hip_batch_load: per UTR its offsets into the ragged arrays, the tensors and the tile
+// extents, its log-domain bins and whether its theta grid is uniform; over the batch the totals, the maxima and whether
+// Phase B may slide.  The arguments are the load's, checked for NULL and the parameter ranges by the caller.
+static int batch_plan(const scape_hip_params &p, int n_utr, const int64_t *bin_off, const int64_t *theta_off,
+                      const double *all_theta, const double *r, const double *pa, const double *utr_L, const double *min_theta,
+                      const double *unif_ll, BatchPlan &out) {
+    BatchPlan s;
+    double bmax = p.betas[0];
+    for (int j = 1; j < p.n_beta; ++j) bmax = std::max(bmax, p.betas[j]);
+    s.h_desc.assign(n_utr, UtrDesc());
+    bool slide = p.n_beta <= 16;
+    for (int u = 0; u < n_utr; ++u) {
+        UtrDesc &d = s.h_desc[u];
+        const int64_t N = bin_off[u + 1] - bin_off[u], T = theta_off[u + 1] - theta_off[u];
+        if (N < 1 || T < 1 || N > (1 << 26) || T > 65535) return fail("UTR " + std::to_string(u) + ": bad n_frag / n_theta");
+        const double *th = all_theta + theta_off[u];
+        for (int64_t i = 1; i < T; ++i)
+            if (!(th[i] >= th[i - 1])) return fail("UTR " + std::to_string(u) + ": all_theta must be ascending");
+        d.bin_off = bin_off[u];
+        d.theta_off = theta_off[u];
+        d.N = (int)N;
+        d.Np = round_up((int)N, PITCH);
+        d.T = (int)T;
+        d.at_off = (int64_t)s.at_total;
+        d.m_off = (int64_t)s.m_total;
+        d.log_off = (int64_t)s.loglist.size();
+        d.tile_off = (int64_t)s.tiles_total;
+        const int nt = (int)((T * p.n_beta + TILE_ROWS - 1) / TILE_ROWS);
+        s.tiles_total += (size_t)nt;
+        s.tiles_max_all = std::max(s.tiles_max_all, nt);
+        for (int64_t n = 0; n < N; ++n)
+            if (!std::isnan(pa[bin_off[u] + n]) || !std::isnan(r[bin_off[u] + n])) s.loglist.push_back((int32_t)n);
+        d.n_log = (int)(s.loglist.size() - (size_t)d.log_off);
+        d.mlog_off = (int64_t)s.mlog_total;
+        if (d.n_log > 0 && d.n_log <= PB_LOGCAP) s.mlog_total += (size_t)T * p.n_beta * d.n_log;
+        s.logbin_utr.insert(s.logbin_utr.end(), (size_t)d.n_log, (int32_t)u);
+        // uniform grid of integer values: theta_w - theta_i is exact and depends on w - i only
+        d.c_lo = 1;
+        d.c_hi = 0;
+        const double step0 = (T > 1) ? th[1] - th[0] : 0.0;
+        bool uni = step0 > 0.0;
+        for (int64_t i = 0; i < T && uni; ++i) uni = std::floor(th[i]) == th[i] && (i == 0 || th[i] - th[i - 1] == step0);
+        if (uni) {
+            const int rmax = (int)std::floor(3 * bmax / step0) + 1;     // reach of the widest window in grid points, + 1 to spare
+            d.c_lo = rmax + 1;
+            d.c_hi = (int)T - 2 - rmax;
+        }
+        if (d.c_lo > d.c_hi) slide = false;
+        d.unif_ll = unif_ll[u];
+        d.L = utr_L[u];
+        d.min_theta = min_theta[u];
+        s.at_total += (size_t)T * d.Np;
+        s.m_total += (size_t)T * p.n_beta * d.Np;
+        s.T_max = std::max(s.T_max, d.T);
+        s.Np_max = std::max(s.Np_max, d.Np);
+        s.W_max = std::max(s.W_max, max_window(th, d.T, bmax));
+    }
+    s.n_utr = n_utr;
+    s.n_bins = bin_off[n_utr];
+    s.n_theta_total = (size_t)theta_off[n_utr];
+    s.n_logbins = s.logbin_utr.size();
+    s.pb_slide = slide && s.W_max <= 4 * PB_STEPS && s.T_max <= 4096;
+    out = std::move(s);
+    return 0;
+}
+
+// Host-side validation of scape_hip_batch_em's job tables: every index a kernel dereferences is checked here.
+static int em_jobs_check(const BatchState &b, int n_jobs, int kmax, const int32_t *job_utr, const int32_t *job_K,
+                         const int32_t *job_fixed, const int32_t *alpha_idx, const int32_t *beta_idx, const int8_t *k_arr) {
+    const int nround = b.prm.nround, B = b.prm.B;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int u = job_utr[j], K = job_K[j];
+        if (u < 0 || u >= b.n_utr) return fail("job " + std::to_string(j) + ": bad UTR index");
+        if (K < 0 || K > kmax) return fail("job " + std::to_string(j) + ": K out of range");
+        const int T = b.h_desc[u].T;
+        for (int k = 0; k < K; ++k) {
+            const int a = alpha_idx[(size_t)j * kmax + k], bi = beta_idx[(size_t)j * kmax + k];
+            if (a < 0 || a >= T || bi < 0 || bi >= B) return fail("job " + std::to_string(j) + ": alpha/beta index out of range");
+            if (k > 0 && a < alpha_idx[(size_t)j * kmax + k - 1]) return fail("job " + std::to_string(j) + ": alpha indices must be non-decreasing");
+        }
+        for (int t = 0; t < nround; ++t) {
+            const int k = k_arr[(size_t)j * nround + t];
+            if (k < 0 || k > K || (K > 0 && k >= K)) return fail("job " + std::to_string(j) + ": k_arr entry out of range");
+        }
+    }
+    // k2_mstep keeps the per-tile list of a UTR's jobs in a fixed LDS table (em_lockstep.inc, s_all)
+    std::vector<int32_t> per_utr(b.n_utr, 0);
+    for (int j = 0; j < n_jobs; ++j)
+        if (!job_fixed[j] && ++per_utr[job_utr[j]] > SCAPE_MAX_JOBS_PER_UTR)
+            return fail("UTR " + std::to_string(job_utr[j]) + ": more than " + std::to_string(SCAPE_MAX_JOBS_PER_UTR) +
+                        " non-fixed jobs in one call (split the call)");
+    return 0;
+}
+
+// The same for the model tables of scape_hip_batch_labels.
+static int labels_check(const BatchState &b, int n_sel, int kmax, const int32_t *sel_utr, const int32_t *sel_K,
+                        const int32_t *alpha_idx, const int32_t *beta_idx) {
+    for (int j = 0; j < n_sel; ++j) {
+        const int u = sel_utr[j], K = sel_K[j];
+        if (u < 0 || u >= b.n_utr) return fail("labels: bad UTR index");
+        if (K < 0 || K > kmax) return fail("labels: K out of range");
+        for (int k = 0; k < K; ++k) {
+            const int a = alpha_idx[(size_t)j * kmax + k], bi = beta_idx[(size_t)j * kmax + k];
+            if (a < 0 || a >= b.h_desc[u].T || bi < 0 || bi >= b.prm.B) return fail("labels: alpha/beta index out of range");
+        }
+    }
+    return 0;
 }
 
 static void report_release(scape_hip_ctx *c);   // report.inc
@@ -1311,27 +1534,18 @@ int scape_hip_device_name(scape_hip_ctx *c, char *buf, int buflen) {
 }
 
 int scape_hip_batch_free(scape_hip_ctx *c) {
-    if (!c) return fail("ctx is NULL");
     CTX_ENTER(c);
-    DevBuf *all[] = {&c->d_tbi, &c->d_tbG, &c->d_tbpm, &c->d_mlog, &c->d_logbin, &c->d_tile_nend, &c->d_x, &c->d_l, &c->d_r, &c->d_pa, &c->d_cnt, &c->d_theta, &c->d_desc, &c->d_loglist,
-                     &c->d_AT, &c->d_V, &c->d_M, &c->j_utr, &c->j_K, &c->j_fixed, &c->j_a, &c->j_b, &c->j_ws,
-                     &c->j_karr, &c->j_ao, &c->j_bo, &c->j_wso, &c->j_bic, &c->j_nlb, &c->j_lb, &c->l_utr,
-                     &c->l_K, &c->l_a, &c->l_b, &c->l_ws, &c->l_labels, &c->j_sel, &c->j_lbsel};
-    for (DevBuf *b : all) b->release();
-    c->em.release();
-    c->last_em_jobs = 0;
-    c->loaded = c->built = c->build_unchecked = false;
-    c->n_utr = 0;
+    c->batch.reset();   // every DevBuf of the batch frees itself, and none of its scalars outlives it
     return 0;
 }
 
-// every DevBuf of the handle must be gone or empty while the device is current and before the stream is destroyed:
-// `delete c` at the end finds nothing left to free
+// The handle's device memory goes while the device is current and before the stream is destroyed: the batch and the
+// report state each as one, the handle's own two buffers here, so that `delete c` finds nothing left to free.
 int scape_hip_destroy(scape_hip_ctx *c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    scape_hip_batch_free(c);
+    c->batch.reset();
     report_release(c);
     c->d_err.release();
     c->d_counters.release();
@@ -1346,41 +1560,40 @@ int scape_hip_destroy(scape_hip_ctx *c) {
 }
 
 // ---- operator level ------------------------------------------------------------------------
-static int op_common(scape_hip_ctx *c, int n, const double *const *in, int n_in, double **dev, double **dout) {
-    if (!c) return fail("ctx is NULL");
+// The frame of an operator call: its device arrays, which free themselves on every return, and the drain that waits
+// ahead of that for whatever the call has queued on the caller's arrays.
+struct OpCall {
+    DevBuf in[3], out;
+    StreamDrain drain;
+    explicit OpCall(scape_hip_ctx *c) : drain(c->stream, false) {}
+    double *dev(int i) const { return in[i].as<double>(); }
+};
+static int op_common(scape_hip_ctx *c, int n, const double *const *in, int n_in, OpCall &k) {
     if (n < 0) return fail("negative length");
     if (set_device(c)) return 1;
+    const size_t bytes = (size_t)n * sizeof(double);
     for (int i = 0; i < n_in; ++i) {
         if (!in[i] && n > 0) return fail("NULL input array");
-        HIPCHK(hipMalloc((void **)&dev[i], std::max<size_t>(16, (size_t)n * sizeof(double))));
-        if (n) HIPCHK(hipMemcpyAsync(dev[i], in[i], (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (k.in[i].ensure(std::max<size_t>(16, bytes))) return 1;
+        k.drain.armed = true;
+        if (n) HIPCHK(hipMemcpyAsync(k.in[i].p, in[i], bytes, hipMemcpyHostToDevice, c->stream));
     }
-    HIPCHK(hipMalloc((void **)dout, std::max<size_t>(16, (size_t)n * sizeof(double))));
-    return 0;
+    return k.out.ensure(std::max<size_t>(16, bytes));
 }
-static int op_finish(scape_hip_ctx *c, int n, double **dev, int n_in, double *dout, double *out) {
-    int rc = 0;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(std::string("kernel launch: ") + hipGetErrorString(e));
-    if (!rc && n) {
-        e = hipMemcpyAsync(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(std::string("copy back: ") + hipGetErrorString(e));
-    }
-    e = hipStreamSynchronize(c->stream);
-    if (!rc && e != hipSuccess) rc = fail(std::string("sync: ") + hipGetErrorString(e));
-    for (int i = 0; i < n_in; ++i) (void)hipFree(dev[i]);
-    (void)hipFree(dout);
-    return rc;
+static int op_finish(scape_hip_ctx *c, int n, OpCall &k, double *out) {
+    HIPCHK(hipGetLastError());
+    if (n) HIPCHK(hipMemcpyAsync(out, k.out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return k.drain.wait();
 }
 
 int scape_hip_loglik_xlr_t_pa(scape_hip_ctx *c, const double *x, const double *l, const double *pa,
                               int32_t n, double theta, double sigma_f, double *out) {
     CTX_GUARD(c);
     const double *in[3] = {x, l, pa};
-    double *dev[3] = {nullptr, nullptr, nullptr}, *dout = nullptr;
-    if (op_common(c, n, in, 3, dev, &dout)) return 1;
-    if (n) hipLaunchKernelGGL(k_op_pa, dim3((n + 255) / 256), dim3(256), 0, c->stream, dev[0], dev[1], dev[2], n, theta, sigma_f, dout);
-    return op_finish(c, n, dev, 3, dout, out);
+    OpCall k(c);
+    if (op_common(c, n, in, 3, k)) return 1;
+    if (n) hipLaunchKernelGGL(k_op_pa, dim3((n + 255) / 256), dim3(256), 0, c->stream, k.dev(0), k.dev(1), k.dev(2), n, theta, sigma_f, k.out.as<double>());
+    return op_finish(c, n, k, out);
 }
 
 int scape_hip_loglik_xlr_t_r_known(scape_hip_ctx *c, const double *x, const double *l, const double *r,
@@ -1391,10 +1604,10 @@ int scape_hip_loglik_xlr_t_r_known(scape_hip_ctx *c, const double *x, const doub
     DevParams P;
     fill_params(P, mu_f, sigma_f, 0, 0, nullptr, n_s, s_dis, pmf_s, 0);
     const double *in[3] = {x, l, r};
-    double *dev[3] = {nullptr, nullptr, nullptr}, *dout = nullptr;
-    if (op_common(c, n, in, 3, dev, &dout)) return 1;
-    if (n) hipLaunchKernelGGL(k_op_r_known, dim3((n + 255) / 256), dim3(256), 0, c->stream, dev[0], dev[1], dev[2], n, P, theta, dout);
-    return op_finish(c, n, dev, 3, dout, out);
+    OpCall k(c);
+    if (op_common(c, n, in, 3, k)) return 1;
+    if (n) hipLaunchKernelGGL(k_op_r_known, dim3((n + 255) / 256), dim3(256), 0, c->stream, k.dev(0), k.dev(1), k.dev(2), n, P, theta, k.out.as<double>());
+    return op_finish(c, n, k, out);
 }
 
 int scape_hip_loglik_xlr_t_r_unknown(scape_hip_ctx *c, const double *x, const double *l, const double *r,
@@ -1406,10 +1619,10 @@ int scape_hip_loglik_xlr_t_r_unknown(scape_hip_ctx *c, const double *x, const do
     DevParams P;
     fill_params(P, mu_f, sigma_f, 0, 0, nullptr, n_s, s_dis, pmf_s, 0);
     const double *in[2] = {x, l};
-    double *dev[2] = {nullptr, nullptr}, *dout = nullptr;
-    if (op_common(c, n, in, 2, dev, &dout)) return 1;
-    if (n) hipLaunchKernelGGL(k_op_r_unknown, dim3((n + 255) / 256), dim3(256), 0, c->stream, dev[0], dev[1], n, P, theta, dout);
-    return op_finish(c, n, dev, 2, dout, out);
+    OpCall k(c);
+    if (op_common(c, n, in, 2, k)) return 1;
+    if (n) hipLaunchKernelGGL(k_op_r_unknown, dim3((n + 255) / 256), dim3(256), 0, c->stream, k.dev(0), k.dev(1), n, P, theta, k.out.as<double>());
+    return op_finish(c, n, k, out);
 }
 
 int scape_hip_get_loglik_marginal_tensor(scape_hip_ctx *c, const double *all_theta, int32_t T,
@@ -1432,31 +1645,27 @@ int scape_hip_get_loglik_marginal_tensor(scape_hip_ctx *c, const double *all_the
     std::vector<double> at((size_t)T * Np, 0.0);
     for (int n = 0; n < N; ++n)
         for (int t = 0; t < T; ++t) at[(size_t)t * Np + n] = A[(size_t)n * T + t];
-    UtrDesc d;
-    memset(&d, 0, sizeof(d));
-    d.N = N;
-    d.Np = Np;
-    d.T = T;
-    DevBuf dAT, dM, dth, ddesc;
-    int rc = 0;
-    if (dAT.ensure(at.size() * sizeof(double)) || dM.ensure((size_t)T * B * Np * sizeof(double)) ||
-        dth.ensure((size_t)T * sizeof(double)) || ddesc.ensure(sizeof(UtrDesc)))
+    PhaseB ch;
+    if (phase_b_choose(B, Wmax, T, false, "v2", ch)) return 1;   // form 0, whatever the environment asks of a batch
+    BatchState t;   // one UTR of log-domain bins only, on buffers of the call's own: they free themselves with it
+    t.prm = P;
+    t.n_utr = 1;
+    t.T_max = T;
+    t.h_desc.assign(1, UtrDesc());
+    t.h_desc[0].N = N;
+    t.h_desc[0].Np = Np;
+    t.h_desc[0].T = T;
+    if (t.d_AT.ensure(at.size() * sizeof(double)) || t.d_M.ensure((size_t)T * B * Np * sizeof(double)) ||
+        t.d_theta.ensure((size_t)T * sizeof(double)) || t.d_desc.ensure(sizeof(UtrDesc)))
         return 1;
-    hipError_t e;
-    e = hipMemcpyAsync(dAT.p, at.data(), at.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dth.p, all_theta, (size_t)T * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ddesc.p, &d, sizeof(d), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return fail(std::string("upload: ") + hipGetErrorString(e));
-    rc = launch_phase_b(c, P, 1, T, Wmax, ddesc.as<UtrDesc>(), nullptr, nullptr, dth.as<double>(), nullptr,
-                        dAT.as<double>(), nullptr, dM.as<double>(), 1, nullptr);
-    if (!rc) rc = check_err_flag(c, "get_loglik_marginal_tensor");
-    if (!rc) {
-        e = hipMemcpy2DAsync(out, (size_t)N * sizeof(double), dM.p, (size_t)Np * sizeof(double),
-                             (size_t)N * sizeof(double), (size_t)T * B, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(std::string("copy back: ") + hipGetErrorString(e));
-    }
-    return rc;
+    StreamDrain drain(c->stream);   // `at` and `t` stand ahead of it
+    if (to_dev(c->stream, t.d_AT, at.data(), at.size() * sizeof(double)) || to_dev(c->stream, t.d_theta, all_theta, (size_t)T * sizeof(double)) ||
+        to_dev(c->stream, t.d_desc, t.h_desc.data(), sizeof(UtrDesc)) || queue_phase_b(c, t, ch, 1) ||
+        check_err_flag(c, "get_loglik_marginal_tensor"))
+        return 1;
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)N * sizeof(double), t.d_M.p, (size_t)Np * sizeof(double), (size_t)N * sizeof(double),
+                            (size_t)T * B, hipMemcpyDeviceToHost, c->stream));
+    return drain.wait();
 }
 
 // ---- batched level ---------------------------------------------------------------------------
@@ -1473,126 +1682,59 @@ int scape_hip_batch_load(scape_hip_ctx *c, const scape_hip_params *p, int32_t n_
         return fail("NULL array argument");
     CTX_ENTER(c);
     HIPCHK(hipStreamSynchronize(c->stream));   // a queued build of the previous batch still reads its buffers
-    c->loaded = c->built = c->build_unchecked = false;
-    fill_params(c->prm, p->mu_f, p->sigma_f, p->max_unif_ws, p->n_beta, p->betas, p->n_s, p->s_dis, p->pmf_s, p->nround);
-    double bmax = p->betas[0];
-    for (int j = 1; j < p->n_beta; ++j) bmax = std::max(bmax, p->betas[j]);
+    if (!c->batch) c->batch.reset(new BatchState());   // a loaded handle keeps its state: the buffers are reused
+    BatchState &b = *c->batch;
+    b.loaded = b.built = b.build_unchecked = false;   // a load refused below leaves the handle unloaded
+    BatchPlan plan;
+    if (batch_plan(*p, n_utr, bin_off, theta_off, all_theta, r, pa, utr_L, min_theta, unif_ll, plan)) return 1;
+    fill_params(b.prm, p->mu_f, p->sigma_f, p->max_unif_ws, p->n_beta, p->betas, p->n_s, p->s_dis, p->pmf_s, p->nround);
+    static_cast<BatchShape &>(b) = std::move(plan);   // the lists stay in `plan` for the upload
+    const std::vector<int32_t> &loglist = plan.loglist, &logbin_utr = plan.logbin_utr;
+    const int64_t nb = b.n_bins, nt = (int64_t)b.n_theta_total;
 
-    c->h_desc.assign(n_utr, UtrDesc());
-    std::vector<int32_t> loglist;
-    size_t at_total = 0, m_total = 0, tiles_total = 0, mlog_total = 0;
-    std::vector<int32_t> logbin_utr;
-    bool pb_slide = p->n_beta <= 16;
-    int T_max = 0, Np_max = 0, W_max = 1, tiles_max_all = 1;
-    for (int u = 0; u < n_utr; ++u) {
-        UtrDesc &d = c->h_desc[u];
-        const int64_t N = bin_off[u + 1] - bin_off[u], T = theta_off[u + 1] - theta_off[u];
-        if (N < 1 || T < 1 || N > (1 << 26) || T > 65535) return fail("UTR " + std::to_string(u) + ": bad n_frag / n_theta");
-        const double *th = all_theta + theta_off[u];
-        for (int64_t i = 1; i < T; ++i)
-            if (!(th[i] >= th[i - 1])) return fail("UTR " + std::to_string(u) + ": all_theta must be ascending");
-        d.bin_off = bin_off[u];
-        d.theta_off = theta_off[u];
-        d.N = (int)N;
-        d.Np = round_up((int)N, PITCH);
-        d.T = (int)T;
-        d.at_off = (int64_t)at_total;
-        d.m_off = (int64_t)m_total;
-        d.log_off = (int64_t)loglist.size();
-        d.tile_off = (int64_t)tiles_total;
-        {
-            const int nt = (int)((T * p->n_beta + TILE_ROWS - 1) / TILE_ROWS);
-            tiles_total += (size_t)nt;
-            tiles_max_all = std::max(tiles_max_all, nt);
-        }
-        for (int64_t n = 0; n < N; ++n)
-            if (!std::isnan(pa[bin_off[u] + n]) || !std::isnan(r[bin_off[u] + n])) loglist.push_back((int32_t)n);
-        d.n_log = (int)(loglist.size() - (size_t)d.log_off);
-        d.mlog_off = (int64_t)mlog_total;
-        if (d.n_log > 0 && d.n_log <= PB_LOGCAP) mlog_total += (size_t)T * p->n_beta * d.n_log;
-        logbin_utr.insert(logbin_utr.end(), (size_t)d.n_log, (int32_t)u);
-        {   // uniform grid of integer values: theta_w - theta_i is exact and depends on w - i only
-            d.c_lo = 1;
-            d.c_hi = 0;
-            const double step0 = (T > 1) ? th[1] - th[0] : 0.0;
-            bool uni = step0 > 0.0;
-            for (int64_t i = 0; i < T && uni; ++i) uni = std::floor(th[i]) == th[i] && (i == 0 || th[i] - th[i - 1] == step0);
-            if (uni) {
-                const int rmax = (int)std::floor(3 * bmax / step0) + 1;     // reach of the widest window in grid points, + 1 to spare
-                d.c_lo = rmax + 1;
-                d.c_hi = (int)T - 2 - rmax;
-            }
-            if (d.c_lo > d.c_hi) pb_slide = false;
-        }
-        d.unif_ll = unif_ll[u];
-        d.L = utr_L[u];
-        d.min_theta = min_theta[u];
-        at_total += (size_t)T * d.Np;
-        m_total += (size_t)T * p->n_beta * d.Np;
-        T_max = std::max(T_max, d.T);
-        Np_max = std::max(Np_max, d.Np);
-        W_max = std::max(W_max, max_window(th, d.T, bmax));
-    }
-    const int64_t nb = bin_off[n_utr], nt = theta_off[n_utr];
-    c->n_utr = n_utr;
-    c->n_bins = nb;
-    c->T_max = T_max;
-    c->Np_max = Np_max;
-    c->W_max = W_max;
-    c->at_total = at_total;
-    c->m_total = m_total;
-    c->tiles_total = tiles_total;
-    c->tiles_max_all = tiles_max_all;
-    c->n_theta_total = (size_t)nt;
-    c->mlog_total = mlog_total;
-    c->n_logbins = logbin_utr.size();
-    c->pb_slide = pb_slide && W_max <= 4 * PB_STEPS && T_max <= 4096;
     const bool trace_load = getenv("SCAPE_HIP_DEBUG") != nullptr;
     const auto t_alloc0 = std::chrono::steady_clock::now();
-    if (c->d_x.ensure(nb * 8) || c->d_l.ensure(nb * 8) || c->d_r.ensure(nb * 8) || c->d_pa.ensure(nb * 8) ||
-        c->d_cnt.ensure(nb * 8) || c->d_theta.ensure(nt * 8) || c->d_desc.ensure(n_utr * sizeof(UtrDesc)) ||
-        c->d_loglist.ensure(loglist.size() * 4) || c->d_AT.ensure(at_total * 8) || c->d_V.ensure(at_total * 8) ||
-        c->d_M.ensure(m_total * 8) || c->d_tile_nend.ensure(tiles_total * 4))
+    hipStream_t s = c->stream;
+    StreamDrain drain(s);   // `plan` and the descriptors stand ahead of it
+    if (b.d_x.ensure(nb * 8) || b.d_l.ensure(nb * 8) || b.d_r.ensure(nb * 8) || b.d_pa.ensure(nb * 8) ||
+        b.d_cnt.ensure(nb * 8) || b.d_theta.ensure(nt * 8) || b.d_desc.ensure(n_utr * sizeof(UtrDesc)) ||
+        b.d_loglist.ensure(loglist.size() * 4) || b.d_AT.ensure(b.at_total * 8) || b.d_V.ensure(b.at_total * 8) ||
+        b.d_M.ensure(b.m_total * 8) || b.d_tile_nend.ensure(b.tiles_total * 4))
         return 1;
     if (p->n_beta <= 16) {   // the three-kernel Phase B (phase_b_split.inc)
-        const size_t WP = (size_t)(((W_max + 3) & ~3) + 1);
-        if (c->d_tbi.ensure((size_t)nt * 40 * 4) || c->d_tbG.ensure((size_t)nt * 16 * 8) || c->d_tbpm.ensure((size_t)nt * 16 * WP * 8) ||
-            c->d_mlog.ensure(mlog_total * 8) || c->d_logbin.ensure(logbin_utr.size() * 4))
+        const size_t WP = (size_t)(((b.W_max + 3) & ~3) + 1);
+        if (b.d_tbi.ensure((size_t)nt * 40 * 4) || b.d_tbG.ensure((size_t)nt * 16 * 8) || b.d_tbpm.ensure((size_t)nt * 16 * WP * 8) ||
+            b.d_mlog.ensure(b.mlog_total * 8) || b.d_logbin.ensure(logbin_utr.size() * 4) ||
+            (!logbin_utr.empty() && to_dev(s, b.d_logbin, logbin_utr.data(), logbin_utr.size() * 4)))
             return 1;
-        if (!logbin_utr.empty())
-            HIPCHK(hipMemcpyAsync(c->d_logbin.p, logbin_utr.data(), logbin_utr.size() * 4, hipMemcpyHostToDevice, c->stream));
     }
     const auto t_up0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpyAsync(c->d_x.p, x, nb * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_l.p, l, nb * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_r.p, r, nb * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_pa.p, pa, nb * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_cnt.p, cnt, nb * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_theta.p, all_theta, nt * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_desc.p, c->h_desc.data(), n_utr * sizeof(UtrDesc), hipMemcpyHostToDevice, c->stream));
-    if (!loglist.empty())
-        HIPCHK(hipMemcpyAsync(c->d_loglist.p, loglist.data(), loglist.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (to_dev(s, b.d_x, x, nb * 8) || to_dev(s, b.d_l, l, nb * 8) || to_dev(s, b.d_r, r, nb * 8) || to_dev(s, b.d_pa, pa, nb * 8) ||
+        to_dev(s, b.d_cnt, cnt, nb * 8) || to_dev(s, b.d_theta, all_theta, nt * 8) ||
+        to_dev(s, b.d_desc, b.h_desc.data(), n_utr * sizeof(UtrDesc)) ||
+        (!loglist.empty() && to_dev(s, b.d_loglist, loglist.data(), loglist.size() * 4)))
+        return 1;
+    if (drain.wait()) return 1;
     if (trace_load) {
         const auto t1 = std::chrono::steady_clock::now();
         fprintf(stderr, "scape_hip_batch_load: %d UTRs, tensors %.2f GB, device buffers (re)allocated in %.1f ms, uploads %.1f ms\n", n_utr,
-                (double)(m_total + 2 * at_total) * 8e-9, std::chrono::duration<double, std::milli>(t_up0 - t_alloc0).count(),
+                (double)(b.m_total + 2 * b.at_total) * 8e-9, std::chrono::duration<double, std::milli>(t_up0 - t_alloc0).count(),
                 std::chrono::duration<double, std::milli>(t1 - t_up0).count());
     }
-    c->loaded = true;
+    b.loaded = true;
     return 0;
 }
 
 int scape_hip_batch_bytes(scape_hip_ctx *c, int64_t *bytes_batch, int64_t *bytes_free, int64_t *bytes_total) {
-    if (!c) return fail("ctx is NULL");
     CTX_ENTER(c);
     size_t f = 0, t = 0;
     HIPCHK(hipMemGetInfo(&f, &t));
+    const BatchState *b = c->batch.get();
     // (+ the column vectors and per-tile partials of the batch's EM calls so far: EM_DEPTH slots per job, EmBufs)
     if (bytes_batch)
-        *bytes_batch = c->loaded ? (int64_t)((2 * c->at_total + c->m_total) * 8 + c->n_bins * 40 + c->em.V.cap + c->em.Vsuf.cap +
-                                             c->em.pt_score.cap + c->em.pt_row.cap)
-                                 : 0;
+        *bytes_batch = b && b->loaded ? (int64_t)((2 * b->at_total + b->m_total) * 8 + b->n_bins * 40 + b->em.V.cap + b->em.Vsuf.cap +
+                                                  b->em.pt_score.cap + b->em.pt_row.cap)
+                                      : 0;
     if (bytes_free) *bytes_free = (int64_t)f;
     if (bytes_total) *bytes_total = (int64_t)t;
     return 0;
@@ -1600,75 +1742,33 @@ int scape_hip_batch_bytes(scape_hip_ctx *c, int64_t *bytes_batch, int64_t *bytes
 
 int scape_hip_batch_phase_b_form(scape_hip_ctx *c, int32_t *form) {
     if (!c || !form) return fail("ctx / form is NULL");
-    *form = c->pb_form;
+    BUILT_BATCH(c, b);
+    *form = b.pb_form;
     return 0;
 }
 
 int scape_hip_batch_build(scape_hip_ctx *c) {
-    if (!c) return fail("ctx is NULL");
-    if (!c->loaded) return fail("no batch loaded");
-    CTX_ENTER(c);
-    if (finish_build(c)) return 1;   // a second build on the handle must not wipe the first one's pending flag
-    dim3 grid((c->Np_max + 255) / 256, (c->T_max + PA_TT - 1) / PA_TT, c->n_utr);
+    CTX_GUARD(c);
+    if (!c->batch || !c->batch->loaded) return fail("no batch loaded");
+    BatchState &b = *c->batch;
+    if (set_device(c) || finish_build(c)) return 1;   // a second build on the handle must not wipe the first one's pending flag
+    PhaseB pb;                       // the environment is read at every build; a refusal leaves nothing queued
+    if (phase_b_choose(b.prm.B, b.W_max, b.T_max, b.pb_slide, getenv("SCAPE_HIP_PHASE_B"), pb)) return 1;
+    dim3 grid((b.Np_max + 255) / 256, (b.T_max + PA_TT - 1) / PA_TT, b.n_utr);
     if (ev_begin(c, 0)) return 1;
-    hipLaunchKernelGGL(k_phase_a, grid, dim3(256), 0, c->stream, c->d_desc.as<UtrDesc>(), c->prm, c->d_x.as<double>(),
-                       c->d_l.as<double>(), c->d_r.as<double>(), c->d_pa.as<double>(), c->d_theta.as<double>(),
-                       c->d_AT.as<double>(), c->d_V.as<double>());
+    hipLaunchKernelGGL(k_phase_a, grid, dim3(256), 0, c->stream, b.d_desc.as<UtrDesc>(), b.prm, b.d_x.as<double>(),
+                       b.d_l.as<double>(), b.d_r.as<double>(), b.d_pa.as<double>(), b.d_theta.as<double>(),
+                       b.d_AT.as<double>(), b.d_V.as<double>());
     HIPCHK(hipGetLastError());
-    if (ev_end(c, 0)) return 1;
-    if (ev_begin(c, 1)) return 1;
-    HIPCHK(hipMemsetAsync(c->d_tile_nend.p, 0, c->tiles_total * 4, c->stream));   // Phase B raises the extents by atomicMax
-    // SCAPE_HIP_PHASE_B = v2: k_phase_b (one kernel); split: tables + log bins, then the matrix path per alpha (measured,
-    // round 3: 10.2 + 10.9 ms against 15.0 for k_phase_b - the log path's gather of A[w][n] at a row pitch of 8.5 KB keeps
-    // the texture addresser busy); default where every theta grid is uniform: tables, log-bin columns, sliding windows
-    const char *pbm = getenv("SCAPE_HIP_PHASE_B");
-    const bool pb_v2 = pbm && strcmp(pbm, "v2") == 0, pb_split = pbm && strcmp(pbm, "split") == 0;
-    if (c->prm.B <= 16 && !pb_v2 && (pb_split || c->pb_slide)) {
-        const bool slide = c->pb_slide && !pb_split;
-        c->pb_form = slide ? 2 : 1;
-        if (c->d_err.ensure(sizeof(int))) return 1;
-        HIPCHK(hipMemsetAsync(c->d_err.p, 0, sizeof(int), c->stream));
-        const int Wmax = c->W_max, WP = ((Wmax + 3) & ~3) + 1, B = c->prm.B;
-        const size_t lds_t = ((size_t)B * Wmax + 16) * sizeof(double) + 32 * sizeof(int);
-        const size_t lds_l = ((size_t)16 * WP + 16 * PB_LOGCAP) * sizeof(double) + PB_LOGCAP * sizeof(int);
-        if (lds_t > 60 * 1024 || lds_l > 60 * 1024) return fail("Phase B: window table does not fit LDS (n_beta x window too large)");
-        hipLaunchKernelGGL(k_pb_tables<16>, dim3((unsigned)c->T_max, (unsigned)c->n_utr), dim3(PB_TAB_THREADS), lds_t, c->stream,
-                           c->d_desc.as<UtrDesc>(), c->prm, c->d_theta.as<double>(), Wmax, WP, c->d_tbi.as<int32_t>(), c->d_tbG.as<double>(),
-                           c->d_tbpm.as<double>(), c->d_err.as<int>(), c->T_max, slide ? nullptr : c->d_loglist.as<int32_t>(), c->d_AT.as<double>(),
-                           c->d_M.as<double>(), c->d_mlog.as<double>(), c->d_tile_nend.as<int32_t>());
-        HIPCHK(hipGetLastError());
-        if (slide) {
-            if (c->n_logbins) {
-                const size_t lds_c = ((size_t)((c->T_max + 1) & ~1) + (size_t)B * Wmax) * sizeof(double) + 16 * sizeof(int);
-                hipLaunchKernelGGL(k_pb_logcol, dim3((unsigned)c->n_logbins), dim3(256), lds_c, c->stream, c->d_desc.as<UtrDesc>(), c->prm,
-                                   c->d_theta.as<double>(), c->d_loglist.as<int32_t>(), c->d_logbin.as<int32_t>(), c->d_AT.as<double>(),
-                                   c->d_tbi.as<int32_t>(), c->d_tbG.as<double>(), c->d_M.as<double>(), c->d_mlog.as<double>(),
-                                   c->d_tile_nend.as<int32_t>(), Wmax);
-                HIPCHK(hipGetLastError());
-            }
-            const int blocks_max = (c->Np_max + 63) / 64;
-            const size_t lds_s = ((size_t)16 * WP + 4 * PB_RING * 16) * sizeof(double);
-            hipLaunchKernelGGL(k_pb_slide, dim3((unsigned)(((c->n_utr + 7) / 8) * 8 * blocks_max)), dim3(256), lds_s, c->stream,
-                               c->d_desc.as<UtrDesc>(), c->prm, c->d_r.as<double>(), c->d_pa.as<double>(), c->d_loglist.as<int32_t>(),
-                               c->d_V.as<double>(), c->d_M.as<double>(), c->d_mlog.as<double>(), WP, c->d_tbi.as<int32_t>(),
-                               c->d_tbpm.as<double>(), c->n_utr, blocks_max, c->d_tile_nend.as<int32_t>());
-        } else {
-            hipLaunchKernelGGL(k_phase_b_lin, dim3((unsigned)(((c->n_utr + 7) / 8) * 8 * c->T_max)), dim3(256), lds_l, c->stream,
-                               c->d_desc.as<UtrDesc>(), c->prm, c->d_r.as<double>(), c->d_pa.as<double>(), c->d_loglist.as<int32_t>(),
-                               c->d_V.as<double>(), c->d_M.as<double>(), c->d_mlog.as<double>(), WP, c->d_tbi.as<int32_t>(),
-                               c->d_tbpm.as<double>(), c->n_utr, c->T_max, c->d_tile_nend.as<int32_t>());
-        }
-        HIPCHK(hipGetLastError());
-    } else if ((c->pb_form = 0), launch_phase_b(c, c->prm, c->n_utr, c->T_max, c->W_max, c->d_desc.as<UtrDesc>(), c->d_r.as<double>(),
-                       c->d_pa.as<double>(), c->d_theta.as<double>(), c->d_loglist.as<int32_t>(),
-                       c->d_AT.as<double>(), c->d_V.as<double>(), c->d_M.as<double>(), 0, c->d_tile_nend.as<int32_t>()))
-        return 1;
-    if (ev_end(c, 1)) return 1;
+    if (ev_end(c, 0) || ev_begin(c, 1)) return 1;
+    HIPCHK(hipMemsetAsync(b.d_tile_nend.p, 0, b.tiles_total * 4, c->stream));   // Phase B raises the extents by atomicMax
+    b.pb_form = pb.form;
+    if (queue_phase_b(c, b, pb) || ev_end(c, 1)) return 1;
     // The kernels are only queued here: the caller's next call (normally scape_hip_batch_em, whose host-side table
     // checks then run while the GPU builds the tensors) launches behind them on the same stream, and reads the
     // consistency flag at its own synchronisation point.  SCAPE_HIP_SYNC_BUILD restores the synchronous behaviour.
-    c->build_unchecked = true;
-    c->built = true;
+    b.build_unchecked = true;
+    b.built = true;
     if (getenv("SCAPE_HIP_SYNC_BUILD") && finish_build(c)) return 1;
     return 0;
 }
@@ -1678,70 +1778,38 @@ int scape_hip_batch_em(scape_hip_ctx *c, int32_t n_jobs, int32_t kmax, const int
                        const int32_t *beta_idx, const double *ws, const int8_t *k_arr,
                        int32_t *alpha_idx_out, int32_t *beta_idx_out, double *ws_out, double *bic_out,
                        int32_t *n_lb_out, double *lb_out) {
-    if (!c) return fail("ctx is NULL");
-    if (!c->built) return fail("batch_build has not run");
+    BUILT_BATCH(c, b);
     if (n_jobs < 1) return fail("n_jobs < 1");
     if (kmax < 1 || kmax > SCAPE_MAX_K) return fail("kmax out of range");
     if (!job_utr || !job_K || !job_fixed || !alpha_idx || !beta_idx || !ws || !k_arr || !alpha_idx_out ||
         !beta_idx_out || !ws_out || !bic_out || !n_lb_out)
         return fail("NULL array argument");          // lb_out may be NULL: scape_hip_batch_em_fetch_lb
-    CTX_ENTER(c);
-    c->last_em_jobs = 0;
-    const int nround = c->prm.nround, B = c->prm.B;
-    // host-side validation: every index a kernel dereferences is checked here
-    for (int j = 0; j < n_jobs; ++j) {
-        const int u = job_utr[j], K = job_K[j];
-        if (u < 0 || u >= c->n_utr) return fail("job " + std::to_string(j) + ": bad UTR index");
-        if (K < 0 || K > kmax) return fail("job " + std::to_string(j) + ": K out of range");
-        const int T = c->h_desc[u].T;
-        for (int k = 0; k < K; ++k) {
-            const int a = alpha_idx[(size_t)j * kmax + k], b = beta_idx[(size_t)j * kmax + k];
-            if (a < 0 || a >= T || b < 0 || b >= B) return fail("job " + std::to_string(j) + ": alpha/beta index out of range");
-            if (k > 0 && a < alpha_idx[(size_t)j * kmax + k - 1]) return fail("job " + std::to_string(j) + ": alpha indices must be non-decreasing");
-        }
-        for (int t = 0; t < nround; ++t) {
-            const int k = k_arr[(size_t)j * nround + t];
-            if (k < 0 || k > K || (K > 0 && k >= K)) return fail("job " + std::to_string(j) + ": k_arr entry out of range");
-        }
-    }
-    {
-        // k2_mstep keeps the per-tile list of a UTR's jobs in a fixed LDS table (em_lockstep.inc, s_all)
-        std::vector<int32_t> per_utr(c->n_utr, 0);
-        for (int j = 0; j < n_jobs; ++j)
-            if (!job_fixed[j] && ++per_utr[job_utr[j]] > SCAPE_MAX_JOBS_PER_UTR)
-                return fail("UTR " + std::to_string(job_utr[j]) + ": more than " + std::to_string(SCAPE_MAX_JOBS_PER_UTR) +
-                            " non-fixed jobs in one call (split the call)");
-    }
-    const size_t nj = n_jobs;
-    if (c->j_utr.ensure(nj * 4) || c->j_K.ensure(nj * 4) || c->j_fixed.ensure(nj * 4) || c->j_a.ensure(nj * kmax * 4) ||
-        c->j_b.ensure(nj * kmax * 4) || c->j_ws.ensure(nj * (kmax + 1) * 8) || c->j_karr.ensure(nj * nround) ||
-        c->j_ao.ensure(nj * kmax * 4) || c->j_bo.ensure(nj * kmax * 4) || c->j_wso.ensure(nj * (kmax + 1) * 8) ||
-        c->j_bic.ensure(nj * 8) || c->j_nlb.ensure(nj * 4) || c->j_lb.ensure(nj * nround * 8))
+    if (set_device(c)) return 1;
+    b.last_em_jobs = 0;
+    if (em_jobs_check(b, n_jobs, kmax, job_utr, job_K, job_fixed, alpha_idx, beta_idx, k_arr)) return 1;
+    JobBufs &j = b.job;
+    hipStream_t s = c->stream;
+    const size_t nj = n_jobs, i4 = nj * 4, k4 = nj * kmax * 4, w8 = nj * (kmax + 1) * 8, ka = nj * b.prm.nround, lb8 = ka * 8;
+    if (j.utr.ensure(i4) || j.K.ensure(i4) || j.fixed.ensure(i4) || j.a.ensure(k4) || j.b.ensure(k4) || j.ws.ensure(w8) ||
+        j.karr.ensure(ka) || j.ao.ensure(k4) || j.bo.ensure(k4) || j.wso.ensure(w8) || j.bic.ensure(nj * 8) || j.nlb.ensure(i4) ||
+        j.lb.ensure(lb8))
         return 1;
-    HIPCHK(hipMemcpyAsync(c->j_utr.p, job_utr, nj * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->j_K.p, job_K, nj * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->j_fixed.p, job_fixed, nj * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->j_a.p, alpha_idx, nj * kmax * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->j_b.p, beta_idx, nj * kmax * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->j_ws.p, ws, nj * (kmax + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->j_karr.p, k_arr, nj * nround, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(c->j_lb.p, 0, nj * nround * 8, c->stream));
-    c->h_traffic[3] = 0;
-    if (ev_begin(c, 2)) return 1;
-    if (em_lockstep(c, n_jobs, kmax, job_utr, job_fixed)) return 1;
-    if (ev_end(c, 2)) return 1;
-    HIPCHK(hipMemcpyAsync(alpha_idx_out, c->j_ao.p, nj * kmax * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(beta_idx_out, c->j_bo.p, nj * kmax * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(ws_out, c->j_wso.p, nj * (kmax + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(bic_out, c->j_bic.p, nj * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(n_lb_out, c->j_nlb.p, nj * 4, hipMemcpyDeviceToHost, c->stream));
-    if (lb_out) HIPCHK(hipMemcpyAsync(lb_out, c->j_lb.p, nj * nround * 8, hipMemcpyDeviceToHost, c->stream));
     unsigned long long hc[N_COUNTERS];
-    HIPCHK(hipMemcpyAsync(hc, c->d_counters.p, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    StreamDrain drain(s);   // from here on the caller's arrays and `hc` have copies queued on them
+    if (to_dev(s, j.utr, job_utr, i4) || to_dev(s, j.K, job_K, i4) || to_dev(s, j.fixed, job_fixed, i4) || to_dev(s, j.a, alpha_idx, k4) ||
+        to_dev(s, j.b, beta_idx, k4) || to_dev(s, j.ws, ws, w8) || to_dev(s, j.karr, k_arr, ka))
+        return 1;
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, N_COUNTERS * sizeof(unsigned long long), s));
+    HIPCHK(hipMemsetAsync(j.lb.p, 0, lb8, s));
+    c->h_traffic[3] = 0;
+    if (ev_begin(c, 2) || em_lockstep(c, n_jobs, kmax, job_utr, job_fixed) || ev_end(c, 2)) return 1;
+    if (to_host(s, alpha_idx_out, j.ao, k4) || to_host(s, beta_idx_out, j.bo, k4) || to_host(s, ws_out, j.wso, w8) ||
+        to_host(s, bic_out, j.bic, nj * 8) || to_host(s, n_lb_out, j.nlb, i4) || (lb_out && to_host(s, lb_out, j.lb, lb8)) ||
+        to_host(s, hc, c->d_counters, sizeof(hc)))
+        return 1;
+    if (drain.wait()) return 1;
     if (finish_build(c)) return 1;        // a batch_build queued before this call: its flag is final now
-    c->last_em_jobs = n_jobs;
+    b.last_em_jobs = n_jobs;
 #ifdef M4_STAMPS   // tools-only: k4_mstep's half-chunk iterations by running column groups and wavefront role (whole call)
     {
         const unsigned long long *st = hc + 4 + 5 * 64 + 16;
@@ -1786,89 +1854,71 @@ int scape_hip_batch_em_fetch_lb(scape_hip_ctx *c, int32_t n_sel, const int32_t *
     if (n_sel < 1 || !job_idx || !lb_out) return fail("fetch_lb: bad arguments");
     CTX_ENTER(c);
     if (finish_build(c)) return 1;
-    if (c->last_em_jobs < 1) return fail("fetch_lb: no completed scape_hip_batch_em call on this handle");
+    BatchState *b = c->batch.get();
+    if (!b || b->last_em_jobs < 1) return fail("fetch_lb: no completed scape_hip_batch_em call on this handle");
     for (int i = 0; i < n_sel; ++i)
-        if (job_idx[i] < 0 || job_idx[i] >= c->last_em_jobs) return fail("fetch_lb: job index out of range");
-    const int nround = c->prm.nround;
-    if (c->j_sel.ensure((size_t)n_sel * 4) || c->j_lbsel.ensure((size_t)n_sel * nround * 8)) return 1;
-    HIPCHK(hipMemcpyAsync(c->j_sel.p, job_idx, (size_t)n_sel * 4, hipMemcpyHostToDevice, c->stream));
+        if (job_idx[i] < 0 || job_idx[i] >= b->last_em_jobs) return fail("fetch_lb: job index out of range");
+    const int nround = b->prm.nround;
+    JobBufs &j = b->job;
+    if (j.sel.ensure((size_t)n_sel * 4) || j.lbsel.ensure((size_t)n_sel * nround * 8)) return 1;
+    StreamDrain drain(c->stream);
+    if (to_dev(c->stream, j.sel, job_idx, (size_t)n_sel * 4)) return 1;
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n_sel * nround + 255) / 256)), dim3(256), 0, c->stream,
-                       c->j_lb.as<double>(), c->j_sel.as<int32_t>(), c->j_lbsel.as<double>(), nround, n_sel);
+                       j.lb.as<double>(), j.sel.as<int32_t>(), j.lbsel.as<double>(), nround, n_sel);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(lb_out, c->j_lbsel.p, (size_t)n_sel * nround * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return to_host(c->stream, lb_out, j.lbsel, (size_t)n_sel * nround * 8) || drain.wait();
 }
 
 int scape_hip_batch_labels(scape_hip_ctx *c, int32_t n_sel, int32_t kmax, const int32_t *sel_utr,
                            const int32_t *sel_K, const int32_t *alpha_idx, const int32_t *beta_idx,
                            const double *ws, int32_t *labels_out) {
-    if (!c) return fail("ctx is NULL");
-    if (!c->built) return fail("batch_build has not run");
+    BUILT_BATCH(c, b);
     if (n_sel < 1) return fail("n_sel < 1");
     if (kmax < 1 || kmax > SCAPE_MAX_K) return fail("kmax out of range");
     if (!sel_utr || !sel_K || !alpha_idx || !beta_idx || !ws || !labels_out) return fail("NULL array argument");
-    CTX_ENTER(c);
-    const int B = c->prm.B;
-    for (int j = 0; j < n_sel; ++j) {
-        const int u = sel_utr[j], K = sel_K[j];
-        if (u < 0 || u >= c->n_utr) return fail("labels: bad UTR index");
-        if (K < 0 || K > kmax) return fail("labels: K out of range");
-        for (int k = 0; k < K; ++k) {
-            const int a = alpha_idx[(size_t)j * kmax + k], b = beta_idx[(size_t)j * kmax + k];
-            if (a < 0 || a >= c->h_desc[u].T || b < 0 || b >= B) return fail("labels: alpha/beta index out of range");
-        }
-    }
-    const size_t ns = n_sel;
-    if (c->l_utr.ensure(ns * 4) || c->l_K.ensure(ns * 4) || c->l_a.ensure(ns * kmax * 4) || c->l_b.ensure(ns * kmax * 4) ||
-        c->l_ws.ensure(ns * (kmax + 1) * 8) || c->l_labels.ensure((size_t)c->n_bins * 4))
+    if (set_device(c)) return 1;
+    if (labels_check(b, n_sel, kmax, sel_utr, sel_K, alpha_idx, beta_idx)) return 1;
+    LabelBufs &lab = b.lab;
+    hipStream_t s = c->stream;
+    const size_t ns = n_sel, i4 = ns * 4, k4 = ns * kmax * 4, w8 = ns * (kmax + 1) * 8;
+    if (lab.utr.ensure(i4) || lab.K.ensure(i4) || lab.a.ensure(k4) || lab.b.ensure(k4) || lab.ws.ensure(w8) ||
+        lab.labels.ensure((size_t)b.n_bins * 4))
         return 1;
-    HIPCHK(hipMemcpyAsync(c->l_utr.p, sel_utr, ns * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->l_K.p, sel_K, ns * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->l_a.p, alpha_idx, ns * kmax * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->l_b.p, beta_idx, ns * kmax * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->l_ws.p, ws, ns * (kmax + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (ev_begin(c, 3)) return 1;
+    StreamDrain drain(s);
+    if (to_dev(s, lab.utr, sel_utr, i4) || to_dev(s, lab.K, sel_K, i4) || to_dev(s, lab.a, alpha_idx, k4) ||
+        to_dev(s, lab.b, beta_idx, k4) || to_dev(s, lab.ws, ws, w8) || ev_begin(c, 3))
+        return 1;
     if (!with_column_class(LabelClasses{}, kmax + 1, [&](auto cm) {
-            hipLaunchKernelGGL(k_labels<decltype(cm)::value>, dim3(n_sel), dim3(256), 0, c->stream, c->d_desc.as<UtrDesc>(), c->prm,
-                               c->d_cnt.as<double>(), c->d_M.as<double>(), kmax, c->l_utr.as<int32_t>(), c->l_K.as<int32_t>(),
-                               c->l_a.as<int32_t>(), c->l_b.as<int32_t>(), c->l_ws.as<double>(), c->l_labels.as<int32_t>());
+            hipLaunchKernelGGL(k_labels<decltype(cm)::value>, dim3(n_sel), dim3(256), 0, c->stream, b.d_desc.as<UtrDesc>(), b.prm,
+                               b.d_cnt.as<double>(), b.d_M.as<double>(), kmax, lab.utr.as<int32_t>(), lab.K.as<int32_t>(),
+                               lab.a.as<int32_t>(), lab.b.as<int32_t>(), lab.ws.as<double>(), lab.labels.as<int32_t>());
         }))
         return fail("no label kernel for kmax " + std::to_string(kmax));
     HIPCHK(hipGetLastError());
     if (ev_end(c, 3)) return 1;
     // copy back only the selected UTRs' bins; contiguous runs of selected UTRs go in one transfer
-    {
-        std::vector<char> sel(c->n_utr, 0);
-        for (int j = 0; j < n_sel; ++j) sel[sel_utr[j]] = 1;
-        int u = 0;
-        while (u < c->n_utr) {
-            if (!sel[u]) {
-                ++u;
-                continue;
-            }
-            int v = u;
-            while (v + 1 < c->n_utr && sel[v + 1]) ++v;
-            const int64_t b0 = c->h_desc[u].bin_off, b1 = c->h_desc[v].bin_off + c->h_desc[v].N;
-            HIPCHK(hipMemcpyAsync(labels_out + b0, c->l_labels.as<int32_t>() + b0, (size_t)(b1 - b0) * 4,
-                                  hipMemcpyDeviceToHost, c->stream));
-            u = v + 1;
-        }
+    std::vector<char> sel(b.n_utr, 0);
+    for (int j = 0; j < n_sel; ++j) sel[sel_utr[j]] = 1;
+    for (int u = 0; u < b.n_utr; ++u) {
+        if (!sel[u]) continue;
+        int v = u;
+        while (v + 1 < b.n_utr && sel[v + 1]) ++v;
+        const int64_t b0 = b.h_desc[u].bin_off, b1 = b.h_desc[v].bin_off + b.h_desc[v].N;
+        HIPCHK(hipMemcpyAsync(labels_out + b0, lab.labels.as<int32_t>() + b0, (size_t)(b1 - b0) * 4, hipMemcpyDeviceToHost, s));
+        u = v;
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (finish_build(c)) return 1;
-    return 0;
+    if (drain.wait()) return 1;
+    return finish_build(c);
 }
 
 int scape_hip_batch_fetch_loglik(scape_hip_ctx *c, int32_t utr, double *A_out) {
     if (!c || !A_out) return fail("NULL argument");
-    if (!c->built) return fail("batch_build has not run");
-    if (utr < 0 || utr >= c->n_utr) return fail("bad UTR index");
-    CTX_ENTER(c);
-    if (finish_build(c)) return 1;
-    const UtrDesc &d = c->h_desc[utr];
+    BUILT_BATCH(c, b);
+    if (utr < 0 || utr >= b.n_utr) return fail("bad UTR index");
+    if (set_device(c) || finish_build(c)) return 1;
+    const UtrDesc &d = b.h_desc[utr];
     std::vector<double> at((size_t)d.T * d.Np);
-    HIPCHK(hipMemcpy(at.data(), c->d_AT.as<double>() + d.at_off, at.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(at.data(), b.d_AT.as<double>() + d.at_off, at.size() * 8, hipMemcpyDeviceToHost));
     for (int n = 0; n < d.N; ++n)
         for (int t = 0; t < d.T; ++t) A_out[(size_t)n * d.T + t] = at[(size_t)t * d.Np + n];
     return 0;
@@ -1876,18 +1926,16 @@ int scape_hip_batch_fetch_loglik(scape_hip_ctx *c, int32_t utr, double *A_out) {
 
 int scape_hip_batch_fetch_tensor(scape_hip_ctx *c, int32_t utr, double *M_out) {
     if (!c || !M_out) return fail("NULL argument");
-    if (!c->built) return fail("batch_build has not run");
-    if (utr < 0 || utr >= c->n_utr) return fail("bad UTR index");
-    CTX_ENTER(c);
-    if (finish_build(c)) return 1;
-    const UtrDesc &d = c->h_desc[utr];
-    HIPCHK(hipMemcpy2D(M_out, (size_t)d.N * 8, c->d_M.as<double>() + d.m_off, (size_t)d.Np * 8, (size_t)d.N * 8,
-                       (size_t)d.T * c->prm.B, hipMemcpyDeviceToHost));
+    BUILT_BATCH(c, b);
+    if (utr < 0 || utr >= b.n_utr) return fail("bad UTR index");
+    if (set_device(c) || finish_build(c)) return 1;
+    const UtrDesc &d = b.h_desc[utr];
+    HIPCHK(hipMemcpy2D(M_out, (size_t)d.N * 8, b.d_M.as<double>() + d.m_off, (size_t)d.Np * 8, (size_t)d.N * 8,
+                       (size_t)d.T * b.prm.B, hipMemcpyDeviceToHost));
     return 0;
 }
 
 int scape_hip_timing_reset(scape_hip_ctx *c) {
-    if (!c) return fail("ctx is NULL");
     CTX_ENTER(c);
     if (ev_collect(c)) return 1;
     for (int w = 0; w < 6; ++w) {
@@ -1898,7 +1946,6 @@ int scape_hip_timing_reset(scape_hip_ctx *c) {
 }
 
 int scape_hip_timing_get(scape_hip_ctx *c, int32_t which, double *ms_total, int32_t *n_launches) {
-    if (!c) return fail("ctx is NULL");
     if (which < 0 || which > 5) return fail("which out of range");
     CTX_ENTER(c);
     if (ev_collect(c)) return 1;

@@ -584,17 +584,19 @@ def test_tensor_ladder_covers_every_boundary_of_the_tensor_build():
         return int(found[0])
     PITCH, TILE_ROWS, PA_TT = (define(src, n) for n in ("PITCH", "TILE_ROWS", "PA_TT"))
     LOGCAP, RING, STEPS = (define(inc, n) for n in ("PB_LOGCAP", "PB_RING", "PB_STEPS"))
-    b_cap = {int(v) for v in re.findall(r"bool pb_slide = p->n_beta <= (\d+);", src) + re.findall(r"c->prm\.B <= (\d+) && !pb_v2", src)
-             + re.findall(r"if \(p->n_beta <= (\d+)\) \{   // the three-kernel Phase B", src)}
-    assert b_cap == {16}, b_cap
-    cap = re.search(r"c->pb_slide = pb_slide && W_max <= 4 \* PB_STEPS && T_max <= (\d+);", src)
+    # the three places that hold it: batch_plan's walk, phase_b_choose, the load's allocation of the Phase B tables
+    b_caps = [re.findall(r"bool slide = p\.n_beta <= (\d+);", src), re.findall(r"if \(B <= (\d+) && !v2 && \(split \|\| slide\)\)", src),
+              re.findall(r"if \(p->n_beta <= (\d+)\) \{   // the three-kernel Phase B", src)]
+    assert b_caps == [["16"]] * 3, b_caps
+    b_cap = {16}
+    cap = re.search(r"s\.pb_slide = slide && s\.W_max <= 4 \* PB_STEPS && s\.T_max <= (\d+);", src)
     assert cap and int(cap.group(1)) == 4096            # the cap exists; a 4097-point grid is not part of the ladder
     xcd = re.findall(r"\(slot / (?:T_max|blocks_max)\) \* (\d+) \+ \(id & (\d+)\)", src + inc)
     assert len(xcd) == 3 and set(xcd) == {("8", "7")}, xcd
     wave_bins, wg_bins = re.search(r"const int n0 = (\d+) \* bb \+ (\d+) \* wave", inc).groups()[::-1]
     wave_bins, wg_bins = int(wave_bins), int(wg_bins)
     pa_lanes = int(re.search(r"__launch_bounds__\((\d+)\) void k_phase_a\(", src).group(1))
-    assert (wave_bins, wg_bins, pa_lanes) == (PITCH, 4 * PITCH, 256) and "(c->Np_max + 255) / 256, (c->T_max + PA_TT - 1) / PA_TT" in src
+    assert (wave_bins, wg_bins, pa_lanes) == (PITCH, 4 * PITCH, 256) and "(b.Np_max + 255) / 256, (b.T_max + PA_TT - 1) / PA_TT" in src
 
     cases = {c.name: c for c in tl.cases()}
     utrs = [q for c in cases.values() for q in c.preps]
