@@ -57,6 +57,7 @@ struct EmState {
     int32_t *rd_k, *rd_lo, *rd_hi, *rd_m;   // round descriptor: component, row window [lo,hi), has M-step
     int32_t *rd_n0, *rd_n1;           // bins [n0,n1) outside which v is exactly 0
     double *rd_lw, *rd_sv;            // log w_k (new), sum_n v[n]
+    double *rd_fl;                    // the score of a row that is all sentinel on the support of v: log w_k sum v + SENT sum v
     double *V;                        // ragged [column][Np]
     double *Vsuf;                     // ragged [column][Np/16 + 1]: Vsuf[b] = sum_{n >= 16 b} V[n] (summed from the end)
     const int64_t *voff;              // [columns]
@@ -134,6 +135,7 @@ __device__ __forceinline__ EstepNext estep_body(
     const size_t col0 = (size_t)job * depth, col = col0 + slot;
     int pre_m[EM_DEPTH], pre_lo[EM_DEPTH], pre_hi[EM_DEPTH], pre_k[EM_DEPTH];
     int64_t pre_ptoff[EM_DEPTH];
+    double pre_fl[EM_DEPTH];
     bool rdm = false;
 #pragma unroll
     for (int q = 0; q < EM_DEPTH; ++q) {
@@ -143,6 +145,7 @@ __device__ __forceinline__ EstepNext estep_body(
         pre_hi[q] = on ? S.rd_hi[col0 + q] : 0;
         pre_k[q] = on ? S.rd_k[col0 + q] : 0;
         pre_ptoff[q] = on ? S.ptoff[col0 + q] : 0;
+        pre_fl[q] = on ? S.rd_fl[col0 + q] : 0.0;
         rdm = rdm || pre_m[q] != 0;
     }
     const int64_t pre_voff = S.voff[col];
@@ -179,9 +182,17 @@ __device__ __forceinline__ EstepNext estep_body(
         pt_best_r[q] = pre_lo[q];
         if (pre_m[q]) {   // per-tile partials of a pending grid arg-max (wave-uniform condition)
             const int t0 = pre_lo[q] / MT_ROWS, t1 = (pre_hi[q] - 1) / MT_ROWS;
+            // Rows that are all sentinel on the support of v are tied exactly (max_alpha_beta gives the first of them),
+            // but a tile sums the sentinel terms below its finite extent by the MFMA chain and the rest from the suffix
+            // sums: tiles of different extent round the same score differently, and a later tile could win.  Every such
+            // evaluation lies within (4 Np + 16) u of the floor (Np roundings each for the suffix sums and the chain, on
+            // either side): a tile score that close to the floor IS the floor, and the first tile keeps the tie.  A row with
+            // a finite entry that cannot lift it out of that band cannot be told from the floor by any f64 evaluation.
+            const double fl = pre_fl[q], ftol = (4.0 * d.Np + 16.0) * 1.1102230246251565e-16 * fabs(fl);
             for (int t = t0 + lane; t <= t1; t += 64) {
-                const double sc = S.pt_score[pre_ptoff[q] + t];
+                double sc = S.pt_score[pre_ptoff[q] + t];
                 const int rr = S.pt_row[pre_ptoff[q] + t];
+                if (fabs(sc - fl) <= ftol) sc = fl;
                 if (sc > pt_best[q]) {
                     pt_best[q] = sc;
                     pt_best_r[q] = rr;
@@ -659,6 +670,7 @@ __device__ __forceinline__ EstepNext estep_body(
         nz_hi = max(nz_hi, __shfl_xor(nz_hi, off, 64));
     }
     ESTEP_STAMP(st3);
+    double v_total = 0.0;             // sum_n v[n] as the suffix sums have it (Vsuf[0])
     if (!fixed && k < K) {
         // suffix sums of v at 16-bin boundaries, accumulated from the last bin backwards (a tail of 1e-100
         // next to a head of 1e3 must come out as 1e-100: the M-step multiplies it by the sentinel)
@@ -695,6 +707,7 @@ __device__ __forceinline__ EstepNext estep_body(
             }
         }
         if (lane == 0) Sj[Np >> 4] = 0.0;
+        v_total = carry;
     }
     ESTEP_STAMP(st4);
     // elbo (:559-561), stopping rule (:743-746), this round's M-step descriptor (:507-523)
@@ -717,6 +730,7 @@ __device__ __forceinline__ EstepNext estep_body(
             S.rd_hi[col] = (hi + 1) * B;
             S.rd_lw[col] = d_logw(wk_new);
             S.rd_sv[col] = sv;
+            S.rd_fl[col] = d_logw(wk_new) * sv + SENT * v_total;
             S.rd_n0[col] = (nz_hi >= 0) ? nz_lo : 0;
             S.rd_n1[col] = (nz_hi >= 0) ? nz_hi + 1 : 0;
             atomicAdd(&counters[CNT_SLAB + (job & 63)], (unsigned long long)(hi + 1 - lo) * B * (unsigned long long)N);

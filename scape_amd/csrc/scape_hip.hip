@@ -782,7 +782,7 @@ struct ReportState;   // report.inc
 // Device buffers of the lock-step EM (em_lockstep.inc): the per-job state the kernels see as an EmState, the index
 // tables of a call's plan (EmPlan) and the debug histogram of SCAPE_HIP_DEBUG.
 struct EmBufs {
-    DevBuf ia, ib, sia, sib, ws, slw, lb, ell, nlb, status, pend, rd_k, rd_lo, rd_hi, rd_m, rd_n0, rd_n1, rd_lw, rd_sv, V, Vsuf,
+    DevBuf ia, ib, sia, sib, ws, slw, lb, ell, nlb, status, pend, rd_k, rd_lo, rd_hi, rd_m, rd_n0, rd_n1, rd_lw, rd_sv, rd_fl, V, Vsuf,
         voff, pt_score, pt_row, ptoff;             // one per EmState member, in its order
     DevBuf ujoff, ujlist, active, elist, dbg;
     // nc = column slots of the call (jobs x depth): what the M-step reads and writes is per column
@@ -791,7 +791,7 @@ struct EmBufs {
                ws.ensure(nj * (kmax + 1) * 8) || slw.ensure(nj * (kmax + 1) * 8) || lb.ensure(nj * 8) || ell.ensure(nj * 8) ||
                nlb.ensure(nj * 4) || status.ensure(nj * 4) || pend.ensure(nj * 8) || rd_k.ensure(nc * 4) || rd_lo.ensure(nc * 4) ||
                rd_hi.ensure(nc * 4) || rd_m.ensure(nc * 4) || rd_n0.ensure(nc * 4) || rd_n1.ensure(nc * 4) ||
-               rd_lw.ensure(nc * 8) || rd_sv.ensure(nc * 8) || V.ensure(vtot * 8) || Vsuf.ensure((vtot / 16 + nc + 1) * 8) ||
+               rd_lw.ensure(nc * 8) || rd_sv.ensure(nc * 8) || rd_fl.ensure(nc * 8) || V.ensure(vtot * 8) || Vsuf.ensure((vtot / 16 + nc + 1) * 8) ||
                voff.ensure(nc * 8) || pt_score.ensure(pttot * 8) || pt_row.ensure(pttot * 4) || ptoff.ensure(nc * 8) ||
                ujoff.ensure((n_utr + 1) * 8) || ujlist.ensure(nc * 4) || active.ensure(n_utr * 4) || elist.ensure(nj * 4);
     }
@@ -800,7 +800,7 @@ struct EmBufs {
                        lb.as<double>(), ell.as<double>(), nlb.as<int32_t>(), status.as<int32_t>(), pend.as<unsigned long long>(),
                        rd_k.as<int32_t>(),
                        rd_lo.as<int32_t>(), rd_hi.as<int32_t>(), rd_m.as<int32_t>(), rd_n0.as<int32_t>(), rd_n1.as<int32_t>(),
-                       rd_lw.as<double>(), rd_sv.as<double>(), V.as<double>(), Vsuf.as<double>(), voff.as<int64_t>(),
+                       rd_lw.as<double>(), rd_sv.as<double>(), rd_fl.as<double>(), V.as<double>(), Vsuf.as<double>(), voff.as<int64_t>(),
                        pt_score.as<double>(), pt_row.as<int32_t>(), ptoff.as<int64_t>()};
     }
 };

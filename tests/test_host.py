@@ -690,3 +690,113 @@ def test_tensor_ladder_covers_every_boundary_of_the_tensor_build():
         want = 2 if tl.expected_slide(c.preps, b_cap=max(b_cap), steps=STEPS, t_cap=int(cap.group(1))) else 0
         assert c.form == want, (c.name, c.form, want)
     assert {c.form for c in cases.values()} == {0, 2}
+
+
+def test_mstep_ladder_covers_every_boundary_of_the_mstep_kernels():
+    """tests/test_mstep_ladder.py runs k2_mstep, k3_mstep and k4_mstep on the cases of tests/mstep_ladder.py.  The
+    boundaries are read here from the sources - MT_ROWS, MT_NC, MT_MAXJ, M3_CH, M4_TPW, EM_DEPTH, SCAPE_MAX_JOBS_PER_UTR,
+    the ring-depth formulas, the jobs_per_pass values, the 1,024-entry rule of em_depth, the n_utr >= 8 split - and the
+    ladder must have a case on both sides of each (whoever moves one has to move the ladder).  The ladder's restatement
+    of the kernel-selection rule (em_wide, em_depth, em_choose) is pinned to the source here as well."""
+    import mstep_ladder as ml
+    csrc = os.path.join(ROOT, "scape_amd", "csrc")
+    src = open(os.path.join(csrc, "scape_hip.hip")).read()
+    k2 = open(os.path.join(csrc, "em_lockstep.inc")).read()
+    k3 = open(os.path.join(csrc, "mstep_ring.inc")).read()
+    k4 = open(os.path.join(csrc, "mstep_multi.inc")).read()
+    hdr = open(os.path.join(ROOT, "include", "scape_hip.h")).read()
+
+    def define(text, name):
+        found = re.findall(r"#define\s+%s\s+(\d+)\b" % name, text)
+        assert len(found) == 1, name
+        return int(found[0])
+    MT_RB, MT_NC, MT_MAXJ, DEPTH = (define(k2, n) for n in ("MT_RB", "MT_NC", "MT_MAXJ", "EM_DEPTH"))
+    assert "#define MT_ROWS (64 * MT_RB)" in k2
+    MT_ROWS = 64 * MT_RB
+    M3_CH, M3_WPC, M4_TPW = define(k3, "M3_CH"), define(k3, "M3_WPC"), define(k4, "M4_TPW")
+    MAX_JOBS = define(hdr, "SCAPE_MAX_JOBS_PER_UTR")
+    # ---- the ladder's constants and its restatement of the selection rule
+    assert (ml.ROWS, ml.HALF, ml.MT_MAXJ, ml.EM_DEPTH, ml.MAX_JOBS_PER_UTR) == (MT_ROWS, M3_CH, MT_MAXJ, DEPTH, MAX_JOBS)
+    assert "const bool wide = n_jobs <= sw.wide_maxjobs && kmax + 1 <= WIDE_MAX_COLUMNS;" in src
+    assert "constexpr int WIDE_MAX_COLUMNS = last_class(WideClasses{});" in src
+    wide = [int(c) for c in re.findall(r"using WideClasses = std::integer_sequence<int,([\d,\s]+)>;", src)[0].split(",")]
+    assert ml.WIDE_MAX_COLUMNS == wide[-1]
+    assert "s.split_maxtiles = env_r ? atoi(env_r) : %d;" % ml.SPLIT_MAXTILES_DEFAULT in src
+    assert "s.wide_maxjobs = env_w ? atoi(env_w) : %d;" % ml.WIDE_MAXJOBS_DEFAULT in src
+    assert "s.depth = std::min(EM_DEPTH, std::max(1, env_d ? atoi(env_d) : EM_DEPTH));" in src
+    assert "if (!any_m || em_wide(sw, n_jobs, kmax)) return 1;" in src
+    entries = re.search(r"while \(depth > 1 && \(\(size_t\)max_jobs_utr \* depth > (\d+) \|\|", src)
+    assert entries and int(entries.group(1)) == ml.LIST_ENTRIES and len(re.findall(r"off < %d\) s_all\[off\] = j;" % ml.LIST_ENTRIES, k2)) == 1
+    assert "k.job_split = (long long)p.active.size() * p.tiles_max <= sw.split_maxtiles;" in src
+    assert "k.multi_mstep = k.ring_mstep && !k.job_split && !sw.debug && p.pttot < ((size_t)1 << 31) && !sw.mstep_v3;" in src
+    assert "const int jobs_per_pass = k.job_split ? 16 : MT_MAXJ;" in src
+    assert "const unsigned psplit = k.job_split ? (unsigned)std::min(64, (p.max_cols_utr + 15) / 16) : 1u;" in src
+    xcd = re.findall(r"if \(n_utr >= (\d+)\) \{", k2 + k3 + k4)
+    assert len(xcd) == 3 and set(xcd) == {str(ml.XCD_UTRS)}, xcd
+    # ---- ring depths, from the formulas
+    assert "#define M3_AREA_BYTES (M3_WPC >= 3 ? 51 * 1024 : 78 * 1024)" in k3
+    assert "constexpr int m3_rv(int G) { return (M3_WPC >= 3) ? (G <= 1 ? 3 : 2) : 3; }" in k3
+    assert re.search(r"constexpr int m3_rt\(int G\) \{\s*return \(M3_AREA_BYTES - m3_rv\(G\) \* G \* 2048\) / 8192 > 10 \? 10 : "
+                     r"\(M3_AREA_BYTES - m3_rv\(G\) \* G \* 2048\) / 8192;", k3)
+    assert "#define M4_REC_BYTES (64 * 24)" in k4 and "#define M4_WPC M3_WPC" in k4
+    assert "#define M4_TAIL_BYTES (4 * 64 * 12 + M4_TPW * (M4_REC_BYTES + 12 * 4) + 16 * 4 + 4 * 8)" in k4
+    assert "#define M4_AREA_BYTES (((M4_WPC >= 3 ? 53760 : 81920) - M4_TAIL_BYTES) / 1024 * 1024)" in k4
+    assert "constexpr int m4_rv(int G) { return M4_AREA_BYTES / (G * 2048 + 8192) < 2 ? 2 : M4_AREA_BYTES / (G * 2048 + 8192); }" in k4
+    assert re.search(r"constexpr int m4_rt\(int G\) \{\s*return \(M4_AREA_BYTES - m4_rv\(G\) \* G \* 2048\) / 8192 > 10 \? 10 : "
+                     r"\(M4_AREA_BYTES - m4_rv\(G\) \* G \* 2048\) / 8192;", k4)
+    a3 = 51 * 1024 if M3_WPC >= 3 else 78 * 1024
+    a4 = ((53760 if M3_WPC >= 3 else 81920) - (4 * 64 * 12 + M4_TPW * (64 * 24 + 12 * 4) + 16 * 4 + 4 * 8)) // 1024 * 1024
+    m3_rv = lambda G: ((3 if G <= 1 else 2) if M3_WPC >= 3 else 3)                  # noqa: E731
+    m3_rt = lambda G: min(10, (a3 - m3_rv(G) * G * 2048) // 8192)                   # noqa: E731
+    m4_rv = lambda G: max(2, a4 // (G * 2048 + 8192))                               # noqa: E731
+    m4_rt = lambda G: min(10, (a4 - m4_rv(G) * G * 2048) // 8192)                   # noqa: E731
+    cases = {c.name: c for c in ml.cases()}
+    ring = cases["ring"]
+    halves = {(q.N + M3_CH - 1) // M3_CH for q in ring.preps}
+    assert halves == set(ml.RING_HALVES) and all(q.N % M3_CH for q in ring.preps)   # Np padding in every one
+    groups = {n // len(ring.preps) // 16 for n in ring.calls}
+    assert groups == {1, 2, 3, 4} == set(range(1, MT_MAXJ // 16 + 1))
+    for n in ring.calls:                                                            # 16 G columns on every UTR's tile
+        per = np.bincount([j.u for j in ring.jobs[:n]])
+        assert np.all(per == n // len(ring.preps)) and per[0] % 16 == 0
+    for G in groups:
+        for depth in (m3_rt(G), m3_rv(G), m4_rt(G), m4_rv(G)):
+            assert {1, 2, depth - 1, depth, depth + 1} - {0} <= halves, (G, depth)
+    tile = {j.a_idx[0] * 8 // MT_ROWS for j in ring.jobs} | {(j.a_idx[2] * 8 + 7) // MT_ROWS for j in ring.jobs}
+    assert tile == {ml.RING_TILE} and len(ring.preps[0].betas) == 8                 # every window inside one tile
+    # ---- bins: the 16-bin half-chunk, k2_mstep's MT_NC-bin chunk
+    Ns = [q.N for q in cases["bins"].preps]
+    for b in (M3_CH, MT_NC):
+        assert {b - 1, b, b + 1} <= set(Ns), b
+    assert 1 in Ns and Ns[:len(ml.N_LADDER)] == list(ml.N_LADDER)
+    for N in ml.N_LADDER:
+        dropped = {nb for (n_, nb) in ml.BIN_SEEDS if n_ == N}
+        assert {0, N - 1} <= dropped and {b for b in (M3_CH - 1, M3_CH, MT_NC - 1, MT_NC) if b < N} <= dropped, N
+    # ---- call shape: 1 UTR, one below / on / above the XCD split; the passes of 16 and of MT_MAXJ; the list limits
+    per_call = [len({j.u for j in cases["bins"].jobs[:n]}) for n in cases["bins"].calls]
+    assert per_call == list(ml.N_UTR_CALLS) and {1, ml.XCD_UTRS - 1, ml.XCD_UTRS, ml.XCD_UTRS + 1} <= set(per_call)
+    cols = set(cases["columns"].calls)
+    for b in (16, 32, 48, MT_MAXJ, 2 * MT_MAXJ):
+        assert {b, b + 1} <= cols, b
+    assert {1, 15} <= cols and all(j.K == 1 for j in cases["columns"].jobs)
+    many = cases["many"]
+    assert max(many.calls) == MAX_JOBS and all(j.K == 1 for j in many.jobs) and many.preps[0].N <= 17
+    for d in range(2, DEPTH + 1):                                                   # em_depth: the largest job count that keeps depth d
+        assert {ml.LIST_ENTRIES // d, ml.LIST_ENTRIES // d + 1} <= set(many.calls), d
+    got = {n: [ml.selection(env, many.jobs[:n], many.preps)["depth"] for _f, env in ml.FORMS] for n in many.calls}
+    assert got[341][1] == 3 and got[342][1] == 2 and got[512][1] == 2 and got[513][1] == 1 and got[1024][1] == 1
+    # ---- every case runs all three kernels, split and whole passes, both E-steps
+    for c in cases.values():
+        for n in c.calls or (len(c.jobs),):
+            sel = [ml.selection(env, c.jobs[:n], c.preps) for _f, env in ml.FORMS]
+            assert {s["kernel"] for s in sel} == {"k2_mstep", "k3_mstep", "k4_mstep"}, (c.name, n)
+            assert {(s["kernel"], s["job_split"]) for s in sel} >= {("k2_mstep", True), ("k2_mstep", False), ("k3_mstep", True),
+                                                                    ("k3_mstep", False), ("k4_mstep", False)}, (c.name, n)
+            assert sel[-1]["wide"] and not any(s["wide"] for s in sel[:-1]), (c.name, n)
+    # ---- window rows: B = 13 reaches every residue; the three beta counts; a grid of another length
+    w = cases["window"]
+    assert len(w.preps[0].betas) == 13 and {len(c.preps[0].betas) for c in cases.values()} == {8, 13, 16}
+    ends = {(e, r) for (e, r) in ml.WINDOW_ENDS}
+    assert ends == {(e, r) for e in ("lo", "hi") for r in (0, 1, 15, 16, 17, MT_ROWS - 1)}
+    assert set(ml.WINDOW_TILES) == {1, 2, 3} and M4_TPW == 2                          # k4_mstep takes tiles in pairs: the odd tile last
+    assert all((q.T * len(q.betas)) % MT_ROWS for c in cases.values() for q in c.preps)   # the last tile is partial everywhere
