@@ -36,8 +36,9 @@ static_assert(EM_DEPTH >= 1 && EM_DEPTH <= 8, "column slots per job");
 #ifndef MT_DEEP
 #define MT_DEEP 2                     // register stages of the M-step's loads in passes of <= 32 jobs (measured: 3 and 4 change nothing, big calls or small)
 #endif
-// device counters (unsigned long long each): [0] rounds, [1] unused, [2] z elements, [3] unused, then
+// device counters (unsigned long long each): [0] rounds, [1] unused, [2] z elements, [3] finalised jobs, then
 // 64-way sharded: slab elements, executed job-rounds, and the M-step's own byte tallies
+#define CNT_DONE 3                    // jobs finalised in this call (one add per job lifetime; read with the early-exit probe)
 #define CNT_SLAB 4
 #define CNT_EXEC (4 + 64)
 #define CNT_MSTEP_TENSOR (4 + 2 * 64)
@@ -64,6 +65,7 @@ struct EmState {
     double *pt_score;                 // ragged [column][n_tiles(utr)]
     int32_t *pt_row;
     const int64_t *ptoff;             // [columns]
+    int32_t *u_done;                  // [n_utr] finalised jobs of each UTR in this call (em_rounds' shrink); null: not counted
 };
 
 __device__ __forceinline__ double d_wave_allsum(double v) {
@@ -296,6 +298,8 @@ __device__ __forceinline__ EstepNext estep_body(
                 ws_out[(size_t)job * (kmax + 1) + i + 1] = 0.0;
             }
             S.status[job] = 2;
+            atomicAdd(&counters[CNT_DONE], 1ull);
+            if (S.u_done) atomicAdd(&S.u_done[u_job], 1);
             atomicAdd(&counters[0], (unsigned long long)n_lb);
             atomicAdd(&counters[2], (unsigned long long)n_lb * (unsigned long long)N * (unsigned long long)C);
         }
@@ -808,6 +812,81 @@ __device__ __forceinline__ EstepNext estep_body(
 // it launches `depth` slots per pass.)
 __host__ __device__ inline bool em_run_ahead_stops(int status, int nlb, int nround, int k_next, unsigned long long pend) {
     return status != 0 || nlb >= nround || (pend & (7ull << k_next)) != 0ull;
+}
+// The slots a pass can use at all, from the largest K among the live ordinary jobs (0: only fixed-inference jobs are
+// live, which run one round per pass): the columns of a pass belong to components that are pairwise neither equal nor
+// adjacent, so K <= 2 never runs ahead and K = 3 only over the pair (0, 2).  Holds for component orders over 0 .. K - 1
+// (gen_k_arr); a round of the uniform component K publishes nothing and could run ahead further - with a slot missing
+// the job runs that round in the next pass, same bits.  em_rounds launches this many k2_estep slots after a shrink.
+__host__ inline int em_slots_needed(int max_k_live, int depth) {
+    return std::min(depth, max_k_live <= 2 ? 1 : max_k_live == 3 ? 2 : depth);
+}
+// Is a list of `listed` entries, `live` of them still needed, due for compaction at threshold `pct` (percent)?
+__host__ inline bool em_shrink_due(long long listed, long long live, int pct) {
+    return live > 0 && live < listed && live * 100 <= listed * pct;
+}
+// Stable compaction, one chunk of the list per step and one entry per thread: where the entry of lane `lane` of wavefront
+// `wave` goes, given the entries kept before this chunk (base), the kept counts of the chunk's wavefronts and the
+// wavefront's own keep mask.  (k_em_shrink; tools/em_schedule_check.cpp replays it on the host.)
+__host__ __device__ inline int em_shrink_pos(int base, const int *wave_cnt, int wave, unsigned long long mask, int lane) {
+    int off = base;
+    for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+    unsigned long long below = mask & ((1ull << lane) - 1ull);
+    int n = 0;
+    for (; below; below &= below - 1) ++n;
+    return off + n;
+}
+
+// The shrink of a call that runs ahead (em_rounds): one workgroup rewrites, in place and in order,
+//   elist  without the jobs at status 2 (a job at status 1 still has its finalising E-step to run and stays), and
+//   active without the UTRs all of whose jobs are finalised (u_done[u] = the UTR's job count),
+// and writes out[0] = jobs kept, out[1] = UTRs kept, out[2] = largest K among the kept ordinary jobs (0: none).
+// In place is safe: a chunk is read whole before any of it is written, and it writes at or below where it read.
+#define EM_SHRINK_THREADS 1024
+#ifndef EM_SHRINK_AT
+#define EM_SHRINK_AT 50               // default of SCAPE_HIP_EM_SHRINK_AT (percent of a list still live; profiles/em_shrink.txt)
+#endif
+__global__ __launch_bounds__(EM_SHRINK_THREADS) void k_em_shrink(int32_t *elist, int n_list, const int32_t *__restrict__ status,
+                                                                 const int32_t *__restrict__ job_K, const int32_t *__restrict__ job_fixed,
+                                                                 int32_t *active, int n_active, const int32_t *__restrict__ u_done,
+                                                                 const int64_t *__restrict__ ujob_off, int depth, int32_t *__restrict__ out) {
+    __shared__ int s_cnt[EM_SHRINK_THREADS / 64];
+    __shared__ int s_k;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_k = 0;
+    int k_live = 0;
+    auto compact = [&](int32_t *list, int n, auto keep) {
+        int base = 0;
+        for (int i0 = 0; i0 < n; i0 += EM_SHRINK_THREADS) {
+            const int i = i0 + tid;
+            int32_t v = 0;
+            bool kp = false;
+            if (i < n) {
+                v = list[i];
+                kp = keep(v);
+            }
+            const unsigned long long mask = __ballot(kp);
+            if (lane == 0) s_cnt[wave] = __popcll(mask);
+            __syncthreads();
+            if (kp) list[em_shrink_pos(base, s_cnt, wave, mask, lane)] = v;
+            for (int w = 0; w < EM_SHRINK_THREADS / 64; ++w) base += s_cnt[w];
+            __syncthreads();
+        }
+        return base;
+    };
+    const int jobs = compact(elist, n_list, [&](int32_t j) {
+        const bool live = status[j] != 2;
+        if (live && job_fixed[j] == 0) k_live = max(k_live, job_K[j]);
+        return live;
+    });
+    const int utrs = compact(active, n_active, [&](int32_t u) { return (int64_t)u_done[u] * depth < ujob_off[u + 1] - ujob_off[u]; });
+    if (k_live) atomicMax(&s_k, k_live);
+    __syncthreads();
+    if (tid == 0) {
+        out[0] = jobs;
+        out[1] = utrs;
+        out[2] = s_k;
+    }
 }
 #define ESTEP_NW 1
 #ifndef ESTEP_WPS

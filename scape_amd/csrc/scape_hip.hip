@@ -785,6 +785,7 @@ struct EmBufs {
     DevBuf ia, ib, sia, sib, ws, slw, lb, ell, nlb, status, pend, rd_k, rd_lo, rd_hi, rd_m, rd_n0, rd_n1, rd_lw, rd_sv, rd_fl, V, Vsuf,
         voff, pt_score, pt_row, ptoff;             // one per EmState member, in its order
     DevBuf ujoff, ujlist, active, elist, dbg;
+    DevBuf udone, shrunk;                          // em_rounds' shrink: finalised jobs per UTR; what k_em_shrink kept (3 ints)
     // nc = column slots of the call (jobs x depth): what the M-step reads and writes is per column
     int ensure(size_t nj, size_t nc, size_t kmax, size_t n_utr, size_t vtot, size_t pttot) {
         return ia.ensure(nj * kmax * 4) || ib.ensure(nj * kmax * 4) || sia.ensure(nj * kmax * 4) || sib.ensure(nj * kmax * 4) ||
@@ -793,15 +794,16 @@ struct EmBufs {
                rd_hi.ensure(nc * 4) || rd_m.ensure(nc * 4) || rd_n0.ensure(nc * 4) || rd_n1.ensure(nc * 4) ||
                rd_lw.ensure(nc * 8) || rd_sv.ensure(nc * 8) || rd_fl.ensure(nc * 8) || V.ensure(vtot * 8) || Vsuf.ensure((vtot / 16 + nc + 1) * 8) ||
                voff.ensure(nc * 8) || pt_score.ensure(pttot * 8) || pt_row.ensure(pttot * 4) || ptoff.ensure(nc * 8) ||
-               ujoff.ensure((n_utr + 1) * 8) || ujlist.ensure(nc * 4) || active.ensure(n_utr * 4) || elist.ensure(nj * 4);
+               ujoff.ensure((n_utr + 1) * 8) || ujlist.ensure(nc * 4) || active.ensure(n_utr * 4) || elist.ensure(nj * 4) ||
+               udone.ensure(n_utr * 4) || shrunk.ensure(4 * 4);
     }
-    EmState state() const {
+    EmState state(bool count_done = false) const {
         return EmState{ia.as<int32_t>(), ib.as<int32_t>(), sia.as<int32_t>(), sib.as<int32_t>(), ws.as<double>(), slw.as<double>(),
                        lb.as<double>(), ell.as<double>(), nlb.as<int32_t>(), status.as<int32_t>(), pend.as<unsigned long long>(),
                        rd_k.as<int32_t>(),
                        rd_lo.as<int32_t>(), rd_hi.as<int32_t>(), rd_m.as<int32_t>(), rd_n0.as<int32_t>(), rd_n1.as<int32_t>(),
                        rd_lw.as<double>(), rd_sv.as<double>(), rd_fl.as<double>(), V.as<double>(), Vsuf.as<double>(), voff.as<int64_t>(),
-                       pt_score.as<double>(), pt_row.as<int32_t>(), ptoff.as<int64_t>()};
+                       pt_score.as<double>(), pt_row.as<int32_t>(), ptoff.as<int64_t>(), count_done ? udone.as<int32_t>() : nullptr};
     }
 };
 
@@ -854,7 +856,7 @@ struct BatchState : BatchShape {
     EmBufs em;
 };
 
-#define N_COUNTERS (4 + 5 * 64 + 16 + 48)   // (+16: ESTEP_STAMPS, +48: M4_STAMPS tools builds) rounds, unused, z elements, unused, then five 64-way sharded counters (em_lockstep.inc)
+#define N_COUNTERS (4 + 5 * 64 + 16 + 48)   // (+16: ESTEP_STAMPS, +48: M4_STAMPS tools builds) rounds, unused, z elements, finalised jobs, then five 64-way sharded counters (em_lockstep.inc)
 // What lives as long as the handle; the batch hangs off it.
 struct scape_hip_ctx {
     int device = 0;
@@ -1095,6 +1097,13 @@ struct EmPlan {
     bool any_m = false;                          // fixed-inference jobs (mstep_fixed) have no grid arg-max
 };
 
+// tiles of the largest UTR of a list: the second factor of the M-step grid (em_plan, and em_rounds after a shrink)
+static int em_tiles_max(const std::vector<UtrDesc> &h_desc, int B, const int32_t *utrs, int n) {
+    int tiles_max = 1;
+    for (int i = 0; i < n; ++i) tiles_max = std::max(tiles_max, (h_desc[utrs[i]].T * B + MT_ROWS - 1) / MT_ROWS);
+    return tiles_max;
+}
+
 static EmPlan em_plan(const std::vector<UtrDesc> &h_desc, int B, size_t nj, const int32_t *job_utr, const int32_t *job_fixed,
                       bool size_order, int depth) {
     EmPlan p;
@@ -1125,8 +1134,8 @@ static EmPlan em_plan(const std::vector<UtrDesc> &h_desc, int B, size_t nj, cons
     const int n_active = (int)p.active.size();
     for (int u : p.active) {
         p.max_cols_utr = std::max<int>(p.max_cols_utr, (int)(p.ujoff[u + 1] - p.ujoff[u]));
-        p.tiles_max = std::max(p.tiles_max, (h_desc[u].T * B + MT_ROWS - 1) / MT_ROWS);
     }
+    p.tiles_max = em_tiles_max(h_desc, B, p.active.data(), n_active);
     p.voff.resize(nj * depth);
     p.ptoff.resize(nj * depth);
     for (size_t j = 0; j < nj; ++j) {
@@ -1161,6 +1170,9 @@ struct EmSwitches {
     bool size_order, debug, fine, mstep_v2, mstep_v3;
     int split_maxtiles, wide_maxjobs;
     int depth;          // SCAPE_HIP_EM_DEPTH: cap on the rounds a job runs per launch (1 = one round per tensor pass)
+    bool shrink;        // SCAPE_HIP_EM_SHRINK=0: the launches of a call that runs ahead keep their first size
+    int shrink_at;      // SCAPE_HIP_EM_SHRINK_AT: compact the lists when at most this percentage of them is live
+    bool trace;         // SCAPE_HIP_ROUND_TRACE: one stderr line per shrink
 };
 static EmSwitches em_switches() {
     const char *env_m = getenv("SCAPE_HIP_MSTEP"), *env_r = getenv("SCAPE_HIP_SPLIT_MAXTILES"), *env_w = getenv("SCAPE_HIP_WIDE_MAXJOBS");
@@ -1174,6 +1186,10 @@ static EmSwitches em_switches() {
     s.wide_maxjobs = env_w ? atoi(env_w) : 1024;
     const char *env_d = getenv("SCAPE_HIP_EM_DEPTH");
     s.depth = std::min(EM_DEPTH, std::max(1, env_d ? atoi(env_d) : EM_DEPTH));
+    const char *env_s = getenv("SCAPE_HIP_EM_SHRINK"), *env_a = getenv("SCAPE_HIP_EM_SHRINK_AT");
+    s.shrink = !(env_s && atoi(env_s) == 0);
+    s.shrink_at = std::min(100, std::max(1, env_a ? atoi(env_a) : EM_SHRINK_AT));
+    s.trace = getenv("SCAPE_HIP_ROUND_TRACE") != nullptr;
     return s;
 }
 
@@ -1301,13 +1317,49 @@ static int em_debug_round(scape_hip_ctx *c, int r, int nround) {
     return 0;
 }
 
+// What the launches of a call that runs ahead are sized by: the jobs on the E-step list, the UTRs on the M-step's list,
+// the tiles of the largest of those and the slots a pass can still use.  The plan's values until the first shrink.
+struct EmLive {
+    int jobs, utrs, tiles_max, slots;
+};
+// One shrink, after the probe of pass r has drained the stream: k_em_shrink compacts both lists on the device, the kept
+// UTR list comes back (a second short wait, on the few shrink events of a call only) and the grids follow it.
+static int em_shrink(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, int r, std::vector<int32_t> &h_active, EmLive &live) {
+    const BatchState &b = *c->batch;
+    const EmBufs &em = b.em;
+    hipLaunchKernelGGL(k_em_shrink, dim3(1), dim3(EM_SHRINK_THREADS), 0, c->stream, em.elist.as<int32_t>(), live.jobs,
+                       em.status.as<int32_t>(), b.job.K.as<int32_t>(), b.job.fixed.as<int32_t>(), em.active.as<int32_t>(), live.utrs,
+                       em.udone.as<int32_t>(), em.ujoff.as<int64_t>(), p.depth, em.shrunk.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    int32_t kept[3] = {0, 0, 0};
+    if (to_host(c->stream, kept, em.shrunk, sizeof(kept)) || to_host(c->stream, h_active.data(), em.active, (size_t)live.utrs * 4)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (kept[0] < 1 || kept[0] > live.jobs || kept[1] < 1 || kept[1] > live.utrs) return fail("EM shrink: inconsistent live counts");
+    const int slots = em_slots_needed(kept[2], p.depth);
+    if (sw.trace)
+        fprintf(stderr, "[shrink] pass %d jobs %d -> %d utrs %d -> %d slots %d\n", r, live.jobs, kept[0], live.utrs, kept[1], slots);
+    live = EmLive{kept[0], kept[1], em_tiles_max(b.h_desc, b.prm.B, h_active.data(), kept[1]), slots};
+    return 0;
+}
+
 // the passes of one call: E-step, M-step, ... and a last E-step that finishes the jobs still running.  A job runs up
 // to p.depth rounds per pass (one k2_estep launch per slot) and at least one, so nround + 1 passes always do.
 static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, const EmKernels &k, int n_jobs, int kmax) {
     EmBufs &em = c->batch->em;
-    const EmState S = em.state();
-    const int nround = c->batch->prm.nround, n_active = (int)p.active.size();
+    // The shrink: late in a call that runs ahead most jobs are finalised and most UTRs have no job left, so the E-step
+    // list, the M-step's UTR list and both grids are cut down to what is live (em_shrink).  Placement only: a job's
+    // rounds and a column's tiles are the same arithmetic wherever they run.
+    const bool shrinking = sw.shrink && p.any_m && !k.wide && !sw.debug;
+    const EmState S = em.state(shrinking);
+    const int nround = c->batch->prm.nround, n_active = (int)p.active.size(), n_utr = c->batch->n_utr;
     const int32_t *jl = em.elist.as<int32_t>();
+    EmLive live{n_jobs, n_active, p.tiles_max, p.depth};
+    std::vector<int32_t> h_done, h_active;
+    if (shrinking) {
+        h_done.assign(n_utr, 0);
+        h_active = p.active;
+        HIPCHK(hipMemsetAsync(em.udone.p, 0, (size_t)n_utr * 4, c->stream));
+    }
     unsigned long long *dbg = nullptr;
     if (sw.debug) {
         if (em.dbg.ensure(24 * sizeof(unsigned long long))) return 1;
@@ -1339,7 +1391,7 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
                          launch_estep(c, k2_estep_cs<decltype(cm)::value>, 256, S, kmax, jl, n_jobs, r);
                      })
                    : with_column_class(EstepClasses{}, kmax + 1, [&](auto cm) {
-                         launch_estep_slots(c, k2_estep<decltype(cm)::value>, S, kmax, jl, n_jobs, r, r < nround ? p.depth : 1, p.depth);
+                         launch_estep_slots(c, k2_estep<decltype(cm)::value>, S, kmax, jl, live.jobs, r, r < nround ? live.slots : 1, p.depth);
                      });
         if (!launched) return fail("no E-step kernel for kmax " + std::to_string(kmax));
         HIPCHK(hipGetLastError());
@@ -1347,11 +1399,11 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
         if (r < nround) {
             if (sw.fine && ev_begin(c, 5)) return 1;
             if (k.multi_mstep)
-                launch_mstep(c, k4_mstep, 1u, 64 * M4_NW, M4_LDS_BYTES, S, n_active, (p.tiles_max + M4_TPW - 1) / M4_TPW);
+                launch_mstep(c, k4_mstep, 1u, 64 * M4_NW, M4_LDS_BYTES, S, live.utrs, (live.tiles_max + M4_TPW - 1) / M4_TPW);
             else if (k.ring_mstep)
-                launch_mstep(c, k3_mstep, psplit, 256, M3_LDS_BYTES, S, n_active, p.tiles_max, jobs_per_pass, dbg);
+                launch_mstep(c, k3_mstep, psplit, 256, M3_LDS_BYTES, S, live.utrs, live.tiles_max, jobs_per_pass, dbg);
             else
-                launch_mstep(c, k2_mstep, psplit, 256, 0, S, n_active, p.tiles_max, jobs_per_pass, dbg);
+                launch_mstep(c, k2_mstep, psplit, 256, 0, S, live.utrs, live.tiles_max, jobs_per_pass, dbg);
             c->h_traffic[3] += 1;
             HIPCHK(hipGetLastError());
             if (sw.fine && ev_end(c, 5)) return 1;
@@ -1361,13 +1413,24 @@ static int em_rounds(scape_hip_ctx *c, const EmPlan &p, const EmSwitches &sw, co
         // early and whose rounds are short, and for calls that run ahead, which end well before launch nround; every 8
         // for wave-sized ones at one round per launch, which run to the last round anyway
         if (r < nround && (r & probe_mask) == probe_mask) {
-            unsigned long long executed = 0, shard[64];
-            HIPCHK(hipMemcpyAsync(shard, c->d_counters.as<unsigned long long>() + CNT_EXEC, sizeof(shard),
-                                  hipMemcpyDeviceToHost, c->stream));
+            unsigned long long executed = 0, head[CNT_EXEC + 64];     // the counters up to the executed shards: CNT_DONE too
+            HIPCHK(hipMemcpyAsync(head, c->d_counters.as<unsigned long long>(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
+            if (shrinking && to_host(c->stream, h_done.data(), em.udone, (size_t)n_utr * 4)) return 1;
             HIPCHK(hipStreamSynchronize(c->stream));
-            for (int i = 0; i < 64; ++i) executed += shard[i];
+            for (int i = 0; i < 64; ++i) executed += head[CNT_EXEC + i];
             if (executed == executed_prev) break;
             executed_prev = executed;
+            if (shrinking) {
+                const long long live_jobs = (long long)n_jobs - (long long)head[CNT_DONE];
+                long long live_utrs = 0;
+                for (int i = 0; i < live.utrs; ++i) {
+                    const int u = h_active[i];
+                    live_utrs += (int64_t)h_done[u] * p.depth < p.ujoff[u + 1] - p.ujoff[u];
+                }
+                if ((em_shrink_due(live.jobs, live_jobs, sw.shrink_at) || em_shrink_due(live.utrs, live_utrs, sw.shrink_at)) &&
+                    em_shrink(c, p, sw, r, h_active, live))
+                    return 1;
+            }
         }
         if (sw.debug && em_debug_round(c, r, nround)) return 1;
     }

@@ -12,6 +12,9 @@
 //      whose own component or index neighbour has its arg-max pending, every pass runs 1..depth consecutive rounds, and
 //      depth 1 is one round per pass;
 //   2. random calls: em_plan's ujoff / ujlist / voff / ptoff / elist / totals for depth 1..4 against a direct count.
+//   3. the host halves of the shrink (em_rounds): em_slots_needed against the longest pass the rule gives any component
+//      order over 0 .. K - 1, em_tiles_max on random live UTR lists, em_shrink_due at its edges, and k_em_shrink's in-place
+//      chunked compaction (em_shrink_pos, replayed here thread by thread) against std::copy_if on random status vectors.
 #include "../scape_amd/csrc/scape_hip.hip"
 
 #include <random>
@@ -176,10 +179,81 @@ static void check_plans(std::mt19937_64 &rng, int n_cases) {
     printf("em_plan: %d random calls\n", n_cases);
 }
 
+static void check_shrink(std::mt19937_64 &rng, int n_cases) {
+    // slots: no pass of a job with K components uses more slots than em_slots_needed says, and the rule is what it claims
+    for (int it = 0; it < n_cases * 20; ++it) {
+        const int K = 1 + (int)(rng() % 12), nround = 1 + (int)(rng() % 50), depth = 1 + (int)(rng() % 4);
+        std::vector<int> k_arr(nround), perm(K);
+        for (int i = 0; i < K; ++i) perm[i] = i;
+        for (int t0 = 0; t0 < nround; t0 += K) {
+            std::shuffle(perm.begin(), perm.end(), rng);
+            for (int i = 0; i < K && t0 + i < nround; ++i) k_arr[t0 + i] = perm[i];
+        }
+        if (rng() % 4 == 0)
+            for (int &k : k_arr) k = (int)(rng() % K);           // any order over the K components
+        const int slots = em_slots_needed(K, depth);
+        CHECK(slots == std::min(depth, K <= 2 ? 1 : K == 3 ? 2 : depth), "slots rule, K %d depth %d", K, depth);
+        for (const Pass &p : run_rule(k_arr, K, depth, nround - 1))
+            CHECK((int)p.rounds.size() <= slots, "K %d depth %d: a pass of %zu rounds, %d slots launched", K, depth, p.rounds.size(), slots);
+    }
+    CHECK(em_slots_needed(0, 3) == 1 && em_slots_needed(3, 1) == 1 && em_slots_needed(63, 3) == 3, "slots rule at its ends");
+    CHECK(!em_shrink_due(100, 100, 100) && em_shrink_due(100, 99, 100) && !em_shrink_due(100, 51, 50) && em_shrink_due(100, 50, 50) &&
+              !em_shrink_due(100, 0, 100) && em_shrink_due(3, 1, 50) && !em_shrink_due(3, 2, 50),
+          "em_shrink_due");
+    for (int it = 0; it < n_cases; ++it) {
+        // the M-step grid's second factor from a live UTR list
+        const int n_utr = 1 + (int)(rng() % 40), B = 1 + (int)(rng() % 13);
+        std::vector<UtrDesc> desc(n_utr);
+        for (UtrDesc &d : desc) {
+            memset(&d, 0, sizeof(d));
+            d.T = 1 + (int)(rng() % 400);
+        }
+        std::vector<int32_t> live;
+        for (int u = 0; u < n_utr; ++u)
+            if (rng() % 3 == 0) live.push_back(u);
+        std::shuffle(live.begin(), live.end(), rng);
+        int want = 1;
+        for (int32_t u : live) want = std::max(want, (desc[u].T * B + MT_ROWS - 1) / MT_ROWS);
+        CHECK(em_tiles_max(desc, B, live.data(), (int)live.size()) == want, "tiles_max of %zu live UTRs", live.size());
+        // the compaction: EM_SHRINK_THREADS entries per chunk, one per thread, in place
+        const int n = 1 + (int)(rng() % 5000), mode = (int)(rng() % 4);
+        std::vector<int32_t> list(n), status(n);
+        for (int i = 0; i < n; ++i) list[i] = i;
+        std::shuffle(list.begin(), list.end(), rng);
+        for (int32_t &st : status) st = mode == 0 ? 2 : mode == 1 ? (int32_t)(rng() % 2) : (int32_t)(rng() % 3);
+        if (mode == 3) std::fill(status.begin(), status.begin() + n / 2, 2);
+        std::vector<int32_t> expect;
+        std::copy_if(list.begin(), list.end(), std::back_inserter(expect), [&](int32_t j) { return status[j] != 2; });
+        constexpr int NW = EM_SHRINK_THREADS / 64;
+        int base = 0;
+        for (int i0 = 0; i0 < n; i0 += EM_SHRINK_THREADS) {
+            int32_t v[EM_SHRINK_THREADS];
+            unsigned long long mask[NW] = {};
+            int cnt[NW] = {};
+            for (int tid = 0; tid < EM_SHRINK_THREADS; ++tid) {          // every thread reads, then the barrier
+                const int i = i0 + tid;
+                v[tid] = i < n ? list[i] : 0;
+                if (i < n && status[v[tid]] != 2) mask[tid >> 6] |= 1ull << (tid & 63);
+            }
+            for (int w = 0; w < NW; ++w) cnt[w] = __builtin_popcountll(mask[w]);
+            for (int tid = 0; tid < EM_SHRINK_THREADS; ++tid)
+                if (mask[tid >> 6] >> (tid & 63) & 1ull) {
+                    const int pos = em_shrink_pos(base, cnt, tid >> 6, mask[tid >> 6], tid & 63);
+                    CHECK(pos >= 0 && pos <= i0 + tid, "entry %d moves up to %d", i0 + tid, pos);
+                    if (pos >= 0 && pos <= i0 + tid) list[pos] = v[tid];
+                }
+            for (int w = 0; w < NW; ++w) base += cnt[w];
+        }
+        CHECK(base == (int)expect.size() && std::equal(expect.begin(), expect.end(), list.begin()), "compaction of %d entries, mode %d", n, mode);
+    }
+    printf("shrink: %d slot cases, %d grid and compaction cases\n", n_cases * 20, n_cases);
+}
+
 int main() {
     std::mt19937_64 rng(20261018);
     check_schedules(rng, 200000);
     check_plans(rng, 3000);
+    check_shrink(rng, 3000);
     if (g_fail) {
         fprintf(stderr, "%d checks FAILED\n", g_fail);
         return 1;
