@@ -193,6 +193,24 @@ int scape_hip_report_render(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, co
    *bytes_out = the block's text bytes, *nnz_out = its entries; the rest as scape_hip_report_render. */
 int scape_hip_report_render_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, const int64_t *rows, int64_t row_no0,
                                 int64_t *bytes_out, int64_t *nnz_out);
+/* ex_pa_len_mat: render the expected pA length of every (record, column) with reads as Matrix Market entries into slot
+   0 or 1.  Record i of the block owns the count rows rec_row0[i] .. rec_row0[i] + K[i] - 1 of the last counts call and
+   is row row_no0 + i of the file (row_no0 >= 1).  For each of its columns c, ascending, with T = the sum of the K counts
+   above 0 it gives the line "<row_no0 + i> <c + 1> <field>\n"; a record with skip[i] != 0 gives none.  The field is
+     what == 1: T;
+     what == 0: '%.6f' of v, the reference's exp_pa_len (apa_core.py:1038-1052) of that cell's reads: v = 1.0 when
+       K[i] == 1, otherwise the sum over l of (c_l / T) * n_l with n_l = n_arr[n_off[i] + l], every operation a correctly
+       rounded f64 one without contraction, the sum in the order of numpy's pairwise sum (below 8 terms sequentially from
+       0.0; up to 128 terms eight accumulators over the multiples of 8, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the
+       remainder sequentially; above that the first n/2 terms rounded down to a multiple of 8 plus the rest, recursively),
+       then added to 0.0.  The text is exact: with v = +-m 2^e, m 10^6 2^e is rounded half to even to an integer q and
+       printed as the sign bit's '-', the digits of q / 10^6, '.', and the six digits of q % 10^6.  The caller keeps
+       |n_l| < 2^31 / 9 and every n_l finite for the records it does not skip (n_arr is not read for the skipped ones).
+   *bytes_out = the block's text bytes (0 when no record of the block has an entry; the slot is then fetched as 0 bytes),
+   *nnz_out = its entries; the rest as scape_hip_report_render. */
+int scape_hip_report_render_len_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rec, const int64_t *rec_row0,
+                                    const int32_t *K, const int64_t *n_off, const double *n_arr, const int8_t *skip,
+                                    int64_t row_no0, int32_t what, int64_t *bytes_out, int64_t *nnz_out);
 /* Pseudo-bulk sums of the last counts call (ex_pa_pseudobulk): segment s is the columns [seg_off[s], seg_off[s+1]) of
    the count matrix, 0 <= seg_off[0] <= ... <= seg_off[n_seg] <= n_cols (the caller passes scape_hip_report_counts an
    id2col that puts every sample's columns side by side).  For row i (count row rows[i]) and segment s,

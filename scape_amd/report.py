@@ -19,6 +19,9 @@ device's rendering of one text block with the gzip of the previous one.
 * ``cal_exp_pa_len``: the device builds, per record, the cluster codes present and the (cluster, label) histogram; the
   host names and orders the clusters with the reference's own ``np.unique(np.array(...))`` and finishes
   ``exp_pa_len`` with the reference's numpy expressions, so every printed digit matches by construction.
+* ``ex_pa_len_mat``: ``exp_pa_len`` per (record, cell) as a Matrix Market directory, with the reads behind each value
+  in a second matrix.  The host forms ``n_arr`` with the reference's numpy expression; the device divides, multiplies
+  and adds in the order of numpy's pairwise sum and renders ``'%.6f'`` in exact integers (section ex_pa_len_mat below).
 * ``ex_pa_pseudobulk``: the count matrix summed over cell groups, the input of the reference's DEXSeq script
   (``examples/Rscript-DEXseq/DifferentialTest.R:63-104``, ``:159-184``).  The host permutes the barcode columns so
   that every pseudo-replicate is one contiguous segment of a count row; the device counts as for ``ex_pa_cnt_mat``
@@ -55,6 +58,7 @@ NaN, whose group never matches itself and gets NaN); unknown barcode or cluster 
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import ctypes
 import functools
@@ -438,6 +442,44 @@ class _MtxSink:
         self.n_rows = self.nnz = 0
 
 
+@contextlib.contextmanager
+def _dir_run(device, out_dir, names):
+    """the _Run of a command that writes the files `names` of the directory out_dir: the directory is made inside the
+    frame, and a run that fails removes it again if it made it, so nothing of that run stays behind"""
+    if os.path.exists(out_dir) and not os.path.isdir(out_dir):
+        raise FileExistsError(f"{out_dir} exists and is not a directory")
+    made_dir = not os.path.isdir(out_dir)
+    try:
+        with _Run(device, [os.path.join(out_dir, name) for name in names]) as run:
+            os.makedirs(out_dir, exist_ok=True)
+            yield run
+    except BaseException:
+        if made_dir:
+            try:
+                os.rmdir(out_dir)
+            except OSError:
+                pass
+        raise
+
+
+def _write_gzip(path, text, pool, times):
+    with open(path, "wb") as fh:
+        w = _GzipWriter(fh, pool, times)
+        w.submit(memoryview(text.encode()))
+        w.drain()
+
+
+def _finish_mtx(path, header, body, times):
+    """a Matrix Market file from its header, which holds the number of entries and so is known last, and the gzip
+    members of its body, collected in the anonymous temporary file `body`"""
+    t0 = timer()
+    with open(path, "wb") as mfh:
+        mfh.write(_gzip_part(header.encode()))
+        body.seek(0)
+        shutil.copyfileobj(body, mfh, 16 << 20)
+    times["finish"] += timer() - t0
+
+
 def _ex_pa_cnt_mtx(output_dir, res_pkl_file, inp, idmap, device):
     """the count matrix as a 10x-style directory <res>.cnt/: matrix.mtx.gz (the dense file's rows and columns, nonzero
     counts only, row-major), features.tsv.gz (per row: pa_info, pa_info, "Gene Expression"; Seurat's Read10X names rows
@@ -447,35 +489,15 @@ def _ex_pa_cnt_mtx(output_dir, res_pkl_file, inp, idmap, device):
     n_cols = inp.n_cols
     bc_text = _tsv_lines([str(b) for b in inp.cb_lst], lambda s: s + "\n", "barcode")
     out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt"))
-    if os.path.exists(out_dir) and not os.path.isdir(out_dir):
-        raise FileExistsError(f"{out_dir} exists and is not a directory")
-    made_dir = not os.path.isdir(out_dir)
-    try:
-        with _Run(device, [os.path.join(out_dir, name) for name in MTX_FILES]) as run:
-            os.makedirs(out_dir, exist_ok=True)
-            with tempfile.TemporaryFile(dir=out_dir) as body, open(run.parts[1], "wb") as ffh, \
-                    ThreadPoolExecutor(_hostlib.host_threads()) as pool:
-                with open(run.parts[2], "wb") as bfh:
-                    bw = _GzipWriter(bfh, pool, run.times)
-                    bw.submit(memoryview(bc_text.encode()))
-                    bw.drain()
-                sink = _MtxSink(_GzipWriter(body, pool, run.times), _GzipWriter(ffh, pool, run.times))
-                ctx = run.device()
-                for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
-                    _render_mtx_batch(ctx, bat, n_cols, sink, run.times)
-                t0 = timer()
-                with open(run.parts[0], "wb") as mfh:
-                    mfh.write(_gzip_part(f"{MTX_BANNER}{sink.n_rows} {n_cols} {sink.nnz}\n".encode()))
-                    body.seek(0)
-                    shutil.copyfileobj(body, mfh, 16 << 20)
-                run.times["finish"] += timer() - t0
-    except BaseException:
-        if made_dir:             # nothing of this run stays behind
-            try:
-                os.rmdir(out_dir)
-            except OSError:
-                pass
-        raise
+    with _dir_run(device, out_dir, MTX_FILES) as run:
+        with tempfile.TemporaryFile(dir=out_dir) as body, open(run.parts[1], "wb") as ffh, \
+                ThreadPoolExecutor(_hostlib.host_threads()) as pool:
+            _write_gzip(run.parts[2], bc_text, pool, run.times)
+            sink = _MtxSink(_GzipWriter(body, pool, run.times), _GzipWriter(ffh, pool, run.times))
+            ctx = run.device()
+            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
+                _render_mtx_batch(ctx, bat, n_cols, sink, run.times)
+            _finish_mtx(run.parts[0], f"{MTX_BANNER}{sink.n_rows} {n_cols} {sink.nnz}\n", body, run.times)
     print("Finish counting for each gene")
     print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
     return out_dir
@@ -515,6 +537,113 @@ def _render_mtx_batch(ctx, bat, n_cols, sink, times):
     _two_slot_blocks(ctx, sink.matrix, blocks(), render, times)
     sink.features.drain()
     sink.n_rows += len(rows)
+
+
+# ---------------------------------------------------------------- ex_pa_len_mat
+# Row r is the r-th record of the stream, the columns are ex_pa_cnt_mat's.  An entry stands for a cell with T >= 1 reads
+# of label < K in the record: matrix.mtx.gz holds '%.6f' of the reference's exp_pa_len(record, labels of that cell's
+# reads) (apa_core.py:1038-1052), reads.mtx.gz holds T at the same places.  The host forms n_arr with the reference's
+# numpy expression; the weights, numpy's pairwise sum and the decimal text are the device's (include/scape_hip.h states
+# them).  A record of K >= 2 whose n_arr is not all finite (a NaN alpha, alpha[-1] == alpha[0]) or reaches LEN_MAX_N is
+# named on stderr and keeps its row without an entry in either matrix.
+LEN_MTX_FILES = ("matrix.mtx.gz", "reads.mtx.gz", "features.tsv.gz", "barcodes.tsv.gz")
+LEN_MTX_BANNER = "%%MatrixMarket matrix coordinate real general\n"
+LEN_MAX_N = 2.0 ** 31 / 9     # |n_l| below it keeps |value| < 2^31, what the device's decimal text is stated for
+
+
+def _len_n_arr(para):
+    """(n_arr of exp_pa_len as the reference's numpy expression gives it, whether the record has values); K == 1 has
+    the value 1.0 and no n_arr"""
+    K = int(para.K)
+    if K == 1:
+        return np.ones(1), True
+    a_arr = np.asarray(para.alpha_arr)
+    if len(a_arr) != K:
+        raise ValueError(f"{para.gene_info_str}: alpha_arr holds {len(a_arr)} values, K is {K}")
+    with np.errstate(all="ignore"):
+        n_arr = np.asarray(1.0 + 9.0 * (a_arr - a_arr[0]) / (a_arr[-1] - a_arr[0]), dtype=np.float64)
+        ok = bool(np.all(np.isfinite(n_arr)) and np.all(np.abs(n_arr) < LEN_MAX_N))
+    return n_arr, ok
+
+
+def _render_len_batch(ctx, bat, n_cols, values, reads, times):
+    """the records of one counted batch, numbered on from values.n_rows: features lines on the host, the entries of both
+    matrices on the device (values.matrix, then reads.matrix, from the same counts), in blocks cut by their text size"""
+    recs, K = bat.recs, bat.K.astype(np.int64)
+    n_rec = len(recs)
+    names = [":".join(p.gene_info_str.split(":")[1:3]) for p in recs]
+    values.features.submit(memoryview(_tsv_lines(names, lambda s: f"{s}\t{s}\tGene Expression\n", "gene_id").encode()))
+    rowbase = np.ascontiguousarray(np.cumsum(K) - K)
+    n_arrs, oks = zip(*(_len_n_arr(p) for p in recs))
+    for p, ok in zip(recs, oks):
+        if not ok:
+            click.echo(f"{p.gene_info_str}: alpha_arr gives no finite expected pA length below 2^31: no entry", err=True)
+    skip = np.array([not ok for ok in oks], dtype=np.int8)
+    n_len = np.array([len(a) for a in n_arrs], dtype=np.int64)
+    n_off = np.ascontiguousarray(np.cumsum(n_len) - n_len)
+    n_arr = np.ascontiguousarray(np.concatenate(n_arrs))
+    n_arr[np.repeat(skip, n_len) != 0] = 0.0     # never read by the device
+    Ks = np.ascontiguousarray(bat.K)
+    # blocks cut against an upper bound of each record's text: at most min(reads, barcodes) entries "<row number>
+    # <column> <field>\n", the field at most the sign, the digits of the record's largest |n_l| + 1, the point and six
+    # digits, or the digits of the record's reads
+    row_no0 = values.n_rows + 1
+    tot = np.add.reduceat(bat.row_tot, rowbase) * (skip == 0)
+    big = np.array([float(np.max(np.abs(a))) for a in n_arrs])
+    big[skip != 0] = 0.0
+    field = np.maximum(8 + _digits(big.astype(np.int64) + 1), _digits(tot))
+    width = len(str(row_no0 + n_rec - 1)) + len(str(n_cols)) + 3 + field
+    cum = np.zeros(n_rec + 1, dtype=np.int64)
+    np.cumsum(np.minimum(tot, n_cols) * width, out=cum[1:])
+    blocks, a = [], 0
+    while a < n_rec:
+        b = int(np.searchsorted(cum, cum[a] + MAX_BLOCK_BYTES, side="right")) - 1
+        b = min(n_rec, a + (1 << 20), max(a + 1, b))
+        blocks.append((a, b))
+        a = b
+
+    def render(sink, what, slot, a, b):
+        nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
+        first = int(n_off[a])            # the block's part of n_arr
+        t0 = timer()
+        check(ctx.lib.scape_hip_report_render_len_mtx(
+            ctx.h, slot, b - a, ptr(rowbase[a:b], P_i64), ptr(Ks[a:b], P_i32), ptr(n_off[a:b] - first, P_i64),
+            ptr(n_arr[first:]), ptr(skip[a:b], P_i8), row_no0 + a, what, ctypes.byref(nbytes), ctypes.byref(nnz)),
+            "report_render_len_mtx")
+        times["render"] += timer() - t0
+        sink.nnz += nnz.value
+    for sink, what in ((values, 0), (reads, 1)):
+        _two_slot_blocks(ctx, sink.matrix, blocks, functools.partial(render, sink, what), times)
+    values.features.drain()
+    values.n_rows += n_rec
+
+
+def _ex_pa_len_mat(output_dir: str, res_pkl_file: str, device=None):
+    """the gene x cell matrix of the expected pA length as a 10x-style directory <res>.len/: matrix.mtx.gz (real),
+    reads.mtx.gz (integer, the reads each value is computed from: the same entries in the same order), features.tsv.gz
+    (per record: gene_id:utr_id, gene_id:utr_id, "Gene Expression") and barcodes.tsv.gz (the CB column).  The four are
+    renamed from .part once all are complete."""
+    inp = _read_inputs(output_dir, res_pkl_file, with_cb=True)
+    n_cols = inp.n_cols
+    idmap = _IdMap(inp.col_ids, np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
+    bc_text = _tsv_lines([str(b) for b in inp.cb_lst], lambda s: s + "\n", "barcode")
+    out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".len"))
+    with _dir_run(device, out_dir, LEN_MTX_FILES) as run:
+        with tempfile.TemporaryFile(dir=out_dir) as vbody, tempfile.TemporaryFile(dir=out_dir) as rbody, \
+                open(run.parts[2], "wb") as ffh, ThreadPoolExecutor(_hostlib.host_threads()) as pool:
+            _write_gzip(run.parts[3], bc_text, pool, run.times)
+            values = _MtxSink(_GzipWriter(vbody, pool, run.times), _GzipWriter(ffh, pool, run.times))
+            reads = _MtxSink(_GzipWriter(rbody, pool, run.times), None)
+            ctx = run.device()
+            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
+                _render_len_batch(ctx, bat, n_cols, values, reads, run.times)
+            if values.nnz != reads.nnz:
+                raise _lib.ScapeHipError("report_render_len_mtx: the two matrices differ in their entries")
+            _finish_mtx(run.parts[0], f"{LEN_MTX_BANNER}{values.n_rows} {n_cols} {values.nnz}\n", vbody, run.times)
+            _finish_mtx(run.parts[1], f"{MTX_BANNER}{values.n_rows} {n_cols} {reads.nnz}\n", rbody, run.times)
+    print("Finish expected pA length for each gene and cell")
+    print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
+    return out_dir
 
 
 # ---------------------------------------------------------------- ex_pa_pseudobulk
@@ -2200,6 +2329,19 @@ def cal_exp_pa_len(output_dir: str, cell_cluster_file: str, res_pkl_file: str):
 def ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, fmt: str):
     """pA x cell read-count matrix <res name>.cnt.tsv.gz from res.gene.pkl / res.utr.pkl (reference utils.py:438-553)."""
     _ex_pa_cnt_mat(output_dir, res_pkl_file, fmt=fmt)
+
+
+@click.command(name="ex_pa_len_mat")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the name of the final '
+                   'result.')
+def ex_pa_len_mat(output_dir: str, res_pkl_file: str):
+    """Gene x cell matrix of the expected pA length, the quantity cal_exp_pa_len reports per cluster, from res.gene.pkl /
+    res.utr.pkl: the directory <res name>.len/ with matrix.mtx.gz, reads.mtx.gz (the reads behind each value),
+    features.tsv.gz and barcodes.tsv.gz (sparse Matrix Market, as read by Seurat Read10X and scanpy read_10x_mtx)."""
+    _ex_pa_len_mat(output_dir, res_pkl_file)
 
 
 @click.command(name="ex_pa_pseudobulk")
