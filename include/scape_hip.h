@@ -527,6 +527,56 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *ctx, int32_t n_rec, const int
                                     const int32_t *x, int64_t *t_out, int64_t *s0_out, int64_t *sq0_out,
                                     int64_t *c0_out /* [2 r] low, [2 r + 1] high 64 bits of C(0) */,
                                     int64_t *n_ge_out /* ADDED to */);
+/* boot_pa_len: the cell bootstrap of a record's mean pA position in each of G = n_groups populations (1 <= G <= 64).
+   (ABI 4 gains these five entry points; nothing that was there changes.)  The tested columns are the first n columns
+   of the count matrix, population 0's first, then population 1's, ...; position j = column j, and cell[j] >= 0 is the
+   0-based column that the cell of position j has in ex_pa_cnt_mat's matrix.  The hash sees cell[j], not j, so a cell's
+   multiplicity depends on the seed, the replicate and the cell only, never on the clustering.  All arithmetic mod 2^64,
+   G and mix those of scape_hip_report_perm_masks:
+     h(b, c) = mix(mix(seed + G * b) + G * (c + 1)),  all 64 bits
+     m(b, c) = #{k in 0..14 : h(b, c) >= P[k]}  for replicate b >= 1 (0 <= m <= 15);  replicate 0 is the observed data, m = 1
+     P[k] = floor(2^64 * e^-1 * sum_{i <= k} 1 / i!):
+       0x5E2D58D8B3BCDF1A 0xBC5AB1B16779BE35 0xEB715E1DC1582DC2 0xFB23979734A252F1 0xFF1025F59174DC3D
+       0xFFD90F3BA4055E19 0xFFFA8B71FC72C913 0xFFFF540C0914B3C9 0xFFFFED1F4AA8F120 0xFFFFFE216E641462
+       0xFFFFFFD4D85D3183 0xFFFFFFFC6DA262B4 0xFFFFFFFFBA12D178 0xFFFFFFFFFB07C64C 0xFFFFFFFFFFAB8EA5
+   so m is Poisson(1) with the tail beyond 15 (probability 1.9e-14) folded into m = 15.
+   scape_hip_report_boot_mult builds m for the replicates b_first .. b_first + b_count - 1 on the device, one byte per
+   (position, replicate): b_count * n bytes laid out [position][replicate].  The buffer is its own: the membership bits
+   and the labels of the permutation tests are untouched.  It replaces the multiplicities of an earlier call and stays
+   until scape_hip_report_free, across scape_hip_report_counts calls.  Checked before anything is queued: 1 <= n < 2^24,
+   every cell[j] >= 0, b_first >= 1, b_count >= 1.  A refused call of these five names its entry point in the message. */
+int scape_hip_report_boot_mult(scape_hip_ctx *ctx, int32_t n, const int32_t *cell, int64_t b_first, int32_t b_count,
+                               uint64_t seed);
+/* The n multiplicities of replicate b_first + b (0 <= b < b_count) of the last boot_mult call. */
+int scape_hip_report_boot_mult_get(scape_hip_ctx *ctx, int32_t b, uint8_t *mult_out);
+/* The replicate values of n_rec records of the last counts call under the replicates of the last boot_mult call.
+   Records, kept rows, t_out[i] and a0_out[i * n_groups + g] are those of scape_hip_report_perm_len_groups; seg_off[0] =
+   0, non-decreasing, seg_off[n_groups] = n of the boot_mult call; q[i] is the INTEGER position of kept row i, 0 <= q[i]
+   <= 2^22.  With c_ij the count of kept row i at position j and g(j) the population of position j, the device forms
+     A_g(b) = sum_i sum_{j in g} m(b, cell[j]) c_ij,     Q_g(b) = sum_i q_i sum_{j in g} m(b, cell[j]) c_ij
+   as exact integers, whatever the order of the adds (a record has T < 2^27 reads in the tested cells, so A <= 15 T <
+   2^31 and Q <= 15 T 2^22 < 2^53), and from them
+     v_g(b) = (double)Q_g(b) / (double)A_g(b),  one IEEE division, contraction off;  +infinity when A_g(b) = 0.
+   Every defined value lies in 0 .. 2^22, so the bit patterns of the values, read as unsigned 64-bit integers, order as
+   the values do, with +infinity last.  v_g(b) is stored at column b - 1 of the device-resident f64 array
+   vals[r * n_groups + g][n_boot].  A call behind a boot_mult call with b_first = 1 allocates or re-uses the array for
+   its record set; a call behind a later chunk of replicates must name the same number of records and groups and the
+   same n_boot and fills further columns.  Checked before anything is queued: a counts and a boot_mult call exist, 1 <=
+   n_groups <= 64, seg_off, the offsets and rows, every q[i], 1 <= n_boot < 2^31 and the chunk's replicates inside 1 ..
+   n_boot.  T comes from the device: a record with T >= 2^27 is refused ("record <r>: ...") once the row sums are back
+   and before the kernel of this entry point is queued.  No LDS: a population's sums live in registers. */
+int scape_hip_report_boot_len(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                              int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
+                              int64_t *a0_out);
+/* The n_boot values of one series (record r, group g: series = r * n_groups + g) of the last boot_len record set. */
+int scape_hip_report_boot_vals_get(scape_hip_ctx *ctx, int64_t series, double *vals_out);
+/* Per series of the last boot_len record set, over its n_boot values and a level of level_bp basis points (1 .. 9999):
+     n_def_out = D = #{b in 1..n_boot : A_g(b) > 0},   k = max(1, floor((D + 1) * (10000 - level_bp) / 20000)) in integers,
+     lo_out = the k-th smallest value,   hi_out = the (D + 1 - k)-th smallest;   both +infinity when D = 0
+   by a radix select over the values' bit patterns (no sort, no cap on n_boot).  Refused unless every column 1 .. n_boot
+   has been written since the array was allocated. */
+int scape_hip_report_boot_quantiles(scape_hip_ctx *ctx, int32_t level_bp, double *lo_out, double *hi_out,
+                                    int64_t *n_def_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */
 int scape_hip_report_fetch(scape_hip_ctx *ctx, int32_t slot, void **host_ptr, int64_t *bytes_out);
 /* per record, the cluster codes present (id2code == NULL: every read in code 0) -> n_groups_out[r]; then

@@ -5,7 +5,9 @@ it between two (per pA site, and per gene for a shift of the 3'UTR length), and 
 ``diff_pa_markers``, which run ``diff_pa`` on every pair of clusters and on every cluster against all other cells,
 ``diff_pa_len_pairs`` and ``diff_pa_len_markers``, which run ``diff_pa_len`` on the same pairs and markers, and
 ``diff_pa_trend`` and ``diff_pa_len_trend``, which test pA usage and 3'UTR length along a per-cell score such as
-pseudotime, and ``ex_pa_len_mat``, the gene x cell matrix of the expected pA length."""
-from scape_amd.report import (cal_exp_pa_len, diff_pa, diff_pa_groups, diff_pa_len, diff_pa_len_groups,  # noqa: F401
-                              diff_pa_len_markers, diff_pa_len_pairs, diff_pa_len_trend, diff_pa_markers,
-                              diff_pa_pairs, diff_pa_trend, ex_pa_cnt_mat, ex_pa_len_mat, ex_pa_pseudobulk)
+pseudotime, and ``ex_pa_len_mat``, the gene x cell matrix of the expected pA length, and ``boot_pa_len``, the
+bootstrap intervals of a cluster's mean pA position and expected pA length."""
+from scape_amd.report import (boot_pa_len, cal_exp_pa_len, diff_pa, diff_pa_groups, diff_pa_len,  # noqa: F401
+                              diff_pa_len_groups, diff_pa_len_markers, diff_pa_len_pairs, diff_pa_len_trend,
+                              diff_pa_markers, diff_pa_pairs, diff_pa_trend, ex_pa_cnt_mat, ex_pa_len_mat,
+                              ex_pa_pseudobulk)

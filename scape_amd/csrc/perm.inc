@@ -48,6 +48,11 @@
 //   k_rep_len_trend_obs / k_rep_perm_len_trend
 //                   diff_pa_len_trend: on the same scores, the covariance of the pA position and the score over a
 //                   record's reads as a 128-bit integer, compared exactly; one walk of the nonzeros, no f64
+// The last section is not a test but the cell bootstrap on the same compaction (boot_pa_len):
+//   k_rep_boot_mult / k_rep_boot_len / k_rep_boot_select
+//                   a Poisson(1) multiplicity per (cell, replicate) as a byte, read off the hash by integer comparisons;
+//                   per (record, population, replicate) the mean pA position from two exact integer sums; and per
+//                   (record, population) the two order statistics of a percentile interval by a radix select
 // On the host a builder leaves a RepLabellings in ReportState (what it built, for the checks of the tests and of the
 // `_get` entry points).  A test fills a RepPermCall, the one frame of its call: rep_perm_prepare checks and compacts from
 // it, rep_perm_launch_classes launches a two-population test per LDS class of records, rep_perm_count brings the
@@ -1637,7 +1642,8 @@ struct RepPermCall : RepPermHost {
     const double *w = nullptr, *tol = nullptr, *tol2 = nullptr, *x = nullptr;
     bool outs_ok = false;
     int64_t max_rec_rows = 0;
-    int64_t n_rows = 0, nnz = 0;       // results of rep_perm_prepare: the kept rows, their nonzeros and the tiles of
+    int32_t reads_bits = 31;           // a record has fewer than 2^reads_bits reads in the tested cells (boot_len: 27)
+    int64_t n_rows = 0, nnz = 0;      // results of rep_perm_prepare: the kept rows, their nonzeros and the tiles of
     int32_t n_tiles = 0;               // REP_THREADS permutations
     StreamDrain drain;                 // waits, where armed, before the base goes
     RepPermCall(scape_hip_ctx *c, const RepLabellings &l, int32_t n_rec_, const int64_t *rec_row_off_, const int64_t *rows_,
@@ -1716,7 +1722,9 @@ static int rep_perm_prepare(scape_hip_ctx *c, RepPermCall &k) {
     for (int r = 0; r < n_rec; ++r) {
         int64_t T = 0;
         for (int64_t i = rec_row_off[r]; i < rec_row_off[r + 1]; ++i) T += k.t_out[i];
-        if (T > INT32_MAX) return fail("record " + std::to_string(r) + ": 2^31 or more reads in the tested cells");
+        if (T >= (int64_t)1 << k.reads_bits)
+            return fail("record " + std::to_string(r) + ": 2^" + std::to_string(k.reads_bits) +
+                        " or more reads in the tested cells");
     }
     if (s->p_nz.ensure(std::max<int64_t>(k.nnz, 1) * 8)) return 1;
     hipLaunchKernelGGL(k_rep_perm_fill, dim3((uint32_t)n_rows), dim3(REP_THREADS), 0, c->stream,
@@ -2365,6 +2373,322 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
         c0_out[2 * (size_t)r + 1] = rec[(size_t)r * REP_LEN_TREND_REC + 5];
     }
     return 0;
+}
+
+}  // extern "C"
+
+// ---- boot_pa_len: the cell bootstrap of the mean pA position per population -------------------------------------------
+// Percentile intervals of a record's mean pA position in each of G = 1..64 populations, by resampling the cells (the
+// Poisson bootstrap).  The tested columns are the populations' columns in front of the count matrix, population 0's
+// first: position j = column j, in the column segments seg_off, and position j carries cell[j], the 0-based column its
+// cell has in ex_pa_cnt_mat's matrix.  The hash sees cell[j], not j: a cell's multiplicity does not depend on the
+// clustering.  All arithmetic mod 2^64, G and mix those of scape_hip_report_perm_masks:
+//   h(b, c) = mix(mix(seed + G b) + G (c + 1)),  all 64 bits
+//   m(b, c) = #{k in 0..14 : h(b, c) >= P[k]}  for replicate b >= 1, so 0 <= m <= 15;  replicate 0 is the observed data, m = 1
+//   P[k] = floor(2^64 e^-1 sum_{i <= k} 1 / i!):  m is Poisson(1), its tail beyond 15 (1.9e-14) folded into m = 15
+// Kept row i of a record carries the integer position q_i, 0 <= q_i <= 2^22; with c_ij its count at position j and g(j)
+// the population of position j:
+//   A_g(b) = sum_i sum_{j in g} m(b, cell[j]) c_ij,   Q_g(b) = sum_i q_i sum_{j in g} m(b, cell[j]) c_ij
+// are exact integers whatever the order of the adds: a record has T < 2^27 reads in the tested cells (checked), so
+// A <= 15 T < 2^31 and Q <= 15 T 2^22 < 2^53.  The replicate's value is
+//   v_g(b) = (double)Q_g(b) / (double)A_g(b),  one IEEE division, contraction off;  +infinity when A_g(b) = 0.
+// Every defined value lies in 0 .. 2^22, so the values' bit patterns, read as unsigned 64-bit integers, order as the
+// values do, with +infinity last.  Per series (record, population), over the replicates 1 .. n_boot and a level of L
+// basis points:
+//   D = #{b : A_g(b) > 0},  k = max(1, floor((D + 1) (10000 - L) / 20000)) in integers,
+//   lo = the k-th smallest of the n_boot values,  hi = the (D + 1 - k)-th smallest;  both +infinity when D = 0.
+//   k_rep_boot_mult    elementwise: lanes along the replicates (the byte stores of one position are contiguous), the
+//                      replicate's inner hash base formed once per lane, the 15 comparisons added up
+//   k_rep_boot_len     workgroup = (record, tile of 256 replicates), one lane per replicate.  A nonzero's population is
+//                      fixed by its column segment, so the walk goes population by population over the row's nonzeros of
+//                      that segment (k_rep_pair_segidx found where they start): A and Q of the one population live in
+//                      registers, every nonzero is read once, and there is no LDS, no atomic, no barrier and no slice
+//   k_rep_boot_select  one workgroup per series: D by a count, then a radix select over the bit patterns, most
+//                      significant byte first, both ranks in the same eight passes over the series (which stays in L2)
+#define REP_BOOT_READS_BITS 27         // T < 2^27
+#define REP_BOOT_MULT_POS 64           // positions a workgroup of k_rep_boot_mult takes per step
+
+__device__ __forceinline__ int rep_boot_mult(unsigned long long h) {
+    constexpr unsigned long long P[15] = {
+        0x5E2D58D8B3BCDF1Aull, 0xBC5AB1B16779BE35ull, 0xEB715E1DC1582DC2ull, 0xFB23979734A252F1ull, 0xFF1025F59174DC3Dull,
+        0xFFD90F3BA4055E19ull, 0xFFFA8B71FC72C913ull, 0xFFFF540C0914B3C9ull, 0xFFFFED1F4AA8F120ull, 0xFFFFFE216E641462ull,
+        0xFFFFFFD4D85D3183ull, 0xFFFFFFFC6DA262B4ull, 0xFFFFFFFFBA12D178ull, 0xFFFFFFFFFB07C64Cull, 0xFFFFFFFFFFAB8EA5ull};
+    int m = 0;
+#pragma unroll
+    for (int k = 0; k < 15; ++k) m += h >= P[k];
+    return m;
+}
+
+// workgroup = (tile of 256 replicates blockIdx.x, positions blockIdx.y * 64 .. in steps of gridDim.y * 64): lane = the
+// replicate b_first + tile * 256 + threadIdx.x, cell[j] is wave-uniform
+__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_mult(int32_t n, const int32_t *__restrict__ cell,
+                                                               unsigned long long b_first, int32_t b_count,
+                                                               unsigned long long seed, uint8_t *__restrict__ mult) {
+    const int p = blockIdx.x * REP_THREADS + threadIdx.x;
+    if (p >= b_count) return;
+    const unsigned long long base = rep_mix(seed + REP_PERM_G * (b_first + (unsigned long long)p));
+    for (int j0 = blockIdx.y * REP_BOOT_MULT_POS; j0 < n; j0 += gridDim.y * REP_BOOT_MULT_POS) {
+        const int j1 = min(n, j0 + REP_BOOT_MULT_POS);
+        for (int j = j0; j < j1; ++j) {
+            const unsigned long long c = (unsigned long long)cell[j];
+            mult[(int64_t)j * b_count + p] = (uint8_t)rep_boot_mult(rep_mix(base + REP_PERM_G * (c + 1)));
+        }
+    }
+}
+
+// workgroup = (record blockIdx.x / n_tiles, tile of 256 replicates of the chunk), one lane per replicate; sg[i] = the
+// G + 1 segment starts of kept row i among the nonzeros.  vals[(r * n_groups + g) * n_boot + col0 + replicate of the
+// chunk] = v_g; a lane beyond the chunk walks the last replicate's bytes and stores nothing
+__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_len(
+    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, int32_t n_groups,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
+    const int32_t *__restrict__ q, int64_t n_boot, int64_t col0, double *__restrict__ vals) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < b_count;
+    const uint8_t *mb = mult + (valid ? p : b_count - 1);
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    const int stride = n_groups + 1;
+    for (int g = 0; g < n_groups; ++g) {
+        long long A = 0, Q = 0;
+        for (int64_t i = row0; i < row1; ++i) {
+            const int64_t *si = sg + i * stride;
+            int a = 0;                           // m <= 15 and the row's reads stay below 2^27
+            rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { a += m * c; });
+            A += a;
+            Q += (long long)a * q[i];
+        }
+        if (valid)
+            vals[((int64_t)r * n_groups + g) * n_boot + col0 + p] =
+                A > 0 ? (double)Q / (double)A : __builtin_huge_val();
+    }
+}
+
+struct RepBootSelectLds {
+    __align__(16) int hist[2][256];
+    unsigned long long sel[2];        // per rank looked for: the prefix of its value's bit pattern
+    long long rank[2];                // and its rank among the values that share the prefix
+    int defined;
+};
+
+// one workgroup per series: n_def[series] = D; lo[series], hi[series] by the rule above.  Values tie, so the select takes
+// all eight bytes; wave w < 2 finds the bin of rank w
+__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_select(const unsigned long long *__restrict__ vals,
+                                                                 int64_t n_boot, int32_t level_bp,
+                                                                 double *__restrict__ lo, double *__restrict__ hi,
+                                                                 int64_t *__restrict__ n_def) {
+    __shared__ RepBootSelectLds lds;
+    const unsigned long long *v = vals + (int64_t)blockIdx.x * n_boot;
+    const unsigned long long inf_bits = 0x7FF0000000000000ull;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) lds.defined = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int64_t i = threadIdx.x; i < n_boot; i += REP_THREADS) mine += v[i] < inf_bits;
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if (lane == 0 && mine) atomicAdd(&lds.defined, mine);
+    __syncthreads();
+    const long long D = lds.defined;
+    if (D == 0) {
+        if (threadIdx.x == 0) {
+            lo[blockIdx.x] = hi[blockIdx.x] = __builtin_huge_val();
+            n_def[blockIdx.x] = 0;
+        }
+        return;
+    }
+    long long k = (D + 1) * (10000 - level_bp) / 20000;
+    if (k < 1) k = 1;
+    unsigned long long prefix[2] = {0, 0};
+    long long rank[2] = {k - 1, D - k};      // 0-based; both below D, so both values are defined
+    for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        lds.hist[0][threadIdx.x] = 0;
+        lds.hist[1][threadIdx.x] = 0;
+        __syncthreads();
+        for (int64_t i = threadIdx.x; i < n_boot; i += REP_THREADS) {
+            const unsigned long long x = v[i];
+#pragma unroll
+            for (int w = 0; w < 2; ++w)
+                if (pass == 0 || (x >> (shift + 8)) == (prefix[w] >> (shift + 8)))
+                    atomicAdd(&lds.hist[w][(x >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (wave < 2) {                      // the bin that holds the value of that rank
+            const int4 h = reinterpret_cast<const int4 *>(lds.hist[wave])[lane];
+            const long long sum = (long long)h.x + h.y + h.z + h.w;
+            long long incl = sum;
+            for (int o = 1; o < 64; o <<= 1) {
+                const long long y = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += y;
+            }
+            const long long want = rank[wave];
+            if (incl - sum <= want && want < incl) {         // one lane: the bins are disjoint
+                long long rr = want - (incl - sum);
+                int b = 4 * lane;
+                if (rr >= h.x) {
+                    rr -= h.x, ++b;
+                    if (rr >= h.y) {
+                        rr -= h.y, ++b;
+                        if (rr >= h.z) rr -= h.z, ++b;
+                    }
+                }
+                lds.sel[wave] = prefix[wave] | ((unsigned long long)b << shift);
+                lds.rank[wave] = rr;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            prefix[w] = lds.sel[w];
+            rank[w] = lds.rank[w];
+        }
+    }
+    if (threadIdx.x == 0) {
+        lo[blockIdx.x] = __longlong_as_double((long long)prefix[0]);
+        hi[blockIdx.x] = __longlong_as_double((long long)prefix[1]);
+        n_def[blockIdx.x] = D;
+    }
+}
+
+// ---- boot_pa_len: host side -------------------------------------------------------------------------------------------
+// a refused call names its entry point in front of the message
+static int rep_boot_named(const char *entry, int rc) {
+    if (rc) g_err = std::string(entry) + ": " + g_err;
+    return rc;
+}
+
+static int rep_boot_build(scape_hip_ctx *c, int32_t n, const int32_t *cell, int64_t b_first, int32_t b_count,
+                          uint64_t seed) {
+    if (n < 1 || n >= REP_PERM_MAX_N) return fail("n must lie in 1 .. 2^24 - 1");
+    if (!cell) return fail("bad argument");
+    for (int32_t j = 0; j < n; ++j)
+        if (cell[j] < 0) return fail("position " + std::to_string(j) + ": a negative cell");
+    if (b_first < 1 || b_count < 1) return fail("b_first and b_count must be at least 1 (replicate 0 is the observed data)");
+    ReportState *s = report_state(c);
+    s->boot.count = 0;
+    StreamDrain drain(c->stream);
+    if (s->b_mult.ensure((int64_t)b_count * n) || s->b_cell.ensure((int64_t)n * 4)) return 1;
+    HIPCHK(hipMemcpyAsync(s->b_cell.p, cell, (int64_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    const uint32_t n_tiles = (uint32_t)((b_count + REP_THREADS - 1) / REP_THREADS);
+    const uint32_t n_pos = (uint32_t)std::min<int64_t>(((int64_t)n + REP_BOOT_MULT_POS - 1) / REP_BOOT_MULT_POS, 65535);
+    hipLaunchKernelGGL(k_rep_boot_mult, dim3(n_tiles, n_pos), dim3(REP_THREADS), 0, c->stream, n, s->b_cell.as<int32_t>(),
+                       (unsigned long long)b_first, b_count, (unsigned long long)seed, s->b_mult.as<uint8_t>());
+    s->b_first = b_first;
+    return rep_built(drain, s->boot, n, b_count);
+}
+
+static int rep_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                        int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
+                        int64_t *a0_out) {
+    ReportState *s = report_state(c);
+    const RepLabellings &l = s->boot;
+    if (l.ready(s->n_cnt_rows)) return 1;
+    if (n_groups < 1 || n_groups > REP_GROUPS_MAX) return fail("n_groups must lie in 1 .. " + std::to_string(REP_GROUPS_MAX));
+    if (!seg_off) return fail("bad argument");
+    if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (seg_off[g + 1] < seg_off[g]) return fail("seg_off must be non-decreasing");
+    if (seg_off[n_groups] != l.n) return fail("seg_off must end at the positions of the last " + std::string(l.builder) + " call");
+    const int64_t b_first = s->b_first, b_count = l.count;
+    if (n_boot < 1 || n_boot > INT32_MAX || b_first + b_count - 1 > n_boot)
+        return fail("the replicates of the last " + std::string(l.builder) + " call must lie in 1 .. n_boot, and n_boot below 2^31");
+    if (n_rec <= 0) return fail("bad argument");
+    const int64_t n_series = (int64_t)n_rec * n_groups;
+    if (b_first > 1 && (n_series != s->b_series || n_groups != s->b_groups || n_boot != s->b_n_boot))
+        return fail("a later chunk of replicates needs the records, groups and n_boot of the call that began at replicate 1");
+    if (n_series > INT32_MAX || n_series > INT64_MAX / 8 / n_boot) return fail("too many records x groups x replicates for one call");
+    RepPermCall k(c, l, n_rec, rec_row_off, rows, t_out);
+    k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off, k.q = q, k.outs_ok = q != nullptr;
+    k.reads_bits = REP_BOOT_READS_BITS;
+    if (rep_perm_prepare(c, k)) return 1;
+    if (rep_pair_segments(c, k, n_groups) || s->b_q.ensure(k.n_rows * 4)) return 1;
+    if (b_first == 1) {
+        s->b_series = 0;                       // nothing to select from until this call has succeeded
+        if (s->b_vals.ensure(n_series * n_boot * 8)) return 1;
+        s->b_written.assign((size_t)n_boot, 0);
+    }
+    HIPCHK(hipMemcpyAsync(s->b_q.p, q, k.n_rows * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rep_boot_len, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), 0, c->stream,
+                       s->b_mult.as<uint8_t>(), k.p_count, k.n_tiles, n_groups, s->p_roff.as<int64_t>(),
+                       s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(), s->b_q.as<int32_t>(), n_boot, b_first - 1,
+                       s->b_vals.as<double>());
+    HIPCHK(hipGetLastError());
+    if (k.drain.wait()) return 1;
+    s->b_series = n_series, s->b_groups = n_groups, s->b_n_boot = (int32_t)n_boot;
+    std::fill(s->b_written.begin() + (b_first - 1), s->b_written.begin() + (b_first - 1 + b_count), 1);
+    return 0;
+}
+
+// the replicate values are there: a boot_len call has succeeded since they were allocated
+static int rep_boot_vals_ok(const ReportState *s) {
+    return s->b_series ? 0 : fail("scape_hip_report_boot_len has not been called");
+}
+
+static int rep_boot_quantiles(scape_hip_ctx *c, int32_t level_bp, double *lo_out, double *hi_out, int64_t *n_def_out) {
+    ReportState *s = report_state(c);
+    if (rep_boot_vals_ok(s)) return 1;
+    if (!lo_out || !hi_out || !n_def_out) return fail("bad argument");
+    if (level_bp < 1 || level_bp > 9999) return fail("level_bp must lie in 1 .. 9999 (basis points)");
+    for (size_t b = 0; b < s->b_written.size(); ++b)
+        if (!s->b_written[b])
+            return fail("replicate " + std::to_string(b + 1) + " has not been written since the values were allocated");
+    const int64_t n_series = s->b_series;
+    if (s->b_lo.ensure(n_series * 8) || s->b_hi.ensure(n_series * 8) || s->b_def.ensure(n_series * 8)) return 1;
+    StreamDrain drain(c->stream);
+    hipLaunchKernelGGL(k_rep_boot_select, dim3((uint32_t)n_series), dim3(REP_THREADS), 0, c->stream,
+                       s->b_vals.as<unsigned long long>(), (int64_t)s->b_n_boot, level_bp, s->b_lo.as<double>(),
+                       s->b_hi.as<double>(), s->b_def.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(lo_out, s->b_lo.p, n_series * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hi_out, s->b_hi.p, n_series * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(n_def_out, s->b_def.p, n_series * 8, hipMemcpyDeviceToHost, c->stream));
+    return drain.wait();
+}
+
+extern "C" {
+
+int scape_hip_report_boot_mult(scape_hip_ctx *c, int32_t n, const int32_t *cell, int64_t b_first, int32_t b_count,
+                               uint64_t seed) {
+    CTX_ENTER(c);
+    return rep_boot_named("scape_hip_report_boot_mult", rep_boot_build(c, n, cell, b_first, b_count, seed));
+}
+
+int scape_hip_report_boot_mult_get(scape_hip_ctx *c, int32_t b, uint8_t *mult_out) {
+    CTX_ENTER(c);
+    ReportState *s = report_state(c);
+    const RepLabellings &l = s->boot;
+    if (rep_get_ok(l, mult_out, nullptr, b)) return rep_boot_named("scape_hip_report_boot_mult_get", 1);
+    StreamDrain drain(c->stream);
+    HIPCHK(hipMemcpy2DAsync(mult_out, 1, s->b_mult.as<uint8_t>() + b, (size_t)l.count, 1, (size_t)l.n,
+                            hipMemcpyDeviceToHost, c->stream));
+    return drain.wait();
+}
+
+int scape_hip_report_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                              int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
+                              int64_t *a0_out) {
+    CTX_ENTER(c);
+    return rep_boot_named("scape_hip_report_boot_len",
+                          rep_boot_len(c, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out));
+}
+
+int scape_hip_report_boot_vals_get(scape_hip_ctx *c, int64_t series, double *vals_out) {
+    CTX_ENTER(c);
+    ReportState *s = report_state(c);
+    if (rep_boot_vals_ok(s)) return rep_boot_named("scape_hip_report_boot_vals_get", 1);
+    if (!vals_out || series < 0 || series >= s->b_series)
+        return rep_boot_named("scape_hip_report_boot_vals_get", fail("series must name a (record, group) of the last boot_len call"));
+    StreamDrain drain(c->stream);
+    HIPCHK(hipMemcpyAsync(vals_out, s->b_vals.as<double>() + series * s->b_n_boot, (int64_t)s->b_n_boot * 8,
+                          hipMemcpyDeviceToHost, c->stream));
+    return drain.wait();
+}
+
+int scape_hip_report_boot_quantiles(scape_hip_ctx *c, int32_t level_bp, double *lo_out, double *hi_out,
+                                    int64_t *n_def_out) {
+    CTX_ENTER(c);
+    return rep_boot_named("scape_hip_report_boot_quantiles", rep_boot_quantiles(c, level_bp, lo_out, hi_out, n_def_out));
 }
 
 }  // extern "C"

@@ -92,6 +92,16 @@ struct ReportState {
     RepLabellings scores{"scape_hip_report_perm_scores", "scores"};
     DevBuf t_scores, t_members, t_q, t_s0, t_sq0, t_lrec;
     int32_t m_n1 = 0, t_qspan = 0;     // population 1's cells of the masks; the largest observed score
+    // boot_pa_len: the multiplicity of every (position, replicate) of the last scape_hip_report_boot_mult call
+    // ([position][replicate], one byte each) and the first replicate of that call; the cell of every position; the
+    // integer row positions of scape_hip_report_boot_len; the replicate values of its record set ([series][replicate],
+    // f64; series = record * n_groups + group), which columns of them have been written since they were allocated, and
+    // what scape_hip_report_boot_quantiles returns per series
+    RepLabellings boot{"scape_hip_report_boot_mult", "multiplicities"};
+    DevBuf b_mult, b_cell, b_q, b_vals, b_lo, b_hi, b_def;
+    int64_t b_first = 0, b_series = 0;
+    int32_t b_n_boot = 0, b_groups = 0;
+    std::vector<uint8_t> b_written;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan

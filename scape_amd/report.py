@@ -1,8 +1,8 @@
 """``scape cal_exp_pa_len``, ``scape ex_pa_cnt_mat``, ``scape ex_pa_pseudobulk``, ``scape diff_pa``,
 ``scape diff_pa_len``, ``scape diff_pa_groups``, ``scape diff_pa_len_groups``, ``scape diff_pa_pairs``,
-``scape diff_pa_markers``, ``scape diff_pa_trend`` and ``scape diff_pa_len_trend``: the stages after ``merge_pa``
-(reference ``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` / ``cal_exp_pa_len_by_cluster`` of
-``apa_core.py:1038-1063``).
+``scape diff_pa_markers``, ``scape diff_pa_trend``, ``scape diff_pa_len_trend`` and ``scape boot_pa_len``: the stages
+after ``merge_pa`` (reference ``src/scape/utils.py:319-427`` and ``:438-553``, with ``exp_pa_len`` /
+``cal_exp_pa_len_by_cluster`` of ``apa_core.py:1038-1063``).
 
 All of them stream the ``Parameters`` records of ``res.gene.pkl`` / ``res.utr.pkl`` (``safe_pickle.iter_pickles``, like
 ``merge_pa``), batch them for the device and hand the per-read work to the HIP kernels of ``csrc/report.inc`` and ``csrc/perm.inc``.  They
@@ -50,6 +50,10 @@ device's rendering of one text block with the gzip of the previous one.
   over the result file, the p-values adjusted over all markers (section diff_pa_markers below).
 * ``diff_pa_trend`` and ``diff_pa_len_trend``: pA usage and 3'UTR length along a per-cell score such as pseudotime, by
   permuting the scores (sections diff_pa_trend and diff_pa_len_trend below).
+* ``boot_pa_len``: how well a cluster's 3'UTR length is known: percentile intervals of the mean pA position and of
+  ``exp_length`` per record and cluster from the cell bootstrap (section boot_pa_len below).  The device draws a
+  Poisson(1) multiplicity per cell and replicate from the permutation tests' hash, forms every replicate's mean position
+  from exact integer sums and selects the interval's two order statistics; the file is exact text.
 
 Reference behaviour kept on purpose: the pivot prints integers only when it is complete (otherwise "2.0"); rows are
 the labels < K with reads, in label order; ``alpha_arr`` is indexed by label, never sorted; cluster values present in a
@@ -61,10 +65,12 @@ from __future__ import annotations
 import contextlib
 import csv
 import ctypes
+import decimal
 import functools
 import io
 import math
 import os
+import re
 import shutil
 import tempfile
 import zlib
@@ -1004,11 +1010,13 @@ def _print_strata(su):
               "clusters have no stratum and were left out")
 
 
-def _perm_run(su, n_perm, device, batch, write):
+def _perm_run(su, n_perm, device, batch, write, record_bytes=0):
     """the run the permutation commands share: the masks (once, when all permutations, at su.perm_bytes device bytes
     each, fit MAX_PERM_BYTES; otherwise per chunk inside every batch), batch(ctx, counted batch, chunk, times) per
-    counted batch, then write(csv writer) into the .part file that is renamed when complete.  Returns the wall seconds;
+    counted batch, then write(csv writer) into the .part file that is renamed when complete.  record_bytes = device
+    bytes a record takes beside its counts and nonzeros (boot_pa_len's replicate values).  Returns the wall seconds;
     LAST_TIMES holds the stages"""
+    counts_cost = _batch_cost(su.n_cols, 12)
     with _Run(device, [su.outpath]) as run:
         times = run.times
         with open(run.parts[0], "w", newline="") as fh:
@@ -1021,7 +1029,8 @@ def _perm_run(su, n_perm, device, batch, write):
             if MAX_BATCH_BYTES is None:
                 budget //= 2
             # the counts of a record and, at worst, as many 8-byte nonzeros as it has tested counts
-            for bat in _counted(ctx, su.res_pkl, su.idmap, su.n_cols, _batch_cost(su.n_cols, 12), budget, times):
+            for bat in _counted(ctx, su.res_pkl, su.idmap, su.n_cols, lambda p: counts_cost(p) + record_bytes, budget,
+                                times):
                 batch(ctx, bat, chunk, times)
             t0 = timer()
             write(csv.writer(fh, delimiter=',', quoting=csv.QUOTE_MINIMAL, lineterminator='\n'))
@@ -1237,18 +1246,11 @@ MAX_GROUPS = 64                  # a group is one byte on the device, and its su
 MAX_ROWS_AND_GROUPS = 4000       # kept rows + populations of a record: the rounding bound of S (include/scape_hip.h)
 
 
-def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, command="diff_pa_groups",
-                  pairs=False, markers=False):
-    """what diff_pa_groups, diff_pa_len_groups, diff_pa_pairs (pairs=True: su.pairs = the two groups of every pair,
-    all (g, h) with g < h in lexicographic order, and the labellings are every pair's membership bits, not the group
-    bytes) and diff_pa_markers (markers=True: 1 to 64 populations, each against every other cell that has a cluster;
-    those of no population follow the populations as one more column segment, su.seg_off has that segment even when it
-    is empty, su.n counts all tested cells, and the labellings are every marker's membership bits) do before the device
-    is opened: the argument and prerequisite checks, the populations, the id -> column table that puts population 0's
-    columns first, then population 1's, ..., and the output path
-    <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv"""
+def _ident_populations(output_dir, res_pkl_file, cell_cluster_file, idents):
+    """what --idents asks of a cluster file, for _groups_setup and _boot_setup: (the idents as text, the file name's tag
+    .<A>+<B>+... or "", _read_inputs' result, the populations: the named clusters in the order given, or every cluster
+    that has a column in order of first appearance); a repeated, unknown or cell-less ident is a ValueError"""
     idents = [str(i) for i in idents or ()]
-    _check_perm_args(n_perm, seed)
     for k, ident in enumerate(idents):
         if ident in idents[:k]:
             raise ValueError(f"ident {ident!r} is given twice")
@@ -1265,6 +1267,21 @@ def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, s
             if ident not in with_cells:
                 raise ValueError(f"cluster {ident!r} has no cell in barcode_index.csv")
         pops = [(ident, with_cells[ident]) for ident in idents]
+    return idents, tag, inp, pops
+
+
+def _groups_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_perm, seed, command="diff_pa_groups",
+                  pairs=False, markers=False):
+    """what diff_pa_groups, diff_pa_len_groups, diff_pa_pairs (pairs=True: su.pairs = the two groups of every pair,
+    all (g, h) with g < h in lexicographic order, and the labellings are every pair's membership bits, not the group
+    bytes) and diff_pa_markers (markers=True: 1 to 64 populations, each against every other cell that has a cluster;
+    those of no population follow the populations as one more column segment, su.seg_off has that segment even when it
+    is empty, su.n counts all tested cells, and the labellings are every marker's membership bits) do before the device
+    is opened: the argument and prerequisite checks, the populations, the id -> column table that puts population 0's
+    columns first, then population 1's, ..., and the output path
+    <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv"""
+    _check_perm_args(n_perm, seed)
+    idents, tag, inp, pops = _ident_populations(output_dir, res_pkl_file, cell_cluster_file, idents)
     if markers and not idents and len(pops) > MAX_GROUPS:
         raise ValueError(f"{len(pops)} clusters: {command} takes at most {MAX_GROUPS} at once, name them with --idents")
     if not (1 if markers else 2) <= len(pops) <= MAX_GROUPS:
@@ -2176,6 +2193,197 @@ def _diff_pa_len_trend(output_dir: str, res_pkl_file: str, cell_score_file: str,
     return su.outpath
 
 
+# ---------------------------------------------------------------- boot_pa_len
+# How well is a cluster's 3'UTR length known?  Percentile intervals of the mean pA position, and of the reference's
+# exp_length, per record and population, by the cell bootstrap: cells are the exchangeable units, as in the permutation
+# tests.  One population per cluster of the cluster file that has a column (order of first appearance, at most 64), or
+# the 1 to 64 clusters named by --idents in the order given, or, without a cluster file, the one population all_cell of
+# every column.  Tested columns: population 0's matrix columns ascending, then population 1's, ... (_samples): positions
+# j = 0 .. n-1, and position j carries cell[j], the 0-based column its cell has in ex_pa_cnt_mat's matrix (inp.col_ids
+# order).  The Poisson bootstrap: cell c gets the multiplicity m(b, c) in replicate b = 1 .. n_boot, all arithmetic mod
+# 2^64, G and mix those of diff_pa's key:
+#     h(b, c) = mix(mix(seed + G b) + G (c + 1)),   m(b, c) = #{k in 0..14: h(b, c) >= P[k]},   replicate 0: m = 1
+#     P[k] = floor(2^64 e^-1 sum_{i <= k} 1 / i!) = BOOT_THRESHOLDS[k]: Poisson(1), the tail beyond 15 folded into 15
+# The hash sees the cell, not the position: replicate b is the same resampled data set for every cluster, every
+# --idents choice and every later command.  Kept rows are the labels < K with a read in a tested cell; a record is
+# reported when it has two or more and span = max x - min x > 0 over their positions x_i = alpha_arr[label] (a
+# non-finite one is diff_pa_len's ValueError); q_i and s are diff_pa_len_groups's (_quantise_positions, 22 bits); a record
+# of 2^27 reads or more in the tested cells is a ValueError.  With c_ij the count of kept row i at position j:
+#     A_g(b) = sum_i sum_{j in g} m(b, cell[j]) c_ij,   Q_g(b) = sum_i q_i sum_{j in g} m(b, cell[j]) c_ij   (exact integers)
+#     v_g(b) = (double)Q_g(b) / (double)A_g(b), one IEEE division;  +infinity when A_g(b) = 0
+#     D_g = #{b in 1..n_boot: A_g(b) > 0},   k = max(1, (D_g + 1) (10000 - L) // 20000),   L = the level in basis points
+#     lo = the k-th smallest of the n_boot values,  hi = the (D_g + 1 - k)-th smallest;  no interval when D_g = 0
+# One line per reported record and population with A_g(0) > 0: reads = A_g(0), mean_pos = the exact rational of the exact
+# x_i rounded once (diff_pa_len_groups's mean_pos.<g>), mean_pos_lo / _hi = min x + ldexp(lo / hi, -s), exp_length =
+# _exp_len_rows of the population's counts over all K labels, exp_length_lo / _hi = 1.0 + 9.0 * (y - a[0]) / (a[-1] - a[0])
+# with y = mean_pos_lo / _hi and a = alpha_arr (empty when exp_length is nan or a[-1] - a[0] is not finite and positive),
+# n_empty = n_boot - D_g.  Everything is an integer up to one correctly rounded division per value, so the file is exact
+# text.  (include/scape_hip.h states the device's side.)
+BOOT_PA_LEN_HEADER = ["gene", "group", "num_pa", "reads", "mean_pos", "mean_pos_lo", "mean_pos_hi", "exp_length",
+                      "exp_length_lo", "exp_length_hi", "n_empty", "n_boot", "level"]
+BOOT_THRESHOLDS = (0x5E2D58D8B3BCDF1A, 0xBC5AB1B16779BE35, 0xEB715E1DC1582DC2, 0xFB23979734A252F1, 0xFF1025F59174DC3D,
+                   0xFFD90F3BA4055E19, 0xFFFA8B71FC72C913, 0xFFFF540C0914B3C9, 0xFFFFED1F4AA8F120, 0xFFFFFE216E641462,
+                   0xFFFFFFD4D85D3183, 0xFFFFFFFC6DA262B4, 0xFFFFFFFFBA12D178, 0xFFFFFFFFFB07C64C, 0xFFFFFFFFFFAB8EA5)
+BOOT_MAX_READS = 1 << 27         # reads of a record in the tested cells: 15 T stays below 2^31 and 15 T 2^22 below 2^53
+
+
+def _parse_level(level):
+    """the level in basis points: a decimal string in percent with at most two decimals, 0 < level < 100, through
+    decimal, never a float ("95" -> 9500, "99.5" -> 9950, "90.00" -> 9000)"""
+    text = str(level)
+    if not re.fullmatch(r"[0-9]+(\.[0-9]{1,2})?", text):
+        raise ValueError(f"level must be a percentage with at most two decimals, such as 95 or 99.5, not {text!r}")
+    bp = int(decimal.Decimal(text) * 100)
+    if not 0 < bp < 10000:
+        raise ValueError(f"level must lie above 0 and below 100, not {text!r}")
+    return bp
+
+
+def _boot_rank(n_def, level_bp):
+    """k of the interval rule: lo is the k-th smallest value and hi the (n_def + 1 - k)-th"""
+    return max(1, (n_def + 1) * (10000 - level_bp) // 20000)
+
+
+def _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed):
+    """what boot_pa_len does before the device is opened: the option checks, then the prerequisites and the populations
+    (_groups_setup's checks of --idents; without a cluster file the one population all_cell), the id -> column table
+    that puts population 0's columns first, the cell of every position, and the output path
+    <cluster file stem>.<gene|utr>[.<A>+<B>+...].boot_pa_len.csv or all_cell.<gene|utr>.boot_pa_len.csv"""
+    if n_boot < 1:
+        raise ValueError(f"n_boot must be at least 1, not {n_boot}")
+    if n_boot >= 1 << 31:
+        raise ValueError(f"n_boot must be below 2^31, not {n_boot}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
+    level_bp = _parse_level(level)
+    if cell_cluster_file is None:
+        if idents:
+            raise ValueError("idents needs a cell_cluster_file")
+        inp = _read_inputs(output_dir, res_pkl_file)
+        pops = [("all_cell", np.arange(inp.n_cols, dtype=np.int64))]
+        outpath = os.path.join(output_dir, "all_cell." + res_pkl_file.replace(".pkl", "").replace("res.", "") +
+                               ".boot_pa_len.csv")
+    else:
+        idents, tag, inp, pops = _ident_populations(output_dir, res_pkl_file, cell_cluster_file, idents)
+        if not idents and len(pops) > MAX_GROUPS:
+            raise ValueError(f"{len(pops)} clusters: boot_pa_len takes at most {MAX_GROUPS} at once, name them with "
+                             "--idents")
+        if not 1 <= len(pops) <= MAX_GROUPS:
+            raise ValueError(f"{len(pops)} populations: boot_pa_len takes 1 to {MAX_GROUPS}")
+        outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + ".boot_pa_len.csv"
+    sizes = np.array([len(cols) for _name, cols in pops], dtype=np.int32)
+    n = int(sizes.sum())
+    if n >= MAX_PERM_CELLS:
+        raise ValueError(f"{n} tested cells: boot_pa_len takes fewer than {MAX_PERM_CELLS}")
+    _table, slot, seg_off, _seg_pop = _samples(pops, 1, inp.n_cols)
+    cell = np.ascontiguousarray(np.concatenate([cols for _name, cols in pops]), dtype=np.int32)
+
+    def labellings(ctx, b_first, b_count):
+        check(ctx.lib.scape_hip_report_boot_mult(ctx.h, n, ptr(cell, P_i32), b_first, b_count, seed), "report_boot_mult")
+    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, n=n, cell=cell,
+                           names=[name for name, _cols in pops], outpath=outpath, level=str(level), level_bp=level_bp,
+                           perm_bytes=n,                 # one byte per tested cell and replicate
+                           labellings=labellings, idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
+
+
+def _boot_columns(lo, hi, x_min, s, alpha_arr, exp_length):
+    """the four interval fields of a line as text, from the order statistics lo and hi of the integer positions (None:
+    no replicate has a read), min x and the scale s of the record: mean_pos_lo / _hi = min x + ldexp(lo / hi, -s), one
+    f64 add each, and exp_length_lo / _hi = 1.0 + 9.0 * (y - a[0]) / (a[-1] - a[0]) in f64 in that order of operations,
+    empty when exp_length is nan or a[-1] - a[0] is not finite and positive"""
+    if lo is None:
+        return ["", "", "", ""]
+    ys = [float(x_min) + math.ldexp(float(v), -s) for v in (lo, hi)]
+    a = np.asarray(alpha_arr, dtype=np.float64)
+    a0, width = float(a[0]), float(a[-1]) - float(a[0])
+    if math.isnan(exp_length) or not (math.isfinite(width) and width > 0):
+        return [repr(ys[0]), repr(ys[1]), "", ""]
+    return [repr(y) for y in ys] + [repr(1.0 + 9.0 * (y - a0) / width) for y in ys]
+
+
+def _boot_pa_len_batch(su, n_boot, out, ctx, bat, chunk, times):
+    """one counted batch: appends the file's lines (lists of fields) of its reported records to `out` and adds their
+    number to su.n_records"""
+    recs, K, G = bat.recs, bat.K, len(su.sizes)
+    pos = {}                     # record -> positions of its kept rows (f64, finite)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos), min_pops=1)
+    sel = sel and _with_span(sel, pos, times)
+    if sel is None:
+        return
+    which, off, rows, sums, rowbase, xs = sel
+    t0 = timer()
+    T = np.add.reduceat(sums.sum(axis=1), off[:-1])
+    for g, r in enumerate(which.tolist()):
+        if int(T[g]) >= BOOT_MAX_READS:
+            raise ValueError(f"{recs[r].gene_info_str}: 2^27 or more reads in the tested cells")
+    q = np.ascontiguousarray(np.concatenate([_quantise_positions(x) for x in xs]))
+    scale = [LEN_GROUPS_Q_BITS - math.frexp(float(x.max() - x.min()))[1] for x in xs]
+    times["finish"] += timer() - t0
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
+    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
+        ctx.lib.scape_hip_report_boot_len(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G, ptr(su.seg_off, P_i32),
+                                          ptr(q, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)), "report_boot_len"))
+    _check_row_sums("report_boot_len", t, a0, sums, sums)
+    lo, hi = np.zeros((len(which), G), np.float64), np.zeros((len(which), G), np.float64)
+    n_def = np.zeros((len(which), G), np.int64)
+    # the populations' counts of ALL K labels of the reported records, for the reference's exp_pa_len
+    all_rows = np.concatenate([int(rowbase[r]) + np.arange(int(K[r]), dtype=np.int64) for r in which.tolist()])
+    full = np.zeros((len(all_rows), G), dtype=np.int32)
+    full_nz = np.zeros((len(all_rows), G), dtype=np.int32)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_boot_quantiles(ctx.h, su.level_bp, ptr(lo), ptr(hi), ptr(n_def, P_i64)),
+          "report_boot_quantiles")
+    check(ctx.lib.scape_hip_report_group_sums(ctx.h, G, ptr(su.seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
+                                              ptr(full, P_i32), ptr(full_nz, P_i32)), "report_group_sums")
+    times["render"] += timer() - t0
+    t0 = timer()
+    k0 = 0
+    for g, r in enumerate(which.tolist()):
+        sl = slice(int(off[g]), int(off[g + 1]))
+        a = a0[sl]
+        _mean, mean_g, _delta = _mean_positions_groups(xs[g], a.tolist())
+        k = int(K[r])
+        counts = np.zeros((G, k + 1), dtype=np.int64)    # slot k: reads of no site, which never weigh
+        counts[:, :k] = full[k0:k0 + k].T
+        k0 += k
+        e = _exp_len_rows(k, recs[r].alpha_arr, counts)
+        A = a.sum(axis=0)
+        for p in range(G):
+            if A[p] == 0:
+                continue
+            D = int(n_def[g, p])
+            ends = (float(lo[g, p]), float(hi[g, p])) if D else (None, None)
+            iv = _boot_columns(*ends, float(xs[g].min()), scale[g], recs[r].alpha_arr, float(e[p]))
+            out.append([recs[r].gene_info_str, su.names[p], int(off[g + 1] - off[g]), int(A[p]), repr(mean_g[p])] +
+                       iv[:2] + [repr(float(e[p]))] + iv[2:] + [n_boot - D, n_boot, su.level])
+        su.n_records += 1
+    times["finish"] += timer() - t0
+
+
+def _boot_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file=None, idents=(), n_boot: int = 9999,
+                 level="95", seed: int = 1, device=None):
+    """percentile bootstrap intervals of the mean pA position and of exp_length per record and population (every cluster
+    of the cluster file, the clusters `idents` in the order given, or all cells without a cluster file), by resampling
+    the cells; writes <cluster file stem>.<gene|utr>[.<A>+<B>+...].boot_pa_len.csv or all_cell.<gene|utr>
+    .boot_pa_len.csv in output_dir, one line per reported record and population with reads, and returns its path"""
+    su = _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed)
+    su.n_records = 0
+    out = []
+
+    batch = functools.partial(_boot_pa_len_batch, su, n_boot, out)
+
+    def write(w):
+        w.writerow(BOOT_PA_LEN_HEADER)
+        w.writerows(out)
+
+    # per record the replicate values of every population, 8 bytes each
+    wall = _perm_run(su, n_boot, device, batch, write, record_bytes=len(su.sizes) * n_boot * 8)
+    print(f"Finish {n_boot} bootstrap replicates of {su.n} cells in {len(su.sizes)} populations for {su.n_records} "
+          "reported records")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
 # ---------------------------------------------------------------- cal_exp_pa_len
 def _exp_len_rows(K, alpha_arr, counts):
     """exp_pa_len (apa_core.py:1038-1052) for every row of counts [groups, K + 1] (slot K: reads with label >= K);
@@ -2552,3 +2760,30 @@ def diff_pa_len_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, 
     the cell scores on the covariance of the pA position and the score over the gene's reads, the score's permutations
     those of diff_pa_trend (delta_pos > 0: longer 3'UTRs in cells further along)."""
     _diff_pa_len_trend(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed)
+
+
+@click.command(name="boot_pa_len")
+@_options(*_OUTPUT_OPTIONS,
+          click.option('--cell_cluster_file', type=str, default=None,
+                       help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
+                            'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
+                            'name of the final result. Default: one population, all_cell, of every cell.'),
+          click.option('--idents', type=str, multiple=True,
+                       help='A cluster to report; give the option once per cluster (1 to 64), the order is kept. Needs '
+                            '--cell_cluster_file. Default: every cluster of the cell_cluster_file (at most 64), in order '
+                            'of first appearance.'),
+          click.option('--n_boot', type=int, default=9999, show_default=True,
+                       help='Bootstrap replicates of the cells.'),
+          click.option('--level', type=str, default="95", show_default=True,
+                       help='Level of the percentile intervals in percent, above 0 and below 100, with at most two '
+                            'decimals.'),
+          click.option('--seed', type=int, default=1, show_default=True,
+                       help='Seed of the replicates, 0 .. 2^64 - 1. The same seed resamples the same cells whatever the '
+                            'cluster file and the idents.'))
+def boot_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file, idents, n_boot: int, level: str, seed: int):
+    """How well a cluster's 3'UTR length is known: per gene and cell population, percentile bootstrap intervals of the
+    mean pA position and of the reference's expected pA length (cal_exp_pa_len's 1..10 scale), by resampling the cells
+    (the Poisson bootstrap, in exact integers on the device)."""
+    if idents and cell_cluster_file is None:
+        raise click.UsageError("--idents needs --cell_cluster_file")
+    _boot_pa_len(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed)
