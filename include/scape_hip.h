@@ -568,9 +568,28 @@ int scape_hip_report_boot_mult_get(scape_hip_ctx *ctx, int32_t b, uint8_t *mult_
 int scape_hip_report_boot_len(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                               int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
                               int64_t *a0_out);
-/* The n_boot values of one series (record r, group g: series = r * n_groups + g) of the last boot_len record set. */
+/* boot_pa_usage: the replicate values of the usage of every kept row (pA site) in every population, under the same
+   multiplicities.  (ABI 4 gains this entry point; nothing that was there changes.)  Arguments, t_out, a0_out, the
+   checks (without q), the T < 2^27 refusal and the chunk protocol are scape_hip_report_boot_len's.  With c_ij the count
+   of kept row i at position j, the device forms
+     a_ig(b) = sum_{j in g} m(b, cell[j]) c_ij,     A_g(b) = sum_i a_ig(b) over the kept rows of the row's record
+   as exact integers (A <= 15 T < 2^31), and from them
+     u_ig(b) = (double)a_ig(b) / (double)A_g(b),  one IEEE division, contraction off;  +infinity when A_g(b) = 0.
+   Every defined value lies in 0 .. 1, so the bit patterns order as the values do, with +infinity last.  u_ig(b) is
+   stored at column b - 1 of vals[k * n_groups + g][n_boot], k = the index of the kept row in `rows`: the array, its
+   written columns and scape_hip_report_boot_vals_get / _boot_quantiles are those of boot_len, and a record set belongs
+   to the entry point that began it at replicate 1: a later chunk must name as many rows, the same groups and n_boot and
+   come through the same entry point (a boot_usage chunk behind a boot_len record set is refused, and the reverse).
+   rows x groups x n_boot x 8 bytes must fit one call.  No LDS, no atomics: a_ig and A_g live in registers; a
+   population's nonzeros are walked once for a record of at most 8 kept rows and twice for a longer one. */
+int scape_hip_report_boot_usage(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out,
+                                int64_t *a0_out);
+/* The n_boot values of one series of the last boot_len record set (record r, group g: series = r * n_groups + g) or
+   boot_usage record set (kept row k, group g: series = k * n_groups + g), whichever came last. */
 int scape_hip_report_boot_vals_get(scape_hip_ctx *ctx, int64_t series, double *vals_out);
-/* Per series of the last boot_len record set, over its n_boot values and a level of level_bp basis points (1 .. 9999):
+/* Per series of the last boot_len or boot_usage record set, over its n_boot values and a level of level_bp basis points
+   (1 .. 9999):
      n_def_out = D = #{b in 1..n_boot : A_g(b) > 0},   k = max(1, floor((D + 1) * (10000 - level_bp) / 20000)) in integers,
      lo_out = the k-th smallest value,   hi_out = the (D + 1 - k)-th smallest;   both +infinity when D = 0
    by a radix select over the values' bit patterns (no sort, no cap on n_boot).  Refused unless every column 1 .. n_boot

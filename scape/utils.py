@@ -6,8 +6,9 @@ it between two (per pA site, and per gene for a shift of the 3'UTR length), and 
 ``diff_pa_len_pairs`` and ``diff_pa_len_markers``, which run ``diff_pa_len`` on the same pairs and markers, and
 ``diff_pa_trend`` and ``diff_pa_len_trend``, which test pA usage and 3'UTR length along a per-cell score such as
 pseudotime, and ``ex_pa_len_mat``, the gene x cell matrix of the expected pA length, and ``boot_pa_len``, the
-bootstrap intervals of a cluster's mean pA position and expected pA length."""
-from scape_amd.report import (boot_pa_len, cal_exp_pa_len, diff_pa, diff_pa_groups, diff_pa_len,  # noqa: F401
-                              diff_pa_len_groups, diff_pa_len_markers, diff_pa_len_pairs, diff_pa_len_trend,
-                              diff_pa_markers, diff_pa_pairs, diff_pa_trend, ex_pa_cnt_mat, ex_pa_len_mat,
-                              ex_pa_pseudobulk)
+bootstrap intervals of a cluster's mean pA position and expected pA length, and ``boot_pa_usage``, those of its usage
+of every pA site."""
+from scape_amd.report import (boot_pa_len, boot_pa_usage, cal_exp_pa_len, diff_pa, diff_pa_groups,  # noqa: F401
+                              diff_pa_len, diff_pa_len_groups, diff_pa_len_markers, diff_pa_len_pairs,
+                              diff_pa_len_trend, diff_pa_markers, diff_pa_pairs, diff_pa_trend, ex_pa_cnt_mat,
+                              ex_pa_len_mat, ex_pa_pseudobulk)

@@ -48,11 +48,13 @@
 //   k_rep_len_trend_obs / k_rep_perm_len_trend
 //                   diff_pa_len_trend: on the same scores, the covariance of the pA position and the score over a
 //                   record's reads as a 128-bit integer, compared exactly; one walk of the nonzeros, no f64
-// The last section is not a test but the cell bootstrap on the same compaction (boot_pa_len):
-//   k_rep_boot_mult / k_rep_boot_len / k_rep_boot_select
+// The last section is not a test but the cell bootstrap on the same compaction (boot_pa_len, boot_pa_usage):
+//   k_rep_boot_mult / k_rep_boot_len / k_rep_boot_usage / k_rep_boot_select
 //                   a Poisson(1) multiplicity per (cell, replicate) as a byte, read off the hash by integer comparisons;
-//                   per (record, population, replicate) the mean pA position from two exact integer sums; and per
-//                   (record, population) the two order statistics of a percentile interval by a radix select
+//                   per (record, population, replicate) the mean pA position from two exact integer sums, or per (kept
+//                   row, population, replicate) the row's share of the population's reads from two; and per series the
+//                   two order statistics of a percentile interval by a radix select (rep_boot_values: the one frame of
+//                   both record sets)
 // On the host a builder leaves a RepLabellings in ReportState (what it built, for the checks of the tests and of the
 // `_get` entry points).  A test fills a RepPermCall, the one frame of its call: rep_perm_prepare checks and compacts from
 // it, rep_perm_launch_classes launches a two-population test per LDS class of records, rep_perm_count brings the
@@ -2405,8 +2407,17 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
 //                      registers, every nonzero is read once, and there is no LDS, no atomic, no barrier and no slice
 //   k_rep_boot_select  one workgroup per series: D by a count, then a radix select over the bit patterns, most
 //                      significant byte first, both ranks in the same eight passes over the series (which stays in L2)
+// boot_pa_usage, on the same multiplicities: with a_ig(b) = sum_{j in g} m(b, cell[j]) c_ij and A_g(b) = sum_i a_ig(b),
+//   u_ig(b) = (double)a_ig(b) / (double)A_g(b),  one IEEE division, contraction off;  +infinity when A_g(b) = 0
+// per series (kept row i, population g).  Every defined value lies in 0 .. 1, so the bit patterns order as above and D,
+// k, lo and hi are the same rule by the same k_rep_boot_select.
+//   k_rep_boot_usage   workgroup and lanes of k_rep_boot_len; per population the a_ig of a record of up to 8 kept rows
+//                      from one walk, held in registers until A_g is known; of a longer record A_g by a walk over all
+//                      its rows, then a_ig row by row; the quotients stored along the replicates; no LDS, atomic or
+//                      barrier
 #define REP_BOOT_READS_BITS 27         // T < 2^27
 #define REP_BOOT_MULT_POS 64           // positions a workgroup of k_rep_boot_mult takes per step
+#define REP_BOOT_USAGE_REG_ROWS 8      // kept rows of a record up to which k_rep_boot_usage holds every a_ig in a register
 
 __device__ __forceinline__ int rep_boot_mult(unsigned long long h) {
     constexpr unsigned long long P[15] = {
@@ -2462,6 +2473,64 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_len(
         if (valid)
             vals[((int64_t)r * n_groups + g) * n_boot + col0 + p] =
                 A > 0 ? (double)Q / (double)A : __builtin_huge_val();
+    }
+}
+
+// boot_pa_usage: workgroup and lanes as k_rep_boot_len; series = kept row i of the call (not the record) x population.
+// vals[(i * n_groups + g) * n_boot + col0 + replicate of the chunk] = (double)a_ig / (double)A_g, stored along the
+// replicates.  15 T < 2^31: both sums are 32-bit.  A record of at most REP_BOOT_USAGE_REG_ROWS kept rows takes one walk
+// per population, the a_ig of its rows in registers until A_g is known (the branch is uniform over the workgroup);
+// a longer one takes two: A_g over all its rows, then a_ig row by row, which finds the multiplicity bytes of the first
+// walk in cache.  Measured at records of 2..8 rows: 32.9 ms with the one walk, 50.3 ms with two walks for every record
+__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_usage(
+    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, int32_t n_groups,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz, int64_t n_boot,
+    int64_t col0, double *__restrict__ vals) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < b_count;
+    const uint8_t *mb = mult + (valid ? p : b_count - 1);
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    const int stride = n_groups + 1;
+    if (row1 - row0 <= REP_BOOT_USAGE_REG_ROWS) {           // one walk: a_ig of every row stays in a register
+        for (int g = 0; g < n_groups; ++g) {
+            int a[REP_BOOT_USAGE_REG_ROWS];
+            int A = 0;
+#pragma unroll
+            for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k) {
+                a[k] = 0;
+                if (row0 + k < row1) {
+                    const int64_t *si = sg + (row0 + k) * stride;
+                    int s = 0;
+                    rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { s += m * c; });
+                    a[k] = s;
+                    A += s;
+                }
+            }
+            const double dA = (double)A;
+#pragma unroll
+            for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k)
+                if (row0 + k < row1 && valid)
+                    vals[((row0 + k) * n_groups + g) * n_boot + col0 + p] =
+                        A > 0 ? (double)a[k] / dA : __builtin_huge_val();
+        }
+        return;
+    }
+    for (int g = 0; g < n_groups; ++g) {
+        int A = 0;
+        for (int64_t i = row0; i < row1; ++i) {
+            const int64_t *si = sg + i * stride;
+            rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { A += m * c; });
+        }
+        const double dA = (double)A;
+        for (int64_t i = row0; i < row1; ++i) {
+            const int64_t *si = sg + i * stride;
+            int a = 0;
+            rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { a += m * c; });
+            if (valid)
+                vals[(i * n_groups + g) * n_boot + col0 + p] = A > 0 ? (double)a / dA : __builtin_huge_val();
+        }
     }
 }
 
@@ -2578,9 +2647,14 @@ static int rep_boot_build(scape_hip_ctx *c, int32_t n, const int32_t *cell, int6
     return rep_built(drain, s->boot, n, b_count);
 }
 
-static int rep_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
-                        int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
-                        int64_t *a0_out) {
+// The frame of scape_hip_report_boot_len (q = the rows' positions, one series per record and group) and of
+// scape_hip_report_boot_usage (usage: no q, one series per kept row and group): the checks, the compaction with the
+// segment starts, the values' array and its written columns; launch(k, grid) queues the entry point's kernel.  A record
+// set is its first chunk's entry point's (b_usage): a later chunk through the other one is refused
+template <typename Launch>
+static int rep_boot_values(scape_hip_ctx *c, bool usage, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                           int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
+                           int64_t *a0_out, Launch launch) {
     ReportState *s = report_state(c);
     const RepLabellings &l = s->boot;
     if (l.ready(s->n_cnt_rows)) return 1;
@@ -2593,36 +2667,60 @@ static int rep_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_
     const int64_t b_first = s->b_first, b_count = l.count;
     if (n_boot < 1 || n_boot > INT32_MAX || b_first + b_count - 1 > n_boot)
         return fail("the replicates of the last " + std::string(l.builder) + " call must lie in 1 .. n_boot, and n_boot below 2^31");
-    if (n_rec <= 0) return fail("bad argument");
-    const int64_t n_series = (int64_t)n_rec * n_groups;
-    if (b_first > 1 && (n_series != s->b_series || n_groups != s->b_groups || n_boot != s->b_n_boot))
-        return fail("a later chunk of replicates needs the records, groups and n_boot of the call that began at replicate 1");
-    if (n_series > INT32_MAX || n_series > INT64_MAX / 8 / n_boot) return fail("too many records x groups x replicates for one call");
+    if (n_rec <= 0 || (usage && !rec_row_off)) return fail("bad argument");
+    if (usage && (rec_row_off[n_rec] <= 0 || rec_row_off[n_rec] > INT32_MAX))
+        return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
+    const int64_t n_series = (usage ? rec_row_off[n_rec] : (int64_t)n_rec) * n_groups;
+    if (b_first > 1 && (n_series != s->b_series || n_groups != s->b_groups || n_boot != s->b_n_boot || usage != s->b_usage))
+        return fail("a later chunk of replicates needs the records, groups and n_boot of the call that began at replicate 1, "
+                    "and its entry point");
+    if (n_series > INT32_MAX || n_series > INT64_MAX / 8 / n_boot)
+        return fail(std::string("too many ") + (usage ? "rows" : "records") + " x groups x replicates for one call");
     RepPermCall k(c, l, n_rec, rec_row_off, rows, t_out);
-    k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off, k.q = q, k.outs_ok = q != nullptr;
+    k.a0_out = a0_out, k.n_groups = n_groups, k.seg_off = seg_off, k.q = q, k.outs_ok = usage || q != nullptr;
     k.reads_bits = REP_BOOT_READS_BITS;
     if (rep_perm_prepare(c, k)) return 1;
-    if (rep_pair_segments(c, k, n_groups) || s->b_q.ensure(k.n_rows * 4)) return 1;
+    if (rep_pair_segments(c, k, n_groups) || (q && s->b_q.ensure(k.n_rows * 4))) return 1;
     if (b_first == 1) {
         s->b_series = 0;                       // nothing to select from until this call has succeeded
         if (s->b_vals.ensure(n_series * n_boot * 8)) return 1;
         s->b_written.assign((size_t)n_boot, 0);
     }
-    HIPCHK(hipMemcpyAsync(s->b_q.p, q, k.n_rows * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_rep_boot_len, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), 0, c->stream,
-                       s->b_mult.as<uint8_t>(), k.p_count, k.n_tiles, n_groups, s->p_roff.as<int64_t>(),
-                       s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(), s->b_q.as<int32_t>(), n_boot, b_first - 1,
-                       s->b_vals.as<double>());
+    if (q) HIPCHK(hipMemcpyAsync(s->b_q.p, q, k.n_rows * 4, hipMemcpyHostToDevice, c->stream));
+    launch(k, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)));
     HIPCHK(hipGetLastError());
     if (k.drain.wait()) return 1;
-    s->b_series = n_series, s->b_groups = n_groups, s->b_n_boot = (int32_t)n_boot;
+    s->b_series = n_series, s->b_groups = n_groups, s->b_n_boot = (int32_t)n_boot, s->b_usage = usage;
     std::fill(s->b_written.begin() + (b_first - 1), s->b_written.begin() + (b_first - 1 + b_count), 1);
     return 0;
 }
 
-// the replicate values are there: a boot_len call has succeeded since they were allocated
+static int rep_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                        int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
+                        int64_t *a0_out) {
+    ReportState *s = report_state(c);
+    return rep_boot_values(c, false, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out,
+                           [&](const RepPermCall &k, dim3 grid) {
+        hipLaunchKernelGGL(k_rep_boot_len, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
+                           k.n_tiles, n_groups, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
+                           s->b_q.as<int32_t>(), n_boot, s->b_first - 1, s->b_vals.as<double>());
+    });
+}
+
+static int rep_boot_usage(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                          int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out, int64_t *a0_out) {
+    ReportState *s = report_state(c);
+    return rep_boot_values(c, true, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr, n_boot, t_out, a0_out,
+                           [&](const RepPermCall &k, dim3 grid) {
+        hipLaunchKernelGGL(k_rep_boot_usage, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
+                           k.n_tiles, n_groups, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
+                           n_boot, s->b_first - 1, s->b_vals.as<double>());
+    });
+}
+
+// the replicate values are there: a boot_len or boot_usage call has succeeded since they were allocated
 static int rep_boot_vals_ok(const ReportState *s) {
-    return s->b_series ? 0 : fail("scape_hip_report_boot_len has not been called");
+    return s->b_series ? 0 : fail("scape_hip_report_boot_usage or scape_hip_report_boot_len has not been called");
 }
 
 static int rep_boot_quantiles(scape_hip_ctx *c, int32_t level_bp, double *lo_out, double *hi_out, int64_t *n_def_out) {
@@ -2673,12 +2771,20 @@ int scape_hip_report_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *re
                           rep_boot_len(c, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out));
 }
 
+int scape_hip_report_boot_usage(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out,
+                                int64_t *a0_out) {
+    CTX_ENTER(c);
+    return rep_boot_named("scape_hip_report_boot_usage",
+                          rep_boot_usage(c, n_rec, rec_row_off, rows, n_groups, seg_off, n_boot, t_out, a0_out));
+}
+
 int scape_hip_report_boot_vals_get(scape_hip_ctx *c, int64_t series, double *vals_out) {
     CTX_ENTER(c);
     ReportState *s = report_state(c);
     if (rep_boot_vals_ok(s)) return rep_boot_named("scape_hip_report_boot_vals_get", 1);
     if (!vals_out || series < 0 || series >= s->b_series)
-        return rep_boot_named("scape_hip_report_boot_vals_get", fail("series must name a (record, group) of the last boot_len call"));
+        return rep_boot_named("scape_hip_report_boot_vals_get", fail("series must name a series of the last boot_len or boot_usage record set"));
     StreamDrain drain(c->stream);
     HIPCHK(hipMemcpyAsync(vals_out, s->b_vals.as<double>() + series * s->b_n_boot, (int64_t)s->b_n_boot * 8,
                           hipMemcpyDeviceToHost, c->stream));

@@ -1014,9 +1014,10 @@ def _perm_run(su, n_perm, device, batch, write, record_bytes=0):
     """the run the permutation commands share: the masks (once, when all permutations, at su.perm_bytes device bytes
     each, fit MAX_PERM_BYTES; otherwise per chunk inside every batch), batch(ctx, counted batch, chunk, times) per
     counted batch, then write(csv writer) into the .part file that is renamed when complete.  record_bytes = device
-    bytes a record takes beside its counts and nonzeros (boot_pa_len's replicate values).  Returns the wall seconds;
-    LAST_TIMES holds the stages"""
+    bytes a record takes beside its counts and nonzeros (boot_pa_len's replicate values), a number or, where they depend
+    on the record (boot_pa_usage's), a function of it.  Returns the wall seconds; LAST_TIMES holds the stages"""
     counts_cost = _batch_cost(su.n_cols, 12)
+    extra = record_bytes if callable(record_bytes) else lambda p: record_bytes
     with _Run(device, [su.outpath]) as run:
         times = run.times
         with open(run.parts[0], "w", newline="") as fh:
@@ -1029,7 +1030,7 @@ def _perm_run(su, n_perm, device, batch, write, record_bytes=0):
             if MAX_BATCH_BYTES is None:
                 budget //= 2
             # the counts of a record and, at worst, as many 8-byte nonzeros as it has tested counts
-            for bat in _counted(ctx, su.res_pkl, su.idmap, su.n_cols, lambda p: counts_cost(p) + record_bytes, budget,
+            for bat in _counted(ctx, su.res_pkl, su.idmap, su.n_cols, lambda p: counts_cost(p) + extra(p), budget,
                                 times):
                 batch(ctx, bat, chunk, times)
             t0 = timer()
@@ -2244,11 +2245,12 @@ def _boot_rank(n_def, level_bp):
     return max(1, (n_def + 1) * (10000 - level_bp) // 20000)
 
 
-def _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed):
-    """what boot_pa_len does before the device is opened: the option checks, then the prerequisites and the populations
-    (_groups_setup's checks of --idents; without a cluster file the one population all_cell), the id -> column table
-    that puts population 0's columns first, the cell of every position, and the output path
-    <cluster file stem>.<gene|utr>[.<A>+<B>+...].boot_pa_len.csv or all_cell.<gene|utr>.boot_pa_len.csv"""
+def _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed, command="boot_pa_len"):
+    """what boot_pa_len and boot_pa_usage (`command`: the name in messages and the output suffix) do before the device
+    is opened: the option checks, then the prerequisites and the populations (_groups_setup's checks of --idents;
+    without a cluster file the one population all_cell), the id -> column table that puts population 0's columns
+    first, the cell of every position, and the output path
+    <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv or all_cell.<gene|utr>.<command>.csv"""
     if n_boot < 1:
         raise ValueError(f"n_boot must be at least 1, not {n_boot}")
     if n_boot >= 1 << 31:
@@ -2262,19 +2264,19 @@ def _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, lev
         inp = _read_inputs(output_dir, res_pkl_file)
         pops = [("all_cell", np.arange(inp.n_cols, dtype=np.int64))]
         outpath = os.path.join(output_dir, "all_cell." + res_pkl_file.replace(".pkl", "").replace("res.", "") +
-                               ".boot_pa_len.csv")
+                               f".{command}.csv")
     else:
         idents, tag, inp, pops = _ident_populations(output_dir, res_pkl_file, cell_cluster_file, idents)
         if not idents and len(pops) > MAX_GROUPS:
-            raise ValueError(f"{len(pops)} clusters: boot_pa_len takes at most {MAX_GROUPS} at once, name them with "
+            raise ValueError(f"{len(pops)} clusters: {command} takes at most {MAX_GROUPS} at once, name them with "
                              "--idents")
         if not 1 <= len(pops) <= MAX_GROUPS:
-            raise ValueError(f"{len(pops)} populations: boot_pa_len takes 1 to {MAX_GROUPS}")
-        outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + ".boot_pa_len.csv"
+            raise ValueError(f"{len(pops)} populations: {command} takes 1 to {MAX_GROUPS}")
+        outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + f".{command}.csv"
     sizes = np.array([len(cols) for _name, cols in pops], dtype=np.int32)
     n = int(sizes.sum())
     if n >= MAX_PERM_CELLS:
-        raise ValueError(f"{n} tested cells: boot_pa_len takes fewer than {MAX_PERM_CELLS}")
+        raise ValueError(f"{n} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
     _table, slot, seg_off, _seg_pop = _samples(pops, 1, inp.n_cols)
     cell = np.ascontiguousarray(np.concatenate([cols for _name, cols in pops]), dtype=np.int32)
 
@@ -2380,6 +2382,95 @@ def _boot_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file=None, ide
     wall = _perm_run(su, n_boot, device, batch, write, record_bytes=len(su.sizes) * n_boot * 8)
     print(f"Finish {n_boot} bootstrap replicates of {su.n} cells in {len(su.sizes)} populations for {su.n_records} "
           "reported records")
+    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- boot_pa_usage
+# How well is a cluster's usage of a pA site known?  Percentile intervals of the quantity the diff_pa family tests, per
+# record, kept row (site) and population, from boot_pa_len's cell bootstrap: options, checks, populations, tested columns
+# and the multiplicities m(b, c) are boot_pa_len's (_boot_setup), so replicate b is the same resampled data set in both
+# files.  Kept rows of a record are the labels < K with a read in a tested cell; a record is reported when it has two or
+# more.  Positions play no part: no span condition, and alpha_arr need not be finite.  A record of 2^27 reads or more in
+# the tested cells is boot_pa_len's ValueError.  With c_ij the count of kept row i at position j, m = 1 for b = 0:
+#     a_ig(b) = sum_{j in g} m(b, cell[j]) c_ij,   A_g(b) = sum_i a_ig(b)                 (exact integers, A <= 15 T < 2^31)
+#     u_ig(b) = (double)a_ig(b) / (double)A_g(b), one IEEE division;  +infinity when A_g(b) = 0
+#     D_g, k, lo, hi: boot_pa_len's rule, per series (kept row i, population g) over u_ig(1 .. n_boot)
+# Every defined value lies in 0 .. 1, so the bit patterns order as the values do and the select is boot_pa_len's.  One
+# line per reported record, kept row and population with A_g(0) > 0, records in file order, then kept rows by ascending
+# label, then populations in their order: pa_info = diff_pa's, num_pa = the kept rows, reads = a_ig(0), gene_reads =
+# A_g(0), usage = repr(a_ig(0) / A_g(0)) (diff_pa's usage.1 text for the same populations), usage_lo / _hi = repr of lo /
+# hi (empty when D_g = 0), n_empty = n_boot - D_g.  A site the population has no read at keeps its line (reads 0, usage
+# 0.0): its upper end is information.  Nothing rounds but the one division, so the file is exact text.
+BOOT_PA_USAGE_HEADER = ["gene", "pa_info", "group", "num_pa", "reads", "gene_reads", "usage", "usage_lo", "usage_hi",
+                        "n_empty", "n_boot", "level"]
+
+
+def _boot_pa_usage_batch(su, n_boot, out, ctx, bat, chunk, times):
+    """one counted batch: appends the file's lines (lists of fields) of its reported records to `out` and adds their
+    number to su.n_records and that of their kept rows to su.n_sites"""
+    recs, G = bat.recs, len(su.sizes)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, min_pops=1)
+    if sel is None:
+        return
+    which, off, rows, _nz, sums, rowbase = sel
+    t0 = timer()
+    T = np.add.reduceat(sums.sum(axis=1), off[:-1])
+    for g, r in enumerate(which.tolist()):
+        if int(T[g]) >= BOOT_MAX_READS:
+            raise ValueError(f"{recs[r].gene_info_str}: 2^27 or more reads in the tested cells")
+    times["finish"] += timer() - t0
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
+    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
+        ctx.lib.scape_hip_report_boot_usage(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G,
+                                            ptr(su.seg_off, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)),
+        "report_boot_usage"))
+    _check_row_sums("report_boot_usage", t, a0, sums, sums)
+    lo, hi = np.zeros((len(rows), G), np.float64), np.zeros((len(rows), G), np.float64)
+    n_def = np.zeros((len(rows), G), np.int64)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_boot_quantiles(ctx.h, su.level_bp, ptr(lo), ptr(hi), ptr(n_def, P_i64)),
+          "report_boot_quantiles")
+    times["render"] += timer() - t0
+    t0 = timer()
+    for g, r in enumerate(which.tolist()):
+        i0, i1 = int(off[g]), int(off[g + 1])
+        A = a0[i0:i1].sum(axis=0).tolist()
+        pa = _pa_info(recs[r], rows[i0:i1] - int(rowbase[r]))
+        for i in range(i0, i1):
+            a, D = a0[i].tolist(), n_def[i].tolist()
+            for p in range(G):
+                if A[p] == 0:
+                    continue
+                ends = [repr(float(lo[i, p])), repr(float(hi[i, p]))] if D[p] else ["", ""]
+                out.append([recs[r].gene_info_str, pa[i - i0], su.names[p], i1 - i0, a[p], A[p], repr(a[p] / A[p])] +
+                           ends + [n_boot - D[p], n_boot, su.level])
+        su.n_records += 1
+        su.n_sites += i1 - i0
+    times["finish"] += timer() - t0
+
+
+def _boot_pa_usage(output_dir: str, res_pkl_file: str, cell_cluster_file=None, idents=(), n_boot: int = 9999,
+                   level="95", seed: int = 1, device=None):
+    """percentile bootstrap intervals of the usage of every pA site per record and population (every cluster of the
+    cluster file, the clusters `idents` in the order given, or all cells without a cluster file), by resampling the
+    cells with boot_pa_len's replicates; writes <cluster file stem>.<gene|utr>[.<A>+<B>+...].boot_pa_usage.csv or
+    all_cell.<gene|utr>.boot_pa_usage.csv in output_dir, one line per reported record, site and population with reads,
+    and returns its path"""
+    su = _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed, "boot_pa_usage")
+    su.n_records = su.n_sites = 0
+    out = []
+
+    batch = functools.partial(_boot_pa_usage_batch, su, n_boot, out)
+
+    def write(w):
+        w.writerow(BOOT_PA_USAGE_HEADER)
+        w.writerows(out)
+
+    # per label of a record (at most that many kept rows) the replicate values of every population, 8 bytes each
+    wall = _perm_run(su, n_boot, device, batch, write, record_bytes=lambda p: int(p.K) * len(su.sizes) * n_boot * 8)
+    print(f"Finish {n_boot} bootstrap replicates of {su.n} cells in {len(su.sizes)} populations for {su.n_sites} pA sites "
+          f"of {su.n_records} reported records")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
     return su.outpath
 
@@ -2762,24 +2853,29 @@ def diff_pa_len_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, 
     _diff_pa_len_trend(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed)
 
 
+# boot_pa_len and boot_pa_usage
+_boot_options = _options(
+    *_OUTPUT_OPTIONS,
+    click.option('--cell_cluster_file', type=str, default=None,
+                 help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
+                      'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
+                      'name of the final result. Default: one population, all_cell, of every cell.'),
+    click.option('--idents', type=str, multiple=True,
+                 help='A cluster to report; give the option once per cluster (1 to 64), the order is kept. Needs '
+                      '--cell_cluster_file. Default: every cluster of the cell_cluster_file (at most 64), in order '
+                      'of first appearance.'),
+    click.option('--n_boot', type=int, default=9999, show_default=True,
+                 help='Bootstrap replicates of the cells.'),
+    click.option('--level', type=str, default="95", show_default=True,
+                 help='Level of the percentile intervals in percent, above 0 and below 100, with at most two '
+                      'decimals.'),
+    click.option('--seed', type=int, default=1, show_default=True,
+                 help='Seed of the replicates, 0 .. 2^64 - 1. The same seed resamples the same cells whatever the '
+                      'cluster file and the idents.'))
+
+
 @click.command(name="boot_pa_len")
-@_options(*_OUTPUT_OPTIONS,
-          click.option('--cell_cluster_file', type=str, default=None,
-                       help='An csv file containing two columns in order: cell barcode index (index) and respective group. '
-                            'Cells with an empty group, or not listed, are left out. Its name will be included in the file '
-                            'name of the final result. Default: one population, all_cell, of every cell.'),
-          click.option('--idents', type=str, multiple=True,
-                       help='A cluster to report; give the option once per cluster (1 to 64), the order is kept. Needs '
-                            '--cell_cluster_file. Default: every cluster of the cell_cluster_file (at most 64), in order '
-                            'of first appearance.'),
-          click.option('--n_boot', type=int, default=9999, show_default=True,
-                       help='Bootstrap replicates of the cells.'),
-          click.option('--level', type=str, default="95", show_default=True,
-                       help='Level of the percentile intervals in percent, above 0 and below 100, with at most two '
-                            'decimals.'),
-          click.option('--seed', type=int, default=1, show_default=True,
-                       help='Seed of the replicates, 0 .. 2^64 - 1. The same seed resamples the same cells whatever the '
-                            'cluster file and the idents.'))
+@_boot_options
 def boot_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file, idents, n_boot: int, level: str, seed: int):
     """How well a cluster's 3'UTR length is known: per gene and cell population, percentile bootstrap intervals of the
     mean pA position and of the reference's expected pA length (cal_exp_pa_len's 1..10 scale), by resampling the cells
@@ -2787,3 +2883,14 @@ def boot_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file, idents, n
     if idents and cell_cluster_file is None:
         raise click.UsageError("--idents needs --cell_cluster_file")
     _boot_pa_len(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed)
+
+
+@click.command(name="boot_pa_usage")
+@_boot_options
+def boot_pa_usage(output_dir: str, res_pkl_file: str, cell_cluster_file, idents, n_boot: int, level: str, seed: int):
+    """How well a cluster's usage of a pA site is known: per gene, pA site and cell population, the site's share of the
+    population's reads of the gene (diff_pa's usage) with a percentile bootstrap interval, by resampling the cells (the
+    replicates of boot_pa_len, in exact integers on the device)."""
+    if idents and cell_cluster_file is None:
+        raise click.UsageError("--idents needs --cell_cluster_file")
+    _boot_pa_usage(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed)
