@@ -585,15 +585,37 @@ int scape_hip_report_boot_len(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *
 int scape_hip_report_boot_usage(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                                 int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out,
                                 int64_t *a0_out);
-/* The n_boot values of one series of the last boot_len record set (record r, group g: series = r * n_groups + g) or
-   boot_usage record set (kept row k, group g: series = k * n_groups + g), whichever came last. */
+/* boot_pa_len_diff and boot_pa_usage_diff: the replicate values of population 0 minus population 1, one series per
+   record (len) or per kept row (usage).  (ABI 4 gains these two entry points; nothing that was there changes.)  The
+   arguments, t_out, a0_out[i * 2 + g], the checks, the T < 2^27 refusal and the chunk protocol are those of
+   scape_hip_report_boot_len and scape_hip_report_boot_usage, except that n_groups must be 2: any other value is refused.
+   With A_g, Q_g, a_ig of those two entry points the device forms, in one walk of the nonzeros for both populations,
+     d(b)   = (double)Q_0(b) / (double)A_0(b) - (double)Q_1(b) / (double)A_1(b)          (boot_len_diff)
+     d_i(b) = (double)a_i0(b) / (double)A_0(b) - (double)a_i1(b) / (double)A_1(b)        (boot_usage_diff)
+   two IEEE divisions and one IEEE subtraction, contraction off: bit for bit v_0(b) - v_1(b) and u_i0(b) - u_i1(b) of the
+   entry points above;  +infinity when A_0(b) = 0 or A_1(b) = 0.  A value is never -0.0 (x - x = +0.0 under round to
+   nearest, and the quotients are never -0).  d(b) is stored at column b - 1 of vals[r][n_boot], d_i(b) of vals[k][n_boot],
+   k = the index of the kept row in `rows`, in the array of boot_len; the record set belongs to the entry point that
+   began it, and a later chunk through any other of the four is refused.  No LDS, no atomics: both populations' sums live
+   in registers. */
+int scape_hip_report_boot_len_diff(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                   int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot,
+                                   int64_t *t_out, int64_t *a0_out);
+int scape_hip_report_boot_usage_diff(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                     int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out,
+                                     int64_t *a0_out);
+/* The n_boot values of one series of the last record set, whichever of the four entry points wrote it: boot_len (record
+   r, group g: series = r * n_groups + g), boot_usage (kept row k, group g: series = k * n_groups + g), boot_len_diff
+   (series = r) or boot_usage_diff (series = k). */
 int scape_hip_report_boot_vals_get(scape_hip_ctx *ctx, int64_t series, double *vals_out);
-/* Per series of the last boot_len or boot_usage record set, over its n_boot values and a level of level_bp basis points
+/* Per series of the last record set of those four, over its n_boot values and a level of level_bp basis points
    (1 .. 9999):
-     n_def_out = D = #{b in 1..n_boot : A_g(b) > 0},   k = max(1, floor((D + 1) * (10000 - level_bp) / 20000)) in integers,
+     n_def_out = D = #{b in 1..n_boot : the value is defined},   k = max(1, floor((D + 1) * (10000 - level_bp) / 20000)) in integers,
      lo_out = the k-th smallest value,   hi_out = the (D + 1 - k)-th smallest;   both +infinity when D = 0
-   by a radix select over the values' bit patterns (no sort, no cap on n_boot).  Refused unless every column 1 .. n_boot
-   has been written since the array was allocated. */
+   by a radix select (no sort, no cap on n_boot) over key(x) = bits(x) ^ (bits(x) >> 63 ? ~0 : 1 << 63), which is
+   monotone over the finite doubles of either sign and puts +infinity above them all; a value is defined when key <
+   key(+infinity), and the result is the inverse map of the selected key.  Over non-negative values the keys order as
+   the bit patterns do.  Refused unless every column 1 .. n_boot has been written since the array was allocated. */
 int scape_hip_report_boot_quantiles(scape_hip_ctx *ctx, int32_t level_bp, double *lo_out, double *hi_out,
                                     int64_t *n_def_out);
 /* wait for a slot's text; *host_ptr stays valid until the next render into that slot or scape_hip_report_free */

@@ -101,6 +101,8 @@ SIGNATURES = {
     "scape_hip_report_boot_mult_get": (c_i, [P_void, c_i32, ctypes.POINTER(ctypes.c_uint8)]),
     "scape_hip_report_boot_len": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, P_i32, c_i64, P_i64, P_i64]),
     "scape_hip_report_boot_usage": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, c_i64, P_i64, P_i64]),
+    "scape_hip_report_boot_len_diff": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, P_i32, c_i64, P_i64, P_i64]),
+    "scape_hip_report_boot_usage_diff": (c_i, [P_void, c_i32, P_i64, P_i64, c_i32, P_i32, c_i64, P_i64, P_i64]),
     "scape_hip_report_boot_vals_get": (c_i, [P_void, c_i64, P_d]),
     "scape_hip_report_boot_quantiles": (c_i, [P_void, c_i32, P_d, P_d, P_i64]),
     "scape_hip_report_fetch": (c_i, [P_void, c_i32, ctypes.POINTER(P_void), P_i64]),

@@ -48,13 +48,15 @@
 //   k_rep_len_trend_obs / k_rep_perm_len_trend
 //                   diff_pa_len_trend: on the same scores, the covariance of the pA position and the score over a
 //                   record's reads as a 128-bit integer, compared exactly; one walk of the nonzeros, no f64
-// The last section is not a test but the cell bootstrap on the same compaction (boot_pa_len, boot_pa_usage):
-//   k_rep_boot_mult / k_rep_boot_len / k_rep_boot_usage / k_rep_boot_select
+// The last section is not a test but the cell bootstrap on the same compaction (boot_pa_len, boot_pa_usage and their
+// two-population differences boot_pa_len_diff, boot_pa_usage_diff):
+//   k_rep_boot_mult / k_rep_boot_len / k_rep_boot_usage / k_rep_boot_len_diff / k_rep_boot_usage_diff / k_rep_boot_select
 //                   a Poisson(1) multiplicity per (cell, replicate) as a byte, read off the hash by integer comparisons;
 //                   per (record, population, replicate) the mean pA position from two exact integer sums, or per (kept
 //                   row, population, replicate) the row's share of the population's reads from two; and per series the
-//                   two order statistics of a percentile interval by a radix select (rep_boot_values: the one frame of
-//                   both record sets)
+//                   two order statistics of a percentile interval by a radix select over a sign-aware key
+//                   (rep_boot_values: the one frame of the four kinds of record set); the _diff kernels form both
+//                   populations' sums in one walk and store the one difference of the two quotients
 // On the host a builder leaves a RepLabellings in ReportState (what it built, for the checks of the tests and of the
 // `_get` entry points).  A test fills a RepPermCall, the one frame of its call: rep_perm_prepare checks and compacts from
 // it, rep_perm_launch_classes launches a two-population test per LDS class of records, rep_perm_count brings the
@@ -2405,8 +2407,9 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
 //                      fixed by its column segment, so the walk goes population by population over the row's nonzeros of
 //                      that segment (k_rep_pair_segidx found where they start): A and Q of the one population live in
 //                      registers, every nonzero is read once, and there is no LDS, no atomic, no barrier and no slice
-//   k_rep_boot_select  one workgroup per series: D by a count, then a radix select over the bit patterns, most
-//                      significant byte first, both ranks in the same eight passes over the series (which stays in L2)
+//   k_rep_boot_select  one workgroup per series: D by a count, then a radix select over the bit patterns (through the
+//                      key below, which keeps this order), most significant byte first, both ranks in the same eight
+//                      passes over the series (which stays in L2)
 // boot_pa_usage, on the same multiplicities: with a_ig(b) = sum_{j in g} m(b, cell[j]) c_ij and A_g(b) = sum_i a_ig(b),
 //   u_ig(b) = (double)a_ig(b) / (double)A_g(b),  one IEEE division, contraction off;  +infinity when A_g(b) = 0
 // per series (kept row i, population g).  Every defined value lies in 0 .. 1, so the bit patterns order as above and D,
@@ -2415,6 +2418,21 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
 //                      from one walk, held in registers until A_g is known; of a longer record A_g by a walk over all
 //                      its rows, then a_ig row by row; the quotients stored along the replicates; no LDS, atomic or
 //                      barrier
+// boot_pa_len_diff and boot_pa_usage_diff, for exactly two populations (segment 0 minus segment 1), one series per
+// record or per kept row:
+//   d(b)   = (double)Q_1(b) / (double)A_1(b) - (double)Q_2(b) / (double)A_2(b)
+//   d_i(b) = (double)a_i1(b) / (double)A_1(b) - (double)a_i2(b) / (double)A_2(b)
+// two IEEE divisions and one IEEE subtraction, contraction off: the v_g and u_ig above, subtracted;  +infinity when
+// A_1(b) = 0 or A_2(b) = 0.  A difference may be negative, so the select orders keys, not bit patterns:
+//   key(x) = bits(x) ^ (bits(x) >> 63 ? ~0 : 1 << 63)
+// is monotone over the finite doubles and puts +infinity above them all; "defined" is key < key(+infinity) and the result
+// is the inverse map of the selected key.  Over non-negative values the keys order as the bit patterns do, so boot_len's
+// and boot_usage's record sets go through the same select and get the bits they always got.  -0.0 (whose key lies below
+// that of +0.0) cannot occur: a quotient of non-negative integers is never -0, and x - x is +0.0 under round-to-nearest.
+//   k_rep_boot_len_diff    k_rep_boot_len's workgroup and lanes; A_1, Q_1, A_2, Q_2 in registers, one walk of every kept
+//                          row's nonzeros, segment 0 into population 1's sums and segment 1 into population 2's
+//   k_rep_boot_usage_diff  k_rep_boot_usage's two shapes: up to 8 kept rows, one walk per population with a_i1 and a_i2
+//                          in registers; more, A_1 and A_2 by a first walk and then row by row
 #define REP_BOOT_READS_BITS 27         // T < 2^27
 #define REP_BOOT_MULT_POS 64           // positions a workgroup of k_rep_boot_mult takes per step
 #define REP_BOOT_USAGE_REG_ROWS 8      // kept rows of a record up to which k_rep_boot_usage holds every a_ig in a register
@@ -2534,27 +2552,127 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_usage(
     }
 }
 
+// boot_pa_len_diff: workgroup and lanes as k_rep_boot_len, two populations, one series per record.
+// vals[r * n_boot + col0 + replicate of the chunk] = Q_1 / A_1 - Q_2 / A_2; sg[i] = the 3 segment starts of kept row i
+__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_len_diff(
+    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, const int64_t *__restrict__ roff,
+    const int64_t *__restrict__ sg, const uint2 *__restrict__ nz, const int32_t *__restrict__ q, int64_t n_boot,
+    int64_t col0, double *__restrict__ vals) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < b_count;
+    const uint8_t *mb = mult + (valid ? p : b_count - 1);
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    long long A1 = 0, Q1 = 0, A2 = 0, Q2 = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        const int64_t *si = sg + i * 3;
+        int a1 = 0, a2 = 0;                  // m <= 15 and the row's reads stay below 2^27
+        rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { a1 += m * c; });
+        rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { a2 += m * c; });
+        const long long qi = q[i];
+        A1 += a1, Q1 += a1 * qi;
+        A2 += a2, Q2 += a2 * qi;
+    }
+    if (valid)
+        vals[(int64_t)r * n_boot + col0 + p] =
+            A1 > 0 && A2 > 0 ? (double)Q1 / (double)A1 - (double)Q2 / (double)A2 : __builtin_huge_val();
+}
+
+// boot_pa_usage_diff: workgroup, lanes and the two shapes of k_rep_boot_usage, two populations, one series per kept row.
+// vals[i * n_boot + col0 + replicate of the chunk] = a_i1 / A_1 - a_i2 / A_2
+__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_usage_diff(
+    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, const int64_t *__restrict__ roff,
+    const int64_t *__restrict__ sg, const uint2 *__restrict__ nz, int64_t n_boot, int64_t col0,
+    double *__restrict__ vals) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
+    const int p = tile * REP_THREADS + threadIdx.x;
+    const bool valid = p < b_count;
+    const uint8_t *mb = mult + (valid ? p : b_count - 1);
+    const int64_t row0 = roff[r], row1 = roff[r + 1];
+    if (row1 - row0 <= REP_BOOT_USAGE_REG_ROWS) {           // one walk per population: a_i1 waits in registers for A_2
+        int a1[REP_BOOT_USAGE_REG_ROWS], a2[REP_BOOT_USAGE_REG_ROWS];
+        int A1 = 0, A2 = 0;
+#pragma unroll
+        for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k) {
+            a1[k] = 0;
+            if (row0 + k < row1) {
+                const int64_t *si = sg + (row0 + k) * 3;
+                int s = 0;
+                rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { s += m * c; });
+                a1[k] = s;
+                A1 += s;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k) {
+            a2[k] = 0;
+            if (row0 + k < row1) {
+                const int64_t *si = sg + (row0 + k) * 3;
+                int s = 0;
+                rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { s += m * c; });
+                a2[k] = s;
+                A2 += s;
+            }
+        }
+        const bool defined = A1 > 0 && A2 > 0;
+        const double dA1 = (double)A1, dA2 = (double)A2;
+#pragma unroll
+        for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k)
+            if (row0 + k < row1 && valid)
+                vals[(row0 + k) * n_boot + col0 + p] =
+                    defined ? (double)a1[k] / dA1 - (double)a2[k] / dA2 : __builtin_huge_val();
+        return;
+    }
+    int A1 = 0, A2 = 0;
+    for (int64_t i = row0; i < row1; ++i) {
+        const int64_t *si = sg + i * 3;
+        rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { A1 += m * c; });
+        rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { A2 += m * c; });
+    }
+    const bool defined = A1 > 0 && A2 > 0;
+    const double dA1 = (double)A1, dA2 = (double)A2;
+    for (int64_t i = row0; i < row1; ++i) {
+        const int64_t *si = sg + i * 3;
+        int a1 = 0, a2 = 0;
+        rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { a1 += m * c; });
+        rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { a2 += m * c; });
+        if (valid)
+            vals[i * n_boot + col0 + p] = defined ? (double)a1 / dA1 - (double)a2 / dA2 : __builtin_huge_val();
+    }
+}
+
+// the select's order: monotone over the finite doubles of either sign, +infinity above them all
+__device__ __forceinline__ unsigned long long rep_boot_key(unsigned long long bits) {
+    return bits ^ (bits >> 63 ? ~0ull : 1ull << 63);
+}
+
+__device__ __forceinline__ unsigned long long rep_boot_unkey(unsigned long long key) {
+    return key ^ (key >> 63 ? 1ull << 63 : ~0ull);
+}
+
 struct RepBootSelectLds {
     __align__(16) int hist[2][256];
-    unsigned long long sel[2];        // per rank looked for: the prefix of its value's bit pattern
+    unsigned long long sel[2];        // per rank looked for: the prefix of its value's key
     long long rank[2];                // and its rank among the values that share the prefix
     int defined;
 };
 
-// one workgroup per series: n_def[series] = D; lo[series], hi[series] by the rule above.  Values tie, so the select takes
-// all eight bytes; wave w < 2 finds the bin of rank w
+// one workgroup per series: n_def[series] = D; lo[series], hi[series] by the rule above, over the keys of the values.
+// Values tie, so the select takes all eight bytes; wave w < 2 finds the bin of rank w
 __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_select(const unsigned long long *__restrict__ vals,
                                                                  int64_t n_boot, int32_t level_bp,
                                                                  double *__restrict__ lo, double *__restrict__ hi,
                                                                  int64_t *__restrict__ n_def) {
     __shared__ RepBootSelectLds lds;
     const unsigned long long *v = vals + (int64_t)blockIdx.x * n_boot;
-    const unsigned long long inf_bits = 0x7FF0000000000000ull;
+    const unsigned long long inf_key = rep_boot_key(0x7FF0000000000000ull);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) lds.defined = 0;
     __syncthreads();
     int mine = 0;
-    for (int64_t i = threadIdx.x; i < n_boot; i += REP_THREADS) mine += v[i] < inf_bits;
+    for (int64_t i = threadIdx.x; i < n_boot; i += REP_THREADS) mine += rep_boot_key(v[i]) < inf_key;
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
     if (lane == 0 && mine) atomicAdd(&lds.defined, mine);
     __syncthreads();
@@ -2576,7 +2694,7 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_select(const unsigned 
         lds.hist[1][threadIdx.x] = 0;
         __syncthreads();
         for (int64_t i = threadIdx.x; i < n_boot; i += REP_THREADS) {
-            const unsigned long long x = v[i];
+            const unsigned long long x = rep_boot_key(v[i]);
 #pragma unroll
             for (int w = 0; w < 2; ++w)
                 if (pass == 0 || (x >> (shift + 8)) == (prefix[w] >> (shift + 8)))
@@ -2614,8 +2732,8 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_select(const unsigned 
         }
     }
     if (threadIdx.x == 0) {
-        lo[blockIdx.x] = __longlong_as_double((long long)prefix[0]);
-        hi[blockIdx.x] = __longlong_as_double((long long)prefix[1]);
+        lo[blockIdx.x] = __longlong_as_double((long long)rep_boot_unkey(prefix[0]));
+        hi[blockIdx.x] = __longlong_as_double((long long)rep_boot_unkey(prefix[1]));
         n_def[blockIdx.x] = D;
     }
 }
@@ -2647,17 +2765,24 @@ static int rep_boot_build(scape_hip_ctx *c, int32_t n, const int32_t *cell, int6
     return rep_built(drain, s->boot, n, b_count);
 }
 
-// The frame of scape_hip_report_boot_len (q = the rows' positions, one series per record and group) and of
-// scape_hip_report_boot_usage (usage: no q, one series per kept row and group): the checks, the compaction with the
-// segment starts, the values' array and its written columns; launch(k, grid) queues the entry point's kernel.  A record
-// set is its first chunk's entry point's (b_usage): a later chunk through the other one is refused
+// The frame of the four entry points that write replicate values, by the kind of their record set: scape_hip_report_
+// boot_len (q = the rows' positions, one series per record and group), _boot_usage (no q, one series per kept row and
+// group) and their differences _boot_len_diff and _boot_usage_diff (exactly two groups, one series per record or per
+// kept row): the checks, the compaction with the segment starts, the values' array and its written columns;
+// launch(k, grid) queues the entry point's kernel.  A record set is its first chunk's entry point's (b_kind): a later
+// chunk through another one is refused
+enum RepBootKind : int32_t { REP_BOOT_LEN, REP_BOOT_USAGE, REP_BOOT_LEN_DIFF, REP_BOOT_USAGE_DIFF };
+
 template <typename Launch>
-static int rep_boot_values(scape_hip_ctx *c, bool usage, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+static int rep_boot_values(scape_hip_ctx *c, RepBootKind kind, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                            int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
                            int64_t *a0_out, Launch launch) {
     ReportState *s = report_state(c);
     const RepLabellings &l = s->boot;
     if (l.ready(s->n_cnt_rows)) return 1;
+    const bool usage = kind == REP_BOOT_USAGE || kind == REP_BOOT_USAGE_DIFF;
+    const bool diff = kind == REP_BOOT_LEN_DIFF || kind == REP_BOOT_USAGE_DIFF;
+    if (diff && n_groups != 2) return fail("n_groups must be 2: the difference is population 0 minus population 1");
     if (n_groups < 1 || n_groups > REP_GROUPS_MAX) return fail("n_groups must lie in 1 .. " + std::to_string(REP_GROUPS_MAX));
     if (!seg_off) return fail("bad argument");
     if (seg_off[0] != 0) return fail("seg_off must start at 0 (position j is column j)");
@@ -2670,8 +2795,8 @@ static int rep_boot_values(scape_hip_ctx *c, bool usage, int32_t n_rec, const in
     if (n_rec <= 0 || (usage && !rec_row_off)) return fail("bad argument");
     if (usage && (rec_row_off[n_rec] <= 0 || rec_row_off[n_rec] > INT32_MAX))
         return fail("rec_row_off must end at the row count, between 1 and 2^31 - 1");
-    const int64_t n_series = (usage ? rec_row_off[n_rec] : (int64_t)n_rec) * n_groups;
-    if (b_first > 1 && (n_series != s->b_series || n_groups != s->b_groups || n_boot != s->b_n_boot || usage != s->b_usage))
+    const int64_t n_series = (usage ? rec_row_off[n_rec] : (int64_t)n_rec) * (diff ? 1 : n_groups);
+    if (b_first > 1 && (n_series != s->b_series || n_groups != s->b_groups || n_boot != s->b_n_boot || kind != s->b_kind))
         return fail("a later chunk of replicates needs the records, groups and n_boot of the call that began at replicate 1, "
                     "and its entry point");
     if (n_series > INT32_MAX || n_series > INT64_MAX / 8 / n_boot)
@@ -2690,7 +2815,7 @@ static int rep_boot_values(scape_hip_ctx *c, bool usage, int32_t n_rec, const in
     launch(k, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)));
     HIPCHK(hipGetLastError());
     if (k.drain.wait()) return 1;
-    s->b_series = n_series, s->b_groups = n_groups, s->b_n_boot = (int32_t)n_boot, s->b_usage = usage;
+    s->b_series = n_series, s->b_groups = n_groups, s->b_n_boot = (int32_t)n_boot, s->b_kind = kind;
     std::fill(s->b_written.begin() + (b_first - 1), s->b_written.begin() + (b_first - 1 + b_count), 1);
     return 0;
 }
@@ -2699,7 +2824,7 @@ static int rep_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_
                         int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
                         int64_t *a0_out) {
     ReportState *s = report_state(c);
-    return rep_boot_values(c, false, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out,
+    return rep_boot_values(c, REP_BOOT_LEN, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out,
                            [&](const RepPermCall &k, dim3 grid) {
         hipLaunchKernelGGL(k_rep_boot_len, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
                            k.n_tiles, n_groups, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
@@ -2710,10 +2835,34 @@ static int rep_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_
 static int rep_boot_usage(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                           int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out, int64_t *a0_out) {
     ReportState *s = report_state(c);
-    return rep_boot_values(c, true, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr, n_boot, t_out, a0_out,
+    return rep_boot_values(c, REP_BOOT_USAGE, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr, n_boot, t_out, a0_out,
                            [&](const RepPermCall &k, dim3 grid) {
         hipLaunchKernelGGL(k_rep_boot_usage, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
                            k.n_tiles, n_groups, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
+                           n_boot, s->b_first - 1, s->b_vals.as<double>());
+    });
+}
+
+static int rep_boot_len_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                             int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
+                             int64_t *a0_out) {
+    ReportState *s = report_state(c);
+    return rep_boot_values(c, REP_BOOT_LEN_DIFF, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out,
+                           [&](const RepPermCall &k, dim3 grid) {
+        hipLaunchKernelGGL(k_rep_boot_len_diff, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
+                           k.n_tiles, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
+                           s->b_q.as<int32_t>(), n_boot, s->b_first - 1, s->b_vals.as<double>());
+    });
+}
+
+static int rep_boot_usage_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                               int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out,
+                               int64_t *a0_out) {
+    ReportState *s = report_state(c);
+    return rep_boot_values(c, REP_BOOT_USAGE_DIFF, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr, n_boot, t_out,
+                           a0_out, [&](const RepPermCall &k, dim3 grid) {
+        hipLaunchKernelGGL(k_rep_boot_usage_diff, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(),
+                           k.p_count, k.n_tiles, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
                            n_boot, s->b_first - 1, s->b_vals.as<double>());
     });
 }
@@ -2777,6 +2926,22 @@ int scape_hip_report_boot_usage(scape_hip_ctx *c, int32_t n_rec, const int64_t *
     CTX_ENTER(c);
     return rep_boot_named("scape_hip_report_boot_usage",
                           rep_boot_usage(c, n_rec, rec_row_off, rows, n_groups, seg_off, n_boot, t_out, a0_out));
+}
+
+int scape_hip_report_boot_len_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                   int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot,
+                                   int64_t *t_out, int64_t *a0_out) {
+    CTX_ENTER(c);
+    return rep_boot_named("scape_hip_report_boot_len_diff",
+                          rep_boot_len_diff(c, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out));
+}
+
+int scape_hip_report_boot_usage_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
+                                     int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out,
+                                     int64_t *a0_out) {
+    CTX_ENTER(c);
+    return rep_boot_named("scape_hip_report_boot_usage_diff",
+                          rep_boot_usage_diff(c, n_rec, rec_row_off, rows, n_groups, seg_off, n_boot, t_out, a0_out));
 }
 
 int scape_hip_report_boot_vals_get(scape_hip_ctx *c, int64_t series, double *vals_out) {

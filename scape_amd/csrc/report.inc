@@ -97,12 +97,13 @@ struct ReportState {
     // integer row positions of scape_hip_report_boot_len; the replicate values of its record set ([series][replicate],
     // f64; series = record * n_groups + group), which columns of them have been written since they were allocated, and
     // what scape_hip_report_boot_quantiles returns per series.  boot_pa_usage: scape_hip_report_boot_usage's record set
-    // takes the place of boot_len's in the same buffers (series = kept row * n_groups + group; b_usage says whose it is)
+    // takes the place of boot_len's in the same buffers (series = kept row * n_groups + group), and so do those of the
+    // two-population differences (series = record, or kept row); b_kind (a RepBootKind) says whose it is
     RepLabellings boot{"scape_hip_report_boot_mult", "multiplicities"};
     DevBuf b_mult, b_cell, b_q, b_vals, b_lo, b_hi, b_def;
     int64_t b_first = 0, b_series = 0;
     int32_t b_n_boot = 0, b_groups = 0;
-    bool b_usage = false;
+    int32_t b_kind = 0;
     std::vector<uint8_t> b_written;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];

@@ -950,23 +950,37 @@ def _log10_labellings(m1, m2):
                for a, b in zip(m1.tolist(), m2.tolist())) / math.log(10)
 
 
+def _two_populations(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, check_options):
+    """the head of the setups of two populations (_perm_setup, _boot_diff_setup): the checks of the idents, the
+    command's own check_options(), then the prerequisites and the populations of _read_inputs, both with a cell"""
+    if idents_1 is None:
+        raise ValueError("idents_1 is required")
+    if idents_1 == idents_2:
+        raise ValueError(f"idents_1 and idents_2 are the same cluster {idents_1!r}")
+    check_options()
+    inp = _read_inputs(output_dir, res_pkl_file, cell_cluster_file, (idents_1, idents_2))
+    pops = inp.pops
+    if len(pops) < 2:
+        empty = "Population2" if pops and pops[0][0] == "Population1" else "Population1"
+        raise ValueError(f"{empty} ({idents_1 if empty == 'Population1' else idents_2 or 'the rest'}) has no cell in "
+                         "barcode_index.csv")
+    return inp
+
+
+def _versus(idents_1, idents_2):
+    """the `versus` column of the files of two populations"""
+    return f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1)
+
+
 def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_perm, seed, command,
                 strata_file=None):
     """what diff_pa and diff_pa_len do before the device is opened: the argument and prerequisite checks, the two
     populations, the id -> column table that puts population 1's columns first and population 2's behind them (with a
     strata file: each ordered by stratum, cells without a stratum left out), and the output path
     <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>[.by_<strata file stem>].<command>.csv"""
-    if idents_1 is None:
-        raise ValueError("idents_1 is required")
-    if idents_1 == idents_2:
-        raise ValueError(f"idents_1 and idents_2 are the same cluster {idents_1!r}")
-    _check_perm_args(n_perm, seed)
-    inp = _read_inputs(output_dir, res_pkl_file, cell_cluster_file, (idents_1, idents_2))
+    inp = _two_populations(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
+                           lambda: _check_perm_args(n_perm, seed))
     n_cols, pops = inp.n_cols, inp.pops
-    if len(pops) < 2:
-        empty = "Population2" if pops and pops[0][0] == "Population1" else "Population1"
-        raise ValueError(f"{empty} ({idents_1 if empty == 'Population1' else idents_2 or 'the rest'}) has no cell in "
-                         "barcode_index.csv")
     strata, left_out, by = None, 0, ""
     if strata_file is not None:
         if not os.path.exists(strata_file):
@@ -999,7 +1013,7 @@ def _perm_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
     return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=n_cols, seg_off=seg_off, n1=n1, n2=n2, outpath=outpath,
                            strata=strata, left_out=left_out, labellings=labellings, perm_bytes=perm_bytes,
                            idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"),
-                           versus=f"{idents_1}_Vs_{idents_2}" if idents_2 is not None else str(idents_1))
+                           versus=_versus(idents_1, idents_2))
 
 
 def _print_strata(su):
@@ -1043,24 +1057,31 @@ def _reprs(v):
     return [repr(x) for x in v.tolist()]
 
 
-def _diff_pa_columns(genes, lines, n1, n2, n_perm):
-    """what diff_pa's lines hold apart from the adjusted p-values, from the per-line integers `lines` and `genes` =
-    (gene_info_str, lines, S(0), gene_n_ge) per tested record of populations with n1 and n2 cells: the text columns
-    gene, pa, pct1, pct2, usage (usage.1, usage.2, delta_usage), n_ge, stat0 and gene_ge per line, the p-values p_val
-    per line and gene_p per record as arrays, and rec_of = the record of every line"""
-    t, a, nz1, nz2, n_ge = (np.concatenate(lines[k]) for k in ("t", "a", "nz1", "nz2", "n_ge"))
-    n_lines = np.array([g[1] for g in genes], dtype=np.int64)
-    rec_of = np.repeat(np.arange(len(genes)), n_lines)
+def _usage_columns(t, a, n_lines):
+    """usage.1, usage.2 and delta_usage of every line as text, from the line's reads t and those of population 1, a,
+    records of n_lines lines each, both populations with reads: a / A, (t - a) / B and the integer a T - t A over the
+    f64 product A B, one division each; and rec_of = the record of every line, A and B per line"""
+    rec_of = np.repeat(np.arange(len(n_lines)), n_lines)
     first = np.concatenate([[0], np.cumsum(n_lines)[:-1]])
     A, T = np.add.reduceat(a, first), np.add.reduceat(t, first)
     Al, Tl = A[rec_of], T[rec_of]
     Bl = Tl - Al
     N = (a * Tl - t * Al).astype(np.float64)
     ab = Al.astype(np.float64) * Bl.astype(np.float64)
+    return [_reprs(v) for v in (a / Al, (t - a) / Bl, N / ab)], rec_of, Al, Bl
+
+
+def _diff_pa_columns(genes, lines, n1, n2, n_perm):
+    """what diff_pa's lines hold apart from the adjusted p-values, from the per-line integers `lines` and `genes` =
+    (gene_info_str, lines, S(0), gene_n_ge) per tested record of populations with n1 and n2 cells: the text columns
+    gene, pa, pct1, pct2, usage (usage.1, usage.2, delta_usage), n_ge, stat0 and gene_ge per line, the p-values p_val
+    per line and gene_p per record as arrays, and rec_of = the record of every line"""
+    t, a, nz1, nz2, n_ge = (np.concatenate(lines[k]) for k in ("t", "a", "nz1", "nz2", "n_ge"))
+    usage, rec_of, _Al, _Bl = _usage_columns(t, a, np.array([g[1] for g in genes], dtype=np.int64))
     gene_ge = np.array([g[3] for g in genes], dtype=np.int64)
     stat0 = np.array([g[2] for g in genes])
     return SimpleNamespace(gene=[genes[g][0] for g in rec_of.tolist()], pa=lines["pa"], pct1=_reprs(nz1 / n1),
-                           pct2=_reprs(nz2 / n2), usage=[_reprs(v) for v in (a / Al, (t - a) / Bl, N / ab)],
+                           pct2=_reprs(nz2 / n2), usage=usage,
                            n_ge=n_ge.tolist(), p_val=(1 + n_ge) / (1 + n_perm), stat0=_reprs(stat0[rec_of]),
                            gene_ge=gene_ge[rec_of].tolist(), gene_p=(1 + gene_ge) / (1 + n_perm), rec_of=rec_of)
 
@@ -1151,10 +1172,34 @@ def _with_span(sel, pos, times):
     return which, off, np.ascontiguousarray(rows[pick]), sums[pick], rowbase, [pos[r] for r in which.tolist()]
 
 
+def _exp_lengths(ctx, seg_off, bat, which, rowbase, times):
+    """the reference's exp_pa_len of every population (_exp_len_rows, one value per segment of seg_off) for the records
+    `which` of a counted batch, from the populations' counts of ALL K labels of those records"""
+    recs, K = bat.recs, bat.K
+    G = len(seg_off) - 1
+    all_rows = np.concatenate([int(rowbase[r]) + np.arange(int(K[r]), dtype=np.int64) for r in which.tolist()])
+    full = np.zeros((len(all_rows), G), dtype=np.int32)
+    full_nz = np.zeros((len(all_rows), G), dtype=np.int32)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_group_sums(ctx.h, G, ptr(seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
+                                              ptr(full, P_i32), ptr(full_nz, P_i32)), "report_group_sums")
+    times["render"] += timer() - t0
+    t0 = timer()
+    out, k0 = [], 0
+    for r in which.tolist():
+        k = int(K[r])
+        counts = np.zeros((G, k + 1), dtype=np.int64)    # slot k: reads of no site, which never weigh
+        counts[:, :k] = full[k0:k0 + k].T
+        k0 += k
+        out.append(_exp_len_rows(k, recs[r].alpha_arr, counts))
+    times["finish"] += timer() - t0
+    return out
+
+
 def _diff_pa_len_batch(su, n_perm, out, ctx, bat, chunk, times):
     """one counted batch: appends (gene, num_pa, A, B, mean_pos.1, mean_pos.2, delta_pos, exp_length.1, exp_length.2,
     n_ge) per tested record to `out`"""
-    recs, K = bat.recs, bat.K
+    recs = bat.recs
     pos = {}                     # record -> positions of its kept rows (f64, finite)
     sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos))
     sel = sel and _with_span(sel, pos, times)
@@ -1170,16 +1215,8 @@ def _diff_pa_len_batch(su, n_perm, out, ctx, bat, chunk, times):
                                           ptr(t, P_i64), ptr(a0, P_i64), ptr(delta0), ptr(n_ge, P_i64)),
         "report_perm_len"))
     _check_row_sums("report_perm_len", t, a0, sums, sums[:, 0])
-    # the two populations' counts of ALL K labels of the tested records, for the reference's exp_pa_len
-    all_rows = np.concatenate([int(rowbase[r]) + np.arange(int(K[r]), dtype=np.int64) for r in which.tolist()])
-    full = np.zeros((len(all_rows), 2), dtype=np.int32)
-    full_nz = np.zeros((len(all_rows), 2), dtype=np.int32)
+    exp_len = _exp_lengths(ctx, su.seg_off, bat, which, rowbase, times)
     t0 = timer()
-    check(ctx.lib.scape_hip_report_group_sums(ctx.h, 2, ptr(su.seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
-                                              ptr(full, P_i32), ptr(full_nz, P_i32)), "report_group_sums")
-    times["render"] += timer() - t0
-    t0 = timer()
-    k0 = 0
     for g, r in enumerate(which.tolist()):
         sl = slice(int(off[g]), int(off[g + 1]))
         a, b = a0[sl], t[sl] - a0[sl]
@@ -1187,11 +1224,7 @@ def _diff_pa_len_batch(su, n_perm, out, ctx, bat, chunk, times):
         if not abs(float(delta0[g]) - d) <= tol[g]:
             raise _lib.ScapeHipError(f"report_perm_len: {recs[r].gene_info_str}: the device's delta {delta0[g]!r} "
                                      f"differs from {d!r}")
-        k = int(K[r])
-        counts = np.zeros((2, k + 1), dtype=np.int64)    # slot k: reads of no site, which never weigh
-        counts[:, :k] = full[k0:k0 + k].T
-        k0 += k
-        e = _exp_len_rows(k, recs[r].alpha_arr, counts)
+        e = exp_len[g]
         out.append((recs[r].gene_info_str, int(off[g + 1] - off[g]), int(a.sum()), int(b.sum()), m1, m2, d,
                     float(e[0]), float(e[1]), int(n_ge[g])))
     times["finish"] += timer() - t0
@@ -2245,19 +2278,42 @@ def _boot_rank(n_def, level_bp):
     return max(1, (n_def + 1) * (10000 - level_bp) // 20000)
 
 
-def _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed, command="boot_pa_len"):
-    """what boot_pa_len and boot_pa_usage (`command`: the name in messages and the output suffix) do before the device
-    is opened: the option checks, then the prerequisites and the populations (_groups_setup's checks of --idents;
-    without a cluster file the one population all_cell), the id -> column table that puts population 0's columns
-    first, the cell of every position, and the output path
-    <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv or all_cell.<gene|utr>.<command>.csv"""
+def _check_boot_args(n_boot, level, seed):
+    """the option checks of the bootstrap commands; returns the level in basis points"""
     if n_boot < 1:
         raise ValueError(f"n_boot must be at least 1, not {n_boot}")
     if n_boot >= 1 << 31:
         raise ValueError(f"n_boot must be below 2^31, not {n_boot}")
     if not 0 <= seed < 1 << 64:
         raise ValueError(f"seed must lie in 0 .. 2^64 - 1, not {seed}")
-    level_bp = _parse_level(level)
+    return _parse_level(level)
+
+
+def _boot_populations(inp, pops, outpath, level, level_bp, seed, command):
+    """the tail of the bootstrap commands' setups, from the populations on: the id -> column table that puts population
+    0's columns first, the cell of every position and the multiplicities' call"""
+    sizes = np.array([len(cols) for _name, cols in pops], dtype=np.int32)
+    n = int(sizes.sum())
+    if n >= MAX_PERM_CELLS:
+        raise ValueError(f"{n} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
+    _table, slot, seg_off, _seg_pop = _samples(pops, 1, inp.n_cols)
+    cell = np.ascontiguousarray(np.concatenate([cols for _name, cols in pops]), dtype=np.int32)
+
+    def labellings(ctx, b_first, b_count):
+        check(ctx.lib.scape_hip_report_boot_mult(ctx.h, n, ptr(cell, P_i32), b_first, b_count, seed), "report_boot_mult")
+    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, n=n, cell=cell,
+                           names=[name for name, _cols in pops], outpath=outpath, level=str(level), level_bp=level_bp,
+                           perm_bytes=n,                 # one byte per tested cell and replicate
+                           labellings=labellings, idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
+
+
+def _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed, command="boot_pa_len"):
+    """what boot_pa_len and boot_pa_usage (`command`: the name in messages and the output suffix) do before the device
+    is opened: the option checks, then the prerequisites and the populations (_groups_setup's checks of --idents;
+    without a cluster file the one population all_cell), the id -> column table that puts population 0's columns
+    first, the cell of every position, and the output path
+    <cluster file stem>.<gene|utr>[.<A>+<B>+...].<command>.csv or all_cell.<gene|utr>.<command>.csv"""
+    level_bp = _check_boot_args(n_boot, level, seed)
     if cell_cluster_file is None:
         if idents:
             raise ValueError("idents needs a cell_cluster_file")
@@ -2273,19 +2329,20 @@ def _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, lev
         if not 1 <= len(pops) <= MAX_GROUPS:
             raise ValueError(f"{len(pops)} populations: {command} takes 1 to {MAX_GROUPS}")
         outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, None, None) + tag + f".{command}.csv"
-    sizes = np.array([len(cols) for _name, cols in pops], dtype=np.int32)
-    n = int(sizes.sum())
-    if n >= MAX_PERM_CELLS:
-        raise ValueError(f"{n} tested cells: {command} takes fewer than {MAX_PERM_CELLS}")
-    _table, slot, seg_off, _seg_pop = _samples(pops, 1, inp.n_cols)
-    cell = np.ascontiguousarray(np.concatenate([cols for _name, cols in pops]), dtype=np.int32)
+    return _boot_populations(inp, pops, outpath, level, level_bp, seed, command)
 
-    def labellings(ctx, b_first, b_count):
-        check(ctx.lib.scape_hip_report_boot_mult(ctx.h, n, ptr(cell, P_i32), b_first, b_count, seed), "report_boot_mult")
-    return SimpleNamespace(res_pkl=inp.res_pkl, n_cols=inp.n_cols, seg_off=seg_off, sizes=sizes, n=n, cell=cell,
-                           names=[name for name, _cols in pops], outpath=outpath, level=str(level), level_bp=level_bp,
-                           perm_bytes=n,                 # one byte per tested cell and replicate
-                           labellings=labellings, idmap=_IdMap(inp.col_ids, slot, "barcode_index.csv"))
+
+def _boot_diff_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed, command):
+    """what boot_pa_len_diff and boot_pa_usage_diff do before the device is opened: diff_pa's checks of the idents and
+    its two populations (_two_populations), _boot_setup's option checks between them, then _boot_setup's tail on
+    population 1's columns followed by population 2's; the output path is
+    <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.<command>.csv"""
+    inp = _two_populations(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
+                           lambda: _check_boot_args(n_boot, level, seed))
+    outpath = _out_stem(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2) + f".{command}.csv"
+    su = _boot_populations(inp, inp.pops, outpath, level, _parse_level(level), seed, command)
+    su.versus = _versus(idents_1, idents_2)
+    return su
 
 
 def _boot_columns(lo, hi, x_min, s, alpha_arr, exp_length):
@@ -2303,10 +2360,36 @@ def _boot_columns(lo, hi, x_min, s, alpha_arr, exp_length):
     return [repr(y) for y in ys] + [repr(1.0 + 9.0 * (y - a0) / width) for y in ys]
 
 
+def _check_boot_reads(recs, which, off, sums):
+    """a record of BOOT_MAX_READS reads or more in the tested cells is a ValueError (sums: per kept row and population)"""
+    T = np.add.reduceat(sums.sum(axis=1), off[:-1])
+    for g, r in enumerate(which.tolist()):
+        if int(T[g]) >= BOOT_MAX_READS:
+            raise ValueError(f"{recs[r].gene_info_str}: 2^27 or more reads in the tested cells")
+
+
+def _boot_positions(xs):
+    """the integer positions q of the kept rows of the records with positions xs, one array, and the scale s per record:
+    q_i = (x_i - min x) 2^s rounded (_quantise_positions)"""
+    q = np.ascontiguousarray(np.concatenate([_quantise_positions(x) for x in xs]))
+    return q, [LEN_GROUPS_Q_BITS - math.frexp(float(x.max() - x.min()))[1] for x in xs]
+
+
+def _boot_quantiles(ctx, su, n_series, times):
+    """(lo, hi, D) per series of the record set on the device, at the run's level"""
+    lo, hi = np.zeros(n_series, np.float64), np.zeros(n_series, np.float64)
+    n_def = np.zeros(n_series, np.int64)
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_boot_quantiles(ctx.h, su.level_bp, ptr(lo), ptr(hi), ptr(n_def, P_i64)),
+          "report_boot_quantiles")
+    times["render"] += timer() - t0
+    return lo, hi, n_def
+
+
 def _boot_pa_len_batch(su, n_boot, out, ctx, bat, chunk, times):
     """one counted batch: appends the file's lines (lists of fields) of its reported records to `out` and adds their
     number to su.n_records"""
-    recs, K, G = bat.recs, bat.K, len(su.sizes)
+    recs, G = bat.recs, len(su.sizes)
     pos = {}                     # record -> positions of its kept rows (f64, finite)
     sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos), min_pops=1)
     sel = sel and _with_span(sel, pos, times)
@@ -2314,41 +2397,22 @@ def _boot_pa_len_batch(su, n_boot, out, ctx, bat, chunk, times):
         return
     which, off, rows, sums, rowbase, xs = sel
     t0 = timer()
-    T = np.add.reduceat(sums.sum(axis=1), off[:-1])
-    for g, r in enumerate(which.tolist()):
-        if int(T[g]) >= BOOT_MAX_READS:
-            raise ValueError(f"{recs[r].gene_info_str}: 2^27 or more reads in the tested cells")
-    q = np.ascontiguousarray(np.concatenate([_quantise_positions(x) for x in xs]))
-    scale = [LEN_GROUPS_Q_BITS - math.frexp(float(x.max() - x.min()))[1] for x in xs]
+    _check_boot_reads(recs, which, off, sums)
+    q, scale = _boot_positions(xs)
     times["finish"] += timer() - t0
     t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
     _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
         ctx.lib.scape_hip_report_boot_len(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G, ptr(su.seg_off, P_i32),
                                           ptr(q, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)), "report_boot_len"))
     _check_row_sums("report_boot_len", t, a0, sums, sums)
-    lo, hi = np.zeros((len(which), G), np.float64), np.zeros((len(which), G), np.float64)
-    n_def = np.zeros((len(which), G), np.int64)
-    # the populations' counts of ALL K labels of the reported records, for the reference's exp_pa_len
-    all_rows = np.concatenate([int(rowbase[r]) + np.arange(int(K[r]), dtype=np.int64) for r in which.tolist()])
-    full = np.zeros((len(all_rows), G), dtype=np.int32)
-    full_nz = np.zeros((len(all_rows), G), dtype=np.int32)
+    lo, hi, n_def = (v.reshape(len(which), G) for v in _boot_quantiles(ctx, su, len(which) * G, times))
+    exp_len = _exp_lengths(ctx, su.seg_off, bat, which, rowbase, times)
     t0 = timer()
-    check(ctx.lib.scape_hip_report_boot_quantiles(ctx.h, su.level_bp, ptr(lo), ptr(hi), ptr(n_def, P_i64)),
-          "report_boot_quantiles")
-    check(ctx.lib.scape_hip_report_group_sums(ctx.h, G, ptr(su.seg_off, P_i32), len(all_rows), ptr(all_rows, P_i64),
-                                              ptr(full, P_i32), ptr(full_nz, P_i32)), "report_group_sums")
-    times["render"] += timer() - t0
-    t0 = timer()
-    k0 = 0
     for g, r in enumerate(which.tolist()):
         sl = slice(int(off[g]), int(off[g + 1]))
         a = a0[sl]
         _mean, mean_g, _delta = _mean_positions_groups(xs[g], a.tolist())
-        k = int(K[r])
-        counts = np.zeros((G, k + 1), dtype=np.int64)    # slot k: reads of no site, which never weigh
-        counts[:, :k] = full[k0:k0 + k].T
-        k0 += k
-        e = _exp_len_rows(k, recs[r].alpha_arr, counts)
+        e = exp_len[g]
         A = a.sum(axis=0)
         for p in range(G):
             if A[p] == 0:
@@ -2415,10 +2479,7 @@ def _boot_pa_usage_batch(su, n_boot, out, ctx, bat, chunk, times):
         return
     which, off, rows, _nz, sums, rowbase = sel
     t0 = timer()
-    T = np.add.reduceat(sums.sum(axis=1), off[:-1])
-    for g, r in enumerate(which.tolist()):
-        if int(T[g]) >= BOOT_MAX_READS:
-            raise ValueError(f"{recs[r].gene_info_str}: 2^27 or more reads in the tested cells")
+    _check_boot_reads(recs, which, off, sums)
     times["finish"] += timer() - t0
     t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
     _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
@@ -2426,12 +2487,7 @@ def _boot_pa_usage_batch(su, n_boot, out, ctx, bat, chunk, times):
                                             ptr(su.seg_off, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)),
         "report_boot_usage"))
     _check_row_sums("report_boot_usage", t, a0, sums, sums)
-    lo, hi = np.zeros((len(rows), G), np.float64), np.zeros((len(rows), G), np.float64)
-    n_def = np.zeros((len(rows), G), np.int64)
-    t0 = timer()
-    check(ctx.lib.scape_hip_report_boot_quantiles(ctx.h, su.level_bp, ptr(lo), ptr(hi), ptr(n_def, P_i64)),
-          "report_boot_quantiles")
-    times["render"] += timer() - t0
+    lo, hi, n_def = (v.reshape(len(rows), G) for v in _boot_quantiles(ctx, su, len(rows) * G, times))
     t0 = timer()
     for g, r in enumerate(which.tolist()):
         i0, i1 = int(off[g]), int(off[g + 1])
@@ -2472,6 +2528,150 @@ def _boot_pa_usage(output_dir: str, res_pkl_file: str, cell_cluster_file=None, i
     print(f"Finish {n_boot} bootstrap replicates of {su.n} cells in {len(su.sizes)} populations for {su.n_sites} pA sites "
           f"of {su.n_records} reported records")
     print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    return su.outpath
+
+
+# ---------------------------------------------------------------- boot_pa_len_diff, boot_pa_usage_diff
+# The effect size beside diff_pa_len's and diff_pa's p-values, with its uncertainty: percentile intervals of population 1
+# minus population 2.  They cannot be read off the two populations' own intervals, whose replicate values are correlated
+# within a replicate.  Populations and tested columns are diff_pa's (_two_populations; population 1's matrix columns
+# first, ascending, then population 2's; without --idents_2 population 2 is every other cell that has a cluster), options,
+# cell[j] and m(b, c) are boot_pa_len's: replicate b is the same resampled data set in all four bootstrap files.
+# boot_pa_len_diff reports diff_pa_len's tested records (two kept rows or more, span > 0, reads in both populations; q_i
+# and s as in boot_pa_len), one series per record:
+#     d(b) = (double)Q_1(b) / (double)A_1(b) - (double)Q_2(b) / (double)A_2(b);  +infinity when A_1(b) = 0 or A_2(b) = 0
+# two IEEE divisions and one subtraction; D, k, lo, hi by boot_pa_len's rule over the D defined values.  The eleven columns
+# it shares with diff_pa_len are that command's text.  delta_pos_lo / _hi = ldexp(lo / hi, -s) (exact, min x cancels),
+# delta_exp_length_lo / _hi = 9.0 * y / (a[-1] - a[0]) with y that end of delta_pos (empty when either exp_length is nan or
+# the width is not finite and positive, _boot_columns' rule), n_empty = n_boot - D.  delta_pos > 0: population 1's 3'UTRs
+# are longer.  boot_pa_usage_diff reports diff_pa's records and lines (two kept rows or more, reads in both populations,
+# one line per kept row), one series per kept row:
+#     d_i(b) = (double)a_i1(b) / (double)A_1(b) - (double)a_i2(b) / (double)A_2(b);  +infinity when either A is 0
+# with pa_info, usage.1, usage.2 and delta_usage diff_pa's text (_usage_columns) and delta_usage_lo / _hi = repr of lo / hi.
+# The interval fields are empty when D = 0.  A replicate's difference is three correctly rounded operations, not the exact
+# rational rounded once as delta_pos and delta_usage are: the ends may differ from such a value in the last place, and
+# they are the same bits as the difference of boot_pa_len's and boot_pa_usage's replicate values.
+BOOT_PA_LEN_DIFF_HEADER = DIFF_PA_LEN_HEADER[:8] + ["delta_pos_lo", "delta_pos_hi"] + DIFF_PA_LEN_HEADER[8:11] + [
+    "delta_exp_length_lo", "delta_exp_length_hi", "n_empty", "n_boot", "level"]
+BOOT_PA_USAGE_DIFF_HEADER = ["gene", "pa_info", "versus", "num_pa", "reads.1", "reads.2", "gene_reads.1", "gene_reads.2",
+                             "usage.1", "usage.2", "delta_usage", "delta_usage_lo", "delta_usage_hi", "n_empty", "n_boot",
+                             "level"]
+
+
+def _boot_pa_len_diff_batch(su, n_boot, out, ctx, bat, chunk, times):
+    """one counted batch: appends the file's lines (lists of fields) of its reported records to `out`"""
+    recs = bat.recs
+    pos = {}                     # record -> positions of its kept rows (f64, finite)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos))
+    sel = sel and _with_span(sel, pos, times)
+    if sel is None:
+        return
+    which, off, rows, sums, rowbase, xs = sel
+    t0 = timer()
+    _check_boot_reads(recs, which, off, sums)
+    q, scale = _boot_positions(xs)
+    times["finish"] += timer() - t0
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), 2), np.int64)
+    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
+        ctx.lib.scape_hip_report_boot_len_diff(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), 2,
+                                               ptr(su.seg_off, P_i32), ptr(q, P_i32), n_boot, ptr(t, P_i64),
+                                               ptr(a0, P_i64)), "report_boot_len_diff"))
+    _check_row_sums("report_boot_len_diff", t, a0, sums, sums)
+    lo, hi, n_def = _boot_quantiles(ctx, su, len(which), times)
+    exp_len = _exp_lengths(ctx, su.seg_off, bat, which, rowbase, times)
+    t0 = timer()
+    for g, r in enumerate(which.tolist()):
+        sl = slice(int(off[g]), int(off[g + 1]))
+        a, b = a0[sl, 0], a0[sl, 1]
+        m1, m2, d = _mean_positions(xs[g], a.tolist(), b.tolist())
+        e1, e2 = float(exp_len[g][0]), float(exp_len[g][1])
+        D = int(n_def[g])
+        ends = [math.ldexp(float(v), -scale[g]) for v in (lo[g], hi[g])] if D else []
+        alpha = np.asarray(recs[r].alpha_arr, dtype=np.float64)
+        width = float(alpha[-1]) - float(alpha[0])
+        scaled = not (math.isnan(e1) or math.isnan(e2)) and math.isfinite(width) and width > 0
+        out.append([recs[r].gene_info_str, su.versus, int(off[g + 1] - off[g]), int(a.sum()), int(b.sum()), repr(m1),
+                    repr(m2), repr(d)] + ([repr(y) for y in ends] or ["", ""]) + [repr(e1), repr(e2), repr(e1 - e2)] +
+                   ([repr(9.0 * y / width) for y in ends] if scaled and D else ["", ""]) + [n_boot - D, n_boot, su.level])
+    times["finish"] += timer() - t0
+
+
+def _boot_pa_usage_diff_batch(su, n_boot, out, ctx, bat, chunk, times):
+    """one counted batch: appends the file's lines (lists of fields), one per kept row of its reported records, to `out`
+    and adds the number of those records to su.n_records"""
+    recs = bat.recs
+    sel = _perm_rows(ctx, bat, su.seg_off, times)
+    if sel is None:
+        return
+    which, off, rows, _nz, sums, rowbase = sel
+    t0 = timer()
+    _check_boot_reads(recs, which, off, sums)
+    times["finish"] += timer() - t0
+    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), 2), np.int64)
+    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
+        ctx.lib.scape_hip_report_boot_usage_diff(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), 2,
+                                                 ptr(su.seg_off, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)),
+        "report_boot_usage_diff"))
+    _check_row_sums("report_boot_usage_diff", t, a0, sums, sums)
+    lo, hi, n_def = _boot_quantiles(ctx, su, len(rows), times)
+    t0 = timer()
+    n_lines = np.diff(off)
+    usage, rec_of, A, B = _usage_columns(t, np.ascontiguousarray(a0[:, 0]), n_lines)
+    pa = [p for g, r in enumerate(which.tolist()) for p in _pa_info(recs[r], rows[off[g]:off[g + 1]] - int(rowbase[r]))]
+    for i, g in enumerate(rec_of.tolist()):
+        D = int(n_def[i])
+        ends = [repr(float(lo[i])), repr(float(hi[i]))] if D else ["", ""]
+        out.append([recs[which[g]].gene_info_str, pa[i], su.versus, int(n_lines[g]), int(a0[i, 0]), int(a0[i, 1]),
+                    int(A[i]), int(B[i]), usage[0][i], usage[1][i], usage[2][i]] + ends + [n_boot - D, n_boot, su.level])
+    su.n_records += len(which)
+    times["finish"] += timer() - t0
+
+
+def _boot_diff(batch_of, header, record_bytes, command, output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
+               n_boot, level, seed, device):
+    """the run of boot_pa_len_diff and boot_pa_usage_diff: the setup, batch_of's batches through _perm_run with
+    record_bytes device bytes of replicate values per record (a number or a function of the record), and the file;
+    returns (setup with the wall seconds, lines)"""
+    su = _boot_diff_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed, command)
+    su.n_records = 0
+    out = []
+
+    def write(w):
+        w.writerow(header)
+        w.writerows(out)
+
+    su.wall = _perm_run(su, n_boot, device, functools.partial(batch_of, su, n_boot, out), write,
+                        record_bytes=record_bytes)
+    return su, out
+
+
+def _boot_pa_len_diff(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
+                      n_boot: int = 9999, level="95", seed: int = 1, device=None):
+    """percentile bootstrap intervals of the difference of the mean pA position, and of exp_length, between the cells of
+    cluster idents_1 and those of idents_2 (None: every other cell that has a cluster), by resampling the cells with
+    boot_pa_len's replicates; writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.boot_pa_len_diff.csv in output_dir,
+    one line per record diff_pa_len tests, and returns its path"""
+    # per record one series of replicate values, 8 bytes each
+    su, out = _boot_diff(_boot_pa_len_diff_batch, BOOT_PA_LEN_DIFF_HEADER, n_boot * 8, "boot_pa_len_diff", output_dir,
+                         res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed, device)
+    print(f"Finish {n_boot} bootstrap replicates of {su.sizes[0]} + {su.sizes[1]} cells for {len(out)} reported records")
+    print(f"Finish {su.res_pkl} in {su.wall / 60} min.")
+    return su.outpath
+
+
+def _boot_pa_usage_diff(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
+                        n_boot: int = 9999, level="95", seed: int = 1, device=None):
+    """percentile bootstrap intervals of the difference of the usage of every pA site between the cells of cluster
+    idents_1 and those of idents_2 (None: every other cell that has a cluster), by resampling the cells with
+    boot_pa_len's replicates; writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.boot_pa_usage_diff.csv in
+    output_dir, one line per line of diff_pa, and returns its path"""
+    # per label of a record (at most that many kept rows) one series of replicate values, 8 bytes each
+    su, out = _boot_diff(_boot_pa_usage_diff_batch, BOOT_PA_USAGE_DIFF_HEADER, lambda p: int(p.K) * n_boot * 8,
+                         "boot_pa_usage_diff", output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot,
+                         level, seed, device)
+    print(f"Finish {n_boot} bootstrap replicates of {su.sizes[0]} + {su.sizes[1]} cells for {len(out)} pA sites of "
+          f"{su.n_records} reported records")
+    print(f"Finish {su.res_pkl} in {su.wall / 60} min.")
     return su.outpath
 
 
@@ -2688,12 +2888,14 @@ def _options(*options):
     return decorate
 
 
-# diff_pa and diff_pa_len (--seed's help differs)
-_perm_options = _options(
-    *_OUTPUT_OPTIONS, _CLUSTER_FILE_OPTION,
+# the two populations of diff_pa, diff_pa_len, boot_pa_len_diff and boot_pa_usage_diff
+_TWO_IDENTS_OPTIONS = (
     click.option('--idents_1', type=str, required=True, help='The cluster of population 1.'),
     click.option('--idents_2', type=str, default=None,
-                 help='The cluster of population 2. Default: every other cell that has a cluster.'),
+                 help='The cluster of population 2. Default: every other cell that has a cluster.'))
+# diff_pa and diff_pa_len (--seed's help differs)
+_perm_options = _options(
+    *_OUTPUT_OPTIONS, _CLUSTER_FILE_OPTION, *_TWO_IDENTS_OPTIONS,
     click.option('--n_perm', type=int, default=9999, show_default=True,
                  help='Permutations of the cell labels; the smallest p-value is 1 / (1 + n_perm).'),
     click.option('--strata_file', type=str, default=None,
@@ -2853,6 +3055,13 @@ def diff_pa_len_trend(output_dir: str, res_pkl_file: str, cell_score_file: str, 
     _diff_pa_len_trend(output_dir, res_pkl_file, cell_score_file, rank, n_perm, seed)
 
 
+# the replicates and the level of the four bootstrap commands
+_BOOT_REPLICATE_OPTIONS = (
+    click.option('--n_boot', type=int, default=9999, show_default=True,
+                 help='Bootstrap replicates of the cells.'),
+    click.option('--level', type=str, default="95", show_default=True,
+                 help='Level of the percentile intervals in percent, above 0 and below 100, with at most two '
+                      'decimals.'))
 # boot_pa_len and boot_pa_usage
 _boot_options = _options(
     *_OUTPUT_OPTIONS,
@@ -2864,14 +3073,18 @@ _boot_options = _options(
                  help='A cluster to report; give the option once per cluster (1 to 64), the order is kept. Needs '
                       '--cell_cluster_file. Default: every cluster of the cell_cluster_file (at most 64), in order '
                       'of first appearance.'),
-    click.option('--n_boot', type=int, default=9999, show_default=True,
-                 help='Bootstrap replicates of the cells.'),
-    click.option('--level', type=str, default="95", show_default=True,
-                 help='Level of the percentile intervals in percent, above 0 and below 100, with at most two '
-                      'decimals.'),
+    *_BOOT_REPLICATE_OPTIONS,
     click.option('--seed', type=int, default=1, show_default=True,
                  help='Seed of the replicates, 0 .. 2^64 - 1. The same seed resamples the same cells whatever the '
                       'cluster file and the idents.'))
+
+
+# boot_pa_len_diff and boot_pa_usage_diff: diff_pa's populations, the bootstrap's other options
+_boot_diff_options = _options(
+    *_OUTPUT_OPTIONS, _CLUSTER_FILE_OPTION, *_TWO_IDENTS_OPTIONS, *_BOOT_REPLICATE_OPTIONS,
+    click.option('--seed', type=int, default=1, show_default=True,
+                 help='Seed of the replicates, 0 .. 2^64 - 1. The same seed resamples the same cells as in boot_pa_len '
+                      'and boot_pa_usage.'))
 
 
 @click.command(name="boot_pa_len")
@@ -2894,3 +3107,23 @@ def boot_pa_usage(output_dir: str, res_pkl_file: str, cell_cluster_file, idents,
     if idents and cell_cluster_file is None:
         raise click.UsageError("--idents needs --cell_cluster_file")
     _boot_pa_usage(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed)
+
+
+@click.command(name="boot_pa_len_diff")
+@_boot_diff_options
+def boot_pa_len_diff(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_boot: int,
+                     level: str, seed: int):
+    """How much longer one population's 3'UTRs are than the other's, and how well that is known: per gene diff_pa_len
+    tests, the difference of the mean pA position and of the expected pA length (population 1 minus population 2) with
+    a percentile bootstrap interval, by resampling the cells (the replicates of boot_pa_len)."""
+    _boot_pa_len_diff(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed)
+
+
+@click.command(name="boot_pa_usage_diff")
+@_boot_diff_options
+def boot_pa_usage_diff(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2, n_boot: int,
+                       level: str, seed: int):
+    """How much more one population uses a pA site than the other, and how well that is known: per pA site diff_pa
+    tests, delta_usage (population 1 minus population 2) with a percentile bootstrap interval, by resampling the cells
+    (the replicates of boot_pa_len)."""
+    _boot_pa_usage_diff(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed)

@@ -31,12 +31,14 @@ def main():
         m = re.search(r"remark:\s+(\w[\w \[\]/]*): (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
-    print(f"{'kernel':44s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'LDS':>7s} {'occ':>4s}")
+    print(f"{'kernel':44s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'scratch':>7s} {'LDS':>7s} "
+          f"{'occ':>4s}")
     for r in rows:
         if pats and not any(p in r["name"] for p in pats):
             continue
         print(f"{r['name'][:44]:44s} {r.get('VGPRs', 0):5d} {r.get('AGPRs', 0):5d} {r.get('TotalSGPRs', 0):5d} "
-              f"{r.get('VGPRs Spill', 0):6d} {r.get('LDS Size [bytes/block]', 0):7d} "
+              f"{r.get('VGPRs Spill', 0):6d} {r.get('ScratchSize [bytes/lane]', 0):7d} "
+              f"{r.get('LDS Size [bytes/block]', 0):7d} "
               f"{r.get('Occupancy [waves/SIMD]', 0):4d}")
 
 
