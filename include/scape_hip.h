@@ -589,7 +589,8 @@ int scape_hip_report_boot_usage(scape_hip_ctx *ctx, int32_t n_rec, const int64_t
    record (len) or per kept row (usage).  (ABI 4 gains these two entry points; nothing that was there changes.)  The
    arguments, t_out, a0_out[i * 2 + g], the checks, the T < 2^27 refusal and the chunk protocol are those of
    scape_hip_report_boot_len and scape_hip_report_boot_usage, except that n_groups must be 2: any other value is refused.
-   With A_g, Q_g, a_ig of those two entry points the device forms, in one walk of the nonzeros for both populations,
+   With A_g, Q_g, a_ig of those two entry points the device forms, in those entry points' kernel bodies with both
+   populations in one series (every nonzero still read once, or twice for a usage record of more than 8 kept rows),
      d(b)   = (double)Q_0(b) / (double)A_0(b) - (double)Q_1(b) / (double)A_1(b)          (boot_len_diff)
      d_i(b) = (double)a_i0(b) / (double)A_0(b) - (double)a_i1(b) / (double)A_1(b)        (boot_usage_diff)
    two IEEE divisions and one IEEE subtraction, contraction off: bit for bit v_0(b) - v_1(b) and u_i0(b) - u_i1(b) of the

@@ -55,8 +55,9 @@
 //                   per (record, population, replicate) the mean pA position from two exact integer sums, or per (kept
 //                   row, population, replicate) the row's share of the population's reads from two; and per series the
 //                   two order statistics of a percentile interval by a radix select over a sign-aware key
-//                   (rep_boot_values: the one frame of the four kinds of record set); the _diff kernels form both
-//                   populations' sums in one walk and store the one difference of the two quotients
+//                   (rep_boot_values: the one frame of the four kinds of record set).  The value kernels are wrappers of
+//                   two bodies, rep_boot_len_body and rep_boot_usage_body, for series of one population or of two: the
+//                   _diff kernels form both populations' sums and store the one difference of the two quotients
 // On the host a builder leaves a RepLabellings in ReportState (what it built, for the checks of the tests and of the
 // `_get` entry points).  A test fills a RepPermCall, the one frame of its call: rep_perm_prepare checks and compacts from
 // it, rep_perm_launch_classes launches a two-population test per LDS class of records, rep_perm_count brings the
@@ -2429,10 +2430,12 @@ int scape_hip_report_perm_len_trend(scape_hip_ctx *c, int32_t n_rec, const int64
 // is the inverse map of the selected key.  Over non-negative values the keys order as the bit patterns do, so boot_len's
 // and boot_usage's record sets go through the same select and get the bits they always got.  -0.0 (whose key lies below
 // that of +0.0) cannot occur: a quotient of non-negative integers is never -0, and x - x is +0.0 under round-to-nearest.
-//   k_rep_boot_len_diff    k_rep_boot_len's workgroup and lanes; A_1, Q_1, A_2, Q_2 in registers, one walk of every kept
-//                          row's nonzeros, segment 0 into population 1's sums and segment 1 into population 2's
-//   k_rep_boot_usage_diff  k_rep_boot_usage's two shapes: up to 8 kept rows, one walk per population with a_i1 and a_i2
-//                          in registers; more, A_1 and A_2 by a first walk and then row by row
+//   k_rep_boot_len_diff    k_rep_boot_len's body with both populations in one series; A_1, Q_1, A_2, Q_2 in registers,
+//                          one walk of every kept row's nonzeros, segment 0 into population 1's sums and segment 1 into
+//                          population 2's
+//   k_rep_boot_usage_diff  k_rep_boot_usage's body likewise, in its two shapes: up to 8 kept rows, one walk per
+//                          population with a_i1 and a_i2 in registers; more, A_1 and A_2 by a first walk and then row by
+//                          row
 #define REP_BOOT_READS_BITS 27         // T < 2^27
 #define REP_BOOT_MULT_POS 64           // positions a workgroup of k_rep_boot_mult takes per step
 #define REP_BOOT_USAGE_REG_ROWS 8      // kept rows of a record up to which k_rep_boot_usage holds every a_ig in a register
@@ -2465,182 +2468,151 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_mult(int32_t n, const 
     }
 }
 
-// workgroup = (record blockIdx.x / n_tiles, tile of 256 replicates of the chunk), one lane per replicate; sg[i] = the
-// G + 1 segment starts of kept row i among the nonzeros.  vals[(r * n_groups + g) * n_boot + col0 + replicate of the
-// chunk] = v_g; a lane beyond the chunk walks the last replicate's bytes and stores nothing
+// The value kernels.  workgroup = (record blockIdx.x / n_tiles, tile of 256 replicates of the chunk), one lane per
+// replicate; a lane beyond the chunk walks the last replicate's bytes and stores nothing.  sg[i] = the n_groups + 1 segment
+// starts of kept row i among the nonzeros.  A series covers NB populations: one (its value is that population's quotient)
+// or the two of a difference (population 0's quotient minus population 1's); its values lie at
+// vals[series * n_boot + col0 + replicate of the chunk], stored along the replicates
+struct RepBootLane {
+    int r, p;                    // record; replicate of the chunk
+    bool valid;
+    const uint8_t *mb;           // the replicate's multiplicity of position 0
+    int64_t row0, row1;          // the record's kept rows
+};
+
+__device__ __forceinline__ RepBootLane rep_boot_lane(const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles,
+                                                     const int64_t *__restrict__ roff) {
+    RepBootLane l;
+    l.r = blockIdx.x / n_tiles;
+    l.p = (blockIdx.x % n_tiles) * REP_THREADS + threadIdx.x;
+    l.valid = l.p < b_count;
+    l.mb = mult + (l.valid ? l.p : b_count - 1);
+    l.row0 = roff[l.r], l.row1 = roff[l.r + 1];
+    return l;
+}
+
+// a_ig: the sum of m x c over the nonzeros of kept row i in segment g (m <= 15 and the row's reads stay below 2^27)
+__device__ __forceinline__ int rep_boot_row_sum(const uint2 *__restrict__ nz, const int64_t *__restrict__ sg, int n_groups,
+                                                int64_t i, int g, const uint8_t *__restrict__ mb, int32_t b_count) {
+    const int64_t *si = sg + i * (n_groups + 1);
+    int a = 0;
+    rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { a += m * c; });
+    return a;
+}
+
+// a series' value from the num / den of its NB populations
+template <int NB, typename T>
+__device__ __forceinline__ double rep_boot_value(const T *num, const T *den) {
+#pragma clang fp contract(off)
+    if (NB == 1) return den[0] > 0 ? (double)num[0] / (double)den[0] : __builtin_huge_val();
+    return den[0] > 0 && den[NB - 1] > 0 ? (double)num[0] / (double)den[0] - (double)num[NB - 1] / (double)den[NB - 1]
+                                         : __builtin_huge_val();
+}
+
+// v_g = Q_g / A_g: one series per record and NB populations.  The walk takes the populations NB at a time, per kept row
+// the row's nonzeros of those segments (k_rep_pair_segidx found where they start): A and Q live in registers, every
+// nonzero is read once, and there is no LDS, no atomic, no barrier and no slice
+template <int NB>
+__device__ __forceinline__ void rep_boot_len_body(const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles,
+                                                  int32_t n_groups, const int64_t *__restrict__ roff,
+                                                  const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
+                                                  const int32_t *__restrict__ q, int64_t n_boot, int64_t col0,
+                                                  double *__restrict__ vals) {
+    const RepBootLane l = rep_boot_lane(mult, b_count, n_tiles, roff);
+    for (int g0 = 0; g0 < n_groups; g0 += NB) {
+        long long A[NB] = {}, Q[NB] = {};
+        for (int64_t i = l.row0; i < l.row1; ++i) {
+            int a[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) a[b] = rep_boot_row_sum(nz, sg, n_groups, i, g0 + b, l.mb, b_count);
+            const long long qi = q[i];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) A[b] += a[b], Q[b] += a[b] * qi;
+        }
+        if (l.valid)
+            vals[((int64_t)l.r * (n_groups / NB) + g0 / NB) * n_boot + col0 + l.p] = rep_boot_value<NB>(Q, A);
+    }
+}
+
+// u_ig = a_ig / A_g: one series per kept row i of the call (not the record) and NB populations.  15 T < 2^31: both sums
+// are 32-bit.  A record of at most REP_BOOT_USAGE_REG_ROWS kept rows takes one walk per population, the a_ig of its rows
+// in registers until A_g is known (the branch is uniform over the workgroup and taken once, in front of the
+// populations); a longer one takes two: A_g over all its rows, then a_ig row by row, which finds the multiplicity bytes
+// of the first walk in cache.  Measured at records of 2..8 rows: 32.9 ms with the one walk, 50.3 ms with two walks for
+// every record.  No LDS, atomic or barrier
+template <int NB>
+__device__ __forceinline__ void rep_boot_usage_body(const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles,
+                                                    int32_t n_groups, const int64_t *__restrict__ roff,
+                                                    const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
+                                                    const int32_t *__restrict__, int64_t n_boot, int64_t col0,
+                                                    double *__restrict__ vals) {
+    const RepBootLane l = rep_boot_lane(mult, b_count, n_tiles, roff);
+    const int n_series = n_groups / NB;          // per kept row
+    if (l.row1 - l.row0 <= REP_BOOT_USAGE_REG_ROWS) {
+        for (int g0 = 0; g0 < n_groups; g0 += NB) {
+            int a[REP_BOOT_USAGE_REG_ROWS][NB], A[NB] = {};
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k) {
+                    a[k][b] = 0;
+                    if (l.row0 + k < l.row1) {
+                        a[k][b] = rep_boot_row_sum(nz, sg, n_groups, l.row0 + k, g0 + b, l.mb, b_count);
+                        A[b] += a[k][b];
+                    }
+                }
+#pragma unroll
+            for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k)
+                if (l.row0 + k < l.row1 && l.valid)
+                    vals[((l.row0 + k) * n_series + g0 / NB) * n_boot + col0 + l.p] = rep_boot_value<NB>(a[k], A);
+        }
+        return;
+    }
+    for (int g0 = 0; g0 < n_groups; g0 += NB) {
+        int A[NB] = {};
+        for (int64_t i = l.row0; i < l.row1; ++i)
+#pragma unroll
+            for (int b = 0; b < NB; ++b) A[b] += rep_boot_row_sum(nz, sg, n_groups, i, g0 + b, l.mb, b_count);
+        for (int64_t i = l.row0; i < l.row1; ++i) {
+            int a[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) a[b] = rep_boot_row_sum(nz, sg, n_groups, i, g0 + b, l.mb, b_count);
+            if (l.valid) vals[(i * n_series + g0 / NB) * n_boot + col0 + l.p] = rep_boot_value<NB>(a, A);
+        }
+    }
+}
+
+// the four kernels, under the names the kernel traces know, on one parameter list: the differences get n_groups = 2,
+// the usage kernels no q.  The usage kernels' bound asks for 8 waves per SIMD: as a body behind a wrapper the register
+// path takes 106 scalar registers and 7 waves without it (the same text as a kernel of its own: 100 and 8), 78 and 8
+// with it, and with it the two kernels are 7 to 19 % faster than before the fold in both paths; the length kernels have
+// 8 waves unasked and were 1.1 to 1.5 % slower under the bound (profiles/boot_one_body_timing.txt)
 __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_len(
     const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, int32_t n_groups,
     const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
     const int32_t *__restrict__ q, int64_t n_boot, int64_t col0, double *__restrict__ vals) {
-#pragma clang fp contract(off)
-    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    const int p = tile * REP_THREADS + threadIdx.x;
-    const bool valid = p < b_count;
-    const uint8_t *mb = mult + (valid ? p : b_count - 1);
-    const int64_t row0 = roff[r], row1 = roff[r + 1];
-    const int stride = n_groups + 1;
-    for (int g = 0; g < n_groups; ++g) {
-        long long A = 0, Q = 0;
-        for (int64_t i = row0; i < row1; ++i) {
-            const int64_t *si = sg + i * stride;
-            int a = 0;                           // m <= 15 and the row's reads stay below 2^27
-            rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { a += m * c; });
-            A += a;
-            Q += (long long)a * q[i];
-        }
-        if (valid)
-            vals[((int64_t)r * n_groups + g) * n_boot + col0 + p] =
-                A > 0 ? (double)Q / (double)A : __builtin_huge_val();
-    }
+    rep_boot_len_body<1>(mult, b_count, n_tiles, n_groups, roff, sg, nz, q, n_boot, col0, vals);
 }
 
-// boot_pa_usage: workgroup and lanes as k_rep_boot_len; series = kept row i of the call (not the record) x population.
-// vals[(i * n_groups + g) * n_boot + col0 + replicate of the chunk] = (double)a_ig / (double)A_g, stored along the
-// replicates.  15 T < 2^31: both sums are 32-bit.  A record of at most REP_BOOT_USAGE_REG_ROWS kept rows takes one walk
-// per population, the a_ig of its rows in registers until A_g is known (the branch is uniform over the workgroup);
-// a longer one takes two: A_g over all its rows, then a_ig row by row, which finds the multiplicity bytes of the first
-// walk in cache.  Measured at records of 2..8 rows: 32.9 ms with the one walk, 50.3 ms with two walks for every record
-__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_usage(
+__global__ __launch_bounds__(REP_THREADS, 8) void k_rep_boot_usage(
     const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, int32_t n_groups,
-    const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz, int64_t n_boot,
-    int64_t col0, double *__restrict__ vals) {
-#pragma clang fp contract(off)
-    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    const int p = tile * REP_THREADS + threadIdx.x;
-    const bool valid = p < b_count;
-    const uint8_t *mb = mult + (valid ? p : b_count - 1);
-    const int64_t row0 = roff[r], row1 = roff[r + 1];
-    const int stride = n_groups + 1;
-    if (row1 - row0 <= REP_BOOT_USAGE_REG_ROWS) {           // one walk: a_ig of every row stays in a register
-        for (int g = 0; g < n_groups; ++g) {
-            int a[REP_BOOT_USAGE_REG_ROWS];
-            int A = 0;
-#pragma unroll
-            for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k) {
-                a[k] = 0;
-                if (row0 + k < row1) {
-                    const int64_t *si = sg + (row0 + k) * stride;
-                    int s = 0;
-                    rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { s += m * c; });
-                    a[k] = s;
-                    A += s;
-                }
-            }
-            const double dA = (double)A;
-#pragma unroll
-            for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k)
-                if (row0 + k < row1 && valid)
-                    vals[((row0 + k) * n_groups + g) * n_boot + col0 + p] =
-                        A > 0 ? (double)a[k] / dA : __builtin_huge_val();
-        }
-        return;
-    }
-    for (int g = 0; g < n_groups; ++g) {
-        int A = 0;
-        for (int64_t i = row0; i < row1; ++i) {
-            const int64_t *si = sg + i * stride;
-            rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { A += m * c; });
-        }
-        const double dA = (double)A;
-        for (int64_t i = row0; i < row1; ++i) {
-            const int64_t *si = sg + i * stride;
-            int a = 0;
-            rep_groups_walk(nz, si[g], si[g + 1], mb, b_count, [&](int m, int c) { a += m * c; });
-            if (valid)
-                vals[(i * n_groups + g) * n_boot + col0 + p] = A > 0 ? (double)a / dA : __builtin_huge_val();
-        }
-    }
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
+    const int32_t *__restrict__ q, int64_t n_boot, int64_t col0, double *__restrict__ vals) {
+    rep_boot_usage_body<1>(mult, b_count, n_tiles, n_groups, roff, sg, nz, q, n_boot, col0, vals);
 }
 
-// boot_pa_len_diff: workgroup and lanes as k_rep_boot_len, two populations, one series per record.
-// vals[r * n_boot + col0 + replicate of the chunk] = Q_1 / A_1 - Q_2 / A_2; sg[i] = the 3 segment starts of kept row i
 __global__ __launch_bounds__(REP_THREADS) void k_rep_boot_len_diff(
-    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, const int64_t *__restrict__ roff,
-    const int64_t *__restrict__ sg, const uint2 *__restrict__ nz, const int32_t *__restrict__ q, int64_t n_boot,
-    int64_t col0, double *__restrict__ vals) {
-#pragma clang fp contract(off)
-    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    const int p = tile * REP_THREADS + threadIdx.x;
-    const bool valid = p < b_count;
-    const uint8_t *mb = mult + (valid ? p : b_count - 1);
-    const int64_t row0 = roff[r], row1 = roff[r + 1];
-    long long A1 = 0, Q1 = 0, A2 = 0, Q2 = 0;
-    for (int64_t i = row0; i < row1; ++i) {
-        const int64_t *si = sg + i * 3;
-        int a1 = 0, a2 = 0;                  // m <= 15 and the row's reads stay below 2^27
-        rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { a1 += m * c; });
-        rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { a2 += m * c; });
-        const long long qi = q[i];
-        A1 += a1, Q1 += a1 * qi;
-        A2 += a2, Q2 += a2 * qi;
-    }
-    if (valid)
-        vals[(int64_t)r * n_boot + col0 + p] =
-            A1 > 0 && A2 > 0 ? (double)Q1 / (double)A1 - (double)Q2 / (double)A2 : __builtin_huge_val();
+    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, int32_t n_groups,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
+    const int32_t *__restrict__ q, int64_t n_boot, int64_t col0, double *__restrict__ vals) {
+    rep_boot_len_body<2>(mult, b_count, n_tiles, n_groups, roff, sg, nz, q, n_boot, col0, vals);
 }
 
-// boot_pa_usage_diff: workgroup, lanes and the two shapes of k_rep_boot_usage, two populations, one series per kept row.
-// vals[i * n_boot + col0 + replicate of the chunk] = a_i1 / A_1 - a_i2 / A_2
-__global__ __launch_bounds__(REP_THREADS) void k_rep_boot_usage_diff(
-    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, const int64_t *__restrict__ roff,
-    const int64_t *__restrict__ sg, const uint2 *__restrict__ nz, int64_t n_boot, int64_t col0,
-    double *__restrict__ vals) {
-#pragma clang fp contract(off)
-    const int r = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
-    const int p = tile * REP_THREADS + threadIdx.x;
-    const bool valid = p < b_count;
-    const uint8_t *mb = mult + (valid ? p : b_count - 1);
-    const int64_t row0 = roff[r], row1 = roff[r + 1];
-    if (row1 - row0 <= REP_BOOT_USAGE_REG_ROWS) {           // one walk per population: a_i1 waits in registers for A_2
-        int a1[REP_BOOT_USAGE_REG_ROWS], a2[REP_BOOT_USAGE_REG_ROWS];
-        int A1 = 0, A2 = 0;
-#pragma unroll
-        for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k) {
-            a1[k] = 0;
-            if (row0 + k < row1) {
-                const int64_t *si = sg + (row0 + k) * 3;
-                int s = 0;
-                rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { s += m * c; });
-                a1[k] = s;
-                A1 += s;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k) {
-            a2[k] = 0;
-            if (row0 + k < row1) {
-                const int64_t *si = sg + (row0 + k) * 3;
-                int s = 0;
-                rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { s += m * c; });
-                a2[k] = s;
-                A2 += s;
-            }
-        }
-        const bool defined = A1 > 0 && A2 > 0;
-        const double dA1 = (double)A1, dA2 = (double)A2;
-#pragma unroll
-        for (int k = 0; k < REP_BOOT_USAGE_REG_ROWS; ++k)
-            if (row0 + k < row1 && valid)
-                vals[(row0 + k) * n_boot + col0 + p] =
-                    defined ? (double)a1[k] / dA1 - (double)a2[k] / dA2 : __builtin_huge_val();
-        return;
-    }
-    int A1 = 0, A2 = 0;
-    for (int64_t i = row0; i < row1; ++i) {
-        const int64_t *si = sg + i * 3;
-        rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { A1 += m * c; });
-        rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { A2 += m * c; });
-    }
-    const bool defined = A1 > 0 && A2 > 0;
-    const double dA1 = (double)A1, dA2 = (double)A2;
-    for (int64_t i = row0; i < row1; ++i) {
-        const int64_t *si = sg + i * 3;
-        int a1 = 0, a2 = 0;
-        rep_groups_walk(nz, si[0], si[1], mb, b_count, [&](int m, int c) { a1 += m * c; });
-        rep_groups_walk(nz, si[1], si[2], mb, b_count, [&](int m, int c) { a2 += m * c; });
-        if (valid)
-            vals[i * n_boot + col0 + p] = defined ? (double)a1 / dA1 - (double)a2 / dA2 : __builtin_huge_val();
-    }
+__global__ __launch_bounds__(REP_THREADS, 8) void k_rep_boot_usage_diff(
+    const uint8_t *__restrict__ mult, int32_t b_count, int32_t n_tiles, int32_t n_groups,
+    const int64_t *__restrict__ roff, const int64_t *__restrict__ sg, const uint2 *__restrict__ nz,
+    const int32_t *__restrict__ q, int64_t n_boot, int64_t col0, double *__restrict__ vals) {
+    rep_boot_usage_body<2>(mult, b_count, n_tiles, n_groups, roff, sg, nz, q, n_boot, col0, vals);
 }
 
 // the select's order: monotone over the finite doubles of either sign, +infinity above them all
@@ -2768,15 +2740,16 @@ static int rep_boot_build(scape_hip_ctx *c, int32_t n, const int32_t *cell, int6
 // The frame of the four entry points that write replicate values, by the kind of their record set: scape_hip_report_
 // boot_len (q = the rows' positions, one series per record and group), _boot_usage (no q, one series per kept row and
 // group) and their differences _boot_len_diff and _boot_usage_diff (exactly two groups, one series per record or per
-// kept row): the checks, the compaction with the segment starts, the values' array and its written columns;
-// launch(k, grid) queues the entry point's kernel.  A record set is its first chunk's entry point's (b_kind): a later
-// chunk through another one is refused
+// kept row): the checks, the compaction with the segment starts, the values' array and its written columns, and the
+// kind's kernel.  A record set is its first chunk's entry point's (b_kind): a later chunk through another one is
+// refused
 enum RepBootKind : int32_t { REP_BOOT_LEN, REP_BOOT_USAGE, REP_BOOT_LEN_DIFF, REP_BOOT_USAGE_DIFF };
 
-template <typename Launch>
 static int rep_boot_values(scape_hip_ctx *c, RepBootKind kind, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
                            int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
-                           int64_t *a0_out, Launch launch) {
+                           int64_t *a0_out) {
+    static constexpr decltype(&k_rep_boot_len) kernels[] = {k_rep_boot_len, k_rep_boot_usage, k_rep_boot_len_diff,
+                                                            k_rep_boot_usage_diff};
     ReportState *s = report_state(c);
     const RepLabellings &l = s->boot;
     if (l.ready(s->n_cnt_rows)) return 1;
@@ -2812,59 +2785,15 @@ static int rep_boot_values(scape_hip_ctx *c, RepBootKind kind, int32_t n_rec, co
         s->b_written.assign((size_t)n_boot, 0);
     }
     if (q) HIPCHK(hipMemcpyAsync(s->b_q.p, q, k.n_rows * 4, hipMemcpyHostToDevice, c->stream));
-    launch(k, dim3((uint32_t)((int64_t)n_rec * k.n_tiles)));
+    hipLaunchKernelGGL(kernels[kind], dim3((uint32_t)((int64_t)n_rec * k.n_tiles)), dim3(REP_THREADS), 0, c->stream,
+                       s->b_mult.as<uint8_t>(), k.p_count, k.n_tiles, n_groups, s->p_roff.as<int64_t>(),
+                       s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(), q ? s->b_q.as<int32_t>() : nullptr, n_boot,
+                       b_first - 1, s->b_vals.as<double>());
     HIPCHK(hipGetLastError());
     if (k.drain.wait()) return 1;
     s->b_series = n_series, s->b_groups = n_groups, s->b_n_boot = (int32_t)n_boot, s->b_kind = kind;
     std::fill(s->b_written.begin() + (b_first - 1), s->b_written.begin() + (b_first - 1 + b_count), 1);
     return 0;
-}
-
-static int rep_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
-                        int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
-                        int64_t *a0_out) {
-    ReportState *s = report_state(c);
-    return rep_boot_values(c, REP_BOOT_LEN, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out,
-                           [&](const RepPermCall &k, dim3 grid) {
-        hipLaunchKernelGGL(k_rep_boot_len, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
-                           k.n_tiles, n_groups, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
-                           s->b_q.as<int32_t>(), n_boot, s->b_first - 1, s->b_vals.as<double>());
-    });
-}
-
-static int rep_boot_usage(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
-                          int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out, int64_t *a0_out) {
-    ReportState *s = report_state(c);
-    return rep_boot_values(c, REP_BOOT_USAGE, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr, n_boot, t_out, a0_out,
-                           [&](const RepPermCall &k, dim3 grid) {
-        hipLaunchKernelGGL(k_rep_boot_usage, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
-                           k.n_tiles, n_groups, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
-                           n_boot, s->b_first - 1, s->b_vals.as<double>());
-    });
-}
-
-static int rep_boot_len_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
-                             int32_t n_groups, const int32_t *seg_off, const int32_t *q, int64_t n_boot, int64_t *t_out,
-                             int64_t *a0_out) {
-    ReportState *s = report_state(c);
-    return rep_boot_values(c, REP_BOOT_LEN_DIFF, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out,
-                           [&](const RepPermCall &k, dim3 grid) {
-        hipLaunchKernelGGL(k_rep_boot_len_diff, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(), k.p_count,
-                           k.n_tiles, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
-                           s->b_q.as<int32_t>(), n_boot, s->b_first - 1, s->b_vals.as<double>());
-    });
-}
-
-static int rep_boot_usage_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
-                               int32_t n_groups, const int32_t *seg_off, int64_t n_boot, int64_t *t_out,
-                               int64_t *a0_out) {
-    ReportState *s = report_state(c);
-    return rep_boot_values(c, REP_BOOT_USAGE_DIFF, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr, n_boot, t_out,
-                           a0_out, [&](const RepPermCall &k, dim3 grid) {
-        hipLaunchKernelGGL(k_rep_boot_usage_diff, grid, dim3(REP_THREADS), 0, c->stream, s->b_mult.as<uint8_t>(),
-                           k.p_count, k.n_tiles, s->p_roff.as<int64_t>(), s->x_seg.as<int64_t>(), s->p_nz.as<uint2>(),
-                           n_boot, s->b_first - 1, s->b_vals.as<double>());
-    });
 }
 
 // the replicate values are there: a boot_len or boot_usage call has succeeded since they were allocated
@@ -2917,7 +2846,8 @@ int scape_hip_report_boot_len(scape_hip_ctx *c, int32_t n_rec, const int64_t *re
                               int64_t *a0_out) {
     CTX_ENTER(c);
     return rep_boot_named("scape_hip_report_boot_len",
-                          rep_boot_len(c, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out));
+                          rep_boot_values(c, REP_BOOT_LEN, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot,
+                                          t_out, a0_out));
 }
 
 int scape_hip_report_boot_usage(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -2925,7 +2855,8 @@ int scape_hip_report_boot_usage(scape_hip_ctx *c, int32_t n_rec, const int64_t *
                                 int64_t *a0_out) {
     CTX_ENTER(c);
     return rep_boot_named("scape_hip_report_boot_usage",
-                          rep_boot_usage(c, n_rec, rec_row_off, rows, n_groups, seg_off, n_boot, t_out, a0_out));
+                          rep_boot_values(c, REP_BOOT_USAGE, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr,
+                                          n_boot, t_out, a0_out));
 }
 
 int scape_hip_report_boot_len_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -2933,7 +2864,8 @@ int scape_hip_report_boot_len_diff(scape_hip_ctx *c, int32_t n_rec, const int64_
                                    int64_t *t_out, int64_t *a0_out) {
     CTX_ENTER(c);
     return rep_boot_named("scape_hip_report_boot_len_diff",
-                          rep_boot_len_diff(c, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot, t_out, a0_out));
+                          rep_boot_values(c, REP_BOOT_LEN_DIFF, n_rec, rec_row_off, rows, n_groups, seg_off, q, n_boot,
+                                          t_out, a0_out));
 }
 
 int scape_hip_report_boot_usage_diff(scape_hip_ctx *c, int32_t n_rec, const int64_t *rec_row_off, const int64_t *rows,
@@ -2941,7 +2873,8 @@ int scape_hip_report_boot_usage_diff(scape_hip_ctx *c, int32_t n_rec, const int6
                                      int64_t *a0_out) {
     CTX_ENTER(c);
     return rep_boot_named("scape_hip_report_boot_usage_diff",
-                          rep_boot_usage_diff(c, n_rec, rec_row_off, rows, n_groups, seg_off, n_boot, t_out, a0_out));
+                          rep_boot_values(c, REP_BOOT_USAGE_DIFF, n_rec, rec_row_off, rows, n_groups, seg_off, nullptr,
+                                          n_boot, t_out, a0_out));
 }
 
 int scape_hip_report_boot_vals_get(scape_hip_ctx *c, int64_t series, double *vals_out) {

@@ -2386,44 +2386,86 @@ def _boot_quantiles(ctx, su, n_series, times):
     return lo, hi, n_def
 
 
-def _boot_pa_len_batch(su, n_boot, out, ctx, bat, chunk, times):
-    """one counted batch: appends the file's lines (lists of fields) of its reported records to `out` and adds their
-    number to su.n_records"""
+def _boot_batch(kind, su, n_boot, out, ctx, bat, chunk, times):
+    """one counted batch of a bootstrap command, `kind` its description: what the four commands share, from the tested
+    records to the intervals, then kind.lines(su, n_boot, out, recs, b) appends the file's lines (lists of fields) of
+    the batch's reported records to `out` and counts them in su.  kind.positions: the command is about positions, so it
+    takes the records with a span, hands the device their integer positions and reports exp_length, and a series
+    belongs to a record, otherwise to a kept row; kind.diff: the populations are two, both with reads, and a series is
+    their difference, otherwise one population with reads is enough and every population has a series; kind.call: the
+    entry point.  b holds which, off, rows, rowbase, t, a0 and lo, hi, n_def by [record or kept row, series], and of a
+    command with positions xs, scale, exp_len"""
     recs, G = bat.recs, len(su.sizes)
     pos = {}                     # record -> positions of its kept rows (f64, finite)
-    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos), min_pops=1)
-    sel = sel and _with_span(sel, pos, times)
+    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos) if kind.positions else None,
+                     min_pops=2 if kind.diff else 1)
+    if kind.positions:
+        sel = sel and _with_span(sel, pos, times)
     if sel is None:
         return
-    which, off, rows, sums, rowbase, xs = sel
+    b = SimpleNamespace(xs=None, scale=None, exp_len=None)
+    if kind.positions:
+        b.which, b.off, b.rows, sums, b.rowbase, b.xs = sel
+    else:
+        b.which, b.off, b.rows, _nz, sums, b.rowbase = sel
     t0 = timer()
-    _check_boot_reads(recs, which, off, sums)
-    q, scale = _boot_positions(xs)
+    _check_boot_reads(recs, b.which, b.off, sums)
+    if kind.positions:
+        q, b.scale = _boot_positions(b.xs)
     times["finish"] += timer() - t0
-    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
-    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
-        ctx.lib.scape_hip_report_boot_len(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G, ptr(su.seg_off, P_i32),
-                                          ptr(q, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)), "report_boot_len"))
-    _check_row_sums("report_boot_len", t, a0, sums, sums)
-    lo, hi, n_def = (v.reshape(len(which), G) for v in _boot_quantiles(ctx, su, len(which) * G, times))
-    exp_len = _exp_lengths(ctx, su.seg_off, bat, which, rowbase, times)
+    b.t, b.a0 = np.zeros(len(b.rows), np.int64), np.zeros((len(b.rows), G), np.int64)
+    args = ([ctx.h, len(b.which), ptr(b.off, P_i64), ptr(b.rows, P_i64), G, ptr(su.seg_off, P_i32)] +
+            ([ptr(q, P_i32)] if kind.positions else []) + [n_boot, ptr(b.t, P_i64), ptr(b.a0, P_i64)])
+    entry = getattr(ctx.lib, "scape_hip_" + kind.call)
+    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(entry(*args), kind.call))
+    _check_row_sums(kind.call, b.t, b.a0, sums, sums)
+    shape = (len(b.which) if kind.positions else len(b.rows), 1 if kind.diff else G)
+    b.lo, b.hi, b.n_def = (v.reshape(shape) for v in _boot_quantiles(ctx, su, shape[0] * shape[1], times))
+    if kind.positions:
+        b.exp_len = _exp_lengths(ctx, su.seg_off, bat, b.which, b.rowbase, times)
     t0 = timer()
-    for g, r in enumerate(which.tolist()):
-        sl = slice(int(off[g]), int(off[g + 1]))
-        a = a0[sl]
-        _mean, mean_g, _delta = _mean_positions_groups(xs[g], a.tolist())
-        e = exp_len[g]
+    kind.lines(su, n_boot, out, recs, b)
+    times["finish"] += timer() - t0
+
+
+def _boot_run(kind, su, n_boot, device):
+    """the run of a bootstrap command (`kind`: its description) behind its setup su: _boot_batch's batches through
+    _perm_run and the file, kind.header and the lines; returns the lines, and su.wall holds the wall seconds"""
+    su.n_records = su.n_sites = 0
+    out = []
+    # the replicate values, 8 bytes each, of every series: per record, or per label of a record (at most that many
+    # kept rows), of every population or of the one difference
+    series = 1 if kind.diff else len(su.sizes)
+
+    def write(w):
+        w.writerow(kind.header)
+        w.writerows(out)
+
+    su.wall = _perm_run(su, n_boot, device, functools.partial(_boot_batch, kind, su, n_boot, out), write,
+                        record_bytes=lambda p: (1 if kind.positions else int(p.K)) * series * n_boot * 8)
+    return out
+
+
+def _boot_pa_len_lines(su, n_boot, out, recs, b):
+    for g, r in enumerate(b.which.tolist()):
+        sl = slice(int(b.off[g]), int(b.off[g + 1]))
+        a = b.a0[sl]
+        _mean, mean_g, _delta = _mean_positions_groups(b.xs[g], a.tolist())
+        e = b.exp_len[g]
         A = a.sum(axis=0)
-        for p in range(G):
+        for p in range(len(su.sizes)):
             if A[p] == 0:
                 continue
-            D = int(n_def[g, p])
-            ends = (float(lo[g, p]), float(hi[g, p])) if D else (None, None)
-            iv = _boot_columns(*ends, float(xs[g].min()), scale[g], recs[r].alpha_arr, float(e[p]))
-            out.append([recs[r].gene_info_str, su.names[p], int(off[g + 1] - off[g]), int(A[p]), repr(mean_g[p])] +
+            D = int(b.n_def[g, p])
+            ends = (float(b.lo[g, p]), float(b.hi[g, p])) if D else (None, None)
+            iv = _boot_columns(*ends, float(b.xs[g].min()), b.scale[g], recs[r].alpha_arr, float(e[p]))
+            out.append([recs[r].gene_info_str, su.names[p], int(b.off[g + 1] - b.off[g]), int(A[p]), repr(mean_g[p])] +
                        iv[:2] + [repr(float(e[p]))] + iv[2:] + [n_boot - D, n_boot, su.level])
         su.n_records += 1
-    times["finish"] += timer() - t0
+
+
+_BOOT_PA_LEN = SimpleNamespace(header=BOOT_PA_LEN_HEADER, call="report_boot_len", positions=True, diff=False,
+                               lines=_boot_pa_len_lines)
 
 
 def _boot_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file=None, idents=(), n_boot: int = 9999,
@@ -2433,20 +2475,10 @@ def _boot_pa_len(output_dir: str, res_pkl_file: str, cell_cluster_file=None, ide
     the cells; writes <cluster file stem>.<gene|utr>[.<A>+<B>+...].boot_pa_len.csv or all_cell.<gene|utr>
     .boot_pa_len.csv in output_dir, one line per reported record and population with reads, and returns its path"""
     su = _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed)
-    su.n_records = 0
-    out = []
-
-    batch = functools.partial(_boot_pa_len_batch, su, n_boot, out)
-
-    def write(w):
-        w.writerow(BOOT_PA_LEN_HEADER)
-        w.writerows(out)
-
-    # per record the replicate values of every population, 8 bytes each
-    wall = _perm_run(su, n_boot, device, batch, write, record_bytes=len(su.sizes) * n_boot * 8)
+    _boot_run(_BOOT_PA_LEN, su, n_boot, device)
     print(f"Finish {n_boot} bootstrap replicates of {su.n} cells in {len(su.sizes)} populations for {su.n_records} "
           "reported records")
-    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    print(f"Finish {su.res_pkl} in {su.wall / 60} min.")
     return su.outpath
 
 
@@ -2470,40 +2502,25 @@ BOOT_PA_USAGE_HEADER = ["gene", "pa_info", "group", "num_pa", "reads", "gene_rea
                         "n_empty", "n_boot", "level"]
 
 
-def _boot_pa_usage_batch(su, n_boot, out, ctx, bat, chunk, times):
-    """one counted batch: appends the file's lines (lists of fields) of its reported records to `out` and adds their
-    number to su.n_records and that of their kept rows to su.n_sites"""
-    recs, G = bat.recs, len(su.sizes)
-    sel = _perm_rows(ctx, bat, su.seg_off, times, min_pops=1)
-    if sel is None:
-        return
-    which, off, rows, _nz, sums, rowbase = sel
-    t0 = timer()
-    _check_boot_reads(recs, which, off, sums)
-    times["finish"] += timer() - t0
-    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), G), np.int64)
-    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
-        ctx.lib.scape_hip_report_boot_usage(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), G,
-                                            ptr(su.seg_off, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)),
-        "report_boot_usage"))
-    _check_row_sums("report_boot_usage", t, a0, sums, sums)
-    lo, hi, n_def = (v.reshape(len(rows), G) for v in _boot_quantiles(ctx, su, len(rows) * G, times))
-    t0 = timer()
-    for g, r in enumerate(which.tolist()):
-        i0, i1 = int(off[g]), int(off[g + 1])
-        A = a0[i0:i1].sum(axis=0).tolist()
-        pa = _pa_info(recs[r], rows[i0:i1] - int(rowbase[r]))
+def _boot_pa_usage_lines(su, n_boot, out, recs, b):
+    for g, r in enumerate(b.which.tolist()):
+        i0, i1 = int(b.off[g]), int(b.off[g + 1])
+        A = b.a0[i0:i1].sum(axis=0).tolist()
+        pa = _pa_info(recs[r], b.rows[i0:i1] - int(b.rowbase[r]))
         for i in range(i0, i1):
-            a, D = a0[i].tolist(), n_def[i].tolist()
-            for p in range(G):
+            a, D = b.a0[i].tolist(), b.n_def[i].tolist()
+            for p in range(len(su.sizes)):
                 if A[p] == 0:
                     continue
-                ends = [repr(float(lo[i, p])), repr(float(hi[i, p]))] if D[p] else ["", ""]
+                ends = [repr(float(b.lo[i, p])), repr(float(b.hi[i, p]))] if D[p] else ["", ""]
                 out.append([recs[r].gene_info_str, pa[i - i0], su.names[p], i1 - i0, a[p], A[p], repr(a[p] / A[p])] +
                            ends + [n_boot - D[p], n_boot, su.level])
         su.n_records += 1
         su.n_sites += i1 - i0
-    times["finish"] += timer() - t0
+
+
+_BOOT_PA_USAGE = SimpleNamespace(header=BOOT_PA_USAGE_HEADER, call="report_boot_usage", positions=False, diff=False,
+                                 lines=_boot_pa_usage_lines)
 
 
 def _boot_pa_usage(output_dir: str, res_pkl_file: str, cell_cluster_file=None, idents=(), n_boot: int = 9999,
@@ -2514,20 +2531,10 @@ def _boot_pa_usage(output_dir: str, res_pkl_file: str, cell_cluster_file=None, i
     all_cell.<gene|utr>.boot_pa_usage.csv in output_dir, one line per reported record, site and population with reads,
     and returns its path"""
     su = _boot_setup(output_dir, res_pkl_file, cell_cluster_file, idents, n_boot, level, seed, "boot_pa_usage")
-    su.n_records = su.n_sites = 0
-    out = []
-
-    batch = functools.partial(_boot_pa_usage_batch, su, n_boot, out)
-
-    def write(w):
-        w.writerow(BOOT_PA_USAGE_HEADER)
-        w.writerows(out)
-
-    # per label of a record (at most that many kept rows) the replicate values of every population, 8 bytes each
-    wall = _perm_run(su, n_boot, device, batch, write, record_bytes=lambda p: int(p.K) * len(su.sizes) * n_boot * 8)
+    _boot_run(_BOOT_PA_USAGE, su, n_boot, device)
     print(f"Finish {n_boot} bootstrap replicates of {su.n} cells in {len(su.sizes)} populations for {su.n_sites} pA sites "
           f"of {su.n_records} reported records")
-    print(f"Finish {su.res_pkl} in {wall / 60} min.")
+    print(f"Finish {su.res_pkl} in {su.wall / 60} min.")
     return su.outpath
 
 
@@ -2558,91 +2565,40 @@ BOOT_PA_USAGE_DIFF_HEADER = ["gene", "pa_info", "versus", "num_pa", "reads.1", "
                              "level"]
 
 
-def _boot_pa_len_diff_batch(su, n_boot, out, ctx, bat, chunk, times):
-    """one counted batch: appends the file's lines (lists of fields) of its reported records to `out`"""
-    recs = bat.recs
-    pos = {}                     # record -> positions of its kept rows (f64, finite)
-    sel = _perm_rows(ctx, bat, su.seg_off, times, _finite_positions(recs, pos))
-    sel = sel and _with_span(sel, pos, times)
-    if sel is None:
-        return
-    which, off, rows, sums, rowbase, xs = sel
-    t0 = timer()
-    _check_boot_reads(recs, which, off, sums)
-    q, scale = _boot_positions(xs)
-    times["finish"] += timer() - t0
-    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), 2), np.int64)
-    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
-        ctx.lib.scape_hip_report_boot_len_diff(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), 2,
-                                               ptr(su.seg_off, P_i32), ptr(q, P_i32), n_boot, ptr(t, P_i64),
-                                               ptr(a0, P_i64)), "report_boot_len_diff"))
-    _check_row_sums("report_boot_len_diff", t, a0, sums, sums)
-    lo, hi, n_def = _boot_quantiles(ctx, su, len(which), times)
-    exp_len = _exp_lengths(ctx, su.seg_off, bat, which, rowbase, times)
-    t0 = timer()
-    for g, r in enumerate(which.tolist()):
-        sl = slice(int(off[g]), int(off[g + 1]))
-        a, b = a0[sl, 0], a0[sl, 1]
-        m1, m2, d = _mean_positions(xs[g], a.tolist(), b.tolist())
-        e1, e2 = float(exp_len[g][0]), float(exp_len[g][1])
-        D = int(n_def[g])
-        ends = [math.ldexp(float(v), -scale[g]) for v in (lo[g], hi[g])] if D else []
+def _boot_pa_len_diff_lines(su, n_boot, out, recs, b):
+    for g, r in enumerate(b.which.tolist()):
+        sl = slice(int(b.off[g]), int(b.off[g + 1]))
+        a1, a2 = b.a0[sl, 0], b.a0[sl, 1]
+        m1, m2, d = _mean_positions(b.xs[g], a1.tolist(), a2.tolist())
+        e1, e2 = float(b.exp_len[g][0]), float(b.exp_len[g][1])
+        D = int(b.n_def[g, 0])
+        ends = [math.ldexp(float(v), -b.scale[g]) for v in (b.lo[g, 0], b.hi[g, 0])] if D else []
         alpha = np.asarray(recs[r].alpha_arr, dtype=np.float64)
         width = float(alpha[-1]) - float(alpha[0])
         scaled = not (math.isnan(e1) or math.isnan(e2)) and math.isfinite(width) and width > 0
-        out.append([recs[r].gene_info_str, su.versus, int(off[g + 1] - off[g]), int(a.sum()), int(b.sum()), repr(m1),
-                    repr(m2), repr(d)] + ([repr(y) for y in ends] or ["", ""]) + [repr(e1), repr(e2), repr(e1 - e2)] +
+        out.append([recs[r].gene_info_str, su.versus, int(b.off[g + 1] - b.off[g]), int(a1.sum()), int(a2.sum()),
+                    repr(m1), repr(m2), repr(d)] + ([repr(y) for y in ends] or ["", ""]) +
+                   [repr(e1), repr(e2), repr(e1 - e2)] +
                    ([repr(9.0 * y / width) for y in ends] if scaled and D else ["", ""]) + [n_boot - D, n_boot, su.level])
-    times["finish"] += timer() - t0
 
 
-def _boot_pa_usage_diff_batch(su, n_boot, out, ctx, bat, chunk, times):
-    """one counted batch: appends the file's lines (lists of fields), one per kept row of its reported records, to `out`
-    and adds the number of those records to su.n_records"""
-    recs = bat.recs
-    sel = _perm_rows(ctx, bat, su.seg_off, times)
-    if sel is None:
-        return
-    which, off, rows, _nz, sums, rowbase = sel
-    t0 = timer()
-    _check_boot_reads(recs, which, off, sums)
-    times["finish"] += timer() - t0
-    t, a0 = np.zeros(len(rows), np.int64), np.zeros((len(rows), 2), np.int64)
-    _perm_chunks(ctx, su, n_boot, chunk, times, lambda: check(
-        ctx.lib.scape_hip_report_boot_usage_diff(ctx.h, len(which), ptr(off, P_i64), ptr(rows, P_i64), 2,
-                                                 ptr(su.seg_off, P_i32), n_boot, ptr(t, P_i64), ptr(a0, P_i64)),
-        "report_boot_usage_diff"))
-    _check_row_sums("report_boot_usage_diff", t, a0, sums, sums)
-    lo, hi, n_def = _boot_quantiles(ctx, su, len(rows), times)
-    t0 = timer()
-    n_lines = np.diff(off)
-    usage, rec_of, A, B = _usage_columns(t, np.ascontiguousarray(a0[:, 0]), n_lines)
-    pa = [p for g, r in enumerate(which.tolist()) for p in _pa_info(recs[r], rows[off[g]:off[g + 1]] - int(rowbase[r]))]
+def _boot_pa_usage_diff_lines(su, n_boot, out, recs, b):
+    n_lines = np.diff(b.off)
+    usage, rec_of, A, B = _usage_columns(b.t, np.ascontiguousarray(b.a0[:, 0]), n_lines)
+    pa = [p for g, r in enumerate(b.which.tolist())
+          for p in _pa_info(recs[r], b.rows[b.off[g]:b.off[g + 1]] - int(b.rowbase[r]))]
     for i, g in enumerate(rec_of.tolist()):
-        D = int(n_def[i])
-        ends = [repr(float(lo[i])), repr(float(hi[i]))] if D else ["", ""]
-        out.append([recs[which[g]].gene_info_str, pa[i], su.versus, int(n_lines[g]), int(a0[i, 0]), int(a0[i, 1]),
+        D = int(b.n_def[i, 0])
+        ends = [repr(float(b.lo[i, 0])), repr(float(b.hi[i, 0]))] if D else ["", ""]
+        out.append([recs[b.which[g]].gene_info_str, pa[i], su.versus, int(n_lines[g]), int(b.a0[i, 0]), int(b.a0[i, 1]),
                     int(A[i]), int(B[i]), usage[0][i], usage[1][i], usage[2][i]] + ends + [n_boot - D, n_boot, su.level])
-    su.n_records += len(which)
-    times["finish"] += timer() - t0
+    su.n_records += len(b.which)
 
 
-def _boot_diff(batch_of, header, record_bytes, command, output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2,
-               n_boot, level, seed, device):
-    """the run of boot_pa_len_diff and boot_pa_usage_diff: the setup, batch_of's batches through _perm_run with
-    record_bytes device bytes of replicate values per record (a number or a function of the record), and the file;
-    returns (setup with the wall seconds, lines)"""
-    su = _boot_diff_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed, command)
-    su.n_records = 0
-    out = []
-
-    def write(w):
-        w.writerow(header)
-        w.writerows(out)
-
-    su.wall = _perm_run(su, n_boot, device, functools.partial(batch_of, su, n_boot, out), write,
-                        record_bytes=record_bytes)
-    return su, out
+_BOOT_PA_LEN_DIFF = SimpleNamespace(header=BOOT_PA_LEN_DIFF_HEADER, call="report_boot_len_diff", positions=True,
+                                    diff=True, lines=_boot_pa_len_diff_lines)
+_BOOT_PA_USAGE_DIFF = SimpleNamespace(header=BOOT_PA_USAGE_DIFF_HEADER, call="report_boot_usage_diff", positions=False,
+                                      diff=True, lines=_boot_pa_usage_diff_lines)
 
 
 def _boot_pa_len_diff(output_dir: str, res_pkl_file: str, cell_cluster_file: str, idents_1: str, idents_2=None,
@@ -2651,9 +2607,9 @@ def _boot_pa_len_diff(output_dir: str, res_pkl_file: str, cell_cluster_file: str
     cluster idents_1 and those of idents_2 (None: every other cell that has a cluster), by resampling the cells with
     boot_pa_len's replicates; writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.boot_pa_len_diff.csv in output_dir,
     one line per record diff_pa_len tests, and returns its path"""
-    # per record one series of replicate values, 8 bytes each
-    su, out = _boot_diff(_boot_pa_len_diff_batch, BOOT_PA_LEN_DIFF_HEADER, n_boot * 8, "boot_pa_len_diff", output_dir,
-                         res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed, device)
+    su = _boot_diff_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed,
+                          "boot_pa_len_diff")
+    out = _boot_run(_BOOT_PA_LEN_DIFF, su, n_boot, device)
     print(f"Finish {n_boot} bootstrap replicates of {su.sizes[0]} + {su.sizes[1]} cells for {len(out)} reported records")
     print(f"Finish {su.res_pkl} in {su.wall / 60} min.")
     return su.outpath
@@ -2665,10 +2621,9 @@ def _boot_pa_usage_diff(output_dir: str, res_pkl_file: str, cell_cluster_file: s
     idents_1 and those of idents_2 (None: every other cell that has a cluster), by resampling the cells with
     boot_pa_len's replicates; writes <cluster file stem>.<gene|utr>.<A>_vs_<B|rest>.boot_pa_usage_diff.csv in
     output_dir, one line per line of diff_pa, and returns its path"""
-    # per label of a record (at most that many kept rows) one series of replicate values, 8 bytes each
-    su, out = _boot_diff(_boot_pa_usage_diff_batch, BOOT_PA_USAGE_DIFF_HEADER, lambda p: int(p.K) * n_boot * 8,
-                         "boot_pa_usage_diff", output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot,
-                         level, seed, device)
+    su = _boot_diff_setup(output_dir, res_pkl_file, cell_cluster_file, idents_1, idents_2, n_boot, level, seed,
+                          "boot_pa_usage_diff")
+    out = _boot_run(_BOOT_PA_USAGE_DIFF, su, n_boot, device)
     print(f"Finish {n_boot} bootstrap replicates of {su.sizes[0]} + {su.sizes[1]} cells for {len(out)} pA sites of "
           f"{su.n_records} reported records")
     print(f"Finish {su.res_pkl} in {su.wall / 60} min.")

@@ -15,6 +15,7 @@ with one repeat; every timed run launches its value kernel and the select once p
     python tools/boot_pa_diff_timing.py --kernel_trace P --batches <the four timed runs', in their order>
 
     python tools/boot_pa_diff_timing.py [--records N] [--cells N] [--n_boot N] [--dir D] [--groups 12] [--repeats 3]
+                                        [--sites 2,8]
 """
 import argparse
 import csv
@@ -81,6 +82,8 @@ def main():
     ap.add_argument("--dir", default=None, help="directory to make the inputs in, or to reuse if it holds them")
     ap.add_argument("--groups", type=int, default=12, help="number of equal-sized clusters; g0 and g1 are compared")
     ap.add_argument("--repeats", type=int, default=3, help="timed runs per command")
+    ap.add_argument("--sites", default="2,8", help="LO,HI: the records made have K = LO..HI pA sites (above 8: the value "
+                                                   "kernels' path for long records)")
     ap.add_argument("--kernel_trace", default=None,
                     help="the -d directory of a rocprofv3 kernel trace of this script: print its kernels' times and stop")
     ap.add_argument("--batches", default="1,1,1,1",
@@ -95,7 +98,7 @@ def main():
     try:
         if not os.path.exists(os.path.join(root, "nz.npz")):
             os.makedirs(root, exist_ok=True)
-            make_dir(root, a.records, a.cells)
+            make_dir(root, a.records, a.cells, sites=tuple(int(v) for v in a.sites.split(",")))
         z = np.load(os.path.join(root, "nz.npz"))
         out.update(rows=int(z["rec_rows"][-1]), nonzeros=int(z["row_off"][-1]), device=_lib.default_context().name())
         clu = make_groups(root, int(z["n_cells"]), a.groups)

@@ -45,9 +45,9 @@ G = np.uint64(0x9E3779B97F4A7C15)
 DENSITY = 0.05
 
 
-def make_dir(root, n_rec, n_cells, seed=7):
+def make_dir(root, n_rec, n_cells, seed=7, sites=(2, 8)):
     """output_dir with barcode_index.csv, groups.csv, res.gene.pkl and nz.npz (the nonzeros the records were made of:
-    row offsets per record, per row its columns and counts)"""
+    row offsets per record, per row its columns and counts); the records' K cycles through sites[0] .. sites[1]"""
     from scape.apa_core import Parameters
     rng = np.random.default_rng(seed)
     os.makedirs(os.path.join(root, "pkl_input"), exist_ok=True)
@@ -60,7 +60,7 @@ def make_dir(root, n_rec, n_cells, seed=7):
     rec_rows, row_off, cols, cnts = [0], [0], [], []
     with open(os.path.join(root, "res.gene.pkl"), "wb") as fh:
         for r in range(n_rec):
-            K = 2 + r % 7
+            K = sites[0] + r % (sites[1] - sites[0] + 1)
             m = (rng.random((K, n_cells)) < DENSITY) * rng.integers(1, 4, (K, n_cells))
             lab, cell = np.nonzero(m)
             c = m[lab, cell]
