@@ -52,6 +52,48 @@ Named perturbations - WRONG M-steps expressed in the reference, to show that a t
     last_max          the last maximum among the exact ties instead of the first
     rows_to=r         rows at or above r are ignored (a partial last tile, a window cut at a tile edge)
 A perturbation that leaves no row gives row -1.
+
+Bounds on the E-step's own outputs (Round / Fit: ws_bound, lb_bound, bic_bound; absolute, MARGIN included).  They follow
+estep_body's sequence and hold for ANY order of the sums (a sum of m terms t_i costs (m - 1) sum |t_i|).  The chain above
+feeds the M-step bound through e(w) as it always did; the E-step bounds run the same chain a second time (suffix F in
+the code) with the weight error carried in full from round to round:
+    W_c   = sum_n cnt Z_c                   e(W_c)  = sum_n cnt Z_c (e(Z_c) + 1) / W_c + (N - 1)
+    S     = sum_c W_c                       e(S)    = sum_c W_c e(W_c) / S + K
+    w_c   = W_c / S                         e(w_c)  = e(W_c) + e(S) + 1;  W_c = 0: w_c = 0 exactly
+    cap:  sk = sum_{c < K} w_c              e(sk)   = sum_c w_c e(w_c) / sk + (K - 1)
+          w_c = ((1 - m) w_c) / sk          e(w_c) += e(sk) + 3;   w_K = m = max_unif_ws is an input: no error
+  ws_bound = u (MARGIN e(w_c) + 1) w_c + (sum cnt + 1) 2^-1074: the 1 is the reference's own rounding to f64, the last term
+  the absolute rounding of values below the normal range (an exp result of 1e-310 has no relative accuracy).  The output
+  sort permutes the bound with the weights.  A weight that was never computed (the init, the cap value) has e = 0.
+ell = sum_{n, c: Z != 0} t,  t = (Z_c cnt) lz_c:
+    |d t|  <= |t| (e(Z_c) + 2) + Z_c cnt E(lz_c)        (two products; E(lz_c) = |lz_c| on a sentinel entry that the
+                                                         rescue made non-zero: the one rounding of log w + SENT)
+    |d ell| <= sum |d t| + (terms - 1) sum |t|
+  bic = -2 ell + (3 K + 1) log N:           |d bic| <= 2 |d ell| + 3 pen + |bic|     (library log, product, sum)
+ent = sum_n cnt sum_c -pk_c L_c over the columns with pk_c > 0; s2 = sum_c Z_c, x2 = s2 - 1, X2 = 2 K + 3 (+ 1 with the
+rescue) bounds |s2 - its exact value| / u: K roundings each of s and s2 and the 3 u of Z_c = z_c rcp(s) - the rounding of
+Z_c that the closed form below does not see is inside X2:
+    pk_c  = Z_c rcp(s2)                     e(pk)   = e(Z_c) + X2 + 2 + 1
+    ls    = d_log_pos(s)  (0.83 ulp)        E(ls)   = e(s) + 1.66 |ls|
+    ls2   = x2 - x2^2 / 2                   E(ls2)  = X2 (+ 3 |x2| + |x2|^3 / (3 u) with the rescue: roundings, the series' tail)
+    L_c   = (arg_c - ls) - ls2              E(L_c)  = E(arg_c) + E(ls) + E(ls2) + |arg_c - ls| + |L_c|
+    L_k   = log(zk) - ls2  (rescue)         E(L_k)  = e(Z_k) + 2 |log zk| + E(ls2) + |L_k|      zk = Z_k + 1e-8
+    |d ent| <= sum cnt pk (|L| (e(pk) + 2) + E(L)) + (terms - 1) sum cnt pk |L|
+  Without the rescue the exact s2 is 1 and the whole of ls2 counts as error.
+lb = ell + ent:                             |d lb|  <= |d ell| + |d ent| + |lb|
+Every bound gets one more u |value| for the reference's own rounding to f64.  The liveness test (lz_c - mx) cnt >= -746
+of estep_body is one more f64 comparison: between -746 and -745.13 exp gives 0 or a subnormal, which the reference takes
+as 0; an argument within 1e-9 relative of -745.13 counts as ``near``, and so does a bin whose row maximum is itself a
+sentinel (log 0 + M), where f64 absorbs what long double keeps.
+
+Named wrong E-steps (E_PERTURBATIONS), used like the M-step ones:
+    e_drop_bin=n      bin n is in no sum (log N of the BIC keeps N)       e_drop_col=c    column c takes no part
+    no_rescue         Z[:, k] is never lifted by 1e-8                     rescue_once     ... lifted, but the entropy is the un-rescued Z's
+    no_cap            the uniform weight is not capped                    cap_inclusive   >= instead of > in the cap
+    fresh_columns     every column's log-weight is refreshed every round, not only column k's
+    untempered        the counts are not in the exponent                  exp_zero=x      exp is cut to 0 below x instead of -745.13
+    entropy_plain     the entropy is -sum Z log Z, not re-normalised by s2
+    zero_weight_as_tiny   log 0 is log 1e-300, not the sentinel
 """
 from __future__ import annotations
 
@@ -68,6 +110,10 @@ LIB = 2.0                               # library log: 1 ulp
 RCP = 2.0                               # z * d_rcp_mid(s) against z / s
 EXP_ZERO = -745.13                      # exp(x) is 0 in f64 below this
 PERTURBATIONS = ("drop_bin", "lo_exclusive", "hi_exclusive", "sentinel_as_zero", "last_max", "rows_to")
+E_PERTURBATIONS = ("e_drop_bin", "e_drop_col", "no_rescue", "rescue_once", "no_cap", "cap_inclusive", "fresh_columns",
+                   "untempered", "exp_zero", "entropy_plain", "zero_weight_as_tiny")
+LOG_DEV = 1.66                          # d_log_pos: 0.83 ulp
+TINY = 2.0 ** -1074                     # the spacing of f64 below the normal range
 
 
 def _need_long_double():
@@ -91,6 +137,11 @@ class Round:
     ws: np.ndarray              # [K + 1] long double, after maximize_ws
     lb: float
     near: int
+    ws_bound: np.ndarray = None # f64 [K + 1] absolute, in the order of `ws`
+    lb_bound: float = 0.0
+    bic_bound: float = 0.0      # of the BIC a job that ends with this round returns
+    capped: bool = False
+    x2: float = 0.0             # largest |s2 - 1| over the bins: 1e-8 with the rescue, 0 without (estep_body's series is for < 1e-5)
 
     @property
     def decided(self):
@@ -114,6 +165,9 @@ class Fit:
     lb: np.ndarray              # f64 [n_lb]
     near: int = 0
     order: np.ndarray = field(default=None)     # the argsort that was applied
+    ws_bound: np.ndarray = field(default=None)  # f64 [K + 1] absolute, in the order of `ws`
+    lb_bound: np.ndarray = field(default=None)  # f64 [n_lb] absolute
+    bic_bound: float = 0.0
 
 
 def _log_w(w):
@@ -129,15 +183,25 @@ def _column(M, a, b, lw, sent_out):
 
 
 def em_rounds(M, cnt, unif_ll, theta, betas, L, min_theta, max_unif_ws, a_idx, b_idx, ws, k_arr, nround, fixed=False,
-              drop_bin=None, lo_exclusive=False, hi_exclusive=False, sentinel_as_zero=False, last_max=False, rows_to=None):
+              drop_bin=None, lo_exclusive=False, hi_exclusive=False, sentinel_as_zero=False, last_max=False, rows_to=None,
+              e_drop_bin=None, e_drop_col=None, no_rescue=False, rescue_once=False, no_cap=False, cap_inclusive=False,
+              fresh_columns=False, untempered=False, exp_zero=None, entropy_plain=False, zero_weight_as_tiny=False):
     """em_algo (:714-779) from a given init on the f64 tensor M [T, B, N]: `nround` rounds at most, the stopping rule
     included.  Returns a Fit; Fit.rounds[i] describes the M-step of round i."""
     _need_long_double()
     M = np.asarray(M, dtype=np.float64)
+    n_bic = M.shape[2]
+    cnt = np.asarray(cnt, dtype=np.float64)
+    if e_drop_bin is not None and 0 <= e_drop_bin < n_bic:
+        keep = np.arange(n_bic) != e_drop_bin
+        M, cnt = M[:, :, keep], cnt[keep]
     T, B, N = M.shape
     theta, betas = np.asarray(theta, np.float64), np.asarray(betas, np.float64)
     cn = np.asarray(cnt, dtype=np.float64).astype(LD)
     cn64 = cn.astype(np.float64)
+    ce, ce64 = (np.ones(N, LD), np.ones(N)) if untempered else (cn, cn64)      # the counts as the exponent has them
+    cut = LD(EXP_ZERO if exp_zero is None else exp_zero)
+    log_w = (lambda x: np.log(LD(1e-300)) if x <= 0 else np.log(x)) if zero_weight_as_tiny else _log_w
     a = np.array(a_idx, dtype=np.int64)
     b = np.array(b_idx, dtype=np.int64)
     K = len(a)
@@ -147,61 +211,84 @@ def em_rounds(M, cnt, unif_ll, theta, betas, L, min_theta, max_unif_ws, a_idx, b
     logz = np.zeros((N, C), dtype=LD)
     sent = np.zeros((N, C), dtype=bool)
     Elw = np.zeros(C)                                    # E(lw_c) of the column as it stands in logz
+    EwF, ElwF = np.zeros(C), np.zeros(C)                 # the same two for the E-step bounds: e(w_c) carried in full
 
     def refresh(c):
-        lw = _log_w(w[c])
+        lw = log_w(w[c])
         Elw[c] = LIB * abs(float(lw)) + Ew[c]
+        ElwF[c] = LIB * abs(float(lw)) + EwF[c]
         if c < K:
             logz[:, c] = _column(M, a[c], b[c], lw, sent[:, c])
         else:
             logz[:, c] = lw + LD(unif_ll)
             sent[:, c] = False
+        if e_drop_col is not None and c == e_drop_col:
+            logz[:, c] = LD(SENT)
+            sent[:, c] = True
     for c in range(C):
         refresh(c)
     rounds, lbs, near_all = [], [], 0
     lb_prev = LD(SENT)
     Z = None
+    ell_new = d_ell = LD(0)
     with np.errstate(all="ignore"):
         for it in range(nround):
             k = int(k_arr[it])
             near = 0
-            refresh(k)
+            for c in (range(C) if fresh_columns else (k,)):
+                refresh(c)
             # ---- norm_z (:490-495)
             mx = logz.max(axis=1)
             amx = logz.argmax(axis=1)
             d = logz - mx[:, None]
-            arg = d * cn[:, None]
-            live = ~sent & (arg >= LD(EXP_ZERO))
+            arg = d * ce[:, None]
+            live = ~sent & (arg >= cut)
             z = np.where(live, np.exp(np.where(live, arg, LD(0))), LD(0))
             s = z.sum(axis=1)
             Zc = z / s[:, None]
+            near += int((~sent & (np.abs(arg.astype(np.float64) / EXP_ZERO - 1) < 1e-9)).sum()) + int((mx < LD(SENT) / 2).sum())
             # e(z_c), e(s), e(Z_c) in u
             a_lz = np.abs(logz).astype(np.float64)
-            E_lz = np.where(sent, 0.0, Elw[None, :] + a_lz)
-            E_mx = E_lz[np.arange(N), amx]
             is_mx = np.arange(C)[None, :] == amx[:, None]
-            E_arg = cn64[:, None] * (E_lz + E_mx[:, None] + np.abs(d).astype(np.float64)) + np.abs(arg).astype(np.float64)
-            e_z = np.where(live & ~is_mx, E_arg + EXP_DEV, 0.0)
-            e_s = (z * e_z.astype(LD)).sum(axis=1).astype(np.float64) / s.astype(np.float64) + K
-            e_Z = np.where(live, e_z + e_s[:, None] + RCP + 1, 0.0)
+
+            def chain(Elw):
+                E_lz = np.where(sent, 0.0, Elw[None, :] + a_lz)
+                E_mx = E_lz[np.arange(N), amx]
+                E_arg = ce64[:, None] * (E_lz + E_mx[:, None] + np.abs(d).astype(np.float64)) + np.abs(arg).astype(np.float64)
+                e_z = np.where(live & ~is_mx, E_arg + EXP_DEV, 0.0)
+                e_s = (z * e_z.astype(LD)).sum(axis=1).astype(np.float64) / s.astype(np.float64) + K
+                e_Z = np.where(live, e_z + e_s[:, None] + RCP + 1, 0.0)
+                return E_lz, E_arg, e_s, e_Z
+            _E_lz, _E_arg, _e_s, e_Z = chain(Elw)
+            E_lzF, E_argF, e_sF, e_ZF = chain(ElwF)
             # ---- mstep (:525-533): rescue, maximize_ws
             sumk = Zc[:, k].sum()
             near += int(abs(float(sumk) / 1e-8 - 1) < 1e-9)
-            rescue = bool(sumk < LD(1e-8))
+            rescue = bool(sumk < LD(1e-8)) and not no_rescue
             Z = Zc.copy()
             if rescue:
                 Z[:, k] = Z[:, k] + LD(1e-8)
                 e_Z[:, k] = e_Z[:, k] + 1
+                e_ZF[:, k] = e_ZF[:, k] + 1
             wn = (cn[:, None] * Z).sum(axis=0)
             cz = (cn[:, None] * Z)
             e_w = (cz * (e_Z + 1).astype(LD)).sum(axis=0).astype(np.float64) / np.where(wn > 0, wn, LD(1)).astype(np.float64) + (N - 1) + K + 1
+            # the same in full: numerators, their sum, the quotient
+            wn64 = wn.astype(np.float64)
+            e_WF = (cz * (e_ZF + 1).astype(LD)).sum(axis=0).astype(np.float64) / np.where(wn64 > 0, wn64, 1.0) + (N - 1)
+            e_wF = np.where(wn64 > 0, e_WF + float((wn64 * e_WF).sum() / wn64.sum()) + K + 1, 0.0)
             wn = wn / wn.sum()
             near += int(abs(float(wn[K]) / max_unif_ws - 1) < 1e-9)
-            if wn[K] > LD(max_unif_ws):
+            capped = bool(wn[K] >= LD(max_unif_ws) if cap_inclusive else wn[K] > LD(max_unif_ws)) and not no_cap
+            if capped:
+                wk64 = wn[:K].astype(np.float64)
+                e_sk = float((wk64 * e_wF[:K]).sum() / wk64.sum()) + max(K - 1, 0) if K else 0.0
+                e_wF = np.where(wn64 > 0, e_wF + e_sk + 3, 0.0)
+                e_wF[K] = 0.0
                 wn[:K] = (LD(1) - LD(max_unif_ws)) * wn[:K] / wn[:K].sum()
                 wn[K] = LD(max_unif_ws)
                 e_w = e_w + K + 2
-            w, Ew = wn, e_w
+            w, Ew, EwF = wn, e_w, e_wF
             v = Z[:, k] * cn
             e_v = e_Z[:, k] + 1
             nz = np.nonzero(v != 0)[0]
@@ -228,8 +315,19 @@ def em_rounds(M, cnt, unif_ll, theta, betas, L, min_theta, max_unif_ws, a_idx, b
                 if rnd.row >= 0:
                     a[k], b[k] = rnd.row // B, rnd.row % B
             # ---- elbo (:559-561) on the logz of this round and the Z the rescue may have changed
-            lb_new = _exp_log_lik(logz, Z, cn) + _entropy(Z, cn)
+            ell_new = _exp_log_lik(logz, Z, cn)
+            Zent = Zc if rescue_once else Z
+            lb_new = ell_new + _entropy(Zent, cn, entropy_plain)
             rnd.lb, rnd.near = float(lb_new), near
+            # ---- the bounds of this round's outputs (module docstring)
+            w64, lb64 = w.astype(np.float64), abs(float(lb_new))
+            rnd.capped = capped
+            rnd.x2 = float(np.max(np.abs(Zent.sum(axis=1) - 1))) if N else 0.0
+            rnd.ws_bound = U * (MARGIN * EwF + 1) * w64 + (float(cn64.sum()) + 1) * TINY
+            d_ell = _ell_error(logz, Z, cn64, sent, E_lzF, e_ZF)
+            d_ent = _entropy_error(Zent, s, arg, is_mx, cn64, K, rescue and not rescue_once, k, E_argF, e_sF, e_ZF)
+            rnd.lb_bound = U * (MARGIN * (d_ell + d_ent + lb64) + lb64)
+            rnd.bic_bound = _bic_bound(float(ell_new), d_ell, K, n_bic)
             near_all += near
             rounds.append(rnd)
             lbs.append(float(lb_new))
@@ -238,11 +336,14 @@ def em_rounds(M, cnt, unif_ll, theta, betas, L, min_theta, max_unif_ws, a_idx, b
             if gap < thr:
                 break
             lb_prev = lb_new
-        bic = LD(-2) * _exp_log_lik(logz, Z, cn) + LD(3 * K + 1) * np.log(LD(N))
+        bic = LD(-2) * _exp_log_lik(logz, Z, cn) + LD(3 * K + 1) * np.log(LD(n_bic))
     order = np.argsort(theta[a], kind="stable")
     wout = w.astype(np.float64)
     wout[:K] = wout[:K][order]
-    return Fit(rounds=rounds, a_idx=a[order], b_idx=b[order], ws=wout, bic=float(bic), lb=np.array(lbs), near=near_all, order=order)
+    wb = rounds[-1].ws_bound.copy()
+    wb[:K] = wb[:K][order]
+    return Fit(rounds=rounds, a_idx=a[order], b_idx=b[order], ws=wout, bic=float(bic), lb=np.array(lbs), near=near_all, order=order,
+               ws_bound=wb, lb_bound=np.array([r.lb_bound for r in rounds]), bic_bound=rounds[-1].bic_bound)
 
 
 def _exp_log_lik(logz, Z, cn):
@@ -250,10 +351,47 @@ def _exp_log_lik(logz, Z, cn):
     return np.where(nzm, (Z * cn[:, None]) * np.where(nzm, logz, LD(0)), LD(0)).sum()
 
 
-def _entropy(Z, cn):
-    pk = Z / Z.sum(axis=1, keepdims=True)
+def _entropy(Z, cn, plain=False):
+    pk = Z if plain else Z / Z.sum(axis=1, keepdims=True)
     pos = pk > 0
     return (cn * np.where(pos, -pk * np.log(np.where(pos, pk, LD(1))), LD(0)).sum(axis=1)).sum()
+
+
+def _ell_error(logz, Z, cn64, sent, E_lz, e_Z):
+    """|d ell| in u (module docstring): the terms' own errors and (terms - 1) sum |t| for the additions."""
+    nzm = Z != 0
+    zc = np.where(nzm, Z, LD(0)).astype(np.float64) * cn64[:, None]
+    a_lz = np.where(nzm, np.abs(logz), LD(0)).astype(np.float64)
+    at = zc * a_lz
+    E = np.where(sent, a_lz, E_lz)
+    return float((at * (e_Z + 2)).sum() + (zc * E).sum() + max(int(nzm.sum()) - 1, 0) * at.sum())
+
+
+def _entropy_error(Z, s, arg, is_mx, cn64, K, rescue, k, E_arg, e_s, e_Z):
+    """|d ent| in u (module docstring), for the closed form of estep_body on the row sums s and s2."""
+    s2 = Z.sum(axis=1)
+    x2 = np.abs(s2 - 1).astype(np.float64)
+    pk = Z / s2[:, None]
+    pos = pk > 0
+    L = np.abs(np.log(np.where(pos, pk, LD(1)))).astype(np.float64)
+    ls = np.abs(np.log(s)).astype(np.float64)
+    X2 = 2 * K + RCP + 1 + (1 if rescue else 0)
+    E_ls2 = X2 + ((3 * x2 + x2 ** 3 / (3 * U)) if rescue else 0.0)
+    a_arg = np.where(pos, np.abs(arg), LD(0)).astype(np.float64)
+    E_L = np.where(is_mx, 0.0, E_arg) + (e_s + LOG_DEV * ls + E_ls2)[:, None] + (a_arg + ls[:, None]) + L
+    if rescue:
+        zk = np.abs(np.log(np.where(Z[:, k] > 0, Z[:, k], LD(1)))).astype(np.float64)
+        E_L[:, k] = e_Z[:, k] + LIB * zk + E_ls2 + L[:, k]
+    e_pk = e_Z + X2 + RCP + 1
+    p64 = np.where(pos, pk, LD(0)).astype(np.float64) * cn64[:, None]
+    t = p64 * L
+    return float((t * (e_pk + 2)).sum() + (p64 * np.where(pos, E_L, 0.0)).sum() + max(int(pos.sum()) - 1, 0) * t.sum())
+
+
+def _bic_bound(ell, d_ell, K, N):
+    pen = (3 * K + 1) * float(np.log(float(N)))
+    bic = abs(-2 * ell + pen)
+    return U * (MARGIN * (2 * d_ell + (LIB + 1) * pen + bic) + bic)
 
 
 def _score_rows(rnd, M2, rows, v, e_v, lw, E_lw, sentinel_as_zero, last_max):

@@ -127,8 +127,8 @@ def run_reference(q, M, job, nround, **perturb):
                         job.ws, job.k_arr, nround, **perturb)
 
 
-def run_oracle(q, M, job, nround):
-    """so_em_algo from the job's init: dict(a, b: grid indices, ws, bic, lb)."""
+def run_oracle(q, M, job, nround, fixed=False):
+    """so_em_algo from the job's init: dict(a, b: grid indices, ws, bic, lb).  fixed: no M-step (mstep_fixed)."""
     import ctypes
     from oracle import scape_oracle as so
     a, b = q.theta[job.a_idx].copy(), q.betas[job.b_idx].copy()
@@ -140,7 +140,7 @@ def run_oracle(q, M, job, nround):
     n = so.lib().so_em_algo(so._p(Mc), ctypes.c_int(q.T), ctypes.c_int(len(be)), ctypes.c_int(q.N), so._p(th), so._p(be), so._p(cnt),
                             ctypes.c_double(q.unif_ll), ctypes.c_double(q.L), ctypes.c_double(q.min_theta),
                             ctypes.c_double(q.p["max_unif_ws"]), ctypes.c_int(job.K), so._p(a), so._p(b), so._p(w),
-                            so._p(ka, so._I64), ctypes.c_int(nround), ctypes.c_int(0), ctypes.byref(bic), so._p(lb))
+                            so._p(ka, so._I64), ctypes.c_int(nround), ctypes.c_int(int(fixed)), ctypes.byref(bic), so._p(lb))
     return dict(a=np.searchsorted(q.theta, a), b=np.searchsorted(q.betas, b), ws=w, bic=bic.value, lb=lb[:n].copy())
 
 

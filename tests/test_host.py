@@ -800,3 +800,75 @@ def test_mstep_ladder_covers_every_boundary_of_the_mstep_kernels():
     assert ends == {(e, r) for e in ("lo", "hi") for r in (0, 1, 15, 16, 17, MT_ROWS - 1)}
     assert set(ml.WINDOW_TILES) == {1, 2, 3} and M4_TPW == 2                          # k4_mstep takes tiles in pairs: the odd tile last
     assert all((q.T * len(q.betas)) % MT_ROWS for c in cases.values() for q in c.preps)   # the last tile is partial everywhere
+
+
+def test_estep_ladder_covers_every_boundary_of_the_estep():
+    """tests/test_estep_ladder.py runs estep_body through k2_estep, k2_estep_all_rounds and k2_estep_cs on the cases of
+    tests/estep_ladder.py.  The boundaries are read here from the sources - the 64 lanes of the bin loop, the row pitch,
+    the column classes and the exact-variant limit of ESTEP_DISPATCH, the liveness cut, the rescue constant, the series
+    limit of log s2, EM_DEPTH - and the ladder must have a value on both sides of each (whoever moves one has to move the
+    ladder).  The ladder's restatement of which E-step kernel a call runs is pinned to the source here as well."""
+    import estep_ladder as el
+    import mstep_ladder as ml
+    csrc = os.path.join(ROOT, "scape_amd", "csrc")
+    src = open(os.path.join(csrc, "scape_hip.hip")).read()
+    k2 = open(os.path.join(csrc, "em_lockstep.inc")).read()
+    # ---- lanes and pitch
+    assert len(re.findall(r"for \(int n = lane; n < Np; n \+= (\d+)\)", k2)) == 1 and len(re.findall(r"for \(int n0 = 0; n0 < Np; n0 \+= (\d+), buf \^= 1\)", k2)) == 1
+    assert {re.search(r"for \(int n = lane; n < Np; n \+= (\d+)\)", k2).group(1),
+            re.search(r"for \(int n0 = 0; n0 < Np; n0 \+= (\d+), buf", k2).group(1)} == {str(el.LANES)}
+    assert "fetch(n + %d, mnext, cnext);" % el.LANES in k2 and "__launch_bounds__(%d, (CMAX > 12 ? 2 : ESTEP_WPS)) void k2_estep(" % el.LANES in k2
+    assert int(re.search(r"#define PITCH (\d+)\b", src).group(1)) == el.PITCH and "d.Np = round_up((int)N, PITCH);" in src
+    Ns = set(el.N_BINS)
+    for b in (el.PITCH, el.LANES, 2 * el.LANES):
+        assert {b - 1, b, b + 1} <= Ns, b
+    assert {1, 4 * el.LANES + 1} <= Ns and max(Ns) <= 257
+    by = {c.name: c for c in el.cases()}
+    assert [q.N for q in by["bins"].preps[:-1]] == list(el.N_BINS)
+    # ---- column classes, the exact variants, the wide cap
+    classes = [int(c) for c in re.findall(r"using EstepClasses = std::integer_sequence<int,([\d,\s]+)>;", src)[0].split(",")]
+    wide = [int(c) for c in re.findall(r"using WideClasses = std::integer_sequence<int,([\d,\s]+)>;", src)[0].split(",")]
+    assert tuple(classes) == el.CLASSES and wide == [c for c in classes if c <= ml.WIDE_MAX_COLUMNS] and wide[-1] == ml.WIDE_MAX_COLUMNS
+    assert "if constexpr (CM <= %d)" % el.EXACT_MAX in k2 and el.EXACT_MAX in classes
+    Ks = set(el.K_COLUMNS)
+    for c in classes[:-1]:                                                      # kmax + 1 <= c: K = c - 1 and K = c
+        assert {c - 1, c} <= Ks, c
+    assert {0, 1, 2, 3, classes[-1] - 1} <= Ks
+    assert [next(c for c in classes if k + 1 <= c) for k in el.MIXED_KMAX] == [24, 24, 32, 64] and set(classes) - {4, 8, 12, 16} == {24, 32, 64}
+    cols = by["columns"]
+    assert cols.calls[:len(el.K_COLUMNS)] == tuple((i,) for i in range(len(el.K_COLUMNS)))
+    assert [max(cols.jobs[i].K for i in call) for call in cols.calls[len(el.K_COLUMNS):]] == list(el.MIXED_KMAX)
+    assert all(min(cols.jobs[i].K for i in call) == 0 for call in cols.calls[len(el.K_COLUMNS):])
+    # ---- the constants of the body
+    assert len(re.findall(r"arg >= (-[\d.]+)\)", k2)) == 2 and set(re.findall(r"arg >= (-[\d.]+)\)", k2)) == {"%.1f" % el.EXP_CUT}
+    assert "any_live |= arg[i] >= %.1f;" % el.EXP_CUT in k2 and mr_exp_zero() > el.EXP_CUT
+    assert k2.count("t_sumk < 1e-8") == 2 and k2.count("if (mod) z[c] += 1e-8;") == 2 and el.RESCUE == 1e-8
+    assert k2.count("if (__ballot(fabs(x2) >= 1e-5)) ls2 = (fabs(x2) < 1e-5) ? ls2 : log(s2);") == 2 and el.LS2_SERIES == 1e-5
+    assert k2.count("if (wK > P.max_unif_ws) {") == 1
+    assert int(re.search(r"#define EM_DEPTH (\d+)", k2).group(1)) == ml.EM_DEPTH
+    # ---- which kernel a call runs
+    assert re.search(r"if \(!p\.any_m\) \{.{0,400}?launch_estep\(c, k2_estep_all_rounds<decltype\(cm\)::value>.{0,300}?return 0;\s*\}", src, re.S)
+    assert re.search(r"k\.wide \? with_column_class\(WideClasses\{\}, kmax \+ 1, \[&\]\(auto cm\) \{\s*launch_estep\(c, k2_estep_cs<", src)
+    assert 's.shrink = !(env_s && atoi(env_s) == 0);' in src and "any_m = any_m || job_fixed[j] == 0;" in src
+    for c in by.values():
+        small = False
+        for call in c.calls or (tuple(range(len(c.jobs))),):
+            jobs = [c.jobs[i] for i in call]
+            assert all(j.fixed for j in jobs) and not c.companion.fixed and c.companion.u == len(c.preps) - 1 and c.companion.K == 1
+            assert all(j.u < len(c.preps) - 1 for j in jobs)                     # the companion's UTR is its own
+            sel = [el.selection(env, jobs + ([c.companion] if comp else [])) for _n, comp, env in el.SHAPES]
+            kmax = max(1, max(j.K for j in jobs))
+            want_cs = kmax + 1 <= ml.WIDE_MAX_COLUMNS
+            small = small or want_cs
+            assert [s["kernel"] for s in sel] == ["k2_estep_all_rounds", "k2_estep", "k2_estep", "k2_estep_cs" if want_cs else "k2_estep", "k2_estep"]
+            assert [s["depth"] for s in sel[1:3]] == [1, ml.EM_DEPTH] and len({s["cls"] for s in sel}) == 1
+        assert small or c.name != "bins"
+    # ---- every family is there, T is the ladder's usual, N stays small
+    assert {c.family for c in by.values()} == set(range(1, 11))
+    assert all(q.N <= 257 and 200 <= q.T <= 230 for c in by.values() for q in c.preps)
+    assert {c.nround for c in by.values() if c.family == 10} == {2, 5, 10, 20}
+
+
+def mr_exp_zero():
+    from oracle import mstep_reference as mr
+    return mr.EXP_ZERO

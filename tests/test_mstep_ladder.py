@@ -12,12 +12,15 @@ once the 4-wavefront E-step - and per job:
     the other components are where they were;
   - in the random family an undecided job must return a row whose long-double score is within the two bounds of the maximum;
   - ws, bic, lb meet the per-call tolerances against the long-double values (ws rtol 1e-6 / atol 1e-10, bic 1e-9, lb 1e-9);
+  - ws, bic, lb of the decided jobs lie within the reference's derived bounds (fit.ws_bound / lb_bound / bic_bound: the
+    E-step chain of oracle/mstep_reference.py, some 1e5 times sharper than the tolerances; tests/test_estep_ladder.py);
   - all forms, and all calls that hold the job, return identical bits.
 Mismatches are collected and reported together.
 
 Measured on an MI355X (printed by every run; measurements, not targets): worst |device ws - reference| / tolerance
 9.9e-8 in every form (the forms are bit-equal); smallest decided gap / bound on the device's tensors 5.08e6 (case
-"bins"; the random family 1.39e7 with 4 of its 240 jobs undecided); the module takes about 3 s.
+"bins"; the random family 1.39e7 with 4 of its 240 jobs undecided); worst observed / E-step bound over ws, lb and bic of
+the decided jobs 0.275 (random family; 0.12 elsewhere); the module takes about 3.5 s.
 
 What the ladder found: the tie case "tiles of extent 0 and 16" failed in all eleven forms before k2_estep's reduction
 over the tiles learned the all-sentinel floor (em_lockstep.inc: rd_fl) - the rows of a dead component's window are tied
@@ -96,6 +99,7 @@ def _summary():
         for f in forms:
             print(f"  {f:<36s} {max(d['ws'].get(f, 0.0) for d in _MEASURED.values()):.3g}")
         print(f"[mstep ladder] smallest decided gap / bound on the device's tensors: {min(d['ratio'] for d in _MEASURED.values()):.3g}")
+        print(f"[mstep ladder] worst observed / E-step bound (ws, lb, bic of the decided jobs): {max(d['bound'] for d in _MEASURED.values()):.3g}")
 
 
 @pytest.mark.parametrize("name", [c.name for c in CASES])
@@ -125,7 +129,7 @@ def _run_case(case, ld):
         print(f"\n[mstep ladder] {case.name}: {len(undecided)} of {len(case.jobs)} jobs undecided on the device's tensor {undecided}")
         assert len(undecided) * 20 <= len(case.jobs)
     # ---- every call, every form
-    ws_worst, first_bits, kernels = {}, {}, set()
+    ws_worst, first_bits, kernels, bound_worst = {}, {}, set(), 0.0
     for n in case.calls or (len(case.jobs),):
         jobs = case.jobs[:n]
         for form, env in ml.FORMS:
@@ -163,9 +167,16 @@ def _run_case(case, ld):
                     problems.append(tag + ("lb", lb[i, :nlb[i]].tolist(), fit.lb.tolist()))
                 if not abs(float(bic[i]) - fit.bic) <= BIC_TOL * abs(fit.bic):
                     problems.append(tag + ("bic", float(bic[i]), fit.bic))
-    _MEASURED[case.name] = dict(ws=ws_worst, ratio=worst_ratio)
+                # the E-step's derived bounds (oracle/mstep_reference.py), where the reference's rows are the device's
+                if i not in undecided and int(nlb[i]) == len(fit.lb):
+                    obs = (float(np.max(np.abs(w - fit.ws) / fit.ws_bound)), float(np.max(np.abs(lb[i, :nlb[i]] - fit.lb) / fit.lb_bound)),
+                           abs(float(bic[i]) - fit.bic) / fit.bic_bound)
+                    bound_worst = max(bound_worst, max(obs))
+                    if not max(obs) <= 1:
+                        problems.append(tag + ("ws, lb, bic outside the E-step bounds: observed / bound", obs))
+    _MEASURED[case.name] = dict(ws=ws_worst, ratio=worst_ratio, bound=bound_worst)
     print(f"\n[mstep ladder] {case.name}: {len(case.jobs)} jobs, calls {case.calls or (len(case.jobs),)}, {len(ml.FORMS)} forms; "
           f"smallest decided gap / bound {worst_ratio:.3g}; worst |ws - reference| / tolerance {max(ws_worst.values()):.3g}; "
-          f"kernels {sorted(kernels)}")
+          f"worst observed / E-step bound {bound_worst:.3g}; kernels {sorted(kernels)}")
     assert {k[0] for k in kernels} == {"k2_mstep", "k3_mstep", "k4_mstep"} and {k[3] for k in kernels} == {False, True}
     assert not problems, f"{len(problems)} mismatches\n" + "\n".join(repr(p) for p in problems[:40])
