@@ -135,7 +135,8 @@ int scape_hip_batch_em_fetch_lb(scape_hip_ctx *ctx, int32_t n_sel, const int32_t
 /*
  * get_label (apa_core.py:873-881) for n_sel models: per-bin arg-max of the responsibilities.
  * labels_out is indexed like the batch's bins (bin_off of sel_utr[i]); only the bins of the
- * selected UTRs are written.
+ * selected UTRs are written.  The output holds one label per bin, so one call labels at most
+ * one model per UTR: a call that names a UTR twice is refused ("labels: a UTR is named twice").
  */
 int scape_hip_batch_labels(scape_hip_ctx *ctx, int32_t n_sel, int32_t kmax, const int32_t *sel_utr,
                            const int32_t *sel_K, const int32_t *alpha_idx, const int32_t *beta_idx,

@@ -1545,12 +1545,16 @@ static int em_jobs_check(const BatchState &b, int n_jobs, int kmax, const int32_
     return 0;
 }
 
-// The same for the model tables of scape_hip_batch_labels.
+// The same for the model tables of scape_hip_batch_labels.  The output is one label per bin of the batch: two models
+// of one UTR in one call would be two workgroups writing the same bins.
 static int labels_check(const BatchState &b, int n_sel, int kmax, const int32_t *sel_utr, const int32_t *sel_K,
                         const int32_t *alpha_idx, const int32_t *beta_idx) {
+    std::vector<char> named(b.n_utr, 0);
     for (int j = 0; j < n_sel; ++j) {
         const int u = sel_utr[j], K = sel_K[j];
         if (u < 0 || u >= b.n_utr) return fail("labels: bad UTR index");
+        if (named[u]) return fail("labels: a UTR is named twice");
+        named[u] = 1;
         if (K < 0 || K > kmax) return fail("labels: K out of range");
         for (int k = 0; k < K; ++k) {
             const int a = alpha_idx[(size_t)j * kmax + k], bi = beta_idx[(size_t)j * kmax + k];

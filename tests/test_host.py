@@ -869,6 +869,61 @@ def test_estep_ladder_covers_every_boundary_of_the_estep():
     assert {c.nround for c in by.values() if c.family == 10} == {2, 5, 10, 20}
 
 
+def test_label_ladder_covers_every_boundary_of_the_label_kernel():
+    """tests/test_label_ladder.py runs k_labels on the cases of tests/label_ladder.py.  The boundaries are read here from the
+    sources - LabelClasses, the 256 threads of the launch bounds, of the launch and so of the stride loop, the 64 lanes of
+    a wavefront, the 16-bin row pitch, the clamp of d_exp_nonpos, SCAPE_MAX_K - and the ladder must have a case on both
+    sides of each (whoever moves one has to move the ladder).  The reference's restatement of the pitch and the block is
+    pinned to the source here as well."""
+    import label_ladder as ll
+    from oracle import label_reference as lr
+    src = open(os.path.join(ROOT, "scape_amd", "csrc", "scape_hip.hip")).read()
+    hdr = open(os.path.join(ROOT, "include", "scape_hip.h")).read()
+    # ---- the column classes
+    classes = [int(c) for c in re.findall(r"using LabelClasses = std::integer_sequence<int,([\d,\s]+)>;", src)[0].split(",")]
+    max_k = int(re.search(r"#define\s+SCAPE_MAX_K\s+(\d+)", hdr).group(1))
+    assert tuple(classes) == ll.CLASSES and classes[-1] == max_k + 1 and ll.KMAX_PAD == max_k
+    Ks = set(ll.K_CLASSES)
+    for c in classes:                                             # kmax + 1 <= c: K = c - 2, c - 1 and (below the last) c
+        assert {c - 2, c - 1} <= Ks and (c == classes[-1] or c in Ks), c
+    assert {0, 1} <= Ks
+    by = {c.name: c for c in ll.cases()}
+    assert [m.K for m in by["classes"].models] == list(ll.K_CLASSES) and by["classes"].calls == tuple((i,) for i in range(len(Ks)))
+    assert all(ll.pitches(by["classes"], call) == ((max(1, by["classes"].models[call[0]].K), max_k) if by["classes"].models[call[0]].K != max_k
+                                                    else (max_k,)) for call in by["classes"].calls)
+    edge = {c for _K, c0, c1 in ll.PLANT_PAIRS for c in (c0, c1)}
+    for c in classes[:-1]:                                        # planted and tied pairs straddle every class edge: columns c - 1 and c
+        assert {c - 1, c} <= edge and any((c0, c1) == (c - 1, c) for _K, c0, c1 in ll.PLANT_PAIRS), c
+        assert any((c0, c1) == (c - 1, c) for _K, c0, c1 in ll.TIE_PAIRS), c
+    assert (max_k, max_k - 1, max_k) in ll.PLANT_PAIRS and {K for K, _c0, c1 in ll.PLANT_PAIRS if c1 == K} >= {1, 7, 8, 16, 32, max_k}
+    # ---- the 256 threads: launch bounds, launch, stride loop; the 64 lanes
+    assert re.search(r"__global__ __launch_bounds__\((\d+)\) void k_labels\(", src).group(1) == str(ll.BLOCK)
+    assert re.search(r"hipLaunchKernelGGL\(k_labels<decltype\(cm\)::value>, dim3\(n_sel\), dim3\((\d+)\)", src).group(1) == str(ll.BLOCK)
+    body = src[src.index("void k_labels("):src.index("// host side")]
+    assert "for (int n = threadIdx.x; n < d.N; n += blockDim.x) {" in body and "labels[d.bin_off + n] = best;" in body
+    assert lr.BLOCK == ll.BLOCK and lr.PITCH == ll.PITCH
+    Ns = set(ll.N_BINS)
+    for b in (ll.PITCH, 64, ll.BLOCK):
+        assert {b - 1, b, b + 1} <= Ns, b
+    assert {1, 2 * ll.BLOCK + 1} <= Ns and max(Ns) == 2 * ll.BLOCK + 1
+    assert ll.PLANT_BINS == (0, ll.BLOCK - 1, ll.BLOCK) and ll.PLANT_N == ll.BLOCK + 1
+    assert {ll.BLOCK + 1, 2 * ll.BLOCK + 1} <= set(ll.CALL_N) and any(n % ll.PITCH == 0 for n in ll.CALL_N)
+    # ---- the row pitch
+    assert int(re.search(r"#define PITCH (\d+)\b", src).group(1)) == ll.PITCH and "d.Np = round_up((int)N, PITCH);" in src
+    assert "* B + b_in[(size_t)sel * kmax + c]) * d.Np : 0;" in body and "d_logw(ws_in[(size_t)sel * (kmax + 1) + c])" in body
+    assert any(n % ll.PITCH for n in Ns) and any(n % ll.PITCH == 0 for n in Ns)
+    # ---- the clamp of d_exp_nonpos, the counts on both sides of it (tests/test_label_reference.py looks at the arguments)
+    assert "x = fmax(x, %.1f);" % ll.EXP_CLAMP in src and "d_exp_nonpos((lz[c] - mx) * cn, s_exptab)" in body
+    assert ll.COUNT_MAX == 1000 and by["counts"].preps[0].cnt.max() == ll.COUNT_MAX and by["counts"].preps[0].cnt[ll.COUNT_BIN] == ll.COUNT_MAX
+    # ---- the first maximum, the zero weight, the refusal
+    assert "if (c < C && (c == 0 || zc > bz)) {" in body and "return (w <= 0.0) ? SENT : log(w); }" in src
+    assert 'return fail("labels: a UTR is named twice");' in src and "a UTR is named twice" in hdr
+    # ---- every family is there, T is the ladder's usual, the tensors stay small
+    assert list(by) == ["bins", "classes", "planted", "ties", "counts", "calls"]
+    assert all(q.N <= 2 * ll.BLOCK + 1 and 200 <= q.T <= 230 and len(q.betas) == 13 for c in by.values() for q in c.preps)
+    assert all(len({by[n].models[i].u for i in call}) == len(call) for n in by for call in by[n].calls)   # one model per UTR and call
+
+
 def mr_exp_zero():
     from oracle import mstep_reference as mr
     return mr.EXP_ZERO
