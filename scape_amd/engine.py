@@ -20,7 +20,11 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-from dataclasses import dataclass, field
+import sys
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
+from itertools import groupby
+from time import perf_counter
 
 import numpy as np
 
@@ -79,16 +83,21 @@ class PackedJobs:
         return self.a.shape[1]
 
 
-def pack_jobs(jobs):
-    n = len(jobs)
-    kmax = max(1, max(j.K for j in jobs))
-    a = np.zeros((n, kmax), dtype=np.int32)
-    b = np.zeros((n, kmax), dtype=np.int32)
+def pack_models(fits):
+    """(K, alpha index, beta index, ws) of a list of Fit (or _Job) as padded tables."""
+    n, kmax = len(fits), max(1, max(f.K for f in fits))
+    a, b = np.zeros((n, kmax), dtype=np.int32), np.zeros((n, kmax), dtype=np.int32)
     w = np.zeros((n, kmax + 1), dtype=np.float64)
-    ka = np.zeros((n, N_ROUND), dtype=np.int8)
-    for i, j in enumerate(jobs):
-        a[i, :j.K], b[i, :j.K], w[i, :j.K + 1], ka[i] = j.a_idx, j.b_idx, j.ws, j.k_arr
-    return PackedJobs(i32([j.u for j in jobs]), i32([j.K for j in jobs]), i32([int(j.fixed) for j in jobs]), a, b, w, ka)
+    for i, f in enumerate(fits):
+        a[i, :f.K], b[i, :f.K], w[i, :f.K + 1] = f.a_idx, f.b_idx, f.ws
+    return i32([f.K for f in fits]), a, b, w
+
+
+def pack_jobs(jobs):
+    jk, a, b, w = pack_models(jobs)
+    ka = np.zeros((len(jobs), N_ROUND), dtype=np.int8)
+    ka[:] = [j.k_arr for j in jobs]
+    return PackedJobs(i32([j.u for j in jobs]), jk, i32([int(j.fixed) for j in jobs]), a, b, w, ka)
 
 
 def concat_packed(packs):
@@ -105,6 +114,30 @@ def concat_packed(packs):
         lo = hi
     cat = lambda name: np.concatenate([getattr(p, name) for p in packs])   # noqa: E731
     return PackedJobs(cat("ju"), cat("jk"), cat("jf"), a, b, w, cat("ka"))
+
+
+# ---- the reference's model-selection rules, once each -------------------------------------------------
+def sweep_winners(bic, spans):
+    """Row of the BIC winner of every UTR's K sweep.  Rows spans[u]:spans[u+1] of `bic` are UTR u's jobs: K descending,
+    N_TRIAL restarts per K.  The reference's bic_arr is np.full(n, np.finfo('f').max), a float32 array (apa_core.py:849,
+    :945), so both arg-mins compare BICs rounded to f32 (ties -> first; above the f32 range -> inf): em_optim0 over
+    the restarts of a K (:865), then run over K (:972).  The BIC at em_optim0's arg-min is the minimum of the K's
+    restarts, so the winning K comes first and the restart arg-min is taken in that K alone."""
+    U = len(spans) - 1
+    if U > 1 and np.any(np.diff(spans) != spans[1] - spans[0]):          # ragged spans: UTR by UTR
+        return np.concatenate([sweep_winners(bic, spans[u:u + 2]) for u in range(U)])
+    with np.errstate(over="ignore"):
+        grid = bic[spans[0]:spans[-1]].astype(np.float32).reshape(U, -1, N_TRIAL)
+    kb = grid.min(axis=2).argmin(axis=1)
+    tb = grid[np.arange(U), kb].argmin(axis=1)
+    return np.asarray(spans[:-1], dtype=np.int64) + kb * N_TRIAL + tb
+
+
+def kept_components(ws, K, min_ws):
+    """rm_component (apa_core.py:836-839): which of the first K components stay, as a mask over the columns of `ws`
+    (one model, or rows of models with K and min_ws per row).  Deliberately not `ws >= min_ws`: a NaN weight stays,
+    as in the reference.  A model needs the prune re-fit when fewer than K stay."""
+    return (np.arange(ws.shape[-1]) < np.asarray(K)[..., None]) & ~(ws < np.asarray(min_ws)[..., None])
 
 
 class HipBatch:
@@ -225,18 +258,7 @@ class HipBatch:
         """sel: list of (u, Fit) -> dict u -> int32 labels per bin (get_label, :873-881)."""
         if not sel:
             return {}
-        n = len(sel)
-        kmax = max(1, max(f.K for _, f in sel))
-        su = i32([u for u, _ in sel])
-        sk = i32([f.K for _, f in sel])
-        a = np.zeros((n, kmax), dtype=np.int32)
-        b = np.zeros((n, kmax), dtype=np.int32)
-        w = np.zeros((n, kmax + 1), dtype=np.float64)
-        for i, (_, f) in enumerate(sel):
-            a[i, :f.K], b[i, :f.K], w[i, :f.K + 1] = f.a_idx, f.b_idx, f.ws
-        out = np.full(self.n_bins, -1, dtype=np.int32)
-        check(self.lib.scape_hip_batch_labels(self.ctx.h, n, kmax, ptr(su, P_i32), ptr(sk, P_i32), ptr(a, P_i32),
-                                              ptr(b, P_i32), ptr(w), ptr(out, P_i32)), "batch_labels")
+        out = self.labels_packed([u for u, _ in sel], *pack_models([f for _, f in sel]))
         return {u: out[self.bin_off[u]:self.bin_off[u + 1]].copy() for u, _ in sel}
 
     def labels_packed(self, su, sk, a, b, w):
@@ -285,10 +307,12 @@ class _Sweep:
         self.trace = trace
         self.pred = None        # Engine._predict_outcomes: None / "clean" / ("prune", K') / "stop" - a guess, never a result
 
+    def kept(self):
+        """rm_component (:836-839): indices of the components of the current best fit that stay."""
+        return np.nonzero(kept_components(self.best.ws, self.best.K, self.prep.p["min_ws"]))[0]
+
     def prune_K(self):
-        """K' of rm_component (:836-839): components of the current best fit that stay."""
-        f = self.best
-        return int(np.count_nonzero(~(f.ws[:f.K] < self.prep.p["min_ws"])))
+        return len(self.kept())
 
     def make_jobs(self, predrawn=None):
         """predrawn = (init_ws table, k_arr) of the prune re-fit when they were drawn ahead (Engine._drive_streams)."""
@@ -300,8 +324,7 @@ class _Sweep:
                     a, b, w, ka = self.sampler.init_job(q, K)
                     jobs.append(_Job(self.u, K, False, a, b, w, ka))
         elif self.stage == "prune":                     # rm_component -> fixed_inference (:843, :708-711)
-            f = self.best
-            keep = np.array([i for i in range(f.K) if not f.ws[i] < q.p["min_ws"]], dtype=int)
+            f, keep = self.best, self.kept()
             Kp = len(keep)
             if Kp == 0:
                 _no_component_left(q)
@@ -315,17 +338,14 @@ class _Sweep:
         return jobs
 
     def make_packed(self, tables=None, predrawn=None):
-        """make_jobs as padded tables (one native call per sweep, engine._drive's fast path); `tables` = the
-        sweep tables when they were drawn together with other streams' (make_packed_many)."""
-        q = self.prep
-        if predrawn is not None:
-            return pack_jobs(self.make_jobs(predrawn))
-        if self.stage == "sweep" and hasattr(self.sampler, "sweep"):
-            jk, a, b, w, ka = tables if tables is not None else self.sampler.sweep(q, self.n_max, self.n_min)
+        """make_jobs as padded tables (one native call per sweep); `tables` = the sweep tables when they were drawn
+        together with other streams' (make_packed_many)."""
+        if predrawn is None and self.stage == "sweep" and hasattr(self.sampler, "sweep"):
+            jk, a, b, w, ka = tables if tables is not None else self.sampler.sweep(self.prep, self.n_max, self.n_min)
             n = len(jk)
             self.n_jobs += n
             return PackedJobs(np.full(n, self.u, np.int32), jk, np.zeros(n, np.int32), a, b, w, ka)
-        return pack_jobs(self.make_jobs())
+        return pack_jobs(self.make_jobs(predrawn))
 
     @staticmethod
     def make_packed_many(sweeps):
@@ -339,46 +359,17 @@ class _Sweep:
         return [sw.make_packed(by.get(i)) for i, sw in enumerate(sweeps)]
 
     def absorb_packed(self, pj, out, lo, hi):
-        """absorb for rows [lo, hi) of a packed EM result: only the winner becomes a Fit."""
+        """Take in rows [lo, hi) of a packed EM result - this sweep's jobs: only the winner becomes a Fit (every row
+        does when the sweep keeps a trace)."""
+        if self.trace is not None:
+            self.trace.extend(HipBatch.fit_at(pj, out, i) for i in range(lo, hi))
         if self.stage == "sweep":
-            with np.errstate(over="ignore"):
-                grid = out[3][lo:hi].astype(np.float32).reshape(-1, N_TRIAL)     # float32 bic_arr (:849, :945)
-            tb = np.argmin(grid, axis=1)                                         # em_optim0 (:865)
-            kb = int(np.argmin(grid[np.arange(len(tb)), tb]))                    # run (:972)
-            self.best = HipBatch.fit_at(pj, out, lo + kb * N_TRIAL + int(tb[kb]))
-            if not self.prep.fixed_run and np.any(self.best.ws[:self.best.K] < self.prep.p["min_ws"]):
+            self.best = HipBatch.fit_at(pj, out, int(sweep_winners(out[3], (lo, hi))[0]))
+            if not self.prep.fixed_run and self.prune_K() < self.best.K:
                 self.stage = "prune"
                 return
         elif self.stage == "prune":
             self.best = HipBatch.fit_at(pj, out, lo)
-        self._after_fit()
-
-    def absorb(self, fits):
-        q = self.prep
-        if self.trace is not None:
-            self.trace.extend(fits)
-        if self.stage == "sweep":
-            per_k = []
-            for i in range(0, len(fits), N_TRIAL):      # em_optim0: first arg-min BIC over trials (:865)
-                grp = fits[i:i + N_TRIAL]
-                # bic_arr is np.full(n, np.finfo('f').max): a float32 array (:849, :945), so both
-                # arg-mins compare BICs rounded to f32 (ties -> first)
-                per_k.append(grp[int(np.argmin(np.array([f.bic for f in grp], dtype=np.float32)))])
-            self.best = per_k[int(np.argmin(np.array([f.bic for f in per_k], dtype=np.float32)))]     # (:972)
-            if not q.fixed_run and any(self.best.ws[i] < q.p["min_ws"] for i in range(self.best.K)):
-                self.stage = "prune"
-                return
-        elif self.stage == "prune":
-            self.best = fits[0]
-        self._after_fit()
-
-    def set_sweep_winner(self, best, n_jobs):
-        """Entry for the vectorised selection: the sweep's BIC winner is already known."""
-        self.best = best
-        self.n_jobs += n_jobs
-        if not self.prep.fixed_run and any(best.ws[i] < self.prep.p["min_ws"] for i in range(best.K)):
-            self.stage = "prune"
-            return
         self._after_fit()
 
     def _after_fit(self):
@@ -387,7 +378,6 @@ class _Sweep:
             if self.n_max + 2 > _lib.MAX_K:
                 # the reference grows n_max_apa without bound (:1023-1030); the kernels hold K <= MAX_K components.
                 # Only this UTR stops re-running - the other UTRs of the wave and file are unaffected.
-                import sys
                 sys.stderr.write(f"scape_amd: {self.prep.gene_info_str}: K reached n_max_apa={self.n_max} and the "
                                  f"next sweep would exceed the library's K <= {_lib.MAX_K}; keeping K={self.best.K} "
                                  "(the reference would re-run with n_max_apa + 2)\n")
@@ -398,6 +388,65 @@ class _Sweep:
             self.stage = "sweep"
             return
         self.done = True
+
+
+@dataclass
+class _FileStream:
+    """One stream of run_streams_rolling: a chunk file's UTRs, its generator, and how far its UTRs have been handed out."""
+    tag: object
+    preps: list
+    sampler: FastSampler
+    results: list
+    cursor: int = 0
+
+
+def compose_wave(active, per_stream, budget, full):
+    """The next wave of run_streams_rolling (no device involved): the next UTRs of the streams in `active`, round-robin,
+    at most `per_stream` of each, until their tensors pass `budget` bytes (the first UTR is taken even then) or the wave
+    holds 65535 UTRs; a UTR above `full`, the device's limit, raises.  Moves the cursors and returns [(stream, index)],
+    streams in the order of `active`, each stream's UTRs contiguous and in file order."""
+    first, n, used = [st.cursor for st in active], 0, 0
+    for _turn in range(per_stream):
+        took = False
+        for st in active:
+            if st.cursor >= len(st.preps) or n >= 65535:
+                continue
+            bts = Engine.utr_bytes(st.preps[st.cursor])
+            if bts > full:
+                raise _lib.ScapeHipError("a UTR's marginal tensor exceeds device memory")
+            if n and used + bts > budget:
+                took = False              # the budget is reached: the wave is closed
+                break
+            st.cursor += 1
+            n, used, took = n + 1, used + bts, True
+        if not took:
+            break
+    return [(st, i) for st, lo in zip(active, first) for i in range(lo, st.cursor)]
+
+
+@dataclass
+class _Stream:
+    """One stream of _drive_streams: a generator, its sweeps in file order, and how many of them are finished."""
+    sampler: FastSampler
+    sweeps: list
+    cursor: int = 0
+
+
+@dataclass
+class _PreparedCall:
+    """The drawn tables of one EM call of the stream driver (Engine._streams_prepare); per stream of `streams`:"""
+    streams: list
+    pj: PackedJobs
+    chains: list      # the sweeps that ride in the call (the head and its followers)
+    packs: list       # their job tables, in the order of pj's rows
+    marks: list       # generator state after each sweep's own draws (depth > 1)
+    ahead: list       # prune tables drawn ahead: (K', init_ws, k_arr) or None
+
+    def forget(self):
+        """The call is never submitted: the sweeps forget the jobs they were handed."""
+        for ch, ps in zip(self.chains, self.packs):
+            for sw, pk in zip(ch, ps):
+                sw.n_jobs -= len(pk)
 
 
 class Engine:
@@ -492,16 +541,21 @@ class Engine:
                     self._finish_deferred(batch, deferred)
                 else:
                     self._drive(batch, sweeps)
-                labs = batch.labels([(sw.u, sw.best) for sw in sweeps])
-                out = [(sw.best, labs[sw.u], sw.n_jobs) for sw in sweeps]
+                self._collect(batch, sweeps, [results[gi] for gi in wave])
             else:
                 plan = self.plan(wp, [seeds[gi] for gi in wave])
-                out = self.process(batch, wp, plan, re_run_mode)
-            for (fit, lab, nj), gi in zip(out, wave):
-                results[gi].fit, results[gi].labels_bin, results[gi].n_jobs = fit, lab, nj
+                for (fit, lab, nj), gi in zip(self.process(batch, wp, plan, re_run_mode), wave):
+                    results[gi].fit, results[gi].labels_bin, results[gi].n_jobs = fit, lab, nj
         if shared is not None:
             shared.rs                      # hand the advanced stream back to the caller's RandomState
         return results
+
+    @staticmethod
+    def _collect(batch, sweeps, results):
+        """Finished sweeps of a wave -> results[k] of sweeps[k]: their labels (one call), then fit, labels, job count."""
+        labs = batch.labels([(sw.u, sw.best) for sw in sweeps])
+        for sw, r in zip(sweeps, results):
+            r.fit, r.labels_bin, r.n_jobs = sw.best, labs[sw.u], sw.n_jobs
 
     # ---- several reference-RNG streams at once (one stream = one chunk file) --------------------------
     def run_streams(self, streams, re_run_mode=True):
@@ -532,64 +586,36 @@ class Engine:
         `stream_wave_utrs` per stream and `stream_wave_bytes` of tensors in all."""
         full = self._budget()
         budget = min(full, Engine.stream_wave_bytes)
-        active = []       # [tag, preps, sampler, cursor, results]
+        active = []       # _FileStream, in the order of admission
         while active or more():
             room = streams_in_flight - len(active)
             if room > 0 and more():
                 for tag, preps, seed in take(not active, room):
-                    st = [tag, preps, FastSampler(np.random.RandomState(seed)), 0, [UtrResult(prep=q) for q in preps]]
                     if len(preps):
-                        active.append(st)
+                        active.append(_FileStream(tag, preps, FastSampler(np.random.RandomState(seed)),
+                                                  [UtrResult(prep=q) for q in preps]))
                     else:
                         on_done(tag, [])
             if not active:
                 continue
-            wave, used, stop = [], 0, False           # (stream, index within the stream), stream-major order below
             per_stream = max(Engine.stream_wave_utrs, -(-Engine.stream_wave_min // len(active)))
-            for turn in range(per_stream):
-                took = False
-                for st in active:
-                    i = st[3]
-                    if i >= len(st[1]) or len(wave) >= 65535:
-                        continue
-                    bts = self.utr_bytes(st[1][i])
-                    if bts > full:
-                        raise _lib.ScapeHipError("a UTR's marginal tensor exceeds device memory")
-                    if wave and used + bts > budget:
-                        stop = True
-                        break
-                    wave.append((st, i))
-                    st[3] = i + 1
-                    used += bts
-                    took = True
-                if stop or not took:
-                    break
-            wave.sort(key=lambda e: (id(e[0]), e[1]))     # each stream's UTRs contiguous and in file order
-            preps = [st[1][i] for st, i in wave]
+            wave = compose_wave(active, per_stream, budget, full)
+            preps = [st.preps[i] for st, i in wave]
             batch = HipBatch(self.ctx, preps)
             batch.build()
-            queues, wave_sweeps = {}, []
-            for u, (st, _i) in enumerate(wave):
-                wave_sweeps.append(_Sweep(u, preps[u], st[2], re_run_mode))
-                queues.setdefault(id(st), (st, []))[1].append(wave_sweeps[-1])
+            sweeps = [_Sweep(u, preps[u], st.sampler, re_run_mode) for u, (st, _i) in enumerate(wave)]
+            streams = [(smp, list(sws)) for smp, sws in groupby(sweeps, key=lambda sw: sw.sampler)]
             done_sweeps, deferred = [], []
-            depth = self._stream_depth(len(queues))
+            depth = self._stream_depth(len(streams))
             if depth > 1:
-                self._predict_outcomes(batch, preps, wave_sweeps, re_run_mode)
-            self._drive_streams(batch, [(st[2], q) for st, q in queues.values()], deferred, done_sweeps.append, depth=depth)
+                self._predict_outcomes(batch, preps, sweeps, re_run_mode)
+            self._drive_streams(batch, streams, deferred, done_sweeps.append, depth=depth)
             self._finish_deferred(batch, deferred)
-            labs = batch.labels([(sw.u, sw.best) for sw in done_sweeps])
-            for sw in done_sweeps:
-                st, i = wave[sw.u]
-                r = st[4][i]
-                r.fit, r.labels_bin, r.n_jobs = sw.best, labs[sw.u], sw.n_jobs
-            still = []
+            self._collect(batch, done_sweeps, [st.results[i] for st, i in (wave[sw.u] for sw in done_sweeps)])
             for st in active:
-                if st[3] < len(st[1]):
-                    still.append(st)
-                else:
-                    on_done(st[0], st[4])
-            active = still
+                if st.cursor >= len(st.preps):
+                    on_done(st.tag, st.results)
+            active = [st for st in active if st.cursor < len(st.preps)]
 
     # ---- fully batched path (per-UTR RNG): pre-drawn job tables + vectorised selection -------------
     @staticmethod
@@ -688,8 +714,7 @@ class Engine:
     def process(self, batch, preps, plan, re_run_mode=True, build=True, labels=True):
         """One pass of the hot path over a resident batch: Phase A/B, the main EM sweep, BIC model
         selection, prune re-fits, re-run sweeps and labels.  Returns [(Fit, labels_bin, n_jobs)]."""
-        from time import perf_counter as _now
-        t0 = _now()
+        t0 = perf_counter()
         pj, spans = plan["main"], plan["spans"]
         # engines that share a device take turns for the long kernels (two EM sweeps at once only slow each
         # other down); uploads, host-side selection and the short re-fit launches overlap freely
@@ -697,44 +722,43 @@ class Engine:
         if build:
             batch.build()        # queued, not awaited: the EM call's host-side table checks run while the GPU builds
         with (self.sweep_lock if self.sweep_lock is not None else contextlib.nullcontext()):
-            out = batch.em_packed(pj, reuse_buffers=True, want_lb=False)   # lb rows of the BIC winners only, below
+            out = batch.em_packed(pj, reuse_buffers=True, want_lb=False)   # lb rows of the BIC winners only (_select)
             self.last_main_em_ms = batch.timing(2)[0] - ms0          # HIP-event time of the sweep launch
         self.last_main_counters = batch.em_counters()
-        t1 = _now()
-        ao, bo, wo, bic, nlb, lb = out
-        U = len(preps)
-        # ---- em_optim0 (:865) + run (:972): first arg-min BIC over restarts, then over K (desc) ----
-        njobs = np.diff(spans)
-        with np.errstate(over="ignore"):
-            bic32 = bic.astype(np.float32)      # the reference's bic_arr is float32 (:849, :945)
-        if np.all(njobs == njobs[0]):
-            nk = int(njobs[0]) // N_TRIAL
-            grid = bic32.reshape(U, nk, N_TRIAL)
-            tb = np.argmin(grid, axis=2)
-            kb = np.argmin(np.take_along_axis(grid, tb[:, :, None], axis=2)[:, :, 0], axis=1)
-            win = spans[:-1] + kb * N_TRIAL + tb[np.arange(U), kb]
-        else:
-            win = np.zeros(U, dtype=np.int64)
-            for u in range(U):
-                lo, hi = int(spans[u]), int(spans[u + 1])
-                g = bic32[lo:hi].reshape(-1, N_TRIAL)
-                tbu = np.argmin(g, axis=1)
-                kbu = int(np.argmin(g[np.arange(len(tbu)), tbu]))
-                win[u] = lo + kbu * N_TRIAL + int(tbu[kbu])
-        lb_win = batch.em_fetch_lb(win)             # Parameters.lb_arr of every UTR's winner (:972), before any other EM call
-        Kw = pj.jk[win].astype(np.int64)
-        min_ws = np.array([q.p["min_ws"] for q in preps])
-        n_max = np.array([q.p["n_max_apa"] for q in preps])
-        comp = np.arange(pj.kmax)[None, :] < Kw[:, None]
-        needs_prune = np.any((wo[win, :pj.kmax] < min_ws[:, None]) & comp, axis=1)
-        fits = [None] * U
-        njob_out = njobs.astype(np.int64).copy()
-        # ---- rm_component (:832-844): ws-only re-fit of the kept components, all pruned UTRs in one launch
-        pu = np.nonzero(needs_prune)[0]
-        refit = {}
+        t1 = perf_counter()
+        win, lb_win = self._select(batch, out, spans)
+        winner = lambda u: HipBatch.fit_at(pj, out, int(win[u]), lb_win[u])   # noqa: E731
+        n_jobs = np.diff(spans).astype(np.int64)
+        fits, K = self._prune_refits(batch, preps, plan, out, win, n_jobs)   # fits[u] is None: UTR u keeps its winner
+        if re_run_mode:
+            self._rerun(batch, preps, plan, K, winner, fits, n_jobs)
+        t2 = perf_counter()
+        flat = self._label_tables(batch, pj, out, win, fits) if labels else None
+        t3 = perf_counter()
+        res = [(fits[u] if fits[u] is not None else winner(u),
+                flat[batch.bin_off[u]:batch.bin_off[u + 1]] if labels else None, int(n_jobs[u])) for u in range(len(preps))]
+        if labels:
+            self.last_host_ms = dict(build_em=(t1 - t0) * 1e3, select_prune=(t2 - t1) * 1e3, labels=(t3 - t2) * 1e3,
+                                     collect=(perf_counter() - t3) * 1e3)
+        return res
+
+    @staticmethod
+    def _select(batch, out, spans):
+        """em_optim0 (:865) + run (:972): the row of every UTR's sweep winner, and the winners' Parameters.lb_arr -
+        fetched before any other EM call (the rows stay on the device after a want_lb=False call)."""
+        win = sweep_winners(out[3], spans)
+        return win, batch.em_fetch_lb(win)
+
+    @staticmethod
+    def _prune_refits(batch, preps, plan, out, win, n_jobs):
+        """rm_component (:832-844): ws-only re-fit of the kept components, all pruned UTRs in one launch, from the
+        tables the plan drew for their K'.  Returns (the re-fit per UTR, None where nothing was pruned; K per UTR)."""
+        pj, (ao, bo, wo), fits = plan["main"], out[:3], [None] * len(preps)
+        keep = kept_components(wo[win, :pj.kmax], pj.jk[win], np.array([q.p["min_ws"] for q in preps]))
+        K = keep.sum(axis=1)
+        pu = np.nonzero(K < pj.jk[win])[0]
         if len(pu):
-            keep = comp[pu] & ~(wo[win[pu], :pj.kmax] < min_ws[pu, None])
-            Kp = keep.sum(axis=1)
+            keep, Kp = keep[pu], K[pu]
             if np.any(Kp == 0):
                 _no_component_left(preps[int(pu[int(np.argmin(Kp))])])
             order = np.argsort(~keep, axis=1, kind="stable")              # kept components first, in order
@@ -746,64 +770,49 @@ class Engine:
             rka = np.ascontiguousarray(plan["prune_ka"][pu, Kp])
             rpj = PackedJobs(i32(pu), i32(Kp), np.ones(len(pu), dtype=np.int32), ra, rb, rw, rka)
             rout = batch.em_packed(rpj)
-            njob_out[pu] += 1
+            n_jobs[pu] += 1
             for i, u in enumerate(pu):
-                refit[int(u)] = (rpj, rout, i)
-        # ---- re-run rule (:1023-1030): K hit the cap -> continue that UTR with the generic state machine
+                fits[u] = HipBatch.fit_at(rpj, rout, i)
+        return fits, K
+
+    @staticmethod
+    def _rerun(batch, preps, plan, K, winner, fits, n_jobs):
+        """Re-run rule (:1023-1030): a UTR whose K hit n_max_apa goes on with the generic state machine, its generator
+        where the plan's draws left it (after the sweep, or after the prune tables of its K')."""
         sweeps = []
-        if re_run_mode:
-            Kfin = Kw.copy()
-            if len(pu):
-                Kfin[pu] = Kp
-            for u in np.nonzero(Kfin == n_max)[0]:
-                u = int(u)
-                rs = np.random.RandomState(0)
-                if u in refit:
-                    rpj, rout, i = refit.pop(u)
-                    best = batch.fit_at(rpj, rout, i)
-                    rs.set_state(_hostlib.state_to_numpy(plan["prune_states"][u][best.K]))
-                else:
-                    best = batch.fit_at(pj, out, int(win[u]), lb_win[u])
-                    rs.set_state(_hostlib.state_to_numpy(plan["states"][u]))
-                sw = _Sweep(u, preps[u], FastSampler(rs), re_run_mode)
-                sw.best, sw.n_jobs = best, int(njob_out[u])
-                sw._after_fit()
-                sweeps.append(sw)
-            self._drive(batch, [sw for sw in sweeps if not sw.done])
-            for sw in sweeps:
-                fits[sw.u], njob_out[sw.u] = sw.best, sw.n_jobs
-        for u, (rpj, rout, i) in refit.items():
-            fits[u] = batch.fit_at(rpj, rout, i)
-        t2 = _now()
-        if not labels:
-            return [(fits[u] if fits[u] is not None else batch.fit_at(pj, out, int(win[u]), lb_win[u]), None, int(njob_out[u]))
-                    for u in range(U)]
-        # ---- labels for every UTR (get_label, :873-881) -------------------------------------------
-        kmax_f = max(1, int(Kw.max()), max((f.K for f in fits if f is not None), default=1))
-        la = np.zeros((U, kmax_f), dtype=np.int32)
-        lbi = np.zeros((U, kmax_f), dtype=np.int32)
+        for u in np.nonzero(K == np.array([q.p["n_max_apa"] for q in preps]))[0]:
+            u = int(u)
+            pruned = fits[u] is not None
+            rs = np.random.RandomState(0)
+            rs.set_state(_hostlib.state_to_numpy(plan["prune_states"][u][K[u]] if pruned else plan["states"][u]))
+            sw = _Sweep(u, preps[u], FastSampler(rs), True)
+            sw.best, sw.n_jobs = fits[u] if pruned else winner(u), int(n_jobs[u])
+            sw._after_fit()
+            sweeps.append(sw)
+        Engine._drive(batch, [sw for sw in sweeps if not sw.done])
+        for sw in sweeps:
+            fits[sw.u], n_jobs[sw.u] = sw.best, sw.n_jobs
+
+    @staticmethod
+    def _label_tables(batch, pj, out, win, fits):
+        """get_label (:873-881) for every UTR: the winners' models straight from the result arrays, the re-fitted and
+        re-run ones from their Fit.  Returns the flat label array of the batch."""
+        (ao, bo, wo), U, lk = out[:3], len(win), i32(pj.jk[win])
+        changed = [u for u in range(U) if fits[u] is not None]
+        kmax_f = max(1, int(lk.max()), max((fits[u].K for u in changed), default=1))
+        la, lbi = np.zeros((U, kmax_f), dtype=np.int32), np.zeros((U, kmax_f), dtype=np.int32)
         lw = np.zeros((U, kmax_f + 1), dtype=np.float64)
-        lk = Kw.astype(np.int32).copy()
         m = min(kmax_f, pj.kmax)
         la[:, :m], lbi[:, :m] = ao[win, :m], bo[win, :m]
         lw[:, :m + 1] = wo[win, :m + 1]
-        for u, f in enumerate(fits):
-            if f is not None:
-                lk[u] = f.K
-                la[u], lbi[u], lw[u] = 0, 0, 0.0
-                la[u, :f.K], lbi[u, :f.K], lw[u, :f.K + 1] = f.a_idx, f.b_idx, f.ws
+        if changed:
+            k, a, b, w = pack_models([fits[u] for u in changed])
+            lk[changed] = k
+            la[changed], lbi[changed], lw[changed] = 0, 0, 0.0
+            la[changed, :a.shape[1]], lbi[changed, :a.shape[1]], lw[changed, :w.shape[1]] = a, b, w
         la[la < 0] = 0
         lbi[lbi < 0] = 0
-        flat = batch.labels_packed(np.arange(U, dtype=np.int32), lk, la, lbi, lw)
-        t3 = _now()
-        res = []
-        for u in range(U):
-            f = fits[u] if fits[u] is not None else batch.fit_at(pj, out, int(win[u]), lb_win[u])
-            res.append((f, flat[batch.bin_off[u]:batch.bin_off[u + 1]], int(njob_out[u])))
-        t4 = _now()
-        self.last_host_ms = dict(build_em=(t1 - t0) * 1e3, select_prune=(t2 - t1) * 1e3, labels=(t3 - t2) * 1e3,
-                                 collect=(t4 - t3) * 1e3)
-        return res
+        return batch.labels_packed(np.arange(U, dtype=np.int32), lk, la, lbi, lw)
 
     @staticmethod
     def _defer_prunes(sweeps, deferred):
@@ -822,16 +831,20 @@ class Engine:
         return rest
 
     @staticmethod
-    def _finish_deferred(batch, deferred):
-        if not deferred:
-            return
-        pj = concat_packed([pk for _sw, pk in deferred])
+    def _em_absorb(batch, sweeps, packs):
+        """One EM call over the job tables packs[k] of sweeps[k]; every sweep takes in its own rows."""
+        pj = concat_packed(packs)
         out = batch.em_packed(pj)
         lo = 0
-        for sw, pk in deferred:
+        for sw, pk in zip(sweeps, packs):
             sw.absorb_packed(pj, out, lo, lo + len(pk))
             lo += len(pk)
-        deferred.clear()
+
+    @staticmethod
+    def _finish_deferred(batch, deferred):
+        if deferred:
+            Engine._em_absorb(batch, *zip(*deferred))
+            deferred.clear()
 
     # ---- the exact-stream modes: UTRs of one random stream, several per EM call --------------------------
     stream_wave_bytes = 32 << 30     # run_streams: tensor bytes of one wave (~850 UTRs of the headline shape)
@@ -894,66 +907,66 @@ class Engine:
         and a job's bits do not depend on what else shares the call (tests: small-call shapes), so results, job counts
         and the generator's final state are those of the serial loop (depth 1).
         """
-        active = [[smp, list(sws), 0] for smp, sws in streams if len(sws)]
-        from concurrent.futures import ThreadPoolExecutor
-        if len(active) < Engine.pingpong_min_streams and (depth <= 1 or not Engine.draw_ahead):
-            stats, base, cur = Engine.spec_stats, dict(Engine.spec_stats), depth
+        active = [_Stream(smp, list(sws)) for smp, sws in streams if len(sws)]
+        if len(active) >= Engine.pingpong_min_streams:
+            Engine._run_two_halves(batch, active, deferred, on_done, depth)
+        elif depth > 1 and Engine.draw_ahead:
+            Engine._run_draw_ahead(batch, active, deferred, on_done, depth)
+        else:
+            Engine._run_call_by_call(batch, active, deferred, on_done, depth)
+
+    @staticmethod
+    def _run_call_by_call(batch, active, deferred, on_done, depth):
+        """Few streams, no look-ahead: draw a call's tables, run it, take its results in."""
+        stats, base, cur = Engine.spec_stats, dict(Engine.spec_stats), depth
+        while active:
+            call = Engine._streams_prepare(active, cur)
+            active, _held = Engine._streams_absorb(call, batch.em_packed(call.pj), deferred, on_done)
+            cur = Engine._next_depth(depth, cur, stats, base)
+
+    @staticmethod
+    def _run_draw_ahead(batch, active, deferred, on_done, depth):
+        """Few streams with followers.  While the GPU runs a call (worker thread, GIL released), this thread already
+        draws the tables of the NEXT call as if every prediction of the running one held - exactly what the serial
+        loop would draw then; they are thrown away otherwise (the host has nothing else to do meanwhile)."""
+        stats, base, cur = Engine.spec_stats, dict(Engine.spec_stats), depth
+        with ThreadPoolExecutor(1) as gpu:
+            call = Engine._streams_prepare(active, cur)
             while active:
-                prepared = Engine._streams_prepare(active, cur)
-                active, _held = Engine._streams_absorb(active, prepared, batch.em_packed(prepared[0]), deferred, on_done)
-                cur = Engine._next_depth(depth, cur, stats, base)
-            return
-        if len(active) < Engine.pingpong_min_streams:
-            # few streams with followers.  While the GPU runs a call (worker thread, GIL released), this thread already
-            # draws the tables of the NEXT call as if every prediction of the running one held - exactly what the serial
-            # loop would draw then; they are thrown away otherwise (the host has nothing else to do meanwhile).
-            stats, base, cur = Engine.spec_stats, dict(Engine.spec_stats), depth
-            with ThreadPoolExecutor(1) as gpu:
-                prepared = Engine._streams_prepare(active, cur)
-                while active:
-                    fut = gpu.submit(batch.em_packed, prepared[0])
-                    end_state = [st[0].state.copy() for st in active]        # where each stream stands if every prediction holds
-                    moved = [len(ch) for ch in prepared[1]]
-                    for st, m in zip(active, moved):
-                        st[2] += m
-                    nxt = [st for st in active if st[2] < len(st[1])]
-                    ahead = Engine._streams_prepare(nxt, cur) if nxt else None
-                    for st, m in zip(active, moved):
-                        st[2] -= m
-                    out = fut.result()
-                    was = list(active)
-                    active, held = Engine._streams_absorb(active, prepared, out, deferred, on_done)
-                    new_cur = Engine._next_depth(depth, cur, stats, base)
-                    if ahead is not None and all(held) and new_cur == cur:
-                        prepared = ahead                   # (all held: `active` is `nxt`, in the same order)
-                        stats["calls_drawn_ahead"] += 1
-                        continue
-                    if ahead is not None:                  # never submitted: the sweeps forget the jobs they were handed,
-                        for ch, ps in zip(ahead[1], ahead[2]):
-                            for sw, pk in zip(ch, ps):
-                                sw.n_jobs -= len(pk)
-                        for st, ok, stt in zip(was, held, end_state):
-                            if ok:                         # and a stream whose predictions held goes back to where its chain ended
-                                st[0].state[:] = stt       # (a stream with a wrong one was put right by _streams_absorb)
-                    cur = new_cur
-                    if active:
-                        prepared = Engine._streams_prepare(active, cur)
-            return
-        # many streams: two alternating halves - while the GPU runs the EM call of one half (a worker thread inside the
-        # library call, GIL released), this thread takes in the other half's results and draws its next tables.  Calls
-        # on the handle stay strictly one after another; which streams share a call never changes a result.
+                fut = gpu.submit(batch.em_packed, call.pj)
+                end_state = [st.sampler.state.copy() for st in active]      # where each stream stands if every prediction holds
+                ahead = Engine._streams_prepare(active, cur, skip=[len(ch) for ch in call.chains])
+                active, held = Engine._streams_absorb(call, fut.result(), deferred, on_done)
+                new_cur = Engine._next_depth(depth, cur, stats, base)
+                if ahead is not None and all(held) and new_cur == cur:
+                    call = ahead                           # (all held: `active` is ahead.streams, in the same order)
+                    stats["calls_drawn_ahead"] += 1
+                    continue
+                if ahead is not None:
+                    ahead.forget()
+                    for st, ok, stt in zip(call.streams, held, end_state):
+                        if ok:                             # a stream whose predictions held goes back to where its chain ended
+                            st.sampler.state[:] = stt      # (a stream with a wrong one was put right by _streams_absorb)
+                cur = new_cur
+                if active:
+                    call = Engine._streams_prepare(active, cur)
+
+    @staticmethod
+    def _run_two_halves(batch, active, deferred, on_done, depth):
+        """Many streams: two alternating halves - while the GPU runs the EM call of one half (a worker thread inside the
+        library call, GIL released), this thread takes in the other half's results and draws its next tables.  Calls
+        on the handle stay strictly one after another; which streams share a call never changes a result."""
         halves = [active[0::2], active[1::2]]
         with ThreadPoolExecutor(1) as gpu:
-            prepared = [Engine._streams_prepare(h, depth) for h in halves]
-            futs = [gpu.submit(batch.em_packed, pr[0]) for pr in prepared]
+            calls = [Engine._streams_prepare(h, depth) for h in halves]
+            futs = [gpu.submit(batch.em_packed, call.pj) for call in calls]
             h = 0
             while halves[0] or halves[1]:
                 if halves[h]:
-                    out = futs[h].result()
-                    halves[h], _held = Engine._streams_absorb(halves[h], prepared[h], out, deferred, on_done)
+                    halves[h], _held = Engine._streams_absorb(calls[h], futs[h].result(), deferred, on_done)
                     if halves[h]:
-                        prepared[h] = Engine._streams_prepare(halves[h], depth)
-                        futs[h] = gpu.submit(batch.em_packed, prepared[h][0])
+                        calls[h] = Engine._streams_prepare(halves[h], depth)
+                        futs[h] = gpu.submit(batch.em_packed, calls[h].pj)
                 h ^= 1
 
     pingpong_min_streams = 32    # fewer streams than this: one call at a time (a half would leave the GPU under-filled)
@@ -970,21 +983,25 @@ class Engine:
         return cur
 
     @staticmethod
-    def _streams_prepare(active, depth):
+    def _streams_prepare(active, depth, skip=None):
         """Draw the tables of the next EM call: up to `depth` UTRs of every active stream (see _drive_streams).
         With depth > 1 the generator state after every sweep's own draws is kept, and the prune tables of a predicted
         K' are drawn right behind the sweep's (also for the last UTR of a chain: the stream then stands where the
-        next call starts if the prediction holds)."""
-        chains = [st[1][st[2]:st[2] + depth] for st in active]
-        packs = [[] for _ in active]
-        marks = [[] for _ in active]      # generator state after each sweep's own draws
-        ahead = [[] for _ in active]      # prune tables drawn ahead: (K', init_ws, k_arr) or None
+        next call starts if the prediction holds).  skip[k]: sweeps of active[k] that a call still running holds - the
+        tables are those of the call after it, of the streams that then have UTRs left (None when no stream has)."""
+        heads = [(st, st.cursor + n) for st, n in zip(active, skip or [0] * len(active))]
+        heads = [(st, lo) for st, lo in heads if lo < len(st.sweeps)]
+        if not heads:
+            return None
+        active = [st for st, _lo in heads]
+        chains = [st.sweeps[lo:lo + depth] for st, lo in heads]
+        packs, marks, ahead = [[] for _ in active], [[] for _ in active], [[] for _ in active]
         for pos in range(depth):          # position by position: the streams' sweeps of one position share a threaded call
             col = [(si, ch[pos]) for si, ch in enumerate(chains) if pos < len(ch)]
             if not col:
                 break
             for (si, sw), pk in zip(col, _Sweep.make_packed_many([sw for _si, sw in col])):
-                smp = active[si][0]
+                smp = active[si].sampler
                 packs[si].append(pk)
                 marks[si].append(smp.state.copy() if depth > 1 else None)
                 pre = None
@@ -996,28 +1013,25 @@ class Engine:
                         Kp = pred[1]
                         pre = (Kp, smp.init_ws(Kp, sw.prep.p["max_unif_ws"]), smp.k_arr(Kp))
                 ahead[si].append(pre)
-        return concat_packed([pk for ps in packs for pk in ps]), chains, packs, marks, ahead
+        return _PreparedCall(active, concat_packed([pk for ps in packs for pk in ps]), chains, packs, marks, ahead)
 
     @staticmethod
-    def _streams_absorb(active, prepared, out, deferred, on_done):
+    def _streams_absorb(call, out, deferred, on_done):
         """Take the results of one EM call in stream order, as far as the predictions held.  Returns (the streams that
-        still have UTRs, per stream of `active`: did every prediction of its chain hold - the generator then stands
+        still have UTRs, per stream of the call: did every prediction of its chain hold - the generator then stands
         where _streams_prepare left it)."""
-        pj, chains, packs, marks, ahead = prepared
         stats = Engine.spec_stats
         stats["calls"] += 1
-        lo, nxt, held = 0, [], []
-        for st, ch, ps, mk, ah in zip(active, chains, packs, marks, ahead):
-            smp, live = st[0], True
+        hi, nxt, held = 0, [], []
+        for st, ch, ps, mk, ah in zip(call.streams, call.chains, call.packs, call.marks, call.ahead):
+            smp, live = st.sampler, True
             for j, (sw, pk) in enumerate(zip(ch, ps)):
-                hi = lo + len(pk)
+                lo, hi = hi, hi + len(pk)
                 if not live:
                     sw.n_jobs -= len(pk)               # drawn from a state the stream never reached: discarded
                     stats["utrs_discarded"] += 1
-                    lo = hi
                     continue
-                sw.absorb_packed(pj, out, lo, hi)
-                lo = hi
+                sw.absorb_packed(call.pj, out, lo, hi)
                 stats["utrs_kept"] += 1
                 pre = ah[j]
                 last = j + 1 == len(ch)
@@ -1043,35 +1057,20 @@ class Engine:
                     continue
                 if live and not last:
                     stats["predicted_right"] += 1
-                st[2] += 1
+                st.cursor += 1
                 if on_done is not None:
                     on_done(sw)
             held.append(live)
-            if st[2] < len(st[1]):
+            if st.cursor < len(st.sweeps):
                 nxt.append(st)
         return nxt, held
 
     @staticmethod
     def _drive(batch, sweeps, deferred=None):
+        """Run sweeps to their end, all of them in every EM call (padded tables end to end)."""
         pending = list(sweeps)
-        while pending and all(sw.trace is None for sw in pending):      # fast path: padded tables end to end
-            packs = _Sweep.make_packed_many(pending)
-            pj = concat_packed(packs)
-            out = batch.em_packed(pj)
-            lo = 0
-            for sw, pk in zip(pending, packs):
-                sw.absorb_packed(pj, out, lo, lo + len(pk))
-                lo += len(pk)
+        while pending:
+            Engine._em_absorb(batch, pending, _Sweep.make_packed_many(pending))
             pending = [sw for sw in pending if not sw.done]
             if deferred is not None:
                 pending = Engine._defer_prunes(pending, deferred)
-        while pending:
-            jobs, spans = [], []
-            for sw in pending:
-                js = sw.make_jobs()
-                spans.append((len(jobs), len(jobs) + len(js)))
-                jobs.extend(js)
-            fits = batch.em(jobs)
-            for sw, (a, b) in zip(pending, spans):
-                sw.absorb(fits[a:b])
-            pending = [sw for sw in pending if not sw.done]

@@ -385,8 +385,42 @@ def test_wave_split_respects_budget(monkeypatch):
 class _FakeBatch:
     """Stands in for HipBatch.em_packed in the stream-driver tests: every job's "fit" is a pure function of that job's
     own table row (as on the GPU, where a job's bits do not depend on what shares its call), made up so that sweeps end
-    clean, pruned to various K' or at K = n_max (re-run)."""
+    clean, pruned to various K' or at K = n_max (re-run).  For Engine.process it also carries the rest of what that calls:
+    the lb rows of the last call stay fetchable, labels are a pure function of the model they are asked for."""
     calls = 0
+
+    def __init__(self, preps=()):
+        self.bin_off = np.zeros(len(preps) + 1, dtype=np.int64)
+        np.cumsum([q.N for q in preps], out=self.bin_off[1:])
+        self.seen = []                                     # (job tables, result arrays) of every call, in call order
+
+    def build(self):
+        pass
+
+    def timing(self, which):
+        return 0.0, 0
+
+    def em_counters(self):
+        return 0, 0, 0
+
+    def em_fetch_lb(self, job_idx):
+        return self.seen[-1][1][5][np.asarray(job_idx, dtype=np.int64)].copy()
+
+    @staticmethod
+    def fit_at(pj, out, i, lb_row=None):
+        from scape_amd.engine import HipBatch
+        return HipBatch.fit_at(pj, out, i, lb_row)
+
+    @staticmethod
+    def label_rule(n, K, a, b):
+        return ((np.arange(n) * (1 + int(np.sum(a[:K])) + int(np.sum(b[:K])))) % (K + 1)).astype(np.int32)
+
+    def labels_packed(self, su, sk, a, b, w):
+        flat = np.full(int(self.bin_off[-1]), -1, dtype=np.int32)
+        for i, u in enumerate(su):
+            lo, hi = int(self.bin_off[u]), int(self.bin_off[u + 1])
+            flat[lo:hi] = self.label_rule(hi - lo, int(sk[i]), a[i], b[i])
+        return flat
 
     def em_packed(self, pj, reuse_buffers=False, want_lb=True):
         import zlib
@@ -406,7 +440,8 @@ class _FakeBatch:
             wo[i, :K + 1] = w
             bic[i] = 2.0 * abs(K - 2.3) + 30.0 * r.random_sample()
             lb[i, :3] = r.random_sample(3)
-        return ao, bo, wo, bic, nlb, lb
+        self.seen.append((pj, (ao, bo, wo, bic, nlb, lb)))
+        return ao, bo, wo, bic, nlb, (lb if want_lb else None)
 
 
 def _stream_preps(n, base):
@@ -494,6 +529,156 @@ def test_prediction_pass_failure_is_not_a_stream_failure():
         assert all(sw.pred is None for sw in sweeps)
         assert eng.last_main_em_ms == 12.5 and eng.last_main_counters == (1, 2, 3)
         assert not hasattr(eng, "last_host_ms")
+
+
+def _fit_sig(f):
+    return (f.K, f.a_idx.tobytes(), f.b_idx.tobytes(), f.ws.tobytes(), np.float64(f.bic).tobytes(), f.lb.tobytes())
+
+
+def test_process_equals_the_sweep_state_machine():
+    """Engine.process (tables of a whole batch drawn up front, vectorised selection) and the _Sweep state machine are
+    the same function of (UTR, seed): K, a_idx, b_idx, ws, bic and lb equal as bytes, and equal job counts, with the
+    re-run rule on and off.  process's labels are those of the fit it returns."""
+    from scape_amd.engine import Engine, _Sweep
+    from scape_amd.host import FastSampler, N_TRIAL, prepare_utr
+    from scape_amd.synth import synth_utr
+    classes = dict(clean=0, pruned=0, rerun=0)
+    for base, n_max, n_min in ((9100, 3, 1), (9500, 4, 2), (9700, 5, 1)):
+        preps = [prepare_utr(df, gene_info_str=g, n_max_apa=n_max, n_min_apa=n_min)
+                 for g, df, _ in (synth_utr(i, 150, k_cap=3, base_seed=base) for i in range(40))]
+        seeds = [(2 ** 32 - 7 + 3 * i) % 2 ** 32 for i in range(len(preps))]
+        n_sweep = (n_max - n_min + 1) * N_TRIAL
+        for re_run in (True, False):
+            eng = Engine.__new__(Engine)
+            eng.sweep_lock = None
+            batch = _FakeBatch(preps)
+            got = eng.process(batch, preps, Engine.plan(preps, seeds), re_run)
+            assert set(eng.last_host_ms) == {"build_em", "select_prune", "labels", "collect"}
+            sweeps = [_Sweep(u, q, FastSampler(np.random.RandomState(sd)), re_run)
+                      for u, (q, sd) in enumerate(zip(preps, seeds))]
+            Engine._drive(_FakeBatch(preps), sweeps)
+            for u, ((fit, lab, nj), sw) in enumerate(zip(got, sweeps)):
+                assert _fit_sig(fit) == _fit_sig(sw.best), (base, re_run, u)
+                assert nj == sw.n_jobs, (base, re_run, u)
+                assert np.array_equal(lab, batch.label_rule(preps[u].N, fit.K, fit.a_idx, fit.b_idx)), (base, re_run, u)
+                if re_run:
+                    classes["clean" if nj == n_sweep else "pruned" if nj == n_sweep + 1 else "rerun"] += 1
+    assert min(classes.values()) >= 5, classes
+
+
+def test_traced_sweeps_equal_untraced_sweeps():
+    """A traced sweep (keep_trace: every fit of the UTR is kept) takes the same draws and gives the same winner and job
+    count as an untraced one - with one sampler per UTR (all UTRs advance together) and with one shared sampler driven
+    one UTR at a time (the reference's stream) - and its trace is, in order, the fit of every row of that UTR the batch
+    was handed."""
+    from scape_amd.engine import Engine, _Sweep
+    from scape_amd.host import FastSampler
+    preps = _stream_preps(30, 9100)
+
+    def run(shared, traced):
+        batch = _FakeBatch(preps)
+        one = FastSampler(np.random.RandomState(11)) if shared else None
+        smps = [one if shared else FastSampler(np.random.RandomState(500 + u)) for u in range(len(preps))]
+        sweeps = [_Sweep(u, q, smp, True, [] if traced else None) for u, (q, smp) in enumerate(zip(preps, smps))]
+        if shared:
+            deferred = []
+            for sw in sweeps:
+                Engine._drive(batch, [sw], deferred)
+            Engine._finish_deferred(batch, deferred)
+        else:
+            Engine._drive(batch, sweeps)
+        return batch, sweeps, [smp.state.copy() for smp in smps]
+
+    for shared in (False, True):
+        _b0, plain, plain_states = run(shared, False)
+        batch, traced, states = run(shared, True)
+        assert [(_fit_sig(sw.best), sw.n_jobs) for sw in traced] == [(_fit_sig(sw.best), sw.n_jobs) for sw in plain]
+        for a, b in zip(states, plain_states):
+            assert np.array_equal(a, b)
+        rows = [[] for _ in preps]
+        for pj, out in batch.seen:
+            for i, u in enumerate(pj.ju):
+                rows[u].append(_fit_sig(_FakeBatch.fit_at(pj, out, i)))
+        for sw in traced:
+            assert len(sw.trace) == sw.n_jobs and [_fit_sig(f) for f in sw.trace] == rows[sw.u], sw.u
+        assert len({sw.n_jobs for sw in traced}) >= 3        # clean, pruned and re-run sweeps all occur
+
+
+def test_sweep_winners_is_the_reference_float32_argmin():
+    """engine.sweep_winners: first arg-min over the restarts of a K, then first arg-min over K, both on BICs rounded to
+    float32 as in the reference's bic_arr - on uniform and on ragged spans."""
+    import warnings
+    from scape_amd.engine import sweep_winners
+    from scape_amd.host import N_TRIAL
+
+    def plain(bic, spans):
+        win = []
+        for lo, hi in zip(spans[:-1], spans[1:]):
+            with np.errstate(over="ignore"):
+                b32 = np.array(bic[lo:hi], dtype=np.float32)
+            per_k = [k0 + int(np.argmin(b32[k0:k0 + N_TRIAL])) for k0 in range(0, hi - lo, N_TRIAL)]     # em_optim0 (:865)
+            win.append(int(lo) + per_k[int(np.argmin(b32[per_k]))])                                       # run (:972)
+        return win
+
+    rs = np.random.RandomState(5)
+    for nks in ([3] * 7, [3, 1, 4, 2, 2, 5, 1], [2]):
+        spans = np.concatenate([[0], np.cumsum(np.array(nks) * N_TRIAL)]).astype(np.int64)
+        bic = np.round(rs.normal(3000.0, 40.0, spans[-1]))          # rounded: plenty of exact ties
+        assert sweep_winners(bic, spans).tolist() == plain(bic, spans), nks
+        bic[rs.choice(len(bic), 3, replace=False)] = np.nan         # np.argmin takes the first NaN, as in the reference
+        assert sweep_winners(bic, spans).tolist() == plain(bic, spans), nks
+    one = np.array([0, 2 * N_TRIAL], dtype=np.int64)
+    bic = np.full(2 * N_TRIAL, 50.0)
+    bic[[3, 7]] = 10.0                                              # tie within a restart block: the first restart
+    assert sweep_winners(bic, one).tolist() == [3]
+    bic[N_TRIAL + 1] = 10.0                                         # tie across K blocks: the first block
+    assert sweep_winners(bic, one).tolist() == [3]
+    bic[N_TRIAL + 1] = 10.0 - 1e-9                                  # smaller in float64, the same float32: still a tie
+    assert np.float32(bic[N_TRIAL + 1]) == np.float32(10.0) and sweep_winners(bic, one).tolist() == [3]
+    bic[N_TRIAL + 1] = 9.0
+    assert sweep_winners(bic, one).tolist() == [N_TRIAL + 1]
+    bic[:] = 1e300                                                  # above the float32 maximum: inf, no warning
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        assert sweep_winners(bic, one).tolist() == [0]
+        bic[N_TRIAL + 4] = 3e38
+        assert sweep_winners(bic, one).tolist() == [N_TRIAL + 4]
+        assert sweep_winners(bic, (N_TRIAL, 2 * N_TRIAL)).tolist() == [N_TRIAL + 4]     # one UTR's slice of a larger call
+
+
+def test_wave_composition_round_robin():
+    """engine.compose_wave: round-robin over the streams in flight with a per-stream cap and a byte budget; each stream's
+    UTRs contiguous and in file order, streams in admission order; the first UTR is taken even over budget; a UTR
+    larger than the device raises."""
+    from scape_amd import _lib, engine
+
+    class Q:
+        def __init__(self, N=100, T=218):
+            self.N, self.T, self.betas, self.gene_info_str = N, T, np.zeros(13), "g"
+    b = engine.Engine.utr_bytes(Q())
+
+    def streams(*sizes):
+        return [engine._FileStream(tag, [Q() for _ in range(n)], None, [None] * n) for tag, n in enumerate(sizes)]
+
+    def ids(wave):
+        return [(st.tag, i) for st, i in wave]
+    act = streams(5, 1, 3)
+    assert ids(engine.compose_wave(act, 2, 100 * b, 1000 * b)) == [(0, 0), (0, 1), (1, 0), (2, 0), (2, 1)]
+    assert [st.cursor for st in act] == [2, 1, 2]
+    assert ids(engine.compose_wave(act, 2, 100 * b, 1000 * b)) == [(0, 2), (0, 3), (2, 2)]      # goes on from the cursors
+    assert [st.cursor for st in act] == [4, 1, 3]
+    act = streams(5, 1, 3)
+    assert ids(engine.compose_wave(act, 2, 4 * b, 1000 * b)) == [(0, 0), (0, 1), (1, 0), (2, 0)]
+    assert [st.cursor for st in act] == [2, 1, 1]
+    act = streams(2, 2)
+    big = Q(1000, 300)
+    act[0].preps[0] = big
+    assert engine.Engine.utr_bytes(big) > 4 * b
+    assert ids(engine.compose_wave(act, 2, 4 * b, engine.Engine.utr_bytes(big))) == [(0, 0)]       # over budget, taken alone
+    assert [st.cursor for st in act] == [1, 0]
+    act[1].preps[0] = big
+    with pytest.raises(_lib.ScapeHipError):
+        engine.compose_wave(act, 2, 4 * b, engine.Engine.utr_bytes(big) - 1)
 
 
 def test_find_peaks_equals_scipy():
