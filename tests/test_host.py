@@ -1112,3 +1112,55 @@ def test_label_ladder_covers_every_boundary_of_the_label_kernel():
 def mr_exp_zero():
     from oracle import mstep_reference as mr
     return mr.EXP_ZERO
+
+
+def test_report_ladder_covers_every_boundary_of_the_report_kernels():
+    """tests/test_report_ladder.py runs the count, scan, render, segment-sum and histogram kernels of report.inc on the
+    cases of tests/report_ladder.py.  The boundaries are read here from the source - REP_THREADS (the column tile of the
+    render kernels, the word tile of k_rep_groups), REP_SCAN_THREADS (the step of k_rep_scan), the 64 lanes that the block
+    helpers hard-code, REP_ZERO_FIELD - and the ladder must have a value on both sides of each, and beyond the second
+    step of the two loops that carry (whoever moves one has to move the ladder)."""
+    import report_ladder as rl
+    src = open(os.path.join(ROOT, "scape_amd", "csrc", "report.inc")).read()
+    threads = int(re.search(r"#define REP_THREADS (\d+)\b", src).group(1))
+    scan = int(re.search(r"#define REP_SCAN_THREADS (\d+)\b", src).group(1))
+    zero = int(re.search(r"#define REP_ZERO_FIELD (\d+)\b", src).group(1))
+    assert (threads, scan, zero) == (rl.THREADS, rl.SCAN, rl.ZERO_FIELD) and "#define REP_WAVES (REP_THREADS / 64)" in src
+    # ---- the wavefront of 64 as the helpers hard-code it
+    helpers = src[src.index("// ---- block helpers"):src.index("__device__ __forceinline__ int rep_digits(")]
+    assert helpers.count("const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;") == 2 and rl.WAVE == 64
+    assert "for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);" in helpers
+    assert "for (int o = 1; o < 64; o <<= 1) {" in helpers and "if (lane >= o) x += y;" in helpers and "if (lane == 63) lds[w] = x;" in helpers
+    # ---- the loops whose strides the ladder straddles
+    assert src.count("for (int base = 0; base < n_cols; base += REP_THREADS) {") == 3      # the three render kernels
+    assert "for (int base = 0; base < n_words; base += REP_THREADS) {" in src and "carry += tile;" in src
+    assert "for (int base = 0; base < n; base += REP_SCAN_THREADS) {" in src and "carry += tot;" in src
+    assert src.count("pos += tile;") == 3 and "for (int s = w; s < n_seg; s += REP_WAVES) {" in src
+    by = {c.name: c for c in rl.cases()}
+    cols, rows = {c.n_cols for c in by.values() if c.family == "a"}, {len(c.rows) for c in by.values() if c.family == "c"}
+    assert cols == set(rl.COLS) and rows == set(rl.ROWS)
+    for c in (rl.WAVE, threads):
+        assert {c - 1, c, c + 1} <= cols, c
+    assert {2 * threads, 2 * threads + 1} <= cols and 1 in cols
+    assert {scan - 1, scan, scan + 1, 2 * scan, 2 * scan + 1} <= rows and 1 in rows
+    # ---- field widths on both sides of the zero field, in both forms; the digit counts the ladder reaches
+    widths = {len(rl.field(v, f)) for v in by["widths"].counts[0] for f in (True, False)}
+    assert {zero - 1, zero, zero + 1} <= widths and {len(str(v)) for v in rl.WIDTH_COUNTS} == set(range(1, 8))
+    assert all(p in rl.WIDTH_COUNTS for d in range(1, 7) for p in (10 ** d - 1, 10 ** d))
+    assert {c for c, v in rl.WIDTH_COLS.items() if v >= 10} >= {0, rl.WAVE - 1, rl.WAVE, threads - 1, threads, threads + 1}
+    assert by["widths"].n_cols == threads + 2
+    # ---- prefixes around the stride of the prefix copy, records around the wavefront
+    assert "for (int64_t k = threadIdx.x; k < plen; k += REP_THREADS) dst[k] = pre[p0 + k];" in src
+    assert {0, 1, threads - 1, threads, threads + 1} <= set(rl.PREFIX_LENGTHS) and max(rl.PREFIX_LENGTHS) > 2 * threads
+    assert {1, rl.WAVE - 1, rl.WAVE} <= set(rl.RECORD_KS) and max(rl.RECORD_KS) > rl.WAVE
+    assert by["records_complete"].n_cols == threads + 1
+    # ---- cluster codes: 32 per bitmap word, REP_THREADS words per step of k_rep_groups
+    assert "atomicOr(&b[code >> 5], 1u << (code & 31));" in src and "const int32_t n_words = (n_codes + 31) / 32;" in src
+    codes = {h.n_codes for h in rl.hist_cases()}
+    assert {32 * threads - 1, 32 * threads, 32 * threads + 1} <= codes and {1, 31, 32, 33, 64, None} <= codes
+    # ---- segments: four wavefronts per workgroup, lengths around the 64 lanes
+    waves = threads // 64
+    assert {waves - 1, waves, waves + 1, 2 * waves + 1, 1} <= set(rl.SEG_LENGTHS)
+    assert {0, 1, rl.WAVE - 1, rl.WAVE, rl.WAVE + 1} <= {n for v in rl.SEG_LENGTHS.values() for n in v}
+    assert max(n for v in rl.SEG_LENGTHS.values() for n in v) > 4 * rl.WAVE                  # beyond the unrolled four
+    assert {"a", "b", "c", "d", "e", "g"} == {c.family for c in by.values()}

@@ -1,7 +1,12 @@
 """`scape ex_pa_cnt_mat` and `scape cal_exp_pa_len` (reference utils.py:319-427, :438-553) against the REFERENCE's own
 outputs on the golden cases of tests/golden/fixture_report.npz (generator: tests/golden/make_golden_report.py): both
 example directories, ~40 fuzzed directories and the infer_pa -> merge_pa chain directory.  The matrix is compared
-byte for byte after decompression, the .pa.len.csv files byte for byte."""
+byte for byte after decompression, the .pa.len.csv files byte for byte.
+
+The golden directories are small (at most 407 matrix rows, counts up to 37 in a dense body, 46 bitmap words of cluster
+codes): the boundary shapes of the kernels underneath - more than 1,024 rows in a render block, 255 / 256 / 257 columns,
+counts of up to seven digits, more than 8,192 cluster codes - are tested in tests/test_report_ladder.py against the
+exact oracle of tests/report_ladder.py."""
 import gzip
 import os
 
