@@ -5,7 +5,7 @@ TEST INFRASTRUCTURE ONLY, like ``scape_oracle.py``: written from the formulas of
 included.  The constant ``PI_REF`` is the reference's f64 literal, not pi.
 
 Beside every value the functions return a FIRST-ORDER BOUND on how far a correct f64 evaluation may lie from it.  The
-bound is derived by counting the roundings of the device's sequence (scape_hip.hip, phase_b_split.inc); where the C
+bound is derived by counting the roundings of the device's sequence (scape_hip.hip, phase_b.inc); where the C
 oracle's sequence differs it rounds less often or the same.  Unit: u = 2^-53, the relative error of one correctly
 rounded f64 operation.  An error of e ulp of a library function is at most 2 e u relative.  The derived bound is
 multiplied by MARGIN = 2 for the second-order terms and never by anything else.

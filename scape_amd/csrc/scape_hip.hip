@@ -61,7 +61,7 @@ struct UtrDesc {
     int64_t m_off;      // offset (f64) of M       [T][B][Np]
     int64_t log_off;    // first entry in the log-domain bin list
     int64_t tile_off;   // first entry of this UTR in the per-tile extent table (64-row tiles of M)
-    int64_t mlog_off;   // first entry of this UTR in the compact table of log-domain values (phase_b_split.inc)
+    int64_t mlog_off;   // first entry of this UTR in the compact table of log-domain values (phase_b.inc)
     int32_t c_lo, c_hi; // uniform theta grid: the interior grid points [c_lo, c_hi] share one window table; c_lo > c_hi: none
     int32_t N, Np, T, n_log;
     double unif_ll, L, min_theta;
@@ -331,316 +331,7 @@ __global__ __launch_bounds__(256) void k_phase_a(const UtrDesc *__restrict__ des
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// Phase B: M[i][j][n] = logsumexp_w( A[n,w] + logN(theta_w; theta_i, beta_j) - G_ij ) over the
-// +-3 beta window (taichi_core.py:218-234).  One workgroup per (UTR, i); the window weights of
-// all betas are built once in LDS.  r-unknown bins take the linear-domain form
-// log( sum_w V[w][n] * exp(g_w - G) ) - mathematically the same sum, no exp per term; bins
-// whose A was built in the log domain (pA-site / r-known) take the reference's two-pass form.
-// LDS layout (f64): g[B][Wmax] | p[B][Wmax] | G[B] | lo[B] hi[B] (int32 pairs)
-// ------------------------------------------------------------------------------------------
-template <int BMAX>
-__global__ __launch_bounds__(256, 5) void k_phase_b(const UtrDesc *__restrict__ descs, DevParams P,
-                                                 const double *__restrict__ r,
-                                                 const double *__restrict__ pa,
-                                                 const double *__restrict__ theta,
-                                                 const int32_t *__restrict__ loglist,
-                                                 const double *__restrict__ AT,
-                                                 const double *__restrict__ V,
-                                                 double *__restrict__ M, int Wmax, int all_log,
-                                                 int *__restrict__ err_flag, int n_utr, int T_max,
-                                                 int32_t *__restrict__ tile_nend, int probe) {
-    extern __shared__ double sm[];
-    __shared__ double2 s_exptab[128];
-    d_load_exptab(s_exptab, threadIdx.x, 256);
-    // blocks b and b+8 share an XCD: all grid points of a UTR go to one XCD so its V rows (each is
-    // read by ~43 neighbouring alphas) are fetched into one L2 only.  Placement only affects speed.
-    const int id = blockIdx.x, slot = id >> 3;
-    const int uu = (slot / T_max) * 8 + (id & 7);
-    if (uu >= n_utr) return;
-    const UtrDesc d = descs[uu];
-    const int i = slot % T_max;
-    if (i >= d.T) return;
-    const int B = P.B;
-    const int tid = threadIdx.x;
-    double *g = sm;                       // [B][Wmax]  logN(theta_w; theta_i, beta_j)
-    double *p = sm + (size_t)B * Wmax;    // [B][Wmax]  exp(g - G), 0 outside the window
-    double *G = p + (size_t)B * Wmax;     // [B]
-    int *lo = (int *)(G + B);             // [B]
-    int *hi = lo + B;                     // [B]
-    const double *th = theta + d.theta_off;
-    const double ti = th[i];
-
-    if (tid < B) {
-        const double beta = P.betas[tid];
-        int a = i, b = i;
-        const double lob = ti - 3 * beta, hib = ti + 3 * beta;
-        // the walks start from where a uniform grid would put the window's ends and correct in either direction (the
-        // grid is ascending, so the boundary is unique): ~6 dependent loads instead of ~40 on the usual grid
-        if (d.T > 1) {
-            const double step = (i + 1 < d.T) ? th[i + 1] - ti : ti - th[i - 1];
-            if (step > 0.0) {
-                const double reach = 3 * beta / step;
-                const int jump = (reach < 1e6) ? (int)reach : 0;
-                a = max(0, i - jump);
-                b = min(d.T - 1, i + jump);
-            }
-        }
-        while (a < i && th[a] < lob) ++a;
-        while (a > 0 && th[a - 1] >= lob) --a;          // searchsorted(left)
-        while (b > i && th[b] > hib) --b;
-        while (b + 1 < d.T && th[b + 1] <= hib) ++b;    // searchsorted(right) - 1
-        if (b - a + 1 > Wmax) {
-            atomicExch(err_flag, 1);
-            b = a + Wmax - 1;
-        }
-        lo[tid] = a;
-        hi[tid] = b;
-    }
-    __syncthreads();
-    for (int e = tid; e < B * Wmax; e += blockDim.x) {
-        const int j = e / Wmax, w = e - j * Wmax;
-        const int tw = lo[j] + w;
-        g[e] = (tw <= hi[j]) ? d_logpdf_normal(th[tw], ti, P.betas[j]) : 0.0;
-    }
-    __syncthreads();
-    if (tid < B) {  // call_logp_theta_sum_kernel (taichi_core.py:160-169), serial order
-        double psum = 0.0;
-        const int W = hi[tid] - lo[tid] + 1;
-        if (probe & 4) psum = 1.0;
-        else
-        for (int w = 0; w < W; ++w) psum += exp(g[(size_t)tid * Wmax + w]);
-        G[tid] = log(psum);
-    }
-    __syncthreads();
-    int lo_all = lo[0], hi_all = hi[0];
-    for (int j = 1; j < B; ++j) {
-        lo_all = min(lo_all, lo[j]);
-        hi_all = max(hi_all, hi[j]);
-    }
-    const int Wall = hi_all - lo_all + 1;  // <= Wmax when windows nest (they do: symmetric in value)
-    // p re-indexed relative to lo_all so the linear path needs no per-beta window test
-    for (int e = tid; e < B * Wmax; e += blockDim.x) {
-        const int j = e / Wmax, w = e - j * Wmax;
-        const int tw = lo_all + w;
-        double val = 0.0;
-        if (w < Wall && tw >= lo[j] && tw <= hi[j]) val = exp(g[(size_t)j * Wmax + (tw - lo[j])] - G[j]);
-        p[e] = val;
-    }
-    __syncthreads();
-    if (Wall > Wmax) {
-        if (tid == 0) atomicExch(err_flag, 2);
-        return;
-    }
-
-    double *Mi = M + (size_t)d.m_off + (size_t)i * B * d.Np;
-    // Tile extents (used by the M-step, em_lockstep.inc): bins are ordered by read start, so each tensor row is finite
-    // on a prefix of the bins and holds the sentinel (read impossible) on the rest - 35-50 % of all entries.  For
-    // every TILE_ROWS-row tile the table gets one past the last bin that is finite in ANY of its rows (rounded up to
-    // 16): beyond it every row of the tile is the sentinel, and the M-step replaces that part of the dot product by
-    // SENT * sum(v) instead of streaming it.  The rows of this workgroup lie in at most two tiles.
-    const int tile0 = (i * B) / TILE_ROWS, j_split = (tile0 + 1) * TILE_ROWS - i * B;   // rows j >= j_split: tile0 + 1
-    int fin0 = 0, fin1 = 0;
-    auto note = [&](int j, int n, double val) {
-        if (val != SENT) {
-            if (j < j_split) fin0 = max(fin0, n + 1);
-            else fin1 = max(fin1, n + 1);
-        }
-    };
-    // ---- linear-domain path -----------------------------------------------------------------
-    // out[j][n] = sum_w p[j][w] * V[w][n] is a [16 x W] x [W x N] product: on the f64 matrix cores one
-    // v_mfma_f64_16x16x4_f64 covers 16 betas (13 used) x 16 bins x 4 taps.  A = weights from LDS (lane l:
-    // beta l&15, tap l>>4), B = V straight from global/L2 (lane l: tap l>>4, bin l&15), D lane l reg q:
-    // beta (l>>4)+4q, bin l&15.
-    if (probe & 2) {
-    } else if (!all_log && BMAX == 16) {
-        typedef double v4d __attribute__((ext_vector_type(4)));
-        const int WP = ((Wmax + 3) & ~3) + 1;                     // odd pitch: conflict-light fragment reads
-        double *pm = reinterpret_cast<double *>(hi + B + (B & 1)); // [16][WP], zero outside window / beyond B
-        for (int e = tid; e < 16 * WP; e += blockDim.x) {
-            const int j = e / WP, w = e - j * WP;
-            pm[e] = (j < B && w < Wmax) ? p[(size_t)j * Wmax + w] : 0.0;
-        }
-        __syncthreads();
-        const double *Vu = V + (size_t)d.at_off;
-        const int lane = tid & 63, wave = tid >> 6, kq = lane >> 4, rc = lane & 15;
-        const int nblocks = d.Np >> 4;
-        // Tap steps whose four rows all exist (lo_all + w0 + 3 <= T - 1) run without a row clamp: the loop body is one
-        // pointer add, one load, one LDS read and the MFMA per block of bins; the (at most one) step that reaches past
-        // the last grid point clamps its row - its weight is 0 there.  Two blocks of 16 bins share every weight fragment.
-        const int steps = (Wall + 3) >> 2;
-        const int full = max(0, min(steps, (d.T - lo_all) >> 2));
-        const size_t rstep = (size_t)4 * d.Np;
-        const double *pw = pm + rc * WP + kq;
-        const double *vbase = Vu + (size_t)(lo_all + kq) * d.Np + rc;
-        // The 16 x 16 result block: row kq + 4q of lane (kq, rc) is beta kq + 4q of bin n.  Written without divergent
-        // branches (the logs are taken on every lane, the stores and the extent bookkeeping are predicated): the
-        // per-value `if`s of a straightforward version compiled to ~40 exec-mask sequences per block.
-        auto finish = [&](int n, const v4d &acc) {
-            const bool pad = n >= d.N;
-            const int nn = pad ? d.N - 1 : n;
-            const bool lin = !pad && isnan(pa[d.bin_off + nn]) && isnan(r[d.bin_off + nn]);   // r-unknown bin: this path's
-            const bool wr = pad || lin;
-            bool f0 = false, f1 = false;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int j = kq + 4 * q;
-                const double a = acc[q];
-                const bool pos = a > 0.0;
-                const double lg = d_log_pos(pos ? a : 1.0);
-                const double val = pad ? 0.0 : (pos ? lg : SENT);
-                if (wr && j < B) Mi[(size_t)j * d.Np + n] = val;
-                const bool fin = lin && pos && j < B;
-                f0 |= fin && j < j_split;
-                f1 |= fin && j >= j_split;
-            }
-            fin0 = max(fin0, f0 ? n + 1 : 0);
-            fin1 = max(fin1, f1 ? n + 1 : 0);
-        };
-        int nb = wave;
-        for (; nb + 4 < nblocks; nb += 8) {
-            const double *v0 = vbase + nb * 16, *v1 = v0 + 64;
-            v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-            int st = 0;
-            // Four tap steps per trip: their eight V fragments are requested together, then consumed - one wait on the
-            // L2 per trip instead of one per step.  (The loop is bound by that latency, not by issue: 8 or 31
-            // instructions per MFMA made no difference, batching the loads took 1.3 ms off; the 1-3 steps left over
-            // are batched the same way: another 0.5 ms.  Measured and not kept: predicated batches of 4 / 6 / 12 steps
-            // (the compiler serialises them), the next pair's first batch requested before this pair's logs and
-            // stores (3 wavefronts per SIMD instead of 4: +1.5 ms; held to 4: -0.15 ms), batched loads in the
-            // log-domain path and the grid points of the window searches in LDS (registers: 3 wavefronts, +2 ms).)
-            auto batch = [&](auto nbc) {
-                constexpr int NB = decltype(nbc)::value;
-                double b0[NB], b1[NB], av[NB];
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    b0[k] = v0[k * rstep];
-                    b1[k] = v1[k * rstep];
-                }
-#pragma unroll
-                for (int k = 0; k < NB; ++k) av[k] = pw[4 * (st + k)];
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[k], b0[k], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[k], b1[k], acc1, 0, 0, 0);
-                }
-                v0 += NB * rstep;
-                v1 += NB * rstep;
-                st += NB;
-            };
-            while (st + 4 <= full) batch(std::integral_constant<int, 4>());
-            switch (full - st) {
-                case 3: batch(std::integral_constant<int, 3>()); break;
-                case 2: batch(std::integral_constant<int, 2>()); break;
-                case 1: batch(std::integral_constant<int, 1>()); break;
-                default: break;
-            }
-            for (; st < steps; ++st) {
-                const int wr = min(lo_all + 4 * st + kq, d.T - 1);
-                const double av = pw[4 * st];
-                const double *vr = Vu + (size_t)wr * d.Np + nb * 16 + rc;
-                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, vr[0], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, vr[64], acc1, 0, 0, 0);
-            }
-            finish(nb * 16 + rc, acc0);
-            finish(nb * 16 + 64 + rc, acc1);
-        }
-        for (; nb < nblocks; nb += 4) {
-            const double *v0 = vbase + nb * 16;
-            v4d acc0 = {0.0, 0.0, 0.0, 0.0};
-            int st = 0;
-#pragma unroll 4
-            for (; st < full; ++st) {
-                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(pw[4 * st], *v0, acc0, 0, 0, 0);
-                v0 += rstep;
-            }
-            for (; st < steps; ++st) {
-                const int wr = min(lo_all + 4 * st + kq, d.T - 1);
-                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(pw[4 * st], Vu[(size_t)wr * d.Np + nb * 16 + rc], acc0, 0, 0, 0);
-            }
-            finish(nb * 16 + rc, acc0);
-        }
-    } else if (!all_log) {
-        const double *Vu = V + (size_t)d.at_off;
-        for (int n = tid; n < d.Np; n += blockDim.x) {
-            if (n >= d.N) {
-                for (int j = 0; j < B; ++j) Mi[(size_t)j * d.Np + n] = 0.0;
-                continue;
-            }
-            if (!isnan(pa[d.bin_off + n]) || !isnan(r[d.bin_off + n])) continue;
-            if (B <= BMAX) {
-                double acc[BMAX];
-#pragma unroll
-                for (int j = 0; j < BMAX; ++j) acc[j] = 0.0;
-                for (int w = 0; w < Wall; ++w) {
-                    const double v = Vu[(size_t)(lo_all + w) * d.Np + n];
-#pragma unroll
-                    for (int j = 0; j < BMAX; ++j)
-                        if (j < B) acc[j] += v * p[(size_t)j * Wmax + w];
-                }
-#pragma unroll
-                for (int j = 0; j < BMAX; ++j)
-                    if (j < B) {
-                        const double val = (acc[j] > 0.0) ? d_log_pos(acc[j]) : SENT;
-                        Mi[(size_t)j * d.Np + n] = val;
-                        note(j, n, val);
-                    }
-            } else {
-                for (int j = 0; j < B; ++j) {
-                    double acc = 0.0;
-                    for (int w = 0; w < Wall; ++w)
-                        acc += Vu[(size_t)(lo_all + w) * d.Np + n] * p[(size_t)j * Wmax + w];
-                    const double val = (acc > 0.0) ? d_log_pos(acc) : SENT;
-                    Mi[(size_t)j * d.Np + n] = val;
-                    note(j, n, val);
-                }
-            }
-        }
-    } else if (all_log) {
-        for (int n = d.N + tid; n < d.Np; n += blockDim.x)
-            for (int j = 0; j < B; ++j) Mi[(size_t)j * d.Np + n] = 0.0;
-    }
-    // ---- log-domain path (cal_res_kernel, taichi_core.py:172-179) ------------------------------
-    const int n_log = (probe & 1) ? 0 : (all_log ? d.N : d.n_log);
-    const double *Au = AT + (size_t)d.at_off;
-    for (int item = tid; item < n_log * B; item += blockDim.x) {
-        const int j = item / n_log, q = item - j * n_log;
-        const int n = all_log ? q : loglist[d.log_off + q];
-        const int a = lo[j], W = hi[j] - lo[j] + 1;
-        const double Gj = G[j];
-        const double *gj = g + (size_t)j * Wmax;
-        double mx = Au[(size_t)a * d.Np + n] + gj[0] - Gj;
-        for (int w = 1; w < W; ++w) {
-            const double t = Au[(size_t)(a + w) * d.Np + n] + gj[w] - Gj;
-            if (t > mx) mx = t;
-        }
-        double sum = 0.0;
-        // every argument is <= 0 (mx is the maximum): the table exp of the E-step, 18 instructions instead of ~40
-        for (int w = 0; w < W; ++w) sum += d_exp_nonpos(Au[(size_t)(a + w) * d.Np + n] + gj[w] - Gj - mx, s_exptab);
-        const double val = d_log_pos(sum) + mx;
-        Mi[(size_t)j * d.Np + n] = val;
-        note(j, n, val);
-    }
-    if (tile_nend) {
-        __shared__ int s_fin[2];
-        if (tid < 2) s_fin[tid] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            fin0 = max(fin0, __shfl_xor(fin0, off, 64));
-            fin1 = max(fin1, __shfl_xor(fin1, off, 64));
-        }
-        if ((tid & 63) == 0) {
-            atomicMax(&s_fin[0], fin0);
-            atomicMax(&s_fin[1], fin1);
-        }
-        __syncthreads();
-        if (tid < 2 && s_fin[tid] > 0)
-            atomicMax(&tile_nend[d.tile_off + tile0 + tid], min(d.Np, (s_fin[tid] + 15) & ~15));
-    }
-}
-
-#include "phase_b_split.inc"
+#include "phase_b.inc"      // Phase B: M[i][j][n], the marginal tensor over (alpha_i, beta_j) - all three forms
 #include "em_lockstep.inc"
 #include "mstep_ring.inc"
 #include "mstep_multi.inc"
@@ -1006,18 +697,12 @@ static int queue_phase_b(scape_hip_ctx *c, const BatchState &b, const PhaseB &ch
     HIPCHK(hipMemsetAsync(c->d_err.p, 0, sizeof(int), c->stream));
     const dim3 by_alpha((unsigned)(((b.n_utr + 7) / 8) * 8 * b.T_max));
     if (ch.form == 0) {
-#ifdef SCAPE_HIP_TOOLS   // tools-only builds (-DSCAPE_HIP_TOOLS): timing probe that switches parts of Phase B off - results are wrong with it
-        const char *pe = getenv("SCAPE_HIP_PB_PROBE");   // 1 no log path, 2 no linear path, 4 no G exps
-        const int probe = pe ? atoi(pe) : 0;
-#else
-        const int probe = 0;
-#endif
         if (b.prm.B <= 16)
             hipLaunchKernelGGL(k_phase_b<16>, by_alpha, dim3(256), ch.lds, c->stream, desc, b.prm, r, pa, theta, loglist, AT, V, M,
-                               ch.Wmax, all_log, c->d_err.as<int>(), b.n_utr, b.T_max, tile_nend, probe);
+                               ch.Wmax, all_log, c->d_err.as<int>(), b.n_utr, b.T_max, tile_nend);
         else
             hipLaunchKernelGGL(k_phase_b<1>, by_alpha, dim3(256), ch.lds, c->stream, desc, b.prm, r, pa, theta, loglist, AT, V, M,
-                               ch.Wmax, all_log, c->d_err.as<int>(), b.n_utr, b.T_max, tile_nend, probe);
+                               ch.Wmax, all_log, c->d_err.as<int>(), b.n_utr, b.T_max, tile_nend);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -1768,7 +1453,7 @@ int scape_hip_batch_load(scape_hip_ctx *c, const scape_hip_params *p, int32_t n_
         b.d_loglist.ensure(loglist.size() * 4) || b.d_AT.ensure(b.at_total * 8) || b.d_V.ensure(b.at_total * 8) ||
         b.d_M.ensure(b.m_total * 8) || b.d_tile_nend.ensure(b.tiles_total * 4))
         return 1;
-    if (p->n_beta <= 16) {   // the three-kernel Phase B (phase_b_split.inc)
+    if (p->n_beta <= 16) {   // the three-kernel Phase B (phase_b.inc)
         const size_t WP = (size_t)(((b.W_max + 3) & ~3) + 1);
         if (b.d_tbi.ensure((size_t)nt * 40 * 4) || b.d_tbG.ensure((size_t)nt * 16 * 8) || b.d_tbpm.ensure((size_t)nt * 16 * WP * 8) ||
             b.d_mlog.ensure(b.mlog_total * 8) || b.d_logbin.ensure(logbin_utr.size() * 4) ||

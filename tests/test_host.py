@@ -761,7 +761,7 @@ def test_tensor_ladder_covers_every_boundary_of_the_tensor_build():
     expects is recomputed from those constants."""
     import tensor_ladder as tl
     src = open(os.path.join(ROOT, "scape_amd", "csrc", "scape_hip.hip")).read()
-    inc = open(os.path.join(ROOT, "scape_amd", "csrc", "phase_b_split.inc")).read()
+    inc = open(os.path.join(ROOT, "scape_amd", "csrc", "phase_b.inc")).read()
 
     def define(text, name):
         found = re.findall(r"#define\s+%s\s+(\d+)\b" % name, text)
@@ -777,7 +777,7 @@ def test_tensor_ladder_covers_every_boundary_of_the_tensor_build():
     cap = re.search(r"s\.pb_slide = slide && s\.W_max <= 4 \* PB_STEPS && s\.T_max <= (\d+);", src)
     assert cap and int(cap.group(1)) == 4096            # the cap exists; a 4097-point grid is not part of the ladder
     xcd = re.findall(r"\(slot / (?:T_max|blocks_max)\) \* (\d+) \+ \(id & (\d+)\)", src + inc)
-    assert len(xcd) == 3 and set(xcd) == {("8", "7")}, xcd
+    assert len(xcd) == 2 and set(xcd) == {("8", "7")}, xcd
     wave_bins, wg_bins = re.search(r"const int n0 = (\d+) \* bb \+ (\d+) \* wave", inc).groups()[::-1]
     wave_bins, wg_bins = int(wave_bins), int(wg_bins)
     pa_lanes = int(re.search(r"__launch_bounds__\((\d+)\) void k_phase_a\(", src).group(1))

@@ -156,7 +156,7 @@ static void check_refused(const Batch &b, const char *message, const char *what)
     CHECK(plan.n_utr == -7 && plan.h_desc.empty(), "%s: a refused walk wrote its result", what);
 }
 
-// the Phase B choice from its rule, the LDS sizes in bytes from the kernels' layouts (phase_b_split.inc, k_phase_b)
+// the Phase B choice from its rule, the LDS sizes in bytes from the kernels' layouts (phase_b.inc)
 static void check_choice(int B, int W, int T_max, bool slide, const char *mode) {
     PhaseB ch;
     const int rc = phase_b_choose(B, W, T_max, slide, mode, ch);
