@@ -212,6 +212,27 @@ int scape_hip_report_render_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows
 int scape_hip_report_render_len_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rec, const int64_t *rec_row0,
                                     const int32_t *K, const int64_t *n_off, const double *n_arr, const int8_t *skip,
                                     int64_t row_no0, int32_t what, int64_t *bytes_out, int64_t *nnz_out);
+/* ex_pa_usage_mat (usage_mat.inc): the per-cell usage c_l / T of every pA site.  scape_hip_report_usage_totals forms, for
+   n_rec records of the last counts call (record i owns the count rows rec_row0[i] .. rec_row0[i] + K[i] - 1) and every
+   column c, T[i][c] = the sum of the K[i] counts of column c (int32: a record holds at most INT32_MAX reads), and keeps
+   them on the device beside the counts until the next scape_hip_report_counts, scape_hip_report_usage_totals or
+   scape_hip_report_free call.  It returns once the kernel is queued. */
+int scape_hip_report_usage_totals(scape_hip_ctx *ctx, int32_t n_rec, const int64_t *rec_row0, const int32_t *K);
+/* Render n_rows rows as Matrix Market entries into slot 0 or 1.  Row i is count row rows[i] of the last counts call, one
+   of the rows of record row_rec[i] of the last totals call, and is row row_no0 + i of the file (row_no0 >= 1).  With c
+   its count and T its record's total in a column, each column, ascending, gives the line
+   "<row_no0 + i> <column + 1> <field>\n" where
+     what == 0: c > 0 and T >= min_reads; the field is '%.6f' of the double (double)c / (double)T, one correctly rounded
+       f64 division, printed exactly as scape_hip_report_render_len_mtx prints its values (ties to even on the binary
+       value: 1 / 128 is 0.007812);
+     what == 1: T >= min_reads, whatever c is; the field is T.
+   min_reads >= 1.  *bytes_out = the block's text bytes (0 when no row of the block has an entry; the slot is then
+   fetched as 0 bytes), *nnz_out = its entries; the rest as scape_hip_report_render.  An error return (no counts, no
+   totals since the last counts, a slot or `what` outside 0 / 1, min_reads < 1, a row or record index out of range, a
+   row outside its record) leaves *bytes_out and *nnz_out as they were. */
+int scape_hip_report_render_usage_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows, const int64_t *rows,
+                                      const int32_t *row_rec, int64_t row_no0, int32_t min_reads, int32_t what,
+                                      int64_t *bytes_out, int64_t *nnz_out);
 /* Pseudo-bulk sums of the last counts call (ex_pa_pseudobulk): segment s is the columns [seg_off[s], seg_off[s+1]) of
    the count matrix, 0 <= seg_off[0] <= ... <= seg_off[n_seg] <= n_cols (the caller passes scape_hip_report_counts an
    id2col that puts every sample's columns side by side).  For row i (count row rows[i]) and segment s,

@@ -8,8 +8,9 @@ them), ``diff_pa_markers`` (diff_pa for every cluster against all other cells), 
 per-cell score such as pseudotime), ``diff_pa_len_trend`` (3'UTR length along the same score), ``boot_pa_len``
 (bootstrap intervals of every cluster's mean pA position and expected pA length, by resampling the cells),
 ``boot_pa_usage`` (the same intervals of every cluster's usage of every pA site), ``boot_pa_len_diff`` and
-``boot_pa_usage_diff`` (the intervals of the difference of either between two cell populations) and
-``ex_pa_len_mat`` (the gene x cell matrix of the expected pA length; the fifteen are this build's own last steps;
+``boot_pa_usage_diff`` (the intervals of the difference of either between two cell populations),
+``ex_pa_len_mat`` (the gene x cell matrix of the expected pA length) and ``ex_pa_usage_mat`` (the pA site x cell matrix
+of the per-cell site usage; the sixteen are this build's own last steps;
 reference cli.py:7-31 registers six commands; ``gen_utr_annotation`` and ``prepare_input`` are outside this build's
 scope)."""
 import click
@@ -19,7 +20,7 @@ from scape_amd.junction_handler import merge_pa
 from scape_amd.report import (boot_pa_len, boot_pa_len_diff, boot_pa_usage, boot_pa_usage_diff, cal_exp_pa_len,
                               diff_pa, diff_pa_groups, diff_pa_len, diff_pa_len_groups, diff_pa_len_markers,
                               diff_pa_len_pairs, diff_pa_len_trend, diff_pa_markers, diff_pa_pairs, diff_pa_trend,
-                              ex_pa_cnt_mat, ex_pa_len_mat, ex_pa_pseudobulk)
+                              ex_pa_cnt_mat, ex_pa_len_mat, ex_pa_pseudobulk, ex_pa_usage_mat)
 
 
 @click.group()
@@ -41,6 +42,7 @@ cli.add_command(prebin)
 cli.add_command(cal_exp_pa_len)
 cli.add_command(ex_pa_cnt_mat)
 cli.add_command(ex_pa_len_mat)
+cli.add_command(ex_pa_usage_mat)
 cli.add_command(ex_pa_pseudobulk)
 cli.add_command(diff_pa)
 cli.add_command(diff_pa_len)

@@ -69,6 +69,8 @@ SIGNATURES = {
     "scape_hip_report_render_mtx": (c_i, [P_void, c_i32, c_i32, P_i64, c_i64, P_i64, P_i64]),
     "scape_hip_report_render_len_mtx": (c_i, [P_void, c_i32, c_i32, P_i64, P_i32, P_i64, P_d, P_i8, c_i64, c_i32, P_i64,
                                               P_i64]),
+    "scape_hip_report_usage_totals": (c_i, [P_void, c_i32, P_i64, P_i32]),
+    "scape_hip_report_render_usage_mtx": (c_i, [P_void, c_i32, c_i32, P_i64, P_i32, c_i64, c_i32, c_i32, P_i64, P_i64]),
     "scape_hip_report_group_sums": (c_i, [P_void, c_i32, P_i32, c_i32, P_i64, P_i32, P_i32]),
     "scape_hip_report_perm_masks": (c_i, [P_void, c_i32, c_i32, c_i64, c_i32, ctypes.c_uint64]),
     "scape_hip_report_perm_masks_strata": (c_i, [P_void, c_i32, P_i32, P_i32, c_i64, c_i32, ctypes.c_uint64]),

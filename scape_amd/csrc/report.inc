@@ -50,6 +50,13 @@ struct ReportState {
     DevBuf r_lab, r_cb, r_off, r_K, r_rowbase, r_map, r_cnt, r_tot, r_cflag, r_err;
     int32_t n_cols = 0;
     int64_t n_cnt_rows = 0;
+    // ex_pa_usage_mat (usage_mat.inc): per record of the last scape_hip_report_usage_totals call and column, the reads
+    // with label < K ([record][column], int32); the records' first count rows and K on the device and on the host; the
+    // number of those records, 0 until that call has followed the last counts call
+    DevBuf u_tot, u_row0, u_K;
+    std::vector<int64_t> u_rows;
+    std::vector<int32_t> u_Ks;
+    int32_t u_n_rec = 0;
     // histograms of the last scape_hip_report_hist call
     DevBuf h_bits, h_wpre, h_nloc, h_goff, h_hoff, h_codes, h_hist;
     std::vector<int64_t> goff, hoff;   // host side of h_goff / h_hoff: alive until the queued copies have run
@@ -109,6 +116,7 @@ struct ReportState {
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
     DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
     DevBuf s_lk[2], s_loff[2], s_lskip[2], s_lnarr[2];   // ex_pa_len_mat blocks: per record K, offset into n_arr, skip; n_arr
+    DevBuf s_urec[2];                  // ex_pa_usage_mat blocks: per row its record among those of the totals
     void *host_out[2] = {nullptr, nullptr};
     size_t host_cap[2] = {0, 0};
     int64_t slot_bytes[2] = {0, 0};
@@ -875,6 +883,7 @@ int scape_hip_report_counts(scape_hip_ctx *c, int32_t n_rec, const int64_t *read
     if (rep_fetch_err(c, s, bad_read_out)) return 1;
     s->n_cols = n_cols;
     s->n_cnt_rows = rows;
+    s->u_n_rec = 0;                      // the totals of usage_mat.inc belonged to the counts before
     return 0;
 }
 

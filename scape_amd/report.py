@@ -22,6 +22,10 @@ device's rendering of one text block with the gzip of the previous one.
 * ``ex_pa_len_mat``: ``exp_pa_len`` per (record, cell) as a Matrix Market directory, with the reads behind each value
   in a second matrix.  The host forms ``n_arr`` with the reference's numpy expression; the device divides, multiplies
   and adds in the order of numpy's pairwise sum and renders ``'%.6f'`` in exact integers (section ex_pa_len_mat below).
+* ``ex_pa_usage_mat``: the usage (PSI) of every pA site per cell, the count of the site over the cell's reads of the
+  record, as a Matrix Market directory on the rows and columns of ``ex_pa_cnt_mat --format mtx``, with the cell's reads
+  of the record in a second matrix.  The device forms the records' column totals once, divides and renders ``'%.6f'``
+  in exact integers (section ex_pa_usage_mat below).
 * ``ex_pa_pseudobulk``: the count matrix summed over cell groups, the input of the reference's DEXSeq script
   (``examples/Rscript-DEXseq/DifferentialTest.R:63-104``, ``:159-184``).  The host permutes the barcode columns so
   that every pseudo-replicate is one contiguous segment of a count row; the device counts as for ``ex_pa_cnt_mat``
@@ -368,6 +372,20 @@ def _two_slot_blocks(ctx, writer, blocks, render, times):
     writer.drain()
 
 
+def _cut_blocks(bound):
+    """[(a, b)]: the rows 0 .. len(bound) in runs whose summed upper bounds of the text stay within MAX_BLOCK_BYTES (a
+    row above it goes alone), at most 2^20 rows each"""
+    cum = np.zeros(len(bound) + 1, dtype=np.int64)
+    np.cumsum(bound, out=cum[1:])
+    blocks, a = [], 0
+    while a < len(bound):
+        b = int(np.searchsorted(cum, cum[a] + MAX_BLOCK_BYTES, side="right")) - 1
+        b = min(len(bound), a + (1 << 20), max(a + 1, b))
+        blocks.append((a, b))
+        a = b
+    return blocks
+
+
 def _render_batch(ctx, bat, n_cols, writer, times):
     """every row of one counted batch: prefixes on the host, text on the device, in blocks of a fixed number of rows"""
     _rowbase, rows, owner, label = _kept_rows(bat)
@@ -522,16 +540,7 @@ def _render_mtx_batch(ctx, bat, n_cols, sink, times):
     row_no0 = sink.n_rows + 1
     tot = bat.row_tot[rows]
     width = len(str(row_no0 + len(rows) - 1)) + len(str(n_cols)) + 3 + _digits(tot)
-    cum = np.zeros(len(rows) + 1, dtype=np.int64)
-    np.cumsum(np.minimum(tot, n_cols) * width, out=cum[1:])
-
-    def blocks():
-        a = 0
-        while a < len(rows):
-            b = int(np.searchsorted(cum, cum[a] + MAX_BLOCK_BYTES, side="right")) - 1
-            b = min(len(rows), a + (1 << 20), max(a + 1, b))
-            yield a, b
-            a = b
+    blocks = _cut_blocks(np.minimum(tot, n_cols) * width)
 
     def render(slot, a, b):
         nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -540,7 +549,7 @@ def _render_mtx_batch(ctx, bat, n_cols, sink, times):
                                                   ctypes.byref(nbytes), ctypes.byref(nnz)), "report_render_mtx")
         times["render"] += timer() - t0
         sink.nnz += nnz.value
-    _two_slot_blocks(ctx, sink.matrix, blocks(), render, times)
+    _two_slot_blocks(ctx, sink.matrix, blocks, render, times)
     sink.features.drain()
     sink.n_rows += len(rows)
 
@@ -599,14 +608,7 @@ def _render_len_batch(ctx, bat, n_cols, values, reads, times):
     big[skip != 0] = 0.0
     field = np.maximum(8 + _digits(big.astype(np.int64) + 1), _digits(tot))
     width = len(str(row_no0 + n_rec - 1)) + len(str(n_cols)) + 3 + field
-    cum = np.zeros(n_rec + 1, dtype=np.int64)
-    np.cumsum(np.minimum(tot, n_cols) * width, out=cum[1:])
-    blocks, a = [], 0
-    while a < n_rec:
-        b = int(np.searchsorted(cum, cum[a] + MAX_BLOCK_BYTES, side="right")) - 1
-        b = min(n_rec, a + (1 << 20), max(a + 1, b))
-        blocks.append((a, b))
-        a = b
+    blocks = _cut_blocks(np.minimum(tot, n_cols) * width)
 
     def render(sink, what, slot, a, b):
         nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -648,6 +650,95 @@ def _ex_pa_len_mat(output_dir: str, res_pkl_file: str, device=None):
             _finish_mtx(run.parts[0], f"{LEN_MTX_BANNER}{values.n_rows} {n_cols} {values.nnz}\n", vbody, run.times)
             _finish_mtx(run.parts[1], f"{MTX_BANNER}{values.n_rows} {n_cols} {reads.nnz}\n", rbody, run.times)
     print("Finish expected pA length for each gene and cell")
+    print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
+    return out_dir
+
+
+# ---------------------------------------------------------------- ex_pa_usage_mat
+# The rows and columns are those of ex_pa_cnt_mat --format mtx (the kept rows of every batch, whatever min_reads is), so
+# features.tsv.gz and barcodes.tsv.gz are that command's byte for byte.  With c the count of a row in a cell and T the
+# cell's reads of label < K in the row's record (ex_pa_len_mat's T): matrix.mtx.gz holds '%.6f' of the double c / T where
+# c > 0 and T >= min_reads, reads.mtx.gz holds T wherever T >= min_reads, at the record's sites without a read of the
+# cell as well.  An entry there without one in the value matrix is an observed usage of 0; no entry there is a usage
+# that is not defined, which a single sparse matrix could not tell apart.  The division and the decimal text are the
+# device's (include/scape_hip.h states them), from per-record totals that the device forms once per batch.
+USAGE_MAX_MIN_READS = 2 ** 31 - 1
+
+
+def _usage_batch_cost(n_cols):
+    """device bytes of a record: _batch_cost's and its row of column totals (int32)"""
+    cost = _batch_cost(n_cols)
+    return lambda p: cost(p) + 4 * n_cols
+
+
+def _render_usage_batch(ctx, bat, n_cols, min_reads, values, reads, times):
+    """the kept rows of one counted batch, numbered on from values.n_rows: features lines on the host, the records'
+    column totals once on the device, then the entries of both matrices (values.matrix, then reads.matrix, from the
+    same counts and totals), in blocks cut by their text size"""
+    rowbase, rows, owner, label = _kept_rows(bat)
+    if not len(rows):
+        return
+    pa = _pa_infos(bat.recs, owner, label)
+    values.features.submit(memoryview(_tsv_lines(pa, lambda s: f"{s}\t{s}\tGene Expression\n", "pa_info").encode()))
+    t0 = timer()
+    check(ctx.lib.scape_hip_report_usage_totals(ctx.h, len(bat.recs), ptr(np.ascontiguousarray(rowbase), P_i64),
+                                                ptr(np.ascontiguousarray(bat.K), P_i32)), "report_usage_totals")
+    times["render"] += timer() - t0
+    row_rec = np.ascontiguousarray(owner.astype(np.int32))
+    # each matrix's blocks are cut against an upper bound of its rows' text, "<row number> <column> <field>\n" per entry:
+    # the value matrix has at most min(the row's reads, barcodes) entries of an 8-byte field; the reads matrix has one
+    # wherever the cell has a read of the RECORD, so at most min(the record's reads, barcodes), of at most the digits of
+    # the record's reads.  (One bound for both would cut the value matrix into blocks too small to keep the gzip
+    # threads busy: a block is compressed in GZIP_PART pieces, one block at a time.)
+    row_no0 = values.n_rows + 1
+    base = len(str(row_no0 + len(rows) - 1)) + len(str(n_cols)) + 3
+    rec_tot = np.add.reduceat(bat.row_tot, rowbase)[owner]
+    bounds = (np.minimum(bat.row_tot[rows], n_cols) * (base + 8), np.minimum(rec_tot, n_cols) * (base + _digits(rec_tot)))
+
+    def render(sink, what, slot, a, b):
+        nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
+        t0 = timer()
+        check(ctx.lib.scape_hip_report_render_usage_mtx(
+            ctx.h, slot, b - a, ptr(rows[a:b], P_i64), ptr(row_rec[a:b], P_i32), row_no0 + a, min_reads, what,
+            ctypes.byref(nbytes), ctypes.byref(nnz)), "report_render_usage_mtx")
+        times["render"] += timer() - t0
+        sink.nnz += nnz.value
+    for sink, what in ((values, 0), (reads, 1)):
+        _two_slot_blocks(ctx, sink.matrix, _cut_blocks(bounds[what]), functools.partial(render, sink, what), times)
+    values.features.drain()
+    values.n_rows += len(rows)
+
+
+def _ex_pa_usage_mat(output_dir: str, res_pkl_file: str, min_reads: int = 1, device=None):
+    """the pA site x cell matrix of the per-cell site usage (PSI) as a 10x-style directory <res>.usage/ (<res>.min<N>.usage/
+    for min_reads N > 1): matrix.mtx.gz (real, c / T where c > 0 and T >= min_reads), reads.mtx.gz (integer, T wherever
+    T >= min_reads), features.tsv.gz and barcodes.tsv.gz (those of ex_pa_cnt_mat --format mtx).  The four are renamed
+    from .part once all are complete."""
+    if isinstance(min_reads, bool) or not isinstance(min_reads, (int, np.integer)) or \
+            not 1 <= min_reads <= USAGE_MAX_MIN_READS:
+        raise ValueError(f"min_reads must be an integer from 1 to {USAGE_MAX_MIN_READS}, not {min_reads!r}")
+    min_reads = int(min_reads)
+    inp = _read_inputs(output_dir, res_pkl_file, with_cb=True)
+    n_cols = inp.n_cols
+    idmap = _IdMap(inp.col_ids, np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
+    bc_text = _tsv_lines([str(b) for b in inp.cb_lst], lambda s: s + "\n", "barcode")
+    tag = ".usage" if min_reads == 1 else f".min{min_reads}.usage"
+    out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", tag))
+    with _dir_run(device, out_dir, LEN_MTX_FILES) as run:
+        with tempfile.TemporaryFile(dir=out_dir) as vbody, tempfile.TemporaryFile(dir=out_dir) as rbody, \
+                open(run.parts[2], "wb") as ffh, ThreadPoolExecutor(_hostlib.host_threads()) as pool:
+            _write_gzip(run.parts[3], bc_text, pool, run.times)
+            values = _MtxSink(_GzipWriter(vbody, pool, run.times), _GzipWriter(ffh, pool, run.times))
+            reads = _MtxSink(_GzipWriter(rbody, pool, run.times), None)
+            ctx = run.device()
+            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _usage_batch_cost(n_cols), _budget(ctx), run.times):
+                _render_usage_batch(ctx, bat, n_cols, min_reads, values, reads, run.times)
+            if values.nnz > reads.nnz:
+                raise _lib.ScapeHipError("report_render_usage_mtx: the value matrix holds entries that the reads matrix "
+                                         "lacks")
+            _finish_mtx(run.parts[0], f"{LEN_MTX_BANNER}{values.n_rows} {n_cols} {values.nnz}\n", vbody, run.times)
+            _finish_mtx(run.parts[1], f"{MTX_BANNER}{values.n_rows} {n_cols} {reads.nnz}\n", rbody, run.times)
+    print("Finish pA site usage for each cell")
     print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
     return out_dir
 
@@ -2796,6 +2887,24 @@ def ex_pa_len_mat(output_dir: str, res_pkl_file: str):
     res.utr.pkl: the directory <res name>.len/ with matrix.mtx.gz, reads.mtx.gz (the reads behind each value),
     features.tsv.gz and barcodes.tsv.gz (sparse Matrix Market, as read by Seurat Read10X and scanpy read_10x_mtx)."""
     _ex_pa_len_mat(output_dir, res_pkl_file)
+
+
+@click.command(name="ex_pa_usage_mat")
+@click.option('--output_dir', type=str, required=True,
+              help='Directory which was used in previous steps to save output by prepare_input and infer_pa.')
+@click.option('--res_pkl_file', type=str, default="None",
+              help='Name of res pickle file that contains PASs. Its name will be included in the name of the final '
+                   'result.')
+@click.option('--min_reads', type=click.IntRange(1, USAGE_MAX_MIN_READS), default=1, show_default=True,
+              help='A cell has a usage in a gene (or UTR) record only with at least this many reads of the '
+                   'record\'s pA sites; above 1 the directory is named <res name>.min<N>.usage/.')
+def ex_pa_usage_mat(output_dir: str, res_pkl_file: str, min_reads: int):
+    """pA site x cell matrix of the per-cell site usage (PSI: the site's reads in a cell over the cell's reads of the
+    whole gene or UTR record) from res.gene.pkl / res.utr.pkl: the directory <res name>.usage/ with matrix.mtx.gz,
+    reads.mtx.gz (the cell's reads of the record wherever the usage is defined, an observed 0 included), features.tsv.gz
+    and barcodes.tsv.gz (those of ex_pa_cnt_mat --format mtx; sparse Matrix Market, as read by Seurat Read10X and scanpy
+    read_10x_mtx)."""
+    _ex_pa_usage_mat(output_dir, res_pkl_file, min_reads)
 
 
 @click.command(name="ex_pa_pseudobulk")
