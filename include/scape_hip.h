@@ -168,7 +168,7 @@ int scape_hip_em_counters(scape_hip_ctx *ctx, int64_t *rounds, int64_t *slab_ele
 int scape_hip_em_traffic(scape_hip_ctx *ctx, int64_t *mstep_tensor_bytes, int64_t *mstep_v_bytes_requested,
                          int64_t *mstep_v_bytes_unique, int64_t *mstep_launches);
 
-/* ---- reporting stages after merge_pa (report.inc) ---------------------------------------------------------------
+/* ---- reporting stages after merge_pa (report.inc; the three Matrix Market renderers: report_mtx.inc) -------------
  * ex_pa_cnt_mat (reference utils.py:438-553) and cal_exp_pa_len (utils.py:319-427, apa_core.py:1038-1063).  A batch is
  * n_rec records; record r owns reads [read_off[r], read_off[r+1]) of label / cb_id and has K[r] pA sites.  Barcode ids
  * map to columns (or cluster codes) through id2x[cb_id - id_min] for 0 <= cb_id - id_min < id_span, -1 = unknown.
@@ -212,7 +212,7 @@ int scape_hip_report_render_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rows
 int scape_hip_report_render_len_mtx(scape_hip_ctx *ctx, int32_t slot, int32_t n_rec, const int64_t *rec_row0,
                                     const int32_t *K, const int64_t *n_off, const double *n_arr, const int8_t *skip,
                                     int64_t row_no0, int32_t what, int64_t *bytes_out, int64_t *nnz_out);
-/* ex_pa_usage_mat (usage_mat.inc): the per-cell usage c_l / T of every pA site.  scape_hip_report_usage_totals forms, for
+/* ex_pa_usage_mat (report_mtx.inc): the per-cell usage c_l / T of every pA site.  scape_hip_report_usage_totals forms, for
    n_rec records of the last counts call (record i owns the count rows rec_row0[i] .. rec_row0[i] + K[i] - 1) and every
    column c, T[i][c] = the sum of the K[i] counts of column c (int32: a record holds at most INT32_MAX reads), and keeps
    them on the device beside the counts until the next scape_hip_report_counts, scape_hip_report_usage_totals or

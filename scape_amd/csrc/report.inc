@@ -1,5 +1,6 @@
 // report.inc - the count matrix of merge_pa's output on the device and the reporting stages that read it (included at
-// the end of scape_hip.hip, before perm.inc, which holds the permutation tests on the same counts).
+// the end of scape_hip.hip, before report_mtx.inc, which renders the same counts as Matrix Market entries, and perm.inc,
+// which holds the permutation tests on them).
 //
 //   ex_pa_cnt_mat   reference utils.py:438-553: per record, a pivot of (label < K) x barcode read counts, padded to every
 //                   barcode of barcode_index.csv and written as a dense, fully quoted CSV row per label.
@@ -14,10 +15,7 @@
 //   k_rep_rowlen / k_rep_scan / k_rep_render
 //                   byte length of every CSV row, their scan, and the row text itself (the host supplies each row's quoted
 //                   pa_info prefix); rows are rendered in blocks into one of two buffers so the host compresses block b
-//                   while the device renders block b + 1
-//   k_rep_mtx_rowlen / k_rep_scan / k_rep_mtx_render
-//                   the same rows as Matrix Market coordinate entries ("<row> <col> <count>\n", nonzero counts only,
-//                   1-based): per row its entries and bytes, their scans, and the entries, through the same two slots
+//                   while the device renders block b + 1; the slots and k_rep_scan serve report_mtx.inc as well
 //   k_rep_present / k_rep_groups / k_rep_hist
 //                   per record, the bitmap of cluster codes present, its compaction to the record's groups and the
 //                   (group, label) histogram; labels >= K share the last slot (they decide whether a group exists and
@@ -50,7 +48,7 @@ struct ReportState {
     DevBuf r_lab, r_cb, r_off, r_K, r_rowbase, r_map, r_cnt, r_tot, r_cflag, r_err;
     int32_t n_cols = 0;
     int64_t n_cnt_rows = 0;
-    // ex_pa_usage_mat (usage_mat.inc): per record of the last scape_hip_report_usage_totals call and column, the reads
+    // ex_pa_usage_mat (report_mtx.inc): per record of the last scape_hip_report_usage_totals call and column, the reads
     // with label < K ([record][column], int32); the records' first count rows and K on the device and on the host; the
     // number of those records, 0 until that call has followed the last counts call
     DevBuf u_tot, u_row0, u_K;
@@ -114,7 +112,7 @@ struct ReportState {
     std::vector<uint8_t> b_written;
     // render slots
     DevBuf s_rows[2], s_int[2], s_poff[2], s_pre[2], s_len[2], s_roff[2], s_out[2];
-    DevBuf s_nnz[2], s_noff[2];        // Matrix Market blocks: entries per row and their scan
+    DevBuf s_nnz[2], s_noff[2];        // report_mtx.inc's blocks: entries per row and their scan
     DevBuf s_lk[2], s_loff[2], s_lskip[2], s_lnarr[2];   // ex_pa_len_mat blocks: per record K, offset into n_arr, skip; n_arr
     DevBuf s_urec[2];                  // ex_pa_usage_mat blocks: per row its record among those of the totals
     void *host_out[2] = {nullptr, nullptr};
@@ -192,6 +190,15 @@ __device__ __forceinline__ int rep_digits64(uint64_t v) {
         ++n;
     }
     return n;
+}
+
+// the nd decimal digits of x at f, back to front
+template <typename U>
+__device__ __forceinline__ void rep_put_uint(char *f, U x, int nd) {
+    for (int d = nd - 1; d >= 0; --d) {
+        f[d] = (char)('0' + x % 10);
+        x /= 10;
+    }
 }
 
 // bytes a count adds over the constant zero field "0.0": "7" -> -2, "7.0" -> 0, "12" -> -1, "12.0" -> +1
@@ -326,11 +333,7 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_render(const int64_t *__res
                 f[5] = '"';
             } else {
                 const int nd = rep_digits((uint32_t)v);
-                uint32_t x = (uint32_t)v;
-                for (int d = nd - 1; d >= 0; --d) {
-                    f[2 + d] = (char)('0' + x % 10);
-                    x /= 10;
-                }
+                rep_put_uint(f + 2, (uint32_t)v, nd);
                 int e = 2 + nd;
                 if (!ii) {
                     f[e++] = '.';
@@ -342,330 +345,6 @@ __global__ __launch_bounds__(REP_THREADS) void k_rep_render(const int64_t *__res
         pos += tile;
     }
     if (threadIdx.x == 0) dst[pos] = '\n';
-}
-
-// ---- Matrix Market rendering ----------------------------------------------------------------------------------------
-// row i of a block: count row rows[i] of the last counts call, number row_no0 + i of the file; its entries are
-// "<row number> <column + 1> <count>\n" for the nonzero columns, ascending.  rnnz[i] = entries, rlen[i] = bytes
-__global__ __launch_bounds__(REP_THREADS) void k_rep_mtx_rowlen(const int64_t *__restrict__ rows, int64_t row_no0,
-                                                                int32_t n_cols, const int32_t *__restrict__ cnt,
-                                                                int64_t *__restrict__ rlen,
-                                                                int64_t *__restrict__ rnnz) {
-    __shared__ long long lds[REP_WAVES];
-    const int i = blockIdx.x;
-    const int32_t *row = cnt + rows[i] * n_cols;
-    long long n = 0, e = 0;
-    for (int c = threadIdx.x; c < n_cols; c += REP_THREADS) {
-        const int v = row[c];
-        if (v) {
-            ++n;
-            e += rep_digits((uint32_t)c + 1) + rep_digits((uint32_t)v);
-        }
-    }
-    n = rep_block_sum<long long, REP_WAVES>(n, lds);
-    e = rep_block_sum<long long, REP_WAVES>(e, lds);
-    if (threadIdx.x == 0) {
-        rnnz[i] = n;
-        rlen[i] = e + n * (rep_digits64((uint64_t)(row_no0 + i)) + 3);   // two spaces and the newline
-    }
-}
-
-// one workgroup per row, 256 columns per step: each lane's entry position is the tile's running offset plus the
-// exclusive scan of the entry lengths (0 for a zero count); the row number is formatted once, into LDS
-__global__ __launch_bounds__(REP_THREADS) void k_rep_mtx_render(const int64_t *__restrict__ rows, int64_t row_no0,
-                                                                int32_t n_cols, const int32_t *__restrict__ cnt,
-                                                                const int64_t *__restrict__ roff,
-                                                                char *__restrict__ out) {
-    __shared__ int lds[REP_WAVES];
-    __shared__ char row_txt[20];
-    const int i = blockIdx.x;
-    const int32_t *row = cnt + rows[i] * n_cols;
-    const uint64_t row_no = (uint64_t)(row_no0 + i);
-    const int rd = rep_digits64(row_no);
-    if (threadIdx.x == 0) {
-        uint64_t x = row_no;
-        for (int d = rd - 1; d >= 0; --d) {
-            row_txt[d] = (char)('0' + x % 10);
-            x /= 10;
-        }
-    }
-    __syncthreads();
-    char *dst = out + roff[i];
-    int64_t pos = 0;
-    for (int base = 0; base < n_cols; base += REP_THREADS) {
-        const int c = base + threadIdx.x;
-        const int v = c < n_cols ? row[c] : 0;
-        const int cd = v ? rep_digits((uint32_t)c + 1) : 0;
-        const int vd = v ? rep_digits((uint32_t)v) : 0;
-        const int elen = v ? rd + cd + vd + 3 : 0;
-        int tile;
-        const int ex = rep_block_excl<int, REP_WAVES>(elen, lds, &tile);
-        if (v) {
-            char *f = dst + pos + ex;
-            for (int d = 0; d < rd; ++d) f[d] = row_txt[d];
-            f[rd] = ' ';
-            f += rd + 1;
-            uint32_t x = (uint32_t)c + 1;
-            for (int d = cd - 1; d >= 0; --d) {
-                f[d] = (char)('0' + x % 10);
-                x /= 10;
-            }
-            f[cd] = ' ';
-            f += cd + 1;
-            x = (uint32_t)v;
-            for (int d = vd - 1; d >= 0; --d) {
-                f[d] = (char)('0' + x % 10);
-                x /= 10;
-            }
-            f[vd] = '\n';
-        }
-        pos += tile;
-    }
-}
-
-// ---- expected pA length per (record, column) ------------------------------------------------------------------------
-// ex_pa_len_mat: the reference's exp_pa_len (apa_core.py:1038-1052) of one cell's reads in one record, from the
-// record's K count rows.  For a column with T = sum_l c_l > 0 reads:  v = 1.0 when K == 1, otherwise the sum of
-// p_l = (c_l / T) * n_l over l = 0 .. K-1 in the order of numpy's pairwise sum, which np.sum(ws * n_arr) runs (the host
-// uploads n_l = 1 + 9 (a_l - a_0) / (a_{K-1} - a_0) as numpy gives it).  Every operation is a correctly rounded IEEE
-// one with contraction off, so v is the reference's double bit for bit.  A thread owns a column and keeps T, the eight
-// accumulators and the decimal digits in registers.
-//
-// p_l; a zero count gives (+0) * n_l without the division (0 / T is +0 as well)
-__device__ __forceinline__ double rep_len_term(const int32_t *__restrict__ col, int64_t stride,
-                                               const double *__restrict__ nn, int l, double T) {
-#pragma clang fp contract(off)
-    const int32_t c = col[l * stride];
-    const double ws = c ? (double)c / T : 0.0;
-    return ws * nn[l];
-}
-
-// numpy's pairwise sum of p_a .. p_{a+n-1} for n <= 128: sequential from 0.0 below eight terms, otherwise eight
-// accumulators over the multiples of eight, their tree, and the remainder one by one
-__device__ __forceinline__ double rep_len_leaf(const int32_t *__restrict__ col, int64_t stride,
-                                               const double *__restrict__ nn, int a, int n, double T) {
-#pragma clang fp contract(off)
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += rep_len_term(col, stride, nn, a + i, T);
-        return res;
-    }
-    double r0 = rep_len_term(col, stride, nn, a, T), r1 = rep_len_term(col, stride, nn, a + 1, T);
-    double r2 = rep_len_term(col, stride, nn, a + 2, T), r3 = rep_len_term(col, stride, nn, a + 3, T);
-    double r4 = rep_len_term(col, stride, nn, a + 4, T), r5 = rep_len_term(col, stride, nn, a + 5, T);
-    double r6 = rep_len_term(col, stride, nn, a + 6, T), r7 = rep_len_term(col, stride, nn, a + 7, T);
-    int i = 8;
-    for (; i < n - n % 8; i += 8) {
-        r0 += rep_len_term(col, stride, nn, a + i, T);
-        r1 += rep_len_term(col, stride, nn, a + i + 1, T);
-        r2 += rep_len_term(col, stride, nn, a + i + 2, T);
-        r3 += rep_len_term(col, stride, nn, a + i + 3, T);
-        r4 += rep_len_term(col, stride, nn, a + i + 4, T);
-        r5 += rep_len_term(col, stride, nn, a + i + 5, T);
-        r6 += rep_len_term(col, stride, nn, a + i + 6, T);
-        r7 += rep_len_term(col, stride, nn, a + i + 7, T);
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < n; ++i) res += rep_len_term(col, stride, nn, a + i, T);
-    return res;
-}
-
-// Above 128 terms numpy halves: n2 = n / 2 rounded down to a multiple of eight, sum(first n2) + sum(rest), each half the
-// same way.  The halves are walked left to right with the open levels on an explicit stack: rest[d] is the length of
-// level d's right half, left[d] the finished sum of its left half, bit d of `right` says that the walk is inside the
-// right half.  A level at least halves the length, so K < 2^31 opens at most 24 of the 32 levels; the stack is touched
-// only when K > 128.  numpy adds the sum to its initial 0.0, which turns a -0.0 into +0.0
-#define REP_LEN_LEVELS 32
-__device__ __forceinline__ double rep_len_value(const int32_t *__restrict__ col, int64_t stride,
-                                                const double *__restrict__ nn, int K, double T) {
-#pragma clang fp contract(off)
-    if (K == 1) return 1.0;
-    if (K <= 128) return 0.0 + rep_len_leaf(col, stride, nn, 0, K, T);
-    int rest[REP_LEN_LEVELS];
-    double left[REP_LEN_LEVELS];
-    uint32_t right = 0;
-    int depth = 0, pos = 0, cur = K;
-    double v;
-    for (;;) {
-        while (cur > 128 && depth < REP_LEN_LEVELS) {
-            int n2 = cur / 2;
-            n2 -= n2 % 8;
-            rest[depth] = cur - n2;
-            right &= ~(1u << depth);
-            ++depth;
-            cur = n2;
-        }
-        v = rep_len_leaf(col, stride, nn, pos, cur > 128 ? 128 : cur, T);   // never above 128 (see the level bound)
-        pos += cur;
-        while (depth > 0 && ((right >> (depth - 1)) & 1u)) {
-            --depth;
-            v = left[depth] + v;
-        }
-        if (depth == 0) break;
-        left[depth - 1] = v;
-        right |= 1u << (depth - 1);
-        cur = rest[depth - 1];
-    }
-    return 0.0 + v;
-}
-
-// Python's '%.6f' % v in integers: v = +-m 2^-s with m < 2^53, x = m 10^6 < 2^73, q = x / 2^s rounded half to even on the
-// dropped bits; the text is the sign (of -0.0 and of what rounds to zero as well), the digits of q / 10^6, a point and
-// the six digits of q % 10^6.  The caller keeps |v| < 2^31, so s >= 22 and q < 2^51; whatever v is, q fits 64 bits of
-// digits and both passes get the same length from it.  Returns q, *neg = the sign bit
-__device__ __forceinline__ uint64_t rep_fixed6(double v, int *neg) {
-    const uint64_t bits = (uint64_t)__double_as_longlong(v);
-    *neg = (int)(bits >> 63);
-    const int ex = (int)((bits >> 52) & 0x7ff);
-    const uint64_t frac = bits & ((1ull << 52) - 1);
-    const uint64_t m = ex ? frac | (1ull << 52) : frac;
-    const int s = ex ? 1075 - ex : 1074;
-    const unsigned __int128 x = (unsigned __int128)m * 1000000u;
-    if (s >= 74) return 0;               // x < 2^73 is less than half of 2^s
-    if (s <= 0) return (uint64_t)x;      // |v| >= 2^52, outside the contract
-    uint64_t q = (uint64_t)(x >> s);
-    const unsigned __int128 rem = x & ((((unsigned __int128)1) << s) - 1), half = ((unsigned __int128)1) << (s - 1);
-    if (rem > half || (rem == half && (q & 1))) ++q;
-    return q;
-}
-
-__device__ __forceinline__ int rep_fixed6_len(uint64_t q, int neg) { return neg + rep_digits64(q / 1000000u) + 7; }
-
-__device__ __forceinline__ void rep_fixed6_put(char *f, uint64_t q, int neg, int len) {
-    uint32_t fr = (uint32_t)(q % 1000000u);
-    uint64_t ip = q / 1000000u;
-    for (int d = 1; d <= 6; ++d) {
-        f[len - d] = (char)('0' + fr % 10);
-        fr /= 10;
-    }
-    f[len - 7] = '.';
-    for (int d = len - 8; d >= neg; --d) {
-        f[d] = (char)('0' + ip % 10);
-        ip /= 10;
-    }
-    if (neg) f[0] = '-';
-}
-
-// one column of record i: T = its reads with label < K (0: no entry) and, for the value text (what == 0), q and the sign
-// of the expected pA length; returns the bytes of the entry's last field
-__device__ __forceinline__ int rep_len_field(const int32_t *__restrict__ col, int64_t stride,
-                                             const double *__restrict__ nn, int K, int what, uint32_t *T_out,
-                                             uint64_t *q_out, int *neg_out) {
-    uint32_t T = 0;
-    for (int l = 0; l < K; ++l) T += (uint32_t)col[l * stride];
-    *T_out = T;
-    *q_out = 0;
-    *neg_out = 0;
-    if (!T) return 0;
-    if (what) return rep_digits(T);
-    *q_out = rep_fixed6(rep_len_value(col, stride, nn, K, (double)T), neg_out);
-    return rep_fixed6_len(*q_out, *neg_out);
-}
-
-// record i of a block: count rows rec_row0[i] .. + Ks[i] of the last counts call, n_l at n_arr + n_off[i], number
-// row_no0 + i of the file; skip[i] != 0 gives it no entry.  Its entries are "<row number> <column + 1> <field>\n" for the
-// columns with T > 0, ascending; the field is the value text (what == 0) or T (what == 1).  rnnz[i] = entries,
-// rlen[i] = bytes.  Thread t takes the columns t, t + 256, ...: a workgroup reads 256 neighbouring counts of a row at a time
-__global__ __launch_bounds__(REP_THREADS) void k_rep_len_mtx_rowlen(const int64_t *__restrict__ rec_row0,
-                                                                    const int32_t *__restrict__ Ks,
-                                                                    const int64_t *__restrict__ n_off,
-                                                                    const double *__restrict__ n_arr,
-                                                                    const int8_t *__restrict__ skip, int64_t row_no0,
-                                                                    int32_t what, int32_t n_cols,
-                                                                    const int32_t *__restrict__ cnt,
-                                                                    int64_t *__restrict__ rlen,
-                                                                    int64_t *__restrict__ rnnz) {
-    __shared__ long long lds[REP_WAVES];
-    const int i = blockIdx.x;
-    long long n = 0, e = 0;
-    if (!skip[i]) {
-        const int K = Ks[i];
-        const int32_t *rec = cnt + rec_row0[i] * n_cols;
-        const double *nn = n_arr + n_off[i];
-        for (int c = threadIdx.x; c < n_cols; c += REP_THREADS) {
-            uint32_t T;
-            uint64_t q;
-            int neg;
-            const int fd = rep_len_field(rec + c, n_cols, nn, K, what, &T, &q, &neg);
-            if (T) {
-                ++n;
-                e += rep_digits((uint32_t)c + 1) + fd;
-            }
-        }
-    }
-    n = rep_block_sum<long long, REP_WAVES>(n, lds);
-    e = rep_block_sum<long long, REP_WAVES>(e, lds);
-    if (threadIdx.x == 0) {
-        rnnz[i] = n;
-        rlen[i] = e + n * (rep_digits64((uint64_t)(row_no0 + i)) + 3);   // two spaces and the newline
-    }
-}
-
-// one workgroup per record, 256 columns per step, as k_rep_mtx_render: each lane's entry position is the tile's running
-// offset plus the exclusive scan of the entry lengths (0 for a column without reads below K)
-__global__ __launch_bounds__(REP_THREADS) void k_rep_len_mtx_render(const int64_t *__restrict__ rec_row0,
-                                                                    const int32_t *__restrict__ Ks,
-                                                                    const int64_t *__restrict__ n_off,
-                                                                    const double *__restrict__ n_arr,
-                                                                    const int8_t *__restrict__ skip, int64_t row_no0,
-                                                                    int32_t what, int32_t n_cols,
-                                                                    const int32_t *__restrict__ cnt,
-                                                                    const int64_t *__restrict__ roff,
-                                                                    char *__restrict__ out) {
-    __shared__ int lds[REP_WAVES];
-    __shared__ char row_txt[20];
-    const int i = blockIdx.x;
-    if (skip[i] || roff[i + 1] == roff[i]) return;   // the same for every thread of the workgroup
-    const int K = Ks[i];
-    const int32_t *rec = cnt + rec_row0[i] * n_cols;
-    const double *nn = n_arr + n_off[i];
-    const uint64_t row_no = (uint64_t)(row_no0 + i);
-    const int rd = rep_digits64(row_no);
-    if (threadIdx.x == 0) {
-        uint64_t x = row_no;
-        for (int d = rd - 1; d >= 0; --d) {
-            row_txt[d] = (char)('0' + x % 10);
-            x /= 10;
-        }
-    }
-    __syncthreads();
-    char *dst = out + roff[i];
-    int64_t pos = 0;
-    for (int base = 0; base < n_cols; base += REP_THREADS) {
-        const int c = base + threadIdx.x;
-        uint32_t T = 0;
-        uint64_t q = 0;
-        int neg = 0, fd = 0;
-        if (c < n_cols) fd = rep_len_field(rec + c, n_cols, nn, K, what, &T, &q, &neg);
-        const int cd = T ? rep_digits((uint32_t)c + 1) : 0;
-        const int elen = T ? rd + cd + fd + 3 : 0;
-        int tile;
-        const int ex = rep_block_excl<int, REP_WAVES>(elen, lds, &tile);
-        if (T) {
-            char *f = dst + pos + ex;
-            for (int d = 0; d < rd; ++d) f[d] = row_txt[d];
-            f[rd] = ' ';
-            f += rd + 1;
-            uint32_t x = (uint32_t)c + 1;
-            for (int d = cd - 1; d >= 0; --d) {
-                f[d] = (char)('0' + x % 10);
-                x /= 10;
-            }
-            f[cd] = ' ';
-            f += cd + 1;
-            if (what) {
-                x = T;
-                for (int d = fd - 1; d >= 0; --d) {
-                    f[d] = (char)('0' + x % 10);
-                    x /= 10;
-                }
-            } else {
-                rep_fixed6_put(f, q, neg, fd);
-            }
-            f[fd] = '\n';
-        }
-        pos += tile;
-    }
 }
 
 // ---- segment sums (pseudo-bulk) ---------------------------------------------------------------------------------------
@@ -814,6 +493,15 @@ static int rep_upload_map(scape_hip_ctx *c, ReportState *s, int64_t id_span, con
     return 0;
 }
 
+// a render call takes a slot over: its pinned host buffer is handed over again once the copy queued into it has run
+static int rep_slot_claim(ReportState *s, int32_t slot) {
+    if (s->pending[slot]) {
+        HIPCHK(hipEventSynchronize(s->done[slot]));
+        s->pending[slot] = false;
+    }
+    return 0;
+}
+
 // a render slot's device text buffer, pinned host buffer and event, for a block of `total` bytes
 static int rep_slot_out(ReportState *s, int32_t slot, int64_t total) {
     if (s->s_out[slot].ensure(total)) return 1;
@@ -883,7 +571,7 @@ int scape_hip_report_counts(scape_hip_ctx *c, int32_t n_rec, const int64_t *read
     if (rep_fetch_err(c, s, bad_read_out)) return 1;
     s->n_cols = n_cols;
     s->n_cnt_rows = rows;
-    s->u_n_rec = 0;                      // the totals of usage_mat.inc belonged to the counts before
+    s->u_n_rec = 0;                      // the totals of report_mtx.inc belonged to the counts before
     return 0;
 }
 
@@ -899,10 +587,7 @@ int scape_hip_report_render(scape_hip_ctx *c, int32_t slot, int32_t n_rows, cons
     if (pre_off[0] != 0) return fail("pre_off must start at 0");
     for (int i = 0; i < n_rows; ++i)
         if (pre_off[i + 1] < pre_off[i]) return fail("pre_off must be non-decreasing");
-    if (s->pending[slot]) {              // the host buffer of this slot is handed over again
-        HIPCHK(hipEventSynchronize(s->done[slot]));
-        s->pending[slot] = false;
-    }
+    if (rep_slot_claim(s, slot)) return 1;
     const int64_t pre_n = pre_off[n_rows];
     if (s->s_rows[slot].ensure(n_rows * 8) || s->s_int[slot].ensure(n_rows) || s->s_poff[slot].ensure((n_rows + 1) * 8) ||
         s->s_pre[slot].ensure(std::max<int64_t>(pre_n, 1)) || s->s_len[slot].ensure(n_rows * 8) ||
@@ -930,111 +615,6 @@ int scape_hip_report_render(scape_hip_ctx *c, int32_t slot, int32_t n_rows, cons
     HIPCHK(hipGetLastError());
     if (rep_slot_queue(c, s, slot, total)) return 1;
     *bytes_out = total;
-    return 0;
-}
-
-int scape_hip_report_render_mtx(scape_hip_ctx *c, int32_t slot, int32_t n_rows, const int64_t *rows, int64_t row_no0,
-                                int64_t *bytes_out, int64_t *nnz_out) {
-    CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
-    if (slot < 0 || slot > 1 || n_rows <= 0 || !rows || !bytes_out || !nnz_out) return fail("bad argument");
-    if (row_no0 < 1 || row_no0 > INT64_MAX - n_rows) return fail("row_no0 out of range");
-    for (int i = 0; i < n_rows; ++i)
-        if (rows[i] < 0 || rows[i] >= s->n_cnt_rows) return fail("row index out of range");
-    if (s->pending[slot]) {              // the host buffer of this slot is handed over again
-        HIPCHK(hipEventSynchronize(s->done[slot]));
-        s->pending[slot] = false;
-    }
-    const int64_t n = n_rows;
-    if (s->s_rows[slot].ensure(n * 8) || s->s_len[slot].ensure(n * 8) || s->s_roff[slot].ensure((n + 1) * 8) ||
-        s->s_nnz[slot].ensure(n * 8) || s->s_noff[slot].ensure((n + 1) * 8))
-        return 1;
-    HIPCHK(hipMemcpyAsync(s->s_rows[slot].p, rows, n * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_rep_mtx_rowlen, dim3(n_rows), dim3(REP_THREADS), 0, c->stream, s->s_rows[slot].as<int64_t>(),
-                       row_no0, s->n_cols, s->r_cnt.as<int32_t>(), s->s_len[slot].as<int64_t>(),
-                       s->s_nnz[slot].as<int64_t>());
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->s_len[slot].as<int64_t>(), n_rows,
-                       s->s_roff[slot].as<int64_t>());
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->s_nnz[slot].as<int64_t>(), n_rows,
-                       s->s_noff[slot].as<int64_t>());
-    HIPCHK(hipGetLastError());
-    int64_t total = 0, nnz = 0;
-    HIPCHK(hipMemcpyAsync(&total, s->s_roff[slot].as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&nnz, s->s_noff[slot].as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (total <= 0) return fail("empty render block");
-    if (rep_slot_out(s, slot, total)) return 1;
-    hipLaunchKernelGGL(k_rep_mtx_render, dim3(n_rows), dim3(REP_THREADS), 0, c->stream, s->s_rows[slot].as<int64_t>(),
-                       row_no0, s->n_cols, s->r_cnt.as<int32_t>(), s->s_roff[slot].as<int64_t>(),
-                       s->s_out[slot].as<char>());
-    HIPCHK(hipGetLastError());
-    if (rep_slot_queue(c, s, slot, total)) return 1;
-    *bytes_out = total;
-    *nnz_out = nnz;
-    return 0;
-}
-
-int scape_hip_report_render_len_mtx(scape_hip_ctx *c, int32_t slot, int32_t n_rec, const int64_t *rec_row0,
-                                    const int32_t *K, const int64_t *n_off, const double *n_arr, const int8_t *skip,
-                                    int64_t row_no0, int32_t what, int64_t *bytes_out, int64_t *nnz_out) {
-    CTX_ENTER(c);
-    ReportState *s = c->rep;
-    if (!s || !s->n_cnt_rows) return fail("scape_hip_report_counts has not been called");
-    if (slot < 0 || slot > 1 || n_rec <= 0 || !rec_row0 || !K || !n_off || !n_arr || !skip || !bytes_out || !nnz_out)
-        return fail("bad argument");
-    if (what < 0 || what > 1) return fail("what must be 0 (value) or 1 (reads)");
-    if (row_no0 < 1 || row_no0 > INT64_MAX - n_rec) return fail("row_no0 out of range");
-    int64_t n_vals = 1;                  // doubles of n_arr that the records name
-    for (int i = 0; i < n_rec; ++i) {
-        if (K[i] < 1 || rec_row0[i] < 0 || rec_row0[i] > s->n_cnt_rows - K[i]) return fail("record rows out of range");
-        if (skip[i]) continue;
-        if (n_off[i] < 0 || n_off[i] > INT64_MAX / 16 - K[i]) return fail("n_off out of range");
-        n_vals = std::max(n_vals, n_off[i] + K[i]);
-    }
-    if (s->pending[slot]) {              // the host buffer of this slot is handed over again
-        HIPCHK(hipEventSynchronize(s->done[slot]));
-        s->pending[slot] = false;
-    }
-    const int64_t n = n_rec;
-    if (s->s_rows[slot].ensure(n * 8) || s->s_len[slot].ensure(n * 8) || s->s_roff[slot].ensure((n + 1) * 8) ||
-        s->s_nnz[slot].ensure(n * 8) || s->s_noff[slot].ensure((n + 1) * 8) || s->s_lk[slot].ensure(n * 4) ||
-        s->s_loff[slot].ensure(n * 8) || s->s_lskip[slot].ensure(n) || s->s_lnarr[slot].ensure(n_vals * 8))
-        return 1;
-    HIPCHK(hipMemcpyAsync(s->s_rows[slot].p, rec_row0, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(s->s_lk[slot].p, K, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(s->s_loff[slot].p, n_off, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(s->s_lskip[slot].p, skip, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(s->s_lnarr[slot].p, n_arr, n_vals * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_rep_len_mtx_rowlen, dim3(n_rec), dim3(REP_THREADS), 0, c->stream,
-                       s->s_rows[slot].as<int64_t>(), s->s_lk[slot].as<int32_t>(), s->s_loff[slot].as<int64_t>(),
-                       s->s_lnarr[slot].as<double>(), s->s_lskip[slot].as<int8_t>(), row_no0, what, s->n_cols,
-                       s->r_cnt.as<int32_t>(), s->s_len[slot].as<int64_t>(), s->s_nnz[slot].as<int64_t>());
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->s_len[slot].as<int64_t>(), n_rec,
-                       s->s_roff[slot].as<int64_t>());
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_rep_scan, dim3(1), dim3(REP_SCAN_THREADS), 0, c->stream, s->s_nnz[slot].as<int64_t>(), n_rec,
-                       s->s_noff[slot].as<int64_t>());
-    HIPCHK(hipGetLastError());
-    int64_t total = 0, nnz = 0;
-    HIPCHK(hipMemcpyAsync(&total, s->s_roff[slot].as<int64_t>() + n_rec, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&nnz, s->s_noff[slot].as<int64_t>() + n_rec, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (total < 0) return fail("negative render block size");
-    if (rep_slot_out(s, slot, std::max<int64_t>(total, 1))) return 1;
-    if (total) {
-        hipLaunchKernelGGL(k_rep_len_mtx_render, dim3(n_rec), dim3(REP_THREADS), 0, c->stream,
-                           s->s_rows[slot].as<int64_t>(), s->s_lk[slot].as<int32_t>(), s->s_loff[slot].as<int64_t>(),
-                           s->s_lnarr[slot].as<double>(), s->s_lskip[slot].as<int8_t>(), row_no0, what, s->n_cols,
-                           s->r_cnt.as<int32_t>(), s->s_roff[slot].as<int64_t>(), s->s_out[slot].as<char>());
-        HIPCHK(hipGetLastError());
-    }
-    if (rep_slot_queue(c, s, slot, total)) return 1;   // a block without an entry is fetched as 0 bytes
-    *bytes_out = total;
-    *nnz_out = nnz;
     return 0;
 }
 

@@ -1727,5 +1727,5 @@ int scape_hip_em_traffic(scape_hip_ctx *c, int64_t *mstep_tensor_bytes, int64_t 
 }  // extern "C"
 
 #include "report.inc"
-#include "usage_mat.inc"
+#include "report_mtx.inc"
 #include "perm.inc"

@@ -415,11 +415,11 @@ def _ex_pa_cnt_mat(output_dir: str, res_pkl_file: str, device=None, fmt="tsv"):
     features.tsv.gz and barcodes.tsv.gz (_ex_pa_cnt_mtx)"""
     if fmt not in ("tsv", "mtx"):
         raise ValueError(f"unknown count matrix format {fmt!r} (tsv or mtx)")
+    if fmt == "mtx":
+        return _ex_pa_cnt_mtx(output_dir, res_pkl_file, device)
     inp = _read_inputs(output_dir, res_pkl_file, with_cb=True)
     n_cols = inp.n_cols
     idmap = _IdMap(inp.col_ids, np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
-    if fmt == "mtx":
-        return _ex_pa_cnt_mtx(output_dir, res_pkl_file, inp, idmap, device)
     outpath = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt.tsv.gz"))
     hdr = io.StringIO()
     csv.writer(hdr, delimiter=',', quoting=csv.QUOTE_ALL, lineterminator='\n').writerow(["pa_info"] + inp.cb_lst)
@@ -504,54 +504,83 @@ def _finish_mtx(path, header, body, times):
     times["finish"] += timer() - t0
 
 
-def _ex_pa_cnt_mtx(output_dir, res_pkl_file, inp, idmap, device):
-    """the count matrix as a 10x-style directory <res>.cnt/: matrix.mtx.gz (the dense file's rows and columns, nonzero
-    counts only, row-major), features.tsv.gz (per row: pa_info, pa_info, "Gene Expression"; Seurat's Read10X names rows
-    from column 2, scanpy's read_10x_mtx from column 2 and keeps only "Gene Expression" rows) and barcodes.tsv.gz (the
-    CB column).  The matrix header holds nnz, known only at the end: the body's gzip members go to an anonymous
-    temporary file and are copied behind the header's member.  The three are renamed from .part once all are complete."""
-    n_cols = inp.n_cols
+def _mtx_run(output_dir, res_pkl_file, tag, names, banners, device, cost, batch, refuse, done):
+    """A 10x-style directory <res><tag>/ of one matrix per banner: names = the matrices' files, features.tsv.gz and
+    barcodes.tsv.gz (the CB column).  batch(ctx, bat, n_cols, sinks, times) renders a counted batch of at most
+    cost(n_cols) device bytes per record into the sinks, one per matrix; the first one carries features.tsv and the
+    row count.  A matrix's header holds its nnz, known only at the end: its body's gzip members go to an anonymous
+    temporary file and are copied behind the header's member.  refuse(*sinks), if given, returns what is wrong with
+    the finished entry counts, or None.  The files are renamed from .part once all are complete; `done` is the
+    command's closing message."""
+    inp = _read_inputs(output_dir, res_pkl_file, with_cb=True)
+    n_cols, m = inp.n_cols, len(banners)
+    idmap = _IdMap(inp.col_ids, np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
     bc_text = _tsv_lines([str(b) for b in inp.cb_lst], lambda s: s + "\n", "barcode")
-    out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".cnt"))
-    with _dir_run(device, out_dir, MTX_FILES) as run:
-        with tempfile.TemporaryFile(dir=out_dir) as body, open(run.parts[1], "wb") as ffh, \
-                ThreadPoolExecutor(_hostlib.host_threads()) as pool:
-            _write_gzip(run.parts[2], bc_text, pool, run.times)
-            sink = _MtxSink(_GzipWriter(body, pool, run.times), _GzipWriter(ffh, pool, run.times))
-            ctx = run.device()
-            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
-                _render_mtx_batch(ctx, bat, n_cols, sink, run.times)
-            _finish_mtx(run.parts[0], f"{MTX_BANNER}{sink.n_rows} {n_cols} {sink.nnz}\n", body, run.times)
-    print("Finish counting for each gene")
+    out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", tag))
+    with _dir_run(device, out_dir, names) as run, contextlib.ExitStack() as stack:
+        bodies = [stack.enter_context(tempfile.TemporaryFile(dir=out_dir)) for _ in banners]
+        ffh = stack.enter_context(open(run.parts[m], "wb"))
+        pool = stack.enter_context(ThreadPoolExecutor(_hostlib.host_threads()))
+        _write_gzip(run.parts[m + 1], bc_text, pool, run.times)
+        sinks = [_MtxSink(_GzipWriter(body, pool, run.times), None if k else _GzipWriter(ffh, pool, run.times))
+                 for k, body in enumerate(bodies)]
+        ctx = run.device()
+        for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, cost(n_cols), _budget(ctx), run.times):
+            batch(ctx, bat, n_cols, sinks, run.times)
+        wrong = refuse(*sinks) if refuse else None
+        if wrong:
+            raise _lib.ScapeHipError(wrong)
+        for path, banner, sink, body in zip(run.parts, banners, sinks, bodies):
+            _finish_mtx(path, f"{banner}{sinks[0].n_rows} {n_cols} {sink.nnz}\n", body, run.times)
+    print(done)
     print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
     return out_dir
 
 
-def _render_mtx_batch(ctx, bat, n_cols, sink, times):
-    """the rows of one counted batch, numbered on from sink.n_rows: features lines on the host, Matrix Market entries
-    on the device, in blocks cut by their text size"""
+def _render_entries(ctx, sinks, names, noun, blocks, call, times):
+    """The len(names) rows of one counted batch, numbered on from sinks[0].n_rows: their features lines (`names`, a
+    `noun` each) on the host, then for every sink the Matrix Market entries on the device, in the blocks (a, b) of
+    blocks[what], what = the sink's place.  call(slot, a, b, what, nbytes, nnz) issues the entry point's call for one
+    block; it looks the entry point up on ctx.lib when it is called."""
+    first = sinks[0]
+    first.features.submit(memoryview(_tsv_lines(names, lambda s: f"{s}\t{s}\tGene Expression\n", noun).encode()))
+
+    def render(sink, what, slot, a, b):
+        nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
+        t0 = timer()
+        call(slot, a, b, what, ctypes.byref(nbytes), ctypes.byref(nnz))
+        times["render"] += timer() - t0
+        sink.nnz += nnz.value
+    for what, sink in enumerate(sinks):
+        _two_slot_blocks(ctx, sink.matrix, blocks[what], functools.partial(render, sink, what), times)
+    first.features.drain()
+    first.n_rows += len(names)
+
+
+def _ex_pa_cnt_mtx(output_dir, res_pkl_file, device):
+    """the count matrix as a 10x-style directory <res>.cnt/: matrix.mtx.gz (the dense file's rows and columns, nonzero
+    counts only, row-major), features.tsv.gz (per row: pa_info, pa_info, "Gene Expression"; Seurat's Read10X names rows
+    from column 2, scanpy's read_10x_mtx from column 2 and keeps only "Gene Expression" rows) and barcodes.tsv.gz"""
+    return _mtx_run(output_dir, res_pkl_file, ".cnt", MTX_FILES, (MTX_BANNER,), device, _batch_cost, _render_mtx_batch,
+                    None, "Finish counting for each gene")
+
+
+def _render_mtx_batch(ctx, bat, n_cols, sinks, times):
+    """the kept rows of one counted batch, in blocks cut by their text size"""
     _rowbase, rows, owner, label = _kept_rows(bat)
     if not len(rows):
         return
-    pa = _pa_infos(bat.recs, owner, label)
-    sink.features.submit(memoryview(_tsv_lines(pa, lambda s: f"{s}\t{s}\tGene Expression\n", "pa_info").encode()))
     # blocks cut against an upper bound of each row's text: at most min(reads, barcodes) entries
     # "<row number> <column> <count>\n", the count at most the row's reads
-    row_no0 = sink.n_rows + 1
+    row_no0 = sinks[0].n_rows + 1
     tot = bat.row_tot[rows]
     width = len(str(row_no0 + len(rows) - 1)) + len(str(n_cols)) + 3 + _digits(tot)
-    blocks = _cut_blocks(np.minimum(tot, n_cols) * width)
 
-    def render(slot, a, b):
-        nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
-        t0 = timer()
-        check(ctx.lib.scape_hip_report_render_mtx(ctx.h, slot, b - a, ptr(rows[a:b], P_i64), row_no0 + a,
-                                                  ctypes.byref(nbytes), ctypes.byref(nnz)), "report_render_mtx")
-        times["render"] += timer() - t0
-        sink.nnz += nnz.value
-    _two_slot_blocks(ctx, sink.matrix, blocks, render, times)
-    sink.features.drain()
-    sink.n_rows += len(rows)
+    def call(slot, a, b, _what, nbytes, nnz):
+        check(ctx.lib.scape_hip_report_render_mtx(ctx.h, slot, b - a, ptr(rows[a:b], P_i64), row_no0 + a, nbytes, nnz),
+              "report_render_mtx")
+    _render_entries(ctx, sinks, _pa_infos(bat.recs, owner, label), "pa_info",
+                    [_cut_blocks(np.minimum(tot, n_cols) * width)], call, times)
 
 
 # ---------------------------------------------------------------- ex_pa_len_mat
@@ -581,13 +610,11 @@ def _len_n_arr(para):
     return n_arr, ok
 
 
-def _render_len_batch(ctx, bat, n_cols, values, reads, times):
-    """the records of one counted batch, numbered on from values.n_rows: features lines on the host, the entries of both
-    matrices on the device (values.matrix, then reads.matrix, from the same counts), in blocks cut by their text size"""
+def _render_len_batch(ctx, bat, n_cols, sinks, times):
+    """the records of one counted batch into the value and the reads matrix (from the same counts), in blocks cut by
+    their text size"""
     recs, K = bat.recs, bat.K.astype(np.int64)
     n_rec = len(recs)
-    names = [":".join(p.gene_info_str.split(":")[1:3]) for p in recs]
-    values.features.submit(memoryview(_tsv_lines(names, lambda s: f"{s}\t{s}\tGene Expression\n", "gene_id").encode()))
     rowbase = np.ascontiguousarray(np.cumsum(K) - K)
     n_arrs, oks = zip(*(_len_n_arr(p) for p in recs))
     for p, ok in zip(recs, oks):
@@ -602,7 +629,7 @@ def _render_len_batch(ctx, bat, n_cols, values, reads, times):
     # blocks cut against an upper bound of each record's text: at most min(reads, barcodes) entries "<row number>
     # <column> <field>\n", the field at most the sign, the digits of the record's largest |n_l| + 1, the point and six
     # digits, or the digits of the record's reads
-    row_no0 = values.n_rows + 1
+    row_no0 = sinks[0].n_rows + 1
     tot = np.add.reduceat(bat.row_tot, rowbase) * (skip == 0)
     big = np.array([float(np.max(np.abs(a))) for a in n_arrs])
     big[skip != 0] = 0.0
@@ -610,20 +637,17 @@ def _render_len_batch(ctx, bat, n_cols, values, reads, times):
     width = len(str(row_no0 + n_rec - 1)) + len(str(n_cols)) + 3 + field
     blocks = _cut_blocks(np.minimum(tot, n_cols) * width)
 
-    def render(sink, what, slot, a, b):
-        nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
+    def call(slot, a, b, what, nbytes, nnz):
         first = int(n_off[a])            # the block's part of n_arr
-        t0 = timer()
         check(ctx.lib.scape_hip_report_render_len_mtx(
             ctx.h, slot, b - a, ptr(rowbase[a:b], P_i64), ptr(Ks[a:b], P_i32), ptr(n_off[a:b] - first, P_i64),
-            ptr(n_arr[first:]), ptr(skip[a:b], P_i8), row_no0 + a, what, ctypes.byref(nbytes), ctypes.byref(nnz)),
-            "report_render_len_mtx")
-        times["render"] += timer() - t0
-        sink.nnz += nnz.value
-    for sink, what in ((values, 0), (reads, 1)):
-        _two_slot_blocks(ctx, sink.matrix, blocks, functools.partial(render, sink, what), times)
-    values.features.drain()
-    values.n_rows += n_rec
+            ptr(n_arr[first:]), ptr(skip[a:b], P_i8), row_no0 + a, what, nbytes, nnz), "report_render_len_mtx")
+    _render_entries(ctx, sinks, [":".join(p.gene_info_str.split(":")[1:3]) for p in recs], "gene_id", [blocks, blocks],
+                    call, times)
+
+
+def _len_refuse(values, reads):
+    return "report_render_len_mtx: the two matrices differ in their entries" if values.nnz != reads.nnz else None
 
 
 def _ex_pa_len_mat(output_dir: str, res_pkl_file: str, device=None):
@@ -631,27 +655,8 @@ def _ex_pa_len_mat(output_dir: str, res_pkl_file: str, device=None):
     reads.mtx.gz (integer, the reads each value is computed from: the same entries in the same order), features.tsv.gz
     (per record: gene_id:utr_id, gene_id:utr_id, "Gene Expression") and barcodes.tsv.gz (the CB column).  The four are
     renamed from .part once all are complete."""
-    inp = _read_inputs(output_dir, res_pkl_file, with_cb=True)
-    n_cols = inp.n_cols
-    idmap = _IdMap(inp.col_ids, np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
-    bc_text = _tsv_lines([str(b) for b in inp.cb_lst], lambda s: s + "\n", "barcode")
-    out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", ".len"))
-    with _dir_run(device, out_dir, LEN_MTX_FILES) as run:
-        with tempfile.TemporaryFile(dir=out_dir) as vbody, tempfile.TemporaryFile(dir=out_dir) as rbody, \
-                open(run.parts[2], "wb") as ffh, ThreadPoolExecutor(_hostlib.host_threads()) as pool:
-            _write_gzip(run.parts[3], bc_text, pool, run.times)
-            values = _MtxSink(_GzipWriter(vbody, pool, run.times), _GzipWriter(ffh, pool, run.times))
-            reads = _MtxSink(_GzipWriter(rbody, pool, run.times), None)
-            ctx = run.device()
-            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _batch_cost(n_cols), _budget(ctx), run.times):
-                _render_len_batch(ctx, bat, n_cols, values, reads, run.times)
-            if values.nnz != reads.nnz:
-                raise _lib.ScapeHipError("report_render_len_mtx: the two matrices differ in their entries")
-            _finish_mtx(run.parts[0], f"{LEN_MTX_BANNER}{values.n_rows} {n_cols} {values.nnz}\n", vbody, run.times)
-            _finish_mtx(run.parts[1], f"{MTX_BANNER}{values.n_rows} {n_cols} {reads.nnz}\n", rbody, run.times)
-    print("Finish expected pA length for each gene and cell")
-    print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
-    return out_dir
+    return _mtx_run(output_dir, res_pkl_file, ".len", LEN_MTX_FILES, (LEN_MTX_BANNER, MTX_BANNER), device, _batch_cost,
+                    _render_len_batch, _len_refuse, "Finish expected pA length for each gene and cell")
 
 
 # ---------------------------------------------------------------- ex_pa_usage_mat
@@ -671,15 +676,12 @@ def _usage_batch_cost(n_cols):
     return lambda p: cost(p) + 4 * n_cols
 
 
-def _render_usage_batch(ctx, bat, n_cols, min_reads, values, reads, times):
-    """the kept rows of one counted batch, numbered on from values.n_rows: features lines on the host, the records'
-    column totals once on the device, then the entries of both matrices (values.matrix, then reads.matrix, from the
-    same counts and totals), in blocks cut by their text size"""
+def _render_usage_batch(min_reads, ctx, bat, n_cols, sinks, times):
+    """the kept rows of one counted batch into the value and the reads matrix: the records' column totals once on the
+    device, then the entries of both (from the same counts and totals), each in blocks cut by its own text size"""
     rowbase, rows, owner, label = _kept_rows(bat)
     if not len(rows):
         return
-    pa = _pa_infos(bat.recs, owner, label)
-    values.features.submit(memoryview(_tsv_lines(pa, lambda s: f"{s}\t{s}\tGene Expression\n", "pa_info").encode()))
     t0 = timer()
     check(ctx.lib.scape_hip_report_usage_totals(ctx.h, len(bat.recs), ptr(np.ascontiguousarray(rowbase), P_i64),
                                                 ptr(np.ascontiguousarray(bat.K), P_i32)), "report_usage_totals")
@@ -690,23 +692,22 @@ def _render_usage_batch(ctx, bat, n_cols, min_reads, values, reads, times):
     # wherever the cell has a read of the RECORD, so at most min(the record's reads, barcodes), of at most the digits of
     # the record's reads.  (One bound for both would cut the value matrix into blocks too small to keep the gzip
     # threads busy: a block is compressed in GZIP_PART pieces, one block at a time.)
-    row_no0 = values.n_rows + 1
+    row_no0 = sinks[0].n_rows + 1
     base = len(str(row_no0 + len(rows) - 1)) + len(str(n_cols)) + 3
     rec_tot = np.add.reduceat(bat.row_tot, rowbase)[owner]
     bounds = (np.minimum(bat.row_tot[rows], n_cols) * (base + 8), np.minimum(rec_tot, n_cols) * (base + _digits(rec_tot)))
 
-    def render(sink, what, slot, a, b):
-        nbytes, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
-        t0 = timer()
+    def call(slot, a, b, what, nbytes, nnz):
         check(ctx.lib.scape_hip_report_render_usage_mtx(
-            ctx.h, slot, b - a, ptr(rows[a:b], P_i64), ptr(row_rec[a:b], P_i32), row_no0 + a, min_reads, what,
-            ctypes.byref(nbytes), ctypes.byref(nnz)), "report_render_usage_mtx")
-        times["render"] += timer() - t0
-        sink.nnz += nnz.value
-    for sink, what in ((values, 0), (reads, 1)):
-        _two_slot_blocks(ctx, sink.matrix, _cut_blocks(bounds[what]), functools.partial(render, sink, what), times)
-    values.features.drain()
-    values.n_rows += len(rows)
+            ctx.h, slot, b - a, ptr(rows[a:b], P_i64), ptr(row_rec[a:b], P_i32), row_no0 + a, min_reads, what, nbytes,
+            nnz), "report_render_usage_mtx")
+    _render_entries(ctx, sinks, _pa_infos(bat.recs, owner, label), "pa_info", [_cut_blocks(b) for b in bounds], call,
+                    times)
+
+
+def _usage_refuse(values, reads):
+    return "report_render_usage_mtx: the value matrix holds entries that the reads matrix lacks" \
+        if values.nnz > reads.nnz else None
 
 
 def _ex_pa_usage_mat(output_dir: str, res_pkl_file: str, min_reads: int = 1, device=None):
@@ -718,29 +719,9 @@ def _ex_pa_usage_mat(output_dir: str, res_pkl_file: str, min_reads: int = 1, dev
             not 1 <= min_reads <= USAGE_MAX_MIN_READS:
         raise ValueError(f"min_reads must be an integer from 1 to {USAGE_MAX_MIN_READS}, not {min_reads!r}")
     min_reads = int(min_reads)
-    inp = _read_inputs(output_dir, res_pkl_file, with_cb=True)
-    n_cols = inp.n_cols
-    idmap = _IdMap(inp.col_ids, np.arange(n_cols, dtype=np.int32), "barcode_index.csv")
-    bc_text = _tsv_lines([str(b) for b in inp.cb_lst], lambda s: s + "\n", "barcode")
-    tag = ".usage" if min_reads == 1 else f".min{min_reads}.usage"
-    out_dir = os.path.join(output_dir, res_pkl_file.replace(".pkl", tag))
-    with _dir_run(device, out_dir, LEN_MTX_FILES) as run:
-        with tempfile.TemporaryFile(dir=out_dir) as vbody, tempfile.TemporaryFile(dir=out_dir) as rbody, \
-                open(run.parts[2], "wb") as ffh, ThreadPoolExecutor(_hostlib.host_threads()) as pool:
-            _write_gzip(run.parts[3], bc_text, pool, run.times)
-            values = _MtxSink(_GzipWriter(vbody, pool, run.times), _GzipWriter(ffh, pool, run.times))
-            reads = _MtxSink(_GzipWriter(rbody, pool, run.times), None)
-            ctx = run.device()
-            for bat in _counted(ctx, inp.res_pkl, idmap, n_cols, _usage_batch_cost(n_cols), _budget(ctx), run.times):
-                _render_usage_batch(ctx, bat, n_cols, min_reads, values, reads, run.times)
-            if values.nnz > reads.nnz:
-                raise _lib.ScapeHipError("report_render_usage_mtx: the value matrix holds entries that the reads matrix "
-                                         "lacks")
-            _finish_mtx(run.parts[0], f"{LEN_MTX_BANNER}{values.n_rows} {n_cols} {values.nnz}\n", vbody, run.times)
-            _finish_mtx(run.parts[1], f"{MTX_BANNER}{values.n_rows} {n_cols} {reads.nnz}\n", rbody, run.times)
-    print("Finish pA site usage for each cell")
-    print(f"Finish {inp.res_pkl} in {run.total / 60} min.")
-    return out_dir
+    return _mtx_run(output_dir, res_pkl_file, ".usage" if min_reads == 1 else f".min{min_reads}.usage", LEN_MTX_FILES,
+                    (LEN_MTX_BANNER, MTX_BANNER), device, _usage_batch_cost,
+                    functools.partial(_render_usage_batch, min_reads), _usage_refuse, "Finish pA site usage for each cell")
 
 
 # ---------------------------------------------------------------- ex_pa_pseudobulk

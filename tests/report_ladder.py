@@ -1,6 +1,7 @@
 """The boundary ladder of the report side's oldest device layer (scape_amd/csrc/report.inc: k_rep_count,
-k_rep_complete, k_rep_rowlen, k_rep_scan, k_rep_render, k_rep_mtx_rowlen, k_rep_mtx_render, k_rep_segsum, k_rep_present,
-k_rep_groups, k_rep_hist and the block helpers rep_block_sum / rep_block_excl): the cases and the exact oracle.  Nothing
+k_rep_complete, k_rep_rowlen, k_rep_scan, k_rep_render, k_rep_segsum, k_rep_present, k_rep_groups, k_rep_hist and the
+block helpers rep_block_sum / rep_block_excl; scape_amd/csrc/report_mtx.inc: k_rep_entries_rowlen / k_rep_entries_render
+under the count rule): the cases and the exact oracle.  Nothing
 here imports from scape_amd (the rule of tests/report_cases.py); tests/test_report_ladder.py runs the cases,
 tests/test_host.py checks the ladder against the constants of the source.
 

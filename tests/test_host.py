@@ -1115,13 +1115,14 @@ def mr_exp_zero():
 
 
 def test_report_ladder_covers_every_boundary_of_the_report_kernels():
-    """tests/test_report_ladder.py runs the count, scan, render, segment-sum and histogram kernels of report.inc on the
-    cases of tests/report_ladder.py.  The boundaries are read here from the source - REP_THREADS (the column tile of the
+    """tests/test_report_ladder.py runs the count, scan, render, segment-sum and histogram kernels of report.inc and the
+    count rule of report_mtx.inc's entry walk on the cases of tests/report_ladder.py.  The boundaries are read here from the source - REP_THREADS (the column tile of the
     render kernels, the word tile of k_rep_groups), REP_SCAN_THREADS (the step of k_rep_scan), the 64 lanes that the block
     helpers hard-code, REP_ZERO_FIELD - and the ladder must have a value on both sides of each, and beyond the second
     step of the two loops that carry (whoever moves one has to move the ladder)."""
     import report_ladder as rl
     src = open(os.path.join(ROOT, "scape_amd", "csrc", "report.inc")).read()
+    mtx = open(os.path.join(ROOT, "scape_amd", "csrc", "report_mtx.inc")).read()
     threads = int(re.search(r"#define REP_THREADS (\d+)\b", src).group(1))
     scan = int(re.search(r"#define REP_SCAN_THREADS (\d+)\b", src).group(1))
     zero = int(re.search(r"#define REP_ZERO_FIELD (\d+)\b", src).group(1))
@@ -1132,10 +1133,12 @@ def test_report_ladder_covers_every_boundary_of_the_report_kernels():
     assert "for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);" in helpers
     assert "for (int o = 1; o < 64; o <<= 1) {" in helpers and "if (lane >= o) x += y;" in helpers and "if (lane == 63) lds[w] = x;" in helpers
     # ---- the loops whose strides the ladder straddles
-    assert src.count("for (int base = 0; base < n_cols; base += REP_THREADS) {") == 3      # the three render kernels
+    tile_loop = "for (int base = 0; base < n_cols; base += REP_THREADS) {"
+    # the dense render; the one Matrix Market walk and the length matrix's render, which is a kernel of its own
+    assert (src.count(tile_loop), mtx.count(tile_loop)) == (1, 2)
     assert "for (int base = 0; base < n_words; base += REP_THREADS) {" in src and "carry += tile;" in src
     assert "for (int base = 0; base < n; base += REP_SCAN_THREADS) {" in src and "carry += tot;" in src
-    assert src.count("pos += tile;") == 3 and "for (int s = w; s < n_seg; s += REP_WAVES) {" in src
+    assert (src.count("pos += tile;"), mtx.count("pos += tile;")) == (1, 2) and "for (int s = w; s < n_seg; s += REP_WAVES) {" in src
     by = {c.name: c for c in rl.cases()}
     cols, rows = {c.n_cols for c in by.values() if c.family == "a"}, {len(c.rows) for c in by.values() if c.family == "c"}
     assert cols == set(rl.COLS) and rows == set(rl.ROWS)
