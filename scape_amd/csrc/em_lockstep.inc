@@ -82,6 +82,45 @@ __device__ __forceinline__ double d_wave_allsum(double v) {
 #ifndef ESTEP_EXP_GROUP
 #define ESTEP_EXP_GROUP 1
 #endif
+// f(integral_constant<c>) for the component c == k of a register array of CMAX, k wave-uniform and held in a scalar
+// register: one scalar branch tree per use.  Written as `if (c == k)` inside the unrolled component loop the same thing
+// is two v_cndmask_b32 per f64 and component for every value the branch assigns (10 per component and bin for the
+// sumk / rescue / zk group of the bin step); a dynamic index z[k] would move the array out of registers.
+template <int CMAX, class F>
+__device__ __forceinline__ void d_at_uniform(int k, F &&f) {
+#define AT_CASE(i)                                                 \
+    case i:                                                        \
+        if constexpr ((i) < CMAX) f(std::integral_constant<int, (i)>{}); \
+        break;
+#define AT_CASE8(b) AT_CASE(b) AT_CASE(b + 1) AT_CASE(b + 2) AT_CASE(b + 3) AT_CASE(b + 4) AT_CASE(b + 5) AT_CASE(b + 6) AT_CASE(b + 7)
+    switch (k) {
+        AT_CASE8(0) AT_CASE8(8) AT_CASE8(16) AT_CASE8(24) AT_CASE8(32) AT_CASE8(40) AT_CASE8(48) AT_CASE8(56)
+        default: break;
+    }
+#undef AT_CASE8
+#undef AT_CASE
+}
+// The row entropy's accumulation en += -pk * d without its guard `(pk > 0) ? ... : 0.0`, rounded as the guarded form was
+// compiled: the first component (en is the literal +0.0 there) one fma onto +0.0, every later one the product rounded
+// on its own, then the sum.  pk >= 0 and d is finite, so with pk == 0 the term is +-0, and +-0 added to an accumulator
+// that started at +0.0 changes nothing; likewise `ell` without its `z != 0` guard (one fma, as it was compiled).
+__device__ __forceinline__ double d_en_add(bool first, double en, double pk, double d) {
+#pragma clang fp contract(off)
+    if (first) return __builtin_fma(-pk, d, 0.0);
+    const double t = -pk * d;
+    return en + t;
+}
+// A shift by N lanes towards lane 0 inside each row of 16 lanes (DPP row_shl, two 32-bit halves; lanes whose source
+// lies beyond the row read +0.0) - in-register, where __shfl_down goes through the LDS crossbar.
+template <int N>
+__device__ __forceinline__ double d_row_shl(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x100 + N, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x100 + N, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double d_lane_value(double v, int l) {      // v of lane l, wave-uniform (two v_readlane_b32)
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
 // Body of one E-step for one job.  CA = compile-time array/loop bound; CX = the job's exact column count
 // K+1 when the caller dispatched on it (every `c < C` test then folds away), 0 = runtime C <= CA.
 // NW = wavefronts that work on the job: 1 (k2_estep: the throughput kernel) or 4 (k2_estep_cs, calls with few jobs):
@@ -123,7 +162,9 @@ __device__ __forceinline__ EstepNext estep_body(
     // reads - value by value, each behind the branch that needs it - the set-up was 7-8 dependent round trips to L2,
     // 15 % of a job-round's lifetime.)  Per-column state sits in lane c and is handed around by shuffles.
     const int u_job = job_utr[job];
-    const int K = (CX > 0) ? CX - 1 : job_K[job], C = K + 1;
+    // (K, the round counter, the round's component and the grid indices derived from it are wave-uniform; taken through
+    // readfirstlane they live in scalar registers, and every test on them is a scalar branch, not a per-lane select)
+    const int K = (CX > 0) ? CX - 1 : __builtin_amdgcn_readfirstlane(job_K[job]), C = K + 1;
     const bool fixed = job_fixed[job] != 0;
     int32_t *ia = S.ia + (size_t)job * kmax, *ib = S.ib + (size_t)job * kmax;
     int32_t *sia = S.sia + (size_t)job * kmax, *sib = S.sib + (size_t)job * kmax;
@@ -155,12 +196,12 @@ __device__ __forceinline__ EstepNext estep_body(
     // round counter it would be one more dependent trip)
     const int k_lane = (lane < nround) ? (int)k_arr[(size_t)job * nround + lane] : 0;
     const double lb_prev = r0 ? SENT : S.lb[job];       // (read after the bin loop these two were one more trip at the end)
-    const int nlb_prev = r0 ? 0 : S.nlb[job];
+    const int nlb_prev = r0 ? 0 : __builtin_amdgcn_readfirstlane(S.nlb[job]);
     auto k_of_round = [&](int i) {
         const int ii = min(i, nround - 1);
         return (nround <= 64) ? __shfl(k_lane, ii, 64) : (int)k_arr[(size_t)job * nround + ii];
     };
-    const int k_now = k_of_round(nlb_prev);
+    const int k_now = __builtin_amdgcn_readfirstlane(k_of_round(nlb_prev));
     const int k_next = __builtin_amdgcn_readfirstlane(k_of_round(nlb_prev + 1));
     double my_ws = 0.0, my_slw = 0.0;                    // lane c < C: weight / snapshot log-weight of column c
     int my_ia = 0, my_ib = 0, my_sia = 0, my_sib = 0;    // lane c < K: current / snapshot grid indices
@@ -314,10 +355,10 @@ __device__ __forceinline__ EstepNext estep_body(
     // cal_z_k(para, k) (:731): refresh the snapshot of column k (every lane computes it, lane 0 stores it)
     const double wk_old = __shfl(my_ws, k, 64);
     const double slw_k = d_logw(wk_old);
-    const int sia_k = (k < K) ? __shfl(my_ia, k, 64) : 0;
-    const int sib_k = (k < K) ? __shfl(my_ib, k, 64) : 0;
+    const int sia_k = (k < K) ? __builtin_amdgcn_readlane(my_ia, k) : 0;
+    const int sib_k = (k < K) ? __builtin_amdgcn_readlane(my_ib, k) : 0;
     // neighbours of component k in the UNSORTED current alpha list: the M-step window of this round (:511-514)
-    const int ia_km1 = __shfl(my_ia, max(k - 1, 0), 64), ia_kp1 = __shfl(my_ia, min(k + 1, 63), 64);
+    const int ia_km1 = __builtin_amdgcn_readlane(my_ia, max(k - 1, 0)), ia_kp1 = __builtin_amdgcn_readlane(my_ia, min(k + 1, 63));
     if (lead && lane == 0) {
         slw[k] = slw_k;
         if (k < K) {
@@ -351,33 +392,27 @@ __device__ __forceinline__ EstepNext estep_body(
     ESTEP_STAMP(st1);
     double tot_w[CMAX], t_sumk = 0.0, t_ell = 0.0, t_ent = 0.0;
     int nz_lo = 0x7fffffff, nz_hi = -1;   // first / last bin of this lane with v != 0
-    bool mod = false;
+    const ExpPoly exp_poly = d_exp_poly_held();       // (scape_hip.hip: no copy in front of a Horner step)
+    const LogPoly log_poly = d_log_poly_held();
+    // One pass over the bins; mod = the pass adds the rescue 1e-8 to column k.  The first pass never does and the second
+    // always does, so `mod` is a compile-time constant of the pass: the first pass (all but a handful of job-rounds run
+    // no other) carries no select, branch or log for the rescue.  Returns: the pass must be redone with the rescue.
     if constexpr (NW == 1) {
-        for (int pass = 0; pass < 2; ++pass) {
+        auto run_pass = [&](auto mod_c) {
+            constexpr bool mod = decltype(mod_c)::value;
     #pragma unroll
             for (int c = 0; c < CMAX; ++c) s_wsum[c * 64 + lane] = 0.0;
             double sumk = 0.0, ell = 0.0, ent = 0.0;
             nz_lo = 0x7fffffff;
             nz_hi = -1;
-            // software pipeline over the bins of this lane: the tensor values of the next bin are
-            // requested before the current bin's exp/div chain runs
-            double mcur[CMAX], ccur = 0.0;
             auto fetch = [&](int n, double (&m)[CMAX], double &cn) {
                 const bool ok = n < N;
                 cn = ok ? cu[n] : 0.0;
     #pragma unroll
                 for (int c = 0; c < CMAX; ++c) m[c] = (ok && c < K) ? Mu[s_roff[c] + n] : 0.0;
             };
-            fetch(lane, mcur, ccur);
-            // the first bin's values must have ARRIVED before the loop: otherwise the compiler's wait-count pass sees loads
-            // pending on mcur at the loop header and puts vmcnt(1) / vmcnt(0) in front of their first use in EVERY iteration -
-            // right behind the requests for the next bin, which are then waited for at once (the counter is in issue order)
-    #pragma unroll
-            for (int c = 0; c < CMAX; ++c) asm volatile("" : "+v"(mcur[c]));
-            asm volatile("" : "+v"(ccur));
-            for (int n = lane; n < Np; n += 64) {
-                double mnext[CMAX], cnext;
-                fetch(n + 64, mnext, cnext);
+            // one bin of this lane, n < Np, from its tensor values mcur and read count ccur
+            auto bin_step = [&](int n, const double (&mcur)[CMAX], double ccur) {
                 double vkn = 0.0;
                 if (n < N) {
                     const double cn = ccur;
@@ -389,7 +424,7 @@ __device__ __forceinline__ EstepNext estep_body(
                     for (int c = 0; c < CMAX; ++c) {
                         if (c < C) {
                             const double v = lzv(c);
-                            mx = (c == 0 || v > mx) ? v : mx;
+                            mx = (c == 0) ? v : fmax(mx, v);       // (v_max_f64: the values are finite, never NaN)
                         }
                     }
                     // exp underflows to exactly 0 below -745.14; when that holds for the whole wavefront the
@@ -421,7 +456,7 @@ __device__ __forceinline__ EstepNext estep_body(
                                     if (c + i < CMAX)
                                         if (c + i < C) {
                                             live |= 1ull << (c + i);
-                                            z[c + i] = d_exp_nonpos(arg[i], s_exptab);
+                                            z[c + i] = d_exp_nonpos(arg[i], s_exptab, exp_poly);
                                         }
                             }
                             __builtin_amdgcn_sched_barrier(0);
@@ -435,7 +470,7 @@ __device__ __forceinline__ EstepNext estep_body(
                             const double arg = (lzv(c) - mx) * cn;
                             if (__ballot(arg >= -746.0)) {
                                 live |= 1ull << c;
-                                z[c] = d_exp_nonpos(arg, s_exptab);
+                                z[c] = d_exp_nonpos(arg, s_exptab, exp_poly);
                             }
                             // keep the scheduler from interleaving all CMAX exp chains (it would spend ~100
                             // extra VGPRs on that; occupancy hides the latency instead)
@@ -447,35 +482,35 @@ __device__ __forceinline__ EstepNext estep_body(
                     const double rs = d_rcp_mid(s);   // one reciprocal per bin (1 <= s <= K+1): z * (1/s) is within 2 ulp of z / s (norm_z :494)
                     double zk = 0.0;
     #pragma unroll
-                    for (int c = 0; c < CMAX; ++c) {
-                        if (live & (1ull << c)) z[c] = z[c] * rs;
-                        if (c == k) {
-                            sumk += z[c];
-                            if (mod) z[c] += 1e-8;
-                            zk = z[c];
-                        }
-                    }
+                    for (int c = 0; c < CMAX; ++c) z[c] = z[c] * rs;     // a skipped component is +0.0 and stays +0.0 (0 < rs <= 1)
+                    d_at_uniform<CMAX>(k, [&](auto ck) {
+                        constexpr int c = decltype(ck)::value;
+                        zk = z[c];
+                        if (mod) z[c] += 1e-8;
+                    });
+                    sumk += zk;                // Z[:,k] before the rescue
+                    if (mod) zk += 1e-8;       // (the same sum as z[k] just took)
                     // entropy of the row (scipy.stats.entropy re-normalises by s2): log pk_c is known in
                     // closed form, log z_c = (lz_c - mx)*cn - log s, so only two logs per bin are needed
                     const double s2 = d_np_sum<CMAX>(z, C);
                     // s2 = sum of the normalised row = 1 +- a few ulp (1 + 1e-8 when the rescue fired): log(s2) by its
                     // series, exact to f64 for |s2 - 1| < 1e-4 (next term x^3/3 < 4e-13 * |x|... < 1 ulp of x)
                     const double x2 = s2 - 1.0;
-                    const double ls = d_log_pos(s), rs2 = d_rcp_mid(s2);   // s >= 1: the row maximum contributes exp(0); s2 = 1 +- tiny
+                    const double ls = d_log_pos(s, log_poly), rs2 = d_rcp_mid(s2);   // s >= 1: the row maximum contributes exp(0); s2 = 1 +- tiny
                     double ls2 = x2 - 0.5 * x2 * x2;
                     if (__ballot(fabs(x2) >= 1e-5)) ls2 = (fabs(x2) < 1e-5) ? ls2 : log(s2);   // wave-uniform: normally skipped
                     double lzk_mod = 0.0;
-                    if (mod) lzk_mod = log(zk);   // wave-uniform branch: one log, not one per unrolled component
+                    if constexpr (mod) lzk_mod = log(zk);   // one log, not one per unrolled component
                     double en = 0.0;
     #pragma unroll
                     for (int c = 0; c < CMAX; ++c) {
                         if (c < C && ((live & (1ull << c)) || (mod && c == k))) {
                             const double lzc_full = lzv(c);
-                            s_wsum[c * 64 + lane] += cn * z[c];
-                            if (z[c] != 0.0) ell += (z[c] * cn) * lzc_full;
+                            s_wsum[c * 64 + lane] = __builtin_fma(cn, z[c], s_wsum[c * 64 + lane]);
+                            ell = __builtin_fma(z[c] * cn, lzc_full, ell);           // (no `z != 0` / `pk > 0` guards: see d_en_add)
                             const double pk = z[c] * rs2;      // s2 = 1 +- few ulp: z/s2 and z*(1/s2) agree to 1 ulp
                             const double lzc = (mod && c == k) ? lzk_mod : (lzc_full - mx) * cn - ls;
-                            en += (pk > 0.0) ? -pk * (lzc - ls2) : 0.0;
+                            en = d_en_add(c == 0, en, pk, lzc - ls2);
                         }
                     }
                     ent += cn * en;
@@ -486,6 +521,22 @@ __device__ __forceinline__ EstepNext estep_body(
                     nz_lo = min(nz_lo, n);
                     nz_hi = n;
                 }
+            };
+            // software pipeline over the bins of this lane: the tensor values of the next bin are requested before the
+            // current bin's exp/div chain runs.  (One bin per trip and the hand-over copy `mcur = mnext`, a v_mov_b64 per
+            // column and bin: two bins per trip with the two buffers swapping roles has no copy but twice the loop's code,
+            // and measured 1 % slower - profiles/estep_bin_step.txt.)
+            double mcur[CMAX], mnext[CMAX], ccur = 0.0, cnext = 0.0;
+            fetch(lane, mcur, ccur);
+            // the first bin's values must have ARRIVED before the loop: otherwise the compiler's wait-count pass sees loads
+            // pending on mcur at the loop header and puts vmcnt(1) / vmcnt(0) in front of their first use in EVERY iteration -
+            // right behind the requests for the next bin, which are then waited for at once (the counter is in issue order)
+    #pragma unroll
+            for (int c = 0; c < CMAX; ++c) asm volatile("" : "+v"(mcur[c]));
+            asm volatile("" : "+v"(ccur));
+            for (int n = lane; n < Np; n += 64) {
+                fetch(n + 64, mnext, cnext);
+                bin_step(n, mcur, ccur);
     #pragma unroll
                 for (int c = 0; c < CMAX; ++c) mcur[c] = mnext[c];
                 ccur = cnext;
@@ -495,15 +546,13 @@ __device__ __forceinline__ EstepNext estep_body(
             t_sumk = d_wave_allsum(sumk);
             t_ell = d_wave_allsum(ell);
             t_ent = d_wave_allsum(ent);
-            if (pass == 0 && t_sumk < 1e-8) {
-                mod = true;  // Z[:,k] += 1e-8 (apa_core.py:528-529): redo the pass
-                continue;
-            }
-            break;
-        }
+            return !mod && t_sumk < 1e-8;
+        };
+        if (run_pass(std::false_type{})) run_pass(std::true_type{});   // Z[:,k] += 1e-8 (apa_core.py:528-529): redo the pass
     } else {
         // ---- NW wavefronts, components split (see the comment above estep_body) ---------------------------------
-        for (int pass = 0; pass < 2; ++pass) {
+        auto run_pass = [&](auto mod_c) {
+            constexpr bool mod = decltype(mod_c)::value;
 #pragma unroll
             for (int c = 0; c < CMAX; ++c)
                 if ((c % NW) == wave) s_wsum[c * 64 + lane] = 0.0;
@@ -537,7 +586,7 @@ __device__ __forceinline__ EstepNext estep_body(
                     for (int c = 0; c < CMAX; ++c) {
                         if (c < C) {
                             const double v = lzv(c);
-                            mx = (c == 0 || v > mx) ? v : mx;
+                            mx = (c == 0) ? v : fmax(mx, v);       // (v_max_f64: the values are finite, never NaN)
                         }
                     }
                     // this wavefront's components: the un-normalised responsibilities go to the exchange buffer
@@ -546,7 +595,7 @@ __device__ __forceinline__ EstepNext estep_body(
                         if (c < C && (c % NW) == wave) {
                             const double arg = (lzv(c) - mx) * cn;
                             double zr = 0.0;
-                            if (__ballot(arg >= -746.0)) zr = d_exp_nonpos(arg, s_exptab);
+                            if (__ballot(arg >= -746.0)) zr = d_exp_nonpos(arg, s_exptab, exp_poly);
                             xz[c * 64 + lane] = zr;
                             __builtin_amdgcn_sched_barrier(0);
                         }
@@ -562,34 +611,34 @@ __device__ __forceinline__ EstepNext estep_body(
                     const double rs = d_rcp_mid(s);
                     double zk = 0.0;
 #pragma unroll
-                    for (int c = 0; c < CMAX; ++c) {
-                        z[c] = z[c] * rs;
-                        if (c == k) {
-                            sumk += z[c];
-                            if (mod) z[c] += 1e-8;
-                            zk = z[c];
-                        }
-                    }
+                    for (int c = 0; c < CMAX; ++c) z[c] = z[c] * rs;
+                    d_at_uniform<CMAX>(k, [&](auto ck) {
+                        constexpr int c = decltype(ck)::value;
+                        zk = z[c];
+                        if (mod) z[c] += 1e-8;
+                    });
+                    sumk += zk;                // Z[:,k] before the rescue
+                    if (mod) zk += 1e-8;       // (the same sum as z[k] just took)
                     const double s2 = d_np_sum<CMAX>(z, C);
                     const double x2 = s2 - 1.0;
-                    const double ls = d_log_pos(s), rs2 = d_rcp_mid(s2);
+                    const double ls = d_log_pos(s, log_poly), rs2 = d_rcp_mid(s2);
                     double ls2 = x2 - 0.5 * x2 * x2;
                     if (__ballot(fabs(x2) >= 1e-5)) ls2 = (fabs(x2) < 1e-5) ? ls2 : log(s2);
                     double lzk_mod = 0.0;
-                    if (mod) lzk_mod = log(zk);
+                    if constexpr (mod) lzk_mod = log(zk);
 #pragma unroll
                     for (int c = 0; c < CMAX; ++c)
-                        if (c < C && (c % NW) == wave) s_wsum[c * 64 + lane] += cn * z[c];
+                        if (c < C && (c % NW) == wave) s_wsum[c * 64 + lane] = __builtin_fma(cn, z[c], s_wsum[c * 64 + lane]);
                     if (lead) {
                         double en = 0.0;
 #pragma unroll
                         for (int c = 0; c < CMAX; ++c) {
                             if (c < C) {
                                 const double lzc_full = lzv(c);
-                                if (z[c] != 0.0) ell += (z[c] * cn) * lzc_full;
+                                ell = __builtin_fma(z[c] * cn, lzc_full, ell);
                                 const double pk = z[c] * rs2;
                                 const double lzc = (mod && c == k) ? lzk_mod : (lzc_full - mx) * cn - ls;
-                                en += (pk > 0.0) ? -pk * (lzc - ls2) : 0.0;
+                                en = d_en_add(c == 0, en, pk, lzc - ls2);
                             }
                         }
                         ent += cn * en;
@@ -619,19 +668,16 @@ __device__ __forceinline__ EstepNext estep_body(
                 t_sumk = d_wave_allsum(sumk);
                 t_ell = d_wave_allsum(ell);
                 t_ent = d_wave_allsum(ent);
-                if (lane == 0) s_tot[CMAX] = (pass == 0 && t_sumk < 1e-8) ? 1.0 : 0.0;
+                if (lane == 0) s_tot[CMAX] = (!mod && t_sumk < 1e-8) ? 1.0 : 0.0;
             }
             __syncthreads();
 #pragma unroll
             for (int c = 0; c < CMAX; ++c) tot_w[c] = s_tot[c];
             const bool redo = s_tot[CMAX] != 0.0;
             __syncthreads();           // s_tot and the exchange buffers are rewritten by a second pass
-            if (redo) {
-                mod = true;  // Z[:,k] += 1e-8 (apa_core.py:528-529): redo the pass
-                continue;
-            }
-            break;
-        }
+            return redo;
+        };
+        if (run_pass(std::false_type{})) run_pass(std::true_type{});   // Z[:,k] += 1e-8 (apa_core.py:528-529): redo the pass
         if (!lead) return EstepNext{0, 0, -1, 0};
     }
 
@@ -690,23 +736,32 @@ __device__ __forceinline__ EstepNext estep_body(
                 const int n = nb - 64 * q + lane;
                 vv[q] = (n >= 0 && n < Np) ? Vj[n] : 0.0;
             }
-            // the eight in-group scans are independent of one another (only the carry links the groups): run together,
-            // their shuffle latencies overlap; groups below bin 0 scan zeros and are not stored
+            // Of a Hillis-Steele scan over the 64 lanes of a group (steps 1, 2, .. 32, each lane adding the lane `step`
+            // above it) only the sums S(0), S(16), S(32), S(48) that start at a 16-bin boundary are used.  Steps 1, 2, 4, 8
+            // leave in the first lane of row r (16 lanes) the row's sum T_r in the order of a balanced tree and never
+            // reach across a row from there: they are row-local DPP shifts, in registers.  Steps 16 and 32 then give
+            // S(48) = T3, S(32) = T2 + T3, S(16) = (T1 + T2) + T3, S(0) = (T0 + T1) + (T2 + T3) - formed here from the four
+            // row heads as wave-uniform values, bit for bit what the six trips through the LDS crossbar returned
+            // (tools/estep_scan_check.cpp).  The eight groups of a batch are independent of one another (only the carry
+            // links them); groups below bin 0 scan zeros and are not stored.
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const double t = __shfl_down(vv[q], off, 64);
-                    if (lane + off < 64) vv[q] += t;
-                }
+            for (int q = 0; q < 8; ++q) {
+                vv[q] += d_row_shl<1>(vv[q]);
+                vv[q] += d_row_shl<2>(vv[q]);
+                vv[q] += d_row_shl<4>(vv[q]);
+                vv[q] += d_row_shl<8>(vv[q]);
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int n0 = nb - 64 * q;
                 if (n0 >= 0) {                        // wave-uniform
                     const int n = n0 + lane;
-                    if ((lane & 15) == 0 && n < Np) Sj[n >> 4] = carry + vv[q];
-                    carry += __shfl(vv[q], 0, 64);
+                    const double T0 = d_lane_value(vv[q], 0), T1 = d_lane_value(vv[q], 16), T2 = d_lane_value(vv[q], 32),
+                                 T3 = d_lane_value(vv[q], 48);
+                    const double S32 = T2 + T3, S16 = (T1 + T2) + T3, S0 = (T0 + T1) + S32;
+                    const double mine = (lane < 16) ? S0 : (lane < 32) ? S16 : (lane < 48) ? S32 : T3;
+                    if ((lane & 15) == 0 && n < Np) Sj[n >> 4] = carry + mine;
+                    carry += S0;
                 }
             }
         }

@@ -85,12 +85,36 @@ struct DevParams {
 // log(1+f) = f - hfsq + s (hfsq + R(s^2)) with the degree-14 minimax R in s (coefficients Lg1..Lg7, error < 2^-58.45),
 // k ln2 added as a hi/lo pair; the quotient comes from v_rcp_f64 plus two Newton steps and a residual correction.
 // Worst error found on 2e7 arguments (host replica of exactly this sequence, against long-double log): 0.83 ulp.
-__device__ __forceinline__ double d_log_pos(double x) {
+// The polynomial constants of d_log_pos / d_exp_nonpos as a caller may hold them.  Left to the compiler (the default
+// argument: plain literals) every Horner step inside a big loop becomes v_mov_b64 (a fresh copy of the addend constant) +
+// v_fmac_f64.  A loop that is bound by its VALU count (the E-step's bin loop) takes d_*_poly_held() in front of the loop
+// instead: the multiplier-side constants sit in scalar registers, the addend-side ones in vector registers the compiler
+// cannot re-create, and each step is one three-address v_fma_f64.  Same operations, same order, same bits.
+struct LogPoly {
+    double Lg1, Lg2, Lg3, Lg4, Lg5, Lg6, Lg7;
+};
+struct ExpPoly {
+    double c5, c4, c3;
+};
+#define D_LOG_POLY LogPoly{6.666666666666735130e-01, 3.999999999940941908e-01, 2.857142874366239149e-01, 2.222219843214978396e-01, \
+                           1.818357216161805012e-01, 1.531383769920937332e-01, 1.479819860511658591e-01}
+#define D_EXP_POLY ExpPoly{1.0 / 120, 1.0 / 24, 1.0 / 6}
+__device__ __forceinline__ LogPoly d_log_poly_held() {
+    LogPoly k = D_LOG_POLY;
+    asm volatile("" : "+s"(k.Lg1), "+s"(k.Lg2), "+s"(k.Lg3), "+s"(k.Lg6), "+s"(k.Lg7));   // multipliers, last addends
+    asm volatile("" : "+v"(k.Lg4), "+v"(k.Lg5));                                            // addends of the innermost steps
+    return k;
+}
+__device__ __forceinline__ ExpPoly d_exp_poly_held() {
+    ExpPoly k = D_EXP_POLY;
+    asm volatile("" : "+s"(k.c5), "+s"(k.c3));
+    asm volatile("" : "+v"(k.c4));
+    return k;
+}
+__device__ __forceinline__ double d_log_pos(double x, const LogPoly &k = D_LOG_POLY) {
 #pragma clang fp contract(off)
     const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10,
-                 Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
-                 Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
-                 Lg7 = 1.479819860511658591e-01;
+                 Lg1 = k.Lg1, Lg2 = k.Lg2, Lg3 = k.Lg3, Lg4 = k.Lg4, Lg5 = k.Lg5, Lg6 = k.Lg6, Lg7 = k.Lg7;
     double m = __builtin_amdgcn_frexp_mant(x);        // [0.5, 1)
     int e = __builtin_amdgcn_frexp_exp(x);
     const bool lo = m < 0.70710678118654752440;
@@ -120,7 +144,7 @@ __device__ __forceinline__ double d_log_pos(double x) {
 __device__ __forceinline__ void d_load_exptab(double2 *tab /* LDS, 128 entries */, int tid, int nthreads) {
     for (int i = tid; i < 128; i += nthreads) tab[i] = g_exp_tab[i];
 }
-__device__ __forceinline__ double d_exp_nonpos(double x, const double2 *tab) {
+__device__ __forceinline__ double d_exp_nonpos(double x, const double2 *tab, const ExpPoly &k = D_EXP_POLY) {
 #pragma clang fp contract(off)
     x = fmax(x, -750.0);
     const double n = __builtin_rint(x * EXP_INV_L);
@@ -129,7 +153,7 @@ __device__ __forceinline__ double d_exp_nonpos(double x, const double2 *tab) {
     const int ni = (int)n;
     const double2 t = tab[ni & 127];
     const double r2 = r * r;
-    const double q = __builtin_fma(r, __builtin_fma(r, __builtin_fma(r, 1.0 / 120, 1.0 / 24), 1.0 / 6), 0.5);
+    const double q = __builtin_fma(r, __builtin_fma(r, __builtin_fma(r, k.c5, k.c4), k.c3), 0.5);
     const double p = __builtin_fma(r2, q, r);
     return ldexp(t.x + __builtin_fma(t.x, p, t.y), ni >> 7);
 }

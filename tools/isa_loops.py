@@ -45,6 +45,9 @@ for k, ins in groups.items():
     sc_l = sum(v for kk, v in c.items() if kk.startswith("scratch_load"))
     sc_s = sum(v for kk, v in c.items() if kk.startswith("scratch_store"))
     print(k, "instr", len(ins), "valu", sum(v for kk, v in c.items() if kk.startswith("v_")), "exps", c["v_rndne_f64_e32"],
+          "cndmask", sum(v for kk, v in c.items() if kk.startswith("v_cndmask")),
+          "mov", sum(v for kk, v in c.items() if kk.startswith("v_mov")),
+          "dpp", sum(v for kk, v in c.items() if kk.endswith("_dpp")), "bpermute", c["ds_bpermute_b32"], "waitcnt", c["s_waitcnt"],
           "scratch ld/st", sc_l, sc_s, "ds", sum(v for kk, v in c.items() if kk.startswith("ds_")),
           "global", sum(v for kk, v in c.items() if kk.startswith("global_")), "mfma", sum(v for kk, v in c.items() if "mfma" in kk),
           "salu", sum(v for kk, v in c.items() if kk.startswith("s_")))
