@@ -10,8 +10,8 @@ inclusive window [alpha_{k-1}, alpha_{k+1}] (min_theta / L at the ends, :511-513
     S(row) = sum_n (log w_k + M[row, n]) v[n],        v[n] = Z[n, k] cnt[n].
 Per round the function returns the winning row (first maximum), every row's score, the rows tied with the winner IN
 EXACT ARITHMETIC - rows whose tensor values are bit-identical to the winner's on every bin with v != 0 - and a
-first-order BOUND per row on how far a correct f64 evaluation by the device's sequence (em_lockstep.inc: estep_body,
-k2_mstep; mstep_ring.inc; mstep_multi.inc) may lie from S(row).  A round is DECIDED when the winner beats every row
+first-order BOUND per row on how far a correct f64 evaluation by the device's sequence (em_lockstep.inc: estep_body;
+mstep.inc and the three kernels built on it: mstep_staged.inc, mstep_ring.inc, mstep_multi.inc) may lie from S(row).  A round is DECIDED when the winner beats every row
 outside its tie set by more than the two rows' bounds: then every correct f64 evaluation returns the same row, and a
 test may demand it exactly.
 

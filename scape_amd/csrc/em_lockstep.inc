@@ -7,20 +7,15 @@
 //   k2_estep  one wavefront per job: finish the previous M-step (reduce per-tile partial arg-maxes),
 //             refresh the stale column, responsibilities / weight update / ELBO / stopping rule,
 //             and publish v = Z[:,k]*cnt plus the (row window, log w_k) of this round's M-step;
-//   k2_mstep  one workgroup per (UTR, 64-row tile of the [T*B, N] tensor): the tile is staged through
-//             LDS once (transposed, lane = tensor row) and multiplied with the v vectors of EVERY job
-//             of that UTR whose window covers it - an LDS-tile x scalar-broadcast FMA stream, 8 jobs
-//             per LDS read, no cross-lane reduction; the per-(job, tile) arg-max goes to a partial
-//             table that the next k2_estep reduces in row order (first-maximum tie rule).
-// score(a,b) = sum_n (log w_k + M[a,b,n]) * v[n] is evaluated as log w_k * sum_n v[n] + sum_n M*v.
+//   an M-step one workgroup per (UTR, 64-row tile of the [T*B, N] tensor): the tile is multiplied on the f64 matrix
+//             cores with the v vectors of EVERY job of that UTR whose window covers it; the per-(job, tile) arg-max
+//             goes to a partial table that the next k2_estep reduces in row order (first-maximum tie rule).
+//             (mstep.inc: the frame; mstep_staged.inc, mstep_ring.inc, mstep_multi.inc: k2_mstep, k3_mstep, k4_mstep.)
+// This file is the E-step and the shrink kernel, and the constants that they, the M-step and the host share.
 
 #define MT_RB 1                      // 16-row blocks per wave
 #define MT_ROWS (64 * MT_RB)          // tensor rows per tile: 4 waves x MT_RB x 16
-#define MT_NC 32
-#define MT_PITCH (MT_NC + 2)          // LDS pitch (f64) of the [row][n] image: rows 272 B apart -> 16-B aligned double2
-#define MT_VPITCH (MT_NC + 2)         // stores, and (2*row + k) mod 32 distinct within every 32-lane read group
-                                      // (ds_read_b64 banking, MI355X_MICROARCH.md section LDS): conflict-free fragments
-#define MT_MAXJ 64
+#define MT_MAXJ 64                    // jobs (columns) of one M-step pass over a tile
 // Run-ahead: between two M-step launches (one PASS over the tensor) a job executes up to EM_DEPTH consecutive rounds, as
 // long as the next round's component is neither equal nor adjacent to one whose grid arg-max is still pending (see
 // k2_estep), and publishes one M-step column (v vector, window, log w_k) per round.  Everything the M-step reads or
@@ -29,13 +24,6 @@
 #define EM_DEPTH 3
 #endif
 static_assert(EM_DEPTH >= 1 && EM_DEPTH <= 8, "column slots per job");
-#ifndef MT_DV1
-#define MT_DV1 1      // the job vectors (L2-resident) are requested one chunk ahead, the tensor tile two: frees 4 G registers (-3 % launch time)
-#endif
-
-#ifndef MT_DEEP
-#define MT_DEEP 2                     // register stages of the M-step's loads in passes of <= 32 jobs (measured: 3 and 4 change nothing, big calls or small)
-#endif
 // device counters (unsigned long long each): [0] rounds, [1] unused, [2] z elements, [3] finalised jobs, then
 // 64-way sharded: slab elements, executed job-rounds, and the M-step's own byte tallies
 #define CNT_DONE 3                    // jobs finalised in this call (one add per job lifetime; read with the early-exit probe)
@@ -1076,325 +1064,3 @@ __global__ __launch_bounds__(256, 1) void k2_estep_cs(
 #undef ESTEP_EXTRA
 #undef ESTEP_DISPATCH
 #undef ESTEP_CASE
-
-
-// (With run-ahead the entries of ujob_list are COLUMNS - job * depth + slot, one v vector, window and partial table
-// each - and every per-"job" array of the three M-step kernels is indexed by column; "job" below reads "column".)
-// one workgroup per (UTR, MT_ROWS-row tile).  D[rows x jobs] = Mtile[rows x n] * V[n x jobs] on the f64
-// matrix cores (v_mfma_f64_16x16x4_f64): wave w owns MT_RB blocks of 16 rows, job columns come in groups
-// of 16.  Operand maps (cdna_hip_programming.md section 3): A lane l = A[row l&15][k l>>4],
-// B lane l = B[k l>>4][col l&15], D lane l reg i = D[row (l>>4)+4i][col l&15].
-// Both operands are staged through LDS as they lie in memory ([row][n] and [job][n], pitch 34 f64: one
-// 16-byte store per loaded double2, fragment reads free of bank conflicts); the global loads of chunks
-// c+1 and c+2 are in flight during the MFMAs of chunk c (two register stages).  The kernel is a stream over
-// the tensor: every tile is read once per round, so HBM bandwidth bounds it, not the MFMA rate.
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-// G = 16-job column groups of the pass, D = chunks of global loads in flight per wavefront (register stages):
-// passes with few jobs have the registers for a deeper pipeline, and they are the ones that wait on memory
-// rather than on the matrix cores
-template <int G, int D>
-__device__ __forceinline__ void mstep_pass(const double *__restrict__ Mu, const double *__restrict__ V,
-                                           const int64_t *__restrict__ voff, const int *s_jobs, double *mt,
-                                           double *vt, int cnt, int Np, int n_lo, int n_hi, int nrows, int row0, int wave, int lane,
-                                           int need, v4f64 (&acc)[MT_RB][MT_MAXJ / 16]) {
-    const int quarter = lane >> 4, ns = 2 * (lane & 15);   // staging: 4 rows (or jobs) x 32 n per wave-instruction
-    const int kq = lane >> 4, rc = lane & 15;              // fragments
-    constexpr int DV = MT_DV1 ? 1 : D;                // chunks of job-vector loads in flight (they come from L2)
-    double2 rm_st[D][4 * MT_RB], rv_st[DV][G];              // D chunks of global loads in flight
-    const double *vsrc[G];
-#pragma unroll
-    for (int it = 0; it < G; ++it) {
-        const int js = 4 * wave + quarter + 16 * it;
-        vsrc[it] = (js < cnt) ? V + voff[s_jobs[js]] : nullptr;
-    }
-    auto fetchV = [&](int n0, double2 (&rv)[G]) {
-        const int nc = (n_hi - n0 < MT_NC) ? n_hi - n0 : MT_NC;
-#pragma unroll
-        for (int it = 0; it < G; ++it)
-            rv[it] = (ns < nc && vsrc[it]) ? *reinterpret_cast<const double2 *>(vsrc[it] + n0 + ns) : make_double2(0.0, 0.0);
-    };
-    auto fetchM = [&](int n0, double2 (&rm)[4 * MT_RB]) {
-        const int nc = (n_hi - n0 < MT_NC) ? n_hi - n0 : MT_NC;   // <= 0 past the end: nothing is loaded
-#pragma unroll
-        for (int it = 0; it < 4 * MT_RB; ++it) {
-            const int row = row0 + 4 * wave + quarter + 16 * it;
-            // iteration `it` stages the 16-row group that MFMA wave it/MT_RB consumes; groups outside every
-            // job's window are not read (their scores are never looked at)
-            rm[it] = (ns < nc && row < nrows && ((need >> (it / MT_RB)) & 1)) ? *reinterpret_cast<const double2 *>(Mu + (size_t)row * Np + n0 + ns)
-                                               : make_double2(0.0, 0.0);
-        }
-    };
-    auto chunk = [&](int n0, double2 (&rm)[4 * MT_RB], double2 (&rv)[G]) {
-        const int nc = (n_hi - n0 < MT_NC) ? n_hi - n0 : MT_NC;  // multiple of 16
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 4 * MT_RB; ++it) {
-            const int rr = 4 * wave + quarter + 16 * it;
-            *reinterpret_cast<double2 *>(&mt[rr * MT_PITCH + ns]) = rm[it];
-        }
-#pragma unroll
-        for (int it = 0; it < G; ++it) {
-            const int js = 4 * wave + quarter + 16 * it;
-            *reinterpret_cast<double2 *>(&vt[js * MT_VPITCH + ns]) = rv[it];
-        }
-        __syncthreads();
-        fetchM(n0 + D * MT_NC, rm);
-        fetchV(n0 + DV * MT_NC, rv);
-        // one k-step per trip: 1 + G fragment reads, then G MFMAs (the compiler does not unroll this).  Measured and
-        // not kept: the reads of k-step i+1 issued before the MFMAs of k-step i (2.24 -> 2.38 ms per launch), two
-        // k-steps per trip (2.19 -> 2.33 ms) - longer MFMA bursts per wavefront interleave worse with the two
-        // neighbours on the SIMD and the two barriers per chunk; s_setprio raised around the MFMA loop, or around the
-        // staging part instead (no change).
-#pragma unroll 4
-        for (int n4 = 0; n4 < nc; n4 += 4) {
-            double a[MT_RB], b[G];
-#pragma unroll
-            for (int rb = 0; rb < MT_RB; ++rb) a[rb] = mt[(16 * (MT_RB * wave + rb) + rc) * MT_PITCH + n4 + kq];
-#pragma unroll
-            for (int g = 0; g < G; ++g) b[g] = vt[(16 * g + rc) * MT_VPITCH + n4 + kq];
-#pragma unroll
-            for (int rb = 0; rb < MT_RB; ++rb)
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                    acc[rb][g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb], b[g], acc[rb][g], 0, 0, 0);
-        }
-    };
-#pragma unroll
-    for (int dd = 0; dd < D; ++dd) fetchM(n_lo + dd * MT_NC, rm_st[dd]);
-#pragma unroll
-    for (int dd = 0; dd < DV; ++dd) fetchV(n_lo + dd * MT_NC, rv_st[dd]);
-    for (int n0 = n_lo; n0 < n_hi; n0 += D * MT_NC) {
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd)
-            if (n0 + dd * MT_NC < n_hi) chunk(n0 + dd * MT_NC, rm_st[dd], rv_st[dd % DV]);
-    }
-}
-
-__global__ __launch_bounds__(256, 3) void k2_mstep(const UtrDesc *__restrict__ descs, DevParams P,
-                                                   const double *__restrict__ M, const int32_t *__restrict__ active, int n_utr, int tiles_max,
-                                                   const int64_t *__restrict__ ujob_off,
-                                                   const int32_t *__restrict__ ujob_list,
-                                                   const double *__restrict__ V,
-                                                   const double *__restrict__ Vsuf,
-                                                   const int64_t *__restrict__ voff,
-                                                   const int32_t *__restrict__ rd_m,
-                                                   const int32_t *__restrict__ rd_lo,
-                                                   const int32_t *__restrict__ rd_hi,
-                                                   const double *__restrict__ rd_lw,
-                                                   const double *__restrict__ rd_sv,
-                                                   const int32_t *__restrict__ rd_n0,
-                                                   const int32_t *__restrict__ rd_n1,
-                                                   const int64_t *__restrict__ ptoff,
-                                                   double *__restrict__ pt_score,
-                                                   int32_t *__restrict__ pt_row,
-                                                   const int32_t *__restrict__ tile_nend,
-                                                   unsigned long long *__restrict__ counters, int jobs_per_pass,
-                                                   unsigned long long *__restrict__ dbg) {
-    __shared__ __attribute__((aligned(16))) double mt[MT_ROWS * MT_PITCH];   // [row][n]
-    __shared__ __attribute__((aligned(16))) double vt[MT_MAXJ * MT_VPITCH];  // [job slot][n]
-    __shared__ int s_jobs[MT_MAXJ];
-    __shared__ int s_all[1024];               // jobs of this UTR whose window covers the tile
-    __shared__ int s_cnt, s_nlo, s_nhi, s_need, s_first;
-    __shared__ double s_ps[4][MT_MAXJ];
-    __shared__ int s_pr[4][MT_MAXJ];
-    __shared__ double s_tail[MT_MAXJ];          // per job: sum of v over the bins beyond the tile's finite extent
-    // blocks b and b+8 share an XCD (its L2): give one XCD all tiles of a UTR so the job vectors
-    // (V, ~1 MB per UTR) are fetched into one L2 only.  Placement only affects speed.
-    // With fewer than 8 UTRs in the call that rule would leave XCDs idle: the tiles are then dealt round-robin.
-    const int id = blockIdx.x;
-    int ul, t;
-    if (n_utr >= 8) {
-        const int slot = id >> 3;
-        ul = (slot / tiles_max) * 8 + (id & 7);
-        t = slot % tiles_max;
-    } else {
-        ul = id % n_utr;
-        t = id / n_utr;
-    }
-    if (ul >= n_utr || t >= tiles_max) return;
-    const int u = active[ul];   // only UTRs that have jobs in this call get workgroups
-    const UtrDesc d = descs[u];
-    const int B = P.B, Np = d.Np;
-    const int nrows = d.T * B, row0 = t * MT_ROWS;
-    if (row0 >= nrows) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double *Mu = M + (size_t)d.m_off;
-    const int64_t jlo = ujob_off[u], jhi = ujob_off[u + 1];
-    // jobs of this UTR whose window covers the tile, in job-list order (a stable compaction: the workgroups that
-    // share a tile when gridDim.y > 1 must agree on which jobs belong to which pass)
-    __shared__ int s_wcnt[4];
-    int found = 0;
-    for (int64_t j0 = jlo; j0 < jhi; j0 += 256) {
-        const int64_t jj = j0 + tid;
-        int j = -1;
-        bool hit = false;
-        if (jj < jhi) {
-            j = ujob_list[jj];
-            hit = rd_m[j] && rd_lo[j] < row0 + MT_ROWS && rd_hi[j] > row0;
-        }
-        const unsigned long long mask = __ballot(hit);
-        if (lane == 0) s_wcnt[wave] = __popcll(mask);
-        __syncthreads();
-        int off = found;
-        for (int w = 0; w < wave; ++w) off += s_wcnt[w];
-        off += __popcll(mask & ((1ull << lane) - 1ull));
-        if (hit && off < 1024) s_all[off] = j;
-        found += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        __syncthreads();
-    }
-    if (tid == 0) s_cnt = found;
-    __syncthreads();
-    const int total = min(s_cnt, 1024);
-    if (dbg && tid == 0) {
-        atomicAdd(&dbg[0], 1ull);
-        atomicAdd(&dbg[1], (unsigned long long)(total > 0));
-        atomicAdd(&dbg[2], (unsigned long long)total);
-        atomicAdd(&dbg[3], (unsigned long long)((total + MT_MAXJ - 1) / MT_MAXJ));
-        atomicAdd(&dbg[4 + min((total + 15) / 16, 11)], 1ull);
-    }
-    if (total == 0) return;
-    // bytes this workgroup asks the memory system for (thread 0 keeps the tally, three sharded adds at the end):
-    // tensor-tile bytes (each live tile is read by exactly one workgroup per pass: HBM traffic), the v vectors as
-    // requested (every tile of a UTR re-reads them: L2 hits after the first) and the v bytes counted once per job
-    __shared__ unsigned long long s_by[3];   // in LDS, not in registers: the streaming loop has none to spare
-    if (tid == 0) s_by[0] = s_by[1] = s_by[2] = 0ull;
-
-    // a tile with more than MT_MAXJ jobs needs several passes; with gridDim.y > 1 (small calls, where a workgroup's
-    // serial time is what counts) the passes of a tile are taken by different workgroups
-    // jobs_per_pass (16 / 32 / 64, a call-wide constant): calls with few live tiles, where a round takes as long as
-    // ONE workgroup's pass over its tile, cut the job list into short passes that gridDim.y workgroups take in
-    // parallel - every score is the same MFMA chain whichever workgroup and column group computes it
-    for (int base = (int)blockIdx.y * jobs_per_pass; base < total; base += jobs_per_pass * (int)gridDim.y) {
-        const int cnt = min(jobs_per_pass, total - base);
-        const int G = (cnt + 15) >> 4;
-        __syncthreads();
-        if (wave == 0) {   // cnt <= 64: one job per lane of the first wavefront, reductions by shuffles (no LDS atomics)
-            int mk = 0, nlo = 0x7fffffff, nhi = 0;
-            bool fst = false;
-            if (lane < cnt) {
-                const int j = s_all[base + lane];
-                s_jobs[lane] = j;
-                fst = rd_lo[j] / MT_ROWS == t;
-                // which of the tile's four 16-row groups this job's window touches
-                const int lo = rd_lo[j] - row0, hi = rd_hi[j] - row0;
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) mk |= (lo < 16 * (g4 + 1) && hi > 16 * g4) ? (1 << g4) : 0;
-                if (rd_n1[j] > rd_n0[j]) {   // bins where this job's v is not exactly 0
-                    nlo = rd_n0[j];
-                    nhi = rd_n1[j];
-                }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                mk |= __shfl_xor(mk, off, 64);
-                nlo = min(nlo, __shfl_xor(nlo, off, 64));
-                nhi = max(nhi, __shfl_xor(nhi, off, 64));
-            }
-            const unsigned long long fmask = __ballot(fst);
-            if (lane == 0) {
-                s_need = mk;
-                s_nlo = nlo;
-                s_nhi = nhi;
-                s_first = __popcll(fmask);
-            }
-        }
-        __syncthreads();
-        // terms with v[n] == 0 add exactly 0 to every score: only the union of the supports is streamed
-        const int n_lo = (s_nhi > 0) ? (s_nlo & ~15) : 0;
-        const int n_sup = (s_nhi > 0) ? min(Np, (s_nhi + 15) & ~15) : 0;
-        // beyond n_ext every row of this tile holds the sentinel (k_tile_extent): that part of each dot
-        // product is SENT * sum_{n >= n_ext} v[n], no tensor bytes needed
-        const int n_ext = tile_nend[d.tile_off + t];
-        const int n_hi = min(n_sup, n_ext);
-        const int need = s_need;
-        if (tid == 0 && n_hi > n_lo) {
-            int rows = 0;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-                if ((need >> g4) & 1) rows += max(0, min(16, nrows - row0 - 16 * g4));
-            const unsigned long long span = (unsigned long long)(n_hi - n_lo) * 8ull;
-            s_by[0] += span * (unsigned long long)rows;
-            s_by[1] += span * (unsigned long long)cnt;
-            s_by[2] += span * (unsigned long long)s_first;   // jobs whose window starts in this tile
-        }
-        for (int sj = tid; sj < cnt; sj += 256) {
-            const int j = s_jobs[sj];
-            s_tail[sj] = Vsuf[(voff[j] >> 4) + j + (n_ext >> 4)];   // sum_{n >= n_ext} v_j[n] (k2_estep)
-        }
-        __syncthreads();
-        v4f64 acc[MT_RB][MT_MAXJ / 16];
-#pragma unroll
-        for (int rb = 0; rb < MT_RB; ++rb)
-#pragma unroll
-            for (int g = 0; g < MT_MAXJ / 16; ++g) acc[rb][g] = (v4f64){0.0, 0.0, 0.0, 0.0};
-        switch (G) {
-            case 1: mstep_pass<1, MT_DEEP>(Mu, V, voff, s_jobs, mt, vt, cnt, Np, n_lo, n_hi, nrows, row0, wave, lane, need, acc); break;
-            case 2: mstep_pass<2, MT_DEEP>(Mu, V, voff, s_jobs, mt, vt, cnt, Np, n_lo, n_hi, nrows, row0, wave, lane, need, acc); break;
-            case 3: mstep_pass<3, 2>(Mu, V, voff, s_jobs, mt, vt, cnt, Np, n_lo, n_hi, nrows, row0, wave, lane, need, acc); break;
-            default: mstep_pass<4, 2>(Mu, V, voff, s_jobs, mt, vt, cnt, Np, n_lo, n_hi, nrows, row0, wave, lane, need, acc); break;
-        }
-        // per job: arg-max over this wave's 16 rows (first maximum = lowest row), then over the 4 waves
-        {
-            const int kq = lane >> 4, rc = lane & 15;
-#pragma unroll
-            for (int g = 0; g < MT_MAXJ / 16; ++g) {
-                if (g < G) {
-                    const int slot_j = 16 * g + rc;
-                    double best = -INFINITY;
-                    int best_r = 0x7fffffff;
-                    if (slot_j < cnt) {
-                        const int j = s_jobs[slot_j];
-                        const int lo = rd_lo[j], hi = rd_hi[j];
-                        const double tl = s_tail[slot_j];
-                        const double c0 = rd_lw[j] * rd_sv[j] + ((tl != 0.0) ? SENT * tl : 0.0);
-#pragma unroll
-                        for (int rb = 0; rb < MT_RB; ++rb) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int row = row0 + 16 * (MT_RB * wave + rb) + kq + 4 * i;
-                                const double sc = c0 + acc[rb][g][i];
-                                if (row >= lo && row < hi && row < nrows && sc > best) {   // ascending rows: first max
-                                    best = sc;
-                                    best_r = row;
-                                }
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int off = 16; off <= 32; off <<= 1) {
-                        const double ob = __shfl_xor(best, off, 64);
-                        const int orr = __shfl_xor(best_r, off, 64);
-                        if (ob > best || (ob == best && orr < best_r)) {
-                            best = ob;
-                            best_r = orr;
-                        }
-                    }
-                    if (kq == 0 && slot_j < cnt) {
-                        s_ps[wave][slot_j] = best;
-                        s_pr[wave][slot_j] = best_r;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        for (int sj = tid; sj < cnt; sj += 256) {
-            double best = s_ps[0][sj];
-            int best_r = s_pr[0][sj];
-            for (int w = 1; w < 4; ++w)
-                if (s_ps[w][sj] > best) {   // waves hold ascending rows: strict > keeps the first maximum
-                    best = s_ps[w][sj];
-                    best_r = s_pr[w][sj];
-                }
-            const int j = s_jobs[sj];
-            pt_score[ptoff[j] + t] = best;
-            pt_row[ptoff[j] + t] = (best_r == 0x7fffffff) ? max(rd_lo[j], row0) : best_r;
-        }
-    }
-    if (tid == 0 && s_by[0]) {
-        const int sh = (int)(blockIdx.x & 63);
-        atomicAdd(&counters[CNT_MSTEP_TENSOR + sh], s_by[0]);
-        atomicAdd(&counters[CNT_MSTEP_VREQ + sh], s_by[1]);
-        atomicAdd(&counters[CNT_MSTEP_VUNI + sh], s_by[2]);
-    }
-}

@@ -1,6 +1,6 @@
 // mstep_multi.inc - k4_mstep: k3_mstep's LDS-DMA stream (mstep_ring.inc) with the per-tile set-up and arg-max epilogue
 // taken off the critical path.  (included by scape_hip.hip after mstep_ring.inc; same inputs, same per-(job, tile)
-// outputs, same MFMA chain per score: identical bits.)  Reference semantics: max_alpha_beta, apa_core.py:507-523.
+// outputs, same frame (mstep.inc) and same MFMA chain per score: identical bits.)  The headline kernel.
 //
 // Why (profiles/README.md, round 3: no-stream / no-MFMA / no-DMA timing builds of k3_mstep): a tile's set-up - job scan,
 // window / support reductions, suffix-sum look-ups: five to six dependent global round trips - and its arg-max epilogue
@@ -32,7 +32,7 @@ static_assert(M4_TPW >= 1 && M4_TPW <= 4, "one wavefront per tile table");
 // (Measured and dropped, see DESIGN.md section 3 - the code is in the history: extra loader wavefronts (4 at 2 workgroups per CU:
 // 2.26 ms per launch; 2 at 3 workgroups per CU, 96 VGPRs: 2.41 ms, against 1.98), fragment prefetch, s_setprio, a third / fourth
 // tile per workgroup, the tile ring deeper than the vector ring.)
-static_assert(M4_TPW * M4_NW <= 16, "per-wavefront hit counts of the set-up");
+static_assert(M4_TPW * M4_NW <= 16 && M4_NW == 4, "per-wavefront hit counts of the set-up (mstep_ordinal: 4 per tile)");
 __device__ __forceinline__ bool m4_is_tile_issuer(int wave) { return wave < 2; }
 __device__ __forceinline__ bool m4_is_vec_issuer(int wave) { return wave >= 2; }
 __device__ __forceinline__ int m4_role_index(int wave) { return wave & 1; }   // 0 / 1 within the role
@@ -106,10 +106,10 @@ __device__ __forceinline__ void m4_seg(const M4Tile &T, unsigned lds_area, const
                                        v4f64 (&acc)[MT_MAXJ / 16]) {
     constexpr int RT = m4_rt(G), RV = m4_rv(G), VSLOT = G * 16 * M3_CH;
     const double *ringV = area, *ringT = area + RV * VSLOT;
-    const int kq = lane >> 4, rc = lane & 15, f = (rc >> 1) & 7;
+    const int kq = lane >> 4, rc = lane & 15;
     int offd[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) offd[s] = ((((2 * s + (kq >> 1)) ^ f) << 1) | (kq & 1));
+    for (int s = 0; s < 4; ++s) offd[s] = m3_frag_index(s, kq, rc);
     const bool vwave = m4_is_vec_issuer(wave);
     const int ahead = vwave ? RV - 1 : RT - 1;
     const int nh = T.nh;
@@ -140,15 +140,7 @@ __device__ __forceinline__ void m4_seg(const M4Tile &T, unsigned lds_area, const
         if (T.needed) {
             const double *ts = ringT + (h % RT) * M3_TSLOT + (16 * wave + rc) * M3_CH;
             const double *vs = ringV + (h % RV) * VSLOT + rc * M3_CH;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const double a = ts[offd[s]];
-                double b[GA];
-#pragma unroll
-                for (int g = 0; g < GA; ++g) b[g] = vs[g * 16 * M3_CH + offd[s]];
-#pragma unroll
-                for (int g = 0; g < GA; ++g) acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[g], acc[g], 0, 0, 0);
-            }
+            mstep_kstep<GA>(ts, vs, offd, acc);
         }
 #ifdef M4_STAMPS
         asm volatile("" : "+v"(acc[0]));          // the last MFMA's result is waited for before the stamp
@@ -192,25 +184,7 @@ __device__ __forceinline__ void m4_loop(const M4Tile &T, unsigned lds_area, cons
     m4_seg<G, 1>(T, lds_area, area, wave, lane, h, nh, acc);
 }
 
-__global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep(const UtrDesc *__restrict__ descs, DevParams P,
-                                                        const double *__restrict__ M, const int32_t *__restrict__ active, int n_utr, int groups_max,
-                                                        const int64_t *__restrict__ ujob_off,
-                                                        const int32_t *__restrict__ ujob_list,
-                                                        const double *__restrict__ V,
-                                                        const double *__restrict__ Vsuf,
-                                                        const int64_t *__restrict__ voff,
-                                                        const int32_t *__restrict__ rd_m,
-                                                        const int32_t *__restrict__ rd_lo,
-                                                        const int32_t *__restrict__ rd_hi,
-                                                        const double *__restrict__ rd_lw,
-                                                        const double *__restrict__ rd_sv,
-                                                        const int32_t *__restrict__ rd_n0,
-                                                        const int32_t *__restrict__ rd_n1,
-                                                        const int64_t *__restrict__ ptoff,
-                                                        double *__restrict__ pt_score,
-                                                        int32_t *__restrict__ pt_row,
-                                                        const int32_t *__restrict__ tile_nend,
-                                                        unsigned long long *__restrict__ counters) {
+__global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep(MSTEP_PARAMS(groups_max)) {
     extern __shared__ __attribute__((aligned(16))) double m4_lds[];
     double *area = m4_lds;
     double *x_ps = m4_lds + M4_AREA_BYTES / 8;                        // exchange [4][64] scores
@@ -222,17 +196,8 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
     unsigned long long *s_by = reinterpret_cast<unsigned long long *>(s_misc + 16);
     const unsigned lds_area = (unsigned)(size_t)(__attribute__((address_space(3))) double *)area;
 
-    const int id = blockIdx.x;
     int ul, tg;
-    if (n_utr >= 8) {   // blocks b and b+8 share an XCD: one XCD gets all tiles of a UTR (its job vectors stay in one L2)
-        const int slot = id >> 3;
-        ul = (slot / groups_max) * 8 + (id & 7);
-        tg = slot % groups_max;
-    } else {
-        ul = id % n_utr;
-        tg = id / n_utr;
-    }
-    if (ul >= n_utr || tg >= groups_max) return;
+    if (!mstep_block(blockIdx.x, n_utr, groups_max, ul, tg)) return;
     const int u = active[ul];
     const UtrDesc d = descs[u];
     const int B = P.B, Np = d.Np;
@@ -264,21 +229,15 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
             for (int i = 0; i < M4_TPW; ++i) {
                 const int row0 = (t_first + i) * MT_ROWS;
                 const bool hit = i >= i_lo && i < i_hi && lo < row0 + MT_ROWS && hi > row0;     // (lo = hi = 0 never hits)
-                const unsigned long long mask = __ballot(hit);
-                if (lane == 0) s_misc[M4_NW * i + wave] = __popcll(mask);
+                mstep_count_hits(hit, lane, wave, s_misc + M4_NW * i);
             }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < M4_TPW; ++i) {
                 const int row0 = (t_first + i) * MT_ROWS;
                 const bool hit = i >= i_lo && i < i_hi && lo < row0 + MT_ROWS && hi > row0;
-                const unsigned long long mask = __ballot(hit);
-                int off = found[i];
-                for (int w = 0; w < wave; ++w) off += s_misc[M4_NW * i + w];
-                off += __popcll(mask & ((1ull << lane) - 1ull));
+                const int off = mstep_ordinal(__ballot(hit), lane, wave, s_misc + M4_NW * i, found[i]);
                 if (hit && off >= base && off < base + 64) rec_i[(i * 64 + off - base) * 6 + 2] = j;
-#pragma unroll
-                for (int w = 0; w < M4_NW; ++w) found[i] += s_misc[M4_NW * i + w];
             }
             __syncthreads();
         }
@@ -288,8 +247,7 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
         const int t = t_first + i, row0 = t * MT_ROWS;
         const int cnt = max(0, min(total - base, 64));
         const int n_ext = tile_nend[d.tile_off + t];
-        int mk = 0, nlo = 0x7fffffff, nhi = 0;
-        bool fst = false;
+        MstepWin w;
         int j = 0, lo = 0, hi = 0, n0 = 0, n1 = 0, po32 = 0, vo16 = 0;
         double c0 = 0.0;
         if (lane < cnt) {
@@ -301,29 +259,13 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
             const int64_t vo = voff[j];
             const double lw = rd_lw[j], sv = rd_sv[j];
             const int64_t po = ptoff[j];
-            const double tl = Vsuf[(vo >> 4) + j + (n_ext >> 4)];   // sum_{n >= n_ext} v_j[n] (k2_estep)
-            c0 = lw * sv + ((tl != 0.0) ? SENT * tl : 0.0);
-            fst = lo / MT_ROWS == t;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) mk |= (lo - row0 < 16 * (g4 + 1) && hi - row0 > 16 * g4) ? (1 << g4) : 0;
-            if (n1 > n0) {
-                nlo = n0;
-                nhi = n1;
-            }
+            c0 = mstep_c0(lw, sv, Vsuf[mstep_tail_index(vo, j, n_ext)]);
+            w = mstep_window_of_job(lo, hi, n0, n1, row0, t);
             po32 = (int)(po + t);              // output slot of this (job, tile)
             vo16 = (int)(vo >> 4);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mk |= __shfl_xor(mk, off, 64);
-            nlo = min(nlo, __shfl_xor(nlo, off, 64));
-            nhi = max(nhi, __shfl_xor(nhi, off, 64));
-        }
-        const unsigned long long fmask = __ballot(fst);
-        const int n_lo = (nhi > 0) ? (nlo & ~15) : 0;
-        const int n_sup = (nhi > 0) ? min(Np, (nhi + 15) & ~15) : 0;
-        const int n_hi = min(n_sup, n_ext);
-        const int nh = (n_hi > n_lo) ? (n_hi - n_lo) >> 4 : 0;
+        w = mstep_window_reduce(w);
+        const MstepSpan sp = mstep_span(w.nlo, w.nhi, Np, n_ext);
         // Terms with v[n] == 0 add exactly 0 to a score, so a job's columns need no k-steps beyond the last bin of its v.
         // Jobs are ranked by that end, longest first, and take their table slots in rank order: column group g (ranks
         // 16 g ..) then runs only he_g = the end of its first member, in half-chunks - the groups drop out of the
@@ -331,7 +273,7 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
         // Which slot a job gets changes nothing in its own chain of MFMAs.
         if (lane < 4) t_he[i * 4 + lane] = 0;
         int hc = 0;                                       // half-chunks this job's v reaches into the streamed range
-        if (lane < cnt && n1 > n0) hc = max(0, min((min(n1, n_hi) - n_lo + 15) >> 4, nh));
+        if (lane < cnt && n1 > n0) hc = max(0, min((min(n1, sp.n_hi) - sp.n_lo + 15) >> 4, sp.nh));
         int rank = 0;
         for (int o = 0; o < 64; ++o) {
             const int other = __shfl(hc, o, 64);
@@ -349,10 +291,10 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
         if (lane == 0) {
             int *sc = t_sc + i * 8;
             sc[0] = cnt;
-            sc[1] = n_lo;
-            sc[2] = nh;
-            sc[3] = mk;
-            sc[4] = __popcll(fmask);
+            sc[1] = sp.n_lo;
+            sc[2] = sp.nh;
+            sc[3] = w.mk;
+            sc[4] = w.first;
             sc[5] = n_ext;
             sc[6] = total;
         }
@@ -390,7 +332,7 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
                 if ((need >> (pc >> 1)) & 1) {
                     const int r = 8 * pc + l8;
                     const int rr = min(row0 + r, nrows - 1) - row0;
-                    const unsigned o = (unsigned)(((size_t)rr * Np + 2 * (u8 ^ ((r >> 1) & 7))) * 8);
+                    const unsigned o = (unsigned)(((size_t)rr * Np + m3_src_unit(r, u8)) * 8);
                     // compact the needed pieces to the front (np_w is wave-uniform: `need` is)
                     if (T.np_w == 0) T.offs[0] = o; else if (T.np_w == 1) T.offs[1] = o; else if (T.np_w == 2) T.offs[2] = o; else T.offs[3] = o;
                     T.pieces |= (unsigned)pc << (4 * T.np_w);
@@ -402,7 +344,7 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
             for (int q = 0; q < 4; ++q) {
                 const int js = 8 * (2 * q + m4_role_index(wave)) + l8;      // job slots of this wavefront's piece of column group q
                 const unsigned vo16 = (unsigned)rec_i[(i * 64 + min(js, max(cnt, 1) - 1)) * 6 + 3];
-                T.offs[q] = (unsigned)((((size_t)vo16 << 4) + 2 * (u8 ^ ((js >> 1) & 7))) * 8);
+                T.offs[q] = (unsigned)((((size_t)vo16 << 4) + m3_src_unit(js, u8)) * 8);
             }
         }
 #ifdef M4_STAMPS
@@ -410,16 +352,7 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
 #endif
         T.tb0 = m3_uniform_ptr(Mu + (size_t)row0 * Np + n_lo);
         T.vb0 = m3_uniform_ptr(V + n_lo);
-        if (tid == 0 && T.nh > 0) {        // byte tally, as k2_mstep / k3_mstep
-            int rows = 0;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-                if ((need >> g4) & 1) rows += max(0, min(16, nrows - row0 - 16 * g4));
-            const unsigned long long span = (unsigned long long)T.nh * 128ull;
-            s_by[0] += span * (unsigned long long)rows;
-            s_by[1] += span * (unsigned long long)cnt;
-            s_by[2] += span * (unsigned long long)sc[4];
-        }
+        if (tid == 0 && T.nh > 0) mstep_tally(s_by, need, nrows, row0, T.nh, cnt, sc[4]);
     };
 #define M4_BY_G(G_, CALL)                 \
     switch (G_) {                          \
@@ -447,41 +380,22 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
         }
         const int cnt = __builtin_amdgcn_readfirstlane(t_sc[i * 8]);
         const int G = (cnt + 15) >> 4;
-        {
-            const int kq = lane >> 4, rc = lane & 15;
+        const int kq = lane >> 4, rc = lane & 15;
 #pragma unroll
-            for (int g = 0; g < MT_MAXJ / 16; ++g) {
-                if (g < G) {
-                    const int slot_j = 16 * g + rc;
-                    double best = -INFINITY;
-                    int best_r = 0x7fffffff;
-                    if (slot_j < cnt) {
-                        const int *rc_ = rec_i + (i * 64 + slot_j) * 6;
-                        const int lo = rc_[0], hi = rc_[1];
-                        const double c0 = *reinterpret_cast<const double *>(rc_ + 4);
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int row = row0 + 16 * wave + kq + 4 * q;
-                            const double sc = c0 + acc[g][q];
-                            if (row >= lo && row < hi && row < nrows && sc > best) {   // ascending rows: first max
-                                best = sc;
-                                best_r = row;
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int off = 16; off <= 32; off <<= 1) {
-                        const double ob = __shfl_xor(best, off, 64);
-                        const int orr = __shfl_xor(best_r, off, 64);
-                        if (ob > best || (ob == best && orr < best_r)) {
-                            best = ob;
-                            best_r = orr;
-                        }
-                    }
-                    if (kq == 0 && slot_j < cnt) {
-                        x_ps[wave * 64 + slot_j] = best;
-                        x_pr[wave * 64 + slot_j] = best_r;
-                    }
+        for (int g = 0; g < MT_MAXJ / 16; ++g) {
+            if (g < G) {
+                const int slot_j = 16 * g + rc;
+                MstepBest b;
+                if (slot_j < cnt) {
+                    const int *rc_ = rec_i + (i * 64 + slot_j) * 6;
+                    const int lo = rc_[0], hi = rc_[1];
+                    const double c0 = *reinterpret_cast<const double *>(rc_ + 4);
+                    b = mstep_best_of_rows(b, acc[g], c0, lo, hi, row0 + 16 * wave + kq, nrows);
+                }
+                b = mstep_merge_lanes(b);
+                if (kq == 0 && slot_j < cnt) {
+                    x_ps[wave * 64 + slot_j] = b.score;
+                    x_pr[wave * 64 + slot_j] = b.row;
                 }
             }
         }
@@ -489,17 +403,11 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (tid < cnt) {         // wavefront 0 (cnt <= 64)
-            double best = x_ps[tid];
-            int best_r = x_pr[tid];
-            for (int w = 1; w < 4; ++w)
-                if (x_ps[w * 64 + tid] > best) {   // waves hold ascending rows: strict > keeps the first maximum
-                    best = x_ps[w * 64 + tid];
-                    best_r = x_pr[w * 64 + tid];
-                }
+            const MstepBest b = mstep_merge_waves(x_ps, x_pr, 64, tid);
             const int *rc_ = rec_i + (i * 64 + tid) * 6;
             // ptoff + t fits 32 bits (the host checks the size of the partial tables)
-            pt_score[(unsigned)rc_[2]] = best;
-            pt_row[(unsigned)rc_[2]] = (best_r == 0x7fffffff) ? max(rc_[0], row0) : best_r;
+            pt_score[(unsigned)rc_[2]] = b.score;
+            pt_row[(unsigned)rc_[2]] = mstep_row_or_fallback(b.row, rc_[0], row0);
         }
         // (the exchange area is rewritten by the next epilogue only behind a later barrier)
     };
@@ -533,10 +441,5 @@ __global__ __launch_bounds__(64 * M4_NW, (M4_NW * M4_WPC + 3) / 4) void k4_mstep
         }
     }
 #undef M4_BY_G
-    if (tid == 0 && s_by[0]) {
-        const int sh = (int)(blockIdx.x & 63);
-        atomicAdd(&counters[CNT_MSTEP_TENSOR + sh], s_by[0]);
-        atomicAdd(&counters[CNT_MSTEP_VREQ + sh], s_by[1]);
-        atomicAdd(&counters[CNT_MSTEP_VUNI + sh], s_by[2]);
-    }
+    if (tid == 0) mstep_tally_flush(counters, s_by);
 }

@@ -1,7 +1,8 @@
-// mstep_ring.inc - k3_mstep: the M-step of em_lockstep.inc with both MFMA operands brought into LDS by LDS-DMA.
-// (included by scape_hip.hip after em_lockstep.inc; same grid, same job tables, same per-(job, tile) outputs as
-// k2_mstep, and the same MFMA chain per score - v_mfma_f64_16x16x4_f64 over ascending bins - so the bits are
-// k2_mstep's.)  Reference semantics: max_alpha_beta, /root/reference/src/scape/apa_core.py:507-523.
+// mstep_ring.inc - k3_mstep: the M-step with both MFMA operands brought into LDS by LDS-DMA.
+// (included by scape_hip.hip after mstep.inc and mstep_staged.inc; same grid, same job tables, same per-(job, tile)
+// outputs as k2_mstep through the same frame (mstep.inc), and the same MFMA chain per score -
+// v_mfma_f64_16x16x4_f64 over ascending bins - so the bits are k2_mstep's.)  Runs small calls whose tiles are shared
+// by several workgroups (gridDim.y > 1), under SCAPE_HIP_MSTEP=v3 and under SCAPE_HIP_DEBUG.
 //
 // What changed against k2_mstep, and why (profiles/r02_mstep_per_round.txt: rounds 0-8 ran at 3.5-4.1 TB/s):
 // k2_mstep stages every 16 KB tile chunk and its job vectors global -> VGPR -> LDS (ds_write_b128: 13 cycles of
@@ -12,9 +13,8 @@
 //   - ONE barrier per half-chunk: wait (counted vmcnt) for this wavefront's own DMAs of half-chunk h, barrier,
 //     then issue the DMAs that refill the slots half-chunk h-1 has just left, then the 4 k-steps of h;
 //   - an LDS-DMA instruction writes 1 KB lane-linear (wave-uniform base + 16 B x lane), so the bank-conflict-free
-//     image is made on the SOURCE side: lane (r8, u) of an instruction fetches 16-byte unit u ^ ((row >> 1) & 7)
-//     of row r8 (cdna_hip_programming.md section 5, "Async global->LDS copy").  Fragment reads (ds_read_b64) of 16
-//     rows x 2 taps then hit 32 distinct bank pairs.
+//     image is made on the SOURCE side (m3_src_unit / m3_frag_index, mstep.inc; cdna_hip_programming.md section 5,
+//     "Async global->LDS copy");
 //   - DMA roles: wavefronts 0-2 issue the 8 tile pieces of a half-chunk (3 + 3 + 2; a piece = 8 rows x 128 B), wavefront 3
 //     issues all job-vector pieces (2 per column group).  s_waitcnt vmcnt counts a wavefront's vector-memory operations
 //     IN ISSUE ORDER, so a wavefront that issued both kinds could only keep what it issued after its newest vector piece
@@ -28,7 +28,6 @@
 #ifndef M3_TILE_NT
 #define M3_TILE_NT true
 #endif
-#define M3_CH 16                       // bins per half-chunk
 #define M3_TSLOT (64 * M3_CH)          // f64 per tile slot (8 KB)
 // LDS of a workgroup: [ring area | s_jobs[64] | s_tail[64] f64 | 16 ints | 4 u64].  gfx950 hands LDS out in granules of
 // 1,280 B (160 KB = 128 granules): 3 workgroups per CU get 42 granules = 53,760 B each, 2 get 64 = 81,920 B.
@@ -95,10 +94,10 @@ __device__ __forceinline__ void m3_stream(const double *tb0 /* Mu + row0 Np + n_
     constexpr int VSLOT = G * 16 * M3_CH;                 // f64 per job-vector slot
     const double *ringV = area, *ringT = area + RV * VSLOT;
     const unsigned lds_V = lds_area, lds_T = lds_area + RV * VSLOT * 8;
-    const int kq = lane >> 4, rc = lane & 15, f = (rc >> 1) & 7;
+    const int kq = lane >> 4, rc = lane & 15;
     int offd[4];   // f64 index inside a 16-bin row of the swizzled image, per k-step
 #pragma unroll
-    for (int s = 0; s < 4; ++s) offd[s] = ((((2 * s + (kq >> 1)) ^ f) << 1) | (kq & 1));
+    for (int s = 0; s < 4; ++s) offd[s] = m3_frag_index(s, kq, rc);
     const bool vwave = wave == 3;
     auto issue = [&](int h) {          // this wavefront's pieces of half-chunk h (tile pieces, or all job-vector pieces)
         if (vwave) {
@@ -129,44 +128,12 @@ __device__ __forceinline__ void m3_stream(const double *tb0 /* Mu + row0 Np + n_
         if (needed) {
             const double *ts = ringT + (h % RT) * M3_TSLOT + (16 * wave + rc) * M3_CH;
             const double *vs = ringV + (h % RV) * VSLOT + rc * M3_CH;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const double a = ts[offd[s]];
-                double b[G];
-#pragma unroll
-                for (int g = 0; g < G; ++g) b[g] = vs[g * 16 * M3_CH + offd[s]];
-#ifdef M3_NO_MFMA   // tools-only timing build: fragment reads without the matrix instructions (results are wrong)
-#pragma unroll
-                for (int g = 0; g < G; ++g) acc[g][0] += a + b[g];
-#else
-#pragma unroll
-                for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[g], acc[g], 0, 0, 0);
-#endif
-            }
+            mstep_kstep<G>(ts, vs, offd, acc);
         }
     }
 }
 
-__global__ __launch_bounds__(256, M3_WPC) void k3_mstep(const UtrDesc *__restrict__ descs, DevParams P,
-                                                        const double *__restrict__ M, const int32_t *__restrict__ active, int n_utr, int tiles_max,
-                                                        const int64_t *__restrict__ ujob_off,
-                                                        const int32_t *__restrict__ ujob_list,
-                                                        const double *__restrict__ V,
-                                                        const double *__restrict__ Vsuf,
-                                                        const int64_t *__restrict__ voff,
-                                                        const int32_t *__restrict__ rd_m,
-                                                        const int32_t *__restrict__ rd_lo,
-                                                        const int32_t *__restrict__ rd_hi,
-                                                        const double *__restrict__ rd_lw,
-                                                        const double *__restrict__ rd_sv,
-                                                        const int32_t *__restrict__ rd_n0,
-                                                        const int32_t *__restrict__ rd_n1,
-                                                        const int64_t *__restrict__ ptoff,
-                                                        double *__restrict__ pt_score,
-                                                        int32_t *__restrict__ pt_row,
-                                                        const int32_t *__restrict__ tile_nend,
-                                                        unsigned long long *__restrict__ counters, int jobs_per_pass,
-                                                        unsigned long long *__restrict__ dbg) {
+__global__ __launch_bounds__(256, M3_WPC) void k3_mstep(MSTEP_PARAMS(tiles_max), int jobs_per_pass, unsigned long long *__restrict__ dbg) {
     // all LDS of the kernel is one dynamic array (a second __shared__ object beside an LDS-DMA target can make the
     // compiler drain the vector-memory counter before LDS reads: cdna_hip_programming.md section 5)
     extern __shared__ __attribute__((aligned(16))) double m3_lds[];
@@ -180,17 +147,8 @@ __global__ __launch_bounds__(256, M3_WPC) void k3_mstep(const UtrDesc *__restric
     int *s_pr = reinterpret_cast<int *>(area + 4 * MT_MAXJ);    // [4][MT_MAXJ]
     const unsigned lds_area = (unsigned)(size_t)(__attribute__((address_space(3))) double *)area;
 
-    const int id = blockIdx.x;
     int ul, t;
-    if (n_utr >= 8) {   // blocks b and b+8 share an XCD: one XCD gets all tiles of a UTR (its job vectors stay in one L2)
-        const int slot = id >> 3;
-        ul = (slot / tiles_max) * 8 + (id & 7);
-        t = slot % tiles_max;
-    } else {
-        ul = id % n_utr;
-        t = id / n_utr;
-    }
-    if (ul >= n_utr || t >= tiles_max) return;
+    if (!mstep_block(blockIdx.x, n_utr, tiles_max, ul, t)) return;
     const int u = active[ul];
     const UtrDesc d = descs[u];
     const int B = P.B, Np = d.Np;
@@ -199,41 +157,17 @@ __global__ __launch_bounds__(256, M3_WPC) void k3_mstep(const UtrDesc *__restric
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const double *Mu = M + (size_t)d.m_off;
     const int64_t jlo = ujob_off[u], jhi = ujob_off[u + 1];
-    // The jobs of this UTR whose window covers the tile, in job-list order (a stable compaction: workgroups that share
-    // a tile when gridDim.y > 1 must agree on which jobs belong to which pass).  There is no LDS for the whole list
-    // beside the rings: a scan stores the hits with ordinals [base, base + jobs_per_pass) straight into s_jobs and
-    // returns the total; tiles with more jobs than one pass holds (rare) scan again per pass.
+    // There is no LDS for a tile's whole job list beside the rings: a scan stores the hits with ordinals
+    // [base, base + jobs_per_pass) straight into s_jobs and returns the total; tiles with more jobs than one pass
+    // holds (rare) scan again per pass.
     auto collect = [&](int base) -> int {
-        int found = 0;
-        for (int64_t j0 = jlo; j0 < jhi; j0 += 256) {
-            const int64_t jj = j0 + tid;
-            int j = -1;
-            bool hit = false;
-            if (jj < jhi) {
-                j = ujob_list[jj];
-                hit = rd_m[j] && rd_lo[j] < row0 + MT_ROWS && rd_hi[j] > row0;
-            }
-            const unsigned long long mask = __ballot(hit);
-            if (lane == 0) s_misc[wave] = __popcll(mask);
-            __syncthreads();
-            int off = found;
-            for (int w = 0; w < wave; ++w) off += s_misc[w];
-            off += __popcll(mask & ((1ull << lane) - 1ull));
-            if (hit && off >= base && off < base + jobs_per_pass) s_jobs[off - base] = j;
-            found += s_misc[0] + s_misc[1] + s_misc[2] + s_misc[3];
-            __syncthreads();
-        }
-        return found;   // the same in every thread
+        return mstep_collect(ujob_list, jlo, jhi, rd_m, rd_lo, rd_hi, row0, tid, lane, wave, s_misc, [&](int off, int j) {
+            if (off >= base && off < base + jobs_per_pass) s_jobs[off - base] = j;
+        });
     };
     const int base0 = (int)blockIdx.y * jobs_per_pass;
     const int total = min(collect(base0), 1024);
-    if (dbg && tid == 0 && blockIdx.y == 0) {
-        atomicAdd(&dbg[0], 1ull);
-        atomicAdd(&dbg[1], (unsigned long long)(total > 0));
-        atomicAdd(&dbg[2], (unsigned long long)total);
-        atomicAdd(&dbg[3], (unsigned long long)((total + MT_MAXJ - 1) / MT_MAXJ));
-        atomicAdd(&dbg[4 + min((total + 15) / 16, 11)], 1ull);
-    }
+    if (dbg && tid == 0 && blockIdx.y == 0) mstep_debug_tile(dbg, total);
     if (total <= base0) return;
     if (tid == 0) s_by[0] = s_by[1] = s_by[2] = 0ull;
 
@@ -243,61 +177,35 @@ __global__ __launch_bounds__(256, M3_WPC) void k3_mstep(const UtrDesc *__restric
         const int G = (cnt + 15) >> 4;
         if (base != base0) collect(base);      // (ends with a barrier: the previous pass's reads of s_jobs and of the exchange area are done)
         if (wave == 0) {
-            int mk = 0, nlo = 0x7fffffff, nhi = 0;
-            bool fst = false;
+            MstepWin w;
             if (lane < cnt) {
                 const int j = s_jobs[lane];
-                fst = rd_lo[j] / MT_ROWS == t;
-                const int lo = rd_lo[j] - row0, hi = rd_hi[j] - row0;
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) mk |= (lo < 16 * (g4 + 1) && hi > 16 * g4) ? (1 << g4) : 0;
-                if (rd_n1[j] > rd_n0[j]) {
-                    nlo = rd_n0[j];
-                    nhi = rd_n1[j];
-                }
+                w = mstep_window_of_job(rd_lo[j], rd_hi[j], rd_n0[j], rd_n1[j], row0, t);
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                mk |= __shfl_xor(mk, off, 64);
-                nlo = min(nlo, __shfl_xor(nlo, off, 64));
-                nhi = max(nhi, __shfl_xor(nhi, off, 64));
-            }
-            const unsigned long long fmask = __ballot(fst);
+            w = mstep_window_reduce(w);
             if (lane == 0) {
-                s_misc[7] = mk;
-                s_misc[5] = nlo;
-                s_misc[6] = nhi;
-                s_misc[8] = __popcll(fmask);
+                s_misc[7] = w.mk;
+                s_misc[5] = w.nlo;
+                s_misc[6] = w.nhi;
+                s_misc[8] = w.first;
             }
         }
         __syncthreads();
         // wave-uniform by construction; readfirstlane tells the compiler so (scalar loop control, scalar DMA bases)
-        const int s_nlo = __builtin_amdgcn_readfirstlane(s_misc[5]), s_nhi = __builtin_amdgcn_readfirstlane(s_misc[6]);
         const int need = __builtin_amdgcn_readfirstlane(s_misc[7]);
-        const int n_lo = (s_nhi > 0) ? (s_nlo & ~15) : 0;
-        const int n_sup = (s_nhi > 0) ? min(Np, (s_nhi + 15) & ~15) : 0;
         const int n_ext = __builtin_amdgcn_readfirstlane(tile_nend[d.tile_off + t]);
-        const int n_hi = min(n_sup, n_ext);
-        if (tid == 0 && n_hi > n_lo) {
-            int rows = 0;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-                if ((need >> g4) & 1) rows += max(0, min(16, nrows - row0 - 16 * g4));
-            const unsigned long long span = (unsigned long long)(n_hi - n_lo) * 8ull;
-            s_by[0] += span * (unsigned long long)rows;
-            s_by[1] += span * (unsigned long long)cnt;
-            s_by[2] += span * (unsigned long long)s_misc[8];
-        }
+        const MstepSpan sp = mstep_span(__builtin_amdgcn_readfirstlane(s_misc[5]), __builtin_amdgcn_readfirstlane(s_misc[6]), Np, n_ext);
+        if (tid == 0 && sp.nh > 0) mstep_tally(s_by, need, nrows, row0, sp.nh, cnt, s_misc[8]);
         for (int sj = tid; sj < cnt; sj += 256) {
             const int j = s_jobs[sj];
-            s_tail[sj] = Vsuf[(voff[j] >> 4) + j + (n_ext >> 4)];
+            s_tail[sj] = Vsuf[mstep_tail_index(voff[j], j, n_ext)];
         }
         if (dbg && wave == 0) {   // how much of the MFMA work lies outside the jobs' own supports (SCAPE_HIP_DEBUG)
             int own = 0, hi_j = 0;
             if (lane < cnt) {
                 const int j = s_jobs[lane];
-                hi_j = max(0, min(rd_n1[j], n_hi) - n_lo);
-                own = (max(0, min(rd_n1[j], n_hi) - max(rd_n0[j] & ~15, n_lo)) + 15) >> 4;
+                hi_j = max(0, min(rd_n1[j], sp.n_hi) - sp.n_lo);
+                own = (max(0, min(rd_n1[j], sp.n_hi) - max(rd_n0[j] & ~15, sp.n_lo)) + 15) >> 4;
             }
             // groups of 16 after sorting by support end: every group runs to its largest end (bitonic-free: rank by counting)
             int rank = 0;
@@ -313,10 +221,9 @@ __global__ __launch_bounds__(256, M3_WPC) void k3_mstep(const UtrDesc *__restric
             }
             for (int o = 32; o > 0; o >>= 1) own += __shfl_xor(own, o, 64);
             if (lane == 0) {
-                const int nhc = (n_hi > n_lo) ? (n_hi - n_lo) >> 4 : 0;
                 atomicAdd(&dbg[16], (unsigned long long)own);
-                atomicAdd(&dbg[17], (unsigned long long)cnt * nhc);
-                atomicAdd(&dbg[18], (unsigned long long)16 * G * nhc);
+                atomicAdd(&dbg[17], (unsigned long long)cnt * sp.nh);
+                atomicAdd(&dbg[18], (unsigned long long)16 * G * sp.nh);
                 atomicAdd(&dbg[19], (unsigned long long)grp_sum);
             }
         }
@@ -333,7 +240,7 @@ __global__ __launch_bounds__(256, M3_WPC) void k3_mstep(const UtrDesc *__restric
                 if (pc < 8 && ((need >> (pc >> 1)) & 1)) {
                     const int r = 8 * pc + l8;
                     const int rr = min(row0 + r, nrows - 1) - row0;
-                    const unsigned o = (unsigned)(((size_t)rr * Np + 2 * (u8 ^ ((r >> 1) & 7))) * 8);
+                    const unsigned o = (unsigned)(((size_t)rr * Np + m3_src_unit(r, u8)) * 8);
                     // compact the needed pieces to the front (np_w is wave-uniform: `need` is)
                     if (np_w == 0) offs[0] = o; else if (np_w == 1) offs[1] = o; else offs[2] = o;
                     pieces |= (unsigned)pc << (4 * np_w);
@@ -345,85 +252,53 @@ __global__ __launch_bounds__(256, M3_WPC) void k3_mstep(const UtrDesc *__restric
             for (int i = 0; i < 8; ++i) {
                 const int js = 8 * i + l8;
                 const int j = s_jobs[min(js, cnt - 1)];
-                offs[i] = (unsigned)((voff[j] + 2 * (u8 ^ ((js >> 1) & 7))) * 8);
+                offs[i] = (unsigned)((voff[j] + m3_src_unit(js, u8)) * 8);
             }
         }
-        const int nh = (n_hi > n_lo) ? (n_hi - n_lo) >> 4 : 0;
-        const double *tb0 = m3_uniform_ptr(Mu + (size_t)row0 * Np + n_lo);
-        const double *vb0 = m3_uniform_ptr(V + n_lo);
+        const double *tb0 = m3_uniform_ptr(Mu + (size_t)row0 * Np + sp.n_lo);
+        const double *vb0 = m3_uniform_ptr(V + sp.n_lo);
         __syncthreads();   // s_tail visible
         v4f64 acc[MT_MAXJ / 16];
 #pragma unroll
         for (int g = 0; g < MT_MAXJ / 16; ++g) acc[g] = (v4f64){0.0, 0.0, 0.0, 0.0};
 #ifdef M3_NOSTREAM   // tools-only timing build: the per-tile set-up and arg-max epilogue without the stream (results are wrong)
-        if (nh < 0)
+        if (sp.nh < 0)
 #endif
         switch (G) {
-            case 1: m3_stream<1>(tb0, vb0, lds_area, area, nh, wave, lane, needed, offs, np_w, pieces, acc); break;
-            case 2: m3_stream<2>(tb0, vb0, lds_area, area, nh, wave, lane, needed, offs, np_w, pieces, acc); break;
-            case 3: m3_stream<3>(tb0, vb0, lds_area, area, nh, wave, lane, needed, offs, np_w, pieces, acc); break;
-            default: m3_stream<4>(tb0, vb0, lds_area, area, nh, wave, lane, needed, offs, np_w, pieces, acc); break;
+            case 1: m3_stream<1>(tb0, vb0, lds_area, area, sp.nh, wave, lane, needed, offs, np_w, pieces, acc); break;
+            case 2: m3_stream<2>(tb0, vb0, lds_area, area, sp.nh, wave, lane, needed, offs, np_w, pieces, acc); break;
+            case 3: m3_stream<3>(tb0, vb0, lds_area, area, sp.nh, wave, lane, needed, offs, np_w, pieces, acc); break;
+            default: m3_stream<4>(tb0, vb0, lds_area, area, sp.nh, wave, lane, needed, offs, np_w, pieces, acc); break;
         }
         // the last fragment reads of the rings are done in every wavefront before the exchange area reuses them
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();
-        {
-            const int kq = lane >> 4, rc = lane & 15;
+        const int kq = lane >> 4, rc = lane & 15;
 #pragma unroll
-            for (int g = 0; g < MT_MAXJ / 16; ++g) {
-                if (g < G) {
-                    const int slot_j = 16 * g + rc;
-                    double best = -INFINITY;
-                    int best_r = 0x7fffffff;
-                    if (slot_j < cnt) {
-                        const int j = s_jobs[slot_j];
-                        const int lo = rd_lo[j], hi = rd_hi[j];
-                        const double tl = s_tail[slot_j];
-                        const double c0 = rd_lw[j] * rd_sv[j] + ((tl != 0.0) ? SENT * tl : 0.0);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int row = row0 + 16 * wave + kq + 4 * i;
-                            const double sc = c0 + acc[g][i];
-                            if (row >= lo && row < hi && row < nrows && sc > best) {   // ascending rows: first max
-                                best = sc;
-                                best_r = row;
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int off = 16; off <= 32; off <<= 1) {
-                        const double ob = __shfl_xor(best, off, 64);
-                        const int orr = __shfl_xor(best_r, off, 64);
-                        if (ob > best || (ob == best && orr < best_r)) {
-                            best = ob;
-                            best_r = orr;
-                        }
-                    }
-                    if (kq == 0 && slot_j < cnt) {
-                        s_ps[wave * MT_MAXJ + slot_j] = best;
-                        s_pr[wave * MT_MAXJ + slot_j] = best_r;
-                    }
+        for (int g = 0; g < MT_MAXJ / 16; ++g) {
+            if (g < G) {
+                const int slot_j = 16 * g + rc;
+                MstepBest b;
+                if (slot_j < cnt) {
+                    const int j = s_jobs[slot_j];
+                    const int lo = rd_lo[j], hi = rd_hi[j];
+                    const double c0 = mstep_c0(rd_lw[j], rd_sv[j], s_tail[slot_j]);
+                    b = mstep_best_of_rows(b, acc[g], c0, lo, hi, row0 + 16 * wave + kq, nrows);
+                }
+                b = mstep_merge_lanes(b);
+                if (kq == 0 && slot_j < cnt) {
+                    s_ps[wave * MT_MAXJ + slot_j] = b.score;
+                    s_pr[wave * MT_MAXJ + slot_j] = b.row;
                 }
             }
         }
         __syncthreads();
         for (int sj = tid; sj < cnt; sj += 256) {
-            double best = s_ps[sj];
-            int best_r = s_pr[sj];
-            for (int w = 1; w < 4; ++w)
-                if (s_ps[w * MT_MAXJ + sj] > best) {   // waves hold ascending rows: strict > keeps the first maximum
-                    best = s_ps[w * MT_MAXJ + sj];
-                    best_r = s_pr[w * MT_MAXJ + sj];
-                }
+            const MstepBest b = mstep_merge_waves(s_ps, s_pr, MT_MAXJ, sj);
             const int j = s_jobs[sj];
-            pt_score[ptoff[j] + t] = best;
-            pt_row[ptoff[j] + t] = (best_r == 0x7fffffff) ? max(rd_lo[j], row0) : best_r;
+            pt_score[ptoff[j] + t] = b.score;
+            pt_row[ptoff[j] + t] = mstep_row_or_fallback(b.row, rd_lo[j], row0);
         }
     }
-    if (tid == 0 && s_by[0]) {
-        const int sh = (int)(blockIdx.x & 63);
-        atomicAdd(&counters[CNT_MSTEP_TENSOR + sh], s_by[0]);
-        atomicAdd(&counters[CNT_MSTEP_VREQ + sh], s_by[1]);
-        atomicAdd(&counters[CNT_MSTEP_VUNI + sh], s_by[2]);
-    }
+    if (tid == 0) mstep_tally_flush(counters, s_by);
 }

@@ -148,7 +148,7 @@ __device__ __forceinline__ void pb_store_log(const UtrDesc &d, int B, int i, int
     }
 }
 
-// Tile extents (used by the M-step, em_lockstep.inc): bins are ordered by read start, so each tensor row is finite on a
+// Tile extents (used by the M-step, mstep.inc: mstep_span): bins are ordered by read start, so each tensor row is finite on a
 // prefix of the bins and holds the sentinel (read impossible) on the rest - 35-50 % of all entries.  For every
 // TILE_ROWS-row tile the table gets one past the last bin that is finite in ANY of its rows (rounded up to 16): beyond
 // it every row of the tile is the sentinel, and the M-step replaces that part of the dot product by SENT * sum(v)

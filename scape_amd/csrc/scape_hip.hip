@@ -9,7 +9,7 @@
 // 64 lanes of a wavefront read/write consecutive f64; rows are padded to a 16-element pitch so
 // rows start 128-B aligned and can be read as double2.  The EM advances all (UTR, K, restart) jobs of a call
 // in lock-step rounds (em_lockstep.inc): k2_estep, one wavefront per job (responsibilities, weights, ELBO),
-// then k2_mstep, one workgroup per (UTR, 64-row tensor tile), which multiplies the tile with the v vectors of
+// then an M-step kernel (mstep.inc), one workgroup per (UTR, 64-row tensor tile), which multiplies the tile with the v vectors of
 // every job whose window covers it on the f64 matrix cores and keeps per-(job, tile) first arg-maxes.
 // All arithmetic is f64 (the reference's finite -inf sentinel overflows f32).
 #include <hip/hip_runtime.h>
@@ -356,7 +356,9 @@ __global__ __launch_bounds__(256) void k_phase_a(const UtrDesc *__restrict__ des
 }
 
 #include "phase_b.inc"      // Phase B: M[i][j][n], the marginal tensor over (alpha_i, beta_j) - all three forms
-#include "em_lockstep.inc"
+#include "em_lockstep.inc"  // the E-step, the shrink kernel and the EM's shared constants
+#include "mstep.inc"        // the M-step: the frame its three kernels share, then k2_mstep, k3_mstep, k4_mstep
+#include "mstep_staged.inc"
 #include "mstep_ring.inc"
 #include "mstep_multi.inc"
 
@@ -770,7 +772,7 @@ static int finish_build(scape_hip_ctx *c) {
 }
 
 // ------------------------------------------------------------------------------------------
-// host driver of the lock-step EM (kernels in em_lockstep.inc, mstep_ring.inc, mstep_multi.inc)
+// host driver of the lock-step EM (kernels in em_lockstep.inc and, on the frame of mstep.inc, mstep_staged.inc, mstep_ring.inc, mstep_multi.inc)
 // ------------------------------------------------------------------------------------------
 // Column classes: the CMAX template arguments each kernel family is instantiated for.  A call runs in the first class
 // that holds its kmax + 1 columns.
@@ -1245,7 +1247,7 @@ static int em_jobs_check(const BatchState &b, int n_jobs, int kmax, const int32_
             if (k < 0 || k > K || (K > 0 && k >= K)) return fail("job " + std::to_string(j) + ": k_arr entry out of range");
         }
     }
-    // k2_mstep keeps the per-tile list of a UTR's jobs in a fixed LDS table (em_lockstep.inc, s_all)
+    // k2_mstep keeps the per-tile list of a UTR's jobs in a fixed LDS table (mstep_staged.inc, s_all)
     std::vector<int32_t> per_utr(b.n_utr, 0);
     for (int j = 0; j < n_jobs; ++j)
         if (!job_fixed[j] && ++per_utr[job_utr[j]] > SCAPE_MAX_JOBS_PER_UTR)

@@ -1,7 +1,8 @@
 """The ladder of tests/test_mstep_ladder.py and tests/test_mstep_reference.py: tiny UTRs and job tables that put the
 bin count, the support of v, the finite extent of a tile, the window rows, the columns of a tile and the shape of the
-call on both sides of every boundary of the M-step kernels (k2_mstep, k3_mstep, k4_mstep) and of the E-step code that
-feeds them (k2_estep: rd_lo / rd_hi / rd_n0 / rd_n1, the suffix sums, the reduction across tiles).
+call on both sides of every boundary of the M-step kernels (k2_mstep, k3_mstep, k4_mstep: mstep_staged.inc,
+mstep_ring.inc, mstep_multi.inc on the frame of mstep.inc) and of the E-step code that feeds them (em_lockstep.inc,
+k2_estep: rd_lo / rd_hi / rd_n0 / rd_n1, the suffix sums, the reduction across tiles).
 tests/test_host.py reads the boundaries from the sources and checks the ladder against them.
 
 UtrPrep objects are built directly (not through prepare_utr), so that N is exactly what a case says; the theta grid is

@@ -886,7 +886,9 @@ def test_mstep_ladder_covers_every_boundary_of_the_mstep_kernels():
     import mstep_ladder as ml
     csrc = os.path.join(ROOT, "scape_amd", "csrc")
     src = open(os.path.join(csrc, "scape_hip.hip")).read()
-    k2 = open(os.path.join(csrc, "em_lockstep.inc")).read()
+    em = open(os.path.join(csrc, "em_lockstep.inc")).read()      # the constants the E-step and the host share with the M-step
+    frame = open(os.path.join(csrc, "mstep.inc")).read()         # what the three kernels share
+    k2 = open(os.path.join(csrc, "mstep_staged.inc")).read()
     k3 = open(os.path.join(csrc, "mstep_ring.inc")).read()
     k4 = open(os.path.join(csrc, "mstep_multi.inc")).read()
     hdr = open(os.path.join(ROOT, "include", "scape_hip.h")).read()
@@ -895,10 +897,12 @@ def test_mstep_ladder_covers_every_boundary_of_the_mstep_kernels():
         found = re.findall(r"#define\s+%s\s+(\d+)\b" % name, text)
         assert len(found) == 1, name
         return int(found[0])
-    MT_RB, MT_NC, MT_MAXJ, DEPTH = (define(k2, n) for n in ("MT_RB", "MT_NC", "MT_MAXJ", "EM_DEPTH"))
-    assert "#define MT_ROWS (64 * MT_RB)" in k2
+    MT_RB, MT_MAXJ, DEPTH = (define(em, n) for n in ("MT_RB", "MT_MAXJ", "EM_DEPTH"))
+    MT_NC = define(k2, "MT_NC")
+    assert "#define MT_ROWS (64 * MT_RB)" in em
     MT_ROWS = 64 * MT_RB
-    M3_CH, M3_WPC, M4_TPW = define(k3, "M3_CH"), define(k3, "M3_WPC"), define(k4, "M4_TPW")
+    M3_CH, M3_WPC, M4_TPW = define(frame, "M3_CH"), define(k3, "M3_WPC"), define(k4, "M4_TPW")
+    assert not re.findall(r"#define\s+(MT_NC|M3_CH)\b", em + k3 + k4)              # one definition each, in the file read above
     MAX_JOBS = define(hdr, "SCAPE_MAX_JOBS_PER_UTR")
     # ---- the ladder's constants and its restatement of the selection rule
     assert (ml.ROWS, ml.HALF, ml.MT_MAXJ, ml.EM_DEPTH, ml.MAX_JOBS_PER_UTR) == (MT_ROWS, M3_CH, MT_MAXJ, DEPTH, MAX_JOBS)
@@ -916,8 +920,10 @@ def test_mstep_ladder_covers_every_boundary_of_the_mstep_kernels():
     assert "k.multi_mstep = k.ring_mstep && !k.job_split && !sw.debug && p.pttot < ((size_t)1 << 31) && !sw.mstep_v3;" in src
     assert "const int jobs_per_pass = k.job_split ? 16 : MT_MAXJ;" in src
     assert "const unsigned psplit = k.job_split ? (unsigned)std::min(64, (p.max_cols_utr + 15) / 16) : 1u;" in src
-    xcd = re.findall(r"if \(n_utr >= (\d+)\) \{", k2 + k3 + k4)
-    assert len(xcd) == 3 and set(xcd) == {str(ml.XCD_UTRS)}, xcd
+    xcd = re.findall(r"if \(n_utr >= (\d+)\) \{", frame)                            # the grid rule: stated once, in mstep_block,
+    assert xcd == [str(ml.XCD_UTRS)] and not re.findall(r"n_utr\s*[<>]=?\s*\d", k2 + k3 + k4), xcd   # and taken from there by all three
+    for k in (k2, k3, k4):
+        assert len(re.findall(r"if \(!mstep_block\(blockIdx\.x, n_utr, \w+, ul, \w+\)\) return;", k)) == 1
     # ---- ring depths, from the formulas
     assert "#define M3_AREA_BYTES (M3_WPC >= 3 ? 51 * 1024 : 78 * 1024)" in k3
     assert "constexpr int m3_rv(int G) { return (M3_WPC >= 3) ? (G <= 1 ? 3 : 2) : 3; }" in k3

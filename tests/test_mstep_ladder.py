@@ -27,8 +27,9 @@ over the tiles learned the all-sentinel floor (em_lockstep.inc: rd_fl) - the row
 exactly, a tile below its finite extent summed the sentinel terms by the MFMA chain, a tile beyond it from the suffix
 sums, the two rounded differently and the later tile won (alpha index 80 where the reference and the oracle give 0).
 Scratch builds with one comparison or term changed (never committed) fail this module's 12 tests as follows:
-`row < hi` -> `row < hi - B` in the three epilogues: 3 (extent, window, random); the `SENT * tl` term dropped from
-c0: 8; `>` -> `>=` in the merge across wavefronts: 1 (ties); rd_n1 published one bin short by k2_estep: 4 (bins,
+`row < hi` -> `row < hi - B` in the epilogue (then written out in each kernel, now mstep_best_of_rows of mstep.inc):
+3 (extent, window, random); the `SENT * tl` term dropped from c0 (mstep_c0): 8; `>` -> `>=` in the merge across
+wavefronts (mstep_merge_waves): 1 (ties); rd_n1 published one bin short by k2_estep: 4 (bins,
 columns, rounds2, random).
 """
 import os
